@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- edge-Jacobians/s per Gauss-Newton iteration on a synthetic SE(2) pose graph.
 
-    python bench.py --gpus N --steps K --warmup W [--config C4] [--iters 20]
+    python bench.py --gpus N --steps K --warmup W [--config C4] [--iters 20] [--dump-outputs DIR] [--full]
 
 A *step* is one ``optimize(20)`` call of the hot path (what the reference runs per accepted loop
 closure: src/sparse_gslam/src/submap_loop_closer.cpp:286-287) from the same initial poses, i.e.
@@ -17,10 +17,17 @@ rows + partial dot products in small all-gather packets; g
 rows (random closures) keep every rank's copy whole and all-reduce the product vectors.  Total work is fixed =>
 "scaling": "strong".
 
-Beside `value` the line carries `roofline` (median-based, recomputable from profiles/: DESIGN.md section 4), `cpu_baseline`,
-`value_init_odom` (BASELINE.md's literal dead-reckoned start), `reference_usage_session` (the reference's flow at its own
-graph size: the single-launch direct path) and `incremental_session` (the reference's flow at the bench workload's size:
-sgo_update_graph_se2 per closure against a fresh sgo_set_graph_se2).
+A plain run sets up, warms up, times the K steps and prints the line: `value`, `ms_per_step` and what the last timed step
+returned (chi2, PCG iterations, per-iteration times).  --dump-outputs DIR also writes what that step's caller receives:
+DIR/poses.npy (the optimised poses), DIR/chi2.npy and DIR/robust_chi2.npy (every iterate), float64; the inputs are the
+seeded generator's, the same in every run with the same arguments.
+
+--full adds everything else the line has carried: `set_graph_ms` (median of 11 set-ups) and the set-up-inclusive figures,
+`final_chi2_rel_err_vs_oracle` (the committed CPU-oracle fixture), `roofline` (median-based, recomputable from profiles/:
+DESIGN.md section 4), `cpu_baseline`, `value_init_odom` (BASELINE.md's literal dead-reckoned start), `reference_usage_session`
+(the reference's flow at its own graph size: the single-launch direct path) and `incremental_session` (the reference's flow
+at the bench workload's size: sgo_update_graph_se2 per closure against a fresh sgo_set_graph_se2).  --no-roofline and
+--no-cpu-baseline leave parts of it out.
 """
 from __future__ import annotations
 
@@ -328,6 +335,15 @@ def incremental_session(device: int, V: int, E: int, seed: int, steps: int = 12,
             "max_rel_chi2_diff_vs_fresh_setup": worst, "bound": 1e-6, "updates": descs}
 
 
+def dump_outputs(path: str, poses, st):
+    """What a caller of the timed path receives from the last timed step, as float64 .npy files: the optimised poses
+    (sgo_get_poses, V x 3) and the chi2 / robust chi2 of every iterate of that optimize() call.  At most 24 MB (C5's 1M
+    poses)."""
+    os.makedirs(path, exist_ok=True)
+    for name, a in (("poses", poses), ("chi2", st["chi2"]), ("robust_chi2", st["robust_chi2"])):
+        np.save(os.path.join(path, name + ".npy"), np.asarray(a, dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -337,8 +353,13 @@ def main():
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--solver", default=None, help="pcg | amg (default: library default)")
     ap.add_argument("--tol", type=float, default=None)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need: set-up time, the oracle fixture's chi2, the "
+                         "dead-reckoned start, the roofline leg, the CPU baseline and the usage sessions")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (poses, chi2, robust chi2) as DIR/<name>.npy, float64")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline and usage sessions")
+    ap.add_argument("--no-roofline", action="store_true", help="--full without the roofline leg, dead-reckoned start and incremental session")
     ap.add_argument("--transport", choices=("rccl", "host"), default="rccl",
                     help="N > 1 only.  rccl: one rank per GPU, libsgo's own RCCL communicator (the measured configuration).  host: the "
                          "same launcher, rendezvous, sharding, MAX-reduce and JSON with libsgo's caller-supplied transport "
@@ -428,11 +449,13 @@ def main():
     if world > 1:
         sharding = opt.solver_description().split("; multi-GPU ", 1)[-1]
     sg_ms = []                     # steady state of repeated calls (the reference re-initialises before every optimize(20)):
-    for _ in range(11):            # median of 11 -- host threads decide single samples
-        t_sg = time.perf_counter()
-        opt.set_graph(*g.arrays())
-        sg_ms.append(1e3 * (time.perf_counter() - t_sg))
-    set_graph_steady_ms = float(np.median(sg_ms))
+    if args.full:
+        for _ in range(11):        # median of 11 -- host threads decide single samples
+            t_sg = time.perf_counter()
+            opt.set_graph(*g.arrays())
+            sg_ms.append(1e3 * (time.perf_counter() - t_sg))
+        set_graph_steady_ms = float(np.median(sg_ms))
+        note(f"set_graph steady state {set_graph_steady_ms:.1f} ms")
 
     def step():
         opt.set_poses(g.poses)
@@ -441,7 +464,7 @@ def main():
             raise SystemExit(f"optimize stopped after {done} iterations: {st}")
         return st
 
-    note(f"set_graph steady state {set_graph_steady_ms:.1f} ms; warm-up")
+    note("warm-up")
     for _ in range(args.warmup):
         step()
     barrier()
@@ -485,15 +508,8 @@ def main():
                                      "path, NOT a scaling measurement)" if host_transport else
                                      ("rccl" if world > 1 else "none (single GPU)"))},
             "final_chi2": st["chi2"][-1], "final_robust_chi2": st["robust_chi2"][-1],
-            "final_chi2_rel_err_vs_oracle": golden_rel_err(args.config, args.iters, st),
             "pcg_iters_per_gn_iter": float(np.mean(st["pcg_iters"])), "pcg_iters": st["pcg_iters"],
             "gn_iter_ms_median": 1e3 * float(np.median(st["seconds"])),
-            "set_graph_ms": set_graph_steady_ms,   # host structure build + upload + multigrid set-up (not in value); median of 11 calls
-            "set_graph_ms_min_max": [float(min(sg_ms)), float(max(sg_ms))],
-            # what one accepted loop closure costs in the reference's flow (slc.cpp:286-287: initializeOptimization +
-            # optimize(20)): the second headline next to `value`
-            "setup_plus_optimize_ms": set_graph_steady_ms + 1e3 * dt / args.steps,
-            "edge_jacobians_per_s_incl_setup": args.iters * g.E / (1e-3 * set_graph_steady_ms + dt / args.steps),
             "linearize_ms_median": 1e3 * float(np.median(st["seconds_linearize"])),
             # lagged refresh of the multigrid hierarchy's coarse operators (sgo_solve.cpp): how many solves of the last timed
             # optimize() call kept the operators of the solve before (every solve runs to pcg_tol on the current Hessian either way;
@@ -501,10 +517,20 @@ def main():
             "coarse_operator_refresh": (opt.solver_description().split("; last sgo_optimize_gn: ")[1].split(";")[0]
                                         if "; last sgo_optimize_gn: " in opt.solver_description() else "refreshed before every solve"),
         }
+        if args.full:
+            out["final_chi2_rel_err_vs_oracle"] = golden_rel_err(args.config, args.iters, st)
+            out["set_graph_ms"] = set_graph_steady_ms   # host structure build + upload + multigrid set-up (not in value); median of 11 calls
+            out["set_graph_ms_min_max"] = [float(min(sg_ms)), float(max(sg_ms))]
+            # what one accepted loop closure costs in the reference's flow (slc.cpp:286-287: initializeOptimization +
+            # optimize(20)): the second headline next to `value`
+            out["setup_plus_optimize_ms"] = set_graph_steady_ms + 1e3 * dt / args.steps
+            out["edge_jacobians_per_s_incl_setup"] = args.iters * g.E / (1e-3 * set_graph_steady_ms + dt / args.steps)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, opt.get_poses(), st)
     opt.close()
 
     note(f"timed region done: {1e3 * dt / args.steps:.1f} ms per step")
-    if rank == 0 and world == 1 and not args.no_roofline and args.config in synth.CONFIGS and g.V <= 200_000:
+    if args.full and rank == 0 and world == 1 and not args.no_roofline and args.config in synth.CONFIGS and g.V <= 200_000:
         # BASELINE.md's dead-reckoned start on the same graph: PCG iterations per GN iteration and where the robust
         # chi2 goes over optimize(20) -- the evidence behind init=incremental as the bench workload
         go = synth.config(args.config, init="odom")
@@ -548,7 +574,7 @@ def main():
                     "the_two_cpu_oracles_rel_diff_iterate_1": float(of["oracle_rel_diff"][1]),
                     "the_two_cpu_oracles_rel_diff_final": float(of["oracle_rel_diff"][-1]),
                     "the_two_cpu_oracles_rel_diff_max": float(np.max(of["oracle_rel_diff"]))}
-    if rank == 0 and world == 1 and not args.no_roofline:
+    if args.full and rank == 0 and world == 1 and not args.no_roofline:
         note("roofline leg")
         # roofline leg: the same workload again with every launch bracketed by HIP events on the
         # context's stream (profile=1 disables the hipGraph so that single launches can be timed)
@@ -663,14 +689,14 @@ def main():
                             "p90_us": round(v.get("p90_us", 0.0), 2),
                             "GB/s": round(v["bytes"] / (v["ms"] * 1e-3) / 1e9, 1)}
                         for n, v in prof.items() if v["ms"] > 0}}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         note("cpu baseline")
         out["cpu_baseline"] = cpu_baseline(g, args.iters, args.config)
         out["reference_usage_session"] = reference_usage_session(local_rank)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.config == "C3s":
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and args.config == "C3s":
         note("mid-size usage session")
         out["midsize_usage_session"] = midsize_usage_session(local_rank, args.config)
-    if rank == 0 and world == 1 and not args.no_roofline and args.config in ("C2", "C4"):
+    if args.full and rank == 0 and world == 1 and not args.no_roofline and args.config in ("C2", "C4"):
         note("incremental session")
         out["incremental_session"] = incremental_session(local_rank, g.V, g.E, g.meta["seed"], iters=args.iters)
     if rank == 0:

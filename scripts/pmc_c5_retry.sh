@@ -10,6 +10,6 @@ python3 $R/scripts/pmc_summary.py $O/pmc_FETCH_SIZE_c5 $O/pmc_WRITE_SIZE_c5 > $O
 find $O -name "*kernel_trace.csv" -delete; find $O -name "*counter_collection.csv" -delete
 cp $O/r05_pmc_traffic_amg_c5.json $R/profiles/
 cd $R
-python3 bench.py --config C5 --no-cpu-baseline 2> $O/r05_bench_c5.err | tail -1 > $O/r05_bench_c5.json
+python3 bench.py --full --config C5 --no-cpu-baseline 2> $O/r05_bench_c5.err | tail -1 > $O/r05_bench_c5.json
 python3 -c "
 import json; d=json.load(open('$O/r05_bench_c5.json')); r=d['roofline']; print(d['value'], r['kernel'], r['frac'], r['traffic'], r['traffic_over_algorithmic'] if 'traffic_over_algorithmic' in r else None, r['level0_product']['frac'], r['level0_product']['traffic_over_algorithmic'])"

@@ -36,13 +36,13 @@ find $O -name "*kernel_trace.csv" -delete; find $O -name "*counter_collection.cs
 cp $O/${tag}_pmc_traffic_amg_$lc.json $O/${tag}_trace_summary_${lc}_graph.json $O/${tag}_trace_summary_${lc}_plain.json $R/profiles/
 cd $R
 if [ "$cfg" = "C4" ]; then
-  python3 bench.py 2>/dev/null | tail -1 > $O/${tag}_bench_c4.json
-  python3 bench.py --steps 20 --warmup 5 2>/dev/null | tail -1 > $O/${tag}_bench_c4_steps20.json
-  python3 bench.py --config C2 2>/dev/null | tail -1 > $O/${tag}_bench_c2.json
-  python3 bench.py --config C3s 2>/dev/null | tail -1 > $O/${tag}_bench_c3s.json
+  python3 bench.py --full 2>/dev/null | tail -1 > $O/${tag}_bench_c4.json
+  python3 bench.py --full --steps 20 --warmup 5 2>/dev/null | tail -1 > $O/${tag}_bench_c4_steps20.json
+  python3 bench.py --full --config C2 2>/dev/null | tail -1 > $O/${tag}_bench_c2.json
+  python3 bench.py --full --config C3s 2>/dev/null | tail -1 > $O/${tag}_bench_c3s.json
   list="c4 c4_steps20 c2 c3s"
 else
-  python3 bench.py --config $cfg --no-cpu-baseline 2> $O/${tag}_bench_$lc.err | tail -1 > $O/${tag}_bench_$lc.json
+  python3 bench.py --full --config $cfg --no-cpu-baseline 2> $O/${tag}_bench_$lc.err | tail -1 > $O/${tag}_bench_$lc.json
   list="$lc"
 fi
 for c in $list; do python3 - $O/${tag}_bench_$c.json <<'PY'

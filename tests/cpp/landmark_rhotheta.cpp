@@ -4,7 +4,7 @@
 // The vertex / edge classes restate include/g2o_bindings/{vertex_rhotheta,edge_se2_rhotheta}.h and
 // src/sparse_gslam/src/g2o_bindings/{vertex_rhotheta.cpp:28-34, edge_se2_rhotheta.cpp:9-16} in this test's own
 // words (the reference's files themselves are compiled against the compat headers by ref_headers_check.cpp,
-// where the checkout is present): a 2-dof (rho, theta) vertex with an additive oplus whose theta is NOT wrapped
+// in scripts/make_golden_ref_rhotheta.py): a 2-dof (rho, theta) vertex with an additive oplus whose theta is NOT wrapped
 // (upstream discards normalize_theta's result), and a computeError-only edge
 //     e = z - transform_line(line, pose^-1),  e[1] wrapped,
 // with transform_line / checkRhoTheta restated from src/ls_extractor/include/ls_extractor/utils.h:22-45.
@@ -13,8 +13,9 @@
 //
 // With -DSGO_REF_SOURCES the restated classes are left out and the program uses the REFERENCE's own g2o::VertexRhoTheta /
 // g2o::EdgeSE2RhoTheta: declarations from include/g2o_bindings/*.h, definitions from src/g2o_bindings/{vertex_rhotheta,
-// edge_se2_rhotheta}.cpp compiled verbatim from the read-only checkout and linked in (tests/test_landmark_lm.py, CPU box
-// only) -- the same schedule then runs through the reference's computeError / oplusImpl and ls_extractor/utils.h.
+// edge_se2_rhotheta}.cpp compiled verbatim from a reference checkout and linked in (scripts/make_golden_ref_rhotheta.py, which
+// records the output in tests/golden/ref_rhotheta.npz) -- the same schedule then runs through the reference's computeError /
+// oplusImpl and ls_extractor/utils.h.
 //
 // usage: landmark_rhotheta <graph.txt>; prints, per stage, "STAGE iterations chi2" and one
 // "IT lambda chi2 trials" line per iteration, then "V id est...".

@@ -1,6 +1,6 @@
 // ref_headers_check.cpp -- compiles the REFERENCE's own custom-type declarations
-// (src/sparse_gslam/include/g2o_bindings/{vertex_rhotheta,edge_se2_rhotheta}.h, included from the
-// read-only reference checkout, never copied) against the g2o compat headers of this repo.  The
+// (src/sparse_gslam/include/g2o_bindings/{vertex_rhotheta,edge_se2_rhotheta}.h, included from a
+// reference checkout by scripts/make_golden_ref_rhotheta.py, never copied) against the g2o compat headers of this repo.  The
 // member definitions below are this test's own (the reference's .cpp files additionally need
 // ls_extractor, Boost and real Eigen); what is checked is that the subclass ABI the reference
 // declares -- BaseVertex<2, Eigen::Vector2d>, BaseBinaryEdge<2, Eigen::Vector2d, VertexSE2,

@@ -297,7 +297,7 @@ def test_bench_gpus_2_runs_end_to_end_over_the_host_transport():
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1",
-           "--config", "C2", "--transport", "host", "--no-cpu-baseline", "--no-roofline"]
+           "--config", "C2", "--transport", "host", "--full", "--no-cpu-baseline", "--no-roofline"]
     r = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
