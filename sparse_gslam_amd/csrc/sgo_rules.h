@@ -1,11 +1,14 @@
 // sgo_rules.h -- the decisions sgo_optimize_gn takes about its multigrid hierarchy, as PURE functions of iteration counts and of
 // sums every rank holds bit-identically: no clocks, no device state, no environment.  Every rank of a multi-GPU run must take the
 // same decision from the same numbers, so the rules live here, apart from the driver that feeds them (optimize_gn, sgo_solve.cpp),
-// and are unit-tested on recorded count sequences without a GPU (tests/cpp/rules_unit.cpp, tests/test_rules.py).
+// and are unit-tested on recorded count sequences without a GPU (tests/cpp/rules_unit.cpp, tests/test_rules.py).  The floor rule at
+// the end (single GPU: whether a solve that stopped short of pcg_tol is accepted) is tested against numpy the same way
+// (tests/cpp/floor_shim.cpp, tests/test_floor_rule.py).
 // DESIGN.md section 5 says what each rule is for and where its constants were measured.
 #pragma once
 #include <algorithm>
 #include <cmath>
+#include <cstddef>
 
 namespace sgo {
 namespace rules {
@@ -72,6 +75,33 @@ inline bool reaggregate(bool far, bool rule_off, int iterations_left_incl, int a
 // The trial's verdict: the re-made hierarchy's better count of its first two solves against the old one's first solve of the call;
 // true = the old hierarchy comes back.
 inline bool trial_reverts(int trial_best, int trial_old) { return 100 * trial_best > 85 * trial_old; }
+
+// The floor rule: a solve that stops without reaching pcg_tol (stagnation guard, pcg_maxit) is accepted -- its step applied, as a
+// backward-stable direct solver's would be -- when the backward error of its x is at most kFloorEta, measured on the Jacobi-scaled
+// system (S H S) y = S b, y = S^-1 x, S = diag(H)^-1/2:
+//     eta = |S r| / (|S H S| |S^-1 x| + |S b|),   r = b - H x (the TRUE residual, not the recurrence's).
+// The scaled measure does not change when one row is made stiffer (a prior, a closure from a sharp score peak): a normwise one with
+// |H| ~ max_i |D_i| lets a cut-off solve through as soon as one diagonal block is large.  S H S has a unit diagonal (>= 1 with the
+// incremental overlay's positive semi-definite U M U^T added to H), so |S H S|_2 >= 1: taking it as 1 UNDER-estimates the norm and
+// eta errs on the strict side.  S_kk comes from the diagonal entries of each row's diagonal block, dblk6[6 i + {0, 3, 5}] (the
+// symmetric packing [00 01 02 11 12 22] of S0.dblk).  A diagonal entry that is not finite or not positive, or a result that is not
+// finite, gives eta = 1: not accepted.  r, x, b: 3 n doubles in the rows' order.
+constexpr double kFloorEta = 1e-12;   // ~ 4 500 units of roundoff
+inline double floor_backward_error(int n, const double* r, const double* x, const double* b, const double* dblk6) {
+  double sr = 0.0, sx = 0.0, sb = 0.0;
+  for (int i = 0; i < n; ++i)
+    for (int q = 0; q < 3; ++q) {
+      const double h = dblk6[6 * (std::size_t)i + (q == 0 ? 0 : q == 1 ? 3 : 5)];
+      if (!(h > 0.0) || !std::isfinite(h)) return 1.0;
+      const std::size_t k = 3 * (std::size_t)i + q;
+      sr += r[k] * r[k] / h;
+      sx += x[k] * x[k] * h;
+      sb += b[k] * b[k] / h;
+    }
+  const double den = std::sqrt(sx) + std::sqrt(sb);
+  const double eta = std::sqrt(sr) / den;
+  return (den > 0.0 && std::isfinite(eta)) ? eta : 1.0;
+}
 
 }  // namespace rules
 }  // namespace sgo

@@ -926,32 +926,44 @@ int check_graph(sgo_ctx* c) {
   return SGO_OK;
 }
 
-// The normwise backward error of the solve's current x, eta = |r| / (|H| |x| + |b|) with |H| taken as 2 max_i |D_i|_F (an
-// UNDER-estimate for rows of high degree: eta errs on the large side).  A solve that stops making progress with eta at a few
-// thousand units of roundoff has the solution double precision can give for this system -- a backward-stable direct solver
-// (LinearSolverEigen's LDL^T, graphs.cpp:19) returns one of the same quality and g2o applies it --, whatever |r| / |b| says: seen
-// from BASELINE.md's dead-reckoned start on large graphs with full information matrices, where undamped Gauss-Newton + DCS blows up
-// (steps of 10^9 m, |x| / |b| ~ 20, |H| ~ 4 10^9: relative residuals of 10^-5 .. 10^-6 at eta = 10^-16 .. 3 10^-14; restarting the
-// recurrence from b - H x changes nothing there: NOTES.md section 29).  Rare path: x and the diagonal blocks are read on the host.
+// The floor rule's backward error of the solve's current x (rules::floor_backward_error, sgo_rules.h: Jacobi-scaled, so one stiff
+// row does not let a cut-off solve through).  A solve that stops making progress with eta at a few thousand units of roundoff has the
+// solution double precision can give for this system -- a backward-stable direct solver (LinearSolverEigen's LDL^T, graphs.cpp:19)
+// returns one of the same quality and g2o applies it --, whatever |r| / |b| says: seen from BASELINE.md's dead-reckoned start on large
+// graphs with full information matrices, where undamped Gauss-Newton + DCS blows up (relative residuals of 10^-5 .. 10^-6 with x at
+// the floor: NOTES.md section 29).  The residual is the TRUE one, r = b - H x with the PCG's own operator (do_spmv: the incremental
+// overlay's U M U^T included), not the recurrence's.  Rare path -- only a solve that stopped short of pcg_tol comes here: one level-0
+// product into q (free between solves: every PCG iteration recomputes it) and r, x, b and the diagonal blocks read on the host.
 static int solve_backward_error(sgo_ctx* c, double* eta) {
-  std::vector<double> hx(3 * (size_t)c->n), hd(6 * (size_t)c->n);
-  HIP_TRY(c, hipMemcpyAsync(hx.data(), c->d_x, sizeof(double) * hx.size(), hipMemcpyDeviceToHost, c->stream));
+  int rc = do_spmv(c, c->d_x, c->d_q, false, nullptr, nullptr);
+  if (rc) return rc;
+  const size_t n3 = 3 * (size_t)c->n;
+  std::vector<double> hx(n3), hr(n3), hb(n3), hd(6 * (size_t)c->n);
+  HIP_TRY(c, hipMemcpyAsync(hx.data(), c->d_x, sizeof(double) * n3, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(hr.data(), c->d_q, sizeof(double) * n3, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(hb.data(), c->d_b, sizeof(double) * n3, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipMemcpyAsync(hd.data(), c->S0.dblk, sizeof(double) * hd.size(), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  double xx = 0.0, dmax = 0.0;
-  for (double v : hx) xx += v * v;
-  for (int i = 0; i < c->n; ++i) {
-    const double* d = hd.data() + 6 * (size_t)i;
-    dmax = std::max(dmax, std::sqrt(d[0] * d[0] + 2 * d[1] * d[1] + 2 * d[2] * d[2] + d[3] * d[3] + 2 * d[4] * d[4] + d[5] * d[5]));
+  for (size_t k = 0; k < n3; ++k) hr[k] = hb[k] - hr[k];
+  *eta = rules::floor_backward_error(c->n, hr.data(), hx.data(), hb.data(), hd.data());
+  if (c->opts.verbose) {
+    // (with round 6's normwise measure beside it, |r_rec| / (2 max_i |D_i|_F |x| + |b|), for comparison)
+    double xx = 0.0, rr = 0.0, dmax = 0.0;
+    for (size_t k = 0; k < n3; ++k) {
+      xx += hx[k] * hx[k];
+      rr += hr[k] * hr[k];
+    }
+    for (int i = 0; i < c->n; ++i) {
+      const double* d = hd.data() + 6 * (size_t)i;
+      dmax = std::max(dmax, std::sqrt(d[0] * d[0] + 2 * d[1] * d[1] + 2 * d[2] * d[2] + d[3] * d[3] + 2 * d[4] * d[4] + d[5] * d[5]));
+    }
+    const double old_eta = std::sqrt(c->h_S->rr) / (2.0 * dmax * std::sqrt(xx) + std::sqrt(c->h_S->bb));
+    std::fprintf(stderr, "[sgo] solve stopped without reaching pcg_tol: |r_rec| %.3e |b - Hx| %.3e |b| %.3e |x| %.3e max|D| %.3e: "
+                 "scaled backward error %.2e (normwise, recurrence residual: %.2e)\n", std::sqrt(c->h_S->rr), std::sqrt(rr),
+                 std::sqrt(c->h_S->bb), std::sqrt(xx), dmax, *eta, old_eta);
   }
-  const double den = 2.0 * dmax * std::sqrt(xx) + std::sqrt(c->h_S->bb);
-  *eta = (den > 0.0 && std::isfinite(den) && std::isfinite(c->h_S->rr)) ? std::sqrt(c->h_S->rr) / den : 1.0;
-  if (c->opts.verbose)
-    std::fprintf(stderr, "[sgo] solve stopped without reaching pcg_tol: |r| %.3e |b| %.3e |x| %.3e max|D| %.3e: normwise backward error %.2e\n", std::sqrt(c->h_S->rr),
-                 std::sqrt(c->h_S->bb), std::sqrt(xx), dmax, *eta);
   return SGO_OK;
 }
-constexpr double kFloorEta = 1e-12;   // ~ 4 500 units of roundoff
 
 int optimize_gn(sgo_ctx* c, int32_t iters, sgo_stats* out) {
     int rc = check_graph(c);
@@ -1169,12 +1181,12 @@ int optimize_gn(sgo_ctx* c, int32_t iters, sgo_stats* out) {
         double eta = 1.0;
         const int r2 = solve_backward_error(c, &eta);
         if (r2) return r2;
-        floor_accept = eta <= kFloorEta;
+        floor_accept = eta <= rules::kFloorEta;
         if (floor_accept) {
           ++floor_solves;
           c->floor_seen = true;
           if (c->opts.verbose)
-            std::fprintf(stderr, "[sgo] iteration %d: the solve's x is at the floating-point floor of its system (backward error %.1e <= %.0e): step applied\n", it, eta, kFloorEta);
+            std::fprintf(stderr, "[sgo] iteration %d: the solve's x is at the floating-point floor of its system (scaled backward error %.1e <= %.0e): step applied\n", it, eta, rules::kFloorEta);
         }
         return SGO_OK;
       };
@@ -1377,7 +1389,7 @@ int optimize_gn(sgo_ctx* c, int32_t iters, sgo_stats* out) {
     if (!agg_note.empty()) c->lag_note += (c->lag_note.empty() ? "" : "; ") + agg_note;
     if (floor_solves > 0)
       c->lag_note += std::string(c->lag_note.empty() ? "last sgo_optimize_gn: " : "; ") + std::to_string(floor_solves) +
-                     " solve(s) stopped at the floating-point floor of their system (normwise backward error <= 1e-12 without reaching pcg_tol): "
+                     " solve(s) stopped at the floating-point floor of their system (Jacobi-scaled backward error <= 1e-12 without reaching pcg_tol): "
                      "steps applied, as a backward-stable direct solver's would be";
     if ((rc = do_chi2(c, c->d_hist + 2 * done, nullptr))) {
       return rc;

@@ -95,7 +95,7 @@ def test_device_aggregation_hierarchy_solves_to_the_goldens(name, monkeypatch):
     dh, sh, _, desch = _run(g, 20, {"SGO_AMG_FORCE_REBUILD": "1", "SGO_AMG_SETUP": "host"}, monkeypatch)
     dd, sd, _, descd = _run(g, 20, {"SGO_AMG_FORCE_REBUILD": "1", "SGO_AMG_SETUP": "device", "SGO_AMG_AGG": "device"}, monkeypatch)
     monkeypatch.delenv("SGO_AMG_AGG", raising=False)
-    assert dh == 20 and dd == 20 and all(sd["pcg_converged"][:20])
+    assert dh == 20 and dd == 20 and set(sd["pcg_converged"][:20]) == {1}
     rel = max(abs(sd["chi2"][k] - f["chi2"][k]) / f["chi2"][k] for k in range(21))
     assert rel <= 1e-6, rel
     print(name, "host", desch.split("; direct")[0], sh["pcg_iters"])
@@ -116,7 +116,7 @@ def test_device_rebuilds_from_the_dead_reckoned_start(monkeypatch):
             res[mode] = (done, st, opt.solver_description())
     monkeypatch.delenv("SGO_AMG_SETUP")
     for mode, (done, st, desc) in res.items():
-        assert done == 20 and all(st["pcg_converged"][:20]), (mode, st["pcg_iters"])
+        assert done == 20 and set(st["pcg_converged"][:20]) == {1}, (mode, st["pcg_iters"])
         print(mode, "call ms", 1e3 * st["seconds_total"], "pcg", st["pcg_iters"])
     assert res["rebuilds"][1]["pcg_iters"][:20] == res["host"][1]["pcg_iters"][:20]
     assert list(res["rebuilds"][1]["chi2"][:21]) == list(res["host"][1]["chi2"][:21])

@@ -32,7 +32,7 @@ def test_kept_coarse_operators_leave_the_iterates_where_the_golden_has_them(name
     assert "kept the coarse operators" not in desc0
     if name == "C4":   # (its last iterations move the blocks by 1e-3 and less; C2's twenty iterations never get below the cautious start
         assert "kept the coarse operators" in desc1, desc1   # of a graph whose sensitivity has not been learned yet)
-    assert all(s1["pcg_converged"][:20])
+    assert set(s1["pcg_converged"][:20]) == {1}
     for k in range(21):
         assert abs(s1["chi2"][k] - f["chi2"][k]) <= 1e-6 * f["chi2"][k], k
         assert abs(s1["chi2"][k] - s0["chi2"][k]) <= 1e-6 * s0["chi2"][k], k
@@ -64,7 +64,7 @@ def test_the_first_solve_of_a_call_always_refreshes():
         done, st = opt.optimize(3)
         desc = opt.solver_description()
     assert done == 3
-    assert all(st["pcg_converged"][:3])
+    assert set(st["pcg_converged"][:3]) == {1}
     if "kept the coarse operators" in desc:
         kept = int(desc.split("last sgo_optimize_gn: ")[1].split(" of ")[0])
         assert kept <= 2
@@ -85,7 +85,7 @@ def test_a_kept_solve_that_falls_behind_is_interrupted_refreshed_and_carried_on(
         opt.set_graph(*g.arrays())
         done, st = opt.optimize(20)
     err = capfd.readouterr().err
-    assert done == 20 and all(st["pcg_converged"][:20])
+    assert done == 20 and set(st["pcg_converged"][:20]) == {1}
     assert "solve behind kept coarse operators interrupted" in err, err[-3000:]
     for k in range(21):
         assert abs(st["chi2"][k] - f["chi2"][k]) <= 1e-6 * f["chi2"][k], k
@@ -115,7 +115,7 @@ def test_a_hierarchy_aggregated_at_poor_poses_is_redone_once_when_the_next_call_
             fixed[0] = True
             inc.update_graph(P0, fixed, *arrs, E_res)
             done, st = inc.optimize(20)
-            assert done == 20 and all(st["pcg_converged"][:20])
+            assert done == 20 and set(st["pcg_converged"][:20]) == {1}
             notes.append("re-aggregated" in inc.solver_description())
             its.append(float(np.mean(st["pcg_iters"][:20])))
             P, E_res = inc.get_poses(), arrs[0].size
@@ -144,7 +144,7 @@ def test_a_re_aggregated_hierarchy_that_is_no_better_is_dropped_for_the_old_one(
             chi, descs, its = [], [], []
             for _ in range(3):
                 done, st = opt.optimize(20)
-                assert done == 20 and all(st["pcg_converged"][:20])
+                assert done == 20 and set(st["pcg_converged"][:20]) == {1}
                 chi += list(st["chi2"][:21])
                 its.append(float(np.mean(st["pcg_iters"][:20])))
                 descs.append(opt.solver_description())
@@ -176,7 +176,7 @@ def test_a_trial_whose_set_up_fails_puts_the_old_hierarchy_back(monkeypatch):
             chi, descs, its = [], [], []
             for _ in range(3):
                 done, st = opt.optimize(20)
-                assert done == 20 and all(st["pcg_converged"][:20]), (done, opt.last_error())
+                assert done == 20 and set(st["pcg_converged"][:20]) == {1}, (done, opt.last_error())
                 chi += list(st["chi2"][:21])
                 its.append(float(np.mean(st["pcg_iters"][:20])))
                 descs.append(opt.solver_description())

@@ -50,7 +50,7 @@ def test_c4_random_closures_full_size_matches_pcg_oracle():
         opt.set_graph(*g.arrays())
         done, st = opt.optimize(20)
         P = opt.get_poses()
-    assert all(st["pcg_converged"])
+    assert set(st["pcg_converged"]) == {1}
     _check_against(f, g, st, P, done)
 
 
@@ -63,7 +63,7 @@ def test_c5_generator_reduced_size_matches_pcg_oracle():
         opt.set_graph(*g.arrays())
         done, st = opt.optimize(20)
         P = opt.get_poses()
-    assert all(st["pcg_converged"])
+    assert set(st["pcg_converged"]) == {1}
     _check_against(f, g, st, P, done)
 
 
@@ -87,7 +87,7 @@ def test_full_size_optimality_and_true_residual(name):
         done, st = opt.optimize(20)
         rr1, g1, it1, _ = _true_relres(opt)
         P = opt.get_poses()
-    assert done == 20 and all(st["pcg_converged"]), st["pcg_iters"]
+    assert done == 20 and set(st["pcg_converged"]) == {1}, st["pcg_iters"]
     assert np.isfinite(P).all()
     assert rr0 <= 1e-7 and rr1 <= 1e-7, (rr0, rr1)
     assert st["robust_chi2"][-1] < st["robust_chi2"][0]

@@ -198,7 +198,7 @@ def test_tolerance_rules_at_their_boundaries():
         with capi.Optimizer(0, direct_rows=0, **kw) as o:
             o.set_graph(*g.arrays())
             done, st = o.optimize(iters)
-            assert done == iters and all(st["pcg_converged"])
+            assert done == iters and set(st["pcg_converged"]) == {1}
             return np.array(st["pcg_relres"])
     V = 2000
     chain = synth.manhattan(V, int(1.45 * V), seed=31, info_mode="full")     # 2E + n < 4n
@@ -229,7 +229,7 @@ def test_stale_aggregation_is_rebuilt_and_the_result_still_matches(capfd):
     err = capfd.readouterr().err
     assert "multigrid hierarchy rebuilt before iteration" in err or "hierarchy rebuilt" in err, err[-2000:]
     oP, ost = _oracle().gauss_newton(*g.arrays(), iters=20)
-    assert done == 20 == ost["iters_done"] and all(st["pcg_converged"])
+    assert done == 20 == ost["iters_done"] and set(st["pcg_converged"]) == {1}
     rel = np.abs(np.array(st["chi2"]) - np.array(ost["chi2"])) / np.array(ost["chi2"])
     assert rel.max() <= 1e-6, rel.max()
     assert max(st["pcg_iters"]) < 400        # no solve ground on with a stale hierarchy
