@@ -371,10 +371,9 @@ int sgo_update_graph_se2(sgo_ctx* c, int32_t V, const double* poses, const uint8
         c->V = V;
         c->E = E;
         c->linearized = false;
-        c->warm_valid = false;
-        // the hierarchy's own staleness rule compares a solve with the best count seen so far (sgo_solve.cpp): the solves after
+        // the hierarchy's own staleness rule compares a solve with the best count seen so far (sgo_policy.h): the solves after
         // an update have another right-hand side (the appended poses' residual) -- their first one sets a new reference
-        c->amg_best = 0;
+        c->hier.new_rhs();
         c->setup_seconds = wall_s() - t0;
         c->update_note = "incremental (" + std::to_string(dE) + " edges appended in " + std::to_string(1e3 * c->setup_seconds).substr(0, 5) + " ms)";
         if (c->opts.verbose)

@@ -19,6 +19,7 @@
 #include "sgo_mfront.h"
 #include "sgo_internal.h"
 #include "sgo_overlay.h"
+#include "sgo_policy.h"
 
 using namespace sgo;   // (internal header: the global sgo_ctx of the C-ABI is made of sgo:: types)
 
@@ -69,41 +70,22 @@ struct sgo_ctx {
   bool halo_failed = false;
   std::vector<double> order_xy;     // [V][2] positions the row order follows when they are not the initial poses (a graph whose
                                     // poses contradict its closures: plan_order_positions, sgo_plan.cpp); empty otherwise
+  HierarchyState hier;              // what the resident graph's hierarchy has taught so far (sgo_policy.h)
   // Lagged refresh of the hierarchy's coarse operators (optimize_gn): d_dref = the level-0 diagonal blocks the coarse operators were
-  // last made from, h_dchg = k_diag_change's three sums (host-mapped), amg_lag_tau = relative movement up to which a solve keeps them
-  bool amg_skip_update = false;     // this solve keeps the coarse operators of the previous one
-  bool amg_lag_on = false;          // inside sgo_optimize_gn, after the call's first refresh
-  bool amg_force_keep = false;      // calibration hook (SGO_AMG_LAG_FORCE, scripts/lag_calib.py)
-  bool amg_lag_expect = false;      // the previous iteration's movement says this one may keep: do_linearize waits for the sums
+  // last made from, h_dchg = k_diag_change's three sums (host-mapped)
   bool amg_dchg_pending = false;    // k_diag_change's sums of this iteration have not been read yet
-  bool amg_ref_valid = false;       // d_dref holds the blocks of the resident coarse operators
-  double amg_lag_tau = 0.0;
-  // what a unit of movement costs this graph's solves in PCG iterations, learned from the kept solves (C4: ~1000, a 50k / 250k
-  // graph: ~4000-8000); a solve keeps while slope x movement <= 4 iterations (a refresh is worth 5-10).  Carried over a set-up when
-  // the graph has about the size of the one before (the reference re-initialises a slowly growing graph before every optimize).
-  double amg_lag_slope = 2700.0;
-  bool amg_lag_slope_seen = false;
-  int amg_lag_n = 0;
   int probe_dev_k = -1;             // what the device's PcgScalars hold (k_set_probe is launched only on a change)
   double probe_dev_max = -1.0;
-  int amg_probe_k = 0;              // progress probe of the kept solves (PcgScalars::probe_k / probe_max), from the last fresh solve
-  double amg_probe_max = 0.0;
-  int amg_lag_cap = 0;              // iteration cap of a solve behind kept operators (then: refresh and solve again)
-  double amg_lag_rows = 1.0;        // ... and the share of rows that may have moved by more than a quarter
   double* d_dref = nullptr;
   // ... and the blocks the hierarchy's AGGREGATION was made from (build_amg): a call whose first solve finds them far from the
   // current ones and needs visibly more iterations than the hierarchy's best redoes the set-up once (optimize_gn)
   double* d_dref_agg = nullptr;
-  bool agg_ref_valid = false;
-  int agg_best = 0;                 // the fewest PCG iterations a fresh solve behind this aggregation has taken
   int agg_grid = 0;                 // k_diag_change's workgroups of that measurement (sums in the second half of h_dchg), 0: none pending
   double* h_dchg = nullptr;         // pinned [2][3][kMaxPartials]: k_diag_change's per-workgroup sums (against d_dref, against d_dref_agg)
   int dchg_grid = 0;                // ... of the launch whose sums are pending
   double* h_dchg_dev = nullptr;     // its device address
   double last_dchg[3] = {0, 0, 0};
-  std::string lag_note;             // sgo_solver_description: how many solves of the last call kept their coarse operators
-  bool amg_no_filter = false;       // this graph's hierarchy rebuilds keep the tentative transfer where the smoothed one is refused
-                                    // (a filtered hierarchy's solve was abandoned: optimize_gn); cleared by the next set-up
+  std::string lag_note;             // sgo_solver_description: what the last call's policy did (CallPolicy::note)
   int* d_comm_flag = nullptr;       // one int for the collective decision about the captured PCG graph (run_pcg)
   bool comm_graph_failed = false;   // capturing the RCCL collectives into the PCG hipGraph failed once: plain launches since
   long long level0_bytes = 0;    // device bytes of the level-0 structure this rank holds (blocks, operands, per-slot / per-block indices)
@@ -128,7 +110,6 @@ struct sgo_ctx {
   DevArena amg_tmp_arena;         // temporaries of the device set-up (sgo_amg_dev.inc): rewound per level, kept between set-ups
   Amg* amg_prev = nullptr;
   std::string amg_prev_desc;
-  bool agg_rule_off = false;      // a trial was lost on this graph: the rule does not fire again before the next set-up
   // The environment knobs a solve depends on, read ONCE per entry-point call (read_call_knobs: sgo_optimize_gn, sgo_solve) and
   // never inside a solve (include/sgo.h's table says so).
   struct CallKnobs {
@@ -151,9 +132,19 @@ struct sgo_ctx {
     int rebuild_cost = 150;          // SGO_AMG_REBUILD_COST (sweep knob): what the count rules take a set-up to be worth, in PCG iterations
     bool force_rebuild = false;      // SGO_AMG_FORCE_REBUILD (test hook): the hierarchy is re-made before the call's first solve
   } knobs;
-  bool test_fail_trial_build = false;
-  bool in_optimize = false;       // inside sgo_optimize_gn (build_amg: which set-up a rebuild takes)
-  bool floor_seen = false;        // a solve of the current call was accepted at the floating-point floor (run_pcg: a shorter stagnation window)
+  // What do_linearize, start_pcg, run_pcg and build_amg read of the running sgo_optimize_gn: set when it begins, these defaults after.
+  struct CallState {
+    bool in_optimize = false;     // inside sgo_optimize_gn (build_amg: which set-up a rebuild takes)
+    int pcg_softcap = 0;          // > 0: iteration cap of the next solve (bail-out, first solve, lag cap)
+    double bb_ref = 0.0;          // |b|^2 of the call's first solve (0: relative tolerance only)
+    bool warm_valid = false;      // d_xprev holds the previous Gauss-Newton step (PCG warm start)
+    bool floor_seen = false;      // a solve was accepted at the floating-point floor (run_pcg: a shorter stagnation window)
+    bool lag_on = false;          // the lagged refresh runs (do_linearize)
+    bool skip_update = false;     // this solve keeps the coarse operators of the previous one
+    bool lag_expect = false;      // the previous iteration's movement says this one may keep: do_linearize waits for the sums
+    bool force_keep = false;      // calibration hook (SGO_AMG_LAG_FORCE, scripts/lag_calib.py)
+    int lag_cap = 0;              // iteration cap of a solve behind kept operators (then: refresh and solve again)
+  } call;
   AmgKeptAgg kept_agg;            // (what such a rebuild keeps: host copies, taken from the hierarchy before it is destroyed)
   double* d_poses = nullptr;
   int* d_free_id = nullptr;
@@ -198,17 +189,11 @@ struct sgo_ctx {
   int pcg_stall_window = 0;
   double tol_scale = 1.0;         // < 1 on chain-like graphs (see sgo_set_graph_se2)
   double* d_xprev = nullptr;      // the previous Gauss-Newton step of the running sgo_optimize_gn (PCG warm start)
-  bool warm_valid = false;
-  double bb_ref = 0.0;            // |b|^2 of the first solve of the running sgo_optimize_gn (0: relative tolerance only)
   double tol_cap = 0.0;           // loosest relative tolerance the absolute criterion may reach (0: off; opts.pcg_tol_cap)
-  int pcg_softcap = 0;            // > 0: iteration cap of the next solve (sgo_optimize_gn: stale-hierarchy bail-out)
-  double amg_theta_scale = 1.0;   // strength thresholds of the next hierarchy build, as a factor (halved when a hierarchy's first solve stalls)
   // level 0's multigrid host analysis running ahead on a helper thread (build_structure starts it, build_amg joins it)
   AmgHostL0* l0_pre = nullptr;
   std::thread l0_thread;
   std::vector<double> l0_w;
-  int amg_best = 0;               // fewest PCG iterations seen with the current hierarchy (0: none yet);
-                                  // kept across optimize() calls so that a hierarchy adapted to other poses is noticed
   PcgScalars* h_S2 = nullptr;     // pinned [2]: pipelined read-back of the stop flag (plain launches)
   double* h_pose_stage = nullptr; // pinned staging of the pose uploads (sgo_set_poses / sgo_update_graph_se2): a pageable source makes
   size_t pose_stage_cap = 0;      // the runtime pin and unpin the caller's buffer per call -- 10-20 ms every few calls on fresh buffers

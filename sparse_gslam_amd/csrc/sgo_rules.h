@@ -1,7 +1,8 @@
 // sgo_rules.h -- the decisions sgo_optimize_gn takes about its multigrid hierarchy, as PURE functions of iteration counts and of
 // sums every rank holds bit-identically: no clocks, no device state, no environment.  Every rank of a multi-GPU run must take the
-// same decision from the same numbers, so the rules live here, apart from the driver that feeds them (optimize_gn, sgo_solve.cpp),
-// and are unit-tested on recorded count sequences without a GPU (tests/cpp/rules_unit.cpp, tests/test_rules.py).  The floor rule at
+// same decision from the same numbers, so the rules live here, apart from the driver that feeds them (CallPolicy, sgo_policy.h,
+// driven by optimize_gn, sgo_solve.cpp), and are unit-tested with that policy on recorded count sequences without a GPU
+// (tests/cpp/rules_unit.cpp, tests/test_rules.py).  The floor rule at
 // the end (single GPU: whether a solve that stopped short of pcg_tol is accepted) is tested against numpy the same way
 // (tests/cpp/floor_shim.cpp, tests/test_floor_rule.py).
 // DESIGN.md section 5 says what each rule is for and where its constants were measured.
@@ -43,6 +44,7 @@ inline Staleness staleness(int eq_iter, int call_best, int iterations_left, int 
 // Lagged refresh: the movement of the level-0 diagonal blocks (relative, summed over the rows) up to which a solve keeps the coarse
 // operators of the solve before -- what costs this graph's solves four PCG iterations by the learned slope, at most tau.
 inline double lag_allowed(double tau, double slope) { return std::min(tau, 4.0 / std::max(slope, 1.0)); }
+constexpr double kLagRowsMoved = 32.0;       // ... and the rows that may have moved by more than a quarter (k_diag_change's third sum)
 constexpr double kLagSlopeStart = 2700.0;    // 0.15 % of movement: the cautious start on a graph not seen before
 constexpr double kLagSlopeMax = 40000.0;     // no solve is locked out over more than 0.01 % of movement
 // ... the slope after a KEPT solve that took `excess` iterations more than the last fresh one over a movement of `moved`:

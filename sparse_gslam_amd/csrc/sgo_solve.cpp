@@ -115,21 +115,21 @@ static int start_pcg_owner(sgo_ctx* c, int grid) {
   const HaloDev& H = c->halo;
   const int G = H.G, nr = H.row1 - H.row0;
   const size_t o3 = 3 * (size_t)H.row0;
-  const int maxit = c->pcg_softcap > 0 ? std::min(c->pcg_softcap, c->opts.pcg_maxit) : c->opts.pcg_maxit;
+  const int maxit = c->call.pcg_softcap > 0 ? std::min(c->call.pcg_softcap, c->opts.pcg_maxit) : c->opts.pcg_maxit;
   const double tol = c->opts.pcg_tol * c->tol_scale;
   double* bb_parts = c->d_partials + kMaxPartials;   // k_finalize: [0] r.z (block-Jacobi), [1] b.b over the owned rows
   int rc;
-  if (c->amg && !c->amg_skip_update && (rc = amg_update(c->amg, c->stream, &c->err))) return rc;
+  if (c->amg && !c->call.skip_update && (rc = amg_update(c->amg, c->stream, &c->err))) return rc;
   if (c->amg && amg_comm_failed(c->amg)) return SGO_ECOMM;
   // the block-diagonal inverse of the neighbours' boundary rows (the halo-row recurrences of the iterations apply it)
   if (c->amg && !halo_exchange(H, c->stream, c->S0.dinv, 6, H.bnd, H.bmax, HaloScalars(), &c->err)) return SGO_ECOMM;
   if (!c->amg) {   // block-Jacobi: k_finalize left z = Dinv b, p = z and the partials of r.z
     if (!xch(c, c->d_p, scal(c->d_partials, grid, bb_parts, grid))) return SGO_ECOMM;
     Scope sc(c, K_INIT_SCALARS, 16.0 * G);
-    launch_init_scalars(c->stream, c->d_S, H.gparts, G, H.gparts + G, G, tol, maxit, c->bb_ref, c->tol_cap);
+    launch_init_scalars(c->stream, c->d_S, H.gparts, G, H.gparts + G, G, tol, maxit, c->call.bb_ref, c->tol_cap);
     return SGO_OK;
   }
-  if (c->warm_valid && c->d_xprev) {
+  if (c->call.warm_valid && c->d_xprev) {
     // warm start (see start_pcg): x_prev is the previous step, gathered to every rank before the pose update
     int gq = 0, gd = 0;
     // (the product's kernel stores both of its dot-product rows: k_finalize's b.b partials move out of its way first)
@@ -143,7 +143,7 @@ static int start_pcg_owner(sgo_ctx* c, int grid) {
     if (!xch(c, nullptr, scal(bb_keep, grid, c->d_partials, gq, c->d_partials + 2 * kMaxPartials, gd))) return SGO_ECOMM;
     {
       Scope sc(c, K_INIT_SCALARS, 16.0 * G);   // ||b||^2, tolerance, iteration count (r.z is replaced below)
-      launch_init_scalars(c->stream, c->d_S, H.gparts, G, H.gparts, G, tol, maxit, c->bb_ref, c->tol_cap);
+      launch_init_scalars(c->stream, c->d_S, H.gparts, G, H.gparts, G, tol, maxit, c->call.bb_ref, c->tol_cap);
     }
     {
       Scope sc(c, K_UPDATE_XR, 120.0 * nr);
@@ -167,7 +167,7 @@ static int start_pcg_owner(sgo_ctx* c, int grid) {
   if (!xch(c, c->d_p, scal(c->d_zparts, gz, bb_parts, grid))) return SGO_ECOMM;
   {
     Scope sc(c, K_INIT_SCALARS, 16.0 * G);
-    launch_init_scalars(c->stream, c->d_S, H.gparts, G, H.gparts + G, G, tol, maxit, c->bb_ref, c->tol_cap);
+    launch_init_scalars(c->stream, c->d_S, H.gparts, G, H.gparts + G, G, tol, maxit, c->call.bb_ref, c->tol_cap);
   }
   if (!xch(c, c->d_r, HaloScalars())) return SGO_ECOMM;   // the halo rows' copies of r start here
   return SGO_OK;
@@ -182,13 +182,16 @@ static RecDev rec_dev(const sgo_ctx* c) {
   return r;
 }
 
-static void read_diag_change(sgo_ctx* c) {   // (after a synchronisation behind the launch)
-  const volatile double* h = c->h_dchg;
+// k_diag_change's three sums over `grid` workgroups, from half `half` of h_dchg (after a synchronisation behind the launch)
+static void sum_diag_change(const sgo_ctx* c, int half, int grid, double v[3]) {
+  const volatile double* h = c->h_dchg + 3 * (size_t)half * kMaxPartials;
   for (int k = 0; k < 3; ++k) {
-    double v = 0.0;
-    for (int i = 0; i < c->dchg_grid; ++i) v += h[(size_t)k * kMaxPartials + i];
-    c->last_dchg[k] = v;
+    v[k] = 0.0;
+    for (int i = 0; i < grid; ++i) v[k] += h[(size_t)k * kMaxPartials + i];
   }
+}
+static void read_diag_change(sgo_ctx* c) {
+  sum_diag_change(c, 0, c->dchg_grid, c->last_dchg);
   c->amg_dchg_pending = false;
 }
 static void set_probe(sgo_ctx* c, int k, double max) {
@@ -200,12 +203,12 @@ static void set_probe(sgo_ctx* c, int k, double max) {
 
 int start_pcg(sgo_ctx* c, int grid) {
   if (c->owner) return start_pcg_owner(c, grid);
-  const int maxit = c->pcg_softcap > 0 ? std::min(c->pcg_softcap, c->opts.pcg_maxit) : c->opts.pcg_maxit;
+  const int maxit = c->call.pcg_softcap > 0 ? std::min(c->call.pcg_softcap, c->opts.pcg_maxit) : c->opts.pcg_maxit;
   const double tol = c->opts.pcg_tol * c->tol_scale;
   if (c->amg) {
-    int rc = c->amg_skip_update ? SGO_OK : amg_update(c->amg, c->stream, &c->err);
+    int rc = c->call.skip_update ? SGO_OK : amg_update(c->amg, c->stream, &c->err);
     if (rc) return rc;
-    const bool warm = c->warm_valid && c->d_xprev;
+    const bool warm = c->call.warm_valid && c->d_xprev;
     if (warm) {
       // Start from the previous Gauss-Newton step scaled by the energy-optimal factor: consecutive steps of a linearly
       // converging iteration are nearly parallel, ||b - gamma H x_prev|| is 0.2-0.45 ||b|| on C4 / C2 (scripts/
@@ -213,7 +216,7 @@ int start_pcg(sgo_ctx* c, int grid) {
       // solution; only the path to it is shorter.
       {
         Scope sc(c, K_INIT_SCALARS, 16.0 * grid);   // ||b||^2, tolerance, iteration count (r.z is replaced below)
-        launch_init_scalars(c->stream, c->d_S, c->d_partials, grid, c->d_partials + kMaxPartials, grid, tol, maxit, c->bb_ref, c->tol_cap);
+        launch_init_scalars(c->stream, c->d_S, c->d_partials, grid, c->d_partials + kMaxPartials, grid, tol, maxit, c->call.bb_ref, c->tol_cap);
       }
       int gq = 0, gd = 0;
       if ((rc = do_spmv(c, c->d_xprev, c->d_q, true, nullptr, &gq))) return rc;
@@ -237,21 +240,23 @@ int start_pcg(sgo_ctx* c, int grid) {
       launch_restart_scalars(c->stream, c->d_S, c->d_zparts, gz, maxit, 1);
     } else {
       Scope sc(c, K_INIT_SCALARS, 8.0 * (gz + grid));
-      launch_init_scalars(c->stream, c->d_S, c->d_zparts, gz, c->d_partials + kMaxPartials, grid, tol, maxit, c->bb_ref, c->tol_cap);
+      launch_init_scalars(c->stream, c->d_S, c->d_zparts, gz, c->d_partials + kMaxPartials, grid, tol, maxit, c->call.bb_ref, c->tol_cap);
     }
     // progress probe of the lagged refresh (PcgScalars): a fresh solve records, a solve behind kept operators is held to the record
-    set_probe(c, c->amg_lag_on ? c->amg_probe_k : 0, c->amg_skip_update ? c->amg_probe_max : 0.0);
+    set_probe(c, c->call.lag_on ? c->hier.probe_k : 0, c->call.skip_update ? c->hier.probe_max : 0.0);
   } else {
     Scope sc(c, K_INIT_SCALARS, 16.0 * grid);
-    launch_init_scalars(c->stream, c->d_S, c->d_partials, grid, c->d_partials + kMaxPartials, grid, tol, maxit, c->bb_ref, c->tol_cap);
+    launch_init_scalars(c->stream, c->d_S, c->d_partials, grid, c->d_partials + kMaxPartials, grid, tol, maxit, c->call.bb_ref, c->tol_cap);
     set_probe(c, 0, 0.0);   // (a probe left armed by an earlier solve behind a hierarchy this graph has since lost would raise stop = 4 here)
   }
   return SGO_OK;
 }
 
 // The movement of the level-0 diagonal blocks up to which a solve keeps its coarse operators: what costs this graph's solves four
-// PCG iterations by the slope learned from its kept solves (sgo_ctx.h), at most amg_lag_tau.
-static double lag_allowed(const sgo_ctx* c) { return rules::lag_allowed(c->amg_lag_tau, c->amg_lag_slope); }
+// PCG iterations by the slope learned from its kept solves (HierarchyState), at most SGO_AMG_LAG_TAU.
+static double lag_allowed(const sgo_ctx* c) { return rules::lag_allowed(c->knobs.lag_tau, c->hier.lag_slope); }
+// ... and how far they have moved against the coarse operators' reference (k_diag_change's sums; `none`: no sums)
+static double moved_rel(const sgo_ctx* c, double none) { return c->last_dchg[1] > 0.0 ? c->last_dchg[0] / c->last_dchg[1] : none; }
 
 // A solve behind KEPT coarse operators was stopped (its progress probe, or its iteration cap): the operators are refreshed and the
 // solve carries on from its current x and r -- z = M^-1 r with the new cycle, p = z, the recurrence restarts (what the kept
@@ -260,8 +265,8 @@ static int refresh_and_continue(sgo_ctx* c, int maxit) {
   int rc = amg_update(c->amg, c->stream, &c->err);
   if (rc) return rc;
   HIP_TRY(c, hipMemcpyAsync(c->d_dref, c->S0.dblk, sizeof(double) * 6 * (size_t)c->n, hipMemcpyDeviceToDevice, c->stream));
-  c->amg_ref_valid = true;
-  c->amg_skip_update = false;
+  c->hier.ref_valid = true;
+  c->call.skip_update = false;
   const int gz = amg_apply(c->amg, c->stream, c->d_r, c->d_z, c->d_r, c->d_zparts, nullptr, nullptr, 0);
   HIP_TRY(c, hipMemcpyAsync(c->d_p, c->d_z, sizeof(double) * 3 * (size_t)c->n, hipMemcpyDeviceToDevice, c->stream));
   {
@@ -293,36 +298,35 @@ int do_linearize(sgo_ctx* c) {
     launch_finalize(c->stream, c->S0, row0, row1, c->d_dgb, c->d_b, c->d_x, c->d_r, c->d_z, c->d_p,
                     c->amg ? amg_xs0(c->amg) : nullptr, c->amg ? amg_omega(c->amg) : 0.0, c->d_partials, &grid);
   }
-  if (c->amg && c->amg_lag_on && !c->owner && c->d_dref) {   // (an incremental overlay changes nothing here: the hierarchy is the resident rows')
+  if (c->amg && c->call.lag_on && !c->owner && c->d_dref) {   // (an incremental overlay changes nothing here: the hierarchy is the resident rows')
     // Lagged refresh: a solve keeps the coarse operators of the previous one while the level-0 diagonal blocks have moved little
     // (lag_allowed: relative, summed over the rows) since those operators were made.
-    c->amg_skip_update = false;
+    c->call.skip_update = false;
     c->amg_dchg_pending = false;
     // The host waits for the sums -- the one round trip of the scheme, with the launches of the refresh not yet queued behind it:
     // 40-50 us -- only when the movement of the PREVIOUS iteration says this one may keep (a converging call's steps shrink);
     // otherwise the solve refreshes, the sums are read behind the solve's own synchronisation, and the kernel that measures
     // stores the new reference on its way.
-    const bool wait = c->amg_ref_valid && ((c->amg_lag_expect && c->amg_probe_max > 0.0) || c->amg_force_keep);
+    const bool wait = c->hier.ref_valid && ((c->call.lag_expect && c->hier.probe_max > 0.0) || c->call.force_keep);
     c->dchg_grid = launch_diag_change(c->stream, 0, c->n, c->S0.dblk, c->d_dref, !wait, c->h_dchg_dev);
-    c->amg_dchg_pending = c->amg_ref_valid;
+    c->amg_dchg_pending = c->hier.ref_valid;
     if (wait) {
       HIP_TRY(c, hipStreamSynchronize(c->stream));
       read_diag_change(c);
-      const double rel = c->last_dchg[1] > 0.0 ? c->last_dchg[0] / c->last_dchg[1] : 1.0;
-      c->amg_skip_update = rel <= lag_allowed(c) && c->last_dchg[2] <= c->amg_lag_rows && c->amg_probe_max > 0.0;
-      if (c->amg_force_keep) {   // calibration (SGO_AMG_LAG_FORCE=N): every solve after iteration N keeps, whatever moved
-        c->amg_skip_update = true;
-        c->amg_lag_cap = 0;
-        c->amg_probe_max = 0.0;
+      c->call.skip_update = moved_rel(c, 1.0) <= lag_allowed(c) && c->last_dchg[2] <= rules::kLagRowsMoved && c->hier.probe_max > 0.0;
+      if (c->call.force_keep) {   // calibration (SGO_AMG_LAG_FORCE=N): every solve after iteration N keeps, whatever moved
+        c->call.skip_update = true;
+        c->call.lag_cap = 0;
+        c->hier.probe_max = 0.0;
       }
-      if (!c->amg_skip_update)
+      if (!c->call.skip_update)
         HIP_TRY(c, hipMemcpyAsync(c->d_dref, c->S0.dblk, sizeof(double) * 6 * (size_t)c->n, hipMemcpyDeviceToDevice, c->stream));
     }
-    if (c->amg_skip_update && c->amg_lag_cap > 0) c->pcg_softcap = c->pcg_softcap > 0 ? std::min(c->pcg_softcap, c->amg_lag_cap) : c->amg_lag_cap;
-    if (!c->amg_skip_update) c->amg_ref_valid = true;
+    if (c->call.skip_update && c->call.lag_cap > 0) c->call.pcg_softcap = c->call.pcg_softcap > 0 ? std::min(c->call.pcg_softcap, c->call.lag_cap) : c->call.lag_cap;
+    if (!c->call.skip_update) c->hier.ref_valid = true;
   } else {
-    c->amg_skip_update = false;
-    c->amg_ref_valid = false;
+    c->call.skip_update = false;
+    c->hier.ref_valid = false;
   }
   int rc = start_pcg(c, grid);
   if (rc) return rc;
@@ -502,13 +506,6 @@ int ensure_pcg_graph(sgo_ctx* c, int chunk, bool* captured) {
   return SGO_OK;
 }
 
-// Runs PCG from the state k_finalize left (x = 0, r = b, ...) until S.stop != 0.
-// Runs PCG from the state k_finalize / start_pcg left (x = 0, r = b, ...) until S.stop != 0.
-// Graph mode: a 2-iteration hipGraph is replayed; the first 0.8 * predicted - 4 iterations -- predicted
-// = the count of the previous solve -- go out without any host check, after that one replay is always
-// in flight while the host waits for the stop flag copied out after the previous one (kernels of
-// iterations past convergence exit on the flag), so the GPU never idles on a host round trip and at
-// most two replays of early-exit launches are wasted.
 void read_call_knobs(sgo_ctx* c) {
   sgo_ctx::CallKnobs k;
   if (const char* e = std::getenv("SGO_COMM_GRAPH")) k.comm_graph = std::atoi(e) != 0 ? 1 : 0;
@@ -528,9 +525,14 @@ void read_call_knobs(sgo_ctx* c) {
   if (const char* e = std::getenv("SGO_AMG_LAG_SLOPE")) k.lag_slope = std::atof(e);
   if (const char* e = std::getenv("SGO_AMG_LAG_FORCE")) k.lag_force_from = std::atoi(e);
   c->knobs = k;
-  c->test_fail_trial_build = k.fail_trial_build;
 }
 
+// Runs PCG from the state k_finalize / start_pcg left (x = 0, r = b, ...) until S.stop != 0.
+// Graph mode: a 2-iteration hipGraph is replayed; the first 0.8 * predicted - 4 iterations -- predicted
+// = the count of the previous solve -- go out without any host check, after that one replay is always
+// in flight while the host waits for the stop flag copied out after the previous one (kernels of
+// iterations past convergence exit on the flag), so the GPU never idles on a host round trip and at
+// most two replays of early-exit launches are wasted.
 int run_pcg(sgo_ctx* c) {
   // Multi-GPU with an RCCL communicator: the collectives are captured into the hipGraph with the kernels around them (every
   // rank replays the same graph the same number of times: the replay count follows snapshots of the device-resident stop flag
@@ -552,7 +554,7 @@ int run_pcg(sgo_ctx* c) {
   c->pcg_stall_window = multi_rank(c) ? 0 : std::max(3000, 30 * std::max(1, c->pcg_pred));
   // (once a solve of this call has been accepted at the floating-point floor of its system -- optimize_gn, solve_backward_error --
   // the call is at the edge of double precision: its later solves wait a tenth as long before they are looked at)
-  if (c->floor_seen && c->pcg_stall_window > 0) c->pcg_stall_window = std::max(300, 3 * std::max(1, c->pcg_pred));
+  if (c->call.floor_seen && c->pcg_stall_window > 0) c->pcg_stall_window = std::max(300, 3 * std::max(1, c->pcg_pred));
   if (c->knobs.stall_window >= 0) c->pcg_stall_window = multi_rank(c) ? 0 : c->knobs.stall_window;   // (test hook; 0: no guard)
   double stall_rr = -1.0;
   int stall_it = 0;
@@ -670,7 +672,6 @@ int run_pcg(sgo_ctx* c) {
   return SGO_OK;
 }
 
-// (Re)build the multigrid hierarchy from the CURRENT level-0 values (requires do_linearize).
 std::string multi_gpu_description(const sgo_ctx* c) {
   if (c->owner)
     return "; multi-GPU row-owner mode: rank " + std::to_string(c->halo.me) + " of " + std::to_string(c->halo.G) + " owns rows [" +
@@ -680,18 +681,17 @@ std::string multi_gpu_description(const sgo_ctx* c) {
   return "";
 }
 
+// (Re)build the multigrid hierarchy from the CURRENT level-0 values (requires do_linearize).
 int build_amg(sgo_ctx* c, bool keep_old, bool keep_agg) {
   // speculative replays of the captured PCG iteration (and the launches queued behind them) may still be
   // in flight: drain the stream before the exec and the old hierarchy's buffers go away
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  c->amg_ref_valid = false;   // (the lagged refresh's reference blocks belong to the old hierarchy's coarse operators)
+  c->hier.new_hierarchy();   // (the lagged refresh's reference blocks belong to the old hierarchy's coarse operators)
   if (c->pcg_exec) {  // the captured PCG iteration references the old hierarchy's buffers
     hipGraphExecDestroy(c->pcg_exec);
     c->pcg_exec = nullptr;
   }
   c->pcg_pred = 0;  // the iteration count of the old hierarchy predicts nothing about the new one
-  c->amg_best = 0;
-  c->agg_best = 0;
   if (c->amg_prev) {   // (whatever an earlier trial kept is gone now)
     amg_destroy(c->amg_prev);
     c->amg_prev = nullptr;
@@ -710,13 +710,13 @@ int build_amg(sgo_ctx* c, bool keep_old, bool keep_agg) {
     c->amg = nullptr;
   }
   c->amg_arena.rewind();
-  if (keep_old && c->amg_prev && c->test_fail_trial_build) {   // test hook (SGO_TEST_FAIL_TRIAL_BUILD, read once per sgo_optimize_gn): the trial's set-up "fails"
+  if (keep_old && c->amg_prev && c->knobs.fail_trial_build) {   // test hook (SGO_TEST_FAIL_TRIAL_BUILD, read once per sgo_optimize_gn): the trial's set-up "fails"
     c->solver_desc = "pcg_block_jacobi (AMG unavailable: test hook)";
     return SGO_OK;
   }
   AmgConfig cfg;
-  cfg.theta_scale = c->amg_theta_scale;
-  cfg.filtered_smoothing = !c->amg_no_filter;
+  cfg.theta_scale = c->hier.theta_scale;
+  cfg.filtered_smoothing = !c->hier.no_filter;
   cfg.keep_agg = reuse_agg ? &c->kept_agg : nullptr;
   AmgProf prof;
   prof.user = c;
@@ -760,7 +760,7 @@ int build_amg(sgo_ctx* c, bool keep_old, bool keep_agg) {
   const double t_create0 = wall_s();
   const bool pre0_ready = c->l0_pre && amg_host_l0_ready(c->l0_pre);
   const bool pre0_agg = pre0_ready && amg_host_l0_agg_only(c->l0_pre);
-  const bool dev_setup = !c->owner && !multi_rank(c) && (pre0_agg || (!pre0_ready && (c->knobs.setup_mode == 2 || (c->knobs.setup_mode == 1 && c->in_optimize))));
+  const bool dev_setup = !c->owner && !multi_rank(c) && (pre0_agg || (!pre0_ready && (c->knobs.setup_mode == 2 || (c->knobs.setup_mode == 1 && c->call.in_optimize))));
   if (dev_setup)
     c->amg = amg_create_dev(c->stream, c->A, c->S0, c->T0, c->H0, c->d_poses, c->d_free_id, cfg, prof, &aerr, &c->amg_scratch, &c->amg_arena,
                             &c->amg_tmp_arena, c->knobs.dev_aggregation, pre0_agg ? c->l0_pre : nullptr);
@@ -808,13 +808,14 @@ int build_amg(sgo_ctx* c, bool keep_old, bool keep_agg) {
   }
   if (c->d_dref_agg && c->S0.dblk && !c->owner) {   // the blocks this aggregation was made from (optimize_gn's movement rule)
     HIP_TRY(c, hipMemcpyAsync(c->d_dref_agg, c->S0.dblk, sizeof(double) * 6 * (size_t)c->n, hipMemcpyDeviceToDevice, c->stream));
-    c->agg_ref_valid = true;
+    c->hier.agg_ref_valid = true;
   }
   return SGO_OK;
 }
 
 // The hierarchy a trial rebuild made is dropped for the one it replaced (build_amg(c, true) kept it): the old one's values are
-// refreshed by the next solve's amg_update like any other iteration's.
+// refreshed by the next solve's amg_update like any other iteration's.  What the hierarchy state forgets with it
+// (HierarchyState::reverted) is the caller's: CallPolicy applies it in order with the trial's verdict.
 int revert_amg(sgo_ctx* c) {
   if (!c->amg_prev) return SGO_OK;
   HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -830,16 +831,9 @@ int revert_amg(sgo_ctx* c) {
   c->amg_arena_prev.rewind();
   c->solver_desc = c->amg_prev_desc;
   c->pcg_pred = 0;
-  c->amg_best = 0;
-  c->agg_best = 0;
-  c->amg_ref_valid = false;   // its coarse operators are two iterations old: the next solve refreshes
-  c->amg_probe_max = 0.0;
-  c->agg_ref_valid = false;   // (and the blocks it was aggregated from are not known any more: the rule is off for this graph anyway)
   return SGO_OK;
 }
 
-// Vectors over the free vertices cross the API in g2o's hessian order and live on the device in the
-// internal (Hilbert) row order: permute on the way (test / single-step entry points only).
 // build_structure + what follows from it (multi-GPU tile range, tolerance rule)
 int build_rows(sgo_ctx* c, const double* poses, const uint8_t* fixed, const int32_t* ei, const int32_t* ej) {
   int rc = build_structure(c, c->V, poses, fixed, c->E, ei, ej);
@@ -895,6 +889,8 @@ int ensure_amg(sgo_ctx* c) {
   return SGO_OK;
 }
 
+// Vectors over the free vertices cross the API in g2o's hessian order and live on the device in the
+// internal (Hilbert) row order: permute on the way (test / single-step entry points only).
 int vec_to_device(sgo_ctx* c, const double* host_asc, double* dev) {
   std::vector<double> tmp(3 * (size_t)c->n);
   for (int i = 0; i < c->n; ++i)
@@ -965,462 +961,306 @@ static int solve_backward_error(sgo_ctx* c, double* eta) {
   return SGO_OK;
 }
 
+// The chi2 history of the call's `done` iterations into sgo_stats (both paths).
+static void copy_history(const sgo_ctx* c, int done, sgo_stats* out) {
+  out->iters_done = done;
+  for (int k = 0; k <= done; ++k) {
+    out->chi2[k] = c->h_hist[2 * k];
+    out->robust_chi2[k] = c->h_hist[2 * k + 1];
+  }
+}
+
+// Small-graph path: the whole call is one launch (sgo_direct.h); mid-size path: one launch per level of the elimination tree and
+// Gauss-Newton iteration, no host round trip inside the call (sgo_mfront.h).
+static int optimize_factored(sgo_ctx* c, int32_t iters, sgo_stats* out, double t0) {
+  hipError_t he;
+  if (c->direct) {
+    Scope sc(c, K_DIRECT, direct_bytes(c->direct, c->E, iters));
+    he = direct_optimize(c->direct, c->stream, c->el, c->d_poses, iters, c->d_hist, c->d_dres);
+  } else {
+    Scope sc(c, K_MFRONT, mfront_bytes(c->mf, c->E, iters), true);
+    he = mfront_optimize(c->mf, c->stream, c->el, c->d_poses, iters, c->d_hist, c->d_dres);
+  }
+  if (he != hipSuccess) {
+    c->err = std::string(c->direct ? "k_direct launch: " : "multifrontal launch: ") + hipGetErrorString(he);
+    return SGO_EHIP;
+  }
+  HIP_TRY(c, hipMemcpyAsync(c->h_hist, c->d_hist, sizeof(double) * 2 * (size_t)(iters + 1), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(c->h_dres, c->d_dres, sizeof(DirectResult), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  prof_flush(c);
+  c->linearized = false;
+  const DirectResult& R = *c->h_dres;
+  const int done = R.done;
+  if (R.fail) {
+    c->err = std::string(c->direct ? "direct" : "multifrontal") + " factorisation failed in GN iteration " + std::to_string(done) +
+             (R.fail == 1 ? " (a pivot block is not positive definite: Hessian not positive definite)"
+                          : " (non-finite update)") + "; the step was not applied";
+  }
+  if (out) {
+    copy_history(c, done, out);
+    const int timed = std::min(iters, done + (R.fail ? 1 : 0));
+    for (int k = 0; k < timed; ++k) {
+      out->pcg_iters[k] = 0;
+      out->pcg_converged[k] = (k < done) ? 1 : 0;
+      out->seconds_linearize[k] = 1e-8 * (double)(R.stamp[2 * k + 1] - R.stamp[2 * k]);
+      out->seconds[k] = 1e-8 * (double)(R.stamp[2 * k + 2] - R.stamp[2 * k]);
+      out->seconds_solve[k] = out->seconds[k] - out->seconds_linearize[k];
+    }
+    out->seconds_total = wall_s() - t0;
+  }
+  if (c->opts.verbose && done > 0 && c->direct)
+    std::fprintf(stderr, "[sgo] direct: %.0f MHz shader clock during the call\n",
+                 (double)R.cycles / (1e-2 * (double)(R.stamp[R.fail ? 2 * done + 2 : 2 * iters + 1] - R.stamp[0])));
+  if (c->opts.verbose && done > 0 && c->direct)
+    std::fprintf(stderr, "[sgo] direct, last iteration [us]: edges %.1f, assembly %.1f, sparse forward %.1f, separators %.1f + %.1f, "
+                 "sparse backward %.1f, update %.1f\n", 1e-2 * (double)(R.phase[1] - R.phase[0]), 1e-2 * (double)(R.phase[2] - R.phase[1]),
+                 1e-2 * (double)(R.phase[3] - R.phase[2]), 1e-2 * (double)(R.phase[4] - R.phase[3]), 1e-2 * (double)(R.phase[5] - R.phase[4]),
+                 1e-2 * (double)(R.phase[6] - R.phase[5]), 1e-2 * (double)(R.phase[7] - R.phase[6]));
+  if (c->opts.verbose > 1)
+    for (int k = 0; k <= done; ++k)
+      std::fprintf(stderr, "[sgo] iteration= %d\t chi2= %.9e\t robust= %.9e\t (%s)\n", k, c->h_hist[2 * k], c->h_hist[2 * k + 1], c->direct ? "direct" : "multifrontal");
+  return R.fail ? 0 : done;
+}
+
+// chi2, buildSystem and the PCG start state of iteration `it`, with the set-up the policy asked for: the movement since the
+// aggregation is measured in the call's first iteration, and a pending rebuild -- a re-aggregation trial's included -- is done here.
+static int linearize_step(sgo_ctx* c, CallPolicy& pol, int it, int iters) {
+  if (pol.trial == CallPolicy::kTrialJudging || pol.rebuild_next) c->hier.ref_valid = false;   // (the trial's solves are fresh ones)
+  int rc;
+  if ((rc = do_chi2(c, c->d_hist + 2 * it, nullptr)) || (rc = do_linearize(c))) return rc;
+  c->agg_grid = 0;
+  if (it == 0 && c->amg && c->call.lag_on && c->hier.agg_ref_valid && !c->owner && iters > 1)   // (read behind the first solve's synchronisation)
+    c->agg_grid = launch_diag_change(c->stream, 0, c->n, c->S0.dblk, c->d_dref_agg, false, c->h_dchg_dev + 3 * (size_t)kMaxPartials);
+  if (!pol.rebuild_next || !c->amg) return SGO_OK;
+  // Robust-kernel re-weighting has changed the strength of connection since the aggregation (CallPolicy::record): redo the set-up.
+  if (pol.last_rebuild()) c->hier.no_filter = true;   // (the call's last rebuild: CallPolicy::abandon)
+  const bool trial = pol.trial == CallPolicy::kTrialPending;
+  rc = build_amg(c, trial, c->knobs.keep_agg);
+  if (trial && c->amg_prev && (rc != SGO_OK || !c->amg) && rc != SGO_ECOMM) {
+    // A TRIAL whose set-up did not come about (out of device memory -- a trial holds two hierarchies --, or the graph cannot be
+    // coarsened at its current values): the parked hierarchy is intact and comes back.
+    const std::string why = c->err;
+    if ((rc = revert_amg(c))) return rc;
+    pol.trial_failed(c->hier, why);
+    c->err.clear();
+    if (c->opts.verbose) std::fprintf(stderr, "[sgo] iteration %d: the trial set-up failed; the previous hierarchy is back\n", it);
+    return do_linearize(c);
+  }
+  if (rc || (rc = do_linearize(c))) return rc;
+  pol.rebuilt();
+  if (c->opts.verbose) std::fprintf(stderr, "[sgo] multigrid hierarchy rebuilt before iteration %d\n", it);
+  return SGO_OK;
+}
+
+// A solve that STAGNATED (run_pcg's guard) or ran out of iterations with x at the floating-point floor of its system: accepted,
+// like a backward-stable direct solver's solution (solve_backward_error above).  Single GPU (the guard's domain).
+static int check_floor(sgo_ctx* c, CallPolicy& pol, int it, bool* accept) {
+  if (*accept || !(c->h_S->stop == 2 && (c->pcg_stalled || c->h_S->iter >= c->opts.pcg_maxit) && !c->owner && !multi_rank(c))) return SGO_OK;
+  double eta = 1.0;
+  const int rc = solve_backward_error(c, &eta);
+  if (rc) return rc;
+  *accept = eta <= rules::kFloorEta;
+  if (*accept) {
+    ++pol.floor_solves;
+    c->call.floor_seen = true;
+    if (c->opts.verbose)
+      std::fprintf(stderr, "[sgo] iteration %d: the solve's x is at the floating-point floor of its system (scaled backward error %.1e <= %.0e): step applied\n", it, eta, rules::kFloorEta);
+  }
+  return SGO_OK;
+}
+
+// The hierarchy is re-made from the current values, the system linearised again and the solve repeated from x = 0 (`what`: why).
+static int rebuild_and_solve(sgo_ctx* c, CallPolicy& pol, int it, bool keep_agg, const std::string& what, bool* floor_accept) {
+  c->call.pcg_softcap = 0;
+  int rc;
+  if ((rc = build_amg(c, false, keep_agg)) || (rc = do_linearize(c)) || (rc = run_pcg(c))) return rc;
+  pol.rebuilt();
+  if (c->opts.verbose) std::fprintf(stderr, "[sgo] iteration %d: %s\n", it, what.c_str());
+  return check_floor(c, pol, it, floor_accept);
+}
+
+// The solve of iteration `it` and its recoveries.  *wasted: the iterations of an abandoned solve; *interrupted: a solve behind kept
+// coarse operators carried on behind refreshed ones; *floor_accept: the solve stands at the floating-point floor.
+static int solve_step(sgo_ctx* c, CallPolicy& pol, int it, int* wasted, bool* interrupted, bool* floor_accept) {
+  int rc;
+  if ((rc = run_pcg(c))) return rc;
+  const PcgScalars& S = *c->h_S;   // (what the latest run_pcg left)
+  if (c->call.skip_update && c->amg && (S.stop == 4 || (S.stop == 2 && S.iter < c->opts.pcg_maxit && c->call.pcg_softcap > 0))) {
+    // A solve behind KEPT coarse operators (lagged refresh) that its progress probe stopped -- half a decade behind the last fresh
+    // solve after a third of its count -- or its cap, the fresh count + 3: the operators are refreshed and the solve carries on.
+    const int at = S.iter;
+    c->call.pcg_softcap = pol.continue_cap(c->hier, at);
+    const int maxit = c->call.pcg_softcap > 0 ? std::min(c->call.pcg_softcap, c->opts.pcg_maxit) : c->opts.pcg_maxit;
+    c->pcg_pred = std::max(2, pol.fresh_pcg);
+    if ((rc = refresh_and_continue(c, maxit)) || (rc = run_pcg(c))) return rc;
+    *interrupted = true;
+    pol.kept_interrupted(c->hier, moved_rel(c, 0.0));
+    if (c->opts.verbose)
+      std::fprintf(stderr, "[sgo] iteration %d: solve behind kept coarse operators interrupted after %d PCG iterations, operators refreshed\n", it, at);
+  }
+  if ((rc = check_floor(c, pol, it, floor_accept))) return rc;
+  if (!*floor_accept && c->call.pcg_softcap > 0 && S.stop == 2 && S.iter < c->opts.pcg_maxit && c->amg) {
+    // The solve ran into the bail-out cap (4x the best count of this hierarchy): the aggregation no longer fits the re-weighted
+    // Hessian -- rebuild and solve again instead of grinding on (seen: 735 iterations where the rebuilt hierarchy needs 16).
+    *wasted = S.iter;
+    pol.abandon(c->hier, amg_has_filtered(c->amg));
+    const std::string what = "solve abandoned after " + std::to_string(*wasted) + " PCG iterations, hierarchy rebuilt";
+    if ((rc = rebuild_and_solve(c, pol, it, c->knobs.keep_agg && c->hier.best != 0, what, floor_accept))) return rc;
+  }
+  if (!*floor_accept && S.stop == 3 && c->amg && amg_has_filtered(c->amg) && pol.can_rebuild()) {
+    // A breakdown (p.Hp <= 0 or non-finite) behind FILTERED transfers: the Gauss-Newton Hessian is positive semi-definite, so the
+    // preconditioner is the first suspect -- redone with tentative transfers, solved once more; an indefinite H fails again.
+    *wasted += S.iter;
+    c->hier.no_filter = true;
+    return rebuild_and_solve(c, pol, it, false, "PCG breakdown behind a filtered hierarchy, rebuilt with tentative transfers and solved again", floor_accept);
+  }
+  return SGO_OK;
+}
+
+// The finished solve (no breakdown) into the call's policy, and what it says to do now: a lost trial's hierarchy goes back.
+static int record_solve(sgo_ctx* c, CallPolicy& pol, int it, bool interrupted, bool floor_accept) {
+  const PcgScalars& S = *c->h_S;
+  double v[3];   // movement since the aggregation (measured in the call's first iteration)
+  if (c->agg_grid > 0) sum_diag_change(c, 1, c->agg_grid, v);
+  const SolveRecord r{it, S.iter, c->opts.pcg_tol * c->tol_scale, std::sqrt(S.tol2), c->call.skip_update, interrupted, floor_accept,
+                      moved_rel(c, 0.0), S.probe_k, S.probe_rel, c->amg_prev != nullptr, c->agg_grid > 0 ? v : nullptr, c->n};
+  c->agg_grid = 0;
+  if (pol.record(c->hier, r, c->opts.verbose ? stderr : nullptr) != CallPolicy::kRevertTrial) return SGO_OK;
+  if (const int rc = revert_amg(c)) return rc;
+  if (c->opts.verbose)
+    std::fprintf(stderr, "[sgo] iteration %d: the re-aggregated hierarchy is no better (%d against %d): the old one is back\n", it, pol.trial_best, pol.trial_old);
+  return SGO_OK;
+}
+
+// Solver failure, as LinearSolverEigen::solve returning false (OptimizationAlgorithm::Fail): stop == 3: p.Hp <= 0 or non-finite
+// (H not positive definite); stop == 2: pcg_maxit iterations without reaching pcg_tol (an inexact step is never applied).
+static std::string failure_message(sgo_ctx* c, const PcgScalars& S, int it) {
+  if (S.stop == 3)
+    return "PCG breakdown in GN iteration " + std::to_string(it) + " (Hessian not positive definite" +
+           (c->amg && amg_coarsest_not_spd(c->amg, c->stream) ? "; its coarsest Galerkin operator has a non-positive pivot" : "") + ")";
+  return (c->pcg_stalled ? "PCG stagnated (no new minimum of the residual in the last " + std::to_string(c->pcg_stall_window) + " of " +
+                               std::to_string(S.iter) + " iterations; pcg_maxit = "
+                         : "PCG did not reach pcg_tol within pcg_maxit = ") + std::to_string(c->opts.pcg_maxit) +
+         (c->pcg_stalled ? ")" : " iterations") + " in GN iteration " + std::to_string(it) + " (relative residual " +
+         std::to_string(S.bb > 0 ? std::sqrt(S.rr / S.bb) : 0.0) + "); the step was not applied";
+}
+
+// g2o's optimize(iters) on the PCG path: per iteration linearise (with any rebuild the policy asked for),
+// solve, recover, check the floor, record the solve in the call's policy (sgo_policy.h), then fail or apply the step.
 int optimize_gn(sgo_ctx* c, int32_t iters, sgo_stats* out) {
-    int rc = check_graph(c);
-    if (rc) return rc;
-    if (iters < 0 || iters > SGO_MAX_ITERS) {
-      c->err = "sgo_optimize_gn: iters must be in [0, SGO_MAX_ITERS]";
-      return SGO_EINVAL;
+  int rc = check_graph(c);
+  if (rc) return rc;
+  if (iters < 0 || iters > SGO_MAX_ITERS) {
+    c->err = "sgo_optimize_gn: iters must be in [0, SGO_MAX_ITERS]";
+    return SGO_EINVAL;
+  }
+  if (out) {
+    std::memset(out, 0, sizeof(*out));
+    out->iters_requested = iters;
+    out->seconds_setup = c->setup_seconds;
+  }
+  if (c->n == 0) return SGO_ENOTHING;
+  const double t0 = wall_s();
+  read_call_knobs(c);
+  if (c->direct || c->mf) return optimize_factored(c, iters, out, t0);
+  if ((rc = ensure_amg(c))) return rc;
+  // per-iteration time stamps: events are kept in the context and reused by later calls
+  while (c->iter_events.size() < 3 * (size_t)iters + 1) {
+    hipEvent_t e = nullptr;
+    HIP_TRY(c, hipEventCreate(&e));
+    c->iter_events.push_back(e);
+  }
+  std::vector<hipEvent_t>& ev = c->iter_events;
+  // the call's caps, accuracy target, warm start and lagged refresh apply to solves inside this call only
+  struct CallScope { sgo_ctx* c; ~CallScope() { c->call = sgo_ctx::CallState(); } } call_scope{c};
+  c->call = sgo_ctx::CallState();
+  c->call.in_optimize = true;
+  // Lagged refresh of the coarse operators (do_linearize): on by default on one GPU (the sharded modes, not exercised on hardware,
+  // refresh before every solve); SGO_AMG_LAG=0 refreshes always.  The call's first solve always refreshes (HierarchyState::begin_call).
+  c->call.lag_on = c->knobs.lag_on && !multi_rank(c);   // (replicated ranks: the whole single-GPU computation each)
+  c->hier.begin_call(c->n, c->knobs.lag_slope);
+  c->lag_note.clear();
+  c->tol_cap = c->opts.pcg_tol_cap > 0.0 ? std::max(c->opts.pcg_tol_cap, c->opts.pcg_tol * c->tol_scale) : 0.0;
+  CallPolicy pol(iters, c->knobs.rebuild_cost, c->knobs.force_rebuild && c->amg != nullptr);   // (test hook: a rebuild first)
+  int done = 0;
+  bool failed = false;
+  for (int it = 0; it < iters; ++it) {
+    hipEventRecord(ev[3 * it], c->stream);
+    c->call.pcg_softcap = pol.solve_cap(c->hier, c->amg != nullptr, c->knobs.first_solve_cap);
+    c->call.lag_cap = pol.lag_cap();
+    c->call.force_keep = c->knobs.lag_force_from >= 0 && it > c->knobs.lag_force_from;   // (calibration hook, scripts/lag_calib.py)
+    if ((rc = linearize_step(c, pol, it, iters))) return rc;
+    hipEventRecord(ev[3 * it + 1], c->stream);
+    int wasted = 0;
+    bool interrupted = false, floor_accept = false;
+    if ((rc = solve_step(c, pol, it, &wasted, &interrupted, &floor_accept))) return rc;
+    if (c->amg_dchg_pending) read_diag_change(c);   // (written before the solve began; the solve's end was waited for)
+    // what the blocks moved by in this iteration, against the operators' reference: when they were refreshed now, the NEXT
+    // iteration's movement against them will be about this iteration's one-step movement or less
+    if (c->call.lag_on)
+      c->call.lag_expect = c->hier.ref_valid && moved_rel(c, 1.0) <= 2.0 * lag_allowed(c) && c->last_dchg[2] <= 4.0 * rules::kLagRowsMoved;
+    const PcgScalars S = *c->h_S;
+    if (it == 0 && c->tol_cap > 0.0 && S.stop == 1) c->call.bb_ref = S.bb;
+    if (c->amg && S.stop != 3 && (rc = record_solve(c, pol, it, interrupted, floor_accept))) return rc;
+    if (it == 0 && S.stop == 1) {   // the call's first solve: what the incremental set-up's staleness rule compares (sgo_ctx.h)
+      c->its_last = S.iter;
+      if (!c->ov.active && c->its_base == 0) c->its_base = S.iter;
     }
     if (out) {
-      std::memset(out, 0, sizeof(*out));
-      out->iters_requested = iters;
-      out->seconds_setup = c->setup_seconds;
+      out->pcg_iters[it] = S.iter + wasted;   // an abandoned solve's iterations count too
+      out->pcg_converged[it] = S.stop == 1 ? 1 : (floor_accept ? 2 : 0);
+      out->pcg_relres[it] = S.bb > 0 ? std::sqrt(S.rr / S.bb) : 0.0;
     }
-    if (c->n == 0) return SGO_ENOTHING;
-    const double t0 = wall_s();
-    read_call_knobs(c);
-    if (c->direct || c->mf) {
-      // ---- small-graph path: the whole call is one launch (sgo_direct.h); mid-size path: one launch per level of the
-      // elimination tree and Gauss-Newton iteration, no host round trip inside the call (sgo_mfront.h)
-      if (c->direct) {
-        Scope sc(c, K_DIRECT, direct_bytes(c->direct, c->E, iters));
-        hipError_t he = direct_optimize(c->direct, c->stream, c->el, c->d_poses, iters, c->d_hist, c->d_dres);
-        if (he != hipSuccess) {
-          c->err = std::string("k_direct launch: ") + hipGetErrorString(he);
-          return SGO_EHIP;
-        }
-      } else {
-        Scope sc(c, K_MFRONT, mfront_bytes(c->mf, c->E, iters), true);
-        hipError_t he = mfront_optimize(c->mf, c->stream, c->el, c->d_poses, iters, c->d_hist, c->d_dres);
-        if (he != hipSuccess) {
-          c->err = std::string("multifrontal launch: ") + hipGetErrorString(he);
-          return SGO_EHIP;
-        }
-      }
-      HIP_TRY(c, hipMemcpyAsync(c->h_hist, c->d_hist, sizeof(double) * 2 * (size_t)(iters + 1), hipMemcpyDeviceToHost, c->stream));
-      HIP_TRY(c, hipMemcpyAsync(c->h_dres, c->d_dres, sizeof(DirectResult), hipMemcpyDeviceToHost, c->stream));
-      HIP_TRY(c, hipStreamSynchronize(c->stream));
-      prof_flush(c);
-      c->linearized = false;
-      const DirectResult& R = *c->h_dres;
-      const int done = R.done;
-      if (R.fail) {
-        c->err = std::string(c->direct ? "direct" : "multifrontal") + " factorisation failed in GN iteration " + std::to_string(done) +
-                 (R.fail == 1 ? " (a pivot block is not positive definite: Hessian not positive definite)"
-                              : " (non-finite update)") + "; the step was not applied";
-      }
-      if (out) {
-        out->iters_done = done;
-        for (int k = 0; k <= done; ++k) {
-          out->chi2[k] = c->h_hist[2 * k];
-          out->robust_chi2[k] = c->h_hist[2 * k + 1];
-        }
-        const int timed = std::min(iters, done + (R.fail ? 1 : 0));
-        for (int k = 0; k < timed; ++k) {
-          out->pcg_iters[k] = 0;
-          out->pcg_converged[k] = (k < done) ? 1 : 0;
-          out->seconds_linearize[k] = 1e-8 * (double)(R.stamp[2 * k + 1] - R.stamp[2 * k]);
-          out->seconds[k] = 1e-8 * (double)(R.stamp[2 * k + 2] - R.stamp[2 * k]);
-          out->seconds_solve[k] = out->seconds[k] - out->seconds_linearize[k];
-        }
-        out->seconds_total = wall_s() - t0;
-      }
-      if (c->opts.verbose && done > 0 && c->direct)
-        std::fprintf(stderr, "[sgo] direct: %.0f MHz shader clock during the call\n",
-                     (double)R.cycles / (1e-2 * (double)(R.stamp[R.fail ? 2 * done + 2 : 2 * iters + 1] - R.stamp[0])));
-      if (c->opts.verbose && done > 0 && c->direct)
-        std::fprintf(stderr, "[sgo] direct, last iteration [us]: edges %.1f, assembly %.1f, sparse forward %.1f, separators %.1f + %.1f, "
-                     "sparse backward %.1f, update %.1f\n", 1e-2 * (double)(R.phase[1] - R.phase[0]), 1e-2 * (double)(R.phase[2] - R.phase[1]),
-                     1e-2 * (double)(R.phase[3] - R.phase[2]), 1e-2 * (double)(R.phase[4] - R.phase[3]), 1e-2 * (double)(R.phase[5] - R.phase[4]),
-                     1e-2 * (double)(R.phase[6] - R.phase[5]), 1e-2 * (double)(R.phase[7] - R.phase[6]));
-      if (c->opts.verbose > 1)
-        for (int k = 0; k <= done; ++k)
-          std::fprintf(stderr, "[sgo] iteration= %d\t chi2= %.9e\t robust= %.9e\t (%s)\n", k, c->h_hist[2 * k], c->h_hist[2 * k + 1], c->direct ? "direct" : "multifrontal");
-      return R.fail ? 0 : done;
-    }
-    if ((rc = ensure_amg(c))) return rc;
-    // per-iteration time stamps: events are kept in the context and reused by later calls
-    while (c->iter_events.size() < 3 * (size_t)iters + 1) {
-      hipEvent_t e = nullptr;
-      HIP_TRY(c, hipEventCreate(&e));
-      c->iter_events.push_back(e);
-    }
-    std::vector<hipEvent_t>& ev = c->iter_events;
-    struct SoftcapGuard {   // the bail-out cap and the absolute accuracy target apply to solves inside this call only
-      sgo_ctx* c;
-      ~SoftcapGuard() {
-        c->pcg_softcap = 0;
-        c->bb_ref = 0.0;
-        c->warm_valid = false;
-        c->amg_lag_on = false;
-        c->amg_skip_update = false;
-        c->in_optimize = false;
-        c->floor_seen = false;
-      }
-    } softcap_guard{c};
-    // Lagged refresh of the coarse operators (do_linearize): on by default on one GPU (the sharded modes refresh before every solve:
-    // a decision the ranks must take alike, not exercised on hardware); SGO_AMG_LAG=0 refreshes before every solve.
-    // The call's first solve always refreshes (the incremental set-up's staleness rule compares first solves, sgo_ctx.h).
-    c->amg_lag_tau = c->knobs.lag_tau;
-    c->amg_lag_rows = 32.0;
-    if (c->amg_lag_n == 0 || std::abs(c->n - c->amg_lag_n) > c->amg_lag_n / 10) {   // another graph: its sensitivity is not known yet
-      c->amg_lag_slope = rules::kLagSlopeStart;
-      c->amg_lag_slope_seen = false;
-    }
-    c->amg_lag_n = c->n;
-    if (c->knobs.lag_slope > 0.0) {   // test hook (SGO_AMG_LAG_SLOPE): the sensitivity every call starts from (1: keep whatever SGO_AMG_LAG_TAU allows)
-      c->amg_lag_slope = c->knobs.lag_slope;
-      c->amg_lag_slope_seen = false;
-    }
-    c->amg_lag_on = c->knobs.lag_on && !multi_rank(c);   // (replicated ranks: the whole single-GPU computation each)
-    c->amg_ref_valid = false;
-    c->amg_probe_max = 0.0;
-    c->amg_lag_expect = false;
-    if (c->amg_probe_k < 4) c->amg_probe_k = 6;
-    const int force_from = c->knobs.lag_force_from;   // (calibration hook, scripts/lag_calib.py)
-    int fresh_pcg = 0;   // the count of the last solve behind freshly made coarse operators
-    int kept_solves = 0;
-    int floor_solves = 0;   // solves accepted at the floating-point floor of their system (solve_backward_error)
-    int call_best = 0;   // the fewest (equal-tolerance) iterations a fresh solve of this call has taken
-    std::string agg_note;
-    int trial = 0, trial_old = 0, trial_best = 0, trial_seen = 0;   // the re-aggregation rule's trial: 1 = rebuild pending, 2 = judging the new hierarchy's first solves
-    c->lag_note.clear();
-    c->warm_valid = false;
-    const bool warm_env = c->opts.pcg_warm_start != 0;
-    c->bb_ref = 0.0;
-    c->tol_cap = c->opts.pcg_tol_cap > 0.0 ? std::max(c->opts.pcg_tol_cap, c->opts.pcg_tol * c->tol_scale) : 0.0;
-    int done = 0;
-    bool failed = false;
-    int rebuilds = 0;
-    bool rebuild_next = c->knobs.force_rebuild && c->amg != nullptr;   // (test hook: the set-up is redone before the call's first solve)
-    c->in_optimize = true;
-    // (a cap on the set-ups redone inside one call, against thrashing: three for a short call, one per three Gauss-Newton
-    // iterations for a long one.  Round 5: with three flat, a call whose weights keep changing -- DCS from a dead-reckoned
-    // start -- used them up by iteration 6 and then had no safety net left: its 10th solve ground on to pcg_maxit.)
-    const int max_rebuilds = rules::max_rebuilds(iters);
-    double its_sum = 0.0;
-    for (int it = 0; it < iters; ++it) {
-      hipEventRecord(ev[3 * it], c->stream);
-      c->pcg_softcap = (c->amg && c->amg_best > 0 && rebuilds < max_rebuilds && !rebuild_next) ? rules::bail_out_cap(c->amg_best) : 0;
-      // A hierarchy that has never solved anything gets 600 iterations (the hardest first solves seen take 200-350: C4 from a
-      // dead-reckoned start): one that needs more has a coarse space that does not carry the slow modes, and the set-up is
-      // redone with HALF the strength thresholds (larger aggregates, sparser coarse operators) instead of grinding on to
-      // pcg_maxit.  (SGO_FIRST_SOLVE_CAP: test hook.)
-      const int first_solve_cap = c->knobs.first_solve_cap;
-      if (c->amg && c->amg_best == 0 && rebuilds < max_rebuilds && c->amg_theta_scale > 0.2) c->pcg_softcap = first_solve_cap;
-      c->amg_lag_cap = rules::lag_cap(fresh_pcg);
-      c->amg_force_keep = force_from >= 0 && it > force_from;
-      if (trial == 2) c->amg_ref_valid = false;   // (the trial's solves are fresh ones)
-      if (rebuild_next) c->amg_ref_valid = false;
-      if ((rc = do_chi2(c, c->d_hist + 2 * it, nullptr)) || (rc = do_linearize(c))) return rc;
-      c->agg_grid = 0;
-      if (it == 0 && c->amg && c->amg_lag_on && c->agg_ref_valid && !c->owner && iters > 1)   // (read behind the first solve's synchronisation)
-        c->agg_grid = launch_diag_change(c->stream, 0, c->n, c->S0.dblk, c->d_dref_agg, false, c->h_dchg_dev + 3 * (size_t)kMaxPartials);
-      if (rebuild_next && c->amg) {
-        // The aggregation was made from the Hessian of an earlier linearisation and robust-kernel
-        // re-weighting has changed the strength of connection since (see the rule below): redo the
-        // set-up from the current values (same cost as in sgo_set_graph_se2).
-        if (rebuilds + 1 >= max_rebuilds) c->amg_no_filter = true;   // (the call's last rebuild: see the abandoned solve below)
-        const bool was_trial = trial == 1;
-        rc = build_amg(c, was_trial, c->knobs.keep_agg);
-        if (was_trial && c->amg_prev && (rc != SGO_OK || !c->amg) && rc != SGO_ECOMM) {
-          // A TRIAL whose set-up did not come about (out of device memory -- a trial holds two hierarchies --, or the graph at its
-          // current values cannot be coarsened): the hierarchy that was parked for the comparison is intact and comes back; the
-          // re-aggregation rule is off for this graph, and the call carries on as if it had never tried.  (Without this the solve
-          // ran behind block-Jacobi under the old hierarchy's bail-out cap and failed, with the working hierarchy unused in
-          // amg_prev for every later call: ADVICE round 5.)
-          const std::string why = c->err;
-          if ((rc = revert_amg(c))) return rc;
-          trial = 0;
-          c->agg_rule_off = true;
-          rebuild_next = false;
-          c->err.clear();
-          agg_note = "a re-aggregation was attempted in the last sgo_optimize_gn and its set-up failed" + (why.empty() ? std::string() : " (" + why + ")") +
-                     ": the previous hierarchy stays";
-          if (c->opts.verbose) std::fprintf(stderr, "[sgo] iteration %d: the trial set-up failed; the previous hierarchy is back\n", it);
-          if ((rc = do_linearize(c))) return rc;
-        } else {
-        if (rc || (rc = do_linearize(c))) return rc;
-        if (trial == 1) trial = 2;
-        rebuild_next = false;
-        ++rebuilds;
-        call_best = 0;   // (another hierarchy: its first solve sets the reference)
-        if (c->opts.verbose) std::fprintf(stderr, "[sgo] multigrid hierarchy rebuilt before iteration %d\n", it);
-        }
-      }
-      hipEventRecord(ev[3 * it + 1], c->stream);
-      int wasted = 0;
-      if ((rc = run_pcg(c))) {
-        return rc;
-      }
-      bool kept_interrupted = false;
-      if (c->amg_skip_update && c->amg && (c->h_S->stop == 4 || (c->h_S->stop == 2 && c->h_S->iter < c->opts.pcg_maxit && c->pcg_softcap > 0))) {
-        // A solve behind KEPT coarse operators (lagged refresh, do_linearize) that its progress probe stopped -- after a third of the
-        // last fresh count its residual was more than half a decade behind that solve's -- or that reached its cap, the
-        // fresh count + 3: the operators are refreshed and the solve carries on from where it is.
-        const int at = c->h_S->iter;
-        c->pcg_softcap = (c->amg_best > 0 && rebuilds < max_rebuilds) ? rules::bail_out_cap(c->amg_best) + at : 0;
-        const int maxit = c->pcg_softcap > 0 ? std::min(c->pcg_softcap, c->opts.pcg_maxit) : c->opts.pcg_maxit;
-        c->pcg_pred = std::max(2, fresh_pcg);
-        if ((rc = refresh_and_continue(c, maxit)) || (rc = run_pcg(c))) return rc;
-        kept_interrupted = true;
-        const double moved = c->last_dchg[1] > 0.0 ? c->last_dchg[0] / c->last_dchg[1] : 0.0;
-        // (counted as sixteen iterations over -- but never past what forbids keeping over 0.01 % of movement: an interruption at next
-        // to no movement was not the movement's doing, and a slope that only kept solves can lower must not lock them out)
-        c->amg_lag_slope = rules::lag_slope_after_interrupt(c->amg_lag_slope, moved);
-        c->amg_lag_slope_seen = true;
-        if (c->opts.verbose)
-          std::fprintf(stderr, "[sgo] iteration %d: solve behind kept coarse operators interrupted after %d PCG iterations, operators refreshed\n", it, at);
-      }
-      // A solve that STAGNATED (run_pcg's guard) or ran out of iterations with x at the floating-point floor of its system: accepted,
-      // like a backward-stable direct solver's solution (solve_backward_error above).  Single GPU (the guard's domain).
-      bool floor_accept = false;
-      auto check_floor = [&]() -> int {
-        if (floor_accept || !(c->h_S->stop == 2 && (c->pcg_stalled || c->h_S->iter >= c->opts.pcg_maxit) && !c->owner && !multi_rank(c))) return SGO_OK;
-        double eta = 1.0;
-        const int r2 = solve_backward_error(c, &eta);
-        if (r2) return r2;
-        floor_accept = eta <= rules::kFloorEta;
-        if (floor_accept) {
-          ++floor_solves;
-          c->floor_seen = true;
-          if (c->opts.verbose)
-            std::fprintf(stderr, "[sgo] iteration %d: the solve's x is at the floating-point floor of its system (scaled backward error %.1e <= %.0e): step applied\n", it, eta, rules::kFloorEta);
-        }
-        return SGO_OK;
-      };
-      if ((rc = check_floor())) return rc;
-      if (!floor_accept && c->pcg_softcap > 0 && c->h_S->stop == 2 && c->h_S->iter < c->opts.pcg_maxit && c->amg) {
-        // The solve ran into the bail-out cap (4x the best count of this hierarchy): the aggregation no
-        // longer fits the re-weighted Hessian.  Redo the set-up from the current values and solve again
-        // from x = 0 instead of grinding on (seen: 735 iterations where the rebuilt hierarchy needs 16).
-        wasted = c->h_S->iter;
-        c->pcg_softcap = 0;
-        // (a hierarchy with FILTERED transfers -- sgo_amg_host.h -- that never solved anything: what the filter dropped is not
-        // negligible together on this graph, it keeps the tentative transfers on those levels from here on.  One that HAS solved
-        // and is abandoned now is stale -- connections it lumped into the diagonal have become strong, and such a hierarchy does
-        // not degrade gracefully --: the rebuild filters by the current values)
-        if (c->amg_best == 0 && amg_has_filtered(c->amg)) c->amg_no_filter = true;
-        else if (c->amg_best == 0) c->amg_theta_scale *= 0.5;   // this hierarchy never worked: coarsen more aggressively
-        // The hierarchy the call's LAST rebuild leaves has no safety net behind it (no bail-out cap without a rebuild to follow):
-        // it keeps the tentative transfers, which go stale gracefully -- 190 -> 240 iterations where a stale filtered one can
-        // grind on to pcg_maxit (seen with another aggregation threshold from the dead-reckoned start: 11 059, then 20 000)
-        if (rebuilds + 1 >= max_rebuilds) c->amg_no_filter = true;
-        if ((rc = build_amg(c, false, c->knobs.keep_agg && c->amg_best != 0)) || (rc = do_linearize(c)) || (rc = run_pcg(c))) return rc;
-        ++rebuilds;
-        call_best = 0;   // (another hierarchy: its first solve sets the reference)
-        rebuild_next = false;
-        if (c->opts.verbose)
-          std::fprintf(stderr, "[sgo] iteration %d: solve abandoned after %d PCG iterations, hierarchy rebuilt\n", it, wasted);
-        if ((rc = check_floor())) return rc;
-      }
-      if (!floor_accept && c->h_S->stop == 3 && c->amg && amg_has_filtered(c->amg) && rebuilds < max_rebuilds) {
-        // A breakdown (p.Hp <= 0 or a non-finite scalar) behind a hierarchy with FILTERED transfers: the Gauss-Newton Hessian is
-        // positive semi-definite by construction, so the first suspect is the preconditioner -- the set-up is redone with the
-        // tentative transfers and the solve repeated once; a Hessian that really is indefinite fails again and is reported.
-        wasted += c->h_S->iter;
-        c->amg_no_filter = true;
-        c->pcg_softcap = 0;
-        if ((rc = build_amg(c)) || (rc = do_linearize(c)) || (rc = run_pcg(c))) return rc;
-        ++rebuilds;
-        call_best = 0;   // (another hierarchy: its first solve sets the reference)
-        rebuild_next = false;
-        if (c->opts.verbose)
-          std::fprintf(stderr, "[sgo] iteration %d: PCG breakdown behind a filtered hierarchy, rebuilt with tentative transfers and solved again\n", it);
-        if ((rc = check_floor())) return rc;
-      }
-      if (c->amg_dchg_pending) read_diag_change(c);   // (written before the solve began; the solve's end was waited for)
-      if (c->amg_lag_on) {
-        // what the blocks moved by in this iteration, against the operators' reference: when they were refreshed now, the NEXT
-        // iteration's movement against them will be about this iteration's one-step movement or less
-        const double moved = c->last_dchg[1] > 0.0 ? c->last_dchg[0] / c->last_dchg[1] : 1.0;
-        c->amg_lag_expect = c->amg_ref_valid && moved <= 2.0 * lag_allowed(c) && c->last_dchg[2] <= 4.0 * c->amg_lag_rows;
-      }
-      const PcgScalars S = *c->h_S;
-      int& best_pcg = c->amg_best;
-      if (it == 0 && c->tol_cap > 0.0 && S.stop == 1) c->bb_ref = S.bb;
-      if (c->amg && S.stop != 3) {
-        // Iteration counts are compared at EQUAL tolerance: a solve that stopped at the absolute criterion (a looser
-        // relative tolerance, see pcg_tol_cap) is scaled to what pcg_tol would have cost -- PCG converges linearly,
-        // iterations ~ log(1 / tolerance) -- or the staleness rules below would take every tight solve that follows
-        // a loose one for a stale hierarchy.
-        const double tol0 = c->opts.pcg_tol * c->tol_scale, tolk = std::sqrt(S.tol2);
-        const int eq_iter = rules::equal_tolerance_count(S.iter, tol0, tolk);
-        if (kept_interrupted || floor_accept) {
-          // (counts of a solve that changed its preconditioner half-way, or that ended at the floating-point floor, say nothing
-          // about either hierarchy state)
-        } else if (c->amg_skip_update) {
-          ++kept_solves;
-          // behind kept coarse operators: judged against the last fresh solve only -- when the lag has cost more than a refresh is
-          // worth (~ 8-10 PCG iterations on C2 / C4), the next solve refreshes whatever the blocks' movement says
-          if (rules::kept_solve_too_slow(eq_iter, fresh_pcg)) c->amg_ref_valid = false;
-          // ... and every kept solve teaches what movement costs on this graph (the first observation replaces the cautious start,
-          // later ones raise the slope at once and lower it slowly)
-          const double moved = c->last_dchg[1] > 0.0 ? c->last_dchg[0] / c->last_dchg[1] : 0.0;
-          c->amg_lag_slope = rules::lag_slope_after_kept(c->amg_lag_slope, c->amg_lag_slope_seen, eq_iter - fresh_pcg, moved);
-          c->amg_lag_slope_seen = true;
-        } else {
-        fresh_pcg = eq_iter;
-        c->amg_lag_slope = rules::lag_slope_after_fresh(c->amg_lag_slope);   // (a high slope is re-examined in time)
-        if (trial == 2) {
-          // The re-made hierarchy's first two (fresh, warm-started) solves against the old one's first solve of this call (cold): a
-          // hierarchy that is better shows it at once -- 22 / 24 against 33 on the C4-sized session --; one that is not -- the
-          // re-aggregation can lose a smoothed transfer it had, 42 / 38 against 27 on a 40 k / 60 k graph -- is dropped for the old.
-          trial_best = trial_seen == 0 ? eq_iter : std::min(trial_best, eq_iter);
-          if (++trial_seen == 2) {
-            trial = 0;
-            if (rules::trial_reverts(trial_best, trial_old)) {
-              if ((rc = revert_amg(c))) return rc;
-              call_best = 0;
-              c->agg_rule_off = true;
-              rebuild_next = false;
-              fresh_pcg = 0;
-              agg_note = "a re-aggregated hierarchy was tried in the last sgo_optimize_gn and dropped (" + std::to_string(trial_best) + " PCG iterations against the old one's " + std::to_string(trial_old) + ")";
-              if (c->opts.verbose) std::fprintf(stderr, "[sgo] iteration %d: the re-aggregated hierarchy is no better (%d against %d): the old one is back\n", it, trial_best, trial_old);
-            }
-          }
-        }
-        if (c->agg_best == 0 || eq_iter < c->agg_best) c->agg_best = eq_iter;   // (an incremental update resets amg_best, not this)
-        // the progress probe of the solves that keep these operators: iteration fresh / 3 (at least 4), half a decade of slack
-        if (S.probe_k > 0 && S.iter >= S.probe_k && S.probe_rel > 0.0) c->amg_probe_max = 10.0 * S.probe_rel;
-        else if (S.probe_k > 0) c->amg_probe_max = 0.0;
-        const int k_new = rules::probe_iteration(S.iter);
-        if (S.probe_k < 4 || std::abs(k_new - S.probe_k) > 1) {   // (the record was taken at another iteration: the next fresh solve records anew)
-          c->amg_probe_k = k_new;
-          c->amg_probe_max = 0.0;
-        }
-        if (best_pcg == 0 || eq_iter < best_pcg) best_pcg = eq_iter;
-        // Redo the aggregation from the current values when that pays: always when the count has more
-        // than doubled, and when it is > 25 % above the best while the PCG iterations it would save
-        // over the remaining GN iterations exceed the set-up's cost (~150 PCG iterations' worth: host
-        // aggregation + one more linearisation).  Counts only -- no clocks -- so that every rank of a
-        // multi-GPU run takes the same decision.
-        // (crediting a rebuild only for as long as the previous one of this call stayed good -- weights that keep changing -- was
-        // measured in round 5 on C4 from a dead-reckoned start and is worse: the hierarchy left in place went from 74 to 400
-        // iterations two solves later; median 29.8 against 23.3 ms per Gauss-Newton iteration)
-        // (against the best count of THIS call: the first solve of a call from a far start is harder than the last solves of the call
-        // before whatever the hierarchy -- C5 re-optimised from its initial poses: 88 iterations against the 31 the previous call ended
-        // with -- and with the best carried over, every such call redid the set-up after its first solve, at a state the NEXT call's
-        // start then found useless: 2.2 instead of 1.4 s per call.  Staleness across calls is the movement rule's business, below.)
-        if (call_best == 0 || eq_iter < call_best) call_best = eq_iter;
-        const int left = iters - it - 1;
-        if (rebuilds < max_rebuilds && rules::staleness(eq_iter, call_best, left, c->knobs.rebuild_cost).rebuild()) rebuild_next = true;
-        // The aggregation's own staleness, across calls: the hierarchy was aggregated from blocks that have since moved a lot -- a
-        // graph set up at poor poses and optimised since -- and this call's first solve needs visibly more iterations than the
-        // hierarchy's best.  The count rules above weigh a rebuild against the iterations left in THIS call; the reference calls
-        // optimize(20) after every closure (slc.cpp:286-287), and the excess is paid in every call (bench.py's incremental session:
-        // 24.7 iterations per solve behind the hierarchy of the initial poses, 19.1 behind one made after the first optimize).
-        if (c->agg_grid > 0) {
-          double v[3] = {0.0, 0.0, 0.0};
-          const volatile double* h = c->h_dchg + 3 * (size_t)kMaxPartials;
-          for (int k = 0; k < 3; ++k)
-            for (int i = 0; i < c->agg_grid; ++i) v[k] += h[(size_t)k * kMaxPartials + i];
-          c->agg_grid = 0;
-          const bool moved_far = rules::moved_far(v[0], v[1], v[2], c->n);
-          if (c->opts.verbose) std::fprintf(stderr, "[sgo] since the aggregation: blocks moved by %.2f %%, %.0f rows by a quarter; first solve %d, best of this aggregation %d\n", v[1] > 0 ? 100.0 * v[0] / v[1] : 0.0, v[2], eq_iter, c->agg_best);
-          if (rules::reaggregate(moved_far, c->agg_rule_off, iters - it, c->agg_best, eq_iter, rebuilds, max_rebuilds, rebuild_next)) {
-            rebuild_next = true;
-            trial = 1;
-            trial_old = eq_iter;
-            char nb[160];
-            std::snprintf(nb, sizeof nb, "hierarchy re-aggregated in the last sgo_optimize_gn (the blocks had moved by %.0f %% since it was made)", 100.0 * v[0] / v[1]);
-            agg_note = nb;
-            if (c->opts.verbose)
-              std::fprintf(stderr, "[sgo] the blocks have moved by %.1f %% (%.0f rows by a quarter) since the hierarchy was aggregated, first solve %d against its best %d: rebuild\n",
-                           100.0 * v[0] / v[1], v[2], eq_iter, c->agg_best);
-          }
-        }
-        }
-      }
-      its_sum += S.iter + wasted;
-      if (it == 0 && S.stop == 1) {   // the call's first solve: what the incremental set-up's staleness rule compares (sgo_ctx.h)
-        c->its_last = S.iter;
-        if (!c->ov.active && c->its_base == 0) c->its_base = S.iter;
-      }
-      if (out) {
-        out->pcg_iters[it] = S.iter + wasted;   // an abandoned solve's iterations count too
-        out->pcg_converged[it] = S.stop == 1 ? 1 : (floor_accept ? 2 : 0);
-        out->pcg_relres[it] = S.bb > 0 ? std::sqrt(S.rr / S.bb) : 0.0;
-      }
-      if (S.stop != 1 && !floor_accept) {
-        // Solver failure, as LinearSolverEigen::solve returning false (OptimizationAlgorithm::Fail): the
-        // step is NOT applied, estimates stay at the last successful update and the call returns 0 like
-        // g2o::SparseOptimizer::optimize.  stop == 3: p.Hp <= 0 or non-finite (H not positive definite);
-        // stop == 2: pcg_maxit iterations without reaching pcg_tol (an inexact step is never applied).
-        if (S.stop == 3) {
-          c->err = "PCG breakdown in GN iteration " + std::to_string(it) + " (Hessian not positive definite";
-          if (c->amg && amg_coarsest_not_spd(c->amg, c->stream)) c->err += "; its coarsest Galerkin operator has a non-positive pivot";
-          c->err += ")";
-        } else {
-          c->err = (c->pcg_stalled ? "PCG stagnated (no new minimum of the residual in the last " + std::to_string(c->pcg_stall_window) + " of " +
-                                         std::to_string(S.iter) + " iterations; pcg_maxit = "
-                                   : "PCG did not reach pcg_tol within pcg_maxit = ") + std::to_string(c->opts.pcg_maxit) +
-                   (c->pcg_stalled ? ")" : " iterations") + " in GN iteration " + std::to_string(it) + " (relative residual " +
-                   std::to_string(S.bb > 0 ? std::sqrt(S.rr / S.bb) : 0.0) + "); the step was not applied";
-        }
-        failed = true;
-        hipEventRecord(ev[3 * it + 2], c->stream);
-        break;
-      }
-      // (row-owner mode: every rank holds all poses; the ranks' slices of the step are gathered first)
-      if (c->owner && !halo_gather_slices(c->halo, c->stream, c->d_x, 3, &c->err)) return SGO_ECOMM;
-      if (c->ov.active) launch_ov_finish(c->stream, c->ov.dev, c->d_x, c->d_poses);   // x_N and the appended poses' update
-      {
-        Scope sc(c, K_POSE_UPDATE, 72.0 * c->n);
-        launch_pose_update(c->stream, c->n, c->d_free_id, c->d_x, c->d_poses);
-      }
-      if (warm_env && c->amg && c->d_xprev) {   // (multi-GPU: the same replicated arithmetic on every rank)
-        HIP_TRY(c, hipMemcpyAsync(c->d_xprev, c->d_x, sizeof(double) * 3 * (size_t)c->n, hipMemcpyDeviceToDevice, c->stream));
-        c->warm_valid = !rebuild_next;   // a rebuilt hierarchy starts cold (its first solve sets the reference counts)
-      }
+    if (S.stop != 1 && !floor_accept) {   // the step is NOT applied; g2o::SparseOptimizer::optimize returns 0
+      c->err = failure_message(c, S, it);
+      failed = true;
       hipEventRecord(ev[3 * it + 2], c->stream);
-      c->linearized = false;
-      ++done;
-      if (c->opts.verbose)
-        std::fprintf(stderr, "[sgo] iteration= %d\t pcg= %d\t relres= %.3e\t |b|= %.3e\t diag moved %.3e (%.0f rows > 1/4; kept up to %.1e)%s\n", it, S.iter,
-                     S.bb > 0 ? std::sqrt(S.rr / S.bb) : 0.0, std::sqrt(S.bb), c->last_dchg[1] > 0 ? c->last_dchg[0] / c->last_dchg[1] : 0.0,
-                     c->last_dchg[2], lag_allowed(c), c->amg_skip_update ? " coarse operators kept" : "");
+      break;
     }
-    c->pcg_softcap = 0;
-    (void)its_sum;
-    if (kept_solves > 0)
-      c->lag_note = "last sgo_optimize_gn: " + std::to_string(kept_solves) + " of " + std::to_string(done) + " solves kept the coarse operators of the one before";
-    if (!agg_note.empty()) c->lag_note += (c->lag_note.empty() ? "" : "; ") + agg_note;
-    if (floor_solves > 0)
-      c->lag_note += std::string(c->lag_note.empty() ? "last sgo_optimize_gn: " : "; ") + std::to_string(floor_solves) +
-                     " solve(s) stopped at the floating-point floor of their system (Jacobi-scaled backward error <= 1e-12 without reaching pcg_tol): "
-                     "steps applied, as a backward-stable direct solver's would be";
-    if ((rc = do_chi2(c, c->d_hist + 2 * done, nullptr))) {
-      return rc;
+    // (row-owner mode: every rank holds all poses; the ranks' slices of the step are gathered first)
+    if (c->owner && !halo_gather_slices(c->halo, c->stream, c->d_x, 3, &c->err)) return SGO_ECOMM;
+    if (c->ov.active) launch_ov_finish(c->stream, c->ov.dev, c->d_x, c->d_poses);   // x_N and the appended poses' update
+    {
+      Scope sc(c, K_POSE_UPDATE, 72.0 * c->n);
+      launch_pose_update(c->stream, c->n, c->d_free_id, c->d_x, c->d_poses);
     }
-    HIP_TRY(c, hipMemcpyAsync(c->h_hist, c->d_hist, sizeof(double) * 2 * (size_t)(done + 1), hipMemcpyDeviceToHost,
-                              c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (c->amg_prev && trial == 0) {   // a trial that was accepted: the replaced hierarchy goes; its arena keeps its chunks for the next
-      amg_destroy(c->amg_prev);      // trial (released and re-grown every time, the chunk size doubled until each trial took a gigabyte)
-      c->amg_prev = nullptr;
-      c->amg_arena_prev.rewind();
+    if (c->opts.pcg_warm_start && c->amg && c->d_xprev) {   // (multi-GPU: the same replicated arithmetic on every rank)
+      HIP_TRY(c, hipMemcpyAsync(c->d_xprev, c->d_x, sizeof(double) * 3 * (size_t)c->n, hipMemcpyDeviceToDevice, c->stream));
+      c->call.warm_valid = !pol.rebuild_next;   // a rebuilt hierarchy starts cold (its first solve sets the reference counts)
     }
-    prof_flush(c);
-    if (out) {
-      out->iters_done = done;
-      for (int k = 0; k <= done; ++k) {
-        out->chi2[k] = c->h_hist[2 * k];
-        out->robust_chi2[k] = c->h_hist[2 * k + 1];
-      }
-      const int timed = std::min(iters, done + 1);
-      for (int k = 0; k < timed; ++k) {
-        float a = 0.f, b = 0.f;
-        hipEventElapsedTime(&a, ev[3 * k], ev[3 * k + 1]);
-        hipEventElapsedTime(&b, ev[3 * k + 1], ev[3 * k + 2]);
-        out->seconds_linearize[k] = a * 1e-3;
-        out->seconds_solve[k] = b * 1e-3;
-        out->seconds[k] = (a + b) * 1e-3;
-      }
-      out->seconds_total = wall_s() - t0;
+    hipEventRecord(ev[3 * it + 2], c->stream);
+    c->linearized = false;
+    ++done;
+    if (c->opts.verbose)
+      std::fprintf(stderr, "[sgo] iteration= %d\t pcg= %d\t relres= %.3e\t |b|= %.3e\t diag moved %.3e (%.0f rows > 1/4; kept up to %.1e)%s\n", it, S.iter,
+                   S.bb > 0 ? std::sqrt(S.rr / S.bb) : 0.0, std::sqrt(S.bb), moved_rel(c, 0.0), c->last_dchg[2], lag_allowed(c),
+                   c->call.skip_update ? " coarse operators kept" : "");
+  }
+  c->lag_note = pol.note(done);
+  if ((rc = do_chi2(c, c->d_hist + 2 * done, nullptr))) return rc;
+  HIP_TRY(c, hipMemcpyAsync(c->h_hist, c->d_hist, sizeof(double) * 2 * (size_t)(done + 1), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if (c->amg_prev && pol.trial == CallPolicy::kNoTrial) {   // a trial that was accepted: the replaced hierarchy goes; its arena keeps
+    amg_destroy(c->amg_prev);                                // its chunks for the next trial (released and re-grown every time, the
+    c->amg_prev = nullptr;                                   // chunk size doubled until each trial took a gigabyte)
+    c->amg_arena_prev.rewind();
+  }
+  prof_flush(c);
+  if (out) {
+    copy_history(c, done, out);
+    const int timed = std::min(iters, done + 1);
+    for (int k = 0; k < timed; ++k) {
+      float a = 0.f, b = 0.f;
+      hipEventElapsedTime(&a, ev[3 * k], ev[3 * k + 1]);
+      hipEventElapsedTime(&b, ev[3 * k + 1], ev[3 * k + 2]);
+      out->seconds_linearize[k] = a * 1e-3;
+      out->seconds_solve[k] = b * 1e-3;
+      out->seconds[k] = (a + b) * 1e-3;
     }
-    return failed ? 0 : done;   // g2o: optimize() returns 0 when the algorithm reported Fail
+    out->seconds_total = wall_s() - t0;
+  }
+  return failed ? 0 : done;   // g2o: optimize() returns 0 when the algorithm reported Fail
 }
 
 // Micro-benchmark of the level-0 product on the resident graph: `reps` back-to-back launches of

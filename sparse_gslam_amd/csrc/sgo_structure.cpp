@@ -88,7 +88,7 @@ void free_graph(sgo_ctx* c) {
     amg_destroy(c->amg_prev);
     c->amg_prev = nullptr;
   }
-  c->agg_rule_off = false;
+  c->hier.new_graph();
   if (c->direct) {
     direct_destroy(c->direct);
     c->direct = nullptr;
@@ -98,8 +98,6 @@ void free_graph(sgo_ctx* c) {
     c->mf = nullptr;
   }
   c->amg_pending = false;
-  c->amg_theta_scale = 1.0;
-  c->amg_no_filter = false;
   c->order_xy.clear();
   c->rows_pending = false;
   c->amg_arena.rewind();
@@ -114,9 +112,6 @@ void free_graph(sgo_ctx* c) {
   c->d_xprev = nullptr;
   c->d_dref = nullptr;
   c->d_dref_agg = nullptr;
-  c->agg_ref_valid = false;
-  c->amg_ref_valid = false;
-  c->warm_valid = false;
   c->has_graph = false;
   c->linearized = false;
   c->owner = false;
