@@ -1,5 +1,6 @@
 // sgo_amg.h -- rigid-body smoothed-aggregation multigrid preconditioner for the block-CSR
-// Gauss-Newton Hessian.  See sgo_amg.hip for the algorithm and DESIGN.md section 5.
+// Gauss-Newton Hessian.  See sgo_amg.hip for the algorithm and DESIGN.md section 5; the set-up: one level assembler behind two
+// pattern producers (AmgPatterns below).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -76,22 +77,25 @@ struct HostLevel {
                             // along a Hilbert curve: chains of odometry edges then pair up regularly
 };
 
+// Where the levels' patterns come from.  Two producers make a level's DevCoarse, one assembler (sgo_amg.hip) turns it into a working
+// level, so the hierarchies differ only in where the patterns were made:
+//   host               host_coarsen (sgo_amg_host.cpp), uploaded: the multi-GPU modes' set-up (the only one the row-owner mode takes),
+//                      SGO_AMG_SETUP=host, the fallback of a device set-up that cannot be made;
+//   device             dev_coarsen (sgo_amg_dev.inc: sort / scan / compress passes) from the host's aggregation -- its greedy walk along
+//                      the trajectory makes the better aggregates and is a fifth of the host set-up's time --: the default on one GPU;
+//   device_aggregation the same with the device's parallel aggregation (SGO_AMG_AGG=device).
+// Kept aggregates (AmgConfig::keep_agg) and the helper thread's level 0 (pre0) take precedence wherever they fit the source.
+enum class AmgPatterns { host, device, device_aggregation };
 // Build the hierarchy for the level-0 matrix: S0 is its symmetric storage (the cycle's level-0 products
 // run on it), A0 its logical view (set-up kernels) and H0 the same structure on the host.  The values
 // (S0.ublk, dblk, dinv) must hold the linearisation at the initial poses (they provide the strength of
 // connection).  `d_poses` / `d_free_id` give the positions of the level-0 nodes: pos of row h =
 // poses[3*free_id[h] + 0..1].  `scratch` (optional) provides host memory for the set-up's large temporary
-// lists; it is rewound here and may be rewound again by the caller once amg_create has returned.
+// lists; it is rewound here and may be rewound again by the caller once amg_create has returned.  `tmp_arena` holds the device
+// temporaries of the set-up (rewound per level, kept between set-ups).
 Amg* amg_create(hipStream_t s, const BsrDev& A0, const Sym0Dev& S0, const Tile0Dev& T0, const HostLevel& H0, const double* d_poses,
-                const int* d_free_id, const AmgConfig& cfg, const AmgProf& prof, std::string* err,
-                ChunkArena* scratch, DevArena* arena, struct AmgHostL0* pre0 = nullptr, const AmgHalo* halo = nullptr);
-// The same hierarchy set up entirely ON THE DEVICE (sgo_amg_dev.inc; single GPU): parallel aggregation, patterns by sort / scan /
-// compress passes.  What a rebuild inside sgo_optimize_gn uses (build_amg, sgo_solve.cpp).
-// aggregate_on_device = false (default of the callers): the aggregation stays the host's greedy walk along the trajectory (its
-// aggregates are the better ones, and it is a fifth of the host set-up's time); everything else on the device.
-Amg* amg_create_dev(hipStream_t s, const BsrDev& A0, const Sym0Dev& S0, const Tile0Dev& T0, const HostLevel& H0, const double* d_poses,
-                    const int* d_free_id, const AmgConfig& cfg, const AmgProf& prof, std::string* err, ChunkArena* scratch, DevArena* arena,
-                    DevArena* tmp_arena, bool aggregate_on_device, const struct AmgHostL0* pre0);
+                const int* d_free_id, const AmgConfig& cfg, const AmgProf& prof, std::string* err, ChunkArena* scratch, DevArena* arena,
+                DevArena* tmp_arena, AmgPatterns patterns, struct AmgHostL0* pre0 = nullptr, const AmgHalo* halo = nullptr);
 // Level 0's host analysis (aggregation, patterns and product lists of the transfer, structure of level 1) made ahead
 // of amg_create from the level's logical structure and the strength weights w (Frobenius norms of the slots' blocks
 // at the initial poses, logical slot order): amg_host_l0_run may execute on a helper thread while the caller still
@@ -99,7 +103,7 @@ Amg* amg_create_dev(hipStream_t s, const BsrDev& A0, const Sym0Dev& S0, const Ti
 // amg_create has returned.
 struct AmgHostL0;
 AmgHostL0* amg_host_l0_new();
-// agg_only: the aggregation alone (the patterns are then made on the device: amg_create_dev(..., pre0))
+// agg_only: the aggregation alone (the patterns are then made on the device: amg_create(..., AmgPatterns::device, pre0))
 void amg_host_l0_run(AmgHostL0* p, const HostLevel& H0, const std::vector<double>& w, const AmgConfig& cfg, ChunkArena* scratch, bool agg_only = false);
 bool amg_host_l0_agg_only(const AmgHostL0* p);
 void amg_host_l0_free(AmgHostL0* p);

@@ -155,7 +155,7 @@ __global__ __launch_bounds__(kBlock) void k_galerkin(BsrDev F, BsrDev C, Galerki
 // Prolongator smoothed by one damped block-Jacobi step, P = (I - w D^-1 A) T, and the Galerkin
 // operator A_c = P^T A P formed in two sparse products (AP = A P, then P^T AP).  The sparsity of
 // P, AP and A_c and the list of block products behind every entry are fixed by the graph and the
-// aggregation: the host lists them once (amg_create), sorted by target entry, and the numeric
+// aggregation: the set-up lists them once (amg_create), sorted by target entry, and the numeric
 // phase of every GN iteration is three segmented-sum kernels of the k_galerkin kind.
 struct ProdMap {
   int n = 0;                 // products
@@ -708,17 +708,36 @@ __global__ __launch_bounds__(kBlock) void k_fold_colptr(const unsigned long long
     ptr[c] = lo;
   }
 }
-// the wave groups longer than kLongColumn (single long columns): their ranges, in any order (one workgroup each later on)
-__global__ __launch_bounds__(kBlock) void k_fold_long(const int* __restrict__ grp, int ngrp, int* __restrict__ count, int* __restrict__ ranges,
-                                                      int cap) {
+// the wave groups longer than kLongColumn (single long columns): their ranges, in any order (one workgroup each later on); ranges
+// holds 2 x ngrp ints
+__global__ __launch_bounds__(kBlock) void k_long_groups(const int* __restrict__ grp, int ngrp, int* __restrict__ count, int* __restrict__ ranges) {
   for (int g = blockIdx.x * kBlock + threadIdx.x; g < ngrp; g += gridDim.x * kBlock) {
     const int b = grp[g], e = grp[g + 1];
     if (e - b > kLongColumn) {
       const int q = atomicAdd(count, 1);
-      if (q < cap) {
-        ranges[2 * q] = b;
-        ranges[2 * q + 1] = e;
-      }
+      ranges[2 * q] = b;
+      ranges[2 * q + 1] = e;
+    }
+  }
+}
+// UpDev of a level >= 1: u_ptr[i] = the row's slots of A + its entries of P~ before row i; then the list itself
+__global__ __launch_bounds__(kBlock) void k_u_ptr(int n, const int* __restrict__ a_rowptr, const int* __restrict__ ap_rowptr, int* __restrict__ u_ptr) {
+  for (int i = blockIdx.x * kBlock + threadIdx.x; i <= n; i += gridDim.x * kBlock) u_ptr[i] = a_rowptr[i] + ap_rowptr[i];
+}
+__global__ __launch_bounds__(kBlock) void k_u_fill(int n, const int* __restrict__ a_rowptr, const int* __restrict__ a_col,
+                                                   const int* __restrict__ ap_rowptr, const int* __restrict__ ap_col, const int* __restrict__ u_ptr,
+                                                   int* __restrict__ u_row, int* __restrict__ u_idx, int* __restrict__ u_col) {
+  for (int i = blockIdx.x * kBlock + threadIdx.x; i < n; i += gridDim.x * kBlock) {
+    int q = u_ptr[i];
+    for (int k = a_rowptr[i]; k < a_rowptr[i + 1]; ++k, ++q) {
+      u_row[q] = i;
+      u_idx[q] = k;
+      u_col[q] = a_col[k];
+    }
+    for (int f = ap_rowptr[i]; f < ap_rowptr[i + 1]; ++f, ++q) {
+      u_row[q] = i;
+      u_idx[q] = ~f;
+      u_col[q] = ap_col[f];
     }
   }
 }
@@ -1529,24 +1548,44 @@ __global__ __launch_bounds__(1024) void k_scan_small(int* __restrict__ v, int n)
   }
   if (threadIdx.x == 1023) v[n] = sm[1023];
 }
-// Wave groups over the segments [ptr[f], ptr[f+1]): whole segments packed up to 64 items, a longer segment its own
-// group -- make_groups' rule, applied independently to chunks of kGroupChunk segments (one thread each: short chunks keep the serial walk short; a chunk starts a new group; the
-// grouping does not change a single sum).  Pass 1 counts a chunk's groups, pass 2 (after a prefix sum) writes them.
-// (kGroupChunk: sgo_amg_host.h -- the host's make_groups applies the same rule to the same chunks)
+// Wave groups over the segments [ptr[f], ptr[f+1]): whole segments packed up to 64 items, a longer segment its own group (the rule
+// of the level-0 row groups in sgo_structure.cpp), applied independently to chunks of kGroupChunk segments -- a chunk starts a new
+// group; one thread per chunk keeps the serial walk short.  A group is recorded by its start; a list is closed by its total.  The
+// grouping never changes WHICH terms a segmented sum has, only their association order inside the wavefront segmented scan (its DPP
+// steps are tied to the lanes' positions) -- which is why a level's lists are grouped here and nowhere else, whichever producer made
+// its patterns (tests/test_gpu_device_setup.py: the two hierarchies are bit-identical).
+// All the lists of a level in two launches (GroupBatch, below): the lists' chunks are numbered through, every list followed by one
+// pseudo-chunk that holds its closing element; pass 1 counts a chunk's groups, pass 2 (after a prefix sum) writes them.
+constexpr int kGroupChunk = 256;
+constexpr int kMaxGroupJobs = 12;
+struct GroupJobsDev {
+  const int* ptr[kMaxGroupJobs];
+  int nseg[kMaxGroupJobs];
+  int total[kMaxGroupJobs];
+  int chunk0[kMaxGroupJobs + 1];   // first global chunk of list j (its pseudo-chunk is chunk0[j + 1] - 1)
+  int njobs;
+};
 template <bool FILL>
-__global__ __launch_bounds__(kBlock) void k_group_chunks(const int* __restrict__ ptr, int nseg, int* __restrict__ cnt_or_off,
-                                                         int* __restrict__ grp) {
-  const int ch = blockIdx.x * kBlock + threadIdx.x, s0 = ch * kGroupChunk;
-  if (s0 >= nseg) return;
-  const int s1 = min(nseg, s0 + kGroupChunk);
-  int out = FILL ? cnt_or_off[ch] : 0, cur = 0, start = ptr[s0];
-  // a group is recorded by its START position; the list is closed with the total by the caller
+__global__ __launch_bounds__(kBlock) void k_group_jobs(GroupJobsDev J, int* __restrict__ cnt_or_off, int* __restrict__ out) {
+  const int c = blockIdx.x * kBlock + threadIdx.x;
+  if (c >= J.chunk0[J.njobs]) return;
+  int j = 0;
+  while (c >= J.chunk0[j + 1]) ++j;
+  const int local = c - J.chunk0[j];
+  if (c == J.chunk0[j + 1] - 1) {   // the list's closing element
+    if (FILL) out[cnt_or_off[c]] = J.total[j];
+    else cnt_or_off[c] = 1;
+    return;
+  }
+  const int* __restrict__ ptr = J.ptr[j];
+  const int nseg = J.nseg[j], s0 = local * kGroupChunk, s1 = min(nseg, s0 + kGroupChunk);
+  int o = FILL ? cnt_or_off[c] : 0, cur = 0, start = ptr[s0];
   bool open = false;
   for (int f = s0; f < s1; ++f) {
-    const int b = ptr[f], e = ptr[f + 1], len = e - b;
+    const int b = ptr[f], len = ptr[f + 1] - b;
     if (open && cur + len > 64) {
-      if (FILL) grp[out] = start;
-      ++out;
+      if (FILL) out[o] = start;
+      ++o;
       open = false;
       cur = 0;
     }
@@ -1556,17 +1595,21 @@ __global__ __launch_bounds__(kBlock) void k_group_chunks(const int* __restrict__
     }
     cur += len;
     if (cur >= 64) {
-      if (FILL) grp[out] = start;
-      ++out;
+      if (FILL) out[o] = start;
+      ++o;
       open = false;
       cur = 0;
     }
   }
   if (open) {
-    if (FILL) grp[out] = start;
-    ++out;
+    if (FILL) out[o] = start;
+    ++o;
   }
-  if (!FILL) cnt_or_off[ch] = out;
+  if (!FILL) cnt_or_off[c] = o;
+}
+__global__ void k_gather_ints(const int* __restrict__ src, GroupJobsDev J, int* __restrict__ dst) {
+  const int j = threadIdx.x;
+  if (blockIdx.x == 0 && j <= J.njobs) dst[j] = src[J.chunk0[j]];
 }
 
 // --------------------------------------------------------------------------------- host
@@ -2204,28 +2247,6 @@ void dev_scan_exclusive(hipStream_t s, int* v, int n, int* sums) {
   SGO_LAUNCH(k_scan_top, dim3(1), dim3(kBlock), 0, s, sums, nb);
   SGO_LAUNCH(k_scan_apply, dim3(std::max(nb, 1)), dim3(kBlock), 0, s, v, n, (const int*)sums, nb);
 }
-// Wave groups over the segments of ptr[0..nseg] on the device: returns the group list (ngrp + 1 starts, closed by the
-// total) and ngrp; synchronises the stream once (the group count sizes the list).  nullptr on failure.
-int* dev_make_groups(hipStream_t s, DevArena* pool, const int* ptr, int nseg, int total, int* ngrp_out) {
-  const int nch = std::max(1, (nseg + kGroupChunk - 1) / kGroupChunk);
-  int* cnt = dev_alloc<int>(pool, (size_t)nch + 1);
-  int* sums = dev_alloc<int>(pool, (size_t)nch / kScanChunk + 3);
-  if (!cnt || !sums) return nullptr;
-  hipMemsetAsync(cnt, 0, sizeof(int) * ((size_t)nch + 1), s);
-  SGO_LAUNCH((k_group_chunks<false>), dim3((nch + kBlock - 1) / kBlock), dim3(kBlock), 0, s, ptr, nseg, cnt, (int*)nullptr);
-  dev_scan_exclusive(s, cnt, nch, sums);
-  int ngrp = 0;
-  if (hipMemcpyAsync(&ngrp, cnt + nch, sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
-    return nullptr;
-  int* grp = dev_alloc<int>(pool, (size_t)ngrp + 1);
-  if (!grp) return nullptr;
-  SGO_LAUNCH((k_group_chunks<true>), dim3((nch + kBlock - 1) / kBlock), dim3(kBlock), 0, s, ptr, nseg, cnt, grp);
-  hipMemcpyAsync(grp + ngrp, &total, sizeof(int), hipMemcpyHostToDevice, s);
-  hipStreamSynchronize(s);   // `total` is a stack variable
-  *ngrp_out = ngrp;
-  return grp;
-}
-
 // The configuration amg_create works with for a level-0 operator of n rows / nslot logical slots: the caller's
 // values, the environment overrides and the size-dependent choices.
 AmgConfig amg_effective_config(const AmgConfig& cfg_in, int n, int nslot) {
@@ -2287,7 +2308,7 @@ void amg_host_l0_run(AmgHostL0* p, const HostLevel& H0, const std::vector<double
   try {
     const AmgConfig cfg = amg_effective_config(cfg_in, H0.n, H0.nslot);
     if (H0.n <= cfg.coarsest_nodes || 1 >= cfg.max_levels) return;   // amg_create will not coarsen level 0 at all
-    if (agg_only) {   // the patterns follow on the device (amg_create_dev)
+    if (agg_only) {   // the patterns follow on the device (amg_create with device patterns)
       p->hc.nc = host_aggregate(H0, w, cfg, 0, scratch, p->hc.agg, p->hc.visit_c, &p->theta_used);
       p->agg_only = true;
       p->ready = true;
@@ -2300,16 +2321,534 @@ void amg_host_l0_run(AmgHostL0* p, const HostLevel& H0, const std::vector<double
   }
 }
 
+namespace {
+
+// ============================================================================================ the level assembler
+// The wave-group lists of one level, made as ONE batch: every list's count pass and scan first, one synchronisation for all the group
+// counts (they size the lists), then the fill passes -- a level has up to a dozen lists, and on the small levels of a hierarchy the
+// set-up's time IS its host round trips.
+enum GroupId { G_MEM, G_VAL, G_R, G_T, G_C, G_F, G_GAL, G_ST, G_PSR, G_U, G_APL, G_RAPL, G_COUNT };
+struct GroupBatch {
+  struct Job {
+    const int* ptr = nullptr;
+    int nseg = 0, total = 0;
+    bool on = false;
+  };
+  Job job[G_COUNT];
+  int* grp[G_COUNT] = {};
+  int ngrp[G_COUNT] = {};
+  void add(GroupId id, const int* ptr, int nseg, int total) {
+    job[id].ptr = ptr;
+    job[id].nseg = nseg;
+    job[id].total = total;
+    job[id].on = true;
+  }
+  // all the pending lists (k_group_jobs): two launches, a scan and one synchronisation; the lists go to the hierarchy's arena
+  bool run(DevSetup& D) {
+    GroupJobsDev J;
+    int ids[kMaxGroupJobs];
+    J.njobs = 0;
+    J.chunk0[0] = 0;
+    for (int g = 0; g < G_COUNT; ++g) {
+      const Job& j = job[g];
+      if (!j.on) continue;
+      const int q = J.njobs++;
+      ids[q] = g;
+      J.ptr[q] = j.ptr;
+      J.nseg[q] = j.nseg;
+      J.total[q] = j.total;
+      J.chunk0[q + 1] = J.chunk0[q] + (j.nseg + kGroupChunk - 1) / kGroupChunk + 1;   // (+ the pseudo-chunk of the closing element)
+    }
+    if (J.njobs == 0) return D.ok;
+    const int nch = J.chunk0[J.njobs];
+    int* off = D.talloc<int>((size_t)nch + 1);
+    int* d_first = D.talloc<int>(kMaxGroupJobs + 1);
+    if (!D.ok) return false;
+    const dim3 grid((nch + kBlock - 1) / kBlock), block(kBlock);
+    SGO_LAUNCH((k_group_jobs<false>), grid, block, 0, D.s, J, off, (int*)nullptr);
+    D.scan(off, nch);
+    if (!D.ok) return false;
+    SGO_LAUNCH(k_gather_ints, dim3(1), dim3(64), 0, D.s, (const int*)off, J, d_first);   // (off[nch] = everything)
+    int h_first[kMaxGroupJobs + 1] = {};
+    if (hipMemcpyAsync(h_first, d_first, sizeof(int) * (size_t)(J.njobs + 1), hipMemcpyDeviceToHost, D.s) != hipSuccess) D.ok = false;
+    if (!D.sync()) return false;
+    int* out = D.alloc<int>((size_t)std::max(h_first[J.njobs], 1));
+    if (!D.ok) return false;
+    SGO_LAUNCH((k_group_jobs<true>), grid, block, 0, D.s, J, off, out);
+    for (int q = 0; q < J.njobs; ++q) {
+      grp[ids[q]] = out + h_first[q];
+      ngrp[ids[q]] = h_first[q + 1] - h_first[q] - 1;
+      job[ids[q]].on = false;
+    }
+    return D.ok;
+  }
+};
+
+// The work vectors of level l (the coarser levels: the K-cycle's too, and its partial sums)
+bool alloc_work(Amg* m, hipStream_t s, int l) {
+  AmgLevel& L = m->lv[l];
+  const int n3 = 3 * L.A.n;
+  L.spmv_grid = grid_for(L.A.ngrp, kWavesPerBlock);
+  L.xs = dev_alloc<double>(m->pool, n3);
+  L.rs = dev_alloc<double>(m->pool, n3);
+  L.tR = dev_alloc<double>(m->pool, n3);
+  if (!L.pos) L.pos = dev_alloc<double>(m->pool, 2 * (size_t)L.A.n);
+  if (!L.xs || !L.rs || !L.tR || !L.pos) return false;
+  if (l == 0) return true;
+  L.bk = dev_alloc<double>(m->pool, n3);
+  L.xk = dev_alloc<double>(m->pool, n3);
+  L.z1 = dev_alloc<double>(m->pool, n3);
+  L.z2 = dev_alloc<double>(m->pool, n3);
+  L.q = dev_alloc<double>(m->pool, n3);
+  L.bk2 = dev_alloc<double>(m->pool, n3);
+  L.p2 = dev_alloc<double>(m->pool, n3);
+  L.q2 = dev_alloc<double>(m->pool, n3);
+  L.pA = dev_alloc<double>(m->pool, 2 * (size_t)kMaxPartials);
+  L.pB = dev_alloc<double>(m->pool, 2 * (size_t)kMaxPartials);
+  L.pC = dev_alloc<double>(m->pool, 2 * (size_t)kMaxPartials);
+  if (!L.bk || !L.xk || !L.z1 || !L.z2 || !L.q || !L.bk2 || !L.p2 || !L.q2 || !L.pA || !L.pB || !L.pC) return false;
+  hipMemsetAsync(L.pA, 0, sizeof(double) * 2 * kMaxPartials, s);
+  hipMemsetAsync(L.pB, 0, sizeof(double) * 2 * kMaxPartials, s);
+  hipMemsetAsync(L.pC, 0, sizeof(double) * 2 * kMaxPartials, s);
+  return true;
+}
+
+// A host-made coarsening step (host_coarsen's, or the set-up pipeline's level-0 result) as the DevCoarse the assembler takes.  Row-owner
+// level 0 (`own`: this rank's rows [row0, row1)): the P entries, their value products and the A P entries of the rank's rows only --
+// allocated for those ranges, base pointers shifted so that global numbers address them -- and the rank's own column order of its
+// entries.  One synchronisation at the end: the host vectors, the rank-local ones made here included, may go away after it.
+bool upload_coarse(DevSetup& D, const HostCoarse& hc, int n, const HaloDev* own, DevCoarse& o) {
+  auto keep = [&](const auto& v) {   // into the hierarchy's arena
+    auto* d = dev_upload(D.pool, v, D.s);
+    if (!d) D.ok = false;
+    return d;
+  };
+  auto temp = [&](const std::vector<int>& v) {   // used by the set-up only: into the temporary arena
+    int* d = dev_upload(D.tmp, v, D.s);
+    if (!d) D.ok = false;
+    return d;
+  };
+  auto range = [&](const int* host, int lo, int hi) -> int* {   // host[lo, hi) into the hierarchy's arena, addressed by global numbers
+    int* d = D.alloc<int>((size_t)(hi - lo));
+    if (!d) return nullptr;
+    if (hi > lo) hipMemcpyAsync(d, host + lo, sizeof(int) * (size_t)(hi - lo), hipMemcpyHostToDevice, D.s);
+    return d - lo;
+  };
+  const SaHost& sa = hc.sa;
+  const HostLevel& Hc = hc.Hc;
+  const int nc = hc.nc;
+  o.nc = nc;
+  o.smooth = hc.smooth;
+  o.filtered = sa.filtered;
+  o.agg = keep(hc.agg);
+  o.mem_ptr = keep(hc.mem_ptr);
+  o.mem = keep(hc.mem);
+  o.nslot_c = Hc.nslot;
+  o.c_rowptr = keep(Hc.rowptr);
+  o.c_row = keep(Hc.row);
+  o.c_col = keep(Hc.col);
+  std::vector<int> t_pos, t_row, t_col, t_idx, t_ptr;   // row-owner level 0: the rank's column order (live until the synchronisation)
+  if (!hc.smooth) {
+    o.gal_src = keep(hc.order);
+    o.gal_tgt = keep(hc.tgt);
+    o.gal_cptr = temp(hc.cptr);
+  } else {
+    if (own && !sa.lists_on_device) {
+      o.err = "amg_create: the row-owner mode needs the device-made product lists (SGO_AMG_LISTS=host is single-GPU only)";
+      return false;
+    }
+    const int r0 = own ? own->row0 : 0, r1 = own ? own->row1 : n;
+    o.local = own != nullptr;
+    o.np = (int)sa.p_row.size();
+    o.e_lo = sa.p_rowptr[r0];
+    o.e_hi = sa.p_rowptr[r1];
+    o.v_lo = sa.val_rowptr[r0];
+    o.nval = sa.val_rowptr[r1] - o.v_lo;
+    o.nap = sa.nap;
+    o.f_lo = own ? sa.ap_rowptr[r0] : 0;
+    o.f_hi = own ? sa.ap_rowptr[r1] : sa.nap;
+    o.n_ap_prod = sa.n_ap_prod;
+    o.n_rap_prod = sa.n_rap_prod;
+    if (sa.filtered) o.strong = keep(sa.strong);
+    o.p_rowptr = keep(sa.p_rowptr);
+    o.p_row = keep(sa.p_row);
+    o.p_col = keep(sa.p_col);
+    o.val_ptr = temp(sa.val_ptr);
+    o.val_src = range(sa.val_src.p, o.v_lo, o.v_lo + o.nval);
+    o.val_tgt = range(sa.val_tgt.p, o.v_lo, o.v_lo + o.nval);
+    if (own) {
+      // this rank's rows' entries in column order (what the restriction streams and what P^T A P is listed from)
+      t_pos.assign((size_t)(o.e_hi - o.e_lo), 0);
+      t_ptr.assign((size_t)nc + 1, 0);
+      for (int a = 0; a < nc; ++a) {
+        for (int t = sa.t_ptr[a]; t < sa.t_ptr[a + 1]; ++t) {
+          const int i = sa.t_row[t];
+          if (i < r0 || i >= r1) continue;
+          const int e = sa.t_idx[t];
+          t_pos[(size_t)(e - o.e_lo)] = (int)t_row.size();
+          t_row.push_back(i);
+          t_col.push_back(a);
+          t_idx.push_back(e);
+        }
+        t_ptr[(size_t)a + 1] = (int)t_row.size();
+      }
+      o.t_pos = range(t_pos.data() - o.e_lo, o.e_lo, o.e_hi);
+      o.t_row = keep(t_row);
+      o.t_col = keep(t_col);
+      o.t_ptr = temp(t_ptr);
+      o.t_idx = temp(t_idx);
+    } else {
+      o.t_pos = keep(sa.t_pos);
+      o.t_row = keep(sa.t_row);
+      o.t_col = keep(sa.t_col);
+      o.t_ptr = temp(sa.t_ptr);
+      if (sa.lists_on_device) o.t_idx = temp(sa.t_idx);
+    }
+    if (sa.lists_on_device) {
+      o.ap_rowptr = temp(sa.ap_rowptr);
+      o.ap_col = range(sa.ap_col.p, o.f_lo, o.f_hi);
+      o.ap_row = range(sa.ap_row.p, o.f_lo, o.f_hi);
+    } else {   // SGO_AMG_LISTS=host: the host's lists, ready-made
+      const UVec* a[2] = {&sa.ap_a, &sa.rap_a};
+      const UVec* b[2] = {&sa.ap_b, &sa.rap_b};
+      const UVec* tgt[2] = {&sa.ap_tgt, &sa.rap_tgt};
+      const std::vector<int>* ptr[2] = {&sa.ap_ptr, &sa.rap_ptr};
+      for (int w = 0; w < 2; ++w) {
+        o.lists[w].a = keep(*a[w]);
+        o.lists[w].b = keep(*b[w]);
+        o.lists[w].tgt = keep(*tgt[w]);
+        o.lists[w].ptr = temp(*ptr[w]);
+      }
+    }
+    o.rap_mirror = keep(sa.rap_mirror);
+  }
+  if (!D.ok) {
+    o.err = "amg_create: out of device memory";
+    return false;
+  }
+  if (!D.sync()) {
+    o.err = "amg_create: upload failed";
+    return false;
+  }
+  return true;
+}
+
+// The one level assembler: a coarsening step's DevCoarse, whichever producer made it, into the transfer data of lv[l] -- P and its
+// streamed fp32 copies, the folded cycle's bookkeeping, the product lists, every wave-group list of the level in one batch, the long
+// columns -- and the structure of the next level lv[l + 1].  Returns the failure's message, empty on success.
+std::string assemble_level(Amg* m, DevSetup& D, int l, const DevCoarse& dc) {
+  hipStream_t s = D.s;
+  const std::string oom = "amg_create: out of device memory";
+  AmgLevel& L = m->lv[l];
+  const int n = L.A.n, nc = dc.nc;
+  const int r0 = dc.local ? m->halo->row0 : 0, r1 = dc.local ? m->halo->row1 : n;   // the rows whose entries are held
+  GroupBatch gb;
+  L.nc = nc;
+  L.agg = dc.agg;
+  L.mem_ptr = dc.mem_ptr;
+  L.mem = dc.mem;
+  L.d = D.alloc<double>(2 * (size_t)n);
+  AmgLevel C;
+  C.A.n = nc;
+  C.A.nslot = dc.nslot_c;
+  C.A.row = dc.c_row;
+  C.A.col = dc.c_col;
+  C.A.rowptr = dc.c_rowptr;
+  C.A.blk = D.alloc<double>(9 * (size_t)dc.nslot_c);
+  C.A.dinv = D.alloc<double>(6 * (size_t)nc);
+  C.pos = D.alloc<double>(2 * (size_t)nc);
+  if (!D.ok) return oom;
+  gb.add(G_MEM, dc.mem_ptr, nc, n);
+  gb.add(G_C, dc.c_rowptr, nc, dc.nslot_c);
+  bool fold_here = false;
+  int *t_ranges = nullptr, *st_ranges = nullptr;
+  if (dc.smooth) {
+    PDev& P = L.P;
+    L.smoothed = true;
+    const size_t ne = (size_t)(dc.e_hi - dc.e_lo), nf = (size_t)(dc.f_hi - dc.f_lo);   // entries of P and of A P held
+    P.local_lists = dc.local;
+    if (dc.filtered) {
+      P.dF = D.alloc<double>(9 * (size_t)n);
+      P.dinvF = D.alloc<double>(9 * (size_t)n);
+      P.strong = dc.strong;
+      gb.add(G_F, L.A.rowptr, n, L.A.nslot);
+    }
+    P.np = dc.np;
+    P.stream_nt = ne >= 200000 ? 1 : 0;   // 2 x 72 B per block streamed per cycle: below ~30 MB it may stay cached
+    P.rowptr = dc.p_rowptr;
+    P.row = dc.p_row;
+    P.col = dc.p_col;
+    P.blk = D.alloc<double>(9 * (size_t)dc.np);
+    P.val.n = dc.nval;
+    P.val.a = dc.val_src;
+    P.val.tgt = dc.val_tgt;
+    P.t_pos = dc.t_pos;
+    P.t_row = dc.t_row;
+    P.t_col = dc.t_col;
+    P.r_n = P.t_n = (int)ne;
+    float* rb = D.alloc<float>(9 * ne + 4);
+    float* tb = D.alloc<float>(9 * ne + 4);
+    P.nap = dc.nap;
+    double* ab = D.alloc<double>(9 * nf);
+    if (!D.ok) return oom;
+    P.r_blk = rb - 4 * (size_t)dc.e_lo;   // row order, addressed by global entry numbers
+    P.r_blk8 = rb + 8 * ne - dc.e_lo;
+    P.t_blk = tb;                         // column order, addressed by the positions held
+    P.t_blk8 = tb + 8 * ne;
+    P.apblk = ab - 9 * (size_t)dc.f_lo;
+    P.rap_mirror = dc.rap_mirror;
+    gb.add(G_VAL, dc.val_ptr + dc.e_lo, (int)ne, dc.v_lo + dc.nval);
+    gb.add(G_R, dc.p_rowptr + r0, r1 - r0, dc.e_hi);
+    gb.add(G_T, dc.t_ptr, nc, (int)ne);
+    if (l == 0) m->level0_bytes += (long long)(72 * (size_t)dc.np + 72 * ne + 72 * nf + 8 * (size_t)dc.nval + 12 * ne + 8 * nf);
+    // (Level 0 is folded only where it is itself launch-bound: P~ has the pattern of A P, twice the entries of P, and on large graphs
+    // streaming it twice per cycle costs what the saved launch and pass bring -- C4: restriction + prolongation 14 + 20 us with P~
+    // against 11 + 9 us with P.  Multi-GPU row-owner runs keep level 0 unfolded as well.)
+    fold_here = m->cfg.fold && nf > 0 && (l > 0 || (!m->halo && n <= m->cfg.fold0_rows));
+    if (fold_here) {
+      // ---- folded cycle: pattern bookkeeping of P~ (the pattern of A P) -- which entry of P sits at the same place, the column order (a
+      // device radix sort of (column, row-major rank) keys), its wave groups and long columns -- and the two streamed fp32 copies
+      FoldDev& Fd = L.F;
+      Fd.f_lo = dc.f_lo;
+      Fd.f_hi = dc.f_hi;
+      Fd.row = dc.ap_row;
+      Fd.col = dc.ap_col;
+      int* a2p = D.alloc<int>(nf);
+      int* stp = D.alloc<int>(nf);
+      u64* keys = D.talloc<u64>(nf);
+      u64* sorted = D.talloc<u64>(nf);
+      int bits = 33;
+      while (bits < 64 && (1ull << (bits - 32)) <= (u64)nc) ++bits;
+      int* st_row = D.alloc<int>(nf);
+      int* st_col = D.alloc<int>(nf);
+      int* st_ptr = D.alloc<int>((size_t)nc + 1);
+      float* sb = D.alloc<float>(9 * nf + 4);
+      float* sbt = D.alloc<float>(9 * nf + 4);
+      if (!D.ok) return oom;
+      Fd.ap2p = a2p - dc.f_lo;
+      Fd.st_pos = stp - dc.f_lo;
+      SGO_LAUNCH(k_fold_match, dim3(grid_for((long long)nf, kBlock)), dim3(kBlock), 0, s, Fd, (const int*)P.rowptr, (const int*)P.col, keys);
+      if (!D.sort(keys, sorted, nf, bits)) return "amg_create: device sort failed";
+      SGO_LAUNCH(k_fold_unpack, dim3(grid_for((long long)nf, kBlock)), dim3(kBlock), 0, s, Fd, (const u64*)sorted, st_row, st_col);
+      SGO_LAUNCH(k_fold_colptr, dim3(grid_for((long long)nc + 1, kBlock)), dim3(kBlock), 0, s, (const u64*)sorted, (int)nf, nc, st_ptr);
+      gb.add(G_ST, st_ptr, nc, (int)nf);
+      gb.add(G_PSR, dc.ap_rowptr + r0, r1 - r0, dc.f_hi);
+      PDev& PS = L.PS;
+      PS = PDev();
+      PS.np = (int)nf;
+      PS.stream_nt = nf >= 200000 ? 1 : 0;
+      PS.row = dc.ap_row;
+      PS.col = dc.ap_col;
+      PS.r_n = PS.t_n = (int)nf;
+      PS.r_blk = sb - 4 * (size_t)dc.f_lo;
+      PS.r_blk8 = sb + 8 * nf - dc.f_lo;
+      PS.t_blk = sbt;
+      PS.t_blk8 = sbt + 8 * nf;
+      PS.t_row = st_row;
+      PS.t_col = st_col;
+      if (l > 0) {
+        // levels >= 1: the slots of A and the entries of P~ of every row as one list (k_up_fold)
+        const int un = L.A.nslot + (int)nf;
+        int* u_ptr = D.alloc<int>((size_t)n + 1);
+        int* u_row = D.alloc<int>((size_t)un);
+        int* u_idx = D.alloc<int>((size_t)un);
+        int* u_col = D.alloc<int>((size_t)un);
+        if (!D.ok) return oom;
+        SGO_LAUNCH(k_u_ptr, dim3(grid_for((long long)n + 1, kBlock)), dim3(kBlock), 0, s, n, (const int*)L.A.rowptr, (const int*)dc.ap_rowptr, u_ptr);
+        SGO_LAUNCH(k_u_fill, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, s, n, (const int*)L.A.rowptr, (const int*)L.A.col, (const int*)dc.ap_rowptr,
+                   (const int*)dc.ap_col, (const int*)u_ptr, u_row, u_idx, u_col);
+        UpDev& U = L.U;
+        U.n = un;
+        U.row = u_row;
+        U.idx = u_idx;
+        U.col = u_col;
+        gb.add(G_U, u_ptr, n, un);
+      }
+      if (l == 0) m->level0_bytes += (long long)(72 * nf + 28 * nf);
+    }
+    char line[160];
+    std::snprintf(line, sizeof line, "(P %d%s, AP %d blocks; %d + %d products) ", P.np, dc.filtered ? " filtered" : "", P.nap, (int)dc.n_ap_prod,
+                  (int)dc.n_rap_prod);
+    m->desc += line;
+    // ---- product lists of A P and P^T A P
+    ProdMap* maps[2] = {&P.ap, &P.rap};
+    const long long nprod[2] = {dc.n_ap_prod, dc.n_rap_prod};
+    const int nseg[2] = {(int)nf, dc.nslot_c};
+    if (dc.lists[0].a) {   // ready-made: grouped with the level's batch
+      for (int w = 0; w < 2; ++w) {
+        maps[w]->n = (int)nprod[w];
+        maps[w]->a = dc.lists[w].a;
+        maps[w]->b = dc.lists[w].b;
+        maps[w]->tgt = dc.lists[w].tgt;
+        gb.add(w == 0 ? G_APL : G_RAPL, dc.lists[w].ptr, nseg[w], (int)nprod[w]);
+      }
+    } else {
+      // from the patterns: count per target, prefix sum, fill (A P, then P^T A P); both lists' totals behind one synchronisation
+      ApPattern ap;
+      ap.ap_row = dc.ap_row;
+      ap.ap_col = dc.ap_col;
+      ap.ap_rowptr = dc.ap_rowptr;
+      ap.f_lo = dc.f_lo;
+      ap.nap = dc.f_hi;
+      int* ptrs[2] = {nullptr, nullptr};   // [nseg + 1] each, from the first target held
+      for (int w = 0; w < 2; ++w) {
+        ptrs[w] = D.talloc<int>((size_t)nseg[w] + 1);
+        int* sums = D.talloc<int>((size_t)nseg[w] / kScanChunk + 3);
+        if (!D.ok) return oom;
+        int* ptr = w == 0 ? ptrs[w] - dc.f_lo : ptrs[w];   // addressed by global target numbers
+        int *la = nullptr, *lb = nullptr, *lt = nullptr;
+        const dim3 grid(grid_for(8LL * nseg[w], kBlock)), block(kBlock);   // eight lanes per target
+        if (w == 0)
+          SGO_LAUNCH((k_ap_list<false>), grid, block, 0, s, ap, (const int*)L.A.rowptr, (const int*)L.A.col, (const int*)P.rowptr,
+                     (const int*)P.col, ptr, la, lb, lt);
+        else
+          SGO_LAUNCH((k_rap_list<false>), grid, block, 0, s, dc.nslot_c, (const int*)C.A.row, (const int*)C.A.col,
+                     (const int*)dc.t_ptr, (const int*)P.t_row, (const int*)dc.t_idx, ap, ptr, la, lb, lt);
+        dev_scan_exclusive(s, ptrs[w], nseg[w], sums);
+      }
+      int totals[2] = {-1, -1};
+      D.read2(ptrs[0] + nseg[0], ptrs[1] + nseg[1], &totals[0], &totals[1]);
+      if (!D.ok) return "amg_create: product-list kernels failed";
+      for (int w = 0; w < 2; ++w) {
+        const int total = totals[w];
+        // (whole ranges: exactly the patterns' count; a rank's own rows: at most that)
+        if ((!dc.local && total != nprod[w]) || total < 0 || total > nprod[w])
+          return "amg_create: internal error (device product lists: " + std::to_string(total) + " products, the patterns say " +
+                 std::to_string(nprod[w]) + ")";
+        int* la = D.alloc<int>((size_t)std::max(total, 1));
+        int* lb = D.alloc<int>((size_t)std::max(total, 1));
+        int* lt = D.alloc<int>((size_t)std::max(total, 1));
+        if (!D.ok) return oom;
+        int* ptr = w == 0 ? ptrs[w] - dc.f_lo : ptrs[w];
+        const dim3 grid(grid_for(8LL * nseg[w], kBlock)), block(kBlock);
+        if (w == 0)
+          SGO_LAUNCH((k_ap_list<true>), grid, block, 0, s, ap, (const int*)L.A.rowptr, (const int*)L.A.col, (const int*)P.rowptr,
+                     (const int*)P.col, ptr, la, lb, lt);
+        else
+          SGO_LAUNCH((k_rap_list<true>), grid, block, 0, s, dc.nslot_c, (const int*)C.A.row, (const int*)C.A.col,
+                     (const int*)dc.t_ptr, (const int*)P.t_row, (const int*)dc.t_idx, ap, ptr, la, lb, lt);
+        maps[w]->n = total;
+        maps[w]->a = la;
+        maps[w]->b = lb;
+        maps[w]->tgt = lt;
+        gb.add(w == 0 ? G_APL : G_RAPL, ptrs[w], nseg[w], total);
+        if (l == 0) m->level0_bytes += 12LL * total;   // (the lists made here: the level-0 bytes have never counted ready-made ones)
+      }
+    }
+  } else {
+    L.gal.n = L.A.nslot;
+    L.gal.src = dc.gal_src;
+    L.gal.tgt = dc.gal_tgt;
+    gb.add(G_GAL, dc.gal_cptr, dc.nslot_c, L.A.nslot);
+  }
+  // ---- every wave-group list of the level in one batch, then the long columns of the two column-ordered copies
+  if (!gb.run(D)) return oom;
+  L.mem_grp = gb.grp[G_MEM];
+  L.mem_ngrp = gb.ngrp[G_MEM];
+  C.A.grp = gb.grp[G_C];
+  C.A.ngrp = gb.ngrp[G_C];
+  if (dc.smooth) {
+    PDev& P = L.P;
+    P.val.grp = gb.grp[G_VAL];
+    P.val.ngrp = gb.ngrp[G_VAL];
+    P.r_grp = gb.grp[G_R];
+    P.r_ngrp = gb.ngrp[G_R];
+    P.t_grp = gb.grp[G_T];
+    P.t_ngrp = gb.ngrp[G_T];
+    if (dc.filtered) {
+      P.f_grp = gb.grp[G_F];
+      P.f_ngrp = gb.ngrp[G_F];
+    }
+    P.ap.grp = gb.grp[G_APL];
+    P.ap.ngrp = gb.ngrp[G_APL];
+    P.rap.grp = gb.grp[G_RAPL];
+    P.rap.ngrp = gb.ngrp[G_RAPL];
+    int* d_cnt = D.talloc<int>(2);
+    t_ranges = D.alloc<int>(2 * (size_t)std::max(P.t_ngrp, 1));
+    if (!D.ok) return oom;
+    hipMemsetAsync(d_cnt, 0, 2 * sizeof(int), s);
+    SGO_LAUNCH(k_long_groups, dim3(grid_for((long long)P.t_ngrp, kBlock)), dim3(kBlock), 0, s, (const int*)P.t_grp, P.t_ngrp, d_cnt, t_ranges);
+    if (fold_here) {
+      PDev& PS = L.PS;
+      PS.r_grp = gb.grp[G_PSR];
+      PS.r_ngrp = gb.ngrp[G_PSR];
+      PS.t_grp = gb.grp[G_ST];
+      PS.t_ngrp = gb.ngrp[G_ST];
+      if (l > 0) {
+        L.U.grp = gb.grp[G_U];
+        L.U.ngrp = gb.ngrp[G_U];
+      }
+      st_ranges = D.alloc<int>(2 * (size_t)std::max(PS.t_ngrp, 1));
+      if (!D.ok) return oom;
+      SGO_LAUNCH(k_long_groups, dim3(grid_for((long long)PS.t_ngrp, kBlock)), dim3(kBlock), 0, s, (const int*)PS.t_grp, PS.t_ngrp, d_cnt + 1, st_ranges);
+    }
+    int nl[2] = {0, 0};
+    D.read2(d_cnt, d_cnt + 1, &nl[0], &nl[1]);
+    if (!D.ok) return "amg_create: set-up kernels failed";
+    P.t_nlong = nl[0];
+    P.t_long = nl[0] ? t_ranges : nullptr;
+    if (fold_here) {
+      constexpr int kLongCap = 4096;   // a level with more long columns than this is not folded
+      L.PS.t_long = st_ranges;
+      L.PS.t_nlong = nl[1];
+      L.fold = nl[1] <= kLongCap;
+    }
+  } else {
+    L.gal.grp = gb.grp[G_GAL];
+    L.gal.ngrp = gb.ngrp[G_GAL];
+  }
+  m->lv.push_back(C);   // invalidates L
+  return std::string();
+}
+
+// Multi-GPU row-owner mode, level 0, between its assembly and its first values: the entries of P in every rank's boundary rows -- what
+// A P of a neighbour's rows gathers from this rank's P -- and exchange buffers large enough for them.  nullptr or the failure's message.
+const char* boundary_entries(hipStream_t s, DevArena* pool, const AmgHalo& halo, const std::vector<int>& p_rowptr) {
+  std::vector<std::vector<int>> pe((size_t)halo.G);
+  int pemax = 1;
+  for (int q = 0; q < halo.G; ++q) {
+    for (int t = 0; t < halo.bmax; ++t) {
+      const int r = halo.bnd_host[(size_t)q * halo.bmax + t];
+      if (r < 0) break;
+      for (int e = p_rowptr[r]; e < p_rowptr[r + 1]; ++e) pe[q].push_back(e);
+    }
+    pemax = std::max(pemax, (int)pe[q].size());
+  }
+  std::vector<int> flat((size_t)halo.G * pemax, -1);
+  for (int q = 0; q < halo.G; ++q) std::copy(pe[q].begin(), pe[q].end(), flat.begin() + (size_t)q * pemax);
+  int* d_pe = dev_upload(pool, flat, s);
+  if (!d_pe || hipStreamSynchronize(s) != hipSuccess) return "amg_create: out of device memory";
+  halo.dev->pemax = pemax;
+  halo.dev->pent = d_pe;
+  if (halo.reserve && !halo.reserve(halo.user, (size_t)kHaloScalars + 9 * (size_t)pemax)) return "amg_create: out of device memory (exchange buffers)";
+  return nullptr;
+}
+
+// The first values of level l + 1 (its strengths need them): positions, centres and lever arms, the Galerkin operator, the diagonal
+// inverses.  No synchronisation: the next level's strengths are read behind its own, the hierarchy's last level behind amg_create's.
+void level_values(Amg* m, hipStream_t s, int l) {
+  AmgLevel& L = m->lv[l];
+  AmgLevel& C = m->lv[l + 1];
+  const int n = L.A.n, nc = C.A.n;
+  if (l == 0) SGO_LAUNCH(k_positions0, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, s, n, m->d_free_id, m->d_poses, L.pos);
+  SGO_LAUNCH(k_centres, dim3(grid_for(nc, kWavesPerBlock)), dim3(kBlock), 0, s, nc, L.mem_ptr, L.mem, L.pos, C.pos, L.d);
+  launch_coarse_operator(m, s, L, C, l == 0);
+  if (l + 1 < m->cfg.max_levels) SGO_LAUNCH(k_level_dinv, dim3(grid_for(C.A.n, kBlock)), dim3(kBlock), 0, s, C.A);
+}
+
+}  // namespace
+
 Amg* amg_create(hipStream_t s, const BsrDev& A0, const Sym0Dev& S0, const Tile0Dev& T0, const HostLevel& H0, const double* d_poses,
-                const int* d_free_id, const AmgConfig& cfg_in, const AmgProf& prof, std::string* err,
-                ChunkArena* scratch, DevArena* arena, AmgHostL0* pre0, const AmgHalo* halo) {
+                const int* d_free_id, const AmgConfig& cfg_in, const AmgProf& prof, std::string* err, ChunkArena* scratch, DevArena* arena,
+                DevArena* tmp_arena, AmgPatterns patterns, AmgHostL0* pre0, const AmgHalo* halo) {
   Amg* m = new Amg();
   if (halo) m->halo = halo->dev;
   m->pool = arena;
-  m->cfg = cfg_in;
   m->S0 = S0;
   m->T0 = T0;
   m->cfg = amg_effective_config(cfg_in, A0.n, A0.nslot);
+  const bool on_host = patterns == AmgPatterns::host;
+  if (!on_host) m->cfg.lists_on_device = true;   // (the device producer makes patterns only; folding stays as amg_effective_config decided)
   // With the smoothed prolongator a V-cycle needs ~1.4x the PCG iterations of the K-cycle (C4: 39 vs
   // 27) at less than half the launches per iteration: V is the default there, K for the tentative one.
   if (m->cfg.smooth) m->kdepth = 0;
@@ -2323,470 +2862,145 @@ Amg* amg_create(hipStream_t s, const BsrDev& A0, const Sym0Dev& S0, const Tile0D
     amg_destroy(m);
     return nullptr;
   };
-
-  HostLevel Hown;              // structure of the level being coarsened: H0 first, then the level built last
-  const HostLevel* Hp = &H0;
-
+  if (halo && !on_host) return fail("amg_create: the row-owner mode needs the host patterns");
+  const bool verbose = std::getenv("SGO_VERBOSE") != nullptr;
+  auto ms_since = [](std::chrono::steady_clock::time_point t) {
+    return 1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t).count();
+  };
+  // level 0 made ahead on the set-up pipeline's helper thread: host_coarsen's whole result, or the aggregation alone
+  const bool pre0_full = pre0 && pre0->ready && !pre0->agg_only, pre0_agg = pre0 && pre0->ready && pre0->agg_only;
   AmgLevel L0;
   L0.A = A0;
   m->lv.push_back(L0);
   char line[160];
+  HostLevel Hown;   // structure of a level l > 0 that the host coarsens or aggregates: the host producer's, or copied back from the device
+  std::vector<double> h_w;
   for (int l = 0;; ++l) {
-    AmgLevel& L = m->lv[l];
-    const HostLevel& H = *Hp;
-    const int n = L.A.n, n3 = 3 * n;
-    L.spmv_grid = grid_for(L.A.ngrp, kWavesPerBlock);
-    std::snprintf(line, sizeof line, "L%d n=%d slots=%d; ", l, n, L.A.nslot);
+    const int n = m->lv[l].A.n;
+    std::snprintf(line, sizeof line, "L%d n=%d slots=%d; ", l, n, m->lv[l].A.nslot);
     m->desc += line;
-    L.xs = dev_alloc<double>(m->pool, n3);
-    L.rs = dev_alloc<double>(m->pool, n3);
-    L.tR = dev_alloc<double>(m->pool, n3);
-    if (!L.pos) L.pos = dev_alloc<double>(m->pool, 2 * (size_t)n);
-    if (l > 0) {
-      L.bk = dev_alloc<double>(m->pool, n3);
-      L.xk = dev_alloc<double>(m->pool, n3);
-      L.z1 = dev_alloc<double>(m->pool, n3);
-      L.z2 = dev_alloc<double>(m->pool, n3);
-      L.q = dev_alloc<double>(m->pool, n3);
-      L.bk2 = dev_alloc<double>(m->pool, n3);
-      L.p2 = dev_alloc<double>(m->pool, n3);
-      L.q2 = dev_alloc<double>(m->pool, n3);
-      L.pA = dev_alloc<double>(m->pool, 2 * (size_t)kMaxPartials);
-      L.pB = dev_alloc<double>(m->pool, 2 * (size_t)kMaxPartials);
-      L.pC = dev_alloc<double>(m->pool, 2 * (size_t)kMaxPartials);
-      if (!L.pC || !L.bk2 || !L.p2 || !L.q2) return fail("amg_create: out of device memory");
-      hipMemsetAsync(L.pA, 0, sizeof(double) * 2 * kMaxPartials, s);
-      hipMemsetAsync(L.pB, 0, sizeof(double) * 2 * kMaxPartials, s);
-      hipMemsetAsync(L.pC, 0, sizeof(double) * 2 * kMaxPartials, s);
-    }
-    if (!L.xs || !L.rs || !L.pos) return fail("amg_create: out of device memory");
+    if (!alloc_work(m, s, l)) return fail("amg_create: out of device memory");
     if (n <= m->cfg.coarsest_nodes || l + 1 >= m->cfg.max_levels) break;
 
-    // strength of connection from the current values of this level
-    std::vector<double> w;
-    if (l == 0 && halo && !(pre0 && pre0->ready)) {
-      if (!halo->w0 || (int)halo->w0->size() != H.nslot) return fail("amg_create: row-owner mode needs the level-0 strength weights");
-      w = *halo->w0;
-    } else if (!(l == 0 && pre0 && pre0->ready)) {
-      w.resize(H.nslot);
-      double* d_w = dev_alloc<double>(m->pool, (size_t)std::max(H.nslot, 1));   // (stays in the arena until its rewind)
-      if (!d_w) return fail("amg_create: out of device memory");
-      SGO_LAUNCH(k_block_norms, dim3(grid_for(H.nslot, kBlock)), dim3(kBlock), 0, s, L.A, d_w);
-      hipMemcpyAsync(w.data(), d_w, sizeof(double) * H.nslot, hipMemcpyDeviceToHost, s);
-      const hipError_t e = hipStreamSynchronize(s);
-      if (e != hipSuccess) return fail("amg_create: strength kernel failed");
-    }
+    AmgLevel& L = m->lv[l];
+    const HostLevel& H = l == 0 ? H0 : Hown;
+    const auto tL = std::chrono::steady_clock::now();
+    tmp_arena->rewind();   // (the previous level's temporaries: every later user is queued behind their last kernel)
+    DevSetup D{s, m->pool, tmp_arena};
+    DevCoarse dc;
     HostCoarse hc_own;
-    HostCoarse* hcp = &hc_own;
-    if (m->cfg.keep_agg && l < (int)m->cfg.keep_agg->agg.size() && (int)m->cfg.keep_agg->agg[l].size() == n && !(l == 0 && pre0 && pre0->ready)) {
-      hc_own.agg = m->cfg.keep_agg->agg[l];
-      hc_own.visit_c = m->cfg.keep_agg->visit_c[l];
-      hc_own.nc = m->cfg.keep_agg->nc[l];
-      hc_own.reuse_agg = true;
-    }
-    if (l == 0 && pre0 && pre0->ready) {
-      hcp = &pre0->hc;   // made ahead on the helper thread, from the same structure and the strengths at the same poses
-    } else {
-      host_coarsen(H, w, m->cfg, l, scratch, hc_own);
-    }
-    HostCoarse& hc = *hcp;
-    if (!hc.err.empty()) return fail(hc.err);
-    if (hc.stop) break;
-    const int nc = hc.nc;
-    const bool smooth = hc.smooth;
-    std::vector<int>&agg = hc.agg, &mem_ptr = hc.mem_ptr, &mem = hc.mem, &order = hc.order, &tgt = hc.tgt, &grp_g = hc.grp_g,
-                    &grp_c = hc.grp_c, &visit_c = hc.visit_c;
-    SaHost& sa = hc.sa;
-    HostLevel& Hc = hc.Hc;
-    auto ms_since = [](std::chrono::steady_clock::time_point t) {
-      return 1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t).count();
-    };
-    if (std::getenv("SGO_VERBOSE"))
-      std::fprintf(stderr, "[sgo] amg level %d: host aggregation + coarse structure %.1f ms (aggregate %.1f, sort %.1f; n=%d -> %d)%s\n",
-                   l, hc.t_all, hc.t_agg, hc.t_sort, n, nc, hcp == &hc_own ? "" : " [made ahead on the helper thread]");
-
-    // upload transfer data of level l and the structure of level l+1
-    const auto tU = std::chrono::steady_clock::now();
-    L.nc = nc;
-    m->kept.agg.push_back(agg);
-    m->kept.visit_c.push_back(visit_c);
-    m->kept.nc.push_back(nc);
-    L.agg = dev_upload(m->pool, agg, s);
-    L.mem_ptr = dev_upload(m->pool, mem_ptr, s);
-    L.mem = dev_upload(m->pool, mem, s);
-    std::vector<int> grp_m = make_groups(mem_ptr);
-    L.mem_grp = dev_upload(m->pool, grp_m, s);
-    L.mem_ngrp = (int)grp_m.size() - 1;
-    L.d = dev_alloc<double>(m->pool, 2 * (size_t)n);
-    struct { int *ap_rowptr, *ap_col, *ap_row, *t_ptr, *t_idx; } l0_dev = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    struct { bool own; int F0, F1; } l0_own = {false, 0, 0};
-    if (smooth) {
-      PDev& P = L.P;
-      L.smoothed = true;
-      // Row-owner mode (level 0): the value lists, the streamed copies of P, the blocks of A P and the product lists are made
-      // for this rank's rows only -- allocated for the rank's range of entries, base pointers shifted so that global entry
-      // numbers address them; the patterns (a few integers per entry) and the gathered copy P.blk stay whole.
-      const bool own = l == 0 && halo != nullptr;
-      if (own && !sa.lists_on_device) return fail("amg_create: the row-owner mode needs the device-made product lists (SGO_AMG_LISTS=host is single-GPU only)");
-      const int orow0 = own ? halo->dev->row0 : 0, orow1 = own ? halo->dev->row1 : n;
-      const size_t E0 = (size_t)sa.p_rowptr[orow0], E1 = (size_t)sa.p_rowptr[orow1], npl = E1 - E0;   // entries of P held
-      const size_t V0 = (size_t)sa.val_rowptr[orow0], V1 = (size_t)sa.val_rowptr[orow1];              // their value products (kept slots)
-      auto up_range = [&](const int* host, size_t lo, size_t hi) -> int* {   // device copy of host[lo, hi), addressed by global numbers
-        int* d = dev_alloc<int>(m->pool, hi - lo);
-        if (d && hi > lo) hipMemcpyAsync(d, host + lo, (hi - lo) * sizeof(int), hipMemcpyHostToDevice, s);
-        return d ? d - lo : nullptr;
-      };
-      P.local_lists = own;
-      if (sa.filtered) {
-        unsigned char* d_strong = (unsigned char*)m->pool->take(std::max<size_t>(sa.strong.size(), 1));
-        P.dF = dev_alloc<double>(m->pool, 9 * (size_t)n);
-        P.dinvF = dev_alloc<double>(m->pool, 9 * (size_t)n);
-        if (!d_strong || !P.dF || !P.dinvF) return fail("amg_create: out of device memory");
-        hipMemcpyAsync(d_strong, sa.strong.data(), sa.strong.size(), hipMemcpyHostToDevice, s);
-        P.strong = d_strong;
-        const std::vector<int> fg = make_groups(H.rowptr);
-        P.f_grp = dev_upload(m->pool, fg, s);
-        P.f_ngrp = (int)fg.size() - 1;
-        if (!P.f_grp || hipStreamSynchronize(s) != hipSuccess) return fail("amg_create: out of device memory");   // (fg is a local)
-      }
-      P.np = (int)sa.p_row.size();
-      P.stream_nt = npl >= 200000 ? 1 : 0;   // 2 x 72 B per block streamed per cycle: below ~30 MB it may stay cached
-      P.rowptr = dev_upload(m->pool, sa.p_rowptr, s);
-      P.row = dev_upload(m->pool, sa.p_row, s);
-      P.col = dev_upload(m->pool, sa.p_col, s);
-      P.blk = dev_alloc<double>(m->pool, 9 * (size_t)P.np);
-      P.val.n = (int)(V1 - V0);
-      P.val.a = up_range(sa.val_src.data(), V0, V1);
-      P.val.tgt = up_range(sa.val_tgt.data(), V0, V1);
-      std::vector<int> val_grp_l, r_grp_l, t_pos_l, t_row_l, t_col_l, t_idx_l, t_ptr_l, t_grp_l;   // (live until the stream is synchronised below)
-      if (own) {
-        std::vector<int> vptr;
-        for (size_t q = V0; q < V1; ++q)
-          if (q == V0 || sa.val_tgt[q] != sa.val_tgt[q - 1]) vptr.push_back((int)q);
-        vptr.push_back((int)V1);
-        val_grp_l = make_groups(vptr);
-        r_grp_l = make_groups(std::vector<int>(sa.p_rowptr.begin() + orow0, sa.p_rowptr.begin() + orow1 + 1));
-        // this rank's rows' entries in column order (what the restriction streams and what P^T A P is listed from)
-        t_pos_l.assign(npl, 0);
-        t_ptr_l.assign((size_t)nc + 1, 0);
-        t_row_l.reserve(npl);
-        t_col_l.reserve(npl);
-        t_idx_l.reserve(npl);
-        for (int a = 0; a < nc; ++a) {
-          for (int t = sa.t_ptr[a]; t < sa.t_ptr[a + 1]; ++t) {
-            const int i = sa.t_row[t];
-            if (i < orow0 || i >= orow1) continue;
-            const int e = sa.t_idx[t];
-            t_pos_l[(size_t)e - E0] = (int)t_row_l.size();
-            t_row_l.push_back(i);
-            t_col_l.push_back(a);
-            t_idx_l.push_back(e);
-          }
-          t_ptr_l[(size_t)a + 1] = (int)t_row_l.size();
-        }
-        t_grp_l = make_groups(t_ptr_l);
-      }
-      const std::vector<int>& val_grp = own ? val_grp_l : sa.val_grp;
-      const std::vector<int>& r_grp = own ? r_grp_l : sa.r_grp;
-      const std::vector<int>& t_grp = own ? t_grp_l : sa.t_grp;
-      P.val.grp = dev_upload(m->pool, val_grp, s);
-      P.val.ngrp = (int)val_grp.size() - 1;
-      P.r_grp = dev_upload(m->pool, r_grp, s);
-      P.r_ngrp = (int)r_grp.size() - 1;
-      P.t_pos = own ? up_range(t_pos_l.data() - E0, E0, E1) : dev_upload(m->pool, sa.t_pos, s);
-      P.t_row = dev_upload(m->pool, own ? t_row_l : sa.t_row, s);
-      P.t_col = dev_upload(m->pool, own ? t_col_l : sa.t_col, s);
-      P.r_n = P.t_n = (int)npl;
-      {
-        float* rb = dev_alloc<float>(m->pool, 9 * npl + 4);
-        float* tb = dev_alloc<float>(m->pool, 9 * npl + 4);
-        if (!rb || !tb) return fail("amg_create: out of device memory");
-        P.r_blk = rb - 4 * E0;            // row order, addressed by global entry numbers
-        P.r_blk8 = rb + 8 * npl - E0;
-        P.t_blk = tb;                     // column order, addressed by the rank's own positions
-        P.t_blk8 = tb + 8 * npl;
-      }
-      P.t_grp = dev_upload(m->pool, t_grp, s);
-      P.t_ngrp = (int)t_grp.size() - 1;
-      std::vector<int> t_long;   // (lives until the stream is synchronised below)
-      for (size_t g = 0; g + 1 < t_grp.size(); ++g)
-        if (t_grp[g + 1] - t_grp[g] > kLongColumn) {
-          t_long.push_back(t_grp[g]);
-          t_long.push_back(t_grp[g + 1]);
-        }
-      P.t_nlong = (int)t_long.size() / 2;
-      P.t_long = P.t_nlong ? dev_upload(m->pool, t_long, s) : nullptr;
-      if (P.t_nlong && !P.t_long) return fail("amg_create: out of device memory");
-      if (P.t_nlong && hipStreamSynchronize(s) != hipSuccess) return fail("amg_create: upload failed");
-      P.nap = sa.nap;
-      size_t F0 = 0, F1 = (size_t)sa.nap;
-      if (own) {
-        F0 = (size_t)sa.ap_rowptr[orow0];
-        F1 = (size_t)sa.ap_rowptr[orow1];
-      }
-      {
-        double* ab = dev_alloc<double>(m->pool, 9 * (F1 - F0));
-        if (!ab) return fail("amg_create: out of device memory");
-        P.apblk = ab - 9 * F0;
-      }
-      int *d_ap_rowptr = nullptr, *d_ap_col = nullptr, *d_ap_row = nullptr, *d_t_ptr = nullptr, *d_t_idx = nullptr;
-      if (sa.lists_on_device) {
-        // the patterns go up (12 B per A P entry instead of 12 B per product); the lists are made below, once the
-        // coarse structure is on the device too
-        d_ap_rowptr = dev_upload(m->pool, sa.ap_rowptr, s);
-        d_ap_col = up_range(sa.ap_col.data(), F0, F1);
-        d_ap_row = up_range(sa.ap_row.data(), F0, F1);
-        d_t_ptr = dev_upload(m->pool, own ? t_ptr_l : sa.t_ptr, s);
-        d_t_idx = dev_upload(m->pool, own ? t_idx_l : sa.t_idx, s);
-        if (!d_ap_rowptr || !d_ap_col || !d_ap_row || !d_t_ptr || !d_t_idx) return fail("amg_create: out of device memory");
-        P.ap.n = (int)sa.n_ap_prod;
-        P.rap.n = (int)sa.n_rap_prod;
+    HostCoarse* hc = nullptr;            // the host producer's result
+    std::vector<int> h_agg, h_visit_c;   // host copies of the aggregates (AmgConfig::keep_agg) and of the next level's visiting order
+    double t_host_agg = 0.0;
+    const bool kept = m->cfg.keep_agg && l < (int)m->cfg.keep_agg->agg.size() && (int)m->cfg.keep_agg->agg[l].size() == n;
+    if (on_host) {
+      if (l == 0 && pre0_full) {
+        hc = &pre0->hc;   // made ahead on the helper thread, from the same structure and the strengths at the same poses
       } else {
-      P.ap.n = (int)sa.ap_a.size();
-      P.ap.a = dev_upload(m->pool, sa.ap_a, s);
-      P.ap.b = dev_upload(m->pool, sa.ap_b, s);
-      P.ap.tgt = dev_upload(m->pool, sa.ap_tgt, s);
-      P.ap.grp = dev_upload(m->pool, sa.ap_grp, s);
-      P.ap.ngrp = (int)sa.ap_grp.size() - 1;
-      P.rap.n = (int)sa.rap_a.size();
-      P.rap.a = dev_upload(m->pool, sa.rap_a, s);
-      P.rap.b = dev_upload(m->pool, sa.rap_b, s);
-      P.rap.tgt = dev_upload(m->pool, sa.rap_tgt, s);
-      P.rap.grp = dev_upload(m->pool, sa.rap_grp, s);
-      P.rap.ngrp = (int)sa.rap_grp.size() - 1;
-      }
-      P.rap_mirror = dev_upload(m->pool, sa.rap_mirror, s);
-      if (!P.rowptr || !P.row || !P.col || !P.blk || !P.val.a || !P.val.tgt || !P.val.grp || !P.r_grp || !P.t_pos || !P.t_row || !P.t_col || !P.t_grp ||
-          (!sa.lists_on_device && (!P.ap.a || !P.ap.b || !P.ap.tgt || !P.ap.grp || !P.rap.a || !P.rap.b || !P.rap.tgt || !P.rap.grp)))
-        return fail("amg_create: out of device memory");
-      if (own && hipStreamSynchronize(s) != hipSuccess) return fail("amg_create: upload failed");   // (the rank-local host lists die with this scope)
-      if (l == 0) m->level0_bytes += (long long)(72 * (size_t)P.np + 72 * npl + 72 * (F1 - F0) + 8 * (V1 - V0) + 12 * npl + 8 * (F1 - F0));
-      l0_own = {own, (int)F0, (int)F1};
-      l0_dev = {d_ap_rowptr, d_ap_col, d_ap_row, d_t_ptr, d_t_idx};
-      // (Level 0 is folded only where it is itself launch-bound: P~ has the pattern of A P, twice the entries of P, and on
-      // large graphs streaming it twice per cycle costs what the saved launch and pass bring -- C4: restriction + prolongation
-      // 14 + 20 us with P~ against 11 + 9 us with P.  Multi-GPU runs keep level 0 unfolded as well.)
-      if (m->cfg.fold && sa.lists_on_device && F1 > F0 && (l > 0 || (!halo && n <= m->cfg.fold0_rows))) {
-        // ---- folded cycle: pattern bookkeeping of P~ (the pattern of A P) -- which entry of P sits at the same place, the
-        // column order (a device radix sort of (column, row-major rank) keys instead of a host counting sort), its wave
-        // groups and long columns -- and the two streamed fp32 copies
-        const size_t nf = F1 - F0;
-        FoldDev& Fd = L.F;
-        Fd.f_lo = (int)F0;
-        Fd.f_hi = (int)F1;
-        Fd.row = d_ap_row;
-        Fd.col = d_ap_col;
-        int* a2p = dev_alloc<int>(m->pool, nf);
-        int* stp = dev_alloc<int>(m->pool, nf);
-        unsigned long long* keys = dev_alloc<unsigned long long>(m->pool, nf);
-        unsigned long long* sorted = dev_alloc<unsigned long long>(m->pool, nf);
-        int bits = 33;
-        while (bits < 64 && (1ull << (bits - 32)) <= (unsigned long long)nc) ++bits;
-        const size_t tmp_bytes = sort_u64_temp_bytes(nf, bits);
-        void* tmp = tmp_bytes ? m->pool->take(tmp_bytes) : nullptr;
-        int* st_row = dev_alloc<int>(m->pool, nf);
-        int* st_col = dev_alloc<int>(m->pool, nf);
-        int* st_ptr = dev_alloc<int>(m->pool, (size_t)nc + 1);
-        constexpr int kLongCap = 4096;
-        int* d_cnt = dev_alloc<int>(m->pool, 1);
-        int* ranges = dev_alloc<int>(m->pool, 2 * (size_t)kLongCap);
-        float* sb = dev_alloc<float>(m->pool, 9 * nf + 4);
-        float* tb = dev_alloc<float>(m->pool, 9 * nf + 4);
-        if (!a2p || !stp || !keys || !sorted || !tmp || !st_row || !st_col || !st_ptr || !d_cnt || !ranges || !sb || !tb)
-          return fail("amg_create: out of device memory");
-        Fd.ap2p = a2p - F0;
-        Fd.st_pos = stp - F0;
-        SGO_LAUNCH(k_fold_match, dim3(grid_for((long long)nf, kBlock)), dim3(kBlock), 0, s, Fd, (const int*)P.rowptr, (const int*)P.col, keys);
-        if (!sort_u64(tmp, tmp_bytes, (const uint64_t*)keys, (uint64_t*)sorted, nf, bits, s)) return fail("amg_create: device sort failed");
-        SGO_LAUNCH(k_fold_unpack, dim3(grid_for((long long)nf, kBlock)), dim3(kBlock), 0, s, Fd, (const unsigned long long*)sorted, st_row, st_col);
-        SGO_LAUNCH(k_fold_colptr, dim3(grid_for((long long)nc + 1, kBlock)), dim3(kBlock), 0, s, (const unsigned long long*)sorted, (int)nf, nc, st_ptr);
-        int st_ngrp = 0;
-        int* st_grp = dev_make_groups(s, m->pool, st_ptr, nc, (int)nf, &st_ngrp);
-        if (!st_grp) return fail("amg_create: out of device memory");
-        hipMemsetAsync(d_cnt, 0, sizeof(int), s);
-        SGO_LAUNCH(k_fold_long, dim3(grid_for((long long)st_ngrp, kBlock)), dim3(kBlock), 0, s, (const int*)st_grp, st_ngrp, d_cnt, ranges, kLongCap);
-        int nlong = 0;
-        if (hipMemcpyAsync(&nlong, d_cnt, sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
-          return fail("amg_create: folded-transfer kernels failed");
-        std::vector<int> s_grp = make_groups(std::vector<int>(sa.ap_rowptr.begin() + orow0, sa.ap_rowptr.begin() + orow1 + 1));
-        PDev& PS = L.PS;
-        PS = PDev();
-        PS.np = (int)nf;
-        PS.stream_nt = nf >= 200000 ? 1 : 0;
-        PS.row = d_ap_row;
-        PS.col = d_ap_col;
-        PS.r_n = PS.t_n = (int)nf;
-        PS.r_blk = sb - 4 * F0;
-        PS.r_blk8 = sb + 8 * nf - F0;
-        PS.t_blk = tb;
-        PS.t_blk8 = tb + 8 * nf;
-        PS.r_grp = dev_upload(m->pool, s_grp, s);
-        PS.r_ngrp = (int)s_grp.size() - 1;
-        PS.t_row = st_row;
-        PS.t_col = st_col;
-        PS.t_grp = st_grp;
-        PS.t_ngrp = st_ngrp;
-        PS.t_long = ranges;
-        PS.t_nlong = nlong;
-        if (!PS.r_grp) return fail("amg_create: out of device memory");
-        if (l > 0) {
-          // levels >= 1: the slots of A and the entries of P~ of every row as one list (k_up_fold)
-          std::vector<int> u_ptr((size_t)n + 1, 0), u_row, u_idx, u_col;
-          for (int i = 0; i < n; ++i) u_ptr[(size_t)i + 1] = u_ptr[i] + (H.rowptr[i + 1] - H.rowptr[i]) + (sa.ap_rowptr[i + 1] - sa.ap_rowptr[i]);
-          u_row.resize((size_t)u_ptr[n]);
-          u_idx.resize((size_t)u_ptr[n]);
-          u_col.resize((size_t)u_ptr[n]);
-          for (int i = 0; i < n; ++i) {
-            int q = u_ptr[i];
-            for (int k = H.rowptr[i]; k < H.rowptr[i + 1]; ++k, ++q) {
-              u_row[q] = i;
-              u_idx[q] = k;
-              u_col[q] = H.col[k];
-            }
-            for (int f = sa.ap_rowptr[i]; f < sa.ap_rowptr[i + 1]; ++f, ++q) {
-              u_row[q] = i;
-              u_idx[q] = ~f;
-              u_col[q] = sa.ap_col[f];
-            }
-          }
-          std::vector<int> u_grp = make_groups(u_ptr);
-          UpDev& U = L.U;
-          U.n = u_ptr[n];
-          U.row = dev_upload(m->pool, u_row, s);
-          U.idx = dev_upload(m->pool, u_idx, s);
-          U.col = dev_upload(m->pool, u_col, s);
-          U.grp = dev_upload(m->pool, u_grp, s);
-          U.ngrp = (int)u_grp.size() - 1;
-          if (!U.row || !U.idx || !U.col || !U.grp) return fail("amg_create: out of device memory");
+        // strength of connection from the current values of this level
+        std::vector<double> w;
+        if (l == 0 && halo) {
+          if (!halo->w0 || (int)halo->w0->size() != H.nslot) return fail("amg_create: row-owner mode needs the level-0 strength weights");
+          w = *halo->w0;
+        } else {
+          w.resize(H.nslot);
+          double* d_w = D.talloc<double>((size_t)std::max(H.nslot, 1));
+          if (!d_w) return fail("amg_create: out of device memory");
+          SGO_LAUNCH(k_block_norms, dim3(grid_for(H.nslot, kBlock)), dim3(kBlock), 0, s, L.A, d_w);
+          hipMemcpyAsync(w.data(), d_w, sizeof(double) * H.nslot, hipMemcpyDeviceToHost, s);
+          if (!D.sync()) return fail("amg_create: strength kernel failed");
         }
-        if (hipStreamSynchronize(s) != hipSuccess) return fail("amg_create: upload failed");   // (host lists of this scope)
-        L.fold = nlong <= kLongCap;
-        if (l == 0) m->level0_bytes += (long long)(72 * nf + 28 * nf);
-      }
-      if (l == 0 && halo) {
-        // the entries of P in every rank's boundary rows: what A P of a neighbour's rows gathers from this rank's P
-        std::vector<std::vector<int>> pe((size_t)halo->G);
-        int pemax = 1;
-        for (int q = 0; q < halo->G; ++q) {
-          for (int t = 0; t < halo->bmax; ++t) {
-            const int r = halo->bnd_host[(size_t)q * halo->bmax + t];
-            if (r < 0) break;
-            for (int e = sa.p_rowptr[r]; e < sa.p_rowptr[r + 1]; ++e) pe[q].push_back(e);
-          }
-          pemax = std::max(pemax, (int)pe[q].size());
+        if (kept) {
+          hc_own.agg = m->cfg.keep_agg->agg[l];
+          hc_own.visit_c = m->cfg.keep_agg->visit_c[l];
+          hc_own.nc = m->cfg.keep_agg->nc[l];
+          hc_own.reuse_agg = true;
         }
-        std::vector<int> flat((size_t)halo->G * pemax, -1);
-        for (int q = 0; q < halo->G; ++q) std::copy(pe[q].begin(), pe[q].end(), flat.begin() + (size_t)q * pemax);
-        int* d_pe = dev_upload(m->pool, flat, s);
-        if (!d_pe || hipStreamSynchronize(s) != hipSuccess) return fail("amg_create: out of device memory");
-        halo->dev->pemax = pemax;
-        halo->dev->pent = d_pe;
-        if (halo->reserve && !halo->reserve(halo->user, (size_t)kHaloScalars + 9 * (size_t)pemax)) return fail("amg_create: out of device memory (exchange buffers)");
+        host_coarsen(H, w, m->cfg, l, scratch, hc_own);
+        hc = &hc_own;
       }
-      std::snprintf(line, sizeof line, "(P %d%s, AP %d blocks; %d + %d products) ", P.np, sa.filtered ? " filtered" : "", P.nap, P.ap.n, P.rap.n);
-      m->desc += line;
+      if (!hc->err.empty()) return fail(hc->err);
+      if (hc->stop) break;
+      t_host_agg = hc->t_agg;
+      if (verbose)
+        std::fprintf(stderr, "[sgo] amg level %d: host aggregation + coarse structure %.1f ms (aggregate %.1f, sort %.1f; n=%d -> %d)%s\n", l,
+                     hc->t_all, hc->t_agg, hc->t_sort, n, hc->nc, hc == &hc_own ? "" : " [made ahead on the helper thread]");
+      if (!upload_coarse(D, *hc, n, l == 0 ? m->halo : nullptr, dc)) return fail(dc.err);
+      h_agg = hc->agg;
+      h_visit_c = hc->visit_c;
     } else {
-      L.gal.n = H.nslot;
-      L.gal.src = dev_upload(m->pool, order, s);
-      L.gal.tgt = dev_upload(m->pool, tgt, s);
-      L.gal.grp = dev_upload(m->pool, grp_g, s);
-      L.gal.ngrp = (int)grp_g.size() - 1;
-      if (!L.gal.src || !L.gal.tgt || !L.gal.grp) return fail("amg_create: out of device memory");
-    }
-    AmgLevel C;
-    C.A.n = nc;
-    C.A.nslot = Hc.nslot;
-    C.A.ngrp = (int)grp_c.size() - 1;
-    C.A.row = dev_upload(m->pool, Hc.row, s);
-    C.A.col = dev_upload(m->pool, Hc.col, s);
-    C.A.grp = dev_upload(m->pool, grp_c, s);
-    C.A.rowptr = dev_upload(m->pool, Hc.rowptr, s);
-    C.A.blk = dev_alloc<double>(m->pool, 9 * (size_t)Hc.nslot);
-    C.A.dinv = dev_alloc<double>(m->pool, 6 * (size_t)nc);
-    if (!L.agg || !L.mem_ptr || !L.mem || !L.mem_grp || !L.d || !C.A.row || !C.A.col ||
-        !C.A.grp || !C.A.rowptr || !C.A.blk || !C.A.dinv)
-      return fail("amg_create: out of device memory");
-    const double t_up0 = ms_since(tU);
-    if (smooth && sa.lists_on_device) {
-      // product lists from the patterns: count per target, prefix sum, fill, wave groups (A P, then P^T A P)
-      PDev& P = L.P;
-      ApPattern ap;
-      ap.nap = P.nap;
-      ap.ap_row = l0_dev.ap_row;
-      ap.ap_col = l0_dev.ap_col;
-      ap.ap_rowptr = l0_dev.ap_rowptr;
-      ap.f_lo = l0_own.own ? l0_own.F0 : 0;
-      ap.nap = l0_own.own ? l0_own.F1 : P.nap;
-      const int seg_lo[2] = {ap.f_lo, 0};
-      const int nseg[2] = {ap.nap - ap.f_lo, Hc.nslot};
-      const int nprod[2] = {P.ap.n, P.rap.n};
-      ProdMap* maps[2] = {&P.ap, &P.rap};
-      for (int w = 0; w < 2; ++w) {
-        int* ptr0 = dev_alloc<int>(m->pool, (size_t)nseg[w] + 1);
-        int* sums = dev_alloc<int>(m->pool, (size_t)nseg[w] / kScanChunk + 3);
-        if (!ptr0 || !sums) return fail("amg_create: out of device memory");
-        int* ptr = ptr0 - seg_lo[w];   // addressed by global target numbers
-        int *la = nullptr, *lb = nullptr, *lt = nullptr;
-        const dim3 grid(grid_for(8LL * nseg[w], kBlock)), block(kBlock);   // eight lanes per target
-        if (w == 0)
-          SGO_LAUNCH((k_ap_list<false>), grid, block, 0, s, ap, (const int*)L.A.rowptr, (const int*)L.A.col, (const int*)P.rowptr,
-                     (const int*)P.col, ptr, la, lb, lt);
-        else
-          SGO_LAUNCH((k_rap_list<false>), grid, block, 0, s, Hc.nslot, (const int*)C.A.row, (const int*)C.A.col,
-                     (const int*)l0_dev.t_ptr, (const int*)P.t_row, (const int*)l0_dev.t_idx, ap, ptr, la, lb, lt);
-        dev_scan_exclusive(s, ptr0, nseg[w], sums);
-        int ngrp = 0, total = -1;
-        if (hipMemcpyAsync(&total, ptr0 + nseg[w], sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess ||
-            hipStreamSynchronize(s) != hipSuccess)
-          return fail("amg_create: product-list kernels failed");
-        if (!l0_own.own && total != nprod[w])
-          return fail("amg_create: internal error (device product lists: " + std::to_string(total) + " products, the host counted " +
-                      std::to_string(nprod[w]) + ")");
-        if (total < 0 || total > nprod[w]) return fail("amg_create: internal error (device product lists)");
-        la = dev_alloc<int>(m->pool, (size_t)std::max(total, 1));
-        lb = dev_alloc<int>(m->pool, (size_t)std::max(total, 1));
-        lt = dev_alloc<int>(m->pool, (size_t)std::max(total, 1));
-        if (!la || !lb || !lt) return fail("amg_create: out of device memory");
-        if (w == 0)
-          SGO_LAUNCH((k_ap_list<true>), grid, block, 0, s, ap, (const int*)L.A.rowptr, (const int*)L.A.col, (const int*)P.rowptr,
-                     (const int*)P.col, ptr, la, lb, lt);
-        else
-          SGO_LAUNCH((k_rap_list<true>), grid, block, 0, s, Hc.nslot, (const int*)C.A.row, (const int*)C.A.col,
-                     (const int*)l0_dev.t_ptr, (const int*)P.t_row, (const int*)l0_dev.t_idx, ap, ptr, la, lb, lt);
-        int* grp = dev_make_groups(s, m->pool, ptr0, nseg[w], total, &ngrp);
-        if (!grp) return fail("amg_create: out of device memory");
-        maps[w]->n = total;
-        maps[w]->a = la;
-        maps[w]->b = lb;
-        maps[w]->tgt = lt;
-        maps[w]->grp = grp;
-        maps[w]->ngrp = ngrp;
-        if (l == 0) m->level0_bytes += 12LL * total;
+      // ---- where the device producer's aggregates come from: kept, the helper thread's, the host's (greedy along the trajectory,
+      // sgo_amg_host.cpp) or the device's own (dev_coarsen aggregates when it is given none)
+      int* given = nullptr;
+      int given_nc = 0;
+      double given_theta = (l == 0 ? m->cfg.theta : m->cfg.theta_coarse) * m->cfg.theta_scale;
+      double* d_w = nullptr;
+      if (kept) {
+        given = dev_upload(tmp_arena, m->cfg.keep_agg->agg[l], s);
+        given_nc = m->cfg.keep_agg->nc[l];
+        if (!given) return fail("amg_create: out of device memory");
+        h_agg = m->cfg.keep_agg->agg[l];
+        h_visit_c = m->cfg.keep_agg->visit_c[l];
+      } else if (l == 0 && pre0_agg) {
+        // level 0's aggregation was made ahead on the helper thread (sgo_set_graph_se2's pipeline), from the same structure and the
+        // strengths at the same poses
+        if (pre0->hc.nc == 0) break;
+        h_agg = pre0->hc.agg;
+        h_visit_c = pre0->hc.visit_c;
+        given_nc = pre0->hc.nc;
+        given_theta = pre0->theta_used;
+        given = dev_upload(tmp_arena, h_agg, s);
+        if (!given) return fail("amg_create: out of device memory");
+      } else if (patterns == AmgPatterns::device) {
+        // the host's aggregation from this level's strengths: the level's pattern (level 0: the context's host copy; coarser levels:
+        // copied back, a few integers per slot) and the slots' block norms
+        if (l > 0) {
+          Hown.n = n;
+          Hown.nslot = L.A.nslot;
+          Hown.rowptr.resize((size_t)n + 1);
+          Hown.col.resize((size_t)L.A.nslot);
+          Hown.row.clear();
+          hipMemcpyAsync(Hown.rowptr.data(), L.A.rowptr, sizeof(int) * ((size_t)n + 1), hipMemcpyDeviceToHost, s);
+          hipMemcpyAsync(Hown.col.data(), L.A.col, sizeof(int) * (size_t)L.A.nslot, hipMemcpyDeviceToHost, s);
+        }
+        h_w.resize((size_t)H.nslot);
+        d_w = dev_alloc<double>(tmp_arena, (size_t)std::max(H.nslot, 1));
+        if (!d_w) return fail("amg_create: out of device memory");
+        SGO_LAUNCH(k_block_norms, dim3(grid_for(H.nslot, kBlock)), dim3(kBlock), 0, s, L.A, d_w);
+        hipMemcpyAsync(h_w.data(), d_w, sizeof(double) * (size_t)H.nslot, hipMemcpyDeviceToHost, s);
+        if (!D.sync()) return fail("amg_create: strength kernel failed");
+        const auto tA = std::chrono::steady_clock::now();
+        given_nc = host_aggregate(H, h_w, m->cfg, l, scratch, h_agg, h_visit_c, &given_theta);
+        t_host_agg = ms_since(tA);
+        if (given_nc == 0) break;   // cannot coarsen further
+        given = dev_upload(tmp_arena, h_agg, s);
+        if (!given) return fail("amg_create: out of device memory");
+      }
+      if (!dev_coarsen(D, L.A, m->cfg, l, given, given_nc, given_theta, d_w, dc)) return fail(dc.err.empty() ? "amg_create: device set-up failed" : dc.err);
+      if (dc.stop) break;
+      if (h_agg.empty()) {   // (the device's aggregates)
+        h_agg.resize((size_t)n);
+        if (hipMemcpyAsync(h_agg.data(), dc.agg, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, s) != hipSuccess || !D.sync())
+          return fail("amg_create: device set-up failed");
       }
     }
-    if (hipStreamSynchronize(s) != hipSuccess) return fail("amg_create: upload failed");  // host vectors die below
-    const double t_up = ms_since(tU);
-    m->lv.push_back(C);  // invalidates L
-    // values of level l+1 (needed for the next level's strengths): positions, centres, Galerkin
-    {
-      AmgLevel& Lr = m->lv[l];
-      AmgLevel& Cr = m->lv[l + 1];
-      Cr.pos = dev_alloc<double>(m->pool, 2 * (size_t)nc);
-      if (!Cr.pos) return fail("amg_create: out of device memory");
-      if (l == 0)
-        SGO_LAUNCH(k_positions0, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, s, n, d_free_id, d_poses, Lr.pos);
-      SGO_LAUNCH(k_centres, dim3(grid_for(nc, kWavesPerBlock)), dim3(kBlock), 0, s, nc, Lr.mem_ptr, Lr.mem, Lr.pos, Cr.pos, Lr.d);
-      launch_coarse_operator(m, s, Lr, Cr, l == 0);
-      if (l + 1 < m->cfg.max_levels) SGO_LAUNCH(k_level_dinv, dim3(grid_for(Cr.A.n, kBlock)), dim3(kBlock), 0, s, Cr.A);
-      if (hipStreamSynchronize(s) != hipSuccess) return fail("amg_create: Galerkin kernel failed");
-      if (std::getenv("SGO_VERBOSE") && (n > 20000 || std::atoi(std::getenv("SGO_VERBOSE")) > 1))
-        std::fprintf(stderr, "[sgo] amg level %d: alloc + upload %.1f ms (of which product lists on the device %.1f), first values %.1f ms\n", l, t_up,
-                     t_up - t_up0, ms_since(tU) - t_up);
-    }
-    Hown = std::move(Hc);
-    Hown.visit = std::move(visit_c);
-    Hp = &Hown;
+    const double t_coarsen = ms_since(tL);
+    m->kept.agg.push_back(std::move(h_agg));
+    m->kept.visit_c.push_back(h_visit_c);
+    m->kept.nc.push_back(dc.nc);
+    const std::string e = assemble_level(m, D, l, dc);
+    if (!e.empty()) return fail(e);
+    if (l == 0 && halo && dc.smooth)
+      if (const char* be = boundary_entries(s, m->pool, *halo, hc->sa.p_rowptr)) return fail(be);
+    level_values(m, s, l);
+    if (verbose)
+      std::fprintf(stderr, "[sgo] amg level %d, patterns on the %s: %.2f ms (of which the host's aggregation %.2f), assembly %.2f ms, "
+                   "%d synchronisations (n=%d -> %d, %s)\n", l, on_host ? "host" : "device", t_coarsen, t_host_agg, ms_since(tL) - t_coarsen,
+                   D.syncs, n, dc.nc, dc.smooth ? (dc.filtered ? "filtered smoothing" : "smoothed") : "tentative");
+    if (on_host) Hown = std::move(hc->Hc);
+    Hown.visit = std::move(h_visit_c);   // (the order in which the next level's aggregation visits its nodes: along the trajectory)
   }
+  if (hipStreamSynchronize(s) != hipSuccess) return fail("amg_create: set-up kernels failed");
   const int last = (int)m->lv.size() - 1;
   // last == 0: the whole graph is at most coarsest_nodes large (or cannot be coarsened) and is
   // "solved" by the dense inverse directly -- the preconditioner is then exact (1-2 PCG iterations)

@@ -1,7 +1,8 @@
-// sgo_amg_dev.inc -- the multigrid set-up ON THE DEVICE (round 6): aggregation, the patterns of the smoothed transfer P, of A P and
-// of P^T A P, the tentative transfer's Galerkin map, the structure of the next level -- what sgo_amg_host.cpp does on host threads
-// -- as sort / scan / compress passes over 64-bit keys.  Included by sgo_amg.hip (inside namespace sgo, after the kernels, PDev,
-// AmgLevel and Amg, before amg_create); amg_create_dev below builds a hierarchy with it.
+// sgo_amg_dev.inc -- the device producer of the multigrid set-up (round 6): aggregation, the patterns of the smoothed transfer P, of
+// A P and of P^T A P, the tentative transfer's Galerkin map, the structure of the next level -- what host_coarsen (sgo_amg_host.cpp)
+// does on host threads -- as sort / scan / compress passes over 64-bit keys.  Included by sgo_amg.hip (inside namespace sgo, after the
+// kernels, PDev, AmgLevel and Amg, before the level assembler); dev_coarsen below makes one level's DevCoarse, which amg_create's
+// assembler turns into a working level exactly as it does an uploaded HostCoarse.
 //
 // Why: g2o's symbolic analysis happens once per optimize() (SURVEY.md section 8(a) a7) and the reference re-initialises before
 // every call (slc.cpp:286-287); a rebuild of the hierarchy INSIDE sgo_optimize_gn -- from BASELINE.md's literal dead-reckoned start
@@ -346,29 +347,6 @@ __global__ __launch_bounds__(kBlock) void k_rap_mirror(int nslot_c, int nc, cons
   }
 }
 
-// ------------------------------------------------------------------ folded cycle, levels >= 1: per row its slots of A, then its
-// entries of P~ (pattern of A P), as one row-major list
-__global__ __launch_bounds__(kBlock) void k_u_ptr(int n, const int* __restrict__ a_rowptr, const int* __restrict__ ap_rowptr, int* __restrict__ u_ptr) {
-  for (int i = blockIdx.x * kBlock + threadIdx.x; i <= n; i += gridDim.x * kBlock) u_ptr[i] = a_rowptr[i] + ap_rowptr[i];
-}
-__global__ __launch_bounds__(kBlock) void k_u_fill(int n, const int* __restrict__ a_rowptr, const int* __restrict__ a_col,
-                                                   const int* __restrict__ ap_rowptr, const int* __restrict__ ap_col, const int* __restrict__ u_ptr,
-                                                   int* __restrict__ u_row, int* __restrict__ u_idx, int* __restrict__ u_col) {
-  for (int i = blockIdx.x * kBlock + threadIdx.x; i < n; i += gridDim.x * kBlock) {
-    int q = u_ptr[i];
-    for (int k = a_rowptr[i]; k < a_rowptr[i + 1]; ++k, ++q) {
-      u_row[q] = i;
-      u_idx[q] = k;
-      u_col[q] = a_col[k];
-    }
-    for (int f = ap_rowptr[i]; f < ap_rowptr[i + 1]; ++f, ++q) {
-      u_row[q] = i;
-      u_idx[q] = ~f;
-      u_col[q] = ap_col[f];
-    }
-  }
-}
-
 // ------------------------------------------------------------------ tentative transfer: coarse slot (agg(row), agg(col)) of every
 // fine slot; key = (coarse row, code of the coarse column, fine slot)
 __global__ __launch_bounds__(kBlock) void k_gal_keys(BsrDev A, const int* __restrict__ agg, int bcode, u64* __restrict__ keys, unsigned* __restrict__ vals) {
@@ -487,93 +465,33 @@ __global__ __launch_bounds__(kBlock) void k_key_rowptr(const u64* __restrict__ s
     rowptr[r] = ex[lo];
   }
 }
-// the wave groups longer than kLongColumn, as k_fold_long, without a cap on their number (ranges holds 2 x ngrp ints)
-__global__ __launch_bounds__(kBlock) void k_long_groups(const int* __restrict__ grp, int ngrp, int* __restrict__ count, int* __restrict__ ranges) {
-  for (int g = blockIdx.x * kBlock + threadIdx.x; g < ngrp; g += gridDim.x * kBlock) {
-    const int b = grp[g], e = grp[g + 1];
-    if (e - b > kLongColumn) {
-      const int q = atomicAdd(count, 1);
-      ranges[2 * q] = b;
-      ranges[2 * q + 1] = e;
-    }
-  }
-}
-
-// All the wave-group lists of a level in two launches (GroupBatch, below): the lists' chunks of kGroupChunk segments are numbered
-// through, every list followed by one pseudo-chunk that holds its closing element (the total); k_group_chunks' rule per chunk.
-constexpr int kMaxGroupJobs = 12;
-struct GroupJobsDev {
-  const int* ptr[kMaxGroupJobs];
-  int nseg[kMaxGroupJobs];
-  int total[kMaxGroupJobs];
-  int chunk0[kMaxGroupJobs + 1];   // first global chunk of list j (its pseudo-chunk is chunk0[j + 1] - 1)
-  int njobs;
-};
-template <bool FILL>
-__global__ __launch_bounds__(kBlock) void k_group_jobs(GroupJobsDev J, int* __restrict__ cnt_or_off, int* __restrict__ out) {
-  const int c = blockIdx.x * kBlock + threadIdx.x;
-  if (c >= J.chunk0[J.njobs]) return;
-  int j = 0;
-  while (c >= J.chunk0[j + 1]) ++j;
-  const int local = c - J.chunk0[j];
-  if (c == J.chunk0[j + 1] - 1) {   // the list's closing element
-    if (FILL) out[cnt_or_off[c]] = J.total[j];
-    else cnt_or_off[c] = 1;
-    return;
-  }
-  const int* __restrict__ ptr = J.ptr[j];
-  const int nseg = J.nseg[j], s0 = local * kGroupChunk, s1 = min(nseg, s0 + kGroupChunk);
-  int o = FILL ? cnt_or_off[c] : 0, cur = 0, start = ptr[s0];
-  bool open = false;
-  for (int f = s0; f < s1; ++f) {
-    const int b = ptr[f], len = ptr[f + 1] - b;
-    if (open && cur + len > 64) {
-      if (FILL) out[o] = start;
-      ++o;
-      open = false;
-      cur = 0;
-    }
-    if (!open) {
-      start = b;
-      open = true;
-    }
-    cur += len;
-    if (cur >= 64) {
-      if (FILL) out[o] = start;
-      ++o;
-      open = false;
-      cur = 0;
-    }
-  }
-  if (open) {
-    if (FILL) out[o] = start;
-    ++o;
-  }
-  if (!FILL) cnt_or_off[c] = o;
-}
-__global__ void k_gather_ints(const int* __restrict__ src, GroupJobsDev J, int* __restrict__ dst) {
-  const int j = threadIdx.x;
-  if (blockIdx.x == 0 && j <= J.njobs) dst[j] = src[J.chunk0[j]];
-}
-
 }  // namespace
 
 // ============================================================================================ host side of the device set-up
-// One coarsening step's result, everything in device memory of the hierarchy's arena (the counterpart of HostCoarse).  The wave-group
-// lists are NOT here: they are made in one batch per level (GroupBatch) once everything they cover exists.
+// One coarsening step's result, everything in device memory (the hierarchy's arena; some arrays the set-up alone reads: the temporary
+// one), made by either producer: dev_coarsen below, or the upload of a HostCoarse (upload_coarse, sgo_amg.hip).  The assembler (assemble_level,
+// sgo_amg.hip) turns it into a working level; the wave-group lists are made there, in one batch per level.
 struct DevCoarse {
   int nc = 0;
   bool stop = false, smooth = false, filtered = false;
   int *agg = nullptr, *mem_ptr = nullptr, *mem = nullptr;
   // smoothed transfer
   unsigned char* strong = nullptr;
-  int np = 0, nval = 0;
+  int np = 0;
   int *p_rowptr = nullptr, *p_row = nullptr, *p_col = nullptr, *val_src = nullptr, *val_tgt = nullptr, *val_ptr = nullptr;
   int *t_pos = nullptr, *t_row = nullptr, *t_col = nullptr, *t_ptr = nullptr, *t_idx = nullptr;
   int nap = 0;
   int *ap_rowptr = nullptr, *ap_col = nullptr, *ap_row = nullptr;
   long long n_ap_prod = 0, n_rap_prod = 0;
   int* rap_mirror = nullptr;
+  // What is held of them (the whole ranges, except in multi-GPU row-owner mode on level 0, where a rank holds its own rows' share, base
+  // pointers shifted so that global numbers address them): the entries [e_lo, e_hi) of P -- t_* then list the rank's entries in column
+  // order, positions 0 .. e_hi - e_lo --, their value products [v_lo, v_lo + nval) and the A P entries [f_lo, f_hi)
+  bool local = false;
+  int e_lo = 0, e_hi = 0, v_lo = 0, nval = 0, f_lo = 0, f_hi = 0;
+  // ready-made product lists of A P and P^T A P with their per-target pointers (the host producer's under SGO_AMG_LISTS=host);
+  // a == nullptr: the assembler makes them from the patterns
+  struct { int *a = nullptr, *b = nullptr, *tgt = nullptr, *ptr = nullptr; } lists[2];
   // tentative transfer
   int *gal_src = nullptr, *gal_tgt = nullptr, *gal_cptr = nullptr;
   // next level
@@ -583,29 +501,6 @@ struct DevCoarse {
 };
 
 namespace {
-
-// The wave-group lists of one level, made as ONE batch: every list's count pass and scan first, one synchronisation for all the
-// group counts (they size the lists), then the fill passes -- instead of two synchronisations per list (dev_make_groups): a level has
-// up to a dozen lists, and on the small levels of a hierarchy the set-up's time IS its host round trips.
-enum GroupId { G_MEM, G_VAL, G_R, G_T, G_C, G_F, G_GAL, G_ST, G_PSR, G_U, G_APL, G_RAPL, G_COUNT };
-struct GroupBatch {
-  struct Job {
-    const int* ptr = nullptr;
-    int nseg = 0, total = 0;
-    int* cnt = nullptr;
-    int nch = 0;
-    bool on = false;
-  };
-  Job job[G_COUNT];
-  int* grp[G_COUNT] = {};
-  int ngrp[G_COUNT] = {};
-  void add(GroupId id, const int* ptr, int nseg, int total) {
-    job[id].ptr = ptr;
-    job[id].nseg = nseg;
-    job[id].total = total;
-    job[id].on = true;
-  }
-};
 
 struct DevSetup {
   hipStream_t s;
@@ -684,46 +579,6 @@ struct DevSetup {
     SGO_LAUNCH(k_head_flags, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, s, sorted, n, shift, ex);
     scan(ex, n);
     return ex;
-  }
-  // all the pending group lists of the batch (see GroupBatch): two launches, a scan and one synchronisation
-  bool run(GroupBatch& gb) {
-    GroupJobsDev J;
-    int ids[kMaxGroupJobs];
-    J.njobs = 0;
-    J.chunk0[0] = 0;
-    for (int g = 0; g < G_COUNT; ++g) {
-      GroupBatch::Job& j = gb.job[g];
-      if (!j.on) continue;
-      const int q = J.njobs++;
-      ids[q] = g;
-      J.ptr[q] = j.ptr;
-      J.nseg[q] = j.nseg;
-      J.total[q] = j.total;
-      J.chunk0[q + 1] = J.chunk0[q] + (j.nseg + kGroupChunk - 1) / kGroupChunk + 1;   // (+ the pseudo-chunk of the closing element)
-    }
-    if (J.njobs == 0) return ok;
-    const int nch = J.chunk0[J.njobs];
-    int* off = talloc<int>((size_t)nch + 1);
-    int* d_first = talloc<int>(kMaxGroupJobs + 1);
-    if (!ok) return false;
-    const dim3 grid((nch + kBlock - 1) / kBlock), block(kBlock);
-    SGO_LAUNCH((k_group_jobs<false>), grid, block, 0, s, J, off, (int*)nullptr);
-    scan(off, nch);
-    if (!ok) return false;
-    J.chunk0[J.njobs] = nch;   // (off[nch] = everything)
-    SGO_LAUNCH(k_gather_ints, dim3(1), dim3(64), 0, s, (const int*)off, J, d_first);
-    int h_first[kMaxGroupJobs + 1] = {};
-    if (hipMemcpyAsync(h_first, d_first, sizeof(int) * (size_t)(J.njobs + 1), hipMemcpyDeviceToHost, s) != hipSuccess) ok = false;
-    if (!sync()) return false;
-    int* out = alloc<int>((size_t)std::max(h_first[J.njobs], 1));
-    if (!ok) return false;
-    SGO_LAUNCH((k_group_jobs<true>), grid, block, 0, s, J, off, out);
-    for (int q = 0; q < J.njobs; ++q) {
-      gb.grp[ids[q]] = out + h_first[q];
-      gb.ngrp[ids[q]] = h_first[q + 1] - h_first[q] - 1;
-      gb.job[ids[q]].on = false;
-    }
-    return ok;
   }
 };
 
@@ -952,9 +807,9 @@ bool dev_tentative(DevSetup& D, const BsrDev& A, const int* agg, int nc, DevCoar
 
 // One coarsening step on the device: the counterpart of host_coarsen (same decisions, sgo_amg_host.cpp).  `given_agg` (device, n
 // ints) / given_nc / given_theta_used: aggregates to use instead of aggregating on the device (the host's; AmgConfig::keep_agg);
-// d_w: the slots' block norms when the caller has made them already.  The level's wave-group lists are registered with `gb`.
+// d_w: the slots' block norms when the caller has made them already.
 bool dev_coarsen(DevSetup& D, const BsrDev& A, const AmgConfig& cfg, int l, const int* given_agg, int given_nc, double given_theta_used,
-                 const double* d_w, GroupBatch& gb, DevCoarse& o) {
+                 const double* d_w, DevCoarse& o) {
   hipStream_t s = D.s;
   DevArena* pool = D.pool;
   const int n = A.n, ns = A.nslot;
@@ -1048,437 +903,10 @@ bool dev_coarsen(DevSetup& D, const BsrDev& A, const AmgConfig& cfg, int l, cons
     return false;
   }
   o.smooth = smooth;
-  gb.add(G_MEM, o.mem_ptr, nc, n);
-  if (smooth) {
-    gb.add(G_VAL, o.val_ptr, o.np, o.nval);
-    gb.add(G_R, o.p_rowptr, n, o.np);
-    gb.add(G_T, o.t_ptr, nc, o.np);
-    if (o.filtered) gb.add(G_F, A.rowptr, n, ns);
-  } else {
-    gb.add(G_GAL, o.gal_cptr, o.nslot_c, ns);
-  }
-  gb.add(G_C, o.c_rowptr, nc, o.nslot_c);
+  o.e_hi = o.np;   // (the whole ranges)
+  o.f_hi = o.nap;
   if (!D.ok) o.err = "amg_create: out of device memory";
   return D.ok;
 }
 
 }  // namespace
-
-// The hierarchy for the level-0 matrix, set up entirely on the device (single GPU; the transfers' product lists are the
-// device-made ones).  Same result structure as amg_create's; with cfg.keep_agg (the aggregates of a hierarchy the host made from
-// the same values) the result is that hierarchy, bit for bit.
-Amg* amg_create_dev(hipStream_t s, const BsrDev& A0, const Sym0Dev& S0, const Tile0Dev& T0, const HostLevel& H0, const double* d_poses,
-                    const int* d_free_id, const AmgConfig& cfg_in, const AmgProf& prof, std::string* err, ChunkArena* scratch, DevArena* arena,
-                    DevArena* tmp_arena, bool aggregate_on_device, const AmgHostL0* pre0) {
-  Amg* m = new Amg();
-  m->pool = arena;
-  m->S0 = S0;
-  m->T0 = T0;
-  m->cfg = amg_effective_config(cfg_in, A0.n, A0.nslot);
-  m->cfg.lists_on_device = true;
-  m->cfg.fold = m->cfg.fold && m->cfg.smooth;
-  if (m->cfg.smooth) m->kdepth = 0;
-  if (const char* e = std::getenv("SGO_AMG_KDEPTH")) m->kdepth = std::atoi(e);
-  if (const char* e = std::getenv("SGO_AMG_FCG2_DEPTH")) m->fcg2_depth = std::atoi(e);
-  m->prof = prof;
-  m->d_poses = d_poses;
-  m->d_free_id = d_free_id;
-  auto fail = [&](const std::string& msg) -> Amg* {
-    if (err) *err = msg;
-    amg_destroy(m);
-    return nullptr;
-  };
-  const bool verbose = std::getenv("SGO_VERBOSE") != nullptr;
-  auto ms_since = [](std::chrono::steady_clock::time_point t) {
-    return 1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t).count();
-  };
-  AmgLevel L0;
-  L0.A = A0;
-  m->lv.push_back(L0);
-  char line[160];
-  HostLevel Hown;              // pattern of the coarse level being aggregated on the host (copied back from the device)
-  std::vector<double> h_w;
-  for (int l = 0;; ++l) {
-    AmgLevel& L = m->lv[l];
-    const int n = L.A.n, n3 = 3 * n;
-    L.spmv_grid = grid_for(L.A.ngrp, kWavesPerBlock);
-    std::snprintf(line, sizeof line, "L%d n=%d slots=%d; ", l, n, L.A.nslot);
-    m->desc += line;
-    L.xs = dev_alloc<double>(m->pool, n3);
-    L.rs = dev_alloc<double>(m->pool, n3);
-    L.tR = dev_alloc<double>(m->pool, n3);
-    if (!L.pos) L.pos = dev_alloc<double>(m->pool, 2 * (size_t)n);
-    if (l > 0) {
-      L.bk = dev_alloc<double>(m->pool, n3);
-      L.xk = dev_alloc<double>(m->pool, n3);
-      L.z1 = dev_alloc<double>(m->pool, n3);
-      L.z2 = dev_alloc<double>(m->pool, n3);
-      L.q = dev_alloc<double>(m->pool, n3);
-      L.bk2 = dev_alloc<double>(m->pool, n3);
-      L.p2 = dev_alloc<double>(m->pool, n3);
-      L.q2 = dev_alloc<double>(m->pool, n3);
-      L.pA = dev_alloc<double>(m->pool, 2 * (size_t)kMaxPartials);
-      L.pB = dev_alloc<double>(m->pool, 2 * (size_t)kMaxPartials);
-      L.pC = dev_alloc<double>(m->pool, 2 * (size_t)kMaxPartials);
-      if (!L.pC || !L.bk2 || !L.p2 || !L.q2) return fail("amg_create: out of device memory");
-      hipMemsetAsync(L.pA, 0, sizeof(double) * 2 * kMaxPartials, s);
-      hipMemsetAsync(L.pB, 0, sizeof(double) * 2 * kMaxPartials, s);
-      hipMemsetAsync(L.pC, 0, sizeof(double) * 2 * kMaxPartials, s);
-    }
-    if (!L.xs || !L.rs || !L.pos) return fail("amg_create: out of device memory");
-    if (n <= m->cfg.coarsest_nodes || l + 1 >= m->cfg.max_levels) break;
-
-    const auto tL = std::chrono::steady_clock::now();
-    tmp_arena->rewind();   // (the previous level's temporaries: every later user is queued behind their last kernel)
-    DevSetup D{s, m->pool, tmp_arena};
-    GroupBatch gb;
-    DevCoarse dc;
-    int* given = nullptr;
-    int given_nc = 0;
-    double given_theta = (l == 0 ? m->cfg.theta : m->cfg.theta_coarse) * m->cfg.theta_scale;
-    std::vector<int> h_agg, h_visit_c;
-    double t_host_agg = 0.0;
-    double* d_w = nullptr;
-    if (m->cfg.keep_agg && l < (int)m->cfg.keep_agg->agg.size() && (int)m->cfg.keep_agg->agg[l].size() == n) {
-      given = dev_upload(tmp_arena, m->cfg.keep_agg->agg[l], s);
-      given_nc = m->cfg.keep_agg->nc[l];
-      if (!given) return fail("amg_create: out of device memory");
-      h_agg = m->cfg.keep_agg->agg[l];
-      h_visit_c = m->cfg.keep_agg->visit_c[l];
-    } else if (l == 0 && pre0 && pre0->ready && pre0->agg_only) {
-      // level 0's aggregation was made ahead on the helper thread (sgo_set_graph_se2's pipeline), from the same structure and the
-      // strengths at the same poses
-      if (pre0->hc.nc == 0) break;
-      h_agg = pre0->hc.agg;
-      h_visit_c = pre0->hc.visit_c;
-      given_nc = pre0->hc.nc;
-      given_theta = pre0->theta_used;
-      given = dev_upload(tmp_arena, h_agg, s);
-      if (!given) return fail("amg_create: out of device memory");
-    } else if (!aggregate_on_device) {
-      // ---- the HOST's aggregation (greedy along the trajectory, sgo_amg_host.cpp) from this level's strengths: the level's pattern
-      // (level 0: the context's host copy; coarser levels: copied back, a few integers per slot) and the slots' block norms
-      if (l > 0) {
-        Hown.n = n;
-        Hown.nslot = L.A.nslot;
-        Hown.rowptr.resize((size_t)n + 1);
-        Hown.col.resize((size_t)L.A.nslot);
-        Hown.row.clear();
-        hipMemcpyAsync(Hown.rowptr.data(), L.A.rowptr, sizeof(int) * ((size_t)n + 1), hipMemcpyDeviceToHost, s);
-        hipMemcpyAsync(Hown.col.data(), L.A.col, sizeof(int) * (size_t)L.A.nslot, hipMemcpyDeviceToHost, s);
-      }
-      const HostLevel& H = l == 0 ? H0 : Hown;
-      h_w.resize((size_t)H.nslot);
-      d_w = dev_alloc<double>(tmp_arena, (size_t)std::max(H.nslot, 1));
-      if (!d_w) return fail("amg_create: out of device memory");
-      SGO_LAUNCH(k_block_norms, dim3(grid_for(H.nslot, kBlock)), dim3(kBlock), 0, s, L.A, d_w);
-      hipMemcpyAsync(h_w.data(), d_w, sizeof(double) * (size_t)H.nslot, hipMemcpyDeviceToHost, s);
-      if (!D.sync()) return fail("amg_create: strength kernel failed");
-      const auto tA = std::chrono::steady_clock::now();
-      given_nc = host_aggregate(H, h_w, m->cfg, l, scratch, h_agg, h_visit_c, &given_theta);
-      t_host_agg = ms_since(tA);
-      if (given_nc == 0) break;   // cannot coarsen further
-      given = dev_upload(tmp_arena, h_agg, s);
-      if (!given) return fail("amg_create: out of device memory");
-    }
-    if (!dev_coarsen(D, L.A, m->cfg, l, given, given_nc, given_theta, d_w, gb, dc)) return fail(dc.err.empty() ? "amg_create: device set-up failed" : dc.err);
-    if (dc.stop) break;
-    const int nc = dc.nc;
-    const double t_coarsen = ms_since(tL);
-    Hown.visit = h_visit_c;   // (the order in which the next level's aggregation visits its nodes: along the trajectory)
-    L.nc = nc;
-    L.agg = dc.agg;
-    L.mem_ptr = dc.mem_ptr;
-    L.mem = dc.mem;
-    L.d = dev_alloc<double>(m->pool, 2 * (size_t)n);
-    {   // host copy of the aggregates (a later rebuild may be asked to keep them: AmgConfig::keep_agg)
-      if (h_agg.empty()) {
-        h_agg.resize((size_t)n);
-        if (hipMemcpyAsync(h_agg.data(), dc.agg, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, s) != hipSuccess || !D.sync())
-          return fail("amg_create: device set-up failed");
-      }
-      m->kept.agg.push_back(std::move(h_agg));
-      m->kept.visit_c.push_back(h_visit_c);
-      m->kept.nc.push_back(nc);
-    }
-    AmgLevel C;
-    C.A.n = nc;
-    C.A.nslot = dc.nslot_c;
-    C.A.row = dc.c_row;
-    C.A.col = dc.c_col;
-    C.A.rowptr = dc.c_rowptr;
-    C.A.blk = dev_alloc<double>(m->pool, 9 * (size_t)dc.nslot_c);
-    C.A.dinv = dev_alloc<double>(m->pool, 6 * (size_t)nc);
-    if (!L.d || !C.A.blk || !C.A.dinv) return fail("amg_create: out of device memory");
-    int *d_ap_rowptr = nullptr, *d_ap_col = nullptr, *d_ap_row = nullptr, *d_t_ptr = nullptr, *d_t_idx = nullptr;
-    bool fold_here = false;
-    int* st_ranges = nullptr;
-    int* t_ranges = nullptr;
-    if (dc.smooth) {
-      PDev& P = L.P;
-      L.smoothed = true;
-      const size_t npl = (size_t)dc.np;
-      if (dc.filtered) {
-        P.dF = dev_alloc<double>(m->pool, 9 * (size_t)n);
-        P.dinvF = dev_alloc<double>(m->pool, 9 * (size_t)n);
-        if (!P.dF || !P.dinvF) return fail("amg_create: out of device memory");
-        P.strong = dc.strong;
-      }
-      P.np = dc.np;
-      P.stream_nt = npl >= 200000 ? 1 : 0;
-      P.rowptr = dc.p_rowptr;
-      P.row = dc.p_row;
-      P.col = dc.p_col;
-      P.blk = dev_alloc<double>(m->pool, 9 * npl);
-      P.val.n = dc.nval;
-      P.val.a = dc.val_src;
-      P.val.tgt = dc.val_tgt;
-      P.t_pos = dc.t_pos;
-      P.t_row = dc.t_row;
-      P.t_col = dc.t_col;
-      P.r_n = P.t_n = dc.np;
-      {
-        float* rb = dev_alloc<float>(m->pool, 9 * npl + 4);
-        float* tb = dev_alloc<float>(m->pool, 9 * npl + 4);
-        if (!rb || !tb || !P.blk) return fail("amg_create: out of device memory");
-        P.r_blk = rb;
-        P.r_blk8 = rb + 8 * npl;
-        P.t_blk = tb;
-        P.t_blk8 = tb + 8 * npl;
-      }
-      P.nap = dc.nap;
-      P.apblk = dev_alloc<double>(m->pool, 9 * (size_t)dc.nap);
-      if (!P.apblk) return fail("amg_create: out of device memory");
-      d_ap_rowptr = dc.ap_rowptr;
-      d_ap_col = dc.ap_col;
-      d_ap_row = dc.ap_row;
-      d_t_ptr = dc.t_ptr;
-      d_t_idx = dc.t_idx;
-      P.ap.n = (int)dc.n_ap_prod;
-      P.rap.n = (int)dc.n_rap_prod;
-      P.rap_mirror = dc.rap_mirror;
-      const size_t nf = (size_t)dc.nap;
-      if (l == 0) m->level0_bytes += (long long)(72 * npl + 72 * npl + 72 * nf + 8 * (size_t)dc.nval + 12 * npl + 8 * nf);
-      fold_here = m->cfg.fold && nf > 0 && (l > 0 || n <= m->cfg.fold0_rows);
-      if (fold_here) {
-        // ---- folded cycle: the bookkeeping of P~ (pattern of A P), as in amg_create; the row groups and the merged row lists of
-        // k_up_fold come from device kernels here
-        FoldDev& Fd = L.F;
-        Fd.f_lo = 0;
-        Fd.f_hi = (int)nf;
-        Fd.row = d_ap_row;
-        Fd.col = d_ap_col;
-        int* a2p = dev_alloc<int>(m->pool, nf);
-        int* stp = dev_alloc<int>(m->pool, nf);
-        unsigned long long* keys = dev_alloc<unsigned long long>(tmp_arena, nf);
-        unsigned long long* sorted = dev_alloc<unsigned long long>(tmp_arena, nf);
-        int bits = 33;
-        while (bits < 64 && (1ull << (bits - 32)) <= (unsigned long long)nc) ++bits;
-        const size_t tmp_bytes = sort_u64_temp_bytes(nf, bits);
-        void* tmp = tmp_bytes ? tmp_arena->take(tmp_bytes) : nullptr;
-        int* st_row = dev_alloc<int>(m->pool, nf);
-        int* st_col = dev_alloc<int>(m->pool, nf);
-        int* st_ptr = dev_alloc<int>(m->pool, (size_t)nc + 1);
-        float* sb = dev_alloc<float>(m->pool, 9 * nf + 4);
-        float* tb = dev_alloc<float>(m->pool, 9 * nf + 4);
-        if (!a2p || !stp || !keys || !sorted || !tmp || !st_row || !st_col || !st_ptr || !sb || !tb) return fail("amg_create: out of device memory");
-        Fd.ap2p = a2p;
-        Fd.st_pos = stp;
-        SGO_LAUNCH(k_fold_match, dim3(grid_for((long long)nf, kBlock)), dim3(kBlock), 0, s, Fd, (const int*)P.rowptr, (const int*)P.col, keys);
-        if (!sort_u64(tmp, tmp_bytes, (const uint64_t*)keys, (uint64_t*)sorted, nf, bits, s)) return fail("amg_create: device sort failed");
-        SGO_LAUNCH(k_fold_unpack, dim3(grid_for((long long)nf, kBlock)), dim3(kBlock), 0, s, Fd, (const unsigned long long*)sorted, st_row, st_col);
-        SGO_LAUNCH(k_fold_colptr, dim3(grid_for((long long)nc + 1, kBlock)), dim3(kBlock), 0, s, (const unsigned long long*)sorted, (int)nf, nc, st_ptr);
-        gb.add(G_ST, st_ptr, nc, (int)nf);
-        gb.add(G_PSR, d_ap_rowptr, n, (int)nf);
-        PDev& PS = L.PS;
-        PS = PDev();
-        PS.np = (int)nf;
-        PS.stream_nt = nf >= 200000 ? 1 : 0;
-        PS.row = d_ap_row;
-        PS.col = d_ap_col;
-        PS.r_n = PS.t_n = (int)nf;
-        PS.r_blk = sb;
-        PS.r_blk8 = sb + 8 * nf;
-        PS.t_blk = tb;
-        PS.t_blk8 = tb + 8 * nf;
-        PS.t_row = st_row;
-        PS.t_col = st_col;
-        if (l > 0) {
-          int* u_ptr = dev_alloc<int>(m->pool, (size_t)n + 1);
-          if (!u_ptr) return fail("amg_create: out of device memory");
-          SGO_LAUNCH(k_u_ptr, dim3(grid_for((long long)n + 1, kBlock)), dim3(kBlock), 0, s, n, (const int*)L.A.rowptr, (const int*)d_ap_rowptr, u_ptr);
-          const int un = L.A.nslot + (int)nf;
-          int* u_row = dev_alloc<int>(m->pool, (size_t)un);
-          int* u_idx = dev_alloc<int>(m->pool, (size_t)un);
-          int* u_col = dev_alloc<int>(m->pool, (size_t)un);
-          if (!u_row || !u_idx || !u_col) return fail("amg_create: out of device memory");
-          SGO_LAUNCH(k_u_fill, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, s, n, (const int*)L.A.rowptr, (const int*)L.A.col, (const int*)d_ap_rowptr,
-                     (const int*)d_ap_col, (const int*)u_ptr, u_row, u_idx, u_col);
-          UpDev& U = L.U;
-          U.n = un;
-          U.row = u_row;
-          U.idx = u_idx;
-          U.col = u_col;
-          gb.add(G_U, u_ptr, n, un);
-        }
-        if (l == 0) m->level0_bytes += (long long)(72 * nf + 28 * nf);
-      }
-      std::snprintf(line, sizeof line, "(P %d%s, AP %d blocks; %d + %d products) ", P.np, dc.filtered ? " filtered" : "", P.nap, P.ap.n, P.rap.n);
-      m->desc += line;
-    } else {
-      L.gal.n = L.A.nslot;
-      L.gal.src = dc.gal_src;
-      L.gal.tgt = dc.gal_tgt;
-    }
-    const double t_fill = ms_since(tL) - t_coarsen;
-    if (dc.smooth) {
-      // product lists from the patterns: count per target, prefix sum, fill (A P, then P^T A P) -- as amg_create; both lists' totals
-      // behind one synchronisation, their wave groups with the level's batch
-      PDev& P = L.P;
-      ApPattern ap;
-      ap.ap_row = d_ap_row;
-      ap.ap_col = d_ap_col;
-      ap.ap_rowptr = d_ap_rowptr;
-      ap.f_lo = 0;
-      ap.nap = P.nap;
-      const int nseg[2] = {P.nap, dc.nslot_c};
-      const int nprod[2] = {P.ap.n, P.rap.n};
-      ProdMap* maps[2] = {&P.ap, &P.rap};
-      int* ptrs[2] = {nullptr, nullptr};
-      for (int w = 0; w < 2; ++w) {
-        ptrs[w] = dev_alloc<int>(tmp_arena, (size_t)nseg[w] + 1);
-        int* sums = dev_alloc<int>(tmp_arena, (size_t)nseg[w] / kScanChunk + 3);
-        if (!ptrs[w] || !sums) return fail("amg_create: out of device memory");
-        int *la = nullptr, *lb = nullptr, *lt = nullptr;
-        const dim3 grid(grid_for(8LL * nseg[w], kBlock)), block(kBlock);
-        if (w == 0)
-          SGO_LAUNCH((k_ap_list<false>), grid, block, 0, s, ap, (const int*)L.A.rowptr, (const int*)L.A.col, (const int*)P.rowptr,
-                     (const int*)P.col, ptrs[w], la, lb, lt);
-        else
-          SGO_LAUNCH((k_rap_list<false>), grid, block, 0, s, dc.nslot_c, (const int*)C.A.row, (const int*)C.A.col,
-                     (const int*)d_t_ptr, (const int*)P.t_row, (const int*)d_t_idx, ap, ptrs[w], la, lb, lt);
-        dev_scan_exclusive(s, ptrs[w], nseg[w], sums);
-      }
-      int totals[2] = {-1, -1};
-      D.read2(ptrs[0] + nseg[0], ptrs[1] + nseg[1], &totals[0], &totals[1]);
-      if (!D.ok) return fail("amg_create: product-list kernels failed");
-      for (int w = 0; w < 2; ++w) {
-        const int total = totals[w];
-        if (total != nprod[w])
-          return fail("amg_create: internal error (device product lists: " + std::to_string(total) + " products, the patterns say " +
-                      std::to_string(nprod[w]) + ")");
-        int* la = dev_alloc<int>(m->pool, (size_t)std::max(total, 1));
-        int* lb = dev_alloc<int>(m->pool, (size_t)std::max(total, 1));
-        int* lt = dev_alloc<int>(m->pool, (size_t)std::max(total, 1));
-        if (!la || !lb || !lt) return fail("amg_create: out of device memory");
-        const dim3 grid(grid_for(8LL * nseg[w], kBlock)), block(kBlock);
-        if (w == 0)
-          SGO_LAUNCH((k_ap_list<true>), grid, block, 0, s, ap, (const int*)L.A.rowptr, (const int*)L.A.col, (const int*)P.rowptr,
-                     (const int*)P.col, ptrs[w], la, lb, lt);
-        else
-          SGO_LAUNCH((k_rap_list<true>), grid, block, 0, s, dc.nslot_c, (const int*)C.A.row, (const int*)C.A.col,
-                     (const int*)d_t_ptr, (const int*)P.t_row, (const int*)d_t_idx, ap, ptrs[w], la, lb, lt);
-        maps[w]->n = total;
-        maps[w]->a = la;
-        maps[w]->b = lb;
-        maps[w]->tgt = lt;
-        gb.add(w == 0 ? G_APL : G_RAPL, ptrs[w], nseg[w], total);
-        if (l == 0) m->level0_bytes += 12LL * total;
-      }
-    }
-    // ---- every wave-group list of the level in one batch, then the long columns of the two column-ordered copies
-    if (!D.run(gb)) return fail("amg_create: out of device memory");
-    L.mem_grp = gb.grp[G_MEM];
-    L.mem_ngrp = gb.ngrp[G_MEM];
-    C.A.grp = gb.grp[G_C];
-    C.A.ngrp = gb.ngrp[G_C];
-    if (dc.smooth) {
-      PDev& P = L.P;
-      P.val.grp = gb.grp[G_VAL];
-      P.val.ngrp = gb.ngrp[G_VAL];
-      P.r_grp = gb.grp[G_R];
-      P.r_ngrp = gb.ngrp[G_R];
-      P.t_grp = gb.grp[G_T];
-      P.t_ngrp = gb.ngrp[G_T];
-      if (dc.filtered) {
-        P.f_grp = gb.grp[G_F];
-        P.f_ngrp = gb.ngrp[G_F];
-      }
-      P.ap.grp = gb.grp[G_APL];
-      P.ap.ngrp = gb.ngrp[G_APL];
-      P.rap.grp = gb.grp[G_RAPL];
-      P.rap.ngrp = gb.ngrp[G_RAPL];
-      int* d_cnt = dev_alloc<int>(tmp_arena, 2);
-      t_ranges = dev_alloc<int>(m->pool, 2 * (size_t)std::max(P.t_ngrp, 1));
-      if (!d_cnt || !t_ranges) return fail("amg_create: out of device memory");
-      hipMemsetAsync(d_cnt, 0, 2 * sizeof(int), s);
-      SGO_LAUNCH(k_long_groups, dim3(grid_for((long long)P.t_ngrp, kBlock)), dim3(kBlock), 0, s, (const int*)P.t_grp, P.t_ngrp, d_cnt, t_ranges);
-      if (fold_here) {
-        PDev& PS = L.PS;
-        PS.r_grp = gb.grp[G_PSR];
-        PS.r_ngrp = gb.ngrp[G_PSR];
-        PS.t_grp = gb.grp[G_ST];
-        PS.t_ngrp = gb.ngrp[G_ST];
-        if (l > 0) {
-          L.U.grp = gb.grp[G_U];
-          L.U.ngrp = gb.ngrp[G_U];
-        }
-        st_ranges = dev_alloc<int>(m->pool, 2 * (size_t)std::max(PS.t_ngrp, 1));
-        if (!st_ranges) return fail("amg_create: out of device memory");
-        SGO_LAUNCH(k_long_groups, dim3(grid_for((long long)PS.t_ngrp, kBlock)), dim3(kBlock), 0, s, (const int*)PS.t_grp, PS.t_ngrp, d_cnt + 1, st_ranges);
-      }
-      int nl[2] = {0, 0};
-      D.read2(d_cnt, d_cnt + 1, &nl[0], &nl[1]);
-      if (!D.ok) return fail("amg_create: device set-up kernels failed");
-      P.t_nlong = nl[0];
-      P.t_long = nl[0] ? t_ranges : nullptr;
-      if (fold_here) {
-        constexpr int kLongCap = 4096;
-        L.PS.t_long = st_ranges;
-        L.PS.t_nlong = nl[1];
-        L.fold = nl[1] <= kLongCap;
-      }
-    } else {
-      L.gal.grp = gb.grp[G_GAL];
-      L.gal.ngrp = gb.ngrp[G_GAL];
-    }
-    const double t_lists = ms_since(tL) - t_coarsen - t_fill;
-    m->lv.push_back(C);  // invalidates L
-    {
-      AmgLevel& Lr = m->lv[l];
-      AmgLevel& Cr = m->lv[l + 1];
-      Cr.pos = dev_alloc<double>(m->pool, 2 * (size_t)nc);
-      if (!Cr.pos) return fail("amg_create: out of device memory");
-      if (l == 0) SGO_LAUNCH(k_positions0, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, s, n, d_free_id, d_poses, Lr.pos);
-      SGO_LAUNCH(k_centres, dim3(grid_for(nc, kWavesPerBlock)), dim3(kBlock), 0, s, nc, Lr.mem_ptr, Lr.mem, Lr.pos, Cr.pos, Lr.d);
-      launch_coarse_operator(m, s, Lr, Cr, l == 0);
-      if (l + 1 < m->cfg.max_levels) SGO_LAUNCH(k_level_dinv, dim3(grid_for(Cr.A.n, kBlock)), dim3(kBlock), 0, s, Cr.A);
-      // (no synchronisation here: the next level's strengths are read behind its own, the hierarchy's last level behind the caller's)
-    }
-    if (verbose)
-      std::fprintf(stderr, "[sgo] amg level %d, patterns ON THE DEVICE: aggregation + patterns %.2f ms (of which the host's aggregation %.2f), level data %.2f, "
-                   "product lists + groups %.2f, %d synchronisations (n=%d -> %d, %s)\n",
-                   l, t_coarsen, t_host_agg, t_fill, t_lists, D.syncs, n, nc,
-                   dc.smooth ? (dc.filtered ? "filtered smoothing" : "smoothed") : "tentative");
-  }
-  if (hipStreamSynchronize(s) != hipSuccess) return fail("amg_create: device set-up kernels failed");
-  const int last = (int)m->lv.size() - 1;
-  if (last == 0 && m->lv[0].A.n > 1024) return fail("amg_create: graph not coarsenable; use the block-Jacobi solver");
-  m->N = 3 * m->lv[last].A.n;
-  m->Np = (m->N + kGjB - 1) / kGjB * kGjB;
-  if (m->N > 3072) return fail("amg_create: coarsest level too large (" + std::to_string(m->N) + " unknowns)");
-  m->inv0 = dev_alloc<double>(m->pool, (size_t)m->Np * m->Np);
-  m->inv1 = dev_alloc<double>(m->pool, (size_t)m->Np * m->Np);
-  m->gjP[0] = dev_alloc<double>(m->pool, kGjB * kGjB);
-  m->gjP[1] = dev_alloc<double>(m->pool, kGjB * kGjB);
-  m->inv = ((m->Np / kGjB) & 1) ? m->inv1 : m->inv0;
-  m->d_fail = dev_alloc<int>(m->pool, 1);
-  if (!m->inv0 || !m->inv1 || !m->d_fail || !m->gjP[0] || !m->gjP[1]) return fail("amg_create: out of device memory");
-  hipMemsetAsync(m->d_fail, 0, sizeof(int), s);
-  if (last >= 1 && !std::getenv("SGO_AMG_NU") && 4LL * m->lv[1].A.nslot > (long long)m->lv[0].A.nslot) m->cfg.nu_coarse = 1;
-  m->cfg.keep_agg = nullptr;
-  std::snprintf(line, sizeof line, "coarsest dense N=%d; theta=%.3g omega=%.2f nu=%d", m->N, m->cfg.theta * m->cfg.theta_scale, m->cfg.omega,
-                m->cfg.nu_coarse);
-  m->desc += line;
-  return m;
-}

@@ -12,43 +12,6 @@
 
 namespace sgo {
 
-// wave groups over segments [ptr[i], ptr[i+1]): whole segments packed up to 64 items; a longer
-// segment is its own group (same rule as the level-0 row groups in sgo_structure.cpp).  Round 6: the rule is applied
-// independently to chunks of kGroupChunk segments -- a chunk starts a new group --, literally as the device's list builder does
-// (k_group_chunks, sgo_amg.hip): a hierarchy set up on the device (sgo_amg_dev.inc) then has the SAME groups as one set up here,
-// and with them the same association order inside every wavefront segmented scan (its DPP steps are tied to the lanes' positions):
-// the two are bit-identical, which is what tests/test_gpu_device_setup.py asserts.  The grouping never changes WHICH terms a sum has.
-std::vector<int> make_groups(const std::vector<int>& ptr) {
-  std::vector<int> grp;
-  const int nseg = (int)ptr.size() - 1;
-  for (int s0 = 0; s0 < nseg; s0 += kGroupChunk) {
-    const int s1 = std::min(nseg, s0 + kGroupChunk);
-    int cur = 0, start = ptr[s0];
-    bool open = false;
-    for (int f = s0; f < s1; ++f) {
-      const int b = ptr[f], len = ptr[f + 1] - b;
-      if (open && cur + len > 64) {
-        grp.push_back(start);
-        open = false;
-        cur = 0;
-      }
-      if (!open) {
-        start = b;
-        open = true;
-      }
-      cur += len;
-      if (cur >= 64) {
-        grp.push_back(start);
-        open = false;
-        cur = 0;
-      }
-    }
-    if (open) grp.push_back(start);
-  }
-  grp.push_back(nseg >= 0 ? ptr[nseg] : 0);   // (the list is closed by the total)
-  return grp;
-}
-
 namespace {
 
 // Greedy root-node aggregation (Vanek et al.) on the strength graph
@@ -254,7 +217,7 @@ bool sa_symbolic(const HostLevel& H, const std::vector<int>& agg, int nc, const 
     }
   });
   val_ptr[np] = nval;
-  o.val_grp = make_groups(val_ptr);
+  o.val_ptr = std::move(val_ptr);
   lap("P");
   // ---- early verdict on the coarse operator's size from every 32nd coarse row (the exact count comes after the AP
   // pattern and product lists, which cost several times this whole function's share so far; graphs with long-range
@@ -384,8 +347,6 @@ bool sa_symbolic(const HostLevel& H, const std::vector<int>& agg, int nc, const 
       o.t_col[t] = o.p_col[e];
     }
   }
-  o.t_grp = make_groups(t_ptr);
-  o.r_grp = make_groups(o.p_rowptr);
   lap("P^T lists");
   o.nap = ap_rowptr[n];
   const int nprod_ap = (int)app[n];
@@ -448,7 +409,7 @@ bool sa_symbolic(const HostLevel& H, const std::vector<int>& agg, int nc, const 
     }
   });
   ap_ptr[o.nap] = nprod_ap;
-  o.ap_grp = make_groups(ap_ptr);
+  o.ap_ptr = std::move(ap_ptr);
   lap("AP fill");
   }
   // ---- A_c = P^T AP: coarse row a collects, over the entries (i, a) of column a of P, row i of AP
@@ -578,7 +539,7 @@ bool sa_symbolic(const HostLevel& H, const std::vector<int>& agg, int nc, const 
     }
   });
   rap_ptr[C.nslot] = nprod_rap;
-  o.rap_grp = make_groups(rap_ptr);
+  o.rap_ptr = std::move(rap_ptr);
   }
   // slot (a, c), c > a  ->  slot (c, a): where the numeric kernel stores the transposed block
   o.rap_mirror.assign((size_t)C.nslot, -1);
@@ -603,9 +564,9 @@ bool sa_symbolic(const HostLevel& H, const std::vector<int>& agg, int nc, const 
     if (lower != mirrored) return false;
   }
   lap("RAP fill");
+  o.t_ptr = std::move(t_ptr);
   if (lists_on_device) {
     o.ap_rowptr = std::move(ap_rowptr);
-    o.t_ptr = std::move(t_ptr);
     o.t_idx = std::move(t_idx);
   }
   return true;
@@ -641,7 +602,7 @@ void host_coarsen(const HostLevel& H, const std::vector<double>& w, const AmgCon
   auto ms_since = [](std::chrono::steady_clock::time_point t) {
     return 1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t).count();
   };
-  if (scratch) scratch->rewind();   // (the previous level's lists have been uploaded: amg_create synchronises per level)
+  if (scratch) scratch->rewind();   // (the previous level's lists have been uploaded: upload_coarse, sgo_amg.hip, synchronises)
   double theta_used = theta_l;
   int nc;
   if (o.reuse_agg && (int)agg.size() == n && o.nc > 0) {
@@ -836,10 +797,8 @@ void host_coarsen(const HostLevel& H, const std::vector<double>& w, const AmgCon
       o.err = "amg_create: internal error (coarse diagonal slot missing)";
       return;
     }
-    o.grp_g = make_groups(cptr);
   }
   o.smooth = smooth;
-  o.grp_c = make_groups(Hc.rowptr);
   o.t_all = ms_since(tA);
 }
 

@@ -1,10 +1,9 @@
-// sgo_amg_host.h -- host side of the multigrid set-up (sgo_amg_host.cpp): aggregation, patterns of the smoothed transfer
-// and of the Galerkin products, structure of the next level.  No device code; amg_create (sgo_amg.hip) uploads what this
-// produces and makes the product lists on the device from the patterns.
-// Round 6: on one GPU the default set-up takes only the AGGREGATION from here (host_aggregate) and makes everything else on the
-// device (amg_create_dev, sgo_amg_dev.inc), bit-identical to what host_coarsen + amg_create produce; this path stays as the
-// multi-GPU modes' set-up, as SGO_AMG_SETUP=host, as the fallback of a device set-up that cannot be made, and as the reference the
-// device set-up is tested against (tests/test_gpu_device_setup.py).
+// sgo_amg_host.h -- the host producer of the multigrid set-up (sgo_amg_host.cpp): aggregation, patterns of the smoothed transfer and
+// of the Galerkin products, structure of the next level.  No device code.  amg_create (sgo_amg.hip) uploads a HostCoarse as the
+// DevCoarse its one level assembler takes, the same result the device producer (dev_coarsen, sgo_amg_dev.inc) makes on the device,
+// bit-identical.  The device producer is the default on one GPU; this one is the multi-GPU modes' set-up, SGO_AMG_SETUP=host, the
+// fallback of a device set-up that cannot be made, and the reference the device producer is tested against
+// (tests/test_gpu_device_setup.py).
 #pragma once
 #include <memory>
 #include <string>
@@ -14,11 +13,6 @@
 #include "sgo_internal.h"
 
 namespace sgo {
-
-// wave groups over segments [ptr[i], ptr[i+1]): whole segments packed up to 64 items; a longer
-// segment is its own group (same rule as the level-0 row groups in sgo_structure.cpp)
-constexpr int kGroupChunk = 256;   // segments per chunk of the grouping rule (host: make_groups; device: k_group_chunks)
-std::vector<int> make_groups(const std::vector<int>& ptr);
 
 // Host side of the smoothed-aggregation set-up: patterns of P, AP = A P and A_c = P^T AP and, for
 // every entry of each, the block products that make it up, listed in target order (all sorting is
@@ -52,18 +46,19 @@ struct SaHost {
   bool filtered = false;
   std::vector<unsigned char> strong;   // [nslot] 1 = kept by the filter (diagonal and alias slots included); empty when !filtered
   std::vector<int> val_rowptr;         // [n + 1] range of row i's value products in val_src / val_tgt (the row's KEPT slots)
-  std::vector<int> p_rowptr, p_row, p_col, val_grp;
+  std::vector<int> p_rowptr, p_row, p_col;
+  std::vector<int> val_ptr;            // [np + 1] first value product of every entry of P
   UVec val_src, val_tgt;   // (the large lists live in the set-up's scratch arena: storage kept between set-ups, no fresh pages)
-  std::vector<int> r_grp, t_pos, t_row, t_col, t_grp;
+  std::vector<int> t_ptr, t_pos, t_row, t_col;   // entries by coarse column: [nc + 1] column pointers, position of entry e, row / column at a position
   int nap = 0;
   UVec ap_a, ap_b, ap_tgt;
-  std::vector<int> ap_grp;
+  std::vector<int> ap_ptr;             // [nap + 1] first product of every A P entry in ap_*
   HostLevel Hc;
   UVec rap_a, rap_b, rap_tgt;
-  std::vector<int> rap_grp, rap_mirror;
+  std::vector<int> rap_ptr, rap_mirror;   // rap_ptr: [coarse slots + 1] first product of every slot in rap_*
   // lists_on_device: the product lists (ap_*, rap_*) are NOT made here; the patterns they follow from are kept instead
   bool lists_on_device = false;
-  std::vector<int> ap_rowptr, t_ptr, t_idx;
+  std::vector<int> ap_rowptr, t_idx;
   UVec ap_col, ap_row;
   long long n_ap_prod = 0, n_rap_prod = 0;
 };
@@ -80,7 +75,7 @@ struct HostCoarse {
   bool smooth = false;   // (sa.filtered says which smoothing)
   SaHost sa;
   HostLevel Hc;
-  std::vector<int> order, tgt, cptr, grp_g, grp_c;
+  std::vector<int> order, tgt, cptr;   // tentative transfer: fine slot of contribution t, its coarse slot; coarse slot -> contributions
   double t_agg = 0, t_sort = 0, t_all = 0;
   std::string err;
 };

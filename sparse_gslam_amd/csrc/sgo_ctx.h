@@ -107,7 +107,7 @@ struct sgo_ctx {
   // The hierarchy a TRIAL rebuild replaced (optimize_gn's re-aggregation rule): kept with its arena until the trial is decided -- a
   // re-made hierarchy that does not solve visibly faster is dropped for it (revert_amg) -- or until the next rebuild.
   DevArena amg_arena_prev;
-  DevArena amg_tmp_arena;         // temporaries of the device set-up (sgo_amg_dev.inc): rewound per level, kept between set-ups
+  DevArena amg_tmp_arena;         // temporaries of the multigrid set-up (amg_create): rewound per level, kept between set-ups
   Amg* amg_prev = nullptr;
   std::string amg_prev_desc;
   // The environment knobs a solve depends on, read ONCE per entry-point call (read_call_knobs: sgo_optimize_gn, sgo_solve) and

@@ -762,8 +762,8 @@ int build_amg(sgo_ctx* c, bool keep_old, bool keep_agg) {
   const bool pre0_agg = pre0_ready && amg_host_l0_agg_only(c->l0_pre);
   const bool dev_setup = !c->owner && !multi_rank(c) && (pre0_agg || (!pre0_ready && (c->knobs.setup_mode == 2 || (c->knobs.setup_mode == 1 && c->call.in_optimize))));
   if (dev_setup)
-    c->amg = amg_create_dev(c->stream, c->A, c->S0, c->T0, c->H0, c->d_poses, c->d_free_id, cfg, prof, &aerr, &c->amg_scratch, &c->amg_arena,
-                            &c->amg_tmp_arena, c->knobs.dev_aggregation, pre0_agg ? c->l0_pre : nullptr);
+    c->amg = amg_create(c->stream, c->A, c->S0, c->T0, c->H0, c->d_poses, c->d_free_id, cfg, prof, &aerr, &c->amg_scratch, &c->amg_arena,
+                        &c->amg_tmp_arena, c->knobs.dev_aggregation ? AmgPatterns::device_aggregation : AmgPatterns::device, c->l0_pre);
   if (dev_setup && c->amg && c->knobs.fail_device_setup) {   // test hook (SGO_TEST_FAIL_DEVICE_SETUP): the device set-up "fails"
     amg_destroy(c->amg);
     c->amg = nullptr;
@@ -777,8 +777,8 @@ int build_amg(sgo_ctx* c, bool keep_old, bool keep_agg) {
     aerr.clear();
   }
   if (!c->amg)
-    c->amg = amg_create(c->stream, c->A, c->S0, c->T0, c->H0, c->d_poses, c->d_free_id, cfg, prof, &aerr, &c->amg_scratch,
-                        &c->amg_arena, pre0_agg ? nullptr : c->l0_pre, c->owner ? &ah : nullptr);
+    c->amg = amg_create(c->stream, c->A, c->S0, c->T0, c->H0, c->d_poses, c->d_free_id, cfg, prof, &aerr, &c->amg_scratch, &c->amg_arena,
+                        &c->amg_tmp_arena, AmgPatterns::host, c->l0_pre, c->owner ? &ah : nullptr);
   l0_discard(c);
   if (c->opts.verbose)
     std::fprintf(stderr, "[sgo] multigrid set-up (%s): %.2f ms\n", dev_setup ? (c->knobs.dev_aggregation ? "aggregation and patterns on the device" : "host aggregation, patterns on the device") : "host", 1e3 * (wall_s() - t_create0));

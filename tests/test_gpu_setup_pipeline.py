@@ -62,11 +62,11 @@ def test_unused_helper_results_are_dropped_cleanly(monkeypatch):
 
 @pytest.mark.parametrize("name", ["C2", "big"])
 def test_device_made_product_lists_equal_the_host_lists(monkeypatch, name):
-    """The lists of block products behind every entry of A P and P^T A P are made on the device from the host's
-    patterns (k_ap_list / k_rap_list, prefix sums, wave groups); SGO_AMG_LISTS=host makes them on the host as before.
-    Same products in the same order per target; the wave-group boundaries differ (the device packs chunks of 2048
-    targets independently), and with them the association order of the wavefront segmented sums: identical
-    hierarchies and product counts, iterates equal to rounding."""
+    """The lists of block products behind every entry of A P and P^T A P are made on the device from the patterns
+    (k_ap_list / k_rap_list, prefix sums); SGO_AMG_LISTS=host makes them on the host as before.  Same products in the
+    same order per target, grouped by the same code in the level's batch.  The host lists go with the host set-up, whose
+    cycle is not folded (amg_effective_config), while the default folds it: the same preconditioner in exact arithmetic,
+    rounded differently.  Identical hierarchies, product counts and PCG counts, iterates equal to rounding."""
     arrs = synth.config("C2", info_mode="full").arrays() if name == "C2" else _graph(0.0)
     res = []
     for mode in ("device", "host"):
