@@ -1655,11 +1655,39 @@ struct AmgLevel {
   FoldDev F;
   UpDev U;
   // work vectors [n][3]
-  double *xs = nullptr, *rs = nullptr;                     // smoother state of cycle()
+  double *xs = nullptr, *rs = nullptr;                     // smoother state of the cycle
   double* tR = nullptr;                                    // second residual buffer of multi-sweep smoothing
   double *bk = nullptr, *xk = nullptr, *z1 = nullptr, *z2 = nullptr, *q = nullptr;  // K-cycle FCG (levels >= 1)
   double *bk2 = nullptr, *p2 = nullptr, *q2 = nullptr;     // residual after the first FCG step; second direction; A p2
   double *pA = nullptr, *pB = nullptr, *pC = nullptr;      // [2][kMaxPartials] each
+};
+
+// Level 0 of a multi-GPU run (the coarser levels are replicated on every rank), as one value:
+//   single     one GPU: every unit, every row;
+//   allreduce  the cycle's two level-0 passes evaluate the work units [u0, u1) (= the rows [row0, row1)) only; the ranks' partial
+//              coarse right-hand sides are summed over `comm`, the post-smoothing pass's result is summed as a whole -- or, with
+//              `part`, all-gathered by rank slices;
+//   owner      row-owner mode (sgo_internal.h): all level-0 work on the owned rows of the partition `part`, boundary exchanges.
+// A collective that fails is recorded here (the cycle is captured into a graph and has no way to return it): amg_comm_failed.
+struct Shard0 {
+  enum Mode { single, allreduce, owner } mode = single;
+  int u0 = 0, u1 = 0, row0 = 0, row1 = 0;   // (0, 0: all)
+  int G = 1;                        // owner: the ranks that share the level-0 passes (the profile books 1 / G of their bytes)
+  Comm* comm = nullptr;             // sums over the ranks (rank emulation, sgo_debug_set_shard: no live communicator, a no-op)
+  const HaloDev* part = nullptr;    // owner: the partition; allreduce: the rank slices product vectors are gathered by (optional)
+  bool failed = false;
+  void reduce(hipStream_t s, double* buf, size_t count) {   // in-place sum over the ranks
+    std::string e;
+    if (comm && !comm->allreduce_f64(buf, count, s, &e)) failed = true;
+  }
+  void exchange(hipStream_t s, double* data, int width, const int* idx, int idx_max) {   // owner: records of the boundary rows
+    std::string e;
+    if (comm && !halo_exchange(*part, s, data, width, idx, idx_max, HaloScalars(), &e)) failed = true;
+  }
+  void gather(hipStream_t s, double* vec) {   // every rank's slice of a [n][3] vector to every rank
+    std::string e;
+    if (!halo_gather_slices(*part, s, vec, 3, &e)) failed = true;
+  }
 };
 
 struct Amg {
@@ -1667,11 +1695,7 @@ struct Amg {
   AmgProf prof;
   Sym0Dev S0;               // level-0 operator in symmetric storage (lv[0].A is its logical view)
   Tile0Dev T0;              // ... and its tile view
-  Comm* comm = nullptr;     // multi-GPU, all-reduce mode: level-0 products over the units [u0, u1) (= rows [row0, row1)) + all-reduce
-  const HaloDev* halo = nullptr;   // multi-GPU, row-owner mode (sgo_internal.h): level-0 work on the owned rows, boundary exchanges
-  const HaloDev* slices = nullptr; // multi-GPU, all-reduce mode with a communicator: product vectors all-gathered by rank slices
-  int u0 = 0, u1 = 0, row0 = 0, row1 = 0;
-  bool comm_failed = false;
+  Shard0 shard;
   long long level0_bytes = 0;   // device bytes of the level-0 transfer data (P blocks, A P blocks, product lists)
   DevArena* pool = nullptr;   // the caller's arena (not owned)
   std::vector<AmgLevel> lv;
@@ -1716,17 +1740,15 @@ double bytes_spmv(const BsrDev& A) { return 80.0 * A.nslot + 48.0 * A.n; }
 // A P of its own fine rows -- A P needs the P rows of the neighbours' boundary rows: one exchange of 72-byte records --
 // and its rows' share of P^T A P; the ranks' partial coarse operators are summed by an all-reduce of the level-1 blocks.
 void launch_coarse_operator(Amg* m, hipStream_t s, AmgLevel& L, AmgLevel& C, bool level0) {
-  const HaloDev* H = level0 ? m->halo : nullptr;
-  const int row0 = H ? H->row0 : 0, row1 = H ? H->row1 : 0;
+  Shard0& sh = m->shard;
+  const bool own = level0 && sh.mode == Shard0::owner;
+  const int row0 = own ? sh.row0 : 0, row1 = own ? sh.row1 : 0;
   if (!L.smoothed) {
     {
       Scope sc(m->prof, level0 ? K_GALERKIN0 : K_GALERKIN, (72.0 + 16.0 + 32.0) * L.A.nslot + 72.0 * C.A.nslot);
       SGO_LAUNCH(k_galerkin, dim3(grid_for(L.gal.ngrp, kWavesPerBlock)), dim3(kBlock), 0, s, L.A, C.A, L.gal, L.d, row0, row1);
     }
-    if (H && H->comm) {
-      std::string e;
-      if (!H->comm->allreduce_f64(C.A.blk, 9 * (size_t)C.A.nslot, s, &e)) m->comm_failed = true;
-    }
+    if (own) sh.reduce(s, C.A.blk, 9 * (size_t)C.A.nslot);
     return;
   }
   PDev& P = L.P;
@@ -1740,10 +1762,7 @@ void launch_coarse_operator(Amg* m, hipStream_t s, AmgLevel& L, AmgLevel& C, boo
     SGO_LAUNCH(k_p_values, dim3(grid_for(P.val.ngrp, kWavesPerBlock)), dim3(kBlock), 0, s, L.A, P, (const int*)L.agg,
                (const double*)L.d, m->cfg.omega_p, row0, row1);
   }
-  if (H && H->comm) {
-    std::string e;
-    if (!halo_exchange(*H, s, P.blk, 9, H->pent, H->pemax, HaloScalars(), &e)) m->comm_failed = true;
-  }
+  if (own) sh.exchange(s, P.blk, 9, sh.part->pent, sh.part->pemax);
   {
     Scope sc(m->prof, level0 ? K_SA_AP0 : K_SA_AP, 156.0 * P.ap.n + 72.0 * P.nap);
     SGO_LAUNCH((k_block_products<true, false, false>), dim3(grid_for(P.ap.ngrp, kWavesPerBlock)), dim3(kBlock), 0, s,
@@ -1762,26 +1781,196 @@ void launch_coarse_operator(Amg* m, hipStream_t s, AmgLevel& L, AmgLevel& C, boo
                P.rap, BsrDev(), (const double*)P.blk, (const double*)P.apblk, C.A.blk, (size_t)C.A.nslot, (const int*)P.rap_mirror,
                (const int*)P.row, row0, P.local_lists ? 0 : row1, 1);
   }
-  if (H && H->comm) {
-    std::string e;
-    if (!H->comm->allreduce_f64(C.A.blk, 9 * (size_t)C.A.nslot, s, &e)) m->comm_failed = true;
-  }
+  if (own) sh.reduce(s, C.A.blk, 9 * (size_t)C.A.nslot);
 }
 
 // The coarse solution of level l as seen by its parent: xk (dense level) or the flexible-CG
 // combination c1 z1 + c2 p2 whose scalars are ratios of the partial sums the FCG SpMVs left
 // in pA / pB (never materialised: the consumers apply it on the fly).
 struct CoarseSol {
-  const double* u1 = nullptr;
-  const double* u2 = nullptr;
+  const double *u1 = nullptr, *u2 = nullptr;
   SpmvRatio c1, c2;
 };
+// The K-cycle's second step: the cycle runs for rhs - c sub, which its first launch forms on the fly and stores to `out`.
+struct RhsSub { const double* sub; SpmvRatio c; double* out; };
+// Partial sums of vec . z (and vec2 . z) asked of the cycle's last launch (vec == nullptr: none).
+struct DotReq { const double *vec = nullptr, *vec2 = nullptr; double* parts = nullptr; };
 
+// The form of level l's cycle and its sweeps per side.  Folded (see "folded V-cycle"): one sweep per side, inside the transfer P~.
+// Two sweeps per side = one explicit sweep around the folded cycle: S E S with E the folded cycle's error propagator.
+struct CycleForm { int nu; enum { unfolded, folded, folded_in_two_sweeps } kind; };
+CycleForm cycle_form(const Amg* m, int l, bool rhs_sub, bool dots) {
+  const AmgLevel& L = m->lv[l];
+  CycleForm f{(l > 0 && L.tR && L.smoothed) ? std::max(1, m->cfg.nu_coarse) : 1, CycleForm::unfolded};
+  if (!L.fold || rhs_sub) return f;
+  if (l == 0) {   // multi-GPU runs keep level 0 unfolded
+    if (m->shard.mode == Shard0::single) f.kind = CycleForm::folded;
+  } else if (!dots) {   // a cycle that must deliver dot products on a level >= 1 is unfolded
+    if (f.nu == 1) f.kind = CycleForm::folded;
+    if (f.nu == 2) f.kind = CycleForm::folded_in_two_sweeps;
+  }
+  return f;
+}
+
+CoarseSol coarse_solve(Amg* m, hipStream_t s, int l, const PcgScalars* S);
+
+// ---- steps shared by the levels
+// C.bk = P^T res (P~^T: `folded`; sums over the aggregates for a tentative transfer).  Level 0 of a multi-GPU run: from this rank's
+// rows only -- a partial coarse right-hand side, which the caller all-reduces (3 n_c doubles instead of the residual's 3 n).
+void restrict_level(Amg* m, hipStream_t s, int l, const double* res, const PcgScalars* S, bool folded = false) {
+  AmgLevel& L = m->lv[l];
+  AmgLevel& C = m->lv[l + 1];
+  const int row0 = l == 0 ? m->shard.row0 : 0, row1 = l == 0 ? m->shard.row1 : 0;
+  if (l == 0 && m->shard.mode == Shard0::owner && L.smoothed && L.P.local_lists)
+    hipMemsetAsync(C.bk, 0, sizeof(double) * 3 * (size_t)C.A.n, s);   // coarse rows none of this rank's rows reaches
+  if (L.smoothed) {
+    const PDev& P = folded ? L.PS : L.P;
+    Scope sc(m->prof, l == 0 ? K_RESTRICT_P0 : K_RESTRICT_P, 44.0 * P.t_n + 24.0 * L.A.n + 24.0 * L.nc);
+    launch_restrict_p(s, P, res, C.bk, S, row0, row1);
+  } else {
+    Scope sc(m->prof, l == 0 ? K_RESTRICT0 : K_RESTRICT, 40.0 * L.A.n + 24.0 * L.nc);
+    SGO_LAUNCH(k_restrict, dim3(grid_for(L.mem_ngrp, kWavesPerBlock)), dim3(kBlock), 0, s, L.mem_ngrp, L.mem_grp, L.mem, L.agg, L.d, res, C.bk, S, row0, row1);
+  }
+}
+// out = x' + omega Dinv (b - A x'), one Jacobi sweep on a coarse level: x' = x, or with `cs` x + T (coarse solution) for the
+// tentative transfer T, gathered on the fly (SPMV_JACOBI_P).  Returns the grid (of the dot products' partial sums).
+int jacobi_sweep(Amg* m, hipStream_t s, AmgLevel& L, const double* x, const double* b, double* out, const PcgScalars* S,
+                 const DotReq& dots = DotReq(), const CoarseSol* cs = nullptr) {
+  SpmvArgs a{};
+  a.x = x; a.b = b; a.y = out; a.omega = m->cfg.omega; a.S = S;
+  if (dots.vec) { a.dotA = dots.vec; a.dotA2 = dots.vec2; a.partials = dots.parts; }
+  if (cs) {
+    a.agg = L.agg; a.d = L.d; a.u1 = cs->u1; a.u2 = cs->u2; a.c1 = cs->c1; a.c2 = cs->c2;
+    Scope sc(m->prof, K_SPMV_JACOBI_P, 80.0 * L.A.nslot + 140.0 * L.A.n + 48.0 * L.nc);
+    return launch_spmv_ex(s, L.A, SPMV_JACOBI_P, a);
+  }
+  Scope sc(m->prof, K_SPMV_JACOBI, 80.0 * L.A.nslot + 120.0 * L.A.n);
+  return launch_spmv_ex(s, L.A, SPMV_JACOBI, a);
+}
+
+// ---- level 0: symmetric storage (tile or wave-group kernel, fp32 or fp64 blocks), three multi-GPU modes (Shard0)
+// One level-0 pass of the cycle (S0_RESID or S0_JACOBI) over this rank's 1 / `ranks` of the work, booked as what launches: the
+// tile kernel reads the fp32 copy of the blocks whenever there is one, the wave-group kernel never.  Returns the grid.
+int pass0(Amg* m, hipStream_t s, int mode, const Spmv0Args& a, int ranks = 1) {
+  const bool tile = m->T0.ntile > 0, f32 = tile && m->S0.fblk != nullptr;
+  const int kid = mode == S0_RESID ? (tile ? (f32 ? K_SPMV0T_RESID_F32 : K_SPMV0T_RESID) : K_SPMV0_RESID)
+                                   : (tile ? (f32 ? K_SPMV0T_JACOBI_F32 : K_SPMV0T_JACOBI) : K_SPMV0_JACOBI);
+  Scope sc(m->prof, kid, bytes_spmv0(m->S0, mode, f32) / ranks);
+  return launch_spmv0_any(s, m->S0, m->T0, mode, a);
+}
+// xs = omega Dinv rhs, the first sweep from zero (normally left by the producer of rhs: AmgXs0)
+void first_sweep0(Amg* m, hipStream_t s, const double* rhs, AmgXs0 xs0) {
+  if (xs0 != AmgXs0::compute) return;
+  const Shard0& sh = m->shard;
+  const bool own = sh.mode == Shard0::owner;   // (its owned rows; every other mode: all rows)
+  const size_t r0 = own ? sh.row0 : 0;
+  Scope sc(m->prof, K_DOT, 96.0 * m->lv[0].A.n);
+  launch_precond_bj(s, own ? sh.row1 - sh.row0 : m->lv[0].A.n, m->S0.dinv + 6 * r0, rhs + 3 * r0, m->lv[0].xs + 3 * r0, m->cfg.omega);
+}
+// The first sweep, then the residual rs = rhs - H xs in one pass over the stored blocks.  Multi-GPU: this rank's units only -- the
+// residual stays a per-rank partial (this rank's rows), which is all the restriction reads.
+void presmooth0(Amg* m, hipStream_t s, const double* rhs, const PcgScalars* S, AmgXs0 xs0) {
+  AmgLevel& L = m->lv[0];
+  Shard0& sh = m->shard;
+  first_sweep0(m, s, rhs, xs0);
+  // row-owner mode: the neighbours' boundary rows of xs (unless the caller keeps them current itself)
+  if (sh.mode == Shard0::owner && xs0 != AmgXs0::ready_with_halo) sh.exchange(s, L.xs, 3, sh.part->bnd, sh.part->bmax);
+  if (sh.mode == Shard0::allreduce && !sh.part) hipMemsetAsync(L.rs, 0, sizeof(double) * 3 * (size_t)L.A.n, s);
+  Spmv0Args a{};
+  a.x = L.xs; a.b = rhs; a.y = L.rs; a.S = S; a.u0 = sh.u0; a.u1 = sh.u1;
+  if (sh.mode == Shard0::single || a.u1 > a.u0) pass0(m, s, S0_RESID, a, sh.G);
+}
+// xs += P (coarse solution), a launch of its own on level 0 (fused into the sweep, the extra gathers would cost more than the
+// launch).  Row-owner mode: on the owned rows, and on this rank's copies of the neighbours' boundary rows (k_prolong_rows: the
+// coarse solution is replicated, so the corrected xs needs no exchange).
+void prolong0(Amg* m, hipStream_t s, const CoarseSol& cs, const PcgScalars* S) {
+  AmgLevel& L = m->lv[0];
+  const Shard0& sh = m->shard;
+  const bool own = sh.mode == Shard0::owner;
+  const int row0 = own ? sh.row0 : 0, row1 = own ? sh.row1 : 0;
+  if (L.smoothed) {
+    Scope sc(m->prof, K_PROLONG_P0, 44.0 * L.P.r_n + 52.0 * L.A.n);
+    SGO_LAUNCH(k_prolong_p, dim3(grid_for(L.P.r_ngrp, kWavesPerBlock)), dim3(kBlock), 0, s, L.A.n, L.P, cs.u1, cs.c1, cs.u2, cs.c2,
+               L.xs, S, (const double*)nullptr, row0, row1);
+  } else {
+    Scope sc(m->prof, K_PROLONG0, 68.0 * L.A.n);
+    SGO_LAUNCH(k_prolong_add, dim3(grid_for(own ? row1 - row0 : L.A.n, kBlock)), dim3(kBlock), 0, s, L.A.n, L.agg, L.d, cs.u1, cs.c1,
+                       cs.u2, cs.c2, L.xs, S, (const double*)nullptr, row0, row1);
+  }
+  if (own && sh.part->nhalo > 0) {
+    const HaloDev& H = *sh.part;
+    SGO_LAUNCH(k_prolong_rows, dim3(grid_for(H.nhalo, kBlock)), dim3(kBlock), 0, s, H.nhalo, H.halo_rows, L.smoothed ? L.P : PDev(),
+               (const int*)L.agg, (const double*)L.d, cs.u1, cs.c1, cs.u2, cs.c2, L.xs, S);
+  }
+}
+// out = xs + omega Dinv (rhs - H xs) on the symmetric storage, with the dot products.  Returns the grid of their partial sums.
+int postsmooth0(Amg* m, hipStream_t s, const double* rhs, double* out, const DotReq& dots, const PcgScalars* S) {
+  AmgLevel& L = m->lv[0];
+  Shard0& sh = m->shard;
+  Spmv0Args b{};
+  b.x = L.xs; b.b = rhs; b.y = out; b.omega = m->cfg.omega; b.S = S; b.u0 = sh.u0; b.u1 = sh.u1;
+  if (sh.mode != Shard0::allreduce) {
+    // single GPU | row-owner mode, this rank's tiles: the dot products ride on the kernel -- there as per-workgroup partials of the
+    // OWNED rows (the caller exchanges their sums)
+    if (dots.vec) { b.dotA = dots.vec; b.dotA2 = dots.vec2; b.partials = dots.parts; }
+    return pass0(m, s, S0_JACOBI, b, sh.G);
+  }
+  // all-reduce mode: this rank's rows, zeros elsewhere, all-reduce (or the ranks' slices gathered: one contributor per row, no
+  // zero fill), then the dot products on the full vector (replicated)
+  if (!sh.part) hipMemsetAsync(out, 0, sizeof(double) * 3 * (size_t)L.A.n, s);
+  if (b.u1 > b.u0) pass0(m, s, S0_JACOBI, b);
+  if (sh.part) sh.gather(s, out);
+  else sh.reduce(s, out, 3 * (size_t)L.A.n);
+  if (!dots.vec) return 0;
+  const int grid = grid_for(3LL * L.A.n, kBlock);
+  Scope sc(m->prof, K_DOT, 72.0 * L.A.n);
+  SGO_LAUNCH(k_dots2, dim3(grid), dim3(kBlock), 0, s, 3 * L.A.n, (const double*)out, dots.vec, dots.vec2, dots.parts, S);
+  return grid;
+}
+// out = cycle(0, rhs) in the folded form (see "folded V-cycle"; single GPU): restriction with P~^T of the right-hand side itself,
+// coarse solve, prolongation with P~ onto the two-sweep term M2 rhs = xs + omega Dinv (rhs - H xs), the level-0 Jacobi pass (into
+// rs).  (That pass does not depend on the coarse levels; running it BESIDE them on a second stream -- a parallel branch of the captured
+// hipGraph -- was measured: the fork and join cost 25 us per PCG iteration on this runtime, C2 1.45 -> 1.95 ms per GN iteration.)
+int cycle0_fold(Amg* m, hipStream_t s, const double* rhs, double* out, const DotReq& dots, const PcgScalars* S, AmgXs0 xs0) {
+  AmgLevel& L = m->lv[0];
+  AmgLevel& C = m->lv[1];
+  first_sweep0(m, s, rhs, xs0);
+  Spmv0Args b{};
+  b.x = L.xs; b.b = rhs; b.y = L.rs; b.omega = m->cfg.omega; b.S = S;
+  if (m->T0.ntile == 0) {   // wave-group kernel: the pass and the restriction in one launch
+    const int nb_spmv = grid_for(m->S0.ngrp, kWavesPerBlock), nb_main = grid_for(L.PS.t_ngrp, kWavesPerBlock);
+    Scope sc(m->prof, K_JACOBI0_RESTRICT, bytes_spmv0(m->S0, S0_JACOBI) + 44.0 * L.PS.t_n + 24.0 * L.A.n + 24.0 * L.nc);
+    SGO_LAUNCH(k_jacobi0_restrict, dim3(nb_spmv + nb_main + L.PS.t_nlong), dim3(kBlock), 0, s, m->S0, b, nb_spmv, L.PS, C.bk, nb_main);
+  } else {
+    pass0(m, s, S0_JACOBI, b);
+    restrict_level(m, s, 0, rhs, S, true);
+  }
+  const CoarseSol cs = coarse_solve(m, s, 0, S);
+  // (the dot products' partial sums are re-reduced by every workgroup of the consumer: a few hundred of them, not thousands)
+  const int grid = std::min(grid_for(L.PS.r_ngrp, kFoldThreads / 64), 512);
+  Scope sc(m->prof, K_PROLONG_FOLD0, 44.0 * L.PS.r_n + 72.0 * L.A.n);
+  SGO_LAUNCH(k_prolong_fold, dim3(grid), dim3(kFoldThreads), 0, s, L.PS, cs.u1, cs.c1, cs.u2, cs.c2, (const double*)L.rs, out, S, dots.vec,
+             dots.vec2, dots.vec ? dots.parts : nullptr);
+  return grid;
+}
+// out = cycle(0, rhs), the whole preconditioner: pre-smoothing from zero + residual, restriction, coarse solve (dense inverse, a
+// V-cycle or flexible-CG steps), prolongation, post-smoothing.  Partial sums of dots.vec . out (and dots.vec2 . out): returns their grid.
+int cycle0(Amg* m, hipStream_t s, const double* rhs, double* out, const DotReq& dots, const PcgScalars* S, AmgXs0 xs0) {
+  if (cycle_form(m, 0, false, dots.vec).kind == CycleForm::folded) return cycle0_fold(m, s, rhs, out, dots, S, xs0);
+  presmooth0(m, s, rhs, S, xs0);
+  restrict_level(m, s, 0, m->lv[0].rs, S);
+  m->shard.reduce(s, m->lv[1].bk, 3 * (size_t)m->lv[1].A.n);   // the ranks' partials (each from its own fine rows) -> their sum
+  const CoarseSol cs = coarse_solve(m, s, 0, S);
+  prolong0(m, s, cs, S);
+  return postsmooth0(m, s, rhs, out, dots, S);
+}
+
+// ---- levels >= 1: BsrDev; transfer by the smoothed P with nu sweeps per side, or by the tentative one fused into the sweeps
 // xs = omega Dinv rhs (first sweep from zero), rs = rhs - A xs on a coarse level.  One fused launch (the gathered operand is
 // omega Dinv[col] rhs[col]: 72 B per slot) where a launch costs more than the level's data; on a LARGE level (C5's first coarse
 // levels: millions of slots) the sweep from zero as a vector kernel of its own and a plain residual pass that gathers 24 B per slot.
 constexpr int kUnfuseSlots = 400000;   // (swept on C5 / C4r: 10^6 87.0 / 64.4 M edge-Jacobians/s, 4 10^5 89.4 / 65.3, 1.5 10^5 89.9 / 64.8, 5 10^4 90.3 / 63.4)
-static void pre_resid(Amg* m, hipStream_t s, AmgLevel& L, const double* rhs, const PcgScalars* S) {
+void pre_resid(Amg* m, hipStream_t s, AmgLevel& L, const double* rhs, const PcgScalars* S) {
   SpmvArgs a{};
   a.b = rhs; a.y = L.rs; a.omega = m->cfg.omega; a.S = S;
   if (L.A.nslot >= kUnfuseSlots) {
@@ -1798,10 +1987,86 @@ static void pre_resid(Amg* m, hipStream_t s, AmgLevel& L, const double* rhs, con
   Scope sc(m->prof, K_SPMV_PRE_RESID, 80.0 * L.A.nslot + 120.0 * L.A.n);
   launch_spmv_ex(s, L.A, SPMV_PRE_RESID, a);
 }
-
-int cycle(Amg* m, hipStream_t s, int l, const double* rhs, const double* rhs_sub, const SpmvRatio& rhs_c,
-          double* rhs_out, double* out, const double* dotvec, double* dotparts, const PcgScalars* S,
-          const double* dotvec2 = nullptr, int xs0_ready = 0);
+// nu pre-smoothing sweeps from zero (accumulated in xs); returns the residual they leave (rs or tR).  With `sub` the first launch
+// also forms the right-hand side.
+const double* presmooth(Amg* m, hipStream_t s, AmgLevel& L, const double* rhs, const RhsSub* sub, int nu, const PcgScalars* S) {
+  if (sub) {
+    SpmvArgs a{};
+    a.b = rhs; a.y = L.rs; a.y2 = L.xs; a.omega = m->cfg.omega; a.S = S; a.bsub = sub->sub; a.c1 = sub->c; a.b_out = sub->out;
+    Scope sc(m->prof, K_SPMV_PRE_RESID_S, 80.0 * L.A.nslot + 168.0 * L.A.n);
+    launch_spmv_ex(s, L.A, SPMV_PRE_RESID_S, a);
+  } else {
+    pre_resid(m, s, L, rhs, S);
+  }
+  // further sweeps (levels walked by the V-cycle only): sweep s applied to the residual of sweep s-1 gives the next correction
+  // (accumulated into xs) and the next residual (rs <-> tR)
+  double* res = L.rs;
+  for (int sw = 1; sw < nu; ++sw) {
+    SpmvArgs a{};
+    a.b = res; a.y = (res == L.rs) ? L.tR : L.rs; a.y2 = L.xs; a.omega = m->cfg.omega; a.S = S;
+    Scope sc(m->prof, K_SPMV_PRE_RESID_ACC, 80.0 * L.A.nslot + 144.0 * L.A.n);
+    launch_spmv_ex(s, L.A, SPMV_PRE_RESID_ACC, a);
+    res = a.y;
+  }
+  return res;
+}
+// out = the post-smoothed xs + P (coarse solution) for the right-hand side rhs: the smoothed P as a launch of its own and nu sweeps |
+// the tentative one unfused on a large level | fused into the sweep.  Returns the grid of the last kernel (the dot products').
+int prolong_postsmooth(Amg* m, hipStream_t s, AmgLevel& L, const double* rhs, double* out, const CoarseSol& cs, int nu,
+                       const DotReq& dots, const PcgScalars* S) {
+  if (L.smoothed) {
+    {
+      Scope sc(m->prof, K_PROLONG_P, 80.0 * L.P.np + 52.0 * L.A.n);
+      SGO_LAUNCH(k_prolong_p, dim3(grid_for(L.P.r_ngrp, kWavesPerBlock)), dim3(kBlock), 0, s, L.A.n, L.P, cs.u1, cs.c1, cs.u2, cs.c2,
+                 L.xs, S, (const double*)nullptr, 0, 0);
+    }
+    const double* x = L.xs;   // the first nu - 1 sweeps through the two residual buffers (free by now)
+    for (int sw = 1; sw < nu; ++sw) {
+      double* dst = (x == L.rs) ? L.tR : L.rs;
+      jacobi_sweep(m, s, L, x, rhs, dst, S);
+      x = dst;
+    }
+    return jacobi_sweep(m, s, L, x, rhs, out, S, dots);
+  }
+  if (L.A.nslot < kUnfuseSlots) return jacobi_sweep(m, s, L, L.xs, rhs, out, S, dots, &cs);
+  // a large level: the prolongation as a vector kernel of its own (same arithmetic, in place), then a plain sweep that gathers
+  // 24 B per slot instead of x, the aggregate number, the coarse vectors and the lever arm (68-92 B)
+  {
+    Scope sc(m->prof, K_PROLONG, 52.0 * L.A.n + 48.0 * L.nc);
+    SGO_LAUNCH(k_prolong_add, dim3(grid_for(L.A.n, kBlock)), dim3(kBlock), 0, s, L.A.n, L.agg, L.d, cs.u1, cs.c1, cs.u2, cs.c2, L.xs, S,
+               (const double*)nullptr, 0, 0);
+  }
+  return jacobi_sweep(m, s, L, L.xs, rhs, out, S, dots);
+}
+// out = cycle(l, rhs) in the folded form: restriction with P~^T of the right-hand side itself, coarse solve, and one launch for
+// the prolongation with P~ onto the two-sweep term M2 rhs (+ xadd).
+int cycle_coarse_fold(Amg* m, hipStream_t s, int l, const double* rhs, double* out, const PcgScalars* S, const double* xadd = nullptr) {
+  AmgLevel& L = m->lv[l];
+  restrict_level(m, s, l, rhs, S, true);
+  const CoarseSol cs = coarse_solve(m, s, l, S);
+  Scope sc(m->prof, K_UP_FOLD, 80.0 * L.A.nslot + 44.0 * L.PS.r_n + 100.0 * L.A.n);
+  const int grid = grid_for(L.U.ngrp, kWavesPerBlock);
+  SGO_LAUNCH(k_up_fold, dim3(grid), dim3(kBlock), 0, s, L.A, L.U, L.PS, rhs, m->cfg.omega, cs.u1, cs.c1, cs.u2, cs.c2, out, S, xadd);
+  return grid;
+}
+// out = cycle(l, rhs'), l >= 1: rhs' = rhs - c sub with `sub` (the K-cycle's second step).  Pre-smoothing from zero + residual,
+// restriction, coarse solve, prolongation fused into the post-smoothing launch where the transfer is the tentative one.  Partial
+// sums of dots.vec . out on request; returns the grid of the last kernel.
+int cycle_coarse(Amg* m, hipStream_t s, int l, const double* rhs, double* out, const PcgScalars* S, const RhsSub* sub = nullptr,
+                 const DotReq& dots = DotReq()) {
+  AmgLevel& L = m->lv[l];
+  const CycleForm f = cycle_form(m, l, sub != nullptr, dots.vec != nullptr);
+  if (f.kind == CycleForm::folded) return cycle_coarse_fold(m, s, l, rhs, out, S);
+  if (f.kind == CycleForm::folded_in_two_sweeps) {
+    pre_resid(m, s, L, rhs, S);                            // xs = omega Dinv rhs, rs = rhs - A xs
+    cycle_coarse_fold(m, s, l, L.rs, L.tR, S, L.xs);       // tR = xs + cycle(rs)
+    return jacobi_sweep(m, s, L, L.tR, rhs, out, S);
+  }
+  const double* res = presmooth(m, s, L, rhs, sub, f.nu, S);
+  restrict_level(m, s, l, res, S);
+  const CoarseSol cs = coarse_solve(m, s, l, S);
+  return prolong_postsmooth(m, s, L, sub ? sub->out : rhs, out, cs, f.nu, dots, S);
+}
 
 // Two flexible-CG steps on level l for A x = bk (Notay's K-cycle), with the vector updates
 // fused into the neighbouring SpMV-type launches:
@@ -1811,8 +2076,7 @@ int cycle(Amg* m, hipStream_t s, int l, const double* rhs, const double* rhs_sub
 //   x = a1 z1 + a2 p2   (returned as a CoarseSol)
 CoarseSol fcg(Amg* m, hipStream_t s, int l, const PcgScalars* S) {
   AmgLevel& L = m->lv[l];
-  SpmvRatio none;
-  cycle(m, s, l, L.bk, nullptr, none, nullptr, L.z1, nullptr, nullptr, S);
+  cycle_coarse(m, s, l, L.bk, L.z1, S);
   int gA;
   {
     SpmvArgs a{};
@@ -1820,14 +2084,12 @@ CoarseSol fcg(Amg* m, hipStream_t s, int l, const PcgScalars* S) {
     Scope sc(m->prof, K_SPMV_AX, bytes_spmv(L.A));
     gA = launch_spmv_ex(s, L.A, SPMV_AX, a);
   }
-  SpmvRatio a1{L.pA + kMaxPartials, gA, L.pA, gA};
-  if (l > m->fcg2_depth) {  // one FCG step only (steepest descent in the cycle's direction)
-    CoarseSol one;
-    one.u1 = L.z1;
-    one.c1 = a1;
-    return one;
-  }
-  const int gC = cycle(m, s, l, L.bk, L.q, a1, L.bk2, L.z2, L.q, L.pC, S);
+  CoarseSol cs;
+  cs.u1 = L.z1;
+  cs.c1 = SpmvRatio{L.pA + kMaxPartials, gA, L.pA, gA};
+  if (l > m->fcg2_depth) return cs;  // one FCG step only (steepest descent in the cycle's direction)
+  const RhsSub sub{L.q, cs.c1, L.bk2};
+  const int gC = cycle_coarse(m, s, l, L.bk, L.z2, S, &sub, DotReq{L.q, nullptr, L.pC});
   int gB;
   {
     SpmvArgs a{};
@@ -1836,271 +2098,24 @@ CoarseSol fcg(Amg* m, hipStream_t s, int l, const PcgScalars* S) {
     Scope sc(m->prof, K_SPMV_AX_C, 80.0 * L.A.nslot + 120.0 * L.A.n);
     gB = launch_spmv_ex(s, L.A, SPMV_AX_C, a);
   }
-  CoarseSol cs;
-  cs.u1 = L.z1;
-  cs.c1 = a1;
   cs.u2 = L.p2;
   cs.c2 = SpmvRatio{L.pB + kMaxPartials, gB, L.pB, gB};
   return cs;
 }
-
-// out = cycle(l, rhs'): rhs' = rhs - c rhs_sub when rhs_sub != nullptr (stored to rhs_out).
-// pre-smooth from zero + residual (one launch), restrict, coarse solve (dense inverse or two FCG
-// steps), prolongation fused into the post-smoothing launch on levels >= 1 (separate launch on
-// level 0, where the extra gathers would cost more than the launch).  Optional partials of
-// dotvec . out (and dotvec2 . out).  Returns the grid of the last kernel.
 // The coarse solve for the right-hand side C.bk of level l + 1, as the parent level sees it.
 CoarseSol coarse_solve(Amg* m, hipStream_t s, int l, const PcgScalars* S) {
   AmgLevel& C = m->lv[l + 1];
-  const int last = (int)m->lv.size() - 1;
   CoarseSol cs;
-  if (l + 1 == last) {
+  cs.u1 = C.xk;
+  if (l + 1 == (int)m->lv.size() - 1) {
     Scope sc(m->prof, K_DENSE_APPLY, 8.0 * m->N * m->N);
-    SGO_LAUNCH(k_dense_apply, dim3(grid_for(m->N, kWavesPerBlock)), dim3(kBlock), 0, s, m->N, m->Np, m->inv, C.bk,
-                       C.xk, S);
-    cs.u1 = C.xk;
-  } else if (l + 1 > m->kdepth && m->lv[l + 1].smoothed) {  // V-cycle below the K-cycle depth; a level whose own
-                                                             // transfer is the tentative one always gets the K-cycle
-    SpmvRatio none;
-    cycle(m, s, l + 1, C.bk, nullptr, none, nullptr, C.xk, nullptr, nullptr, S);
-    cs.u1 = C.xk;
+    SGO_LAUNCH(k_dense_apply, dim3(grid_for(m->N, kWavesPerBlock)), dim3(kBlock), 0, s, m->N, m->Np, m->inv, C.bk, C.xk, S);
+  } else if (l + 1 > m->kdepth && C.smoothed) {  // V-cycle below the K-cycle depth (a tentative transfer always gets the K-cycle)
+    cycle_coarse(m, s, l + 1, C.bk, C.xk, S);
   } else {
     cs = fcg(m, s, l + 1, S);
   }
   return cs;
-}
-
-// out = cycle(l, rhs) in the folded form (see "folded V-cycle"): restriction with P~^T of the right-hand side itself,
-// coarse solve, prolongation with P~ onto the two-sweep term M2 rhs -- on level 0 the level-0 Jacobi pass; on the coarser
-// levels part of the prolongation launch.
-int cycle_fold(Amg* m, hipStream_t s, int l, const double* rhs, double* out, const double* dotvec, double* dotparts,
-               const PcgScalars* S, const double* dotvec2, int xs0_ready, const double* xadd = nullptr) {
-  AmgLevel& L = m->lv[l];
-  AmgLevel& C = m->lv[l + 1];
-  bool fused0 = false;
-  if (l == 0) {   // (single GPU: multi-GPU runs keep level 0 unfolded)
-    if (!xs0_ready) {   // xs = omega Dinv rhs (normally left by the producer of rhs)
-      Scope sc(m->prof, K_DOT, 96.0 * L.A.n);
-      launch_precond_bj(s, L.A.n, m->S0.dinv, rhs, L.xs, m->cfg.omega);
-    }
-    // M2 rhs = xs + omega Dinv (rhs - H xs): the level-0 Jacobi pass, into rs.  (It does not depend on the coarse levels;
-    // running it BESIDE them on a second stream -- a parallel branch of the captured hipGraph -- was measured: the fork and
-    // join cost 25 us per PCG iteration on this runtime, C2 1.45 -> 1.95 ms per GN iteration.)
-    Spmv0Args b{};
-    b.x = L.xs; b.b = rhs; b.y = L.rs; b.omega = m->cfg.omega; b.S = S;
-    if (m->T0.ntile == 0) {   // wave-group kernel: the pass and the restriction in one launch
-      const int nb_spmv = grid_for(m->S0.ngrp, kWavesPerBlock), nb_main = grid_for(L.PS.t_ngrp, kWavesPerBlock);
-      Scope sc(m->prof, K_JACOBI0_RESTRICT, 76.0 * m->S0.npairs + 168.0 * m->S0.n + 44.0 * L.PS.t_n + 24.0 * L.A.n + 24.0 * L.nc);
-      SGO_LAUNCH(k_jacobi0_restrict, dim3(nb_spmv + nb_main + L.PS.t_nlong), dim3(kBlock), 0, s, m->S0, b, nb_spmv, L.PS, C.bk, nb_main);
-      fused0 = true;
-    } else {
-      const bool f32 = m->S0.fblk != nullptr;
-      Scope sc(m->prof, f32 ? K_SPMV0T_JACOBI_F32 : K_SPMV0T_JACOBI, (f32 ? 40.0 : 76.0) * m->S0.npairs + 168.0 * m->S0.n);
-      launch_spmv0_any(s, m->S0, m->T0, S0_JACOBI, b);
-    }
-  }
-  if (!fused0) {
-    Scope sc(m->prof, l == 0 ? K_RESTRICT_P0 : K_RESTRICT_P, 44.0 * L.PS.t_n + 24.0 * L.A.n + 24.0 * L.nc);
-    launch_restrict_p(s, L.PS, rhs, C.bk, S, 0, 0);
-  }
-  const CoarseSol cs = coarse_solve(m, s, l, S);
-  if (l > 0) {
-    Scope sc(m->prof, K_UP_FOLD, 80.0 * L.A.nslot + 44.0 * L.PS.r_n + 100.0 * L.A.n);
-    const int grid = grid_for(L.U.ngrp, kWavesPerBlock);
-    SGO_LAUNCH(k_up_fold, dim3(grid), dim3(kBlock), 0, s, L.A, L.U, L.PS, rhs, m->cfg.omega, cs.u1, cs.c1, cs.u2, cs.c2, out, S, xadd);
-    return grid;
-  }
-  // (the dot products' partial sums are re-reduced by every workgroup of the consumer: a few hundred of them, not thousands)
-  const int grid = std::min(grid_for(L.PS.r_ngrp, kFoldThreads / 64), 512);
-  Scope sc(m->prof, K_PROLONG_FOLD0, 44.0 * L.PS.r_n + 72.0 * L.A.n);
-  SGO_LAUNCH(k_prolong_fold, dim3(grid), dim3(kFoldThreads), 0, s, L.PS, cs.u1, cs.c1, cs.u2, cs.c2, (const double*)L.rs, out, S, dotvec,
-             dotvec2, dotvec ? dotparts : nullptr);
-  return grid;
-}
-
-int cycle(Amg* m, hipStream_t s, int l, const double* rhs, const double* rhs_sub, const SpmvRatio& rhs_c,
-          double* rhs_out, double* out, const double* dotvec, double* dotparts, const PcgScalars* S,
-          const double* dotvec2, int xs0_ready) {
-  AmgLevel& L = m->lv[l];
-  AmgLevel& C = m->lv[l + 1];
-  {
-    const int nu_l = (l > 0 && L.tR && L.smoothed) ? std::max(1, m->cfg.nu_coarse) : 1;
-    if (L.fold && nu_l == 1 && !rhs_sub && (l == 0 ? !(m->halo || m->comm) : !dotvec)) return cycle_fold(m, s, l, rhs, out, dotvec, dotparts, S, dotvec2, xs0_ready);
-    if (L.fold && nu_l == 2 && !rhs_sub && l > 0 && !dotvec) {
-      // two sweeps per side = one explicit sweep around the folded cycle: S E S with E the folded cycle's error propagator
-      pre_resid(m, s, L, rhs, S);   // xs = omega Dinv rhs, rs = rhs - A xs
-      cycle_fold(m, s, l, L.rs, L.tR, nullptr, nullptr, S, nullptr, 0, L.xs);   // tR = xs + cycle(rs)
-      SpmvArgs a{};
-      a.x = L.tR; a.b = rhs; a.y = out; a.omega = m->cfg.omega; a.S = S;
-      Scope sc(m->prof, K_SPMV_JACOBI, 80.0 * L.A.nslot + 120.0 * L.A.n);
-      return launch_spmv_ex(s, L.A, SPMV_JACOBI, a);
-    }
-  }
-  const double* rhs_eff = rhs;
-  const HaloDev* H = l == 0 ? m->halo : nullptr;           // multi-GPU, row-owner mode
-  const bool sharded0 = l == 0 && m->comm != nullptr && !H;   // multi-GPU, all-reduce mode
-  const int frow0 = H ? H->row0 : (sharded0 ? m->row0 : 0), frow1 = H ? H->row1 : (sharded0 ? m->row1 : 0);
-  if (l == 0) {
-    // finest level, symmetric storage: xs = omega Dinv rhs (first sweep from zero; normally left by the
-    // producer of rhs), then the residual rs = rhs - H xs in one pass over the stored blocks
-    if (!xs0_ready) {
-      Scope sc(m->prof, K_DOT, 96.0 * L.A.n);
-      if (H) launch_precond_bj(s, H->row1 - H->row0, m->S0.dinv + 6 * (size_t)H->row0, rhs + 3 * (size_t)H->row0, L.xs + 3 * (size_t)H->row0, m->cfg.omega);
-      else launch_precond_bj(s, L.A.n, m->S0.dinv, rhs, L.xs, m->cfg.omega);
-    }
-    Spmv0Args a{};
-    a.x = L.xs; a.b = rhs; a.y = L.rs; a.S = S;
-    if (H) {   // the neighbours' boundary rows of xs (unless the caller keeps them current itself), then this rank's tiles
-      std::string e;
-      if (xs0_ready < 2 && !halo_exchange(*H, s, L.xs, 3, H->bnd, H->bmax, HaloScalars(), &e)) m->comm_failed = true;
-      a.u0 = H->u0; a.u1 = H->u1;
-    } else if (m->comm) {
-      a.u0 = m->u0; a.u1 = m->u1;
-      if (!m->slices) hipMemsetAsync(L.rs, 0, sizeof(double) * 3 * (size_t)L.A.n, s);   // (the restriction reads this rank's rows only)
-    }
-    if (!(H || m->comm) || a.u1 > a.u0) {
-      const bool f32 = m->T0.ntile > 0 && m->S0.fblk != nullptr;   // (fp32 copy of the blocks: 36 + 4 B per pair)
-      Scope sc(m->prof, m->T0.ntile > 0 ? (f32 ? K_SPMV0T_RESID_F32 : K_SPMV0T_RESID) : K_SPMV0_RESID,
-               ((f32 ? 40.0 : 76.0) * m->S0.npairs + 120.0 * m->S0.n) / (H ? H->G : 1));
-      launch_spmv0_any(s, m->S0, m->T0, S0_RESID, a);
-    }
-    // multi-GPU: the residual stays a per-rank partial (this rank's rows); the restriction below takes only those
-    // rows and the coarse right-hand side is what gets all-reduced (3 n_c doubles instead of 3 n)
-  } else {
-    SpmvArgs a{};
-    a.b = rhs; a.y = L.rs; a.y2 = L.xs; a.omega = m->cfg.omega; a.S = S;
-    if (rhs_sub) {
-      a.bsub = rhs_sub; a.c1 = rhs_c; a.b_out = rhs_out;
-      rhs_eff = rhs_out;
-      Scope sc(m->prof, K_SPMV_PRE_RESID_S, 80.0 * L.A.nslot + 168.0 * L.A.n);
-      launch_spmv_ex(s, L.A, SPMV_PRE_RESID_S, a);
-    } else {
-      pre_resid(m, s, L, rhs, S);
-    }
-  }
-  // further pre-smoothing sweeps (levels walked by the V-cycle only): sweep s applied to the residual
-  // of sweep s-1 gives the next correction (accumulated into xs) and the next residual (rs <-> tR)
-  const int nu = (l > 0 && L.tR && L.smoothed) ? std::max(1, m->cfg.nu_coarse) : 1;
-  double* res = L.rs;
-  for (int sw = 1; sw < nu; ++sw) {
-    double* nxt = (res == L.rs) ? L.tR : L.rs;
-    SpmvArgs a{};
-    a.b = res; a.y = nxt; a.y2 = L.xs; a.omega = m->cfg.omega; a.S = S;
-    Scope sc(m->prof, K_SPMV_PRE_RESID_ACC, 80.0 * L.A.nslot + 144.0 * L.A.n);
-    launch_spmv_ex(s, L.A, SPMV_PRE_RESID_ACC, a);
-    res = nxt;
-  }
-  if (H && L.smoothed && L.P.local_lists) hipMemsetAsync(C.bk, 0, sizeof(double) * 3 * (size_t)C.A.n, s);   // coarse rows none of this rank's rows reaches
-  if (L.smoothed) {
-    Scope sc(m->prof, l == 0 ? K_RESTRICT_P0 : K_RESTRICT_P, 44.0 * L.P.t_n + 24.0 * L.A.n + 24.0 * L.nc);
-    launch_restrict_p(s, L.P, res, C.bk, S, frow0, frow1);
-  } else {
-    Scope sc(m->prof, l == 0 ? K_RESTRICT0 : K_RESTRICT, 40.0 * L.A.n + 24.0 * L.nc);
-    SGO_LAUNCH(k_restrict, dim3(grid_for(L.mem_ngrp, kWavesPerBlock)), dim3(kBlock), 0, s, L.mem_ngrp, L.mem_grp,
-                       L.mem, L.agg, L.d, res, C.bk, S, frow0, frow1);
-  }
-  if (sharded0 || H) {   // the ranks' partial coarse right-hand sides (each from its own fine rows) -> their sum
-    std::string e;
-    if (!(H ? H->comm : m->comm)->allreduce_f64(C.bk, 3 * (size_t)C.A.n, s, &e)) m->comm_failed = true;
-  }
-  const CoarseSol cs = coarse_solve(m, s, l, S);
-  SpmvArgs a{};
-  a.x = L.xs; a.b = rhs_eff; a.y = out; a.omega = m->cfg.omega; a.S = S;
-  if (dotvec) {
-    a.dotA = dotvec;
-    a.dotA2 = dotvec2;
-    a.partials = dotparts;
-  }
-  if (l == 0) {   // prolongation, then the post-smoothing sweep on the symmetric storage
-    if (L.smoothed) {
-      Scope sc(m->prof, K_PROLONG_P0, 44.0 * L.P.r_n + 52.0 * L.A.n);
-      SGO_LAUNCH(k_prolong_p, dim3(grid_for(L.P.r_ngrp, kWavesPerBlock)), dim3(kBlock), 0, s, L.A.n, L.P, cs.u1, cs.c1, cs.u2, cs.c2,
-                 L.xs, S, (const double*)nullptr, H ? H->row0 : 0, H ? H->row1 : 0);
-    } else {
-      Scope sc(m->prof, K_PROLONG0, 68.0 * L.A.n);
-      SGO_LAUNCH(k_prolong_add, dim3(grid_for(H ? H->row1 - H->row0 : L.A.n, kBlock)), dim3(kBlock), 0, s, L.A.n, L.agg, L.d, cs.u1, cs.c1,
-                         cs.u2, cs.c2, L.xs, S, (const double*)nullptr, H ? H->row0 : 0, H ? H->row1 : 0);
-    }
-    Spmv0Args b{};
-    b.x = L.xs; b.b = rhs; b.y = out; b.omega = m->cfg.omega; b.S = S;
-    if (dotvec) {
-      b.dotA = dotvec;
-      b.dotA2 = dotvec2;
-      b.partials = dotparts;
-    }
-    if (H) {
-      // row-owner mode: the corrected xs of the neighbours' boundary rows, then the sweep over this rank's tiles; the dot
-      // products ride on the kernel as per-workgroup partials of the OWNED rows (the caller exchanges their sums)
-      // (no exchange for that: this rank prolongates the replicated coarse solution on its copies of the neighbours' boundary
-      // rows itself, k_prolong_rows)
-      if (H->nhalo > 0) {
-        PDev Ph = L.smoothed ? L.P : PDev();
-        SGO_LAUNCH(k_prolong_rows, dim3(grid_for(H->nhalo, kBlock)), dim3(kBlock), 0, s, H->nhalo, H->halo_rows, Ph, (const int*)L.agg,
-                   (const double*)L.d, cs.u1, cs.c1, cs.u2, cs.c2, L.xs, S);
-      }
-      b.u0 = H->u0; b.u1 = H->u1;
-      Scope sc(m->prof, m->S0.fblk ? K_SPMV0T_JACOBI_F32 : K_SPMV0T_JACOBI, ((m->S0.fblk ? 40.0 : 76.0) * m->S0.npairs + 168.0 * m->S0.n) / H->G);
-      return launch_spmv0_any(s, m->S0, m->T0, S0_JACOBI, b);
-    }
-    if (m->comm) {
-      // this rank's rows, zeros elsewhere, all-reduce, then the dot products on the full vector (replicated)
-      b.u0 = m->u0; b.u1 = m->u1;
-      b.dotA = nullptr; b.dotA2 = nullptr; b.partials = nullptr;
-      if (!m->slices) hipMemsetAsync(out, 0, sizeof(double) * 3 * (size_t)L.A.n, s);
-      if (b.u1 > b.u0) {
-        Scope sc(m->prof, m->T0.ntile > 0 ? K_SPMV0T_JACOBI : K_SPMV0_JACOBI, 76.0 * m->S0.npairs + 168.0 * m->S0.n);
-        launch_spmv0_any(s, m->S0, m->T0, S0_JACOBI, b);
-      }
-      std::string e;
-      if (m->slices) {
-        if (!halo_gather_slices(*m->slices, s, out, 3, &e)) m->comm_failed = true;
-      } else if (!m->comm->allreduce_f64(out, 3 * (size_t)L.A.n, s, &e)) {
-        m->comm_failed = true;
-      }
-      if (!dotvec) return 0;
-      const int grid = grid_for(3LL * L.A.n, kBlock);
-      Scope sc(m->prof, K_DOT, 72.0 * L.A.n);
-      SGO_LAUNCH(k_dots2, dim3(grid), dim3(kBlock), 0, s, 3 * L.A.n, (const double*)out, dotvec, dotvec2, dotparts, S);
-      return grid;
-    }
-    const bool f32 = m->T0.ntile > 0 && m->S0.fblk != nullptr;
-    Scope sc(m->prof, m->T0.ntile > 0 ? (f32 ? K_SPMV0T_JACOBI_F32 : K_SPMV0T_JACOBI) : K_SPMV0_JACOBI, (f32 ? 40.0 : 76.0) * m->S0.npairs + 168.0 * m->S0.n);
-    return launch_spmv0_any(s, m->S0, m->T0, S0_JACOBI, b);
-  }
-  if (L.smoothed) {
-    {
-      Scope sc(m->prof, K_PROLONG_P, 80.0 * L.P.np + 52.0 * L.A.n);
-      SGO_LAUNCH(k_prolong_p, dim3(grid_for(L.P.r_ngrp, kWavesPerBlock)), dim3(kBlock), 0, s, L.A.n, L.P, cs.u1, cs.c1, cs.u2, cs.c2,
-                 L.xs, S, (const double*)nullptr, 0, 0);
-    }
-    // post-smoothing: nu sweeps, the first nu - 1 through the two residual buffers (free by now)
-    for (int sw = 1; sw < nu; ++sw) {
-      double* dst = (a.x == L.rs) ? L.tR : L.rs;
-      SpmvArgs b = a;
-      b.y = dst; b.dotA = nullptr; b.dotA2 = nullptr; b.partials = nullptr;
-      {
-        Scope sc(m->prof, K_SPMV_JACOBI, 80.0 * L.A.nslot + 120.0 * L.A.n);
-        launch_spmv_ex(s, L.A, SPMV_JACOBI, b);
-      }
-      a.x = dst;
-    }
-    Scope sc(m->prof, K_SPMV_JACOBI, 80.0 * L.A.nslot + 120.0 * L.A.n);
-    return launch_spmv_ex(s, L.A, SPMV_JACOBI, a);
-  }
-  if (L.A.nslot >= kUnfuseSlots && a.x == L.xs) {
-    // a large level: the prolongation as a vector kernel of its own (same arithmetic, in place), then a plain sweep that gathers
-    // 24 B per slot instead of x, the aggregate number, the coarse vectors and the lever arm (68-92 B)
-    {
-      Scope sc(m->prof, K_PROLONG, 52.0 * L.A.n + 48.0 * L.nc);
-      SGO_LAUNCH(k_prolong_add, dim3(grid_for(L.A.n, kBlock)), dim3(kBlock), 0, s, L.A.n, L.agg, L.d, cs.u1, cs.c1, cs.u2, cs.c2, L.xs, S,
-                 (const double*)nullptr, 0, 0);
-    }
-    Scope sc(m->prof, K_SPMV_JACOBI, 80.0 * L.A.nslot + 120.0 * L.A.n);
-    return launch_spmv_ex(s, L.A, SPMV_JACOBI, a);
-  }
-  a.agg = L.agg; a.d = L.d; a.u1 = cs.u1; a.u2 = cs.u2; a.c1 = cs.c1; a.c2 = cs.c2;
-  Scope sc(m->prof, K_SPMV_JACOBI_P, 80.0 * L.A.nslot + 140.0 * L.A.n + 48.0 * L.nc);
-  return launch_spmv_ex(s, L.A, SPMV_JACOBI_P, a);
 }
 
 }  // namespace
@@ -2178,49 +2193,33 @@ int amg_update(Amg* m, hipStream_t s, std::string* err) {
 }
 
 void amg_set_shard(Amg* m, Comm* comm, int u0, int u1, int row0, int row1, const HaloDev* slices) {
-  m->slices = slices;
-  m->comm = comm;
-  m->u0 = u0;
-  m->u1 = u1;
-  m->row0 = row0;
-  m->row1 = row1;
+  m->shard.mode = Shard0::allreduce;
+  m->shard.u0 = u0; m->shard.u1 = u1; m->shard.row0 = row0; m->shard.row1 = row1;
+  m->shard.comm = comm;
+  m->shard.part = slices;
 }
-bool amg_comm_failed(const Amg* m) { return m && m->comm_failed; }
+bool amg_comm_failed(const Amg* m) { return m && m->shard.failed; }
 // Test hook: the coarse right-hand side the first half of a level-0 cycle produces from r (first sweep from zero,
-// residual pass, restriction) -- with a shard set and no communicator, this rank's PARTIAL coarse right-hand side.
+// residual pass, restriction; where level 0 has the folded transfer, its restriction of r itself: the same vector in exact
+// arithmetic) -- with a shard set, this rank's PARTIAL coarse right-hand side: the cycle's steps short of the all-reduce.
 int amg_debug_coarse_rhs(Amg* m, hipStream_t s, const double* r, double* out_dev, int cap3) {
   if (!m || m->lv.size() < 2) return 0;
-  AmgLevel& L = m->lv[0];
-  AmgLevel& C = m->lv[1];
-  const int n3c = 3 * C.A.n;
+  const int n3c = 3 * m->lv[1].A.n;
   if (cap3 < n3c) return -1;
-  const bool sharded = m->comm != nullptr;
-  if (L.fold) {   // folded cycle: the restriction with P~^T of r itself (the same vector in exact arithmetic)
-    launch_restrict_p(s, L.PS, r, C.bk, nullptr, sharded ? m->row0 : 0, sharded ? m->row1 : 0);
-    hipMemcpyAsync(out_dev, C.bk, sizeof(double) * n3c, hipMemcpyDeviceToDevice, s);
-    return n3c;
+  if (m->lv[0].fold) {
+    restrict_level(m, s, 0, r, nullptr, true);
+  } else {
+    presmooth0(m, s, r, nullptr, AmgXs0::compute);
+    restrict_level(m, s, 0, m->lv[0].rs, nullptr);
   }
-  launch_precond_bj(s, L.A.n, m->S0.dinv, r, L.xs, m->cfg.omega);
-  Spmv0Args a{};
-  a.x = L.xs; a.b = r; a.y = L.rs;
-  if (sharded) {
-    a.u0 = m->u0; a.u1 = m->u1;
-    hipMemsetAsync(L.rs, 0, sizeof(double) * 3 * (size_t)L.A.n, s);
-  }
-  if (!sharded || a.u1 > a.u0) launch_spmv0_any(s, m->S0, m->T0, S0_RESID, a);
-  if (L.smoothed)
-    launch_restrict_p(s, L.P, L.rs, C.bk, nullptr, sharded ? m->row0 : 0, sharded ? m->row1 : 0);
-  else
-    SGO_LAUNCH(k_restrict, dim3(grid_for(L.mem_ngrp, kWavesPerBlock)), dim3(kBlock), 0, s, L.mem_ngrp, L.mem_grp, L.mem, L.agg,
-               L.d, (const double*)L.rs, C.bk, (const PcgScalars*)nullptr, sharded ? m->row0 : 0, sharded ? m->row1 : 0);
-  hipMemcpyAsync(out_dev, C.bk, sizeof(double) * n3c, hipMemcpyDeviceToDevice, s);
+  hipMemcpyAsync(out_dev, m->lv[1].bk, sizeof(double) * n3c, hipMemcpyDeviceToDevice, s);
   return n3c;
 }
 double* amg_xs0(Amg* m) { return (m && m->lv.size() > 1) ? m->lv[0].xs : nullptr; }
 double amg_omega(const Amg* m) { return m ? m->cfg.omega : 0.0; }
 
 int amg_apply(Amg* m, hipStream_t s, const double* r, double* z, const double* dotvec, double* partials,
-              const PcgScalars* S, const double* dotvec2, int xs0_ready) {
+              const PcgScalars* S, const double* dotvec2, AmgXs0 xs0) {
   if (m->lv.size() == 1) {  // single (dense) level: z = H^-1 r
     {
       Scope sc(m->prof, K_DENSE_APPLY, 8.0 * m->N * m->N);
@@ -2232,8 +2231,7 @@ int amg_apply(Amg* m, hipStream_t s, const double* r, double* z, const double* d
     SGO_LAUNCH(k_dots2, dim3(grid), dim3(kBlock), 0, s, m->N, (const double*)z, dotvec, dotvec2, partials, S);
     return grid;
   }
-  SpmvRatio none;
-  return cycle(m, s, 0, r, nullptr, none, nullptr, z, dotvec, partials, S, dotvec2, xs0_ready);
+  return cycle0(m, s, r, z, DotReq{dotvec, dotvec2, partials}, S, xs0);
 }
 
 // v[0..n) counts -> exclusive prefix sums in place, v[n] = total (device, on the stream); `sums` holds n / kScanChunk + 2 ints
@@ -2275,7 +2273,7 @@ AmgConfig amg_effective_config(const AmgConfig& cfg_in, int n, int nslot) {
   if (const char* e = std::getenv("SGO_AMG_FOLD0_ROWS")) cfg.fold0_rows = std::atoi(e);
   cfg.fold = cfg.fold && cfg.smooth && cfg.lists_on_device;
   // (the folded cycle folds ONE sweep per side into the transfers -- two would need the pattern of A A P; a second sweep is
-  // one explicit sweep around it, see cycle().  One sweep everywhere was measured on C4: five coarse launches instead of
+  // one explicit sweep around it, see cycle_form().  One sweep everywhere was measured on C4: five coarse launches instead of
   // nine, but 27.9 instead of 22.1 PCG iterations, 5.07 against 4.59 ms per GN iteration)
   if (const char* e = std::getenv("SGO_AMG_NU")) cfg.nu_coarse = std::max(1, std::atoi(e));
   // larger graphs afford a larger dense coarsest level (its inverse costs O(N^3) once per GN
@@ -2541,7 +2539,7 @@ std::string assemble_level(Amg* m, DevSetup& D, int l, const DevCoarse& dc) {
   const std::string oom = "amg_create: out of device memory";
   AmgLevel& L = m->lv[l];
   const int n = L.A.n, nc = dc.nc;
-  const int r0 = dc.local ? m->halo->row0 : 0, r1 = dc.local ? m->halo->row1 : n;   // the rows whose entries are held
+  const int r0 = dc.local ? m->shard.row0 : 0, r1 = dc.local ? m->shard.row1 : n;   // the rows whose entries are held
   GroupBatch gb;
   L.nc = nc;
   L.agg = dc.agg;
@@ -2604,7 +2602,7 @@ std::string assemble_level(Amg* m, DevSetup& D, int l, const DevCoarse& dc) {
     // (Level 0 is folded only where it is itself launch-bound: P~ has the pattern of A P, twice the entries of P, and on large graphs
     // streaming it twice per cycle costs what the saved launch and pass bring -- C4: restriction + prolongation 14 + 20 us with P~
     // against 11 + 9 us with P.  Multi-GPU row-owner runs keep level 0 unfolded as well.)
-    fold_here = m->cfg.fold && nf > 0 && (l > 0 || (!m->halo && n <= m->cfg.fold0_rows));
+    fold_here = m->cfg.fold && nf > 0 && (l > 0 || (m->shard.mode != Shard0::owner && n <= m->cfg.fold0_rows));
     if (fold_here) {
       // ---- folded cycle: pattern bookkeeping of P~ (the pattern of A P) -- which entry of P sits at the same place, the column order (a
       // device radix sort of (column, row-major rank) keys), its wave groups and long columns -- and the two streamed fp32 copies
@@ -2842,7 +2840,14 @@ Amg* amg_create(hipStream_t s, const BsrDev& A0, const Sym0Dev& S0, const Tile0D
                 const int* d_free_id, const AmgConfig& cfg_in, const AmgProf& prof, std::string* err, ChunkArena* scratch, DevArena* arena,
                 DevArena* tmp_arena, AmgPatterns patterns, AmgHostL0* pre0, const AmgHalo* halo) {
   Amg* m = new Amg();
-  if (halo) m->halo = halo->dev;
+  if (halo) {   // row-owner mode
+    const HaloDev& H = *halo->dev;
+    m->shard.mode = Shard0::owner;
+    m->shard.u0 = H.u0; m->shard.u1 = H.u1; m->shard.row0 = H.row0; m->shard.row1 = H.row1;
+    m->shard.G = H.G;
+    m->shard.comm = H.comm;
+    m->shard.part = halo->dev;
+  }
   m->pool = arena;
   m->S0 = S0;
   m->T0 = T0;
@@ -2925,7 +2930,7 @@ Amg* amg_create(hipStream_t s, const BsrDev& A0, const Sym0Dev& S0, const Tile0D
       if (verbose)
         std::fprintf(stderr, "[sgo] amg level %d: host aggregation + coarse structure %.1f ms (aggregate %.1f, sort %.1f; n=%d -> %d)%s\n", l,
                      hc->t_all, hc->t_agg, hc->t_sort, n, hc->nc, hc == &hc_own ? "" : " [made ahead on the helper thread]");
-      if (!upload_coarse(D, *hc, n, l == 0 ? m->halo : nullptr, dc)) return fail(dc.err);
+      if (!upload_coarse(D, *hc, n, l == 0 && halo ? halo->dev : nullptr, dc)) return fail(dc.err);
       h_agg = hc->agg;
       h_visit_c = hc->visit_c;
     } else {

@@ -545,6 +545,12 @@ int launch_spmv0t(hipStream_t s, const Sym0Dev& A, const Tile0Dev& T, int mode, 
 inline int launch_spmv0_any(hipStream_t s, const Sym0Dev& A, const Tile0Dev& T, int mode, const Spmv0Args& a) {
   return T.ntile > 0 ? launch_spmv0t(s, A, T, mode, a) : launch_spmv0(s, A, mode, a);
 }
+// Algorithmic bytes of one level-0 product: every stored off-diagonal block once
+// with one index (76 B per edge; 36 + 4 B where the pass reads the fp32 copy of the blocks: `f32`), the diagonal block (48 B), the
+// operand and the result (24 B each) per row; + the right-hand side (RESID, JACOBI) and the block-diagonal inverse (JACOBI).
+inline double bytes_spmv0(const Sym0Dev& A, int mode, bool f32 = false) {
+  return (f32 ? 40.0 : 76.0) * A.npairs + (96.0 + (mode != S0_AX ? 24.0 : 0.0) + (mode == S0_JACOBI ? 48.0 : 0.0)) * A.n;
+}
 constexpr int kTileLdsMax = 157 * 1024;   // one 1024-thread tile workgroup per CU (160 KiB of LDS)
 int launch_spmv_ex(hipStream_t s, const BsrDev& A, int mode, const SpmvArgs& a);  // returns grid
 void launch_update_xr(hipStream_t s, int n, PcgScalars* S, const double* pq_parts, int n_pq, const double* dinv,

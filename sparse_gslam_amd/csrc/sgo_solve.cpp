@@ -62,12 +62,7 @@ void prof_flush(sgo_ctx* c) {
 }
 
 // ---- algorithmic bytes per launch ------------
-// Level-0 product: every stored off-diagonal block once with one index (76 B per edge), the diagonal
-// block (48 B), the operand and the result (24 B each) per row; + the right-hand side (RESID, JACOBI)
-// and the block-diagonal inverse (JACOBI).
-double bytes_spmv0(const Sym0Dev& A, int mode) {
-  return 76.0 * A.npairs + (96.0 + (mode != S0_AX ? 24.0 : 0.0) + (mode == S0_JACOBI ? 48.0 : 0.0)) * A.n;
-}
+// (the level-0 product: bytes_spmv0, sgo_internal.h)
 // linearise + assemble: the row-parallel design reads each edge's operands once per endpoint row
 // (2 x 128 B: indices, inverse measurement, information, two poses), writes the off-diagonal block once
 // (72 B) and 72 B of (diagonal block, b) per row
@@ -150,7 +145,7 @@ static int start_pcg_owner(sgo_ctx* c, int grid) {
       launch_warm_start(c->stream, 3 * nr, c->d_xprev + o3, c->d_q + o3, c->d_b + o3, c->d_x + o3, c->d_r + o3, H.gparts + G, G,
                         H.gparts + 2 * G, G);
     }
-    const int gz = amg_apply(c->amg, c->stream, c->d_r, c->d_z, c->d_r, c->d_zparts, nullptr, nullptr, 0);
+    const int gz = amg_apply(c->amg, c->stream, c->d_r, c->d_z, c->d_r, c->d_zparts, nullptr, nullptr, AmgXs0::compute);
     if (amg_comm_failed(c->amg)) return SGO_ECOMM;
     HIP_TRY(c, hipMemcpyAsync(c->d_p + o3, c->d_z + o3, sizeof(double) * 3 * (size_t)nr, hipMemcpyDeviceToDevice, c->stream));
     if (!xch(c, c->d_p, scal(c->d_zparts, gz))) return SGO_ECOMM;
@@ -161,7 +156,7 @@ static int start_pcg_owner(sgo_ctx* c, int grid) {
     if (!xch(c, c->d_r, HaloScalars())) return SGO_ECOMM;   // the halo rows' copies of r start here
     return SGO_OK;
   }
-  const int gz = amg_apply(c->amg, c->stream, c->d_r, c->d_z, c->d_r, c->d_zparts, nullptr, nullptr, 1);
+  const int gz = amg_apply(c->amg, c->stream, c->d_r, c->d_z, c->d_r, c->d_zparts, nullptr, nullptr, AmgXs0::ready);
   if (amg_comm_failed(c->amg)) return SGO_ECOMM;
   HIP_TRY(c, hipMemcpyAsync(c->d_p + o3, c->d_z + o3, sizeof(double) * 3 * (size_t)nr, hipMemcpyDeviceToDevice, c->stream));
   if (!xch(c, c->d_p, scal(c->d_zparts, gz, bb_parts, grid))) return SGO_ECOMM;
@@ -231,7 +226,7 @@ int start_pcg(sgo_ctx* c, int grid) {
       }
     }
     // (cold: k_finalize left x = 0, r = b and xs = omega Dinv b, the cycle's first sweep from zero)
-    const int xs_ready = warm ? 0 : 1;
+    const AmgXs0 xs_ready = warm ? AmgXs0::compute : AmgXs0::ready;
     const int gz = amg_apply(c->amg, c->stream, c->d_r, c->d_z, c->d_r, c->d_zparts, nullptr, nullptr, xs_ready);
     if (amg_comm_failed(c->amg)) return SGO_ECOMM;
     HIP_TRY(c, hipMemcpyAsync(c->d_p, c->d_z, sizeof(double) * 3 * (size_t)c->n, hipMemcpyDeviceToDevice, c->stream));
@@ -267,7 +262,7 @@ static int refresh_and_continue(sgo_ctx* c, int maxit) {
   HIP_TRY(c, hipMemcpyAsync(c->d_dref, c->S0.dblk, sizeof(double) * 6 * (size_t)c->n, hipMemcpyDeviceToDevice, c->stream));
   c->hier.ref_valid = true;
   c->call.skip_update = false;
-  const int gz = amg_apply(c->amg, c->stream, c->d_r, c->d_z, c->d_r, c->d_zparts, nullptr, nullptr, 0);
+  const int gz = amg_apply(c->amg, c->stream, c->d_r, c->d_z, c->d_r, c->d_zparts, nullptr, nullptr, AmgXs0::compute);
   HIP_TRY(c, hipMemcpyAsync(c->d_p, c->d_z, sizeof(double) * 3 * (size_t)c->n, hipMemcpyDeviceToDevice, c->stream));
   {
     Scope sc(c, K_INIT_SCALARS, 8.0 * gz);
@@ -412,7 +407,7 @@ static int pcg_iteration_owner(sgo_ctx* c) {
                        c->d_r + o3, c->d_z + o3, amg_xs0(c->amg) + o3, amg_omega(c->amg), parts2, &g2);
     }
     launch_update_xr_rows(c->stream, H.nhalo, H.halo_rows, c->d_S, c->S0.dinv, c->d_p, c->d_q, c->d_r, amg_xs0(c->amg), amg_omega(c->amg));
-    const int gz = amg_apply(c->amg, c->stream, c->d_r, c->d_z, c->d_r, c->d_zparts, c->d_S, c->d_q, 2);
+    const int gz = amg_apply(c->amg, c->stream, c->d_r, c->d_z, c->d_r, c->d_zparts, c->d_S, c->d_q, AmgXs0::ready_with_halo);
     if (amg_comm_failed(c->amg)) {
       c->err = "collective failed inside the multigrid cycle";
       return SGO_ECOMM;
@@ -454,7 +449,7 @@ int pcg_iteration(sgo_ctx* c) {
   }
   if (c->amg) {
     // the K-cycle is a (mildly) variable preconditioner: flexible beta from z.q
-    const int gz = amg_apply(c->amg, c->stream, c->d_r, c->d_z, c->d_r, c->d_zparts, c->d_S, c->d_q, true);
+    const int gz = amg_apply(c->amg, c->stream, c->d_r, c->d_z, c->d_r, c->d_zparts, c->d_S, c->d_q, AmgXs0::ready);
     if (amg_comm_failed(c->amg)) {
       c->err = "collective failed inside the multigrid cycle";
       return SGO_ECOMM;
