@@ -362,6 +362,57 @@ int sgo_debug_coarse_rhs(sgo_ctx* ctx, const double* r, double* out, int cap);
  * per-slot / per-block index arrays, level-0 transfer blocks and product lists): proportional to 1 / nranks in row-owner mode. */
 int64_t sgo_debug_level0_bytes(sgo_ctx* ctx);
 double sgo_debug_spmv0_us(sgo_ctx* ctx, int mode, int variant, int reps);
+/* Test hook: a read-only copy of one array of the resident multigrid hierarchy, exactly as the next sgo_precondition (the
+ * cycle) and the next refresh of the coarse operators read it -- device memory as stored, nothing recomputed; the one gather
+ * is SGO_AMG_A_BLK, a level's logical 3x3 blocks [nslot][9] (level 0: through its references into the symmetric storage;
+ * SGO_AMG_A_BLK_F32: the same with the off-diagonal blocks from the fp32 copy, where the cycle's level-0 passes read that).
+ * Rows are in the internal order: SGO_AMG_ROW_ORDER (level 0) gives the internal row of every hessian-order row.
+ * `what` is one of SGO_AMG_*; tests/amg_reference.py names every array's type and shape.  The streamed fp32 copies
+ * (P_RBLK, P_TBLK, PS_RBLK, PS_TBLK) come as stored: components 0..3 [m][4], components 4..7 [m][4], component 8 [m].
+ * SGO_AMG_INFO: SGO_AMG_INFO_COUNT doubles { n, nslot, nc, smoothed, filtered, folded, cycle form (0 unfolded, 1 folded,
+ * 2 folded in two sweeps), sweeps per side, omega, omega_p, entries of P, of A P, products of P's values, of A P, of
+ * P^T A P, levels, level-0 passes read fp32, N, Np of the coarsest inverse, long columns of P, of P~, K-cycle depth,
+ * theta_filter, slots of the next level }.
+ * Returns the array's size in bytes (copied when cap_bytes suffices), 0 when the level has no such array, < 0 on error.
+ * Requires sgo_linearize; refuses the row-owner mode and an active overlay, as sgo_debug_coarse_rhs does. */
+#define SGO_AMG_INFO 0
+#define SGO_AMG_A_ROWPTR 1
+#define SGO_AMG_A_COL 2
+#define SGO_AMG_A_BLK 3
+#define SGO_AMG_A_BLK_F32 4
+#define SGO_AMG_A_DINV 5
+#define SGO_AMG_POS 6
+#define SGO_AMG_D 7
+#define SGO_AMG_AGG 8
+#define SGO_AMG_MEM_PTR 9
+#define SGO_AMG_MEM 10
+#define SGO_AMG_P_ROWPTR 11
+#define SGO_AMG_P_ROW 12
+#define SGO_AMG_P_COL 13
+#define SGO_AMG_P_BLK 14
+#define SGO_AMG_P_RBLK 15
+#define SGO_AMG_P_TBLK 16
+#define SGO_AMG_P_TPOS 17
+#define SGO_AMG_P_TROW 18
+#define SGO_AMG_P_TCOL 19
+#define SGO_AMG_STRONG 20
+#define SGO_AMG_DF 21
+#define SGO_AMG_DINVF 22
+#define SGO_AMG_AP_A 23
+#define SGO_AMG_AP_B 24
+#define SGO_AMG_AP_TGT 25
+#define SGO_AMG_AP_BLK 26
+#define SGO_AMG_PS_ROW 27
+#define SGO_AMG_PS_COL 28
+#define SGO_AMG_PS_RBLK 29
+#define SGO_AMG_PS_TBLK 30
+#define SGO_AMG_PS_TROW 31
+#define SGO_AMG_PS_TCOL 32
+#define SGO_AMG_PS_STPOS 33
+#define SGO_AMG_INV 34
+#define SGO_AMG_ROW_ORDER 35
+#define SGO_AMG_INFO_COUNT 24
+int64_t sgo_debug_amg_array(sgo_ctx* ctx, int32_t level, int32_t what, void* out, int64_t cap_bytes);
 /* Diagnostic (env SGO_LANCZOS=1 when the graph is set): alpha, beta of every PCG iteration of the last solve as pairs in
  * iteration order -- the Lanczos matrix of the preconditioned operator follows from them (scripts/ritz_probe.py).  Returns
  * the iterations written (<= cap pairs), < 0 on error. */

@@ -29,7 +29,7 @@ SYMBOLS = [
     "sgo_comm_init", "sgo_comm_size", "sgo_shard_range", "sgo_debug_set_shard", "sgo_last_error",
     "sgo_closure_information", "sgo_plan_rows", "sgo_mfront_plan", "sgo_debug_coarse_rhs", "sgo_debug_spmv0_us",
     "sgo_solver_description", "sgo_comm_init_host", "sgo_comm_host_allgather", "sgo_debug_level0_bytes",
-    "sgo_kernel_profile_samples", "sgo_update_graph_se2", "sgo_debug_lanczos",
+    "sgo_kernel_profile_samples", "sgo_update_graph_se2", "sgo_debug_lanczos", "sgo_debug_amg_array",
 ]
 
 
@@ -130,6 +130,8 @@ def lib():
     L.sgo_comm_size.argtypes = [vp]
     L.sgo_comm_init_host.argtypes = [vp, C.c_int, C.c_int, HOST_ALLREDUCE, vp]
     L.sgo_comm_host_allgather.argtypes = [vp, HOST_ALLGATHER]
+    L.sgo_debug_amg_array.restype = C.c_int64
+    L.sgo_debug_amg_array.argtypes = [vp, C.c_int32, C.c_int32, vp, C.c_int64]
     L.sgo_debug_level0_bytes.restype = C.c_int64
     L.sgo_debug_level0_bytes.argtypes = [vp]
     L.sgo_shard_range.restype = None

@@ -132,6 +132,7 @@ struct Comm;
 void amg_set_shard(Amg* m, Comm* comm, int u0, int u1, int row0, int row1, const HaloDev* slices = nullptr);   // slices: all-gather the product vectors by rank slices
 bool amg_comm_failed(const Amg* m);
 int amg_debug_coarse_rhs(Amg* m, hipStream_t s, const double* r, double* out_dev, int cap3);   // test hook, see sgo_amg.hip
+long long amg_debug_array(Amg* m, hipStream_t s, int level, int what, void* out, long long cap_bytes);   // test hook, see sgo_amg.hip
 double* amg_xs0(Amg* m);     // [n][3] on the device; nullptr for a single-level (dense) hierarchy
 double amg_omega(const Amg* m);
 // true when the last amg_update met a non-positive pivot in the coarsest operator (synchronises `s`)

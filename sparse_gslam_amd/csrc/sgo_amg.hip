@@ -30,6 +30,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <numeric>
 #include <vector>
 
@@ -2214,6 +2215,116 @@ int amg_debug_coarse_rhs(Amg* m, hipStream_t s, const double* r, double* out_dev
   }
   hipMemcpyAsync(out_dev, m->lv[1].bk, sizeof(double) * n3c, hipMemcpyDeviceToDevice, s);
   return n3c;
+}
+namespace {
+// The logical slots' blocks as [nslot][9] records (load_block: level 0 through its references into the symmetric storage).  With
+// fblk: the off-diagonal blocks from the fp32 copy the preconditioner's level-0 tile passes read (diagonal blocks stay fp64 there).
+__global__ __launch_bounds__(kBlock) void k_debug_blocks(BsrDev A, const float* __restrict__ fblk, const float* __restrict__ fblk8,
+                                                         double* __restrict__ out) {
+  for (int k = blockIdx.x * kBlock + threadIdx.x; k < A.nslot; k += gridDim.x * kBlock) {
+    double b[9];
+    load_block(A, (size_t)k, b);
+    if (fblk && A.ref && A.ref[k] >= 0) {
+      const int r = A.ref[k];
+      const size_t u = (size_t)(r >> 1), nu = (size_t)A.nus;
+      double v[9];
+      for (int c = 0; c < 8; ++c) v[c] = (double)fblk[4 * ((size_t)(c >> 2) * nu + u) + (c & 3)];
+      v[8] = (double)fblk8[u];
+      for (int p = 0; p < 3; ++p)
+        for (int q = 0; q < 3; ++q) b[3 * p + q] = (r & 1) ? v[3 * q + p] : v[3 * p + q];
+    }
+    for (int c = 0; c < 9; ++c) out[9 * (size_t)k + c] = b[c];
+  }
+}
+}  // namespace
+
+// Test hook (sgo_debug_amg_array, sgo.h): array `what` of level `level` of the resident hierarchy, exactly as the next cycle and the
+// next amg_update read it -- device memory copied as stored; the one gather is a level's logical blocks (k_debug_blocks).  Returns the
+// array's size in bytes and copies it when cap_bytes suffices, 0 when the level has no such array, < 0 on error.  Single GPU only.
+long long amg_debug_array(Amg* m, hipStream_t s, int level, int what, void* out, long long cap_bytes) {
+  if (!m || level < 0 || level >= (int)m->lv.size()) return 0;
+  if (m->shard.mode != Shard0::single) return SGO_EINVAL;
+  const int last = (int)m->lv.size() - 1;
+  AmgLevel& L = m->lv[level];
+  const PDev& P = L.P;
+  const PDev& PS = L.PS;
+  const bool transfer = level < last, sm = transfer && L.smoothed, fo = sm && L.fold;
+  const size_t n = (size_t)L.A.n, ns = (size_t)L.A.nslot, nc = transfer ? (size_t)L.nc : 0;
+  const size_t nsc = transfer ? (size_t)m->lv[level + 1].A.nslot : 0;
+  const void* src = nullptr;
+  size_t bytes = 0;
+  auto arr = [&](bool have, const void* p, size_t count, size_t elem) {
+    if (have && p) {
+      src = p;
+      bytes = count * elem;
+    }
+  };
+  const size_t I = sizeof(int), F = sizeof(float), Dd = sizeof(double);
+  const bool f32 = level == 0 && m->T0.ntile > 0 && m->S0.fblk != nullptr;   // (pass0's rule)
+  switch (what) {
+    case SGO_AMG_INFO: {
+      const CycleForm cf = cycle_form(m, level, false, false);
+      const double v[SGO_AMG_INFO_COUNT] = {(double)n, (double)ns, (double)nc, sm ? 1.0 : 0.0, (sm && P.dF) ? 1.0 : 0.0, fo ? 1.0 : 0.0,
+                                            transfer ? (double)cf.kind : 0.0, transfer ? (double)cf.nu : 0.0, m->cfg.omega, m->cfg.omega_p,
+                                            sm ? (double)P.np : 0.0, sm ? (double)P.nap : 0.0, sm ? (double)P.val.n : 0.0,
+                                            sm ? (double)P.ap.n : 0.0, sm ? (double)P.rap.n : 0.0, (double)(last + 1), f32 ? 1.0 : 0.0,
+                                            (double)m->N, (double)m->Np, sm ? (double)P.t_nlong : 0.0, fo ? (double)PS.t_nlong : 0.0,
+                                            (double)m->kdepth, m->cfg.theta_filter, (double)nsc};
+      if (cap_bytes >= (long long)sizeof v) std::memcpy(out, v, sizeof v);
+      return (long long)sizeof v;
+    }
+    case SGO_AMG_A_ROWPTR: arr(true, L.A.rowptr, n + 1, I); break;
+    case SGO_AMG_A_COL: arr(true, L.A.col, ns, I); break;
+    case SGO_AMG_A_BLK:
+    case SGO_AMG_A_BLK_F32: {
+      if (what == SGO_AMG_A_BLK_F32 && !f32) return 0;
+      const long long need = (long long)(9 * ns * Dd);
+      if (cap_bytes < need) return need;
+      double* tmp = nullptr;
+      if (hipMalloc(&tmp, (size_t)need) != hipSuccess) return SGO_ENOMEM;
+      SGO_LAUNCH(k_debug_blocks, dim3(grid_for((long long)ns, kBlock)), dim3(kBlock), 0, s, L.A,
+                 what == SGO_AMG_A_BLK_F32 ? (const float*)m->S0.fblk : (const float*)nullptr, (const float*)m->S0.fblk8, tmp);
+      hipError_t e = hipMemcpyAsync(out, tmp, (size_t)need, hipMemcpyDeviceToHost, s);
+      if (e == hipSuccess) e = hipStreamSynchronize(s);
+      hipFree(tmp);
+      return e == hipSuccess ? need : (long long)SGO_EHIP;
+    }
+    case SGO_AMG_A_DINV: arr(true, L.A.dinv, 6 * n, Dd); break;
+    case SGO_AMG_POS: arr(true, L.pos, 2 * n, Dd); break;
+    case SGO_AMG_D: arr(transfer, L.d, 2 * n, Dd); break;
+    case SGO_AMG_AGG: arr(transfer, L.agg, n, I); break;
+    case SGO_AMG_MEM_PTR: arr(transfer, L.mem_ptr, nc + 1, I); break;
+    case SGO_AMG_MEM: arr(transfer, L.mem, n, I); break;
+    case SGO_AMG_P_ROWPTR: arr(sm, P.rowptr, n + 1, I); break;
+    case SGO_AMG_P_ROW: arr(sm, P.row, (size_t)P.np, I); break;
+    case SGO_AMG_P_COL: arr(sm, P.col, (size_t)P.np, I); break;
+    case SGO_AMG_P_BLK: arr(sm, P.blk, 9 * (size_t)P.np, Dd); break;
+    case SGO_AMG_P_RBLK: arr(sm, P.r_blk, 9 * (size_t)P.r_n, F); break;   // quads [2][np][4], then component 8 [np]
+    case SGO_AMG_P_TBLK: arr(sm, P.t_blk, 9 * (size_t)P.t_n, F); break;
+    case SGO_AMG_P_TPOS: arr(sm, P.t_pos, (size_t)P.np, I); break;
+    case SGO_AMG_P_TROW: arr(sm, P.t_row, (size_t)P.np, I); break;
+    case SGO_AMG_P_TCOL: arr(sm, P.t_col, (size_t)P.np, I); break;
+    case SGO_AMG_STRONG: arr(sm && P.dF, P.strong, ns, 1); break;
+    case SGO_AMG_DF: arr(sm, P.dF, 9 * n, Dd); break;
+    case SGO_AMG_DINVF: arr(sm, P.dinvF, 9 * n, Dd); break;
+    case SGO_AMG_AP_A: arr(sm, P.ap.a, (size_t)P.ap.n, I); break;
+    case SGO_AMG_AP_B: arr(sm, P.ap.b, (size_t)P.ap.n, I); break;
+    case SGO_AMG_AP_TGT: arr(sm, P.ap.tgt, (size_t)P.ap.n, I); break;
+    case SGO_AMG_AP_BLK: arr(sm, P.apblk, 9 * (size_t)P.nap, Dd); break;
+    case SGO_AMG_PS_ROW: arr(fo, PS.row, (size_t)PS.np, I); break;
+    case SGO_AMG_PS_COL: arr(fo, PS.col, (size_t)PS.np, I); break;
+    case SGO_AMG_PS_RBLK: arr(fo, PS.r_blk, 9 * (size_t)PS.r_n, F); break;
+    case SGO_AMG_PS_TBLK: arr(fo, PS.t_blk, 9 * (size_t)PS.t_n, F); break;
+    case SGO_AMG_PS_TROW: arr(fo, PS.t_row, (size_t)PS.np, I); break;
+    case SGO_AMG_PS_TCOL: arr(fo, PS.t_col, (size_t)PS.np, I); break;
+    case SGO_AMG_PS_STPOS: arr(fo, L.F.st_pos, (size_t)PS.np, I); break;
+    case SGO_AMG_INV: arr(level == last, m->inv, (size_t)m->Np * m->Np, Dd); break;
+    default: return SGO_EINVAL;
+  }
+  if (!src || bytes == 0) return 0;
+  if (cap_bytes < (long long)bytes) return (long long)bytes;
+  if (hipMemcpyAsync(out, src, bytes, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) return SGO_EHIP;
+  return (long long)bytes;
 }
 double* amg_xs0(Amg* m) { return (m && m->lv.size() > 1) ? m->lv[0].xs : nullptr; }
 double amg_omega(const Amg* m) { return m ? m->cfg.omega : 0.0; }

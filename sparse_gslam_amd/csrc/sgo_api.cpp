@@ -661,6 +661,39 @@ int sgo_debug_coarse_rhs(sgo_ctx* c, const double* r, double* out, int cap) {
   return n3;
 }
 
+// Test hook: one array of the resident multigrid hierarchy as the next cycle / refresh reads it (amg_debug_array, sgo_amg.hip).
+int64_t sgo_debug_amg_array(sgo_ctx* c, int32_t level, int32_t what, void* out, int64_t cap_bytes) {
+  try {
+    int rc = check_graph(c);
+    if (rc) return rc;
+    if (c->ov.active) {
+      c->err = "single-step entry points need a full set-up: the resident graph carries an incremental overlay (call sgo_set_graph_se2)";
+      return SGO_EINVAL;
+    }
+    if (!c->linearized) {
+      c->err = "sgo_debug_amg_array: call sgo_linearize first";
+      return SGO_EINVAL;
+    }
+    if (c->owner) {   // a rank holds its own rows' blocks and transfer entries only
+      c->err = "sgo_debug_amg_array: not available in multi-GPU row-owner mode";
+      return SGO_EINVAL;
+    }
+    if (cap_bytes < 0 || (cap_bytes > 0 && !out)) return SGO_EINVAL;
+    if (!c->amg) return 0;
+    if (what == SGO_AMG_ROW_ORDER) {
+      if (level != 0) return 0;
+      const int64_t bytes = (int64_t)sizeof(int) * c->n;
+      if (cap_bytes >= bytes)
+        for (int i = 0; i < c->n; ++i) static_cast<int*>(out)[i] = c->row_of_asc[i];
+      return bytes;
+    }
+    const long long r = amg_debug_array(c->amg, c->stream, level, what, out, cap_bytes);
+    if (r == SGO_EINVAL) c->err = "sgo_debug_amg_array: unknown array, or the level-0 passes are sharded";
+    if (r == SGO_EHIP) c->err = "sgo_debug_amg_array: device copy failed";
+    return r;
+  } SGO_CATCH(c)
+}
+
 // Diagnostic (env SGO_LANCZOS=1 at sgo_set_graph_se2): alpha / beta of every PCG iteration of the last solve, pairs in
 // iteration order; returns the number of iterations written (the Lanczos matrix of the preconditioned operator follows
 // from them: scripts/ritz_probe.py), < 0 on error.

@@ -1,0 +1,426 @@
+"""The stage checkers of tests/amg_reference.py, proven without a GPU.
+
+Small hierarchies (three levels, 600 poses of synth.manhattan, aggregates = consecutive triples along the trajectory) are built
+forward in plain fp64 with scipy's block-sparse products -- an implementation that shares nothing with the reference's own
+enumeration of block products and sums in another order -- into export-shaped dictionaries: one smoothed, one filtered (the weak
+slots made by switching closures off through phi), one tentative.  Every stage checker must pass on them at the constants the
+GPU cases use, and must FAIL on each
+mutation below at a ratio error / bound of at least 10 x the stage's constant (the ratios are printed: run with -s).  The cycle
+reference is validated against dense long-double algebra and against the rigid modes, not against its own recursion.
+"""
+import copy
+
+import numpy as np
+import pytest
+import scipy.sparse as sp
+
+import amg_reference as ar
+from kernel_reference import LD, U
+from oracle import np_oracle as npo
+from sparse_gslam_amd import synth
+
+OMEGA, OMEGA_P, THETA_F = 0.8, 0.66, 1e-3
+
+
+# ------------------------------------------------------------------ forward builder (plain fp64, scipy)
+def _bsr(rowptr, col, blk, shape):
+    return sp.bsr_matrix((np.ascontiguousarray(blk), np.asarray(col), np.asarray(rowptr)), shape=shape, blocksize=(3, 3))
+
+
+def _diag_first(M):
+    """rowptr, col, blk of a block-sparse matrix with every row's diagonal slot first, the others ascending."""
+    M = M.tobsr((3, 3))
+    M.sort_indices()
+    rp, col, blk = M.indptr.copy(), M.indices.copy(), M.data.copy()
+    for i in range(rp.size - 1):
+        s = slice(rp[i], rp[i + 1])
+        q = int(np.flatnonzero(col[s] == i)[0])
+        order = np.r_[q, np.delete(np.arange(col[s].size), q)]
+        col[s], blk[s] = col[s][order], blk[s][order]
+    return rp.astype(np.int32), col.astype(np.int32), blk
+
+
+def _pack6(M):
+    return np.stack([M[:, 0, 0], M[:, 0, 1], M[:, 0, 2], M[:, 1, 1], M[:, 1, 2], M[:, 2, 2]], axis=1)
+
+
+def _column_order(col):
+    order = np.argsort(col, kind="stable")
+    pos = np.empty(col.size, dtype=np.int32)
+    pos[order] = np.arange(col.size, dtype=np.int32)
+    return order, pos
+
+
+def build(kind, V=601, E=1500, mut=None, forms=((ar.FOLDED, 1), (ar.UNFOLDED, 2)), seed=3, hubs=True):
+    """Three levels (kind: "smoothed" | "filtered" | "tentative") as export-shaped dicts, and the rows of level 0 that have an
+    edge to the fixed vertex.  mut: a mistake built INTO the hierarchy (the exported formula inputs stay the true ones)."""
+    g = synth.manhattan(V, E, seed=seed, info_mode="full")
+    phi = g.phi.copy()
+    if kind == "filtered":
+        close = np.flatnonzero(phi >= 0)
+        phi[close[::2]] = 1e-7            # DCS switches these closures off: their blocks fall below the filter's threshold
+    ei, ej, meas, info = g.ei, g.ej, g.meas, g.info
+    if kind == "filtered" and hubs:
+        # rows without any kept connection: both odometry neighbours made heavy hubs by a closure of 10^8 times the usual weight
+        a = np.array([100, 250, 400])
+        hi, hj = np.r_[a - 1, a + 1], np.r_[a + 40, a + 50]
+        ei, ej = np.r_[ei, hi].astype(np.int32), np.r_[ej, hj].astype(np.int32)
+        meas = np.r_[meas, npo.se2_mul(npo.se2_inv(g.poses[hi]), g.poses[hj])]
+        info = np.r_[info, np.tile(np.array([1e10, 0.0, 0.0, 1e10, 0.0, 1e10]), (hi.size, 1))]
+        phi = np.r_[phi, np.full(hi.size, -1.0)]
+    H, *_ = npo.linearize(g.poses, g.fixed, ei, ej, meas, info, phi)
+    hidx, free = npo.hessian_index(g.fixed)
+    anchored = np.zeros(free.size, dtype=bool)
+    for a, b in ((ei, ej), (ej, ei)):
+        anchored[hidx[a[g.fixed[b] & ~g.fixed[a]]]] = True
+    pos = g.poses[free][:, :2].copy()
+    A = H.tobsr((3, 3))
+    levels = []
+    for l in range(3):
+        rp, col, blk = _diag_first(A)
+        n = rp.size - 1
+        L = dict(n=n, nslot=int(col.size), nc=0, smoothed=0, filtered=0, folded=0, kind=0, nu=1, omega=OMEGA, omega_p=OMEGA_P,
+                 theta_filter=THETA_F, f32=0, levels=3, rowptr=rp, col=col, blk=blk, pos=pos,
+                 dinv=_pack6(np.linalg.inv((blk[rp[:-1]] + np.swapaxes(blk[rp[:-1]], 1, 2)) / 2)))
+        levels.append(L)
+        if l == 2:
+            N = 3 * n
+            Np = (N + 31) // 32 * 32
+            inv = np.zeros((Np, Np))
+            inv[:N, :N] = np.linalg.inv(ar.dense_of(L))
+            L.update(N=N, Np=Np, inv=inv)
+            break
+        nc = (n + 2) // 3
+        agg = (np.arange(n) // 3).astype(np.int32)
+        mem_ptr = np.minimum(3 * np.arange(nc + 1), n).astype(np.int32)
+        src = pos + 0.01 if (mut == "stale_centres" and l == 0) else pos
+        cpos = np.stack([np.bincount(agg, weights=src[:, q], minlength=nc) for q in range(2)], axis=1) / np.bincount(agg)[:, None]
+        d = pos - cpos[agg]
+        L.update(nc=nc, agg=agg, mem_ptr=mem_ptr, mem=np.arange(n, dtype=np.int32), d=d)
+        dP = d * np.array([1.0, -1.0]) if (mut == "flip_dy" and l == 0) else d
+        T = _bsr(np.arange(n + 1), agg, ar.T_of(dP), (3 * n, 3 * nc))
+        row = ar.slot_rows(L)
+        if kind == "tentative":
+            A = (T.T @ A @ T).tobsr((3, 3))
+        else:
+            form, nu = forms[l]
+            L.update(smoothed=1, kind=form, nu=nu, folded=int(form != ar.UNFOLDED))
+            Dinv = ar.sym6(L["dinv"])
+            Asm = A
+            if kind == "filtered" and l == 0:
+                w = np.sqrt((blk ** 2).sum(axis=(1, 2)))
+                strong = ((w > 0) & (w * w >= THETA_F ** 2 * w[rp[:-1]][row] * w[rp[:-1]][col])).astype(np.uint8)
+                strong[rp[:-1]] = 1
+                weak = np.flatnonzero(strong == 0)
+                acc = np.zeros((n, 3, 3))
+                np.add.at(acc, row[weak], blk[weak] @ ar.T_of(pos[col[weak]] - pos[row[weak]]))
+                kept = np.bincount(row[(strong != 0) & (col != row)], minlength=n)
+                dF = blk[rp[:-1]] + np.where((kept > 0)[:, None, None], acc, 0.0)
+                tr = -np.einsum("nij,nji->n", Dinv, acc)
+                zero = (kept == 0) | (tr > 0.5)
+                if mut == "unjustified_zero":
+                    zero[np.flatnonzero(~zero & (tr < 0.4))[5]] = True
+                dinvF = np.where(zero[:, None, None], 0.0, np.linalg.inv(dF))
+                L.update(filtered=1, strong=strong, dF=dF, dinvF=dinvF)
+                bF = blk.copy()
+                if mut != "D_not_DF":
+                    bF[rp[:-1]] = dF
+                keep = np.flatnonzero(strong)
+                Asm = _bsr(*_csr_blocks(n, row[keep], col[keep], bF[keep]), (3 * n, 3 * n))
+                Dinv = dinvF
+            X = (Asm @ T).tobsr((3, 3))
+            X.sort_indices()
+            p_rowptr, p_col = X.indptr.astype(np.int32), X.indices.astype(np.int32)
+            p_row = np.repeat(np.arange(n), np.diff(p_rowptr)).astype(np.int32)
+            wp = 0.67 if (mut == "omega_p_067" and l == 0) else OMEGA_P
+            p_blk = -wp * (Dinv[p_row] @ X.data)
+            own = p_col == agg[p_row]
+            p_blk[own] += ar.T_of(dP[p_row[own]])
+            P = _bsr(p_rowptr, p_col, p_blk, (3 * n, 3 * nc))
+            AP = (A @ P).tobsr((3, 3))
+            AP.sort_indices()
+            ap_row = np.repeat(np.arange(n), np.diff(AP.indptr)).astype(np.int64)
+            order, t_pos = _column_order(p_col)
+            r32 = p_blk.reshape(-1, 9).astype(np.float32)
+            L.update(p_rowptr=p_rowptr, p_row=p_row, p_col=p_col, p_blk=p_blk, r_blk=r32, t_blk=r32[order], t_pos=t_pos,
+                     t_row=p_row[order], t_col=p_col[order], ap_row=ap_row, ap_col=AP.indices.astype(np.int64), apblk=AP.data.copy(),
+                     np=int(p_col.size), nap=int(AP.indices.size))
+            if L["folded"]:
+                e = ar.lookup(ar._p_keys(L), np.arange(p_col.size), ap_row * nc + AP.indices)
+                w = OMEGA_P if (mut == "ptilde_omega_p" and l == 0) else OMEGA
+                pt = np.where((e >= 0)[:, None, None], p_blk[np.maximum(e, 0)], 0.0) - w * (ar.sym6(L["dinv"])[ap_row] @ AP.data)
+                so, st = _column_order(AP.indices)
+                s32 = pt.reshape(-1, 9).astype(np.float32)
+                L.update(ps_r=s32, ps_t=s32[so], ps_stpos=st, ps_trow=ap_row[so].astype(np.int32), ps_tcol=AP.indices[so].astype(np.int32))
+            A = (P.T @ AP).tobsr((3, 3))
+        if kind != "tentative":   # the device makes the slots c >= a and mirrors them
+            A.sort_indices()
+            br = np.repeat(np.arange(nc), np.diff(A.indptr)).astype(np.int64)
+            lo = np.flatnonzero(A.indices < br)
+            mk = ar.lookup(br * nc + A.indices, np.arange(br.size), A.indices[lo].astype(np.int64) * nc + br[lo])
+            A.data[lo] = np.swapaxes(A.data[mk], 1, 2)
+        if mut == "coarse_fp32" and l == 0:
+            A.data[:] = A.data.astype(np.float32)
+        pos = cpos
+    return levels, anchored
+
+
+def _csr_blocks(n, row, col, blk):
+    """rowptr, col, blk of the slots (row, col, blk) sorted by (row, col); duplicates do not occur at this call."""
+    order = np.lexsort((col, row))
+    return np.searchsorted(row[order], np.arange(n + 1)), col[order], blk[order]
+
+
+@pytest.fixture(scope="module")
+def hier():
+    return {k: build(k)[0] for k in ("smoothed", "filtered", "tentative")}
+
+
+# ------------------------------------------------------------------ the reference's names against the header
+def test_array_codes_and_info_fields_follow_the_header():
+    """amg_reference.WHAT / INFO address sgo_debug_amg_array by position: they must be include/sgo.h's SGO_AMG_* numbering and
+    the INFO array it documents, field for field."""
+    import os
+    import re
+    src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "sgo.h")).read()
+    defs = {k: int(v) for k, v in re.findall(r"#define SGO_AMG_([A-Z0-9_]+) (\d+)", src)}
+    assert defs.pop("INFO_COUNT") == len(ar.INFO)
+    assert defs == ar.WHAT
+    doc = src[src.index("SGO_AMG_INFO: SGO_AMG_INFO_COUNT doubles {"):]
+    doc = re.sub(r"\s*\*\s*", " ", doc[doc.index("{") + 1:doc.index("}")])
+    fields = [f.strip() for f in re.sub(r"\([^)]*\)", "", doc).split(",")]
+    assert len(fields) == len(ar.INFO), fields
+    for k, name in ((0, "n"), (2, "nc"), (5, "folded"), (8, "omega"), (15, "levels"), (17, "N"), (23, "slots of the next level")):
+        assert fields[k].startswith(name) or name in fields[k], (k, fields[k])
+    assert ar.INFO[15] == "levels" and ar.INFO[17] == "N" and ar.INFO[23] == "nslot_c"
+
+
+# ------------------------------------------------------------------ the checkers pass on correct hierarchies
+@pytest.mark.parametrize("kind", ["smoothed", "filtered", "tentative"])
+def test_every_stage_passes_on_a_forward_built_hierarchy(hier, kind):
+    lv = hier[kind]
+    res = ar.check_hierarchy(lv, poses_xy=lv[0]["pos"])
+    print(kind, {k: round(v[0], 3) for k, v in ar.worst_by_stage(res).items()})
+    assert not ar.failures(res), ar.failures(res)
+    stages = {k.split(".")[0] for _, k in res}
+    want = {"partition", "geometry", "galerkin", "coarsest"}
+    if kind != "tentative":
+        want |= {"transfer", "copies", "folded", "pscopies"}
+    if kind == "filtered":
+        want |= {"filtered"}
+        assert lv[0]["_zero_rows"] > 0 and lv[0]["_nonzero_rows"] > 0 and (lv[0]["strong"] == 0).sum() > 50
+    assert stages == want, stages
+
+
+# ------------------------------------------------------------------ ... and fail on wrong ones
+def _drop_p_entry(lv):
+    L = lv[0]
+    e = int(np.flatnonzero(L["p_col"] != L["agg"][L["p_row"]])[7])
+    i = int(L["p_row"][e])
+    for k in ("p_row", "p_col", "p_blk", "r_blk"):
+        L[k] = np.delete(L[k], e, axis=0)
+    L["p_rowptr"] = L["p_rowptr"].copy()
+    L["p_rowptr"][i + 1:] -= 1
+
+
+def _drop_ap_product(lv):
+    L = lv[0]
+    f = 40
+    i, c = int(L["ap_row"][f]), int(L["ap_col"][f])
+    k, e = next((k, int(e[0])) for k in range(L["rowptr"][i], L["rowptr"][i + 1])
+                for e in [np.flatnonzero((L["p_row"] == L["col"][k]) & (L["p_col"] == c))] if e.size)
+    L["apblk"] = L["apblk"].copy()
+    L["apblk"][f] -= L["blk"][k] @ L["p_blk"][e]
+
+
+def _coarse_slot(lv, upper=True):
+    N = lv[1]
+    row = ar.slot_rows(N)
+    return int(np.flatnonzero((N["col"] > row) if upper else (N["col"] < row))[11])
+
+
+def _drop_coarse_product(lv):
+    L, N = lv[0], lv[1]
+    s = _coarse_slot(lv)
+    a, c = int(ar.slot_rows(N)[s]), int(N["col"][s])
+    e = int(np.flatnonzero(L["p_col"] == a)[0])
+    f = int(np.flatnonzero((L["ap_row"] == L["p_row"][e]) & (L["ap_col"] == c))[0])
+    N["blk"] = N["blk"].copy()
+    N["blk"][s] -= L["p_blk"][e].T @ L["apblk"][f]
+
+
+def _mirror_not_transposed(lv):
+    N = lv[1]
+    s = _coarse_slot(lv, upper=False)
+    N["blk"] = N["blk"].copy()
+    N["blk"][s] = N["blk"][s].T.copy()
+
+
+def _t_blk_last_bit(lv):
+    L = lv[0]
+    t = L["t_blk"].copy()
+    t.view(np.uint32)[17, 4] ^= 1
+    L["t_blk"] = t
+
+
+# (name, kind, mutation built into the hierarchy | None, mutation of the dictionary | None, the check that must reject it, stage)
+MUTATIONS = [
+    ("a P entry dropped", "smoothed", None, _drop_p_entry, (0, "transfer.pattern"), "transfer"),
+    ("a product dropped from one A P entry", "smoothed", None, _drop_ap_product, (0, "galerkin.ap"), "galerkin"),
+    ("a product dropped from one coarse slot", "smoothed", None, _drop_coarse_product, (0, "galerkin.coarse"), "galerkin"),
+    ("a mirror slot not transposed", "smoothed", None, _mirror_not_transposed, (0, "galerkin.mirror"), "galerkin"),
+    ("d_y with the wrong sign", "smoothed", "flip_dy", None, (0, "transfer.values"), "transfer"),
+    ("centres from poses displaced by 1 cm", "smoothed", "stale_centres", None, (0, "geometry.centres"), "geometry"),
+    ("omega_p = 0.67", "smoothed", "omega_p_067", None, (0, "transfer.values"), "transfer"),
+    ("D instead of D_F", "filtered", "D_not_DF", None, (0, "transfer.values"), "transfer"),
+    ("a zeroed dinvF row without a reason", "filtered", "unjustified_zero", None, (0, "filtered.zero_rows"), "filtered"),
+    ("coarse blocks rounded to fp32", "smoothed", "coarse_fp32", None, (0, "galerkin.coarse"), "galerkin"),
+    ("t_blk differs from r_blk in one last bit", "smoothed", None, _t_blk_last_bit, (0, "copies.t_blk"), "transfer"),
+    ("P~ built with omega_p", "smoothed", "ptilde_omega_p", None, (0, "folded.values"), "folded"),
+]
+
+
+@pytest.mark.parametrize("name,kind,built,mutate,check,stage", MUTATIONS, ids=[m[0] for m in MUTATIONS])
+def test_every_mutation_is_rejected_ten_times_over(hier, name, kind, built, mutate, check, stage):
+    lv = build(kind, mut=built)[0] if built else copy.copy([dict(L) for L in hier[kind]])
+    if mutate:
+        mutate(lv)
+    res = ar.check_hierarchy(lv, poses_xy=lv[0]["pos"], stages=(1, 2, 3, 4, 5, 6, 7))
+    scaled, raw, at = res[check]
+    print(f"{name}: error / bound = {raw:.3g} (C = {ar.C_STAGE[stage]}, {raw / ar.C_STAGE[stage]:.3g} x C) at {at}")
+    assert raw >= 10.0 * ar.C_STAGE[stage], (name, raw)
+    assert check in ar.failures(res)
+
+
+def _vectors(n, seed):
+    rng = np.random.default_rng(seed)
+    return [rng.standard_normal((n, 3)), rng.uniform(-1.0, 1.0, (n, 3)),
+            rng.standard_normal((n, 3)) * 10.0 ** rng.choice([-6.0, 6.0], size=(n, 1))]
+
+
+def _wrong_restriction_column(lv, r):
+    L = lv[0]
+    key, rows = ("ps_tcol", "ps_trow") if L["folded"] else ("t_col", "t_row")
+    t = int(np.argmax(np.abs(r[L[rows]]).sum(axis=1)))      # (an entry whose row carries weight in this vector)
+    c = L[key].copy()
+    c[t] = (c[t] + 5) % L["nc"]
+    L[key] = c
+
+
+CYCLE_MUTATIONS = [("post-smoothing left out", dict(skip_post=True), None),
+                   ("nu off by one", {}, lambda lv, r: [L.update(nu=L["nu"] + 1) for L in lv[:2] if L["kind"] == ar.UNFOLDED]),
+                   ("the restriction reads one wrong column", {}, _wrong_restriction_column)]
+
+
+@pytest.mark.parametrize("forms", [((ar.FOLDED, 1), (ar.UNFOLDED, 2)), ((ar.UNFOLDED, 1), (ar.FOLDED2, 2))], ids=["folded0", "unfolded0"])
+@pytest.mark.parametrize("name,kw,mutate", CYCLE_MUTATIONS, ids=[m[0] for m in CYCLE_MUTATIONS])
+def test_cycle_mutations_exceed_ten_k_eps(name, kw, mutate, forms):
+    lv = build("smoothed", forms=forms)[0]
+    for q, r in enumerate(_vectors(lv[0]["n"], 5)):
+        z, eps = ar.cycle_scale(lv, r)
+        m = [dict(L) for L in lv]
+        if mutate:
+            mutate(m, r)
+        ratio = ar.cycle_ratio(ar.Cycle(m, LD, **kw)(0, r), z, eps)
+        print(f"{name}, vector {q}: eps = {eps:.3g}, error / eps = {ratio:.3g} ({ratio / ar.K_CYCLE:.3g} x K)")
+        assert eps < 1e-12 and ratio >= 10.0 * ar.K_CYCLE, (name, q, ratio, eps)
+
+
+# ------------------------------------------------------------------ the cycle reference against dense algebra
+def _dense_blocks(row, col, blk, n, m):
+    M = np.zeros((3 * n, 3 * m), dtype=LD)
+    for r in range(3):
+        for c in range(3):
+            np.add.at(M, (3 * np.asarray(row, dtype=np.int64) + r, 3 * np.asarray(col, dtype=np.int64) + c), np.asarray(blk, dtype=LD)[:, r, c])
+    return M
+
+
+def _two_level(nu):
+    lv = build("smoothed", V=241, E=600, forms=((ar.UNFOLDED, nu), (ar.UNFOLDED, 1)))[0][:2]
+    N = 3 * lv[1]["n"]
+    inv = np.linalg.inv(ar.dense_of(lv[1]))
+    lv[1].update(N=N, Np=N, inv=inv, levels=2)
+    lv[0]["levels"] = 2
+    return lv
+
+
+@pytest.mark.parametrize("nu", [1, 2])
+def test_error_propagator_of_the_two_level_cycle(nu):
+    """I - M A = S^nu (I - P B_c P^T A) S^nu with S = I - omega D^-1 A, B_c the coarse level's (exported) inverse and P the
+    transfer as stored: M formed column by column from the reference, the right side in dense long-double algebra."""
+    lv = _two_level(nu)
+    L = lv[0]
+    if nu == 2:
+        L["nu"] = 2   # (level 0 runs one sweep on the device; the formula holds for any nu, and level >= 1 code is the same)
+    n, nc = L["n"], L["nc"]
+    cyc = ar.Cycle(lv, LD)
+    eye = np.eye(3 * n)
+    M = np.stack([cyc(0, eye[:, k].reshape(n, 3)).reshape(-1) for k in range(3 * n)], axis=1)
+    A = _dense_blocks(ar.slot_rows(L), L["col"], L["blk"], n, n)
+    P = _dense_blocks(L["p_row"], L["p_col"], L["r_blk"].reshape(-1, 3, 3), n, nc)
+    Dinv = _dense_blocks(np.arange(n), np.arange(n), ar.sym6(L["dinv"]), n, n)
+    I = np.eye(3 * n, dtype=LD)
+    S = I - LD(OMEGA) * ar.matmul_ld(Dinv, A)
+    Sn = S if nu == 1 else ar.matmul_ld(S, S)
+    Bc = lv[1]["inv"].astype(LD)
+    E = ar.matmul_ld(Sn, ar.matmul_ld(I - ar.matmul_ld(P, ar.matmul_ld(Bc, ar.matmul_ld(P.T, A))), Sn))
+    # (M A cancels to O(1) from products of the size of cond(A): the long-double rounding of that product is the scale)
+    scale = 3 * n * np.finfo(LD).eps * ar.matmul_ld(np.abs(M), np.abs(A)).max()
+    err = np.abs(I - ar.matmul_ld(M, A) - E).max()
+    print("error propagator, nu", nu, float(err), "allowed", float(scale))
+    assert err <= scale and scale < 1e-9, (float(err), float(scale))
+
+
+def test_folded_and_unfolded_forms_agree_with_unrounded_ptilde():
+    lv = _two_level(1)
+    L = lv[0]
+    n, nc = L["n"], L["nc"]
+    A = _dense_blocks(ar.slot_rows(L), L["col"], L["blk"], n, n)
+    P = _dense_blocks(L["p_row"], L["p_col"], L["r_blk"].reshape(-1, 3, 3), n, nc)
+    Dinv = _dense_blocks(np.arange(n), np.arange(n), ar.sym6(L["dinv"]), n, n)
+    Pt = P - LD(OMEGA) * ar.matmul_ld(Dinv, ar.matmul_ld(A, P))
+    i, c = L["ap_row"], L["ap_col"]
+    blocks = np.stack([Pt[3 * i[f]:3 * i[f] + 3, 3 * c[f]:3 * c[f] + 3] for f in range(i.size)])
+    rebuilt = _dense_blocks(i, c, blocks, n, nc)
+    assert np.array_equal(rebuilt, Pt), "P~ has entries outside A P's pattern"
+    so, st = _column_order(c)
+    F = [dict(L, kind=ar.FOLDED, folded=1, ps_r=blocks.reshape(-1, 9), ps_t=blocks.reshape(-1, 9)[so], ps_stpos=st,
+              ps_trow=i[so], ps_tcol=c[so]), lv[1]]
+    for r in _vectors(n, 9):
+        zu, zf = ar.Cycle(lv, LD)(0, r), ar.Cycle(F, LD)(0, r)
+        err = float(np.sqrt(((zu - zf) ** 2).sum()) / np.sqrt((zu ** 2).sum()))
+        assert err < 1e-16, err
+
+
+@pytest.mark.parametrize("kind", ["smoothed", "filtered"])
+def test_transfers_reproduce_the_rigid_modes(kind):
+    """P_l B_{l+1} = B_l, B the three rigid modes about the level's positions (T(pos) per node), on every row whose operator row
+    annihilates them: level 0 rows without an edge to the fixed vertex, a coarse row none of whose fine rows has one.  This holds
+    for the formula of stage 4 and for no variant of it with a wrong lever arm, damping or diagonal block."""
+    lv, anchored = build(kind, hubs=False)   # (without the 10^10 hub closures: their rounding would set the scale of every row)
+    for l in range(2):
+        L, N = lv[l], lv[l + 1]
+        got = np.zeros((L["n"], 3, 3), dtype=LD)
+        mag = np.zeros((L["n"], 3, 3))
+        Tc = ar.T_of(N["pos"][L["p_col"]])
+        ar.seg_add(got, L["p_row"].astype(np.int64), ar.bmm(L["p_blk"], Tc))
+        ar.seg_add(mag, L["p_row"].astype(np.int64), np.abs(L["p_blk"]) @ np.abs(Tc))
+        # the smoothing term's own cancellation: omega_p |Dinv| sum |A_k| |T(p_j)|
+        row = ar.slot_rows(L)
+        sm = np.zeros((L["n"], 3, 3))
+        ar.seg_add(sm, row, np.abs(L["blk"]) @ np.abs(ar.T_of(L["pos"][L["col"]])))
+        Dinv = np.abs(L["dinvF"]) if L["filtered"] else np.abs(ar.sym6(L["dinv"]))
+        # (64: the builder's own sequential sums of up to ~160 terms stand behind a coarse level's operator row)
+        # ... and the diagonal block's own rounding, U |D| normwise (its entries are sums that cancel: J^T W J through rotations)
+        Dn = np.linalg.norm(Dinv, axis=(1, 2)) * np.linalg.norm(L["blk"][L["rowptr"][:-1]], axis=(1, 2)) * (1.0 + np.abs(L["pos"]).sum(axis=1))
+        bound = 64 * U * (mag + OMEGA_P * (Dinv @ sm + Dn[:, None, None]))
+        err = np.abs(got - ar.T_of(L["pos"], LD)).astype(np.float64)
+        Ap = sp.csr_matrix((np.ones(row.size), (row, L["col"])), shape=(L["n"], L["n"]))
+        free = ~anchored
+        assert free.sum() > 0.8 * free.size
+        assert (err[free] <= bound[free]).all(), (l, float(np.nanmax(err[free] / np.maximum(bound[free], 1e-300))))
+        assert (err[anchored] > bound[anchored]).any()      # ... and an anchored row does not
+        # the next level's row a annihilates the modes only if P B = B holds on every row A P's column a reaches
+        nxt = np.zeros(L["nc"], dtype=bool)
+        nxt[L["ap_col"][anchored[L["ap_row"]] | (Ap @ anchored.astype(float) > 0)[L["ap_row"]]]] = True
+        anchored = nxt
