@@ -17,8 +17,13 @@ struct AmgConfig {
   double theta_scale = 1.0;    // both thresholds are multiplied by this (the caller halves it when a hierarchy's first solve stalls)
   double omega = 0.8;      // block-Jacobi damping
   int max_levels = 10;
-  int nu_coarse = 1;           // smoothing sweeps on the coarser V-cycle levels; amg_create picks 2 for
-                               // graphs with >= 6 * 10^5 level-0 blocks, where a coarse sweep is cheap next to level 0
+  int nu_coarse = 1;           // smoothing sweeps on the coarser V-cycle levels; amg_effective_config picks 2 for
+                               // graphs with >= 6 * 10^5 level-0 blocks, where a coarse sweep is cheap next to level 0 (env
+                               // SGO_AMG_NU), and amg_create goes back to 1 for a hierarchy whose level 1 is large
+  bool nu_from_env = false;    // ... SGO_AMG_NU was set: amg_create leaves nu_coarse as it is
+  int kdepth = 1 << 20;        // levels <= kdepth use the K-cycle, deeper ones a V-cycle; amg_effective_config: 0 with the smoothed
+                               // prolongator (env SGO_AMG_KDEPTH)
+  int fcg2_depth = 1;          // levels <= this take two FCG steps, deeper K-cycle levels one (env SGO_AMG_FCG2_DEPTH; see Amg)
   bool smooth = true;          // smoothed aggregation: P = (I - omega_p D^-1 A) T (env SGO_AMG_SMOOTH=0: tentative P)
   double omega_p = 0.66;       // damping of the prolongator smoothing step
   double theta_filter = 1e-3;       // ... "strong" for that filter: w_ij >= theta_filter sqrt(w_ii w_jj) -- far below the aggregation's

@@ -1702,14 +1702,14 @@ struct Amg {
   std::vector<AmgLevel> lv;
   const double* d_poses = nullptr;
   const int* d_free_id = nullptr;
-  int kdepth = 1 << 20;  // levels <= kdepth use the K-cycle (two FCG steps), deeper ones a V-cycle
+  int kdepth = 1 << 20;  // levels <= kdepth use the K-cycle (two FCG steps), deeper ones a V-cycle (amg_create: AmgConfig::kdepth)
   // Levels <= this take two FCG steps, deeper K-cycle levels one.  Two steps everywhere visit level l 2^l times:
   // on hierarchies of six levels (C4 with 5 % random closures: 100k -> 11k -> 2.5k -> 897 -> 627 -> 1) that is ~150
   // coarse launches per PCG iteration.  Two steps on level 1 only keep the PCG counts within 3-9 % (C4r 580 -> 597
   // over optimize(20)) at a third of the launches: C4r 22.5 -> 10.8 ms per GN iteration, 30k-pose graphs 1.2-1.3 x
   // (scripts/kcycle_sweep.py, profiles/r02_kcycle_sweep.txt); one step everywhere is faster still on average but
   // needs 40-50 % more iterations and doubles the worst solve.
-  int fcg2_depth = 1;
+  int fcg2_depth = 1;   // (amg_create: AmgConfig::fcg2_depth)
   // coarsest dense inverse (row-major, leading dimension Np = N rounded up to 32)
   int N = 0, Np = 0;
   double* inv = nullptr;
@@ -1811,6 +1811,14 @@ CycleForm cycle_form(const Amg* m, int l, bool rhs_sub, bool dots) {
     if (f.nu == 2) f.kind = CycleForm::folded_in_two_sweeps;
   }
   return f;
+}
+
+// Whether the set-up folds level l, whose share of A P (the pattern of P~) holds nf entries.  Level 0 is folded only where it is itself
+// launch-bound: P~ has the pattern of A P, twice the entries of P, and on large graphs streaming it twice per cycle costs what the
+// saved launch and pass bring -- C4: restriction + prolongation 14 + 20 us with P~ against 11 + 9 us with P.  Multi-GPU row-owner
+// runs keep level 0 unfolded as well.  (A level with too many long columns is not folded after all: long_columns.)
+bool fold_level(const Amg* m, int l, int nf) {
+  return m->cfg.fold && nf > 0 && (l > 0 || (m->shard.mode != Shard0::owner && m->lv[0].A.n <= m->cfg.fold0_rows));
 }
 
 CoarseSol coarse_solve(Amg* m, hipStream_t s, int l, const PcgScalars* S);
@@ -2386,7 +2394,15 @@ AmgConfig amg_effective_config(const AmgConfig& cfg_in, int n, int nslot) {
   // (the folded cycle folds ONE sweep per side into the transfers -- two would need the pattern of A A P; a second sweep is
   // one explicit sweep around it, see cycle_form().  One sweep everywhere was measured on C4: five coarse launches instead of
   // nine, but 27.9 instead of 22.1 PCG iterations, 5.07 against 4.59 ms per GN iteration)
-  if (const char* e = std::getenv("SGO_AMG_NU")) cfg.nu_coarse = std::max(1, std::atoi(e));
+  if (const char* e = std::getenv("SGO_AMG_NU")) {
+    cfg.nu_coarse = std::max(1, std::atoi(e));
+    cfg.nu_from_env = true;   // (amg_create then leaves the count alone: finish_coarsest)
+  }
+  // With the smoothed prolongator a V-cycle needs ~1.4x the PCG iterations of the K-cycle (C4: 39 vs
+  // 27) at less than half the launches per iteration: V is the default there, K for the tentative one.
+  if (cfg.smooth) cfg.kdepth = 0;
+  if (const char* e = std::getenv("SGO_AMG_KDEPTH")) cfg.kdepth = std::atoi(e);
+  if (const char* e = std::getenv("SGO_AMG_FCG2_DEPTH")) cfg.fcg2_depth = std::atoi(e);
   // larger graphs afford a larger dense coarsest level (its inverse costs O(N^3) once per GN
   // iteration, one K-cycle level less halves the coarse-level launches of every PCG iteration).  A SMALLER dense level
   // (one more sparse level) was measured in round 3: the dense inverse gets cheaper but the cycle weaker -- stopping at
@@ -2442,17 +2458,16 @@ struct GroupBatch {
     const int* ptr = nullptr;
     int nseg = 0, total = 0;
     bool on = false;
+    const int** grp = nullptr;   // where run() leaves the list and its group count: the owner's fields
+    int* ngrp = nullptr;
   };
   Job job[G_COUNT];
-  int* grp[G_COUNT] = {};
-  int ngrp[G_COUNT] = {};
-  void add(GroupId id, const int* ptr, int nseg, int total) {
-    job[id].ptr = ptr;
-    job[id].nseg = nseg;
-    job[id].total = total;
-    job[id].on = true;
+  template <class IntPtr>   // (the owners' fields are int* or const int*)
+  void add(GroupId id, const int* ptr, int nseg, int total, IntPtr* grp, int* ngrp) {
+    job[id] = Job{ptr, nseg, total, true, (const int**)grp, ngrp};
   }
-  // all the pending lists (k_group_jobs): two launches, a scan and one synchronisation; the lists go to the hierarchy's arena
+  // all the pending lists (k_group_jobs): two launches, a scan and one synchronisation; the lists go to the hierarchy's arena and
+  // their addresses to the owners the jobs were added with
   bool run(DevSetup& D) {
     GroupJobsDev J;
     int ids[kMaxGroupJobs];
@@ -2485,9 +2500,10 @@ struct GroupBatch {
     if (!D.ok) return false;
     SGO_LAUNCH((k_group_jobs<true>), grid, block, 0, D.s, J, off, out);
     for (int q = 0; q < J.njobs; ++q) {
-      grp[ids[q]] = out + h_first[q];
-      ngrp[ids[q]] = h_first[q + 1] - h_first[q] - 1;
-      job[ids[q]].on = false;
+      Job& j = job[ids[q]];
+      *j.grp = out + h_first[q];
+      *j.ngrp = h_first[q + 1] - h_first[q] - 1;
+      j.on = false;
     }
     return D.ok;
   }
@@ -2642,22 +2658,20 @@ bool upload_coarse(DevSetup& D, const HostCoarse& hc, int n, const HaloDev* own,
   return true;
 }
 
-// The one level assembler: a coarsening step's DevCoarse, whichever producer made it, into the transfer data of lv[l] -- P and its
-// streamed fp32 copies, the folded cycle's bookkeeping, the product lists, every wave-group list of the level in one batch, the long
-// columns -- and the structure of the next level lv[l + 1].  Returns the failure's message, empty on success.
-std::string assemble_level(Amg* m, DevSetup& D, int l, const DevCoarse& dc) {
-  hipStream_t s = D.s;
-  const std::string oom = "amg_create: out of device memory";
+// ---- the steps of assemble_level, in its order.  Each returns the failure's message, empty on success.  lv[l] is theirs to fill; the
+// next level C stays assemble_level's local until every step has run.
+const char kOom[] = "amg_create: out of device memory";
+
+// The next level's shell -- structure from the producer; blocks, diagonal inverses and positions allocated -- and what lv[l] holds of
+// its aggregates
+std::string next_level_shell(Amg* m, DevSetup& D, int l, const DevCoarse& dc, GroupBatch& gb, AmgLevel& C) {
   AmgLevel& L = m->lv[l];
   const int n = L.A.n, nc = dc.nc;
-  const int r0 = dc.local ? m->shard.row0 : 0, r1 = dc.local ? m->shard.row1 : n;   // the rows whose entries are held
-  GroupBatch gb;
   L.nc = nc;
   L.agg = dc.agg;
   L.mem_ptr = dc.mem_ptr;
   L.mem = dc.mem;
   L.d = D.alloc<double>(2 * (size_t)n);
-  AmgLevel C;
   C.A.n = nc;
   C.A.nslot = dc.nslot_c;
   C.A.row = dc.c_row;
@@ -2666,247 +2680,260 @@ std::string assemble_level(Amg* m, DevSetup& D, int l, const DevCoarse& dc) {
   C.A.blk = D.alloc<double>(9 * (size_t)dc.nslot_c);
   C.A.dinv = D.alloc<double>(6 * (size_t)nc);
   C.pos = D.alloc<double>(2 * (size_t)nc);
-  if (!D.ok) return oom;
-  gb.add(G_MEM, dc.mem_ptr, nc, n);
-  gb.add(G_C, dc.c_rowptr, nc, dc.nslot_c);
-  bool fold_here = false;
-  int *t_ranges = nullptr, *st_ranges = nullptr;
-  if (dc.smooth) {
-    PDev& P = L.P;
-    L.smoothed = true;
-    const size_t ne = (size_t)(dc.e_hi - dc.e_lo), nf = (size_t)(dc.f_hi - dc.f_lo);   // entries of P and of A P held
-    P.local_lists = dc.local;
-    if (dc.filtered) {
-      P.dF = D.alloc<double>(9 * (size_t)n);
-      P.dinvF = D.alloc<double>(9 * (size_t)n);
-      P.strong = dc.strong;
-      gb.add(G_F, L.A.rowptr, n, L.A.nslot);
+  if (!D.ok) return kOom;
+  gb.add(G_MEM, dc.mem_ptr, nc, n, &L.mem_grp, &L.mem_ngrp);
+  gb.add(G_C, dc.c_rowptr, nc, dc.nslot_c, &C.A.grp, &C.A.ngrp);
+  return std::string();
+}
+
+// The two streamed fp32 copies of a transfer's n blocks, numbered from lo: the row-ordered one addressed by global entry numbers, the
+// column-ordered one by the positions held
+void streamed_copies(DevSetup& D, PDev& P, size_t n, int lo) {
+  float* rb = D.alloc<float>(9 * n + 4);
+  float* tb = D.alloc<float>(9 * n + 4);
+  if (!D.ok) return;
+  P.stream_nt = n >= 200000 ? 1 : 0;   // 2 x 72 B per block streamed per cycle: below ~30 MB it may stay cached
+  P.r_n = P.t_n = (int)n;
+  P.r_blk = rb - 4 * (size_t)lo;
+  P.r_blk8 = rb + 8 * n - lo;
+  P.t_blk = tb;
+  P.t_blk8 = tb + 8 * n;
+}
+
+// The arrays of the smoothed transfer P: its pattern and value products from the producer, its blocks, the two streamed fp32 copies
+// and the blocks of A P (base pointers shifted so that global numbers address what is held), the filtered operator's diagonals
+std::string transfer_arrays(Amg* m, DevSetup& D, int l, const DevCoarse& dc, GroupBatch& gb) {
+  AmgLevel& L = m->lv[l];
+  PDev& P = L.P;
+  const int n = L.A.n;
+  const int r0 = dc.local ? m->shard.row0 : 0, r1 = dc.local ? m->shard.row1 : n;   // the rows whose entries are held
+  const size_t ne = (size_t)(dc.e_hi - dc.e_lo), nf = (size_t)(dc.f_hi - dc.f_lo);   // entries of P and of A P held
+  L.smoothed = true;
+  P.local_lists = dc.local;
+  if (dc.filtered) {
+    P.dF = D.alloc<double>(9 * (size_t)n);
+    P.dinvF = D.alloc<double>(9 * (size_t)n);
+    P.strong = dc.strong;
+    gb.add(G_F, L.A.rowptr, n, L.A.nslot, &P.f_grp, &P.f_ngrp);
+  }
+  P.np = dc.np;
+  P.rowptr = dc.p_rowptr;
+  P.row = dc.p_row;
+  P.col = dc.p_col;
+  P.blk = D.alloc<double>(9 * (size_t)dc.np);
+  P.val.n = dc.nval;
+  P.val.a = dc.val_src;
+  P.val.tgt = dc.val_tgt;
+  P.t_pos = dc.t_pos;
+  P.t_row = dc.t_row;
+  P.t_col = dc.t_col;
+  streamed_copies(D, P, ne, dc.e_lo);
+  P.nap = dc.nap;
+  double* ab = D.alloc<double>(9 * nf);
+  if (!D.ok) return kOom;
+  P.apblk = ab - 9 * (size_t)dc.f_lo;
+  P.rap_mirror = dc.rap_mirror;
+  gb.add(G_VAL, dc.val_ptr + dc.e_lo, (int)ne, dc.v_lo + dc.nval, &P.val.grp, &P.val.ngrp);
+  gb.add(G_R, dc.p_rowptr + r0, r1 - r0, dc.e_hi, &P.r_grp, &P.r_ngrp);
+  gb.add(G_T, dc.t_ptr, dc.nc, (int)ne, &P.t_grp, &P.t_ngrp);
+  if (l == 0) m->level0_bytes += (long long)(72 * (size_t)dc.np + 72 * ne + 72 * nf + 8 * (size_t)dc.nval + 12 * ne + 8 * nf);
+  return std::string();
+}
+
+// The folded cycle's pattern bookkeeping of P~ (the pattern of A P) -- which entry of P sits at the same place, the column order (a
+// device radix sort of (column, row-major rank) keys), its wave groups -- the two streamed fp32 copies of the view PS, and on levels
+// >= 1 the slots of A and the entries of P~ of every row as one list (k_up_fold)
+std::string fold_bookkeeping(Amg* m, DevSetup& D, int l, const DevCoarse& dc, GroupBatch& gb) {
+  hipStream_t s = D.s;
+  AmgLevel& L = m->lv[l];
+  const PDev& P = L.P;
+  const int n = L.A.n, nc = dc.nc;
+  const int r0 = dc.local ? m->shard.row0 : 0, r1 = dc.local ? m->shard.row1 : n;
+  const size_t nf = (size_t)(dc.f_hi - dc.f_lo);
+  FoldDev& Fd = L.F;
+  Fd.f_lo = dc.f_lo;
+  Fd.f_hi = dc.f_hi;
+  Fd.row = dc.ap_row;
+  Fd.col = dc.ap_col;
+  int* a2p = D.alloc<int>(nf);
+  int* stp = D.alloc<int>(nf);
+  u64* keys = D.talloc<u64>(nf);
+  u64* sorted = D.talloc<u64>(nf);
+  int bits = 33;
+  while (bits < 64 && (1ull << (bits - 32)) <= (u64)nc) ++bits;
+  int* st_row = D.alloc<int>(nf);
+  int* st_col = D.alloc<int>(nf);
+  int* st_ptr = D.alloc<int>((size_t)nc + 1);
+  PDev& PS = L.PS;
+  PS = PDev();
+  streamed_copies(D, PS, nf, dc.f_lo);
+  if (!D.ok) return kOom;
+  Fd.ap2p = a2p - dc.f_lo;
+  Fd.st_pos = stp - dc.f_lo;
+  SGO_LAUNCH(k_fold_match, dim3(grid_for((long long)nf, kBlock)), dim3(kBlock), 0, s, Fd, (const int*)P.rowptr, (const int*)P.col, keys);
+  if (!D.sort(keys, sorted, nf, bits)) return "amg_create: device sort failed";
+  SGO_LAUNCH(k_fold_unpack, dim3(grid_for((long long)nf, kBlock)), dim3(kBlock), 0, s, Fd, (const u64*)sorted, st_row, st_col);
+  SGO_LAUNCH(k_fold_colptr, dim3(grid_for((long long)nc + 1, kBlock)), dim3(kBlock), 0, s, (const u64*)sorted, (int)nf, nc, st_ptr);
+  PS.np = (int)nf;
+  PS.row = dc.ap_row;
+  PS.col = dc.ap_col;
+  PS.t_row = st_row;
+  PS.t_col = st_col;
+  gb.add(G_ST, st_ptr, nc, (int)nf, &PS.t_grp, &PS.t_ngrp);
+  gb.add(G_PSR, dc.ap_rowptr + r0, r1 - r0, dc.f_hi, &PS.r_grp, &PS.r_ngrp);
+  if (l > 0) {
+    const int un = L.A.nslot + (int)nf;
+    int* u_ptr = D.alloc<int>((size_t)n + 1);
+    int* u_row = D.alloc<int>((size_t)un);
+    int* u_idx = D.alloc<int>((size_t)un);
+    int* u_col = D.alloc<int>((size_t)un);
+    if (!D.ok) return kOom;
+    SGO_LAUNCH(k_u_ptr, dim3(grid_for((long long)n + 1, kBlock)), dim3(kBlock), 0, s, n, (const int*)L.A.rowptr, (const int*)dc.ap_rowptr, u_ptr);
+    SGO_LAUNCH(k_u_fill, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, s, n, (const int*)L.A.rowptr, (const int*)L.A.col, (const int*)dc.ap_rowptr,
+               (const int*)dc.ap_col, (const int*)u_ptr, u_row, u_idx, u_col);
+    UpDev& U = L.U;
+    U.n = un;
+    U.row = u_row;
+    U.idx = u_idx;
+    U.col = u_col;
+    gb.add(G_U, u_ptr, n, un, &U.grp, &U.ngrp);
+  }
+  if (l == 0) m->level0_bytes += (long long)(72 * nf + 28 * nf);
+  return std::string();
+}
+
+// One pass of a product list from the patterns -- w == 0: A P, w == 1: P^T A P; the count pass leaves every target's count at ptr, the
+// fill pass (ptr scanned) the products at la / lb / lt
+template <bool FILL>
+void launch_product_list(hipStream_t s, int w, const ApPattern& ap, const AmgLevel& L, const AmgLevel& C, const DevCoarse& dc, int nseg, int* ptr,
+                         int* la, int* lb, int* lt) {
+  const dim3 grid(grid_for(8LL * nseg, kBlock)), block(kBlock);   // eight lanes per target
+  if (w == 0)
+    SGO_LAUNCH((k_ap_list<FILL>), grid, block, 0, s, ap, (const int*)L.A.rowptr, (const int*)L.A.col, (const int*)L.P.rowptr,
+               (const int*)L.P.col, ptr, la, lb, lt);
+  else
+    SGO_LAUNCH((k_rap_list<FILL>), grid, block, 0, s, dc.nslot_c, (const int*)C.A.row, (const int*)C.A.col, (const int*)dc.t_ptr,
+               (const int*)L.P.t_row, (const int*)dc.t_idx, ap, ptr, la, lb, lt);
+}
+
+// The product lists of A P and P^T A P: the producer's ready-made ones, or made here from the patterns
+std::string product_lists(Amg* m, DevSetup& D, int l, const DevCoarse& dc, GroupBatch& gb, const AmgLevel& C) {
+  hipStream_t s = D.s;
+  AmgLevel& L = m->lv[l];
+  PDev& P = L.P;
+  char line[160];
+  std::snprintf(line, sizeof line, "(P %d%s, AP %d blocks; %d + %d products) ", P.np, dc.filtered ? " filtered" : "", P.nap, (int)dc.n_ap_prod,
+                (int)dc.n_rap_prod);
+  m->desc += line;
+  ProdMap* maps[2] = {&P.ap, &P.rap};
+  const GroupId gid[2] = {G_APL, G_RAPL};
+  const long long nprod[2] = {dc.n_ap_prod, dc.n_rap_prod};
+  const int nseg[2] = {dc.f_hi - dc.f_lo, dc.nslot_c};
+  if (dc.lists[0].a) {   // ready-made: grouped with the level's batch
+    for (int w = 0; w < 2; ++w) {
+      maps[w]->n = (int)nprod[w];
+      maps[w]->a = dc.lists[w].a;
+      maps[w]->b = dc.lists[w].b;
+      maps[w]->tgt = dc.lists[w].tgt;
+      gb.add(gid[w], dc.lists[w].ptr, nseg[w], (int)nprod[w], &maps[w]->grp, &maps[w]->ngrp);
     }
-    P.np = dc.np;
-    P.stream_nt = ne >= 200000 ? 1 : 0;   // 2 x 72 B per block streamed per cycle: below ~30 MB it may stay cached
-    P.rowptr = dc.p_rowptr;
-    P.row = dc.p_row;
-    P.col = dc.p_col;
-    P.blk = D.alloc<double>(9 * (size_t)dc.np);
-    P.val.n = dc.nval;
-    P.val.a = dc.val_src;
-    P.val.tgt = dc.val_tgt;
-    P.t_pos = dc.t_pos;
-    P.t_row = dc.t_row;
-    P.t_col = dc.t_col;
-    P.r_n = P.t_n = (int)ne;
-    float* rb = D.alloc<float>(9 * ne + 4);
-    float* tb = D.alloc<float>(9 * ne + 4);
-    P.nap = dc.nap;
-    double* ab = D.alloc<double>(9 * nf);
-    if (!D.ok) return oom;
-    P.r_blk = rb - 4 * (size_t)dc.e_lo;   // row order, addressed by global entry numbers
-    P.r_blk8 = rb + 8 * ne - dc.e_lo;
-    P.t_blk = tb;                         // column order, addressed by the positions held
-    P.t_blk8 = tb + 8 * ne;
-    P.apblk = ab - 9 * (size_t)dc.f_lo;
-    P.rap_mirror = dc.rap_mirror;
-    gb.add(G_VAL, dc.val_ptr + dc.e_lo, (int)ne, dc.v_lo + dc.nval);
-    gb.add(G_R, dc.p_rowptr + r0, r1 - r0, dc.e_hi);
-    gb.add(G_T, dc.t_ptr, nc, (int)ne);
-    if (l == 0) m->level0_bytes += (long long)(72 * (size_t)dc.np + 72 * ne + 72 * nf + 8 * (size_t)dc.nval + 12 * ne + 8 * nf);
-    // (Level 0 is folded only where it is itself launch-bound: P~ has the pattern of A P, twice the entries of P, and on large graphs
-    // streaming it twice per cycle costs what the saved launch and pass bring -- C4: restriction + prolongation 14 + 20 us with P~
-    // against 11 + 9 us with P.  Multi-GPU row-owner runs keep level 0 unfolded as well.)
-    fold_here = m->cfg.fold && nf > 0 && (l > 0 || (m->shard.mode != Shard0::owner && n <= m->cfg.fold0_rows));
-    if (fold_here) {
-      // ---- folded cycle: pattern bookkeeping of P~ (the pattern of A P) -- which entry of P sits at the same place, the column order (a
-      // device radix sort of (column, row-major rank) keys), its wave groups and long columns -- and the two streamed fp32 copies
-      FoldDev& Fd = L.F;
-      Fd.f_lo = dc.f_lo;
-      Fd.f_hi = dc.f_hi;
-      Fd.row = dc.ap_row;
-      Fd.col = dc.ap_col;
-      int* a2p = D.alloc<int>(nf);
-      int* stp = D.alloc<int>(nf);
-      u64* keys = D.talloc<u64>(nf);
-      u64* sorted = D.talloc<u64>(nf);
-      int bits = 33;
-      while (bits < 64 && (1ull << (bits - 32)) <= (u64)nc) ++bits;
-      int* st_row = D.alloc<int>(nf);
-      int* st_col = D.alloc<int>(nf);
-      int* st_ptr = D.alloc<int>((size_t)nc + 1);
-      float* sb = D.alloc<float>(9 * nf + 4);
-      float* sbt = D.alloc<float>(9 * nf + 4);
-      if (!D.ok) return oom;
-      Fd.ap2p = a2p - dc.f_lo;
-      Fd.st_pos = stp - dc.f_lo;
-      SGO_LAUNCH(k_fold_match, dim3(grid_for((long long)nf, kBlock)), dim3(kBlock), 0, s, Fd, (const int*)P.rowptr, (const int*)P.col, keys);
-      if (!D.sort(keys, sorted, nf, bits)) return "amg_create: device sort failed";
-      SGO_LAUNCH(k_fold_unpack, dim3(grid_for((long long)nf, kBlock)), dim3(kBlock), 0, s, Fd, (const u64*)sorted, st_row, st_col);
-      SGO_LAUNCH(k_fold_colptr, dim3(grid_for((long long)nc + 1, kBlock)), dim3(kBlock), 0, s, (const u64*)sorted, (int)nf, nc, st_ptr);
-      gb.add(G_ST, st_ptr, nc, (int)nf);
-      gb.add(G_PSR, dc.ap_rowptr + r0, r1 - r0, dc.f_hi);
-      PDev& PS = L.PS;
-      PS = PDev();
-      PS.np = (int)nf;
-      PS.stream_nt = nf >= 200000 ? 1 : 0;
-      PS.row = dc.ap_row;
-      PS.col = dc.ap_col;
-      PS.r_n = PS.t_n = (int)nf;
-      PS.r_blk = sb - 4 * (size_t)dc.f_lo;
-      PS.r_blk8 = sb + 8 * nf - dc.f_lo;
-      PS.t_blk = sbt;
-      PS.t_blk8 = sbt + 8 * nf;
-      PS.t_row = st_row;
-      PS.t_col = st_col;
-      if (l > 0) {
-        // levels >= 1: the slots of A and the entries of P~ of every row as one list (k_up_fold)
-        const int un = L.A.nslot + (int)nf;
-        int* u_ptr = D.alloc<int>((size_t)n + 1);
-        int* u_row = D.alloc<int>((size_t)un);
-        int* u_idx = D.alloc<int>((size_t)un);
-        int* u_col = D.alloc<int>((size_t)un);
-        if (!D.ok) return oom;
-        SGO_LAUNCH(k_u_ptr, dim3(grid_for((long long)n + 1, kBlock)), dim3(kBlock), 0, s, n, (const int*)L.A.rowptr, (const int*)dc.ap_rowptr, u_ptr);
-        SGO_LAUNCH(k_u_fill, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, s, n, (const int*)L.A.rowptr, (const int*)L.A.col, (const int*)dc.ap_rowptr,
-                   (const int*)dc.ap_col, (const int*)u_ptr, u_row, u_idx, u_col);
-        UpDev& U = L.U;
-        U.n = un;
-        U.row = u_row;
-        U.idx = u_idx;
-        U.col = u_col;
-        gb.add(G_U, u_ptr, n, un);
-      }
-      if (l == 0) m->level0_bytes += (long long)(72 * nf + 28 * nf);
-    }
-    char line[160];
-    std::snprintf(line, sizeof line, "(P %d%s, AP %d blocks; %d + %d products) ", P.np, dc.filtered ? " filtered" : "", P.nap, (int)dc.n_ap_prod,
-                  (int)dc.n_rap_prod);
-    m->desc += line;
-    // ---- product lists of A P and P^T A P
-    ProdMap* maps[2] = {&P.ap, &P.rap};
-    const long long nprod[2] = {dc.n_ap_prod, dc.n_rap_prod};
-    const int nseg[2] = {(int)nf, dc.nslot_c};
-    if (dc.lists[0].a) {   // ready-made: grouped with the level's batch
-      for (int w = 0; w < 2; ++w) {
-        maps[w]->n = (int)nprod[w];
-        maps[w]->a = dc.lists[w].a;
-        maps[w]->b = dc.lists[w].b;
-        maps[w]->tgt = dc.lists[w].tgt;
-        gb.add(w == 0 ? G_APL : G_RAPL, dc.lists[w].ptr, nseg[w], (int)nprod[w]);
-      }
-    } else {
-      // from the patterns: count per target, prefix sum, fill (A P, then P^T A P); both lists' totals behind one synchronisation
-      ApPattern ap;
-      ap.ap_row = dc.ap_row;
-      ap.ap_col = dc.ap_col;
-      ap.ap_rowptr = dc.ap_rowptr;
-      ap.f_lo = dc.f_lo;
-      ap.nap = dc.f_hi;
-      int* ptrs[2] = {nullptr, nullptr};   // [nseg + 1] each, from the first target held
-      for (int w = 0; w < 2; ++w) {
-        ptrs[w] = D.talloc<int>((size_t)nseg[w] + 1);
-        int* sums = D.talloc<int>((size_t)nseg[w] / kScanChunk + 3);
-        if (!D.ok) return oom;
-        int* ptr = w == 0 ? ptrs[w] - dc.f_lo : ptrs[w];   // addressed by global target numbers
-        int *la = nullptr, *lb = nullptr, *lt = nullptr;
-        const dim3 grid(grid_for(8LL * nseg[w], kBlock)), block(kBlock);   // eight lanes per target
-        if (w == 0)
-          SGO_LAUNCH((k_ap_list<false>), grid, block, 0, s, ap, (const int*)L.A.rowptr, (const int*)L.A.col, (const int*)P.rowptr,
-                     (const int*)P.col, ptr, la, lb, lt);
-        else
-          SGO_LAUNCH((k_rap_list<false>), grid, block, 0, s, dc.nslot_c, (const int*)C.A.row, (const int*)C.A.col,
-                     (const int*)dc.t_ptr, (const int*)P.t_row, (const int*)dc.t_idx, ap, ptr, la, lb, lt);
-        dev_scan_exclusive(s, ptrs[w], nseg[w], sums);
-      }
-      int totals[2] = {-1, -1};
-      D.read2(ptrs[0] + nseg[0], ptrs[1] + nseg[1], &totals[0], &totals[1]);
-      if (!D.ok) return "amg_create: product-list kernels failed";
-      for (int w = 0; w < 2; ++w) {
-        const int total = totals[w];
-        // (whole ranges: exactly the patterns' count; a rank's own rows: at most that)
-        if ((!dc.local && total != nprod[w]) || total < 0 || total > nprod[w])
-          return "amg_create: internal error (device product lists: " + std::to_string(total) + " products, the patterns say " +
-                 std::to_string(nprod[w]) + ")";
-        int* la = D.alloc<int>((size_t)std::max(total, 1));
-        int* lb = D.alloc<int>((size_t)std::max(total, 1));
-        int* lt = D.alloc<int>((size_t)std::max(total, 1));
-        if (!D.ok) return oom;
-        int* ptr = w == 0 ? ptrs[w] - dc.f_lo : ptrs[w];
-        const dim3 grid(grid_for(8LL * nseg[w], kBlock)), block(kBlock);
-        if (w == 0)
-          SGO_LAUNCH((k_ap_list<true>), grid, block, 0, s, ap, (const int*)L.A.rowptr, (const int*)L.A.col, (const int*)P.rowptr,
-                     (const int*)P.col, ptr, la, lb, lt);
-        else
-          SGO_LAUNCH((k_rap_list<true>), grid, block, 0, s, dc.nslot_c, (const int*)C.A.row, (const int*)C.A.col,
-                     (const int*)dc.t_ptr, (const int*)P.t_row, (const int*)dc.t_idx, ap, ptr, la, lb, lt);
-        maps[w]->n = total;
-        maps[w]->a = la;
-        maps[w]->b = lb;
-        maps[w]->tgt = lt;
-        gb.add(w == 0 ? G_APL : G_RAPL, ptrs[w], nseg[w], total);
-        if (l == 0) m->level0_bytes += 12LL * total;   // (the lists made here: the level-0 bytes have never counted ready-made ones)
-      }
-    }
-  } else {
+    return std::string();
+  }
+  // from the patterns: count per target, prefix sum, fill (A P, then P^T A P); both lists' totals behind one synchronisation
+  ApPattern ap;
+  ap.ap_row = dc.ap_row;
+  ap.ap_col = dc.ap_col;
+  ap.ap_rowptr = dc.ap_rowptr;
+  ap.f_lo = dc.f_lo;
+  ap.nap = dc.f_hi;
+  int* ptrs[2] = {nullptr, nullptr};   // [nseg + 1] each, from the first target held
+  int* ptr[2] = {nullptr, nullptr};    // ... addressed by global target numbers
+  for (int w = 0; w < 2; ++w) {
+    ptrs[w] = D.talloc<int>((size_t)nseg[w] + 1);
+    int* sums = D.talloc<int>((size_t)nseg[w] / kScanChunk + 3);
+    if (!D.ok) return kOom;
+    ptr[w] = w == 0 ? ptrs[w] - dc.f_lo : ptrs[w];
+    launch_product_list<false>(s, w, ap, L, C, dc, nseg[w], ptr[w], nullptr, nullptr, nullptr);
+    dev_scan_exclusive(s, ptrs[w], nseg[w], sums);
+  }
+  int totals[2] = {-1, -1};
+  D.read2(ptrs[0] + nseg[0], ptrs[1] + nseg[1], &totals[0], &totals[1]);
+  if (!D.ok) return "amg_create: product-list kernels failed";
+  for (int w = 0; w < 2; ++w) {
+    const int total = totals[w];
+    // (whole ranges: exactly the patterns' count; a rank's own rows: at most that)
+    if ((!dc.local && total != nprod[w]) || total < 0 || total > nprod[w])
+      return "amg_create: internal error (device product lists: " + std::to_string(total) + " products, the patterns say " +
+             std::to_string(nprod[w]) + ")";
+    int* la = D.alloc<int>((size_t)std::max(total, 1));
+    int* lb = D.alloc<int>((size_t)std::max(total, 1));
+    int* lt = D.alloc<int>((size_t)std::max(total, 1));
+    if (!D.ok) return kOom;
+    launch_product_list<true>(s, w, ap, L, C, dc, nseg[w], ptr[w], la, lb, lt);
+    maps[w]->n = total;
+    maps[w]->a = la;
+    maps[w]->b = lb;
+    maps[w]->tgt = lt;
+    gb.add(gid[w], ptrs[w], nseg[w], total, &maps[w]->grp, &maps[w]->ngrp);
+    if (l == 0) m->level0_bytes += 12LL * total;   // (the lists made here: the level-0 bytes have never counted ready-made ones)
+  }
+  return std::string();
+}
+
+// The long columns of the two column-ordered copies (P's and, folded, P~'s), behind the wave groups: one synchronisation for both counts
+std::string long_columns(Amg* m, DevSetup& D, int l, bool fold_here) {
+  hipStream_t s = D.s;
+  AmgLevel& L = m->lv[l];
+  PDev &P = L.P, &PS = L.PS;
+  int* d_cnt = D.talloc<int>(2);
+  int* t_ranges = D.alloc<int>(2 * (size_t)std::max(P.t_ngrp, 1));
+  int* st_ranges = nullptr;
+  if (!D.ok) return kOom;
+  hipMemsetAsync(d_cnt, 0, 2 * sizeof(int), s);
+  SGO_LAUNCH(k_long_groups, dim3(grid_for((long long)P.t_ngrp, kBlock)), dim3(kBlock), 0, s, (const int*)P.t_grp, P.t_ngrp, d_cnt, t_ranges);
+  if (fold_here) {
+    st_ranges = D.alloc<int>(2 * (size_t)std::max(PS.t_ngrp, 1));
+    if (!D.ok) return kOom;
+    SGO_LAUNCH(k_long_groups, dim3(grid_for((long long)PS.t_ngrp, kBlock)), dim3(kBlock), 0, s, (const int*)PS.t_grp, PS.t_ngrp, d_cnt + 1, st_ranges);
+  }
+  int nl[2] = {0, 0};
+  D.read2(d_cnt, d_cnt + 1, &nl[0], &nl[1]);
+  if (!D.ok) return "amg_create: set-up kernels failed";
+  P.t_nlong = nl[0];
+  P.t_long = nl[0] ? t_ranges : nullptr;
+  if (fold_here) {
+    constexpr int kLongCap = 4096;   // a level with more long columns than this is not folded
+    PS.t_long = st_ranges;
+    PS.t_nlong = nl[1];
+    L.fold = nl[1] <= kLongCap;
+  }
+  return std::string();
+}
+
+// The one level assembler: a coarsening step's DevCoarse, whichever producer made it, into the transfer data of lv[l] -- P and its
+// streamed fp32 copies, the folded cycle's bookkeeping, the product lists, every wave-group list of the level in one batch (each step
+// adds its lists with the fields they go to), the long columns -- and the structure of the next level lv[l + 1].  Returns the
+// failure's message, empty on success.
+std::string assemble_level(Amg* m, DevSetup& D, int l, const DevCoarse& dc) {
+  GroupBatch gb;
+  AmgLevel C;
+  const bool fold_here = dc.smooth && fold_level(m, l, dc.f_hi - dc.f_lo);
+  std::string e = next_level_shell(m, D, l, dc, gb, C);
+  if (e.empty() && dc.smooth) e = transfer_arrays(m, D, l, dc, gb);
+  if (e.empty() && fold_here) e = fold_bookkeeping(m, D, l, dc, gb);
+  if (e.empty() && dc.smooth) e = product_lists(m, D, l, dc, gb, C);
+  if (!e.empty()) return e;
+  if (!dc.smooth) {   // tentative transfer: the Galerkin map
+    AmgLevel& L = m->lv[l];
     L.gal.n = L.A.nslot;
     L.gal.src = dc.gal_src;
     L.gal.tgt = dc.gal_tgt;
-    gb.add(G_GAL, dc.gal_cptr, dc.nslot_c, L.A.nslot);
+    gb.add(G_GAL, dc.gal_cptr, dc.nslot_c, L.A.nslot, &L.gal.grp, &L.gal.ngrp);
   }
-  // ---- every wave-group list of the level in one batch, then the long columns of the two column-ordered copies
-  if (!gb.run(D)) return oom;
-  L.mem_grp = gb.grp[G_MEM];
-  L.mem_ngrp = gb.ngrp[G_MEM];
-  C.A.grp = gb.grp[G_C];
-  C.A.ngrp = gb.ngrp[G_C];
-  if (dc.smooth) {
-    PDev& P = L.P;
-    P.val.grp = gb.grp[G_VAL];
-    P.val.ngrp = gb.ngrp[G_VAL];
-    P.r_grp = gb.grp[G_R];
-    P.r_ngrp = gb.ngrp[G_R];
-    P.t_grp = gb.grp[G_T];
-    P.t_ngrp = gb.ngrp[G_T];
-    if (dc.filtered) {
-      P.f_grp = gb.grp[G_F];
-      P.f_ngrp = gb.ngrp[G_F];
-    }
-    P.ap.grp = gb.grp[G_APL];
-    P.ap.ngrp = gb.ngrp[G_APL];
-    P.rap.grp = gb.grp[G_RAPL];
-    P.rap.ngrp = gb.ngrp[G_RAPL];
-    int* d_cnt = D.talloc<int>(2);
-    t_ranges = D.alloc<int>(2 * (size_t)std::max(P.t_ngrp, 1));
-    if (!D.ok) return oom;
-    hipMemsetAsync(d_cnt, 0, 2 * sizeof(int), s);
-    SGO_LAUNCH(k_long_groups, dim3(grid_for((long long)P.t_ngrp, kBlock)), dim3(kBlock), 0, s, (const int*)P.t_grp, P.t_ngrp, d_cnt, t_ranges);
-    if (fold_here) {
-      PDev& PS = L.PS;
-      PS.r_grp = gb.grp[G_PSR];
-      PS.r_ngrp = gb.ngrp[G_PSR];
-      PS.t_grp = gb.grp[G_ST];
-      PS.t_ngrp = gb.ngrp[G_ST];
-      if (l > 0) {
-        L.U.grp = gb.grp[G_U];
-        L.U.ngrp = gb.ngrp[G_U];
-      }
-      st_ranges = D.alloc<int>(2 * (size_t)std::max(PS.t_ngrp, 1));
-      if (!D.ok) return oom;
-      SGO_LAUNCH(k_long_groups, dim3(grid_for((long long)PS.t_ngrp, kBlock)), dim3(kBlock), 0, s, (const int*)PS.t_grp, PS.t_ngrp, d_cnt + 1, st_ranges);
-    }
-    int nl[2] = {0, 0};
-    D.read2(d_cnt, d_cnt + 1, &nl[0], &nl[1]);
-    if (!D.ok) return "amg_create: set-up kernels failed";
-    P.t_nlong = nl[0];
-    P.t_long = nl[0] ? t_ranges : nullptr;
-    if (fold_here) {
-      constexpr int kLongCap = 4096;   // a level with more long columns than this is not folded
-      L.PS.t_long = st_ranges;
-      L.PS.t_nlong = nl[1];
-      L.fold = nl[1] <= kLongCap;
-    }
-  } else {
-    L.gal.grp = gb.grp[G_GAL];
-    L.gal.ngrp = gb.ngrp[G_GAL];
-  }
-  m->lv.push_back(C);   // invalidates L
+  if (!gb.run(D)) return kOom;
+  if (dc.smooth) e = long_columns(m, D, l, fold_here);
+  if (!e.empty()) return e;
+  m->lv.push_back(C);   // invalidates lv[l]'s address: no step holds a reference across this
   return std::string();
 }
 
@@ -2945,6 +2972,168 @@ void level_values(Amg* m, hipStream_t s, int l) {
   if (l + 1 < m->cfg.max_levels) SGO_LAUNCH(k_level_dinv, dim3(grid_for(C.A.n, kBlock)), dim3(kBlock), 0, s, C.A);
 }
 
+double ms_since(std::chrono::steady_clock::time_point t) {
+  return 1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t).count();
+}
+
+// The strengths of connection of a level from its current values: the block norms of its nslot slots, on the device (temporary arena;
+// dev_coarsen takes them from there) and in w on the host, behind one synchronisation.  nullptr: failed, the message in err.
+double* level_strengths(DevSetup& D, const BsrDev& A, int nslot, std::vector<double>& w, std::string& err) {
+  w.resize((size_t)nslot);
+  double* d_w = D.talloc<double>((size_t)std::max(nslot, 1));
+  if (!d_w) {
+    err = kOom;
+    return nullptr;
+  }
+  SGO_LAUNCH(k_block_norms, dim3(grid_for(nslot, kBlock)), dim3(kBlock), 0, D.s, A, d_w);
+  hipMemcpyAsync(w.data(), d_w, sizeof(double) * (size_t)nslot, hipMemcpyDeviceToHost, D.s);
+  if (!D.sync()) {
+    err = "amg_create: strength kernel failed";
+    return nullptr;
+  }
+  return d_w;
+}
+
+// The aggregates a rebuild keeps for level l of n nodes (AmgConfig::keep_agg), where they fit; nullptr: none
+const AmgKeptAgg* kept_aggregates(const Amg* m, int l, int n) {
+  const AmgKeptAgg* k = m->cfg.keep_agg;
+  return k && l < (int)k->agg.size() && (int)k->agg[l].size() == n ? k : nullptr;
+}
+
+bool refuse(DevCoarse& dc, const char* msg) {   // a producer's failure
+  dc.err = msg;
+  return false;
+}
+
+// The two producers of level l's DevCoarse.  Both return false on a failure (the message in dc.err), set dc.stop where the level
+// cannot be coarsened further, and leave the host copies of the aggregates (h_agg) and of the next level's visiting order (h_visit_c)
+// and the milliseconds of the host's aggregation (t_host_agg).
+//
+// On the host: host_coarsen's result -- or, for level 0, the one the set-up pipeline's helper thread made ahead (pre0) -- uploaded.
+// `hc` is the HostCoarse it came from (the helper thread's, or hc_own).
+bool coarsen_on_host(Amg* m, DevSetup& D, int l, const HostLevel& H, ChunkArena* scratch, AmgHostL0* pre0, const AmgHalo* halo, bool verbose,
+                     HostCoarse& hc_own, HostCoarse*& hc, std::vector<int>& h_agg, std::vector<int>& h_visit_c, double& t_host_agg, DevCoarse& dc) {
+  const int n = m->lv[l].A.n;
+  hc = &hc_own;
+  if (l == 0 && pre0 && pre0->ready && !pre0->agg_only) {
+    hc = &pre0->hc;   // made ahead on the helper thread, from the same structure and the strengths at the same poses
+  } else {
+    // strength of connection from the current values of this level
+    std::vector<double> w;
+    if (l == 0 && halo) {
+      if (!halo->w0 || (int)halo->w0->size() != H.nslot) return refuse(dc, "amg_create: row-owner mode needs the level-0 strength weights");
+      w = *halo->w0;
+    } else if (!level_strengths(D, m->lv[l].A, H.nslot, w, dc.err)) {
+      return false;
+    }
+    if (const AmgKeptAgg* k = kept_aggregates(m, l, n)) {
+      hc_own.agg = k->agg[l];
+      hc_own.visit_c = k->visit_c[l];
+      hc_own.nc = k->nc[l];
+      hc_own.reuse_agg = true;
+    }
+    host_coarsen(H, w, m->cfg, l, scratch, hc_own);
+  }
+  if (!hc->err.empty()) return refuse(dc, hc->err.c_str());
+  if (hc->stop) {
+    dc.stop = true;
+    return true;
+  }
+  if (verbose)
+    std::fprintf(stderr, "[sgo] amg level %d: host aggregation + coarse structure %.1f ms (aggregate %.1f, sort %.1f; n=%d -> %d)%s\n", l,
+                 hc->t_all, hc->t_agg, hc->t_sort, n, hc->nc, hc == &hc_own ? "" : " [made ahead on the helper thread]");
+  h_agg = hc->agg;
+  h_visit_c = hc->visit_c;
+  t_host_agg = hc->t_agg;
+  return upload_coarse(D, *hc, n, l == 0 && halo ? halo->dev : nullptr, dc);
+}
+
+// On the device: dev_coarsen from given aggregates -- kept ones, the helper thread's (level 0, pre0), or the host's (greedy along the
+// trajectory, sgo_amg_host.cpp: from this level's strengths and its pattern, which for a coarse level is copied back into Hown, a few
+// integers per slot) -- or, given none (AmgPatterns::device_aggregation), from the device's own.
+bool coarsen_on_device(Amg* m, DevSetup& D, int l, const HostLevel& H0, HostLevel& Hown, AmgPatterns patterns, ChunkArena* scratch,
+                       AmgHostL0* pre0, std::vector<double>& h_w, std::vector<int>& h_agg, std::vector<int>& h_visit_c, double& t_host_agg,
+                       DevCoarse& dc) {
+  hipStream_t s = D.s;
+  const BsrDev& A = m->lv[l].A;
+  const int n = A.n;
+  int given_nc = 0;
+  double given_theta = (l == 0 ? m->cfg.theta : m->cfg.theta_coarse) * m->cfg.theta_scale;
+  double* d_w = nullptr;
+  if (const AmgKeptAgg* k = kept_aggregates(m, l, n)) {
+    h_agg = k->agg[l];
+    h_visit_c = k->visit_c[l];
+    given_nc = k->nc[l];
+  } else if (l == 0 && pre0 && pre0->ready && pre0->agg_only) {
+    // level 0's aggregation was made ahead on the helper thread (sgo_set_graph_se2's pipeline), from the same structure and the
+    // strengths at the same poses
+    h_agg = pre0->hc.agg;
+    h_visit_c = pre0->hc.visit_c;
+    given_nc = pre0->hc.nc;
+    given_theta = pre0->theta_used;
+    dc.stop = given_nc == 0;
+  } else if (patterns == AmgPatterns::device) {
+    if (l > 0) {
+      Hown.n = n;
+      Hown.nslot = A.nslot;
+      Hown.rowptr.resize((size_t)n + 1);
+      Hown.col.resize((size_t)A.nslot);
+      Hown.row.clear();
+      hipMemcpyAsync(Hown.rowptr.data(), A.rowptr, sizeof(int) * ((size_t)n + 1), hipMemcpyDeviceToHost, s);
+      hipMemcpyAsync(Hown.col.data(), A.col, sizeof(int) * (size_t)A.nslot, hipMemcpyDeviceToHost, s);
+    }
+    const HostLevel& H = l == 0 ? H0 : Hown;
+    if (!(d_w = level_strengths(D, A, H.nslot, h_w, dc.err))) return false;
+    const auto tA = std::chrono::steady_clock::now();
+    given_nc = host_aggregate(H, h_w, m->cfg, l, scratch, h_agg, h_visit_c, &given_theta);
+    t_host_agg = ms_since(tA);
+    dc.stop = given_nc == 0;
+  }
+  if (dc.stop) return true;
+  int* given = nullptr;   // (none: dev_coarsen aggregates)
+  if (!h_agg.empty() && !(given = dev_upload(D.tmp, h_agg, s))) return refuse(dc, kOom);
+  if (!dev_coarsen(D, A, m->cfg, l, given, given_nc, given_theta, d_w, dc)) return dc.err.empty() ? refuse(dc, "amg_create: device set-up failed") : false;
+  if (!dc.stop && h_agg.empty()) {   // (the device's aggregates)
+    h_agg.resize((size_t)n);
+    if (hipMemcpyAsync(h_agg.data(), dc.agg, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, s) != hipSuccess || !D.sync())
+      return refuse(dc, "amg_create: device set-up failed");
+  }
+  return true;
+}
+
+// Behind the last level: the dense inverse's buffers for it, the sweeps per coarse level, the description's tail.  Returns the
+// failure's message, empty on success.
+std::string finish_coarsest(Amg* m, hipStream_t s) {
+  if (hipStreamSynchronize(s) != hipSuccess) return "amg_create: set-up kernels failed";
+  const int last = (int)m->lv.size() - 1;
+  // last == 0: the whole graph is at most coarsest_nodes large (or cannot be coarsened) and is
+  // "solved" by the dense inverse directly -- the preconditioner is then exact (1-2 PCG iterations)
+  if (last == 0 && m->lv[0].A.n > 1024) return "amg_create: graph not coarsenable; use the block-Jacobi solver";
+  m->N = 3 * m->lv[last].A.n;
+  m->Np = (m->N + kGjB - 1) / kGjB * kGjB;
+  if (m->N > 3072) return "amg_create: coarsest level too large (" + std::to_string(m->N) + " unknowns)";
+  m->inv0 = dev_alloc<double>(m->pool, (size_t)m->Np * m->Np);
+  m->inv1 = dev_alloc<double>(m->pool, (size_t)m->Np * m->Np);
+  m->gjP[0] = dev_alloc<double>(m->pool, kGjB * kGjB);
+  m->gjP[1] = dev_alloc<double>(m->pool, kGjB * kGjB);
+  m->inv = ((m->Np / kGjB) & 1) ? m->inv1 : m->inv0;
+  m->d_fail = dev_alloc<int>(m->pool, 1);
+  if (!m->inv0 || !m->inv1 || !m->d_fail || !m->gjP[0] || !m->gjP[1]) return kOom;
+  hipMemsetAsync(m->d_fail, 0, sizeof(int), s);
+  // Two sweeps per coarse level (amg_effective_config) pay while the coarse levels are small next to level 0.  A hierarchy
+  // whose level 1 holds more than a quarter of level 0's blocks -- filtered transfers along the trajectory: aggregates of three
+  // poses whose rows keep all their closures, C4 from a dead-reckoned start: 1.15 M of 2.1 M -- pays four bandwidth-bound
+  // passes per level for them: one sweep there (measured: 23.3 -> 20.9 ms per Gauss-Newton iteration at that start; C4's usual
+  // hierarchy, level 1 at 6 %, keeps two: 4.06 against 4.45 ms with one).
+  if (last >= 1 && !m->cfg.nu_from_env && 4LL * m->lv[1].A.nslot > (long long)m->lv[0].A.nslot) m->cfg.nu_coarse = 1;
+  m->cfg.keep_agg = nullptr;   // (the caller's object: only read during this set-up)
+  char line[160];
+  std::snprintf(line, sizeof line, "coarsest dense N=%d; theta=%.3g omega=%.2f nu=%d", m->N,
+                m->cfg.theta * m->cfg.theta_scale, m->cfg.omega, m->cfg.nu_coarse);
+  m->desc += line;
+  return std::string();
+}
+
 }  // namespace
 
 Amg* amg_create(hipStream_t s, const BsrDev& A0, const Sym0Dev& S0, const Tile0Dev& T0, const HostLevel& H0, const double* d_poses,
@@ -2965,11 +3154,8 @@ Amg* amg_create(hipStream_t s, const BsrDev& A0, const Sym0Dev& S0, const Tile0D
   m->cfg = amg_effective_config(cfg_in, A0.n, A0.nslot);
   const bool on_host = patterns == AmgPatterns::host;
   if (!on_host) m->cfg.lists_on_device = true;   // (the device producer makes patterns only; folding stays as amg_effective_config decided)
-  // With the smoothed prolongator a V-cycle needs ~1.4x the PCG iterations of the K-cycle (C4: 39 vs
-  // 27) at less than half the launches per iteration: V is the default there, K for the tentative one.
-  if (m->cfg.smooth) m->kdepth = 0;
-  if (const char* e = std::getenv("SGO_AMG_KDEPTH")) m->kdepth = std::atoi(e);
-  if (const char* e = std::getenv("SGO_AMG_FCG2_DEPTH")) m->fcg2_depth = std::atoi(e);
+  m->kdepth = m->cfg.kdepth;
+  m->fcg2_depth = m->cfg.fcg2_depth;
   m->prof = prof;
   m->d_poses = d_poses;
   m->d_free_id = d_free_id;
@@ -2980,11 +3166,6 @@ Amg* amg_create(hipStream_t s, const BsrDev& A0, const Sym0Dev& S0, const Tile0D
   };
   if (halo && !on_host) return fail("amg_create: the row-owner mode needs the host patterns");
   const bool verbose = std::getenv("SGO_VERBOSE") != nullptr;
-  auto ms_since = [](std::chrono::steady_clock::time_point t) {
-    return 1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t).count();
-  };
-  // level 0 made ahead on the set-up pipeline's helper thread: host_coarsen's whole result, or the aggregation alone
-  const bool pre0_full = pre0 && pre0->ready && !pre0->agg_only, pre0_agg = pre0 && pre0->ready && pre0->agg_only;
   AmgLevel L0;
   L0.A = A0;
   m->lv.push_back(L0);
@@ -2995,11 +3176,9 @@ Amg* amg_create(hipStream_t s, const BsrDev& A0, const Sym0Dev& S0, const Tile0D
     const int n = m->lv[l].A.n;
     std::snprintf(line, sizeof line, "L%d n=%d slots=%d; ", l, n, m->lv[l].A.nslot);
     m->desc += line;
-    if (!alloc_work(m, s, l)) return fail("amg_create: out of device memory");
+    if (!alloc_work(m, s, l)) return fail(kOom);
     if (n <= m->cfg.coarsest_nodes || l + 1 >= m->cfg.max_levels) break;
 
-    AmgLevel& L = m->lv[l];
-    const HostLevel& H = l == 0 ? H0 : Hown;
     const auto tL = std::chrono::steady_clock::now();
     tmp_arena->rewind();   // (the previous level's temporaries: every later user is queued behind their last kernel)
     DevSetup D{s, m->pool, tmp_arena};
@@ -3008,98 +3187,10 @@ Amg* amg_create(hipStream_t s, const BsrDev& A0, const Sym0Dev& S0, const Tile0D
     HostCoarse* hc = nullptr;            // the host producer's result
     std::vector<int> h_agg, h_visit_c;   // host copies of the aggregates (AmgConfig::keep_agg) and of the next level's visiting order
     double t_host_agg = 0.0;
-    const bool kept = m->cfg.keep_agg && l < (int)m->cfg.keep_agg->agg.size() && (int)m->cfg.keep_agg->agg[l].size() == n;
-    if (on_host) {
-      if (l == 0 && pre0_full) {
-        hc = &pre0->hc;   // made ahead on the helper thread, from the same structure and the strengths at the same poses
-      } else {
-        // strength of connection from the current values of this level
-        std::vector<double> w;
-        if (l == 0 && halo) {
-          if (!halo->w0 || (int)halo->w0->size() != H.nslot) return fail("amg_create: row-owner mode needs the level-0 strength weights");
-          w = *halo->w0;
-        } else {
-          w.resize(H.nslot);
-          double* d_w = D.talloc<double>((size_t)std::max(H.nslot, 1));
-          if (!d_w) return fail("amg_create: out of device memory");
-          SGO_LAUNCH(k_block_norms, dim3(grid_for(H.nslot, kBlock)), dim3(kBlock), 0, s, L.A, d_w);
-          hipMemcpyAsync(w.data(), d_w, sizeof(double) * H.nslot, hipMemcpyDeviceToHost, s);
-          if (!D.sync()) return fail("amg_create: strength kernel failed");
-        }
-        if (kept) {
-          hc_own.agg = m->cfg.keep_agg->agg[l];
-          hc_own.visit_c = m->cfg.keep_agg->visit_c[l];
-          hc_own.nc = m->cfg.keep_agg->nc[l];
-          hc_own.reuse_agg = true;
-        }
-        host_coarsen(H, w, m->cfg, l, scratch, hc_own);
-        hc = &hc_own;
-      }
-      if (!hc->err.empty()) return fail(hc->err);
-      if (hc->stop) break;
-      t_host_agg = hc->t_agg;
-      if (verbose)
-        std::fprintf(stderr, "[sgo] amg level %d: host aggregation + coarse structure %.1f ms (aggregate %.1f, sort %.1f; n=%d -> %d)%s\n", l,
-                     hc->t_all, hc->t_agg, hc->t_sort, n, hc->nc, hc == &hc_own ? "" : " [made ahead on the helper thread]");
-      if (!upload_coarse(D, *hc, n, l == 0 && halo ? halo->dev : nullptr, dc)) return fail(dc.err);
-      h_agg = hc->agg;
-      h_visit_c = hc->visit_c;
-    } else {
-      // ---- where the device producer's aggregates come from: kept, the helper thread's, the host's (greedy along the trajectory,
-      // sgo_amg_host.cpp) or the device's own (dev_coarsen aggregates when it is given none)
-      int* given = nullptr;
-      int given_nc = 0;
-      double given_theta = (l == 0 ? m->cfg.theta : m->cfg.theta_coarse) * m->cfg.theta_scale;
-      double* d_w = nullptr;
-      if (kept) {
-        given = dev_upload(tmp_arena, m->cfg.keep_agg->agg[l], s);
-        given_nc = m->cfg.keep_agg->nc[l];
-        if (!given) return fail("amg_create: out of device memory");
-        h_agg = m->cfg.keep_agg->agg[l];
-        h_visit_c = m->cfg.keep_agg->visit_c[l];
-      } else if (l == 0 && pre0_agg) {
-        // level 0's aggregation was made ahead on the helper thread (sgo_set_graph_se2's pipeline), from the same structure and the
-        // strengths at the same poses
-        if (pre0->hc.nc == 0) break;
-        h_agg = pre0->hc.agg;
-        h_visit_c = pre0->hc.visit_c;
-        given_nc = pre0->hc.nc;
-        given_theta = pre0->theta_used;
-        given = dev_upload(tmp_arena, h_agg, s);
-        if (!given) return fail("amg_create: out of device memory");
-      } else if (patterns == AmgPatterns::device) {
-        // the host's aggregation from this level's strengths: the level's pattern (level 0: the context's host copy; coarser levels:
-        // copied back, a few integers per slot) and the slots' block norms
-        if (l > 0) {
-          Hown.n = n;
-          Hown.nslot = L.A.nslot;
-          Hown.rowptr.resize((size_t)n + 1);
-          Hown.col.resize((size_t)L.A.nslot);
-          Hown.row.clear();
-          hipMemcpyAsync(Hown.rowptr.data(), L.A.rowptr, sizeof(int) * ((size_t)n + 1), hipMemcpyDeviceToHost, s);
-          hipMemcpyAsync(Hown.col.data(), L.A.col, sizeof(int) * (size_t)L.A.nslot, hipMemcpyDeviceToHost, s);
-        }
-        h_w.resize((size_t)H.nslot);
-        d_w = dev_alloc<double>(tmp_arena, (size_t)std::max(H.nslot, 1));
-        if (!d_w) return fail("amg_create: out of device memory");
-        SGO_LAUNCH(k_block_norms, dim3(grid_for(H.nslot, kBlock)), dim3(kBlock), 0, s, L.A, d_w);
-        hipMemcpyAsync(h_w.data(), d_w, sizeof(double) * (size_t)H.nslot, hipMemcpyDeviceToHost, s);
-        if (!D.sync()) return fail("amg_create: strength kernel failed");
-        const auto tA = std::chrono::steady_clock::now();
-        given_nc = host_aggregate(H, h_w, m->cfg, l, scratch, h_agg, h_visit_c, &given_theta);
-        t_host_agg = ms_since(tA);
-        if (given_nc == 0) break;   // cannot coarsen further
-        given = dev_upload(tmp_arena, h_agg, s);
-        if (!given) return fail("amg_create: out of device memory");
-      }
-      if (!dev_coarsen(D, L.A, m->cfg, l, given, given_nc, given_theta, d_w, dc)) return fail(dc.err.empty() ? "amg_create: device set-up failed" : dc.err);
-      if (dc.stop) break;
-      if (h_agg.empty()) {   // (the device's aggregates)
-        h_agg.resize((size_t)n);
-        if (hipMemcpyAsync(h_agg.data(), dc.agg, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, s) != hipSuccess || !D.sync())
-          return fail("amg_create: device set-up failed");
-      }
-    }
+    const bool made = on_host ? coarsen_on_host(m, D, l, l == 0 ? H0 : Hown, scratch, pre0, halo, verbose, hc_own, hc, h_agg, h_visit_c, t_host_agg, dc)
+                              : coarsen_on_device(m, D, l, H0, Hown, patterns, scratch, pre0, h_w, h_agg, h_visit_c, t_host_agg, dc);
+    if (!made) return fail(dc.err);
+    if (dc.stop) break;   // cannot coarsen further
     const double t_coarsen = ms_since(tL);
     m->kept.agg.push_back(std::move(h_agg));
     m->kept.visit_c.push_back(h_visit_c);
@@ -3116,32 +3207,8 @@ Amg* amg_create(hipStream_t s, const BsrDev& A0, const Sym0Dev& S0, const Tile0D
     if (on_host) Hown = std::move(hc->Hc);
     Hown.visit = std::move(h_visit_c);   // (the order in which the next level's aggregation visits its nodes: along the trajectory)
   }
-  if (hipStreamSynchronize(s) != hipSuccess) return fail("amg_create: set-up kernels failed");
-  const int last = (int)m->lv.size() - 1;
-  // last == 0: the whole graph is at most coarsest_nodes large (or cannot be coarsened) and is
-  // "solved" by the dense inverse directly -- the preconditioner is then exact (1-2 PCG iterations)
-  if (last == 0 && m->lv[0].A.n > 1024) return fail("amg_create: graph not coarsenable; use the block-Jacobi solver");
-  m->N = 3 * m->lv[last].A.n;
-  m->Np = (m->N + kGjB - 1) / kGjB * kGjB;
-  if (m->N > 3072) return fail("amg_create: coarsest level too large (" + std::to_string(m->N) + " unknowns)");
-  m->inv0 = dev_alloc<double>(m->pool, (size_t)m->Np * m->Np);
-  m->inv1 = dev_alloc<double>(m->pool, (size_t)m->Np * m->Np);
-  m->gjP[0] = dev_alloc<double>(m->pool, kGjB * kGjB);
-  m->gjP[1] = dev_alloc<double>(m->pool, kGjB * kGjB);
-  m->inv = ((m->Np / kGjB) & 1) ? m->inv1 : m->inv0;
-  m->d_fail = dev_alloc<int>(m->pool, 1);
-  if (!m->inv0 || !m->inv1 || !m->d_fail || !m->gjP[0] || !m->gjP[1]) return fail("amg_create: out of device memory");
-  hipMemsetAsync(m->d_fail, 0, sizeof(int), s);
-  // Two sweeps per coarse level (amg_effective_config) pay while the coarse levels are small next to level 0.  A hierarchy
-  // whose level 1 holds more than a quarter of level 0's blocks -- filtered transfers along the trajectory: aggregates of three
-  // poses whose rows keep all their closures, C4 from a dead-reckoned start: 1.15 M of 2.1 M -- pays four bandwidth-bound
-  // passes per level for them: one sweep there (measured: 23.3 -> 20.9 ms per Gauss-Newton iteration at that start; C4's usual
-  // hierarchy, level 1 at 6 %, keeps two: 4.06 against 4.45 ms with one).
-  if (last >= 1 && !std::getenv("SGO_AMG_NU") && 4LL * m->lv[1].A.nslot > (long long)m->lv[0].A.nslot) m->cfg.nu_coarse = 1;
-  m->cfg.keep_agg = nullptr;   // (the caller's object: only read during this set-up)
-  std::snprintf(line, sizeof line, "coarsest dense N=%d; theta=%.3g omega=%.2f nu=%d", m->N,
-                m->cfg.theta * m->cfg.theta_scale, m->cfg.omega, m->cfg.nu_coarse);
-  m->desc += line;
+  const std::string e = finish_coarsest(m, s);
+  if (!e.empty()) return fail(e);
   return m;
 }
 

@@ -676,8 +676,10 @@ std::string multi_gpu_description(const sgo_ctx* c) {
   return "";
 }
 
-// (Re)build the multigrid hierarchy from the CURRENT level-0 values (requires do_linearize).
-int build_amg(sgo_ctx* c, bool keep_old, bool keep_agg) {
+// ---- build_amg's steps, in its order
+// The hierarchy in use goes away, or -- a trial rebuild (keep_old) -- stays intact in its arena while the new one goes into the
+// other.  *reuse_agg: the new set-up keeps its aggregates (host copies in c->kept_agg).
+static int retire_hierarchy(sgo_ctx* c, bool keep_old, bool keep_agg, bool* reuse_agg) {
   // speculative replays of the captured PCG iteration (and the launches queued behind them) may still be
   // in flight: drain the stream before the exec and the old hierarchy's buffers go away
   HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -698,21 +700,44 @@ int build_amg(sgo_ctx* c, bool keep_old, bool keep_agg) {
     std::swap(c->amg_arena.chunks, c->amg_arena_prev.chunks);
     std::swap(c->amg_arena.next_chunk, c->amg_arena_prev.next_chunk);
   }
-  const bool reuse_agg = keep_agg && !keep_old && c->amg && !c->owner;
-  if (reuse_agg) amg_kept_aggregates(c->amg, &c->kept_agg);
+  *reuse_agg = keep_agg && !keep_old && c->amg && !c->owner;
+  if (*reuse_agg) amg_kept_aggregates(c->amg, &c->kept_agg);
   if (c->amg) {
     amg_destroy(c->amg);
     c->amg = nullptr;
   }
   c->amg_arena.rewind();
-  if (keep_old && c->amg_prev && c->knobs.fail_trial_build) {   // test hook (SGO_TEST_FAIL_TRIAL_BUILD, read once per sgo_optimize_gn): the trial's set-up "fails"
-    c->solver_desc = "pcg_block_jacobi (AMG unavailable: test hook)";
-    return SGO_OK;
+  return SGO_OK;
+}
+
+// Row-owner mode: a rank holds current blocks for its own rows only; the strength weights w0 of ALL level-0 slots come from the
+// (replicated) edge list at the current poses, as in the set-up pipeline -- made here unless the helper thread has a result -- and
+// the partition for amg_create
+static int owner_inputs(sgo_ctx* c, std::vector<double>& w0, AmgHalo& ah) {
+  if (!(c->l0_pre && amg_host_l0_ready(c->l0_pre))) {
+    double* d_w = (double*)c->amg_arena.take(sizeof(double) * (size_t)std::max(c->H0.nslot, 1));
+    if (!d_w) {
+      c->err = "out of device memory";
+      return SGO_ENOMEM;
+    }
+    launch_early_strength(c->stream, c->el, c->d_poses, c->n, c->d_rowptr, c->d_eidx, c->es.flags, c->d_hrowptr, d_w);
+    w0.resize((size_t)c->H0.nslot);
+    HIP_TRY(c, hipMemcpyAsync(w0.data(), d_w, sizeof(double) * w0.size(), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
   }
-  AmgConfig cfg;
-  cfg.theta_scale = c->hier.theta_scale;
-  cfg.filtered_smoothing = !c->hier.no_filter;
-  cfg.keep_agg = reuse_agg ? &c->kept_agg : nullptr;
+  ah.dev = &c->halo;
+  ah.G = c->halo_host.G;
+  ah.bmax = c->halo_host.bmax;
+  ah.bnd_host = c->halo_host.bnd.data();
+  ah.user = c;
+  ah.reserve = [](void* u, size_t doubles) { return halo_reserve((sgo_ctx*)u, doubles) == SGO_OK; };
+  ah.w0 = &w0;
+  return SGO_OK;
+}
+
+// c->amg from the device set-up where it applies, otherwise -- or when that cannot be made -- from the host set-up; nullptr: neither
+// (the reason in aerr)
+static void create_amg(sgo_ctx* c, const AmgConfig& cfg, const AmgHalo* ah, std::string& aerr) {
   AmgProf prof;
   prof.user = c;
   prof.begin = [](void* u, int kid, double bytes) {
@@ -724,41 +749,17 @@ int build_amg(sgo_ctx* c, bool keep_old, bool keep_agg) {
     delete (Scope*)cc->amg_scope;
     cc->amg_scope = nullptr;
   };
-  std::string aerr;
-  l0_join(c, true);   // the helper thread's analysis of level 0, when set_graph started one (first build only)
-  AmgHalo ah;
-  std::vector<double> w0;
-  if (c->owner) {
-    // row-owner mode: a rank holds current blocks for its own rows only; the strength weights of ALL level-0 slots come
-    // from the (replicated) edge list at the current poses, as in the set-up pipeline
-    if (!(c->l0_pre && amg_host_l0_ready(c->l0_pre))) {
-      double* d_w = (double*)c->amg_arena.take(sizeof(double) * (size_t)std::max(c->H0.nslot, 1));
-      if (!d_w) {
-        c->err = "out of device memory";
-        return SGO_ENOMEM;
-      }
-      launch_early_strength(c->stream, c->el, c->d_poses, c->n, c->d_rowptr, c->d_eidx, c->es.flags, c->d_hrowptr, d_w);
-      w0.resize((size_t)c->H0.nslot);
-      HIP_TRY(c, hipMemcpyAsync(w0.data(), d_w, sizeof(double) * w0.size(), hipMemcpyDeviceToHost, c->stream));
-      HIP_TRY(c, hipStreamSynchronize(c->stream));
-    }
-    ah.dev = &c->halo;
-    ah.G = c->halo_host.G;
-    ah.bmax = c->halo_host.bmax;
-    ah.bnd_host = c->halo_host.bnd.data();
-    ah.user = c;
-    ah.reserve = [](void* u, size_t doubles) { return halo_reserve((sgo_ctx*)u, doubles) == SGO_OK; };
-    ah.w0 = &w0;
-  }
-  // The set-up ON THE DEVICE (sgo_amg_dev.inc): the rebuilds inside sgo_optimize_gn on one GPU (SGO_AMG_SETUP=host: the host
-  // set-up for them too; =device: every set-up, sgo_set_graph_se2's included, whose level 0 the helper thread has not made ahead).
+  auto create = [&](AmgPatterns patterns, const AmgHalo* halo) {
+    return amg_create(c->stream, c->A, c->S0, c->T0, c->H0, c->d_poses, c->d_free_id, cfg, prof, &aerr, &c->amg_scratch, &c->amg_arena,
+                      &c->amg_tmp_arena, patterns, c->l0_pre, halo);
+  };
   const double t_create0 = wall_s();
   const bool pre0_ready = c->l0_pre && amg_host_l0_ready(c->l0_pre);
   const bool pre0_agg = pre0_ready && amg_host_l0_agg_only(c->l0_pre);
+  // The set-up ON THE DEVICE (sgo_amg_dev.inc): the rebuilds inside sgo_optimize_gn on one GPU (SGO_AMG_SETUP=host: the host
+  // set-up for them too; =device: every set-up, sgo_set_graph_se2's included, whose level 0 the helper thread has not made ahead).
   const bool dev_setup = !c->owner && !multi_rank(c) && (pre0_agg || (!pre0_ready && (c->knobs.setup_mode == 2 || (c->knobs.setup_mode == 1 && c->call.in_optimize))));
-  if (dev_setup)
-    c->amg = amg_create(c->stream, c->A, c->S0, c->T0, c->H0, c->d_poses, c->d_free_id, cfg, prof, &aerr, &c->amg_scratch, &c->amg_arena,
-                        &c->amg_tmp_arena, c->knobs.dev_aggregation ? AmgPatterns::device_aggregation : AmgPatterns::device, c->l0_pre);
+  if (dev_setup) c->amg = create(c->knobs.dev_aggregation ? AmgPatterns::device_aggregation : AmgPatterns::device, nullptr);
   if (dev_setup && c->amg && c->knobs.fail_device_setup) {   // test hook (SGO_TEST_FAIL_DEVICE_SETUP): the device set-up "fails"
     amg_destroy(c->amg);
     c->amg = nullptr;
@@ -771,19 +772,15 @@ int build_amg(sgo_ctx* c, bool keep_old, bool keep_agg) {
     c->amg_arena.rewind();
     aerr.clear();
   }
-  if (!c->amg)
-    c->amg = amg_create(c->stream, c->A, c->S0, c->T0, c->H0, c->d_poses, c->d_free_id, cfg, prof, &aerr, &c->amg_scratch, &c->amg_arena,
-                        &c->amg_tmp_arena, AmgPatterns::host, c->l0_pre, c->owner ? &ah : nullptr);
+  if (!c->amg) c->amg = create(AmgPatterns::host, ah);
   l0_discard(c);
   if (c->opts.verbose)
     std::fprintf(stderr, "[sgo] multigrid set-up (%s): %.2f ms\n", dev_setup ? (c->knobs.dev_aggregation ? "aggregation and patterns on the device" : "host aggregation, patterns on the device") : "host", 1e3 * (wall_s() - t_create0));
-  if (c->amg && amg_comm_failed(c->amg)) {
-    c->err = "collective failed during the multigrid set-up";
-    return SGO_ECOMM;
-  }
+}
+
+// What solver_description says of the set-up's outcome (aerr: why there is no hierarchy)
+static void describe_amg(sgo_ctx* c, const std::string& aerr) {
   if (c->amg) {
-    if (!c->owner && multi_rank(c))
-      amg_set_shard(c->amg, &c->comm, c->shard_u0, c->shard_u1, c->shard_row0, c->shard_row1, c->gather_slices ? &c->halo : nullptr);
     // (a graph on the single-launch direct or the multifrontal path gets here through a single-step entry point -- sgo_linearize,
     // sgo_solve --: sgo_optimize_gn keeps running the factorisation, and the description keeps saying so)
     std::string amg_desc;
@@ -801,6 +798,34 @@ int build_amg(sgo_ctx* c, bool keep_old, bool keep_agg) {
     else c->solver_desc = "pcg_block_jacobi (AMG unavailable: " + aerr + ")";
     if (c->opts.verbose) std::fprintf(stderr, "[sgo] %s\n", c->solver_desc.c_str());
   }
+}
+
+// (Re)build the multigrid hierarchy from the CURRENT level-0 values (requires do_linearize).
+int build_amg(sgo_ctx* c, bool keep_old, bool keep_agg) {
+  bool reuse_agg = false;
+  int rc = retire_hierarchy(c, keep_old, keep_agg, &reuse_agg);
+  if (rc != SGO_OK) return rc;
+  if (keep_old && c->amg_prev && c->knobs.fail_trial_build) {   // test hook (SGO_TEST_FAIL_TRIAL_BUILD, read once per sgo_optimize_gn): the trial's set-up "fails"
+    c->solver_desc = "pcg_block_jacobi (AMG unavailable: test hook)";
+    return SGO_OK;
+  }
+  AmgConfig cfg;
+  cfg.theta_scale = c->hier.theta_scale;
+  cfg.filtered_smoothing = !c->hier.no_filter;
+  cfg.keep_agg = reuse_agg ? &c->kept_agg : nullptr;
+  l0_join(c, true);   // the helper thread's analysis of level 0, when set_graph started one (first build only)
+  AmgHalo ah;
+  std::vector<double> w0;
+  if (c->owner && (rc = owner_inputs(c, w0, ah)) != SGO_OK) return rc;
+  std::string aerr;
+  create_amg(c, cfg, c->owner ? &ah : nullptr, aerr);
+  if (c->amg && amg_comm_failed(c->amg)) {
+    c->err = "collective failed during the multigrid set-up";
+    return SGO_ECOMM;
+  }
+  if (c->amg && !c->owner && multi_rank(c))
+    amg_set_shard(c->amg, &c->comm, c->shard_u0, c->shard_u1, c->shard_row0, c->shard_row1, c->gather_slices ? &c->halo : nullptr);
+  describe_amg(c, aerr);
   if (c->d_dref_agg && c->S0.dblk && !c->owner) {   // the blocks this aggregation was made from (optimize_gn's movement rule)
     HIP_TRY(c, hipMemcpyAsync(c->d_dref_agg, c->S0.dblk, sizeof(double) * 6 * (size_t)c->n, hipMemcpyDeviceToDevice, c->stream));
     c->hier.agg_ref_valid = true;
