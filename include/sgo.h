@@ -413,6 +413,44 @@ double sgo_debug_spmv0_us(sgo_ctx* ctx, int mode, int variant, int reps);
 #define SGO_AMG_ROW_ORDER 35
 #define SGO_AMG_INFO_COUNT 24
 int64_t sgo_debug_amg_array(sgo_ctx* ctx, int32_t level, int32_t what, void* out, int64_t cap_bytes);
+/* Test hooks for the incremental overlay (sgo_update_graph_se2; tests/overlay_reference.py names every array's type and shape).
+ * All three return SGO_EINVAL when no overlay is resident and in a multi-GPU context; the single-step entry points above keep
+ * refusing an overlay.
+ * sgo_debug_overlay_array: a read-only copy of one array of the resident overlay as of the last linearisation -- device memory
+ *   as stored, nothing recomputed, sizes from the device's own header.  Same convention as sgo_debug_amg_array: returns the
+ *   array's size in bytes (0: it has no entries) and copies it when cap_bytes holds it.  `what` is one of SGO_OV_*: HDR = int32
+ *   { chain rows k, touched rows nt, right-hand-side columns ncol = 3 (nt + nx) + 1, nnz, hub rows nx }; RP [k + nt + nx + 1],
+ *   ENT_EDGE / ENT_OTHER (int32) and ENT_SIDE (uint8) per entry; VTX [k + nx], TROW [nt] (internal rows), NZ [nnz] (int32);
+ *   doubles: DN [k][6], UN [k][9], H0 and Y [3 k][ncol], SINV [k][6], M0 and S [3 nk][3 nk] (nk = nt + nx), BT and GK [3 nk],
+ *   WX [3 nx][3 nt + 1], M [3 nt][3 nt].  XT is the one gather: the 3 nt entries of the last solve's step at the touched rows.
+ * sgo_debug_overlay_linearize: linearises the resident graph WITH its overlay at the current poses, as every Gauss-Newton
+ *   iteration of sgo_optimize_gn does, and returns the resident rows' right-hand side b[n][3] in the hessian order of the
+ *   resident free poses (ascending vertex id: what sgo_free_ids gave before the update).
+ * sgo_debug_overlay_apply: y = H_base x + U M U^T x for x[n][3] (same order) through the PCG iteration's own product with its
+ *   dot product on; *dot = the sum of the partial sums the recurrence reads as p.q.  Needs sgo_debug_overlay_linearize first. */
+#define SGO_OV_HDR 0
+#define SGO_OV_RP 1
+#define SGO_OV_ENT_EDGE 2
+#define SGO_OV_ENT_OTHER 3
+#define SGO_OV_ENT_SIDE 4
+#define SGO_OV_VTX 5
+#define SGO_OV_TROW 6
+#define SGO_OV_NZ 7
+#define SGO_OV_DN 8
+#define SGO_OV_UN 9
+#define SGO_OV_H0 10
+#define SGO_OV_Y 11
+#define SGO_OV_SINV 12
+#define SGO_OV_M0 13
+#define SGO_OV_BT 14
+#define SGO_OV_S 15
+#define SGO_OV_GK 16
+#define SGO_OV_WX 17
+#define SGO_OV_M 18
+#define SGO_OV_XT 19
+int64_t sgo_debug_overlay_array(sgo_ctx* ctx, int32_t what, void* out, int64_t cap_bytes);
+int sgo_debug_overlay_linearize(sgo_ctx* ctx, double* b);
+int sgo_debug_overlay_apply(sgo_ctx* ctx, const double* x, double* y, double* dot);
 /* Diagnostic (env SGO_LANCZOS=1 when the graph is set): alpha, beta of every PCG iteration of the last solve as pairs in
  * iteration order -- the Lanczos matrix of the preconditioned operator follows from them (scripts/ritz_probe.py).  Returns
  * the iterations written (<= cap pairs), < 0 on error. */

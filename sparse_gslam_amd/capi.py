@@ -30,6 +30,7 @@ SYMBOLS = [
     "sgo_closure_information", "sgo_plan_rows", "sgo_mfront_plan", "sgo_debug_coarse_rhs", "sgo_debug_spmv0_us",
     "sgo_solver_description", "sgo_comm_init_host", "sgo_comm_host_allgather", "sgo_debug_level0_bytes",
     "sgo_kernel_profile_samples", "sgo_update_graph_se2", "sgo_debug_lanczos", "sgo_debug_amg_array",
+    "sgo_debug_overlay_array", "sgo_debug_overlay_linearize", "sgo_debug_overlay_apply",
 ]
 
 
@@ -132,6 +133,10 @@ def lib():
     L.sgo_comm_host_allgather.argtypes = [vp, HOST_ALLGATHER]
     L.sgo_debug_amg_array.restype = C.c_int64
     L.sgo_debug_amg_array.argtypes = [vp, C.c_int32, C.c_int32, vp, C.c_int64]
+    L.sgo_debug_overlay_array.restype = C.c_int64
+    L.sgo_debug_overlay_array.argtypes = [vp, C.c_int32, vp, C.c_int64]
+    L.sgo_debug_overlay_linearize.argtypes = [vp, d]
+    L.sgo_debug_overlay_apply.argtypes = [vp, d, d, d]
     L.sgo_debug_level0_bytes.restype = C.c_int64
     L.sgo_debug_level0_bytes.argtypes = [vp]
     L.sgo_shard_range.restype = None

@@ -694,6 +694,76 @@ int64_t sgo_debug_amg_array(sgo_ctx* c, int32_t level, int32_t what, void* out, 
   } SGO_CATCH(c)
 }
 
+// Test hooks for the incremental overlay (include/sgo.h): the arrays of sgo_overlay.h as stored, the linearisation and the
+// operator of a Gauss-Newton iteration under an overlay.
+static int overlay_hook_ready(sgo_ctx* c, const char* name) {
+  int rc = check_graph(c);
+  if (rc) return rc;
+  if (!c->ov.active) {
+    c->err = std::string(name) + ": the resident graph carries no incremental overlay";
+    return SGO_EINVAL;
+  }
+  if (c->owner || multi_rank(c) || c->comm.nranks > 1) {
+    c->err = std::string(name) + ": not available in a multi-GPU context";
+    return SGO_EINVAL;
+  }
+  if (c->rows_pending || c->amg_pending || c->n == 0) {
+    c->err = std::string(name) + ": the resident structures are not built";
+    return SGO_EINVAL;
+  }
+  return SGO_OK;
+}
+
+int64_t sgo_debug_overlay_array(sgo_ctx* c, int32_t what, void* out, int64_t cap_bytes) {
+  try {
+    int rc = overlay_hook_ready(c, "sgo_debug_overlay_array");
+    if (rc) return rc;
+    if (cap_bytes < 0 || (cap_bytes > 0 && !out)) return SGO_EINVAL;
+    const long long r = overlay_debug_array(c->ov, c->stream, what, c->d_x, out, cap_bytes);
+    if (r == SGO_EINVAL) c->err = "sgo_debug_overlay_array: unknown array";
+    if (r == SGO_EHIP) c->err = "sgo_debug_overlay_array: device copy failed";
+    return r;
+  } SGO_CATCH(c)
+}
+
+int sgo_debug_overlay_linearize(sgo_ctx* c, double* b) {
+  try {
+    int rc = overlay_hook_ready(c, "sgo_debug_overlay_linearize");
+    if (rc) return rc;
+    if (!b) return SGO_EINVAL;
+    if ((rc = do_linearize(c))) return rc;
+    std::vector<double> dgb(9 * (size_t)c->n);
+    HIP_TRY(c, hipMemcpyAsync(dgb.data(), c->d_dgb, sizeof(double) * dgb.size(), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    for (int i = 0; i < c->n; ++i)
+      for (int q = 0; q < 3; ++q) b[3 * (size_t)i + q] = dgb[9 * (size_t)c->row_of_asc[i] + 6 + q];
+    return SGO_OK;
+  } SGO_CATCH(c)
+}
+
+int sgo_debug_overlay_apply(sgo_ctx* c, const double* x, double* y, double* dot) {
+  try {
+    int rc = overlay_hook_ready(c, "sgo_debug_overlay_apply");
+    if (rc) return rc;
+    if (!x || !y || !dot) return SGO_EINVAL;
+    if (!c->linearized) {
+      c->err = "sgo_debug_overlay_apply: call sgo_debug_overlay_linearize first";
+      return SGO_EINVAL;
+    }
+    if ((rc = vec_to_device(c, x, c->d_s1))) return rc;
+    int grid = 0;
+    if ((rc = do_spmv(c, c->d_s1, c->d_s2, true, nullptr, &grid))) return rc;
+    if (grid < 0 || grid > (int)kMaxPartials) return SGO_EHIP;
+    std::vector<double> parts((size_t)grid);
+    if (grid > 0) HIP_TRY(c, hipMemcpyAsync(parts.data(), c->d_partials, sizeof(double) * (size_t)grid, hipMemcpyDeviceToHost, c->stream));
+    if ((rc = vec_from_device(c, c->d_s2, y))) return rc;
+    long double s = 0.0L;
+    for (double p : parts) s += p;
+    *dot = (double)s;
+    return SGO_OK;
+  } SGO_CATCH(c)
+}
+
 // Diagnostic (env SGO_LANCZOS=1 at sgo_set_graph_se2): alpha / beta of every PCG iteration of the last solve, pairs in
 // iteration order; returns the number of iterations written (the Lanczos matrix of the preconditioned operator follows
 // from them: scripts/ritz_probe.py), < 0 on error.

@@ -59,6 +59,7 @@ struct OverlayDev {
   double* H0 = nullptr;              // [3 k][ncol] row-major: [H_NT | b_N]
   double* Y = nullptr;               // [3 k][ncol] H_NN^-1 [H_NT | b_N]
   double* Sinv = nullptr;            // [k][6]  inverses of the pivot blocks
+  double* Spiv = nullptr;            // [k][6]  the pivot blocks themselves (the solves refine the inverse's product against them)
   double* M0 = nullptr;              // [3 nk][3 nk] appended edges' direct contributions to the kept rows (nk = nt + nx)
   double* bt = nullptr;              // [3 nk]       ... to their right-hand side
   double* S = nullptr;               // [3 nk][3 nk] M0 - H_KN H_NN^-1 H_NK, symmetrised; gk [3 nk] the matching right-hand side
@@ -94,6 +95,11 @@ void overlay_release(Overlay& ov);
 // appends `cnt` raw edges (host arrays) to the overlay's device edge list at position `at`
 bool overlay_upload_edges(Overlay& ov, hipStream_t s, int at, int cnt, const int32_t* ei, const int32_t* ej, const double* meas,
                           const double* info, const double* phi, std::string* err);
+
+// Test hook (sgo_debug_overlay_array, include/sgo.h): one array of the resident overlay as stored on the device, copied to `out`
+// when cap_bytes holds it; `what` is one of SGO_OV_*; x: the last solve's step d_x ([n][3], internal row order), read for SGO_OV_XT
+// only.  Returns the array's size in bytes (0: no entries), SGO_EINVAL for an unknown array, SGO_EHIP when a copy fails.
+long long overlay_debug_array(const Overlay& ov, hipStream_t s, int what, const double* x, void* out, long long cap_bytes);
 
 void launch_ov_lin(hipStream_t s, const OverlayDev& O, const double* poses);
 // factorisation + Schur complement; adds g to the right-hand sides of the touched rows in dgb ([n][9]: entries 6..8)

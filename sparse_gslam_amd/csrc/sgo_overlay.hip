@@ -143,16 +143,33 @@ __device__ __forceinline__ bool sym3_inverse(const double (&d)[6], double (&v)[6
   return ok;
 }
 
+// x = S^-1 b for a pivot block S with its stored inverse V (both in symmetric packing): the inverse applied, then one step of
+// iterative refinement against S itself.  A product with an explicit inverse alone leaves a residual of kappa(S) U |S| |x| -- 10^7 U
+// on a pose with a closure of weight 10^10 and a lever arm of some tens of metres, 10^2 U far down a long chain --; with the
+// step the solve is backward stable, and so is the chain's block LDL^T (tests/overlay_reference.py, stage 4).
+__device__ __forceinline__ void ov_pivot_solve(const double* __restrict__ v, const double* __restrict__ s, const double (&b)[3], double (&x)[3]) {
+  const double x0 = v[0] * b[0] + v[1] * b[1] + v[2] * b[2];
+  const double x1 = v[1] * b[0] + v[3] * b[1] + v[4] * b[2];
+  const double x2 = v[2] * b[0] + v[4] * b[1] + v[5] * b[2];
+  const double r0 = b[0] - (s[0] * x0 + s[1] * x1 + s[2] * x2);
+  const double r1 = b[1] - (s[1] * x0 + s[3] * x1 + s[4] * x2);
+  const double r2 = b[2] - (s[2] * x0 + s[4] * x1 + s[5] * x2);
+  x[0] = x0 + (v[0] * r0 + v[1] * r1 + v[2] * r2);
+  x[1] = x1 + (v[1] * r0 + v[3] * r1 + v[4] * r2);
+  x[2] = x2 + (v[2] * r0 + v[4] * r1 + v[5] * r2);
+}
+
 // ---------------------------------------------------------------------------- k_ov_solve
 // One workgroup.  Block-tridiagonal LDL^T of H_NN along the chain with the ncol right-hand sides [H_NT | b_N] on the THREADS
 // of the workgroup (round 6; one wave's lanes before: 16 kept rows at most), one column each; every thread repeats the 3x3
 // pivot arithmetic (uniform: same inputs from LDS, same registers, same order -- no hand-over between the waves inside a tile:
-// a column is private to its thread), the chain walked in LDS tiles of kOvTile rows that all threads load and store; then M = M0 - H_TN Y (symmetrised) and g = bt - H_TN y_b, which is added to the touched rows'
-// right-hand sides in dgb.  A pivot block that is not positive definite (an appended chain that hangs in the air) makes
+// a column is private to its thread), the chain walked in LDS tiles of kOvTile rows that all threads load and store; every solve
+// with a pivot block applies its stored inverse and refines once against the block itself (ov_pivot_solve); then
+// M = M0 - H_TN Y (symmetrised) and g = bt - H_TN y_b, which is added to the touched rows' right-hand sides in dgb.  A pivot block that is not positive definite (an appended chain that hangs in the air) makes
 // g non-finite: the PCG start then reports a breakdown, as for any Hessian that is not positive definite.
 __global__ __launch_bounds__(kOvThreads) void k_ov_solve(OverlayDev O, double* __restrict__ dgb) {
   __shared__ double Yt[3 * kOvTile * kOvCols];
-  __shared__ double Dt[kOvTile * 6], Ut[kOvTile * 9], Sv[kOvTile * 6];
+  __shared__ double Dt[kOvTile * 6], Ut[kOvTile * 9], Sv[kOvTile * 6], Pv[kOvTile * 6];
   __shared__ double fcol[3 * kOvMaxHubs];
   __shared__ int fail, bad_x;
   const int tid = threadIdx.x;
@@ -160,7 +177,7 @@ __global__ __launch_bounds__(kOvThreads) void k_ov_solve(OverlayDev O, double* _
   if (tid == 0) fail = bad_x = 0;
   __syncthreads();
   // ---- forward elimination
-  double sp[6] = {0, 0, 0, 0, 0, 0}, up[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, rpv[3] = {0, 0, 0};
+  double sp[6] = {0, 0, 0, 0, 0, 0}, pp[6] = {0, 0, 0, 0, 0, 0}, up[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, rpv[3] = {0, 0, 0};   // (previous row: inverse, pivot, U, r)
   for (int t0 = 0; t0 < k; t0 += kOvTile) {
     const int rows = min(kOvTile, k - t0);
     for (int i = tid; i < 3 * rows * nc; i += kOvThreads) Yt[i] = O.H0[(size_t)3 * t0 * nc + i];
@@ -177,30 +194,42 @@ __global__ __launch_bounds__(kOvThreads) void k_ov_solve(OverlayDev O, double* _
           r[0] = Yt[(3 * i) * nc + tid]; r[1] = Yt[(3 * i + 1) * nc + tid]; r[2] = Yt[(3 * i + 2) * nc + tid];
         }
         if (t0 + i > 0) {
-          // L = U_prev^T Sinv_prev ; S -= L U_prev ; r -= L r_prev
-          const double P[9] = {sp[0], sp[1], sp[2], sp[1], sp[3], sp[4], sp[2], sp[4], sp[5]};
-          double L[9];
+          // W = S_prev^-1 U_prev, z = S_prev^-1 r_prev (ov_pivot_solve) ; S -= U_prev^T W ; r -= U_prev^T z
+          double W[9], z[3];
 #pragma unroll
-          for (int a = 0; a < 3; ++a)
+          for (int c2 = 0; c2 < 3; ++c2) {
+            const double ucol[3] = {up[c2], up[3 + c2], up[6 + c2]};
+            double w[3];
+            ov_pivot_solve(sp, pp, ucol, w);
+            W[c2] = w[0]; W[3 + c2] = w[1]; W[6 + c2] = w[2];
+          }
+          ov_pivot_solve(sp, pp, rpv, z);
+          S[0] -= up[0] * W[0] + up[3] * W[3] + up[6] * W[6];
+          S[1] -= up[0] * W[1] + up[3] * W[4] + up[6] * W[7];
+          S[2] -= up[0] * W[2] + up[3] * W[5] + up[6] * W[8];
+          S[3] -= up[1] * W[1] + up[4] * W[4] + up[7] * W[7];
+          S[4] -= up[1] * W[2] + up[4] * W[5] + up[7] * W[8];
+          S[5] -= up[2] * W[2] + up[5] * W[5] + up[8] * W[8];
 #pragma unroll
-            for (int c2 = 0; c2 < 3; ++c2) L[3 * a + c2] = up[a] * P[c2] + up[3 + a] * P[3 + c2] + up[6 + a] * P[6 + c2];
-          S[0] -= L[0] * up[0] + L[1] * up[3] + L[2] * up[6];
-          S[1] -= L[0] * up[1] + L[1] * up[4] + L[2] * up[7];
-          S[2] -= L[0] * up[2] + L[1] * up[5] + L[2] * up[8];
-          S[3] -= L[3] * up[1] + L[4] * up[4] + L[5] * up[7];
-          S[4] -= L[3] * up[2] + L[4] * up[5] + L[5] * up[8];
-          S[5] -= L[6] * up[2] + L[7] * up[5] + L[8] * up[8];
-#pragma unroll
-          for (int a = 0; a < 3; ++a) r[a] -= L[3 * a] * rpv[0] + L[3 * a + 1] * rpv[1] + L[3 * a + 2] * rpv[2];
+          for (int a = 0; a < 3; ++a) r[a] -= up[a] * z[0] + up[3 + a] * z[1] + up[6 + a] * z[2];
         }
         double si[6];
         if (!sym3_inverse(S, si) && tid == 0) fail = 1;
-        if (tid < 6) Sv[6 * i + tid] = si[tid];
+        if (tid == 0) {   // (one lane, constant indices: a lane-indexed read would put the blocks into scratch memory)
+#pragma unroll
+          for (int q = 0; q < 6; ++q) {
+            Sv[6 * i + q] = si[q];
+            Pv[6 * i + q] = S[q];
+          }
+        }
         if (tid < nc) {
           Yt[(3 * i) * nc + tid] = r[0]; Yt[(3 * i + 1) * nc + tid] = r[1]; Yt[(3 * i + 2) * nc + tid] = r[2];
         }
 #pragma unroll
-        for (int q = 0; q < 6; ++q) sp[q] = si[q];
+        for (int q = 0; q < 6; ++q) {
+          sp[q] = si[q];
+          pp[q] = S[q];
+        }
 #pragma unroll
         for (int q = 0; q < 9; ++q) up[q] = Ut[9 * i + q];
         rpv[0] = r[0]; rpv[1] = r[1]; rpv[2] = r[2];
@@ -208,16 +237,22 @@ __global__ __launch_bounds__(kOvThreads) void k_ov_solve(OverlayDev O, double* _
     }
     __syncthreads();
     for (int i = tid; i < 3 * rows * nc; i += kOvThreads) O.Y[(size_t)3 * t0 * nc + i] = Yt[i];
-    for (int i = tid; i < 6 * rows; i += kOvThreads) O.Sinv[6 * (size_t)t0 + i] = Sv[i];
+    for (int i = tid; i < 6 * rows; i += kOvThreads) {
+      O.Sinv[6 * (size_t)t0 + i] = Sv[i];
+      O.Spiv[6 * (size_t)t0 + i] = Pv[i];
+    }
     __syncthreads();
   }
-  // ---- back substitution: y_i = Sinv_i (r_i - U_i y_{i+1})
+  // ---- back substitution: y_i = S_i^-1 (r_i - U_i y_{i+1}) (ov_pivot_solve)
   double yn[3] = {0, 0, 0};
   const int ntile = (k + kOvTile - 1) / kOvTile;
   for (int tt = ntile - 1; tt >= 0; --tt) {
     const int t0 = tt * kOvTile, rows = min(kOvTile, k - t0);
     for (int i = tid; i < 3 * rows * nc; i += kOvThreads) Yt[i] = O.Y[(size_t)3 * t0 * nc + i];
-    for (int i = tid; i < 6 * rows; i += kOvThreads) Sv[i] = O.Sinv[6 * (size_t)t0 + i];
+    for (int i = tid; i < 6 * rows; i += kOvThreads) {
+      Sv[i] = O.Sinv[6 * (size_t)t0 + i];
+      Pv[i] = O.Spiv[6 * (size_t)t0 + i];
+    }
     for (int i = tid; i < 9 * rows; i += kOvThreads) Ut[i] = O.Un[9 * (size_t)t0 + i];
     __syncthreads();
     if (tid < nc) {
@@ -228,10 +263,7 @@ __global__ __launch_bounds__(kOvThreads) void k_ov_solve(OverlayDev O, double* _
 #pragma unroll
           for (int a = 0; a < 3; ++a) r[a] -= U[3 * a] * yn[0] + U[3 * a + 1] * yn[1] + U[3 * a + 2] * yn[2];
         }
-        const double* v = Sv + 6 * i;
-        yn[0] = v[0] * r[0] + v[1] * r[1] + v[2] * r[2];
-        yn[1] = v[1] * r[0] + v[3] * r[1] + v[4] * r[2];
-        yn[2] = v[2] * r[0] + v[4] * r[1] + v[5] * r[2];
+        ov_pivot_solve(Sv + 6 * i, Pv + 6 * i, r, yn);
         Yt[(3 * i) * nc + tid] = yn[0]; Yt[(3 * i + 1) * nc + tid] = yn[1]; Yt[(3 * i + 2) * nc + tid] = yn[2];
       }
     }
@@ -405,11 +437,11 @@ void launch_ov_finish(hipStream_t s, const OverlayDev& O, const double* x, doubl
 // Device buffers of an overlay, carved out of one allocation made at first use (capacities of sgo_overlay.h):
 //   ints:    header[4] = {k, nt, ncol, nnz} | rp | ent_edge | ent_other | vtx | trow | nz | el.vi | el.vj
 //   bytes:   ent_side
-//   doubles: el.phi, el.zinv[3], el.info[6], raw meas / info staging, Dn, Un, H0, Y, Sinv, M0, bt, M
+//   doubles: el.phi, el.zinv[3], el.info[6], raw meas / info staging, Dn, Un, H0, Y, Sinv, Spiv, M0, bt, M
 namespace {
 struct Layout {
   size_t i_hdr, i_rp, i_edge, i_other, i_vtx, i_trow, i_nz, i_vi, i_vj, n_int;
-  size_t d_phi, d_zinv, d_info, d_raw, d_Dn, d_Un, d_H0, d_Y, d_Sinv, d_M0, d_bt, d_M, d_S, d_gk, d_Wx, n_dbl;
+  size_t d_phi, d_zinv, d_info, d_raw, d_Dn, d_Un, d_H0, d_Y, d_Sinv, d_Spiv, d_M0, d_bt, d_M, d_S, d_gk, d_Wx, n_dbl;
   Layout() {
     size_t o = 0;
     i_hdr = o; o += 8;
@@ -434,6 +466,7 @@ struct Layout {
     d_H0 = o; o += 3 * (size_t)kOvMaxRows * kOvCols;
     d_Y = o; o += 3 * (size_t)kOvMaxRows * kOvCols;
     d_Sinv = o; o += 6 * (size_t)kOvMaxRows;
+    d_Spiv = o; o += 6 * (size_t)kOvMaxRows;
     d_M0 = o; o += (size_t)(kOvCols - 1) * (kOvCols - 1);
     d_bt = o; o += kOvCols;
     d_M = o; o += (size_t)(kOvCols - 1) * (kOvCols - 1);
@@ -493,6 +526,7 @@ static bool overlay_alloc(Overlay& ov, std::string* err) {
   O.H0 = d + L.d_H0;
   O.Y = d + L.d_Y;
   O.Sinv = d + L.d_Sinv;
+  O.Spiv = d + L.d_Spiv;
   O.M0 = d + L.d_M0;
   O.bt = d + L.d_bt;
   O.M = d + L.d_M;
@@ -658,6 +692,63 @@ bool overlay_build(Overlay& ov, int V, hipStream_t s, std::string* why, std::str
   ov.new_vertex = nv;
   (void)V;
   return true;
+}
+
+// The test hook's copy: the sizes come from the DEVICE's header and row pointers (what the kernels read), not from the host's.
+long long overlay_debug_array(const Overlay& ov, hipStream_t s, int what, const double* x, void* out, long long cap_bytes) {
+  const OverlayDev& O = ov.dev;
+  if (!ov.buf) return SGO_EINVAL;
+  int hdr[5] = {0, 0, 0, 0, 0};
+  if (hipMemcpyAsync(hdr, O.hdr, sizeof(hdr), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) return SGO_EHIP;
+  const long long k = hdr[0], nt = hdr[1], nc = hdr[2], nnz = hdr[3], nx = hdr[4], nk = nt + nx;
+  if (k < 0 || k > kOvMaxRows || nt < 0 || nx < 0 || nx > kOvMaxHubs || nk > kOvMaxTouched || nc != 3 * nk + 1 || nnz < 0 || nnz > k) return SGO_EHIP;
+  long long nent = 0;
+  if (what == SGO_OV_ENT_EDGE || what == SGO_OV_ENT_OTHER || what == SGO_OV_ENT_SIDE) {
+    int last = 0;
+    if (hipMemcpyAsync(&last, O.rp + (k + nk), sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) return SGO_EHIP;
+    if (last < 0 || last > 2 * kOvMaxEdges) return SGO_EHIP;
+    nent = last;
+  }
+  const void* src = nullptr;
+  long long bytes = 0;
+  const long long I = sizeof(int), D = sizeof(double);
+  switch (what) {
+    case SGO_OV_HDR: src = O.hdr; bytes = 5 * I; break;
+    case SGO_OV_RP: src = O.rp; bytes = (k + nk + 1) * I; break;
+    case SGO_OV_ENT_EDGE: src = O.ent_edge; bytes = nent * I; break;
+    case SGO_OV_ENT_OTHER: src = O.ent_other; bytes = nent * I; break;
+    case SGO_OV_ENT_SIDE: src = O.ent_side; bytes = nent; break;
+    case SGO_OV_VTX: src = O.vtx; bytes = (k + nx) * I; break;
+    case SGO_OV_TROW: src = O.trow; bytes = nt * I; break;
+    case SGO_OV_NZ: src = O.nz; bytes = nnz * I; break;
+    case SGO_OV_DN: src = O.Dn; bytes = 6 * k * D; break;
+    case SGO_OV_UN: src = O.Un; bytes = 9 * k * D; break;
+    case SGO_OV_H0: src = O.H0; bytes = 3 * k * nc * D; break;
+    case SGO_OV_Y: src = O.Y; bytes = 3 * k * nc * D; break;
+    case SGO_OV_SINV: src = O.Sinv; bytes = 6 * k * D; break;
+    case SGO_OV_M0: src = O.M0; bytes = 9 * nk * nk * D; break;
+    case SGO_OV_BT: src = O.bt; bytes = 3 * nk * D; break;
+    case SGO_OV_S: src = O.S; bytes = 9 * nk * nk * D; break;
+    case SGO_OV_GK: src = O.gk; bytes = 3 * nk * D; break;
+    case SGO_OV_WX: src = O.Wx; bytes = 3 * nx * (3 * nt + 1) * D; break;
+    case SGO_OV_M: src = O.M; bytes = 9 * nt * nt * D; break;
+    case SGO_OV_XT: bytes = 3 * nt * D; break;
+    default: return SGO_EINVAL;
+  }
+  if (bytes == 0 || cap_bytes < bytes) return bytes;
+  if (what == SGO_OV_XT) {   // the one gather: the step's entries at the touched rows
+    if (!x) return SGO_EINVAL;
+    std::vector<int> trow((size_t)nt);
+    if (hipMemcpyAsync(trow.data(), O.trow, nt * I, hipMemcpyDeviceToHost, s) != hipSuccess) return SGO_EHIP;
+    if (hipStreamSynchronize(s) != hipSuccess) return SGO_EHIP;
+    for (long long t = 0; t < nt; ++t) {
+      if (trow[t] < 0 || trow[t] >= ov.base_n) return SGO_EHIP;
+      if (hipMemcpyAsync(static_cast<double*>(out) + 3 * t, x + 3 * (size_t)trow[t], 3 * D, hipMemcpyDeviceToHost, s) != hipSuccess) return SGO_EHIP;
+    }
+    return hipStreamSynchronize(s) == hipSuccess ? bytes : (long long)SGO_EHIP;
+  }
+  if (hipMemcpyAsync(out, src, (size_t)bytes, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) return SGO_EHIP;
+  return bytes;
 }
 
 }  // namespace sgo

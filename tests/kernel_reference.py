@@ -120,6 +120,7 @@ def edge_terms(xi, xj, meas, info, phi, x_i=(), x_j=(), e=None):
              bi=-np.einsum("nij,nj->ni", At, We), bj=-np.einsum("nij,nj->ni", Bt, We),
              bi_abs=np.einsum("nij,nj->ni", Abt, Wea), bj_abs=np.einsum("nij,nj->ni", Bbt, Wea),
              Hii=At @ W @ A, Hjj=Bt @ W @ B, Hii_abs=Abt @ Wa @ Ab, Hjj_abs=Bbt @ Wa @ Bb,
+             Hij=At @ W @ B, Hij_abs=Abt @ Wa @ Bb,      # (the off-diagonal block towards the second vertex; its transpose the other way)
              yi=[], yj=[], yi_abs=[], yj_abs=[])
     for a, c in zip(x_i, x_j):
         v = np.einsum("nij,nj->ni", W, np.einsum("nij,nj->ni", A, a) + np.einsum("nij,nj->ni", B, c))
