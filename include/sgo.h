@@ -451,6 +451,55 @@ int64_t sgo_debug_amg_array(sgo_ctx* ctx, int32_t level, int32_t what, void* out
 int64_t sgo_debug_overlay_array(sgo_ctx* ctx, int32_t what, void* out, int64_t cap_bytes);
 int sgo_debug_overlay_linearize(sgo_ctx* ctx, double* b);
 int sgo_debug_overlay_apply(sgo_ctx* ctx, const double* x, double* y, double* dot);
+
+/* Test hooks for the multifrontal path (mid-size graphs: DESIGN.md section 5c; tests/mfront_reference.py checks every stage of
+ * one Gauss-Newton iteration from these arrays).
+ * sgo_debug_mfront_array: a read-only copy of one array of the resident multifrontal factorisation as the LAST Gauss-Newton
+ *   iteration of the last sgo_optimize_gn left it -- device memory as stored, nothing recomputed (the closing chi2 pass of a call
+ *   writes no array).  Same convention as sgo_debug_amg_array: returns the array's size in bytes (0: it has no entries) and
+ *   copies it when cap_bytes holds it.  SGO_EINVAL with a message when the resident graph is not on the multifrontal path
+ *   (sgo_solver_description does not start with multifrontal_cholesky) or no sgo_optimize_gn with iters > 0 has run on it.
+ * sgo_mfront_plan_array: the same arrays SGO_MF_INFO .. SGO_MF_ELIM_VERTEX from the host's originals -- the plan sgo_set_graph_se2 makes for
+ *   this graph (arguments as sgo_mfront_plan's; leaf <= 0 and max_crit_mflop <= 0: its defaults, SGO_MFRONT_LEAF / _CRIT_MFLOP /
+ *   _DEGREE of the environment included), on the host alone.  SGO_ENOTHING: the graph does not qualify.
+ * `what` is one of SGO_MF_*:
+ *   INFO         int64[8] { free poses n, edges E, fronts, levels, doubles of the arena, entries of PINV, targets, contributions }
+ *                (the host's sizes: the device holds no copy)
+ *   FRONTS       int64[fronts][14], fronts numbered children first: e0 (first elimination position of the own poses), own3 (own
+ *                scalar rows), m (own + boundary scalar rows; the right-hand side is row m), ld, off (the matrix' place in ARENA:
+ *                column-major, lower triangle, own columns first), nb (boundary poses), bnd_off, kid[0], kid[1] (-1: none),
+ *                pinv_off[0], pinv_off[1], tgt0, tgt1, parent (-1: a root)
+ *   LEVEL_PTR    int32[levels + 1] (host), LEVEL_FRONT int32[fronts]: the fronts of height h are LEVEL_FRONT[LEVEL_PTR[h] .. LEVEL_PTR[h + 1])
+ *   BND          int32: the boundary poses of front f, elimination positions ascending, at bnd_off .. + nb
+ *   PINV         int32: child k of front f: PINV[pinv_off[k] + local pose of f] = that pose's index among the child's boundary
+ *                poses, -1: the child does not hold it
+ *   TARGETS      int32[targets][4] { li, lj (local poses, li >= lj), c0, c1 }: the 3x3 blocks of front f that edges add to are
+ *                tgt0 .. tgt1; CONTRIB int32: edge << 2 | part (0: D_ii and b_i, 1: D_jj and b_j, 2: H_ij as stored, 3: its transpose)
+ *   ELIM_VERTEX  int32[n]: the vertex at every elimination position
+ *   ELEM         double[E][28]: D_ii (upper triangle by rows, 6), D_jj (6), H_ij (9, by rows), b_i (3), b_j (3), one pad
+ *   ARENA        double: every front's matrix after its factorisation: columns < own3 hold L11, L21 and (row m) the
+ *                forward-substituted right-hand side; columns >= own3 the assembled boundary block and its right-hand side
+ *   X            double[3 n]: the step by elimination position;  INVD double[3 n]: 1 / L[c][c];  YINV double[3 n][16]: row i of the
+ *                inverse of its 16 x 16 diagonal block's factor
+ *   FLAGS        int32[8]: fail, iteration of the failure, non-finite substitution, updates applied */
+#define SGO_MF_INFO 0
+#define SGO_MF_FRONTS 1
+#define SGO_MF_LEVEL_PTR 2
+#define SGO_MF_LEVEL_FRONT 3
+#define SGO_MF_BND 4
+#define SGO_MF_PINV 5
+#define SGO_MF_TARGETS 6
+#define SGO_MF_CONTRIB 7
+#define SGO_MF_ELIM_VERTEX 8
+#define SGO_MF_ELEM 9
+#define SGO_MF_ARENA 10
+#define SGO_MF_X 11
+#define SGO_MF_INVD 12
+#define SGO_MF_YINV 13
+#define SGO_MF_FLAGS 14
+int64_t sgo_debug_mfront_array(sgo_ctx* ctx, int32_t what, void* out, int64_t cap_bytes);
+int64_t sgo_mfront_plan_array(int32_t V, const double* poses, const uint8_t* fixed, int32_t E, const int32_t* ei, const int32_t* ej,
+                              int32_t leaf, double max_crit_mflop, int32_t what, void* out, int64_t cap_bytes);
 /* Diagnostic (env SGO_LANCZOS=1 when the graph is set): alpha, beta of every PCG iteration of the last solve as pairs in
  * iteration order -- the Lanczos matrix of the preconditioned operator follows from them (scripts/ritz_probe.py).  Returns
  * the iterations written (<= cap pairs), < 0 on error. */

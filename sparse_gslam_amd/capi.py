@@ -31,6 +31,7 @@ SYMBOLS = [
     "sgo_solver_description", "sgo_comm_init_host", "sgo_comm_host_allgather", "sgo_debug_level0_bytes",
     "sgo_kernel_profile_samples", "sgo_update_graph_se2", "sgo_debug_lanczos", "sgo_debug_amg_array",
     "sgo_debug_overlay_array", "sgo_debug_overlay_linearize", "sgo_debug_overlay_apply",
+    "sgo_debug_mfront_array", "sgo_mfront_plan_array",
 ]
 
 
@@ -137,6 +138,10 @@ def lib():
     L.sgo_debug_overlay_array.argtypes = [vp, C.c_int32, vp, C.c_int64]
     L.sgo_debug_overlay_linearize.argtypes = [vp, d]
     L.sgo_debug_overlay_apply.argtypes = [vp, d, d, d]
+    L.sgo_debug_mfront_array.restype = C.c_int64
+    L.sgo_debug_mfront_array.argtypes = [vp, C.c_int32, vp, C.c_int64]
+    L.sgo_mfront_plan_array.restype = C.c_int64
+    L.sgo_mfront_plan_array.argtypes = [C.c_int32, d, u8, C.c_int32, i32, i32, C.c_int32, C.c_double, C.c_int32, vp, C.c_int64]
     L.sgo_debug_level0_bytes.restype = C.c_int64
     L.sgo_debug_level0_bytes.argtypes = [vp]
     L.sgo_shard_range.restype = None
@@ -225,6 +230,42 @@ def mfront_plan(poses, fixed, ei, ej, leaf: int = 0, max_crit_mflop: float = 0.0
     out["elim_vertex"] = ev[:n].copy()
     out["front_of_elim"] = fe[:n].copy()
     return out
+
+
+# SGO_MF_* of include/sgo.h: name -> (number, dtype, columns); the first nine are the host plan's as well
+MFRONT_ARRAYS = {"INFO": (0, np.int64, 0), "FRONTS": (1, np.int64, 14), "LEVEL_PTR": (2, np.int32, 0), "LEVEL_FRONT": (3, np.int32, 0),
+                 "BND": (4, np.int32, 0), "PINV": (5, np.int32, 0), "TARGETS": (6, np.int32, 4), "CONTRIB": (7, np.int32, 0),
+                 "ELIM_VERTEX": (8, np.int32, 0), "ELEM": (9, np.float64, 28), "ARENA": (10, np.float64, 0), "X": (11, np.float64, 0),
+                 "INVD": (12, np.float64, 0), "YINV": (13, np.float64, 16), "FLAGS": (14, np.int32, 0)}
+MFRONT_PLAN_ARRAYS = ("INFO", "FRONTS", "LEVEL_PTR", "LEVEL_FRONT", "BND", "PINV", "TARGETS", "CONTRIB", "ELIM_VERTEX")
+
+
+def _mfront_fetch(name, call, err):
+    what, dtype, cols = MFRONT_ARRAYS[name]
+    size = call(what, None, 0)
+    if size < 0:
+        raise SgoError(f"{name}: rc={size}: " + err())
+    out = np.empty(size // np.dtype(dtype).itemsize, dtype=dtype)
+    if size:
+        got = call(what, out.ctypes.data_as(C.c_void_p), out.nbytes)
+        if got != size:
+            raise SgoError(f"{name}: {got} bytes after {size}: " + err())
+    return out.reshape(-1, cols) if cols else out
+
+
+def mfront_plan_arrays(poses, fixed, ei, ej, leaf: int = 0, max_crit_mflop: float = 0.0):
+    """The host plan's arrays (sgo_mfront_plan_array; needs no GPU): {name: array} for MFRONT_PLAN_ARRAYS, the very tables
+    sgo_set_graph_se2 uploads for this graph under the same environment.  SgoError when the graph does not qualify."""
+    p = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 3)
+    f = np.ascontiguousarray(fixed, dtype=np.uint8)
+    a = np.ascontiguousarray(ei, dtype=np.int32)
+    b = np.ascontiguousarray(ej, dtype=np.int32)
+    L = lib()
+
+    def call(what, out, cap):
+        return L.sgo_mfront_plan_array(p.shape[0], _dp(p), f.ctypes.data_as(C.POINTER(C.c_uint8)), a.size, _ip(a), _ip(b), leaf,
+                                       max_crit_mflop, what, out, cap)
+    return {k: _mfront_fetch(k, call, lambda: L.sgo_last_error(None).decode()) for k in MFRONT_PLAN_ARRAYS}
 
 
 def comm_unique_id() -> bytes:
@@ -448,6 +489,11 @@ class Optimizer:
     def last_error(self) -> str:
         """Text of the last error on this context (sgo_last_error)."""
         return lib().sgo_last_error(self._h).decode()
+
+    def mfront_arrays(self, names=tuple(MFRONT_ARRAYS)):
+        """The resident multifrontal factorisation's arrays as the last optimize() left them (sgo_debug_mfront_array)."""
+        return {k: _mfront_fetch(k, lambda what, out, cap: lib().sgo_debug_mfront_array(self._h, what, out, cap), self.last_error)
+                for k in names}
 
     def solver_description(self) -> str:
         """Which solver sgo_optimize_gn runs for the resident graph (sgo_solver_description)."""

@@ -764,6 +764,27 @@ int sgo_debug_overlay_apply(sgo_ctx* c, const double* x, double* y, double* dot)
   } SGO_CATCH(c)
 }
 
+// Test hook for the multifrontal path (include/sgo.h): the resident factorisation's arrays as stored (mfront_debug_array).
+int64_t sgo_debug_mfront_array(sgo_ctx* c, int32_t what, void* out, int64_t cap_bytes) {
+  try {
+    int rc = check_graph(c);
+    if (rc) return rc;
+    if (!c->mf) {
+      c->err = "sgo_debug_mfront_array: the resident graph is not on the multifrontal path (" + c->solver_desc.substr(0, c->solver_desc.find(':')) + ")";
+      return SGO_EINVAL;
+    }
+    if (cap_bytes < 0 || (cap_bytes > 0 && !out)) return SGO_EINVAL;
+    const long long r = mfront_debug_array(c->mf, c->stream, what, out, cap_bytes);
+    if (r == SGO_ENOTHING) {
+      c->err = "sgo_debug_mfront_array: no sgo_optimize_gn has run on the resident graph";
+      return SGO_EINVAL;
+    }
+    if (r == SGO_EINVAL) c->err = "sgo_debug_mfront_array: unknown array";
+    if (r == SGO_EHIP) c->err = "sgo_debug_mfront_array: device copy failed";
+    return r;
+  } SGO_CATCH(c)
+}
+
 // Diagnostic (env SGO_LANCZOS=1 at sgo_set_graph_se2): alpha / beta of every PCG iteration of the last solve, pairs in
 // iteration order; returns the number of iterations written (the Lanczos matrix of the preconditioned operator follows
 // from them: scripts/ritz_probe.py), < 0 on error.

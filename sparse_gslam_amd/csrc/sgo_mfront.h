@@ -85,6 +85,16 @@ struct MfLimits {
 bool mfront_analyze(int V, int n, const int* free_id, const double* poses, int E, const int* ei, const int* ej, const MfLimits& lim,
                     MfPlan* plan, std::string* why);
 
+// The front table in plain columns (sgo_debug_mfront_array / sgo_mfront_plan_array, SGO_MF_FRONTS of include/sgo.h):
+// e0, own3, m, ld, off, nb, bnd_off, kid[0], kid[1], pinv_off[0], pinv_off[1], tgt0, tgt1, parent
+constexpr int kMfFrontCols = 14;
+void mfront_tables(const MfPlan& plan, std::vector<long long>* fronts, std::vector<int>* pinv);
+// The limits sgo_set_graph_se2 analyses with: the defaults and the environment's SGO_MFRONT_LEAF / _CRIT_MFLOP / _DEGREE.
+void mfront_env_limits(MfLimits* lim);
+// One array of a host plan by its SGO_MF_* number (the plan's share: INFO .. ELIM_VERTEX): bytes, copied when cap_bytes holds
+// them; SGO_EINVAL for any other array.
+long long mfront_plan_array(const MfPlan& plan, int E, int what, void* out, long long cap_bytes);
+
 struct Mfront;   // opaque: plan + device arrays
 
 struct MfrontInfo {
@@ -106,5 +116,7 @@ const MfrontInfo& mfront_info(const Mfront* m);
 hipError_t mfront_optimize(Mfront* m, hipStream_t s, const EdgeListDev& el, double* d_poses, int iters, double* d_hist,
                            DirectResult* d_res);
 double mfront_bytes(const Mfront* m, int E, int iters);
+// Test hook (sgo_debug_mfront_array): one resident array as stored after the last mfront_optimize; SGO_ENOTHING before the first.
+long long mfront_debug_array(const Mfront* m, hipStream_t s, int what, void* out, long long cap_bytes);
 
 }  // namespace sgo

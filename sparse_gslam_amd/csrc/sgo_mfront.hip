@@ -269,7 +269,7 @@ __global__ __launch_bounds__(kBlock) void k_mf_merge(MfDev M, int t0, int t1) {
 //   D1  P = A[k0.., k0 .. k0+16) - L[k0.., 0 .. k0) L[k0 .. k0+16, 0 .. k0)^T to LDS (matrix cores, operands from L2);
 //   D2  the 16 x 16 Cholesky on wave 0 and the inverse of its factor on wave 1, one pivot behind (rows on the lanes, columns in
 //       registers, broadcasts by v_readlane; wave 0 hands every finished column and pivot to wave 1 through LDS);
-//   D3  L21 = P21 L11^-T on the matrix cores, straight to the front's matrix.
+//   D3  L21 = P21 L11^-T on the matrix cores, refined once against L11, straight to the front's matrix.
 __global__ __launch_bounds__(kMfThreads) void k_mf_panels(MfDev M, int lvl0, int it, int stamp_slot, int nparts, double* __restrict__ hist,
                                                          DirectResult* __restrict__ res) {
   extern __shared__ double Pn[];               // panel: column c at Pn + c * ldp, rows relative to k0 
@@ -523,22 +523,35 @@ __global__ __launch_bounds__(kMfThreads) void k_mf_panels(MfDev M, int lvl0, int
     }
     if (tid == 0) s_half = 0;   // (both are read again only after the barrier that ends the next D1)
     if (tid < kMfPanel) LI[tid] = 0.0;
-    // D3: rows below the diagonal block, straight to the front's matrix
+    // D3: rows below the diagonal block, straight to the front's matrix.  The product with the explicit inverse alone is not
+    // backward stable -- its error carries the block's condition number (measured on a graph whose information is scaled by
+    // 10^+-6: the forward-substituted right-hand side 2.5e4 U |L| |L^T| off) --, so it is refined once
+    // against the factor itself: X = P21 Y^T, X += (P21 - X L11^T) Y^T.  All three products are formed TRANSPOSED (the
+    // inverse or the factor as the first operand): a lane then holds row (rr0 + lr) of the result at the columns lk + 4 q,
+    // which is exactly the operand layout of the next product's contraction index -- no exchange between the steps.
     {
       const int R2 = R - wp;
       for (int rt = wave; rt < ((R2 + 15) >> 4); rt += kMfNW) {
         const int rr0 = wp + 16 * rt;
         const bool rv = rr0 + lr < R;
-        double av[4];
+        double av[4], yv[4], lv[4];
 #pragma unroll
-        for (int s = 0; s < 4; ++s) av[s] = rv ? Pn[(4 * s + lk) * ldp + rr0 + lr] : 0.0;
-        mf_d4 acc = {0.0, 0.0, 0.0, 0.0};
+        for (int s = 0; s < 4; ++s) {
+          av[s] = rv ? Pn[(4 * s + lk) * ldp + rr0 + lr] : 0.0;      // P21[row][4 s + lk]
+          yv[s] = Yt[(4 * s + lk) * kMfPanel + lr];                  // (L11^-1)[lr][4 s + lk]
+          lv[s] = lr >= 4 * s + lk ? LX[4 * s + lk][lr] : 0.0;       // L11[lr][4 s + lk] (LX holds wave 0's working values above the diagonal)
+        }
+        mf_d4 x = {0.0, 0.0, 0.0, 0.0}, xl = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
-        for (int s = 0; s < 4; ++s) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(av[s], Yt[(4 * s + lk) * kMfPanel + lr], acc, 0, 0, 0);
+        for (int s = 0; s < 4; ++s) x = __builtin_amdgcn_mfma_f64_16x16x4f64(yv[s], av[s], x, 0, 0, 0);       // x[q] = X[row][lk + 4 q]
+#pragma unroll
+        for (int s = 0; s < 4; ++s) xl = __builtin_amdgcn_mfma_f64_16x16x4f64(lv[s], x[s], xl, 0, 0, 0);     // xl[q] = (X L11^T)[row][lk + 4 q]
+#pragma unroll
+        for (int s = 0; s < 4; ++s) x = __builtin_amdgcn_mfma_f64_16x16x4f64(yv[s], av[s] - xl[s], x, 0, 0, 0);
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-          const int row = rr0 + lk + 4 * q;
-          if (row < R && cv) A[(size_t)(k0 + lr) * ld + k0 + row] = acc[q];
+          const int c = lk + 4 * q;
+          if (rv && c < wp) A[(size_t)(k0 + c) * ld + k0 + rr0 + lr] = x[q];
         }
       }
     }
@@ -719,6 +732,8 @@ struct Mfront {
   std::vector<int> level_lds;        // dynamic LDS of the panel launch of every level
   std::vector<int> level_solve_lds;  // ... of the substitution launch
   std::vector<int> mtile_ptr;        // k_mf_merge's tiles of level h: [mtile_ptr[h], mtile_ptr[h + 1])
+  size_t n_pinv = 0;                 // entries of dev.pinv
+  bool ran = false;                  // an mfront_optimize with iters > 0 has filled elem, the arena, x, invd and yinv
 };
 
 const MfrontInfo& mfront_info(const Mfront* m) { return m->info; }
@@ -736,9 +751,7 @@ Mfront* mfront_create(hipStream_t s, DevArena* arena, int V, int n, const int* f
     const int prev_n = *order_hint >> 1;
     if (std::abs(prev_n - n) * 10 <= prev_n) lim.only_kind = *order_hint & 1;
   }
-  if (const char* e = std::getenv("SGO_MFRONT_LEAF")) lim.leaf = std::max(4, std::atoi(e));
-  if (const char* e = std::getenv("SGO_MFRONT_CRIT_MFLOP")) lim.max_crit_flops = 1e6 * std::atof(e);
-  if (const char* e = std::getenv("SGO_MFRONT_DEGREE")) lim.max_degree = std::atof(e);
+  mfront_env_limits(&lim);
   std::unique_ptr<Mfront, void (*)(Mfront*)> M(new Mfront, &mfront_destroy);   // (frees the device buffer on every early return)
   if (!mfront_analyze(V, n, free_id, poses, E, ei, ej, lim, &M->plan, why)) {
     if (lim.only_kind < 0) return nullptr;
@@ -759,38 +772,32 @@ Mfront* mfront_create(hipStream_t s, DevArena* arena, int V, int n, const int* f
   M->info.crit_flops = P.crit_flops;
   M->info.arena_bytes = (size_t)P.arena_doubles * 8;
   const int nf = (int)P.fronts.size();
+  // the front table and the inverse extend-add maps (mfront_tables: the host plan's own), then the merge kernel's tiles
+  std::vector<long long> ftab;
+  std::vector<int> pinv;
+  mfront_tables(P, &ftab, &pinv);
   std::vector<MfFrontDev> fd(nf);
   for (int f = 0; f < nf; ++f) {
-    const MfFront& F = P.fronts[f];
+    const long long* T = ftab.data() + (size_t)f * kMfFrontCols;
     MfFrontDev& D = fd[f];
-    D.e0 = F.e0;
-    D.own3 = 3 * F.own;
-    D.m = 3 * (F.own + F.nb);
-    D.ld = F.ld;
-    D.off = F.off;
-    D.nb = F.nb;
-    D.bnd_off = F.bnd_off;
-    D.kid[0] = F.kid[0];
-    D.kid[1] = F.kid[1];
-    D.pinv_off[0] = D.pinv_off[1] = 0;
-    D.tgt0 = F.tgt0;
-    D.tgt1 = F.tgt1;
-    D.parent = F.parent;
+    D.e0 = (int)T[0];
+    D.own3 = (int)T[1];
+    D.m = (int)T[2];
+    D.ld = (int)T[3];
+    D.off = T[4];
+    D.nb = (int)T[5];
+    D.bnd_off = (int)T[6];
+    D.kid[0] = (int)T[7];
+    D.kid[1] = (int)T[8];
+    D.pinv_off[0] = (int)T[9];
+    D.pinv_off[1] = (int)T[10];
+    D.tgt0 = (int)T[11];
+    D.tgt1 = (int)T[12];
+    D.parent = (int)T[13];
   }
-  // inverse extend-add maps and the merge kernel's tiles
-  std::vector<int> pinv;
+  M->n_pinv = pinv.size();
   std::vector<int2> mtile;
   M->mtile_ptr.assign((size_t)P.height + 2, 0);
-  for (int f = 0; f < nf; ++f) {
-    const MfFront& F = P.fronts[f];
-    for (int k = 0; k < 2; ++k) {
-      if (F.kid[k] < 0) continue;
-      fd[f].pinv_off[k] = (int)pinv.size();
-      pinv.resize(pinv.size() + (size_t)(F.own + F.nb), -1);
-      const MfFront& C = P.fronts[F.kid[k]];
-      for (int b = 0; b < C.nb; ++b) pinv[(size_t)fd[f].pinv_off[k] + P.cmap[(size_t)F.map_off[k] + b]] = b;
-    }
-  }
   for (int h = 1; h <= P.height; ++h) {
     M->mtile_ptr[h] = (int)mtile.size();
     for (int q = P.level_ptr[h]; q < P.level_ptr[h + 1]; ++q) {
@@ -937,6 +944,7 @@ hipError_t mfront_optimize(Mfront* m, hipStream_t s, const EdgeListDev& el, doub
     hipLaunchKernelGGL(k_mf_update, dim3(ugrid), dim3(kBlock), 0, s, D, d_poses, it);
   }
   hipLaunchKernelGGL(k_mf_finish, dim3(1), dim3(64), 0, s, D, iters, egrid, d_hist, d_res);
+  if (iters > 0) m->ran = true;
   if (D.dbg && iters > 0) {   // diagnostic: phases of the LAST factorisation, per level the front with the longest total
     std::vector<long long> h(8 * P.fronts.size());
     if (hipStreamSynchronize(s) == hipSuccess && hipMemcpy(h.data(), D.dbg, sizeof(long long) * h.size(), hipMemcpyDeviceToHost) == hipSuccess) {
@@ -960,6 +968,77 @@ hipError_t mfront_optimize(Mfront* m, hipStream_t s, const EdgeListDev& el, doub
     }
   }
   return hipGetLastError();
+}
+
+// The plan's arrays by their SGO_MF_* numbers, from the host's copy
+long long mfront_plan_array(const MfPlan& P, int E, int what, void* out, long long cap_bytes) {
+  std::vector<long long> l64;
+  std::vector<int> pinv;
+  const void* src = nullptr;
+  long long bytes = 0;
+  const long long I = sizeof(int);
+  switch (what) {
+    case SGO_MF_INFO:
+      mfront_tables(P, &l64, &pinv);
+      l64 = {P.n, E, (long long)P.fronts.size(), P.height + 1, P.arena_doubles, (long long)pinv.size(), (long long)P.targets.size(),
+             (long long)P.contrib.size()};
+      src = l64.data(); bytes = 8 * (long long)l64.size(); break;
+    case SGO_MF_FRONTS: mfront_tables(P, &l64, &pinv); src = l64.data(); bytes = 8 * (long long)l64.size(); break;
+    case SGO_MF_LEVEL_PTR: src = P.level_ptr.data(); bytes = I * (long long)P.level_ptr.size(); break;
+    case SGO_MF_LEVEL_FRONT: src = P.level_front.data(); bytes = I * (long long)P.level_front.size(); break;
+    case SGO_MF_BND: src = P.bnd.data(); bytes = I * (long long)P.bnd.size(); break;
+    case SGO_MF_PINV: mfront_tables(P, &l64, &pinv); src = pinv.data(); bytes = I * (long long)pinv.size(); break;
+    case SGO_MF_TARGETS: src = P.targets.data(); bytes = (long long)sizeof(MfTarget) * (long long)P.targets.size(); break;
+    case SGO_MF_CONTRIB: src = P.contrib.data(); bytes = I * (long long)P.contrib.size(); break;
+    case SGO_MF_ELIM_VERTEX: src = P.elim_vertex.data(); bytes = I * (long long)P.elim_vertex.size(); break;
+    default: return SGO_EINVAL;
+  }
+  if (bytes == 0 || cap_bytes < bytes) return bytes;
+  std::memcpy(out, src, (size_t)bytes);
+  return bytes;
+}
+
+// The test hook's copy: device memory as stored.  The front table is the one regrouping: MfFrontDev's fields as int64 columns.
+// INFO and LEVEL_PTR have no device copy (the host sizes the launches with them): they come from the host plan.
+long long mfront_debug_array(const Mfront* m, hipStream_t s, int what, void* out, long long cap_bytes) {
+  if (!m->ran) return SGO_ENOTHING;
+  const MfPlan& P = m->plan;
+  const MfDev& D = m->dev;
+  if (what == SGO_MF_INFO || what == SGO_MF_LEVEL_PTR) return mfront_plan_array(P, D.E, what, out, cap_bytes);
+  const void* src = nullptr;
+  long long bytes = 0;
+  const long long I = sizeof(int), F = sizeof(double), n3 = 3 * (long long)D.n;
+  switch (what) {
+    case SGO_MF_FRONTS: bytes = 8 * (long long)kMfFrontCols * D.nfront; break;
+    case SGO_MF_LEVEL_FRONT: src = D.level_front; bytes = I * D.nfront; break;
+    case SGO_MF_BND: src = D.bnd; bytes = I * (long long)P.bnd.size(); break;
+    case SGO_MF_PINV: src = D.pinv; bytes = I * (long long)m->n_pinv; break;
+    case SGO_MF_TARGETS: src = D.targets; bytes = (long long)sizeof(MfTarget) * (long long)P.targets.size(); break;
+    case SGO_MF_CONTRIB: src = D.contrib; bytes = I * (long long)P.contrib.size(); break;
+    case SGO_MF_ELIM_VERTEX: src = D.elim_vertex; bytes = I * D.n; break;
+    case SGO_MF_ELEM: src = D.elem; bytes = F * kElemStride * D.E; break;
+    case SGO_MF_ARENA: src = D.arena; bytes = F * P.arena_doubles; break;
+    case SGO_MF_X: src = D.x; bytes = F * n3; break;
+    case SGO_MF_INVD: src = D.invd; bytes = F * n3; break;
+    case SGO_MF_YINV: src = D.yinv; bytes = F * n3 * kMfPanel; break;
+    case SGO_MF_FLAGS: src = D.flags; bytes = I * 8; break;
+    default: return SGO_EINVAL;
+  }
+  if (bytes == 0 || cap_bytes < bytes) return bytes;
+  if (what == SGO_MF_FRONTS) {
+    std::vector<MfFrontDev> fd((size_t)D.nfront);
+    if (hipMemcpyAsync(fd.data(), D.fronts, sizeof(MfFrontDev) * fd.size(), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
+      return SGO_EHIP;
+    long long* T = static_cast<long long*>(out);
+    for (const MfFrontDev& f : fd) {
+      const long long row[kMfFrontCols] = {f.e0, f.own3, f.m, f.ld, f.off, f.nb, f.bnd_off, f.kid[0], f.kid[1], f.pinv_off[0], f.pinv_off[1],
+                                           f.tgt0, f.tgt1, f.parent};
+      T = std::copy(row, row + kMfFrontCols, T);
+    }
+    return bytes;
+  }
+  if (hipMemcpyAsync(out, src, (size_t)bytes, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) return SGO_EHIP;
+  return bytes;
 }
 
 double mfront_bytes(const Mfront* m, int E, int iters) {

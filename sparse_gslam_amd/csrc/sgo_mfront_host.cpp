@@ -3,6 +3,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <functional>
 #include <numeric>
@@ -469,6 +470,44 @@ bool mfront_analyze(int V, int n, const int* free_id, const double* poses, int E
   if (!have) return no(last_why.empty() ? "no usable row order" : last_why);
   *plan = std::move(best);
   return true;
+}
+
+void mfront_env_limits(MfLimits* lim) {
+  if (const char* e = std::getenv("SGO_MFRONT_LEAF")) lim->leaf = std::max(4, std::atoi(e));
+  if (const char* e = std::getenv("SGO_MFRONT_CRIT_MFLOP")) lim->max_crit_flops = 1e6 * std::atof(e);
+  if (const char* e = std::getenv("SGO_MFRONT_DEGREE")) lim->max_degree = std::atof(e);
+}
+
+// The front table as the device holds it (MfFrontDev of sgo_mfront.hip) in kMfFrontCols int64 columns per front, and the inverse
+// extend-add maps: for child k of front f, pinv[pinv_off[k] + local pose of f] = that pose's index among the child's boundary
+// poses, -1 where the child does not hold it.  One source for mfront_create's upload and the host plan of sgo_mfront_plan_array.
+void mfront_tables(const MfPlan& P, std::vector<long long>* fronts, std::vector<int>* pinv) {
+  const int nf = (int)P.fronts.size();
+  fronts->assign((size_t)nf * kMfFrontCols, 0);
+  pinv->clear();
+  for (int f = 0; f < nf; ++f) {
+    const MfFront& F = P.fronts[f];
+    long long* D = fronts->data() + (size_t)f * kMfFrontCols;
+    D[0] = F.e0;
+    D[1] = 3 * F.own;
+    D[2] = 3 * (F.own + F.nb);
+    D[3] = F.ld;
+    D[4] = F.off;
+    D[5] = F.nb;
+    D[6] = F.bnd_off;
+    D[7] = F.kid[0];
+    D[8] = F.kid[1];
+    D[11] = F.tgt0;
+    D[12] = F.tgt1;
+    D[13] = F.parent;
+    for (int k = 0; k < 2; ++k) {
+      if (F.kid[k] < 0) continue;
+      D[9 + k] = (long long)pinv->size();
+      pinv->resize(pinv->size() + (size_t)(F.own + F.nb), -1);
+      const MfFront& C = P.fronts[F.kid[k]];
+      for (int b = 0; b < C.nb; ++b) (*pinv)[(size_t)D[9 + k] + P.cmap[(size_t)F.map_off[k] + b]] = b;
+    }
+  }
 }
 
 }  // namespace sgo

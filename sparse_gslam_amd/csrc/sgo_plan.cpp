@@ -545,36 +545,45 @@ int sgo_plan_rows(int32_t V, const double* poses, const uint8_t* fixed, int32_t 
   }
 }
 
+// The analysis behind sgo_mfront_plan and sgo_mfront_plan_array: SGO_OK with *P, SGO_ENOTHING (g_err says why) or an error.
+static int mfront_host_plan(const char* name, int32_t V, const double* poses, const uint8_t* fixed, int32_t E, const int32_t* ei,
+                            const int32_t* ej, int32_t leaf, double max_crit_mflop, MfPlan* P, int64_t* n_free) {
+  std::vector<int> deg((size_t)V, 0), free_id;
+  for (int e = 0; e < E; ++e) {
+    if (ei[e] < 0 || ei[e] >= V || ej[e] < 0 || ej[e] >= V || ei[e] == ej[e]) {
+      g_err = std::string(name) + ": bad edge " + std::to_string(e);
+      return SGO_EINVAL;
+    }
+    deg[ei[e]]++;
+    deg[ej[e]]++;
+  }
+  for (int v = 0; v < V; ++v)
+    if (!fixed[v] && deg[v] > 0) free_id.push_back(v);
+  MfLimits lim;
+  lim.max_rows = 1 << 30;
+  mfront_env_limits(&lim);
+  if (leaf > 0) lim.leaf = leaf;
+  if (max_crit_mflop > 0.0) {
+    lim.max_crit_flops = 1e6 * max_crit_mflop;
+    lim.max_degree = 1e9;   // (an explicit budget: analyse whatever the density)
+  }
+  std::string why;
+  if (n_free) *n_free = (int64_t)free_id.size();
+  if (!mfront_analyze(V, (int)free_id.size(), free_id.data(), poses, E, ei, ej, lim, P, &why)) {
+    g_err = why;
+    return SGO_ENOTHING;   // the graph does not qualify (sgo_last_error says why)
+  }
+  return SGO_OK;
+}
+
 int sgo_mfront_plan(int32_t V, const double* poses, const uint8_t* fixed, int32_t E, const int32_t* ei, const int32_t* ej,
                     int32_t leaf, double max_crit_mflop, int64_t* stats, int32_t* elim_vertex, int32_t* front_of_elim) {
   if (V <= 0 || E < 0 || !poses || !fixed || (E > 0 && (!ei || !ej)) || !stats) return SGO_EINVAL;
   try {
-    std::vector<int> deg((size_t)V, 0), free_id;
-    for (int e = 0; e < E; ++e) {
-      if (ei[e] < 0 || ei[e] >= V || ej[e] < 0 || ej[e] >= V || ei[e] == ej[e]) {
-        g_err = "sgo_mfront_plan: bad edge " + std::to_string(e);
-        return SGO_EINVAL;
-      }
-      deg[ei[e]]++;
-      deg[ej[e]]++;
-    }
-    for (int v = 0; v < V; ++v)
-      if (!fixed[v] && deg[v] > 0) free_id.push_back(v);
-    MfLimits lim;
-    lim.max_rows = 1 << 30;
-    if (leaf > 0) lim.leaf = leaf;
-    if (max_crit_mflop > 0.0) {
-      lim.max_crit_flops = 1e6 * max_crit_mflop;
-      lim.max_degree = 1e9;   // (an explicit budget: analyse whatever the density)
-    }
     MfPlan P;
-    std::string why;
     std::memset(stats, 0, sizeof(int64_t) * 12);
-    stats[0] = (int64_t)free_id.size();
-    if (!mfront_analyze(V, (int)free_id.size(), free_id.data(), poses, E, ei, ej, lim, &P, &why)) {
-      g_err = why;
-      return SGO_ENOTHING;   // the graph does not qualify (sgo_last_error says why)
-    }
+    const int rc = mfront_host_plan("sgo_mfront_plan", V, poses, fixed, E, ei, ej, leaf, max_crit_mflop, &P, &stats[0]);
+    if (rc) return rc;
     stats[1] = (int64_t)P.fronts.size();
     stats[2] = P.height + 1;
     stats[3] = P.max_dim;
@@ -593,6 +602,22 @@ int sgo_mfront_plan(int32_t V, const double* poses, const uint8_t* fixed, int32_
     return SGO_OK;
   } catch (const std::bad_alloc&) {
     g_err = "sgo_mfront_plan: out of host memory";
+    return SGO_ENOMEM;
+  }
+}
+
+int64_t sgo_mfront_plan_array(int32_t V, const double* poses, const uint8_t* fixed, int32_t E, const int32_t* ei, const int32_t* ej,
+                              int32_t leaf, double max_crit_mflop, int32_t what, void* out, int64_t cap_bytes) {
+  if (V <= 0 || E < 0 || !poses || !fixed || (E > 0 && (!ei || !ej)) || cap_bytes < 0 || (cap_bytes > 0 && !out)) return SGO_EINVAL;
+  try {
+    MfPlan P;
+    const int rc = mfront_host_plan("sgo_mfront_plan_array", V, poses, fixed, E, ei, ej, leaf, max_crit_mflop, &P, nullptr);
+    if (rc) return rc;
+    const long long r = mfront_plan_array(P, E, what, out, cap_bytes);
+    if (r == SGO_EINVAL) g_err = "sgo_mfront_plan_array: not an array of the plan";
+    return r;
+  } catch (const std::bad_alloc&) {
+    g_err = "sgo_mfront_plan_array: out of host memory";
     return SGO_ENOMEM;
   }
 }
