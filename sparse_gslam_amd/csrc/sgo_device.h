@@ -1,5 +1,5 @@
-// sgo_device.h -- device-side helpers shared by the HIP translation units (wave64 reductions,
-// the wavefront segmented scan, the XCD-aware group walk).
+// sgo_device.h -- device-side helpers shared by the HIP translation units (the arithmetic of EdgeSE2,
+// wave64 reductions, the wavefront segmented scan, the XCD-aware group walk).
 #pragma once
 #include "sgo_internal.h"
 
@@ -18,22 +18,52 @@ __device__ __forceinline__ double norm_theta(double t) {
   return t;
 }
 
+// ---------------------------------------------------------------------------- the arithmetic of EdgeSE2
+// One statement of what every edge kernel evaluates, in layers: operands -> computeError -> Omega e, e^2 and the DCS
+// weight -> the Jacobians of linearizeOplus -> one side's terms of constructQuadraticForm.  k_chi2 stops after the
+// weight; k_linearize and k_ov_lin take all of it (edge_side_terms).  Three kernels share the first layers and keep
+// a contraction of their own, because each rounds differently from edge_side:
+//   k_direct (sgo_direct.hip)        error from its one sincos, weight, Jacobians; then both sides at once, with the
+//                                    Jacobians' constant 0 / +-1 entries folded by hand
+//   k_mf_edges (sgo_mfront.hip)      error, weight; generic 3x3 loops over A, B, Ow A, Ow B; the gradient as -w (A^T (Omega e))
+//   k_row_strength (sgo_kernels.hip) error; e^2 summed entry by entry, generic 3x3 loops, Ow R as w (Omega R)
+// The last two also write the Jacobians' entries out themselves: with full 3x3 arrays under generic loops the compiler
+// shares products between entries (A01 = B10, A10 = B01, ...) only when it sees the expressions in place, and through
+// edge_jacobians it emits other multiplies (7 more in each), which the byte-for-byte equality of a refactor rules out.
+
+// Src: EdgeListDev or EdgeSlotsDev, k an edge or a compact slot of it, ns the component stride of its zinv / info.
+// Poses and inverse measurement of edge k.
+struct EdgeOperands {
+  double xi, yi, ti, xj, yj, tj;                // poses of vertices()[0] and [1]
+  double zx, zy, zt;                            // cached inverse measurement
+};
+template <class Src>
+__device__ __forceinline__ void edge_operands(const Src& s, size_t ns, int k, const double* __restrict__ poses, EdgeOperands& p) {
+  const int vi = s.vi[k], vj = s.vj[k];
+  p.xi = poses[3 * (size_t)vi]; p.yi = poses[3 * (size_t)vi + 1]; p.ti = poses[3 * (size_t)vi + 2];
+  p.xj = poses[3 * (size_t)vj]; p.yj = poses[3 * (size_t)vj + 1]; p.tj = poses[3 * (size_t)vj + 2];
+  p.zx = s.zinv[k]; p.zy = s.zinv[ns + k]; p.zt = s.zinv[2 * ns + k];
+}
+
 // EdgeSE2::computeError with the cached inverse measurement Zi:
 //   e = toVector( Zi * (Xi^-1 * Xj) ),  SE2 algebra literal (g2o SE2::operator* / inverse).
-__device__ __forceinline__ void edge_error(double xi, double yi, double ti, double xj, double yj, double tj,
-                                           double zx, double zy, double zt, double sz, double cz,
-                                           double (&e)[3]) {
-  const double tin = norm_theta(-ti);
+// tin = norm_theta(-ti) with its sine and cosine s1, c1 come from the caller; sz, cz: sine and cosine of zt.
+__device__ __forceinline__ void edge_error_sc(const EdgeOperands& p, double tin, double s1, double c1, double sz, double cz,
+                                              double (&e)[3]) {
+  const double ix = c1 * (-p.xi) - s1 * (-p.yi);
+  const double iy = s1 * (-p.xi) + c1 * (-p.yi);
+  const double dx = ix + c1 * p.xj - s1 * p.yj;
+  const double dy = iy + s1 * p.xj + c1 * p.yj;
+  const double dth = norm_theta(tin + p.tj);
+  e[0] = p.zx + cz * dx - sz * dy;
+  e[1] = p.zy + sz * dx + cz * dy;
+  e[2] = norm_theta(p.zt + dth);
+}
+__device__ __forceinline__ void edge_error(const EdgeOperands& p, double sz, double cz, double (&e)[3]) {
+  const double tin = norm_theta(-p.ti);
   double s1, c1;
   sincos(tin, &s1, &c1);
-  const double ix = c1 * (-xi) - s1 * (-yi);
-  const double iy = s1 * (-xi) + c1 * (-yi);
-  const double dx = ix + c1 * xj - s1 * yj;
-  const double dy = iy + s1 * xj + c1 * yj;
-  const double dth = norm_theta(tin + tj);
-  e[0] = zx + cz * dx - sz * dy;
-  e[1] = zy + sz * dx + cz * dy;
-  e[2] = norm_theta(zt + dth);
+  edge_error_sc(p, tin, s1, c1, sz, cz, e);
 }
 
 // RobustKernelDCS::robustify; phi < 0: no kernel.
@@ -48,6 +78,102 @@ __device__ __forceinline__ void dcs(double e2, double phi, double* rho0, double*
   }
   *rho0 = r0;
   *rho1 = r1;
+}
+
+// The information's upper triangle, Omega e (unscaled), e^2 = e^T Omega e, and the robust kernel's rho0 and weight w = rho1.
+// (The information is loaded here, after the error, not with the operands: held across the error's sincos it costs
+// k_chi2 a step of occupancy.)
+struct EdgeWeight {
+  double o00, o01, o02, o11, o12, o22, oe0, oe1, oe2, e2, rho0, w;
+};
+template <class Src>
+__device__ __forceinline__ void edge_weight(const Src& s, size_t ns, int k, const double (&e)[3], EdgeWeight& W) {
+  W.o00 = s.info[k]; W.o01 = s.info[ns + k]; W.o02 = s.info[2 * ns + k];
+  W.o11 = s.info[3 * ns + k]; W.o12 = s.info[4 * ns + k]; W.o22 = s.info[5 * ns + k];
+  W.oe0 = W.o00 * e[0] + W.o01 * e[1] + W.o02 * e[2];
+  W.oe1 = W.o01 * e[0] + W.o11 * e[1] + W.o12 * e[2];
+  W.oe2 = W.o02 * e[0] + W.o12 * e[1] + W.o22 * e[2];
+  W.e2 = e[0] * W.oe0 + e[1] * W.oe1 + e[2] * W.oe2;
+  dcs(W.e2, s.phi[k], &W.rho0, &W.w);
+}
+
+// EdgeSE2::linearizeOplus: A = d e / d x_i = Rz a, B = d e / d x_j = Rz b (rows: error components), with Rz of the
+// inverse measurement.  The entries not held are constant: A's third row is (0, 0, -1), B's (0, 0, 1), B02 = B12 = 0.
+struct EdgeJac {
+  double A00, A01, A02, A10, A11, A12, B00, B01, B10, B11;
+};
+__device__ __forceinline__ void edge_jacobians(double si, double ci, double sz, double cz, double ddx, double ddy, EdgeJac& J) {
+  const double a02 = -si * ddx + ci * ddy, a12 = -ci * ddx - si * ddy;
+  J.A00 = cz * (-ci) - sz * si; J.A01 = cz * (-si) - sz * (-ci); J.A02 = cz * a02 - sz * a12;
+  J.A10 = sz * (-ci) + cz * si; J.A11 = sz * (-si) + cz * (-ci); J.A12 = sz * a02 + cz * a12;
+  J.B00 = cz * ci - sz * (-si); J.B01 = cz * si - sz * ci;
+  J.B10 = sz * ci + cz * (-si); J.B11 = sz * si + cz * ci;
+}
+__device__ __forceinline__ void edge_jacobians(const EdgeOperands& p, double sz, double cz, EdgeJac& J) {
+  double si, ci;
+  sincos(p.ti, &si, &ci);
+  edge_jacobians(si, ci, sz, cz, p.xj - p.xi, p.yj - p.yi, J);
+}
+
+// BaseBinaryEdge::constructQuadraticForm for the row on one side of the edge (dir 0: vertices()[0], row Jacobian R = A;
+// dir 1: vertices()[1], R = B; column Jacobian C the other one), with robustInformation Ow = w Omega and Omega e scaled
+// by w:  T = Ow R,  D = R^T T (symmetric packing 00 01 02 11 12 22),  g = R^T (Ow e).
+struct EdgeSide {
+  double R00, R01, R02, R10, R11, R12, R22;   // third row (0, 0, R22)
+  double C00, C01, C02, C10, C11, C12, C22;
+  double T00, T01, T02, T10, T11, T12, T20, T21, T22;
+  double D[6], g[3];
+};
+__device__ __forceinline__ void edge_side(const EdgeWeight& W, const EdgeJac& J, bool dir, EdgeSide& S) {
+  const double w = W.w;
+  const double w00 = w * W.o00, w01 = w * W.o01, w02 = w * W.o02, w11 = w * W.o11, w12 = w * W.o12, w22 = w * W.o22;
+  const double oe0 = W.oe0 * w, oe1 = W.oe1 * w, oe2 = W.oe2 * w;
+  S.R00 = dir ? J.B00 : J.A00; S.R01 = dir ? J.B01 : J.A01; S.R02 = dir ? 0.0 : J.A02;
+  S.R10 = dir ? J.B10 : J.A10; S.R11 = dir ? J.B11 : J.A11; S.R12 = dir ? 0.0 : J.A12;
+  S.R22 = dir ? 1.0 : -1.0;
+  S.C00 = dir ? J.A00 : J.B00; S.C01 = dir ? J.A01 : J.B01; S.C02 = dir ? J.A02 : 0.0;
+  S.C10 = dir ? J.A10 : J.B10; S.C11 = dir ? J.A11 : J.B11; S.C12 = dir ? J.A12 : 0.0;
+  S.C22 = dir ? -1.0 : 1.0;
+  // T = Ow * R  (3x3), R has zero entries (2,0),(2,1)
+  S.T00 = w00 * S.R00 + w01 * S.R10; S.T01 = w00 * S.R01 + w01 * S.R11; S.T02 = w00 * S.R02 + w01 * S.R12 + w02 * S.R22;
+  S.T10 = w01 * S.R00 + w11 * S.R10; S.T11 = w01 * S.R01 + w11 * S.R11; S.T12 = w01 * S.R02 + w11 * S.R12 + w12 * S.R22;
+  S.T20 = w02 * S.R00 + w12 * S.R10; S.T21 = w02 * S.R01 + w12 * S.R11; S.T22 = w02 * S.R02 + w12 * S.R12 + w22 * S.R22;
+  S.D[0] = S.R00 * S.T00 + S.R10 * S.T10;
+  S.D[1] = S.R00 * S.T01 + S.R10 * S.T11;
+  S.D[2] = S.R00 * S.T02 + S.R10 * S.T12;
+  S.D[3] = S.R01 * S.T01 + S.R11 * S.T11;
+  S.D[4] = S.R01 * S.T02 + S.R11 * S.T12;
+  S.D[5] = S.R02 * S.T02 + S.R12 * S.T12 + S.R22 * S.T22;
+  S.g[0] = S.R00 * oe0 + S.R10 * oe1;
+  S.g[1] = S.R01 * oe0 + S.R11 * oe1;
+  S.g[2] = S.R02 * oe0 + S.R12 * oe1 + S.R22 * oe2;
+}
+// the off-diagonal block towards the other endpoint, row-major:  R^T Ow C = T^T C  (T^T because Ow is symmetric)
+__device__ __forceinline__ void edge_block(const EdgeSide& S, double (&blk)[9]) {
+  blk[0] = S.T00 * S.C00 + S.T10 * S.C10; blk[1] = S.T00 * S.C01 + S.T10 * S.C11; blk[2] = S.T00 * S.C02 + S.T10 * S.C12 + S.T20 * S.C22;
+  blk[3] = S.T01 * S.C00 + S.T11 * S.C10; blk[4] = S.T01 * S.C01 + S.T11 * S.C11; blk[5] = S.T01 * S.C02 + S.T11 * S.C12 + S.T21 * S.C22;
+  blk[6] = S.T02 * S.C00 + S.T12 * S.C10; blk[7] = S.T02 * S.C01 + S.T12 * S.C11; blk[8] = S.T02 * S.C02 + S.T12 * S.C12 + S.T22 * S.C22;
+}
+// All layers for edge (or slot) k of s, seen from the row on side `dir`.  The caller adds S.D, subtracts S.g and, where it
+// wants the block, calls edge_block.
+template <class Src>
+__device__ __forceinline__ void edge_side_terms(const Src& s, size_t ns, int k, const double* __restrict__ poses, bool dir, EdgeSide& S) {
+  EdgeOperands p;
+  edge_operands(s, ns, k, poses, p);
+  double sz, cz, e[3];
+  sincos(p.zt, &sz, &cz);
+  edge_error(p, sz, cz, e);
+  EdgeWeight W;
+  edge_weight(s, ns, k, e, W);
+  EdgeJac J;
+  edge_jacobians(p, sz, cz, J);
+  edge_side(W, J, dir, S);
+}
+
+// v of lane l (wave-uniform)
+__device__ __forceinline__ double readlane_d(double v, int l) {
+  const int lo = __builtin_amdgcn_readlane(__double2loint(v), l), hi = __builtin_amdgcn_readlane(__double2hiint(v), l);
+  return __hiloint2double(hi, lo);
 }
 
 __device__ __forceinline__ double wave_sum(double v);   // (below, with the DPP helpers)
@@ -224,28 +350,22 @@ __device__ __forceinline__ void load_block(const BsrDev& A, size_t k, double (&b
 // Map (block, wave) -> first group and stride so that XCD x (blocks with blockIdx % 8 == x under
 // the observed round-robin dispatch; speed only, never correctness) walks the contiguous band
 // [x * ngrp / 8, (x + 1) * ngrp / 8) of groups.
-// (nblocks: the workgroups that walk -- a multiple of 8; a launch may carry more behind them with another job)
-__device__ __forceinline__ void group_walk_n(int ngrp, int nblocks, int* first, int* last, int* stride) {
-  const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, per_xcd = nblocks >> 3;
-  const int lo = (int)(((long long)ngrp * xcd) >> 3), hi = (int)(((long long)ngrp * (xcd + 1)) >> 3);
-  *first = lo + slot * kWavesPerBlock + (threadIdx.x >> 6);
-  *last = hi;
-  *stride = per_xcd * kWavesPerBlock;
-}
-// (block: this workgroup's index among the nblocks walkers, when they do not start at blockIdx 0)
-__device__ __forceinline__ void group_walk_b(int ngrp, int nblocks, int block, int* first, int* last, int* stride) {
+// (nblocks: the workgroups that walk -- a multiple of 8; block: this workgroup's index among them.  NB, B: int or unsigned
+// as the caller has them, so that a built-in index keeps its unsigned shift)
+template <class NB, class B>
+__device__ __forceinline__ void group_walk_b(int ngrp, NB nblocks, B block, int* first, int* last, int* stride) {
   const int xcd = block & 7, slot = block >> 3, per_xcd = nblocks >> 3;
   const int lo = (int)(((long long)ngrp * xcd) >> 3), hi = (int)(((long long)ngrp * (xcd + 1)) >> 3);
   *first = lo + slot * kWavesPerBlock + (threadIdx.x >> 6);
   *last = hi;
   *stride = per_xcd * kWavesPerBlock;
 }
+// (the walkers are the launch's first nblocks workgroups; it may carry more behind them with another job)
+__device__ __forceinline__ void group_walk_n(int ngrp, int nblocks, int* first, int* last, int* stride) {
+  group_walk_b(ngrp, nblocks, blockIdx.x, first, last, stride);
+}
 __device__ __forceinline__ void group_walk(int ngrp, int* first, int* last, int* stride) {
-  const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, per_xcd = gridDim.x >> 3;
-  const int lo = (int)(((long long)ngrp * xcd) >> 3), hi = (int)(((long long)ngrp * (xcd + 1)) >> 3);
-  *first = lo + slot * kWavesPerBlock + (threadIdx.x >> 6);
-  *last = hi;
-  *stride = per_xcd * kWavesPerBlock;
+  group_walk_b(ngrp, gridDim.x, blockIdx.x, first, last, stride);
 }
 
 // Body of the wave-group level-0 product k_spmv0 (sgo_kernels.hip; modes and storage described there): the first

@@ -129,57 +129,35 @@ __device__ __forceinline__ void store9g(double* __restrict__ p, const double (&v
   q[3] = make_double2(v[6], v[7]);
   p[8] = v[8];
 }
-__device__ __forceinline__ double readlane_d(double v, int l) {   // l wave-uniform
-  const int lo = __builtin_amdgcn_readlane(__double2loint(v), l), hi = __builtin_amdgcn_readlane(__double2hiint(v), l);
-  return __hiloint2double(hi, lo);
-}
 __device__ __forceinline__ int tri_at(int i, int j) { return i * (i + 1) / 2 + j; }   // i >= j
 
 // Everything an edge contributes at the current poses: rec = Hii(6) bi(3) Hjj(6) bj(3) Hij(9)
-// (EdgeSE2::computeError, linearizeOplus, RobustKernelDCS::robustify, constructQuadraticForm; the arithmetic of
-// k_linearize, with sin / cos of the inverse measurement's angle taken from zsc and sin(-t_i) = -sin(t_i)).
+// (the layers of sgo_device.h up to the Jacobians, with sin / cos of the inverse measurement's angle taken from zsc and
+// sin(-t_i) = -sin(t_i), then constructQuadraticForm for both sides).
 // Returns e2 and rho0 for the chi2 sums.
 __device__ __forceinline__ void edge_terms(const EdgeListDev& el, const double* __restrict__ zsc, int k,
                                            const double* __restrict__ poses, bool jac, double* __restrict__ rec,
                                            double (&hij)[9], double* e2_out, double* rho_out) {
   const size_t E = (size_t)el.E;
-  const int vi = el.vi[k], vj = el.vj[k];
-  const double zx = el.zinv[k], zy = el.zinv[E + k], zt = el.zinv[2 * E + k];
+  EdgeOperands p;
+  edge_operands(el, E, k, poses, p);
   const double sz = zsc[k], cz = zsc[E + k];
-  const double o00 = el.info[k], o01 = el.info[E + k], o02 = el.info[2 * E + k];
-  const double o11 = el.info[3 * E + k], o12 = el.info[4 * E + k], o22 = el.info[5 * E + k];
-  const double ph = el.phi[k];
-  const double xi = poses[3 * (size_t)vi], yi = poses[3 * (size_t)vi + 1], ti = poses[3 * (size_t)vi + 2];
-  const double xj = poses[3 * (size_t)vj], yj = poses[3 * (size_t)vj + 1], tj = poses[3 * (size_t)vj + 2];
-  double si, ci;
-  sincos(ti, &si, &ci);
-  // e = toVector(Zi * (Xi^-1 * Xj)), SE2 algebra as edge_error (sgo_device.h): Xi^-1 = (R(-ti), -R(-ti) t_i)
-  const double tin = norm_theta(-ti);
-  const double s1 = -si, c1 = ci;
-  const double ix = c1 * (-xi) - s1 * (-yi), iy = s1 * (-xi) + c1 * (-yi);
-  const double dx = ix + c1 * xj - s1 * yj, dy = iy + s1 * xj + c1 * yj;
-  const double dth = norm_theta(tin + tj);
-  double e[3];
-  e[0] = zx + cz * dx - sz * dy;
-  e[1] = zy + sz * dx + cz * dy;
-  e[2] = norm_theta(zt + dth);
-  double oe0 = o00 * e[0] + o01 * e[1] + o02 * e[2];
-  double oe1 = o01 * e[0] + o11 * e[1] + o12 * e[2];
-  double oe2 = o02 * e[0] + o12 * e[1] + o22 * e[2];
-  const double e2 = e[0] * oe0 + e[1] * oe1 + e[2] * oe2;
-  double r0, w;
-  dcs(e2, ph, &r0, &w);
-  *e2_out = e2;
-  *rho_out = r0;
+  double si, ci, e[3];
+  sincos(p.ti, &si, &ci);
+  edge_error_sc(p, norm_theta(-p.ti), -si, ci, sz, cz, e);   // Xi^-1 = (R(-ti), -R(-ti) t_i) from the one sincos
+  EdgeWeight W;
+  edge_weight(el, E, k, e, W);
+  *e2_out = W.e2;
+  *rho_out = W.rho0;
   if (!jac) return;
-  const double w00 = w * o00, w01 = w * o01, w02 = w * o02, w11 = w * o11, w12 = w * o12, w22 = w * o22;
-  oe0 *= w; oe1 *= w; oe2 *= w;
-  const double ddx = xj - xi, ddy = yj - yi;
-  const double a02 = -si * ddx + ci * ddy, a12 = -ci * ddx - si * ddy;
-  const double A00 = cz * (-ci) - sz * si, A01 = cz * (-si) - sz * (-ci), A02 = cz * a02 - sz * a12;
-  const double A10 = sz * (-ci) + cz * si, A11 = sz * (-si) + cz * (-ci), A12 = sz * a02 + cz * a12;
-  const double B00 = cz * ci - sz * (-si), B01 = cz * si - sz * ci;
-  const double B10 = sz * ci + cz * (-si), B11 = sz * si + cz * ci;
+  const double w = W.w;
+  const double w00 = w * W.o00, w01 = w * W.o01, w02 = w * W.o02, w11 = w * W.o11, w12 = w * W.o12, w22 = w * W.o22;
+  const double oe0 = W.oe0 * w, oe1 = W.oe1 * w, oe2 = W.oe2 * w;
+  EdgeJac J;
+  edge_jacobians(si, ci, sz, cz, p.xj - p.xi, p.yj - p.yi, J);
+  const double A00 = J.A00, A01 = J.A01, A02 = J.A02, A10 = J.A10, A11 = J.A11, A12 = J.A12;
+  const double B00 = J.B00, B01 = J.B01, B10 = J.B10, B11 = J.B11;
+  // contractions of this kernel's own (sgo_device.h): both sides at once, the Jacobians' constant entries folded
   // TA = Ow A (A's third row is (0, 0, -1)), TB = Ow B (third row (0, 0, 1), B02 = B12 = 0)
   const double TA00 = w00 * A00 + w01 * A10, TA01 = w00 * A01 + w01 * A11, TA02 = w00 * A02 + w01 * A12 - w02;
   const double TA10 = w01 * A00 + w11 * A10, TA11 = w01 * A01 + w11 * A11, TA12 = w01 * A02 + w11 * A12 - w12;

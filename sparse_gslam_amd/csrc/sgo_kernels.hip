@@ -42,35 +42,20 @@ const char* const kKernelNames[K_COUNT] = {
 
 namespace {
 
-struct EdgeLin {
-  double e[3];
-  double e2, rho0, rho1;
-};
-
 // ---------------------------------------------------------------------------- k_chi2
 __device__ __forceinline__ void chi2_range(const EdgeListDev& el, int e0, int e1, const double* __restrict__ poses,
                                            double* __restrict__ e2_out, double (&acc)[2]) {
-  const int E = el.E;
   for (int k = e0 + blockIdx.x * kBlock + threadIdx.x; k < e1; k += gridDim.x * kBlock) {
-    const int vi = el.vi[k], vj = el.vj[k];
-    const double xi = poses[3 * (size_t)vi], yi = poses[3 * (size_t)vi + 1], ti = poses[3 * (size_t)vi + 2];
-    const double xj = poses[3 * (size_t)vj], yj = poses[3 * (size_t)vj + 1], tj = poses[3 * (size_t)vj + 2];
-    const double zx = el.zinv[k], zy = el.zinv[(size_t)E + k], zt = el.zinv[2 * (size_t)E + k];
-    double sz, cz;
-    sincos(zt, &sz, &cz);
-    double e[3];
-    edge_error(xi, yi, ti, xj, yj, tj, zx, zy, zt, sz, cz, e);
-    const double o00 = el.info[k], o01 = el.info[(size_t)E + k], o02 = el.info[2 * (size_t)E + k];
-    const double o11 = el.info[3 * (size_t)E + k], o12 = el.info[4 * (size_t)E + k], o22 = el.info[5 * (size_t)E + k];
-    const double oe0 = o00 * e[0] + o01 * e[1] + o02 * e[2];
-    const double oe1 = o01 * e[0] + o11 * e[1] + o12 * e[2];
-    const double oe2 = o02 * e[0] + o12 * e[1] + o22 * e[2];
-    const double e2 = e[0] * oe0 + e[1] * oe1 + e[2] * oe2;
-    double r0, r1;
-    dcs(e2, el.phi[k], &r0, &r1);
-    if (e2_out) e2_out[k] = e2;
-    acc[0] += e2;
-    acc[1] += r0;
+    EdgeOperands p;
+    edge_operands(el, (size_t)el.E, k, poses, p);
+    double sz, cz, e[3];
+    sincos(p.zt, &sz, &cz);
+    edge_error(p, sz, cz, e);
+    EdgeWeight W;
+    edge_weight(el, (size_t)el.E, k, e, W);
+    if (e2_out) e2_out[k] = W.e2;
+    acc[0] += W.e2;
+    acc[1] += W.rho0;
   }
 }
 // edges [e0, e1) of el, then the first el2.cnt edges of el2 (an empty list when there is no overlay)
@@ -132,7 +117,9 @@ __global__ __launch_bounds__(kBlock) void k_slot_expand(int k0, int k1, const in
 // the matrix.  This kernel produces them straight from the edge list and the per-row slot lists -- before the level-0
 // storage (tiles, slot types) exists -- so that the host's aggregation and symbolic phase can run on a helper thread
 // while the storage is still being laid out (sgo_structure.cpp, build_structure).  One thread per row walks the row's
-// compact slots (edge, side) and evaluates each edge as k_linearize does: w of the row's logical slots -- the diagonal
+// compact slots (edge, side) and evaluates each edge with the error and the Jacobians k_linearize uses (sgo_device.h) but
+// with generic 3x3 loops of its own for e^2, Ow R = w (Omega R) and the products: the norms agree with those of
+// k_linearize's blocks to rounding, not to the bit.  w of the row's logical slots -- the diagonal
 // slot first (norm of the summed R^T Ow R), then ||R^T Ow C||_F for every slot whose column is free.
 __global__ __launch_bounds__(kBlock) void k_row_strength(int n, const int* __restrict__ rowptr, const int* __restrict__ eidx,
                                                          const unsigned char* __restrict__ flags, const int* __restrict__ hrowptr,
@@ -143,27 +130,25 @@ __global__ __launch_bounds__(kBlock) void k_row_strength(int n, const int* __res
     int q = hrowptr[r] + 1;
     for (int k = rowptr[r]; k < rowptr[r + 1]; ++k) {
       const int e = eidx[k], fl = flags[k];
-      const int vi = el.vi[e], vj = el.vj[e];
-      const double xi = poses[3 * (size_t)vi], yi = poses[3 * (size_t)vi + 1], ti = poses[3 * (size_t)vi + 2];
-      const double xj = poses[3 * (size_t)vj], yj = poses[3 * (size_t)vj + 1], tj = poses[3 * (size_t)vj + 2];
-      const double zx = el.zinv[e], zy = el.zinv[E + e], zt = el.zinv[2 * E + e];
-      double sz, cz;
-      sincos(zt, &sz, &cz);
-      double er[3];
-      edge_error(xi, yi, ti, xj, yj, tj, zx, zy, zt, sz, cz, er);
+      EdgeOperands p;
+      edge_operands(el, E, e, poses, p);
+      double sz, cz, er[3];
+      sincos(p.zt, &sz, &cz);
+      edge_error(p, sz, cz, er);
       double O[3][3];
       O[0][0] = el.info[e]; O[0][1] = O[1][0] = el.info[E + e]; O[0][2] = O[2][0] = el.info[2 * E + e];
       O[1][1] = el.info[3 * E + e]; O[1][2] = O[2][1] = el.info[4 * E + e]; O[2][2] = el.info[5 * E + e];
-      double e2 = 0.0;
+      double e2 = 0.0;   // (entry by entry: not edge_weight's e . (Omega e), whose last bits differ)
 #pragma unroll
       for (int a = 0; a < 3; ++a)
 #pragma unroll
         for (int b = 0; b < 3; ++b) e2 += er[a] * O[a][b] * er[b];
       double r0_, wt;
       dcs(e2, el.phi[e], &r0_, &wt);
+      // (the Jacobians written out here, not through edge_jacobians: sgo_device.h says why)
       double si, ci;
-      sincos(ti, &si, &ci);
-      const double ddx = xj - xi, ddy = yj - yi;
+      sincos(p.ti, &si, &ci);
+      const double ddx = p.xj - p.xi, ddy = p.yj - p.yi;
       const double a02 = -si * ddx + ci * ddy, a12 = -ci * ddx - si * ddy;
       double A[3][3], B[3][3];
       A[0][0] = cz * (-ci) - sz * si; A[0][1] = cz * (-si) - sz * (-ci); A[0][2] = cz * a02 - sz * a12;
@@ -234,73 +219,26 @@ __global__ __launch_bounds__(kBlock) void k_linearize(Sym0Dev A, int g0, int g1,
       row = r0 + (m & 63);
       const int fl = es.flags[k];
       if (fl & kSlotNoEdge) continue;
-      const int vi = es.vi[k], vj = es.vj[k];
-      const double xi = poses[3 * (size_t)vi], yi = poses[3 * (size_t)vi + 1], ti = poses[3 * (size_t)vi + 2];
-      const double xj = poses[3 * (size_t)vj], yj = poses[3 * (size_t)vj + 1], tj = poses[3 * (size_t)vj + 2];
-      const double zx = es.zinv[k], zy = es.zinv[ns + k], zt = es.zinv[2 * ns + k];
-      double sz, cz;
-      sincos(zt, &sz, &cz);
-      double e[3];
-      edge_error(xi, yi, ti, xj, yj, tj, zx, zy, zt, sz, cz, e);
-      const double o00 = es.info[k], o01 = es.info[ns + k], o02 = es.info[2 * ns + k];
-      const double o11 = es.info[3 * ns + k], o12 = es.info[4 * ns + k], o22 = es.info[5 * ns + k];
-      double oe0 = o00 * e[0] + o01 * e[1] + o02 * e[2];
-      double oe1 = o01 * e[0] + o11 * e[1] + o12 * e[2];
-      double oe2 = o02 * e[0] + o12 * e[1] + o22 * e[2];
-      const double e2 = e[0] * oe0 + e[1] * oe1 + e[2] * oe2;
-      double r0_, w;
-      dcs(e2, es.phi[k], &r0_, &w);
-      // robustInformation: Ow = rho1 * Omega ; omega_r scaled by rho1
-      const double w00 = w * o00, w01 = w * o01, w02 = w * o02, w11 = w * o11, w12 = w * o12, w22 = w * o22;
-      oe0 *= w; oe1 *= w; oe2 *= w;
-      // EdgeSE2::linearizeOplus: A = Rz a, B = Rz b  (third rows (0,0,-1) and (0,0,1))
-      double si, ci;
-      sincos(ti, &si, &ci);
-      const double ddx = xj - xi, ddy = yj - yi;
-      const double a02 = -si * ddx + ci * ddy, a12 = -ci * ddx - si * ddy;
-      const double A00 = cz * (-ci) - sz * si, A01 = cz * (-si) - sz * (-ci), A02 = cz * a02 - sz * a12;
-      const double A10 = sz * (-ci) + cz * si, A11 = sz * (-si) + cz * (-ci), A12 = sz * a02 + cz * a12;
-      const double B00 = cz * ci - sz * (-si), B01 = cz * si - sz * ci;
-      const double B10 = sz * ci + cz * (-si), B11 = sz * si + cz * ci;
-      const bool dir = fl & kSlotDir;
-      // row / column Jacobians (row-major), third row is (0,0,s3)
-      const double R00 = dir ? B00 : A00, R01 = dir ? B01 : A01, R02 = dir ? 0.0 : A02;
-      const double R10 = dir ? B10 : A10, R11 = dir ? B11 : A11, R12 = dir ? 0.0 : A12;
-      const double R22 = dir ? 1.0 : -1.0;
-      // T = Ow * R  (3x3), R has zero entries (2,0),(2,1)
-      const double T00 = w00 * R00 + w01 * R10, T01 = w00 * R01 + w01 * R11, T02 = w00 * R02 + w01 * R12 + w02 * R22;
-      const double T10 = w01 * R00 + w11 * R10, T11 = w01 * R01 + w11 * R11, T12 = w01 * R02 + w11 * R12 + w12 * R22;
-      const double T20 = w02 * R00 + w12 * R10, T21 = w02 * R01 + w12 * R11, T22 = w02 * R02 + w12 * R12 + w22 * R22;
-      // D = R^T T (symmetric): d00 d01 d02 d11 d12 d22
-      acc[0] += R00 * T00 + R10 * T10;
-      acc[1] += R00 * T01 + R10 * T11;
-      acc[2] += R00 * T02 + R10 * T12;
-      acc[3] += R01 * T01 + R11 * T11;
-      acc[4] += R01 * T02 + R11 * T12;
-      acc[5] += R02 * T02 + R12 * T12 + R22 * T22;
-      // b = -R^T (Ow e)
-      acc[6] -= R00 * oe0 + R10 * oe1;
-      acc[7] -= R01 * oe0 + R11 * oe1;
-      acc[8] -= R02 * oe0 + R12 * oe1 + R22 * oe2;
+      EdgeSide S;
+      edge_side_terms(es, ns, k, poses, (fl & kSlotDir) != 0, S);
+#pragma unroll
+      for (int c = 0; c < 6; ++c) acc[c] += S.D[c];
+#pragma unroll
+      for (int c = 0; c < 3; ++c) acc[6 + c] -= S.g[c];   // b = -R^T (Ow e)
       if (owned) {
-        // off-diagonal block  R^T Ow C = T^T C   (T^T because Ow is symmetric: R^T Ow = (Ow R)^T)
-        const double C00 = dir ? A00 : B00, C01 = dir ? A01 : B01, C02 = dir ? A02 : 0.0;
-        const double C10 = dir ? A10 : B10, C11 = dir ? A11 : B11, C12 = dir ? A12 : 0.0;
-        const double C22 = dir ? -1.0 : 1.0;
+        double h[9];
+        edge_block(S, h);
         double2* __restrict__ bp = reinterpret_cast<double2*>(A.ublk);
-        bp[idx] = make_double2(T00 * C00 + T10 * C10, T00 * C01 + T10 * C11);
-        bp[nu + idx] = make_double2(T00 * C02 + T10 * C12 + T20 * C22, T01 * C00 + T11 * C10);
-        bp[2 * nu + idx] = make_double2(T01 * C01 + T11 * C11, T01 * C02 + T11 * C12 + T21 * C22);
-        bp[3 * nu + idx] = make_double2(T02 * C00 + T12 * C10, T02 * C01 + T12 * C11);
-        const double b8 = T02 * C02 + T12 * C12 + T22 * C22;
-        A.ublk8[idx] = b8;
+        bp[idx] = make_double2(h[0], h[1]);
+        bp[nu + idx] = make_double2(h[2], h[3]);
+        bp[2 * nu + idx] = make_double2(h[4], h[5]);
+        bp[3 * nu + idx] = make_double2(h[6], h[7]);
+        A.ublk8[idx] = h[8];
         if (A.fblk) {   // fp32 copy for the preconditioner's passes
           float4* __restrict__ fp = reinterpret_cast<float4*>(A.fblk);
-          fp[idx] = make_float4((float)(T00 * C00 + T10 * C10), (float)(T00 * C01 + T10 * C11),
-                                (float)(T00 * C02 + T10 * C12 + T20 * C22), (float)(T01 * C00 + T11 * C10));
-          fp[nu + idx] = make_float4((float)(T01 * C01 + T11 * C11), (float)(T01 * C02 + T11 * C12 + T21 * C22),
-                                     (float)(T02 * C00 + T12 * C10), (float)(T02 * C01 + T12 * C11));
-          A.fblk8[idx] = (float)b8;
+          fp[idx] = make_float4((float)h[0], (float)h[1], (float)h[2], (float)h[3]);
+          fp[nu + idx] = make_float4((float)h[4], (float)h[5], (float)h[6], (float)h[7]);
+          A.fblk8[idx] = (float)h[8];
         }
       }
     }

@@ -64,11 +64,6 @@ struct MfDev {
 
 typedef double mf_d4 __attribute__((ext_vector_type(4)));
 
-__device__ __forceinline__ double mf_readlane(double v, int l) {   // l wave-uniform
-  const int lo = __builtin_amdgcn_readlane(__double2loint(v), l), hi = __builtin_amdgcn_readlane(__double2hiint(v), l);
-  return __hiloint2double(hi, lo);
-}
-
 // acc += sum_{k < K} L[ra][k] L[rb][k] for the 16 x 16 tile whose operand rows this lane addresses through pa / pb (= the
 // front's matrix + (lane >> 4) * ld + row: rows beyond the front are CLAMPED by the caller, not masked -- a tile element
 // depends on its own row and column only, the caller does not store the others).  The loads of eight (then four) MFMA steps
@@ -136,33 +131,28 @@ __global__ __launch_bounds__(kBlock) void k_mf_edges(MfDev M, EdgeListDev el, co
   const size_t ns = (size_t)el.E;
   double acc[2] = {0.0, 0.0};
   for (int e = blockIdx.x * kBlock + threadIdx.x; e < M.E; e += gridDim.x * kBlock) {
-    const int vi = el.vi[e], vj = el.vj[e];
-    const double xi = poses[3 * (size_t)vi], yi = poses[3 * (size_t)vi + 1], ti = poses[3 * (size_t)vi + 2];
-    const double xj = poses[3 * (size_t)vj], yj = poses[3 * (size_t)vj + 1], tj = poses[3 * (size_t)vj + 2];
-    const double zx = el.zinv[e], zy = el.zinv[ns + e], zt = el.zinv[2 * ns + e];
-    double sz, cz;
-    sincos(zt, &sz, &cz);
-    double er[3];
-    edge_error(xi, yi, ti, xj, yj, tj, zx, zy, zt, sz, cz, er);
-    const double o00 = el.info[e], o01 = el.info[ns + e], o02 = el.info[2 * ns + e];
-    const double o11 = el.info[3 * ns + e], o12 = el.info[4 * ns + e], o22 = el.info[5 * ns + e];
-    double oe[3] = {o00 * er[0] + o01 * er[1] + o02 * er[2], o01 * er[0] + o11 * er[1] + o12 * er[2], o02 * er[0] + o12 * er[1] + o22 * er[2]};
-    const double e2 = er[0] * oe[0] + er[1] * oe[1] + er[2] * oe[2];
-    double r0, w;
-    dcs(e2, el.phi[e], &r0, &w);
-    acc[0] += e2;
-    acc[1] += r0;
+    EdgeOperands p;
+    edge_operands(el, ns, e, poses, p);
+    double sz, cz, er[3];
+    sincos(p.zt, &sz, &cz);
+    edge_error(p, sz, cz, er);
+    EdgeWeight Wt;
+    edge_weight(el, ns, e, er, Wt);
+    acc[0] += Wt.e2;
+    acc[1] += Wt.rho0;
     if (chi2_only) continue;
-    // EdgeSE2::linearizeOplus: A = d e / d x_i, B = d e / d x_j (rows: error components), with Rz of the inverse measurement
+    // Jacobians and contractions of this kernel's own (sgo_device.h says why): generic loops over the full 3x3 matrices,
+    // Omega e scaled last
+    const double w = Wt.w, oe[3] = {Wt.oe0, Wt.oe1, Wt.oe2};
     double si, ci;
-    sincos(ti, &si, &ci);
-    const double ddx = xj - xi, ddy = yj - yi;
+    sincos(p.ti, &si, &ci);
+    const double ddx = p.xj - p.xi, ddy = p.yj - p.yi;
     const double a02 = -si * ddx + ci * ddy, a12 = -ci * ddx - si * ddy;
     const double A[3][3] = {{cz * (-ci) - sz * si, cz * (-si) - sz * (-ci), cz * a02 - sz * a12},
                             {sz * (-ci) + cz * si, sz * (-si) + cz * (-ci), sz * a02 + cz * a12},
                             {0.0, 0.0, -1.0}};
     const double B[3][3] = {{cz * ci - sz * (-si), cz * si - sz * ci, 0.0}, {sz * ci + cz * (-si), sz * si + cz * ci, 0.0}, {0.0, 0.0, 1.0}};
-    const double W[3][3] = {{w * o00, w * o01, w * o02}, {w * o01, w * o11, w * o12}, {w * o02, w * o12, w * o22}};
+    const double W[3][3] = {{w * Wt.o00, w * Wt.o01, w * Wt.o02}, {w * Wt.o01, w * Wt.o11, w * Wt.o12}, {w * Wt.o02, w * Wt.o12, w * Wt.o22}};
     double WA[3][3], WB[3][3];
 #pragma unroll
     for (int a = 0; a < 3; ++a)
@@ -403,9 +393,9 @@ __global__ __launch_bounds__(kMfThreads) void k_mf_panels(MfDev M, int lvl0, int
 #pragma unroll
           for (int jj = kHand; jj < kHalf; ++jj)
 #pragma unroll
-            for (int c = kHalf; c < kMfPanel; ++c) a[c] -= a[jj] * mf_readlane(a[jj], c);
+            for (int c = kHalf; c < kMfPanel; ++c) a[c] -= a[jj] * readlane_d(a[jj], c);
         }
-        const double d = mf_readlane(a[j], j);
+        const double d = readlane_d(a[j], j);
         ok = ok && d > 0.0 && isfinite(d);
         double inv = mf_rsqrt(d);
         if (!(inv > 0.0) || !isfinite(inv)) inv = 1.0;   // (a failed pivot: the followers wait for a NON-ZERO reciprocal; the call fails after the barrier)
@@ -415,7 +405,7 @@ __global__ __launch_bounds__(kMfThreads) void k_mf_panels(MfDev M, int lvl0, int
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");   // (compiler ordering only: the hardware keeps a wave's LDS stores in order)
         if (lane == 0) __hip_atomic_store(&LI[j], inv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 #pragma unroll
-        for (int c = j + 1; c < (j < kHalf ? kHalf : kMfPanel); ++c) a[c] -= lij * mf_readlane(lij, c);
+        for (int c = j + 1; c < (j < kHalf ? kHalf : kMfPanel); ++c) a[c] -= lij * readlane_d(lij, c);
         __builtin_amdgcn_sched_barrier(0);   // (pivots are sequential anyway; without it the scheduler hoists the broadcasts of several steps and spills scalar registers)
       }
       if (!ok && lane == 0) s_fail = 1;   // (the factor block goes to memory from LX, by wave 2)
@@ -436,10 +426,10 @@ __global__ __launch_bounds__(kMfThreads) void k_mf_panels(MfDev M, int lvl0, int
         if (i == j) myinv = inv;
         if (lowc) {
 #pragma unroll
-          for (int c = 0; c <= (j < kInvCut - 1 ? j : kInvCut - 1); ++c) y[c] -= lm * mf_readlane(y[c], j);
+          for (int c = 0; c <= (j < kInvCut - 1 ? j : kInvCut - 1); ++c) y[c] -= lm * readlane_d(y[c], j);
         } else {
 #pragma unroll
-          for (int c = kInvCut; c <= j; ++c) y[c] -= lm * mf_readlane(y[c], j);
+          for (int c = kInvCut; c <= j; ++c) y[c] -= lm * readlane_d(y[c], j);
         }
         __builtin_amdgcn_sched_barrier(0);
       }
@@ -472,7 +462,7 @@ __global__ __launch_bounds__(kMfThreads) void k_mf_panels(MfDev M, int lvl0, int
         double lij, inv;
         follow(j, i, lij, inv);
 #pragma unroll
-        for (int c = 0; c < kHalf; ++c) bq[c] -= lij * mf_readlane(lij, c + kHalf);
+        for (int c = 0; c < kHalf; ++c) bq[c] -= lij * readlane_d(lij, c + kHalf);
         __builtin_amdgcn_sched_barrier(0);
       }
       if (lane < kMfPanel) {
@@ -632,7 +622,7 @@ __global__ __launch_bounds__(kMfThreads) void k_mf_solve(MfDev M, int lvl0) {
       double t = 0.0;
 #pragma unroll
       for (int r = 0; r < kMfPanel; ++r)
-        if (r < wp) t += Yl[(c0 + r) * kMfPanel + i] * mf_readlane(tv, r);   // (L^-1)[r][i] is zero for i > r
+        if (r < wp) t += Yl[(c0 + r) * kMfPanel + i] * readlane_d(tv, r);   // (L^-1)[r][i] is zero for i > r
       if (lane < wp) {
         xs[c0 + lane] = t;
         M.x[3 * (size_t)F.e0 + c0 + lane] = t;
@@ -676,7 +666,7 @@ __global__ __launch_bounds__(kMfThreads) void k_mf_solve(MfDev M, int lvl0) {
 #pragma unroll
       for (int r = kMfPanel - 1; r >= 0; --r) {
         if (r < wp) {   // uniform
-          const double xr = mf_readlane(t, r) * M.invd[3 * (size_t)F.e0 + c0 + r];
+          const double xr = readlane_d(t, r) * M.invd[3 * (size_t)F.e0 + c0 + r];
           if (i < r) t -= Ld[r * (kMfPanel + 1) + i] * xr;
           else if (i == r) t = xr;
         }

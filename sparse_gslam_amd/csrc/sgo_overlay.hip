@@ -17,59 +17,16 @@ static_assert(kOvCols <= kOvThreads, "one right-hand-side column per thread");
 static_assert(3 * kOvMaxHubs * (3 * kOvMaxTouched + 1) <= 3 * kOvTile * kOvCols, "the hubs' Gauss-Jordan tableau lives in the elimination's LDS tile");
 
 // What edge e contributes to the row on its `side` (0: vertices()[0], Jacobian A; 1: vertices()[1], Jacobian B):
-// D += R^T Ow R (symmetric packing), b -= R^T Ow e, blk = R^T Ow C (block towards the other endpoint).  The arithmetic of
-// k_linearize (EdgeSE2::computeError, linearizeOplus, RobustKernelDCS::robustify, constructQuadraticForm).
+// D += R^T Ow R (symmetric packing), b -= R^T Ow e, blk = R^T Ow C (block towards the other endpoint).
 __device__ __forceinline__ void ov_edge_terms(const EdgeListDev& el, int e, int side, const double* __restrict__ poses,
                                               double (&D)[6], double (&b)[3], double (&blk)[9]) {
-  const size_t ns = (size_t)el.E;
-  const int vi = el.vi[e], vj = el.vj[e];
-  const double xi = poses[3 * (size_t)vi], yi = poses[3 * (size_t)vi + 1], ti = poses[3 * (size_t)vi + 2];
-  const double xj = poses[3 * (size_t)vj], yj = poses[3 * (size_t)vj + 1], tj = poses[3 * (size_t)vj + 2];
-  const double zx = el.zinv[e], zy = el.zinv[ns + e], zt = el.zinv[2 * ns + e];
-  double sz, cz;
-  sincos(zt, &sz, &cz);
-  double er[3];
-  edge_error(xi, yi, ti, xj, yj, tj, zx, zy, zt, sz, cz, er);
-  const double o00 = el.info[e], o01 = el.info[ns + e], o02 = el.info[2 * ns + e];
-  const double o11 = el.info[3 * ns + e], o12 = el.info[4 * ns + e], o22 = el.info[5 * ns + e];
-  double oe0 = o00 * er[0] + o01 * er[1] + o02 * er[2];
-  double oe1 = o01 * er[0] + o11 * er[1] + o12 * er[2];
-  double oe2 = o02 * er[0] + o12 * er[1] + o22 * er[2];
-  const double e2 = er[0] * oe0 + er[1] * oe1 + er[2] * oe2;
-  double r0_, w;
-  dcs(e2, el.phi[e], &r0_, &w);
-  const double w00 = w * o00, w01 = w * o01, w02 = w * o02, w11 = w * o11, w12 = w * o12, w22 = w * o22;
-  oe0 *= w; oe1 *= w; oe2 *= w;
-  double si, ci;
-  sincos(ti, &si, &ci);
-  const double ddx = xj - xi, ddy = yj - yi;
-  const double a02 = -si * ddx + ci * ddy, a12 = -ci * ddx - si * ddy;
-  const double A00 = cz * (-ci) - sz * si, A01 = cz * (-si) - sz * (-ci), A02 = cz * a02 - sz * a12;
-  const double A10 = sz * (-ci) + cz * si, A11 = sz * (-si) + cz * (-ci), A12 = sz * a02 + cz * a12;
-  const double B00 = cz * ci - sz * (-si), B01 = cz * si - sz * ci;
-  const double B10 = sz * ci + cz * (-si), B11 = sz * si + cz * ci;
-  const bool dir = side != 0;
-  const double R00 = dir ? B00 : A00, R01 = dir ? B01 : A01, R02 = dir ? 0.0 : A02;
-  const double R10 = dir ? B10 : A10, R11 = dir ? B11 : A11, R12 = dir ? 0.0 : A12;
-  const double R22 = dir ? 1.0 : -1.0;
-  const double T00 = w00 * R00 + w01 * R10, T01 = w00 * R01 + w01 * R11, T02 = w00 * R02 + w01 * R12 + w02 * R22;
-  const double T10 = w01 * R00 + w11 * R10, T11 = w01 * R01 + w11 * R11, T12 = w01 * R02 + w11 * R12 + w12 * R22;
-  const double T20 = w02 * R00 + w12 * R10, T21 = w02 * R01 + w12 * R11, T22 = w02 * R02 + w12 * R12 + w22 * R22;
-  D[0] += R00 * T00 + R10 * T10;
-  D[1] += R00 * T01 + R10 * T11;
-  D[2] += R00 * T02 + R10 * T12;
-  D[3] += R01 * T01 + R11 * T11;
-  D[4] += R01 * T02 + R11 * T12;
-  D[5] += R02 * T02 + R12 * T12 + R22 * T22;
-  b[0] -= R00 * oe0 + R10 * oe1;
-  b[1] -= R01 * oe0 + R11 * oe1;
-  b[2] -= R02 * oe0 + R12 * oe1 + R22 * oe2;
-  const double C00 = dir ? A00 : B00, C01 = dir ? A01 : B01, C02 = dir ? A02 : 0.0;
-  const double C10 = dir ? A10 : B10, C11 = dir ? A11 : B11, C12 = dir ? A12 : 0.0;
-  const double C22 = dir ? -1.0 : 1.0;
-  blk[0] = T00 * C00 + T10 * C10; blk[1] = T00 * C01 + T10 * C11; blk[2] = T00 * C02 + T10 * C12 + T20 * C22;
-  blk[3] = T01 * C00 + T11 * C10; blk[4] = T01 * C01 + T11 * C11; blk[5] = T01 * C02 + T11 * C12 + T21 * C22;
-  blk[6] = T02 * C00 + T12 * C10; blk[7] = T02 * C01 + T12 * C11; blk[8] = T02 * C02 + T12 * C12 + T22 * C22;
+  EdgeSide S;
+  edge_side_terms(el, (size_t)el.E, e, poses, side != 0, S);
+#pragma unroll
+  for (int q = 0; q < 6; ++q) D[q] += S.D[q];
+#pragma unroll
+  for (int q = 0; q < 3; ++q) b[q] -= S.g[q];
+  edge_block(S, blk);
 }
 
 // ---------------------------------------------------------------------------- k_ov_lin
