@@ -500,6 +500,55 @@ int sgo_debug_overlay_apply(sgo_ctx* ctx, const double* x, double* y, double* do
 int64_t sgo_debug_mfront_array(sgo_ctx* ctx, int32_t what, void* out, int64_t cap_bytes);
 int64_t sgo_mfront_plan_array(int32_t V, const double* poses, const uint8_t* fixed, int32_t E, const int32_t* ei, const int32_t* ej,
                               int32_t leaf, double max_crit_mflop, int32_t what, void* out, int64_t cap_bytes);
+/* Test hooks for the PCG recurrence (tests/pcg_reference.py checks every stage of one iteration and of the start from them).
+ * Both need sgo_linearize and refuse a multi-GPU context and an active overlay, as the sibling hooks do.
+ * sgo_debug_pcg_array: a read-only copy of one array of the recurrence as the last start / solve left it -- device memory as
+ *   stored, nothing recomputed.  Same convention as sgo_debug_amg_array: returns the array's size in bytes (0: no such array
+ *   here) and copies it when cap_bytes holds it.  `what` is one of SGO_PCG_*:
+ *   B X R Z P Q   double[n][3], rows in the internal order (ROW_ORDER int32[n]: the internal row of every hessian-order row)
+ *   DINV          double[n][6], the block-diagonal inverse (upper triangle by rows);  XS0 double[n][3], the cycle's first sweep
+ *                 from zero, omega Dinv r (0 bytes without a hierarchy)
+ *   SCALARS       the device's PcgScalars, 104 bytes: doubles rz, pq, rr, bb, alpha, beta, tol2, rz_prev at 0, 8, .. 56; int32
+ *                 iter, maxit, stop, iter_prev, probe_k, (pad) at 64 .. 84; doubles probe_rel, probe_max at 88, 96.
+ *                 HOST_SCALARS: the host copy the last solve returned with;  MIRROR: the pinned copy k_update_p rewrites
+ *                 (both undefined before the first solve on the context: sgo_linearize alone writes neither)
+ *   PARTIALS      double[3][2048], the partial-sum rows as stored;  ZPARTS double[2][2048], the cycle's (0 bytes without a
+ *                 hierarchy);  COUNTS int32[8] { start_bb, start_rz, n_pq, n_rz, n_rr, n_zq, n_xq, n_bx }: how many entries
+ *                 of a row the latest launches wrote.  After a start: b.b = PARTIALS[1][0 .. start_bb); r.z = PARTIALS[0]
+ *                 (block-Jacobi) or ZPARTS[0] (multigrid) [0 .. start_rz); a warm start's x_prev . H x_prev = PARTIALS[0]
+ *                 [0 .. n_xq) and b . x_prev = PARTIALS[2][0 .. n_bx) (that product stores over PARTIALS[1] too: b.b was
+ *                 reduced before it).  After an iteration: p.q = PARTIALS[0][0 .. n_pq);
+ *                 r.r = PARTIALS[2][0 .. n_rr); r.z = PARTIALS[1] (block-Jacobi) or ZPARTS[0] (multigrid) [0 .. n_rz);
+ *                 z.q = ZPARTS[1][0 .. n_zq) (n_zq = 0: block-Jacobi, plain beta).  The iteration's counts are those of the
+ *                 latest launch or capture of an iteration (a replayed hipGraph keeps them).
+ *   START_ARGS    double[4] { tol, tol_cap, bb_ref, maxit }: what the last start handed to k_init_scalars (host bookkeeping)
+ *   LANCZOS       double[min(iter, 2048)][3] { alpha, beta, rz_prev } per iteration (0 bytes unless SGO_LANCZOS was set)
+ * sgo_debug_pcg_run: sgo_solve with the per-call fields sgo_optimize_gn sets for the solves of a call: an iteration cap
+ *   (maxit > 0; maxit == 0: the start state alone, no iteration runs), a warm start from x_prev[n][3] (hessian order; NULL:
+ *   cold), the absolute-tolerance reference bb_ref = |b|^2 of a call's first solve (0: relative tolerance) with the cap
+ *   derived from sgo_opts.pcg_tol_cap as sgo_optimize_gn derives it, and the progress probe (probe_k = 0: none; probe_max = 0:
+ *   record only; probe_max > 0 keeps the coarse operators as a lagged solve does).  The warm start and the probe need a
+ *   multigrid hierarchy.  The fields are restored afterwards.  Returns the iterations run; a breakdown (stop == 3) is read
+ *   from the scalars, not from the return value. */
+#define SGO_PCG_B 0
+#define SGO_PCG_X 1
+#define SGO_PCG_R 2
+#define SGO_PCG_Z 3
+#define SGO_PCG_P 4
+#define SGO_PCG_Q 5
+#define SGO_PCG_DINV 6
+#define SGO_PCG_XS0 7
+#define SGO_PCG_SCALARS 8
+#define SGO_PCG_HOST_SCALARS 9
+#define SGO_PCG_MIRROR 10
+#define SGO_PCG_PARTIALS 11
+#define SGO_PCG_ZPARTS 12
+#define SGO_PCG_COUNTS 13
+#define SGO_PCG_LANCZOS 14
+#define SGO_PCG_ROW_ORDER 15
+#define SGO_PCG_START_ARGS 16
+int64_t sgo_debug_pcg_array(sgo_ctx* ctx, int32_t what, void* out, int64_t cap_bytes);
+int sgo_debug_pcg_run(sgo_ctx* ctx, int32_t maxit, const double* x_prev, double bb_ref, int32_t probe_k, double probe_max);
 /* Diagnostic (env SGO_LANCZOS=1 when the graph is set): alpha, beta of every PCG iteration of the last solve as pairs in
  * iteration order -- the Lanczos matrix of the preconditioned operator follows from them (scripts/ritz_probe.py).  Returns
  * the iterations written (<= cap pairs), < 0 on error. */

@@ -31,7 +31,7 @@ SYMBOLS = [
     "sgo_solver_description", "sgo_comm_init_host", "sgo_comm_host_allgather", "sgo_debug_level0_bytes",
     "sgo_kernel_profile_samples", "sgo_update_graph_se2", "sgo_debug_lanczos", "sgo_debug_amg_array",
     "sgo_debug_overlay_array", "sgo_debug_overlay_linearize", "sgo_debug_overlay_apply",
-    "sgo_debug_mfront_array", "sgo_mfront_plan_array",
+    "sgo_debug_mfront_array", "sgo_mfront_plan_array", "sgo_debug_pcg_array", "sgo_debug_pcg_run",
 ]
 
 
@@ -140,6 +140,9 @@ def lib():
     L.sgo_debug_overlay_apply.argtypes = [vp, d, d, d]
     L.sgo_debug_mfront_array.restype = C.c_int64
     L.sgo_debug_mfront_array.argtypes = [vp, C.c_int32, vp, C.c_int64]
+    L.sgo_debug_pcg_array.restype = C.c_int64
+    L.sgo_debug_pcg_array.argtypes = [vp, C.c_int32, vp, C.c_int64]
+    L.sgo_debug_pcg_run.argtypes = [vp, C.c_int32, d, C.c_double, C.c_int32, C.c_double]
     L.sgo_mfront_plan_array.restype = C.c_int64
     L.sgo_mfront_plan_array.argtypes = [C.c_int32, d, u8, C.c_int32, i32, i32, C.c_int32, C.c_double, C.c_int32, vp, C.c_int64]
     L.sgo_debug_level0_bytes.restype = C.c_int64
@@ -266,6 +269,17 @@ def mfront_plan_arrays(poses, fixed, ei, ej, leaf: int = 0, max_crit_mflop: floa
         return L.sgo_mfront_plan_array(p.shape[0], _dp(p), f.ctypes.data_as(C.POINTER(C.c_uint8)), a.size, _ip(a), _ip(b), leaf,
                                        max_crit_mflop, what, out, cap)
     return {k: _mfront_fetch(k, call, lambda: L.sgo_last_error(None).decode()) for k in MFRONT_PLAN_ARRAYS}
+
+
+# SGO_PCG_* of include/sgo.h: name -> (number, dtype, columns); SCALARS / HOST_SCALARS / MIRROR are PcgScalars records
+PCG_SCALARS = np.dtype([("rz", "f8"), ("pq", "f8"), ("rr", "f8"), ("bb", "f8"), ("alpha", "f8"), ("beta", "f8"), ("tol2", "f8"),
+                        ("rz_prev", "f8"), ("iter", "i4"), ("maxit", "i4"), ("stop", "i4"), ("iter_prev", "i4"), ("probe_k", "i4"),
+                        ("pad", "i4"), ("probe_rel", "f8"), ("probe_max", "f8")])
+PCG_ARRAYS = {"B": (0, np.float64, 3), "X": (1, np.float64, 3), "R": (2, np.float64, 3), "Z": (3, np.float64, 3), "P": (4, np.float64, 3),
+              "Q": (5, np.float64, 3), "DINV": (6, np.float64, 6), "XS0": (7, np.float64, 3), "SCALARS": (8, PCG_SCALARS, 0),
+              "HOST_SCALARS": (9, PCG_SCALARS, 0), "MIRROR": (10, PCG_SCALARS, 0), "PARTIALS": (11, np.float64, 2048),
+              "ZPARTS": (12, np.float64, 2048), "COUNTS": (13, np.int32, 0), "LANCZOS": (14, np.float64, 3), "ROW_ORDER": (15, np.int32, 0),
+              "START_ARGS": (16, np.float64, 0)}
 
 
 def comm_unique_id() -> bytes:
@@ -479,6 +493,26 @@ class Optimizer:
         rr = C.c_double()
         it = self._check(lib().sgo_solve(self._h, _dp(x), C.byref(rr)), "sgo_solve")
         return x, it, rr.value
+
+    def pcg_run(self, maxit: int, x_prev=None, bb_ref: float = 0.0, probe_k: int = 0, probe_max: float = 0.0) -> int:
+        """sgo_debug_pcg_run: sgo_solve under the per-call fields of an optimize() call; returns the iterations run."""
+        xp = None if x_prev is None else np.ascontiguousarray(x_prev, dtype=np.float64).reshape(self.n_free, 3)
+        return self._check(lib().sgo_debug_pcg_run(self._h, maxit, None if xp is None else _dp(xp), bb_ref, probe_k, probe_max),
+                           "sgo_debug_pcg_run")
+
+    def pcg_array(self, name):
+        """One array of the PCG recurrence as stored (sgo_debug_pcg_array; PCG_ARRAYS); None where there is no such array."""
+        what, dtype, cols = PCG_ARRAYS[name]
+        size = lib().sgo_debug_pcg_array(self._h, what, None, 0)
+        if size < 0:
+            raise SgoError(f"sgo_debug_pcg_array({name}): rc={size}: " + self.last_error())
+        if size == 0:
+            return None
+        out = np.empty(size // np.dtype(dtype).itemsize, dtype=dtype)
+        got = lib().sgo_debug_pcg_array(self._h, what, out.ctypes.data_as(C.c_void_p), out.nbytes)
+        if got != size:
+            raise SgoError(f"sgo_debug_pcg_array({name}): {got} bytes after {size}: " + self.last_error())
+        return out.reshape(-1, cols) if cols else out
 
     def lanczos(self):
         """(alpha, beta) of every PCG iteration of the last solve (needs env SGO_LANCZOS=1 at set_graph)."""

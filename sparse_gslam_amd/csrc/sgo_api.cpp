@@ -600,6 +600,19 @@ int sgo_precondition(sgo_ctx* c, const double* r, double* z) {
   } SGO_CATCH(c)
 }
 
+// What sgo_solve and sgo_debug_pcg_run share: the start state of the last linearisation again (idempotent re-finalize), start_pcg
+// under the context's current `call` fields, then the solve (run == false: the start state alone, its scalars copied to h_S).
+static int solve_from_linearization(sgo_ctx* c, bool run) {
+  int rc, grid = 0;
+  launch_finalize(c->stream, c->S0, c->owner ? c->halo.row0 : 0, c->owner ? c->halo.row1 : c->n, c->d_dgb, c->d_b, c->d_x, c->d_r,
+                  c->d_z, c->d_p, c->amg ? amg_xs0(c->amg) : nullptr, c->amg ? amg_omega(c->amg) : 0.0, c->d_partials, &grid);
+  if ((rc = start_pcg(c, grid))) return rc;
+  if (run) return run_pcg(c);
+  HIP_TRY(c, hipMemcpyAsync(c->h_S, c->d_S, sizeof(PcgScalars), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return SGO_OK;
+}
+
 int sgo_solve(sgo_ctx* c, double* x, double* relres) {
   try {
     int rc = check_graph(c);
@@ -613,12 +626,7 @@ int sgo_solve(sgo_ctx* c, double* x, double* relres) {
       return SGO_EINVAL;
     }
     read_call_knobs(c);
-    // restart from the state of the last linearisation (idempotent re-finalize)
-    int grid = 0;
-    launch_finalize(c->stream, c->S0, c->owner ? c->halo.row0 : 0, c->owner ? c->halo.row1 : c->n, c->d_dgb, c->d_b, c->d_x, c->d_r,
-                    c->d_z, c->d_p, c->amg ? amg_xs0(c->amg) : nullptr, c->amg ? amg_omega(c->amg) : 0.0, c->d_partials, &grid);
-    if ((rc = start_pcg(c, grid))) return rc;
-    if ((rc = run_pcg(c))) return rc;
+    if ((rc = solve_from_linearization(c, true))) return rc;
     if (c->owner && !halo_gather_slices(c->halo, c->stream, c->d_x, 3, &c->err)) return SGO_ECOMM;
     if (x && (rc = vec_from_device(c, c->d_x, x))) return rc;
     if (relres) *relres = c->h_S->bb > 0 ? std::sqrt(c->h_S->rr / c->h_S->bb) : 0.0;
@@ -626,6 +634,134 @@ int sgo_solve(sgo_ctx* c, double* x, double* relres) {
       c->err = "PCG breakdown (p.Hp <= 0 or non-finite): Hessian not positive definite";
       return SGO_EINVAL;
     }
+    return c->h_S->iter;
+  } SGO_CATCH(c)
+}
+
+// Test hooks for the PCG recurrence (include/sgo.h; tests/pcg_reference.py checks every stage of an iteration from these arrays).
+static int pcg_hook_ready(sgo_ctx* c, const char* name) {
+  int rc = check_graph(c);
+  if (rc) return rc;
+  if (c->ov.active) {
+    c->err = "single-step entry points need a full set-up: the resident graph carries an incremental overlay (call sgo_set_graph_se2)";
+    return SGO_EINVAL;
+  }
+  if (c->owner || multi_rank(c)) {   // a rank holds its own rows; the multi-rank iterations keep other partial-sum rows
+    c->err = std::string(name) + ": not available in a multi-GPU context";
+    return SGO_EINVAL;
+  }
+  if (!c->linearized) {
+    c->err = std::string(name) + ": call sgo_linearize first";
+    return SGO_EINVAL;
+  }
+  return SGO_OK;
+}
+
+static_assert(sizeof(PcgScalars) == 104, "sgo_debug_pcg_array documents the layout of PcgScalars (include/sgo.h)");
+
+int64_t sgo_debug_pcg_array(sgo_ctx* c, int32_t what, void* out, int64_t cap_bytes) {
+  try {
+    int rc = pcg_hook_ready(c, "sgo_debug_pcg_array");
+    if (rc) return rc;
+    if (cap_bytes < 0 || (cap_bytes > 0 && !out)) {
+      c->err = "sgo_debug_pcg_array: negative capacity, or a capacity without a buffer";
+      return SGO_EINVAL;
+    }
+    const size_t n = (size_t)c->n;
+    const void* dev = nullptr;    // a device array ...
+    const void* host = nullptr;   // ... or host memory
+    size_t bytes = 0;
+    int counts[8];
+    double args[4];
+    switch (what) {
+      case SGO_PCG_B: dev = c->d_b; bytes = 24 * n; break;
+      case SGO_PCG_X: dev = c->d_x; bytes = 24 * n; break;
+      case SGO_PCG_R: dev = c->d_r; bytes = 24 * n; break;
+      case SGO_PCG_Z: dev = c->d_z; bytes = 24 * n; break;
+      case SGO_PCG_P: dev = c->d_p; bytes = 24 * n; break;
+      case SGO_PCG_Q: dev = c->d_q; bytes = 24 * n; break;
+      case SGO_PCG_DINV: dev = c->S0.dinv; bytes = 48 * n; break;
+      case SGO_PCG_XS0: dev = c->amg ? amg_xs0(c->amg) : nullptr; bytes = dev ? 24 * n : 0; break;
+      case SGO_PCG_SCALARS: dev = c->d_S; bytes = sizeof(PcgScalars); break;
+      case SGO_PCG_HOST_SCALARS: host = c->h_S; bytes = sizeof(PcgScalars); break;
+      case SGO_PCG_MIRROR: host = c->h_Sz; bytes = sizeof(PcgScalars); break;
+      case SGO_PCG_PARTIALS: dev = c->d_partials; bytes = sizeof(double) * 3 * (size_t)kMaxPartials; break;
+      case SGO_PCG_ZPARTS: dev = c->amg ? c->d_zparts : nullptr; bytes = dev ? sizeof(double) * 2 * (size_t)kMaxPartials : 0; break;
+      case SGO_PCG_COUNTS: {
+        const sgo_ctx::PcgCounts& k = c->pcg_counts;
+        const int v[8] = {k.start_bb, k.start_rz, k.n_pq, k.n_rz, k.n_rr, k.n_zq, k.n_xq, k.n_bx};
+        std::memcpy(counts, v, sizeof(v));
+        host = counts;
+        bytes = sizeof(counts);
+        break;
+      }
+      case SGO_PCG_LANCZOS: {   // (sized from the device's own iteration count: the host copy is undefined before the first solve)
+        dev = c->d_lanczos;
+        PcgScalars S{};
+        if (dev) {
+          HIP_TRY(c, hipStreamSynchronize(c->stream));
+          HIP_TRY(c, hipMemcpy(&S, c->d_S, sizeof(PcgScalars), hipMemcpyDeviceToHost));
+        }
+        bytes = dev ? sizeof(double) * 3 * (size_t)std::min(std::max(S.iter, 0), (int)kLanczosMax) : 0;
+        break;
+      }
+      case SGO_PCG_START_ARGS:
+        args[0] = c->pcg_start.tol; args[1] = c->pcg_start.tol_cap; args[2] = c->pcg_start.bb_ref; args[3] = c->pcg_start.maxit;
+        host = args;
+        bytes = sizeof(args);
+        break;
+      case SGO_PCG_ROW_ORDER: host = c->row_of_asc.data(); bytes = sizeof(int) * n; break;
+      default: c->err = "sgo_debug_pcg_array: unknown array"; return SGO_EINVAL;
+    }
+    if (bytes == 0 || (int64_t)bytes > cap_bytes) return (int64_t)bytes;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));   // (the pinned copies are written by kernels: nothing may be in flight)
+    if (dev) HIP_TRY(c, hipMemcpy(out, dev, bytes, hipMemcpyDeviceToHost));
+    else std::memcpy(out, host, bytes);
+    return (int64_t)bytes;
+  } SGO_CATCH(c)
+}
+
+int sgo_debug_pcg_run(sgo_ctx* c, int32_t maxit, const double* x_prev, double bb_ref, int32_t probe_k, double probe_max) {
+  try {
+    int rc = pcg_hook_ready(c, "sgo_debug_pcg_run");
+    if (rc) return rc;
+    if (maxit < 0 || probe_k < 0 || !(probe_max >= 0.0) || !(bb_ref >= 0.0)) {
+      c->err = "sgo_debug_pcg_run: maxit, probe_k, probe_max and bb_ref must be >= 0";
+      return SGO_EINVAL;
+    }
+    if ((x_prev || probe_k > 0) && !c->amg) {   // (start_pcg: both belong to the solves behind a hierarchy)
+      c->err = "sgo_debug_pcg_run: the warm start and the progress probe need a multigrid hierarchy";
+      return SGO_EINVAL;
+    }
+    read_call_knobs(c);
+    // the per-call fields optimize_gn would set, put back whatever happens
+    struct Restore {
+      sgo_ctx* c;
+      sgo_ctx::CallState call;
+      double tol_cap;
+      int probe_k;
+      double probe_max;
+      ~Restore() {
+        c->call = call;
+        c->tol_cap = tol_cap;
+        c->hier.probe_k = probe_k;
+        c->hier.probe_max = probe_max;
+      }
+    } restore{c, c->call, c->tol_cap, c->hier.probe_k, c->hier.probe_max};
+    c->call.pcg_softcap = maxit;
+    c->tol_cap = c->opts.pcg_tol_cap > 0.0 ? std::max(c->opts.pcg_tol_cap, c->opts.pcg_tol * c->tol_scale) : 0.0;
+    c->call.bb_ref = c->tol_cap > 0.0 ? bb_ref : 0.0;
+    c->call.warm_valid = false;
+    if (x_prev) {
+      if ((rc = vec_to_device(c, x_prev, c->d_xprev))) return rc;
+      c->call.warm_valid = true;
+    }
+    // the probe as a solve of the lagged refresh carries it (start_pcg): armed at hier.probe_k, held to hier.probe_max behind kept operators
+    c->call.lag_on = probe_k > 0;
+    c->call.skip_update = probe_k > 0 && probe_max > 0.0;
+    c->hier.probe_k = probe_k;
+    c->hier.probe_max = probe_max;
+    if ((rc = solve_from_linearization(c, maxit > 0))) return rc;
     return c->h_S->iter;
   } SGO_CATCH(c)
 }

@@ -179,6 +179,17 @@ struct sgo_ctx {
   DirectResult* d_dres = nullptr;
   DirectResult* h_dres = nullptr; // pinned
   double* d_zparts = nullptr;     // [2][kMaxPartials] partials of r.z from the cycle's last kernel
+  // How many partial sums the latest launches of the recurrence wrote per row (sgo_debug_pcg_array): host bookkeeping of
+  // start_pcg / pcg_iteration, read by no launch.  A replayed hipGraph keeps the counts of its capture.
+  struct PcgCounts {
+    int start_bb = 0, start_rz = 0;   // k_finalize's workgroups (b.b; r.z under block-Jacobi) | the r.z row k_init / k_restart_scalars reduced
+    int n_pq = 0, n_rz = 0, n_rr = 0, n_zq = 0;   // one iteration: p.q | r.z | r.r | z.q (0: block-Jacobi)
+    int n_xq = 0, n_bx = 0;           // warm start: x_prev . H x_prev | b . x_prev (0: the last start was cold)
+  } pcg_counts;
+  struct PcgStartArgs {               // what the last start handed to k_init_scalars (same hook, same bookkeeping)
+    double tol = 0.0, tol_cap = 0.0, bb_ref = 0.0;
+    int maxit = 0;
+  } pcg_start;
   std::string solver_desc;
   std::string solver_text;        // what sgo_solver_description hands out
 

@@ -200,6 +200,12 @@ int start_pcg(sgo_ctx* c, int grid) {
   if (c->owner) return start_pcg_owner(c, grid);
   const int maxit = c->call.pcg_softcap > 0 ? std::min(c->call.pcg_softcap, c->opts.pcg_maxit) : c->opts.pcg_maxit;
   const double tol = c->opts.pcg_tol * c->tol_scale;
+  c->pcg_counts.start_bb = c->pcg_counts.start_rz = grid;
+  c->pcg_counts.n_xq = c->pcg_counts.n_bx = 0;
+  c->pcg_start.tol = tol;
+  c->pcg_start.tol_cap = c->tol_cap;
+  c->pcg_start.bb_ref = c->call.bb_ref;
+  c->pcg_start.maxit = maxit;
   if (c->amg) {
     int rc = c->call.skip_update ? SGO_OK : amg_update(c->amg, c->stream, &c->err);
     if (rc) return rc;
@@ -224,12 +230,15 @@ int start_pcg(sgo_ctx* c, int grid) {
         launch_warm_start(c->stream, 3 * c->n, c->d_xprev, c->d_q, c->d_b, c->d_x, c->d_r, c->d_partials, gq,
                           c->d_partials + 2 * kMaxPartials, gd);
       }
+      c->pcg_counts.n_xq = gq;
+      c->pcg_counts.n_bx = gd;
     }
     // (cold: k_finalize left x = 0, r = b and xs = omega Dinv b, the cycle's first sweep from zero)
     const AmgXs0 xs_ready = warm ? AmgXs0::compute : AmgXs0::ready;
     const int gz = amg_apply(c->amg, c->stream, c->d_r, c->d_z, c->d_r, c->d_zparts, nullptr, nullptr, xs_ready);
     if (amg_comm_failed(c->amg)) return SGO_ECOMM;
     HIP_TRY(c, hipMemcpyAsync(c->d_p, c->d_z, sizeof(double) * 3 * (size_t)c->n, hipMemcpyDeviceToDevice, c->stream));
+    c->pcg_counts.start_rz = gz;
     if (warm) {
       Scope sc(c, K_INIT_SCALARS, 8.0 * gz);
       launch_restart_scalars(c->stream, c->d_S, c->d_zparts, gz, maxit, 1);
@@ -454,15 +463,18 @@ int pcg_iteration(sgo_ctx* c) {
       c->err = "collective failed inside the multigrid cycle";
       return SGO_ECOMM;
     }
+    c->pcg_counts.n_rz = c->pcg_counts.n_zq = gz;
     Scope sc(c, K_UPDATE_P, 3 * 24.0 * c->n);
     launch_update_p(c->stream, c->n, c->d_S, c->d_zparts, gz, parts2 + kMaxPartials, g2, c->d_zparts + kMaxPartials,
                     c->d_z, c->d_p, rec_dev(c));
   } else {
+    c->pcg_counts.n_rz = g2;
+    c->pcg_counts.n_zq = 0;
     Scope sc(c, K_UPDATE_P, 3 * 24.0 * c->n);
-    RecDev rec;
-    rec.mirror = c->d_Sz;
-    launch_update_p(c->stream, c->n, c->d_S, parts2, g2, parts2 + kMaxPartials, g2, nullptr, c->d_z, c->d_p, rec);
+    launch_update_p(c->stream, c->n, c->d_S, parts2, g2, parts2 + kMaxPartials, g2, nullptr, c->d_z, c->d_p, rec_dev(c));
   }
+  c->pcg_counts.n_pq = g1;
+  c->pcg_counts.n_rr = g2;
   return SGO_OK;
 }
 
