@@ -44,6 +44,7 @@
 #include <cassert>
 #include <cmath>
 #include <cstdint>
+#include <cstdlib>
 #include <cstring>
 #include <deque>
 #include <fstream>
@@ -1003,7 +1004,13 @@ class SparseOptimizer : public OptimizableGraph {
   //   * the device's graph is a PREFIX of the new one -- what the reference's loop closer produces: the graph it
   //     optimised before + a chain of new poses + one closure (slc.cpp:205-226, :272-287) -- : sgo_update_graph_se2,
   //     which keeps the resident structures when the appended part allows it (include/sgo.h);
-  //   * anything else: sgo_set_graph_se2.
+  //   * same vertices, and the new edge records are the device's with some LEFT OUT, in order -- what removeEdge of EdgeSE2 edges
+  //     followed by initializeOptimization() produces, the closure gate of log_runner.cpp:182-204 --: sgo_set_edge_information
+  //     with zero rows for the missing edges (they are deactivated, every resident structure is kept), then sgo_set_poses.  _m
+  //     keeps the device's records with a `dead` flag each, and later calls compare against the records that are not dead.
+  //     SGO_INCREMENTAL=0 in the environment, or a refusal of that call, takes the full set-up;
+  //   * anything else (growth or a re-added edge after a removal and a removed vertex included): sgo_set_graph_se2, which
+  //     clears the flags.
   bool uploadGraph() {
     if (!_ctx) {
       _ctx = sgo_create(-1, nullptr);
@@ -1043,7 +1050,7 @@ class SparseOptimizer : public OptimizableGraph {
     // vertices (compact numbers then agree), bit-identical edge records for its edges
     auto same = [](const void* a, const void* b, size_t n) { return n == 0 || std::memcmp(a, b, n) == 0; };
     const int dV = (int)_m.vid.size(), dE = (int)_m.ei.size();
-    const bool prefix = _graphOnDevice && V >= dV && E >= dE && same(vid.data(), _m.vid.data(), sizeof(int32_t) * (size_t)dV) &&
+    const bool prefix = _graphOnDevice && _m.nDead == 0 && V >= dV && E >= dE && same(vid.data(), _m.vid.data(), sizeof(int32_t) * (size_t)dV) &&
                         same(fixed.data(), _m.fixed.data(), (size_t)dV) && same(ei.data(), _m.ei.data(), sizeof(int32_t) * (size_t)dE) &&
                         same(ej.data(), _m.ej.data(), sizeof(int32_t) * (size_t)dE) && same(meas.data(), _m.meas.data(), sizeof(double) * 3 * (size_t)dE) &&
                         same(info.data(), _m.info.data(), sizeof(double) * 6 * (size_t)dE) && same(phi.data(), _m.phi.data(), sizeof(double) * (size_t)dE);
@@ -1051,6 +1058,33 @@ class SparseOptimizer : public OptimizableGraph {
       if (sgo_set_poses(_ctx, poses.data()) == SGO_OK) return true;
       std::cerr << "SparseOptimizer: " << sgo_last_error(_ctx) << std::endl;
       return false;
+    }
+    // the device's live records with some left out?  (greedy in-order match: of two identical records either may be the one that left)
+    bool incremental = true;
+    if (const char* env = std::getenv("SGO_INCREMENTAL")) incremental = std::atoi(env) != 0;
+    if (_graphOnDevice && incremental && V == dV && E <= dE - _m.nDead && (E < dE - _m.nDead || _m.nDead > 0) &&
+        same(vid.data(), _m.vid.data(), sizeof(int32_t) * (size_t)dV) && same(fixed.data(), _m.fixed.data(), (size_t)dV)) {
+      std::vector<int32_t> missing;
+      int k = 0;
+      for (int r = 0; r < dE; ++r) {
+        if (_m.dead[r]) continue;
+        if (k < E && ei[k] == _m.ei[r] && ej[k] == _m.ej[r] && same(&meas[3 * (size_t)k], &_m.meas[3 * (size_t)r], sizeof(double) * 3) &&
+            same(&info[6 * (size_t)k], &_m.info[6 * (size_t)r], sizeof(double) * 6) && same(&phi[k], &_m.phi[r], sizeof(double)))
+          ++k;
+        else
+          missing.push_back(r);
+      }
+      if (k == E) {
+        const std::vector<double> zero(6 * missing.size(), 0.0);
+        if (missing.empty() || sgo_set_edge_information(_ctx, (int32_t)missing.size(), missing.data(), zero.data()) == SGO_OK) {
+          for (int32_t r : missing) _m.dead[r] = 1;
+          _m.nDead += (int)missing.size();
+          if (sgo_set_poses(_ctx, poses.data()) == SGO_OK) return true;
+          std::cerr << "SparseOptimizer: " << sgo_last_error(_ctx) << std::endl;
+          return false;
+        }
+        // (refused -- a pose that would lose its last edge, a multi-GPU context --: the full set-up below)
+      }
     }
     _graphOnDevice = false;
     const int rc = prefix ? sgo_update_graph_se2(_ctx, V, poses.data(), fixed.data(), E, ei.data(), ej.data(), meas.data(), info.data(),
@@ -1069,6 +1103,8 @@ class SparseOptimizer : public OptimizableGraph {
     _m.meas.swap(meas);
     _m.info.swap(info);
     _m.phi.swap(phi);
+    _m.dead.assign((size_t)E, 0);
+    _m.nDead = 0;
     return true;
   }
   void downloadEstimates() {
@@ -1097,6 +1133,8 @@ class SparseOptimizer : public OptimizableGraph {
     std::vector<int32_t> vid, ei, ej;
     std::vector<uint8_t> fixed;
     std::vector<double> meas, info, phi;
+    std::vector<uint8_t> dead;   // the record's edge left the graph since and is deactivated on the device (zero information)
+    int nDead = 0;
   } _m;
   std::unique_ptr<sgo_stats> _lastStats;
   std::deque<VertexSE2> _loadedVertices;   // objects created by load(): the optimiser's own

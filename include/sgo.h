@@ -107,7 +107,8 @@ typedef struct sgo_opts {
  *   mirrors of sgo_opts fields (the environment wins): SGO_SOLVER={pcg,amg}, SGO_PCG_TOL, SGO_PCG_TOL_CAP, SGO_PCG_MAXIT,
  *     SGO_PCG_CHUNK, SGO_PCG_WARM, SGO_USE_GRAPH, SGO_PROFILE, SGO_VERBOSE, SGO_DIRECT_ROWS, SGO_DEVICE
  *   path selection: SGO_MFRONT=0 (no multifrontal path), SGO_MFRONT_ROWS / _CRIT_MFLOP / _DEGREE / _LEAF (its admission limits
- *     and leaf size), SGO_INCREMENTAL=0 (sgo_update_graph_se2 is always a full set-up), SGO_SPMV0={tile,group} (level-0 product
+ *     and leaf size), SGO_INCREMENTAL=0 (sgo_update_graph_se2 is always a full set-up; the g2o-compat header, which reads it too, then also
+ *     takes the full set-up after a removeEdge instead of sgo_set_edge_information), SGO_SPMV0={tile,group} (level-0 product
  *     kernel), SGO_PRECOND_F32=0 (fp64 blocks in the preconditioner's level-0 passes)
  *   multigrid set-up: SGO_AMG_THETA (strength threshold), SGO_AMG_THETA_FILTER / SGO_AMG_FILTER=0 (filtered smoothing),
  *     SGO_AMG_SMOOTH=0 (tentative transfers only), SGO_AMG_OMEGA, SGO_AMG_OMEGA_P, SGO_AMG_NU, SGO_AMG_FOLD, SGO_AMG_FOLD0_ROWS,
@@ -216,6 +217,33 @@ int sgo_chi2(sgo_ctx* ctx, double* plain, double* robust);
 /* Replaces: EdgeSE2::computeError(); chi2() per edge (log_runner.cpp:183-184, the 11.345 gate).
  * e2[E] in the edge order given to sgo_set_graph_se2. */
 int sgo_edge_chi2(sgo_ctx* ctx, double* e2);
+
+/* Replaces: EdgeSE2::setInformation on resident edges, and SparseOptimizer::removeEdge + initializeOptimization
+ * (log_runner.cpp:186,203) with an all-zero row.  edge_ids in [0, E) in the order given to sgo_set_graph_se2 /
+ * sgo_update_graph_se2 (appended overlay edges included); info[n][6] upper triangles.  Keeps every resident structure.
+ *
+ * An edge whose information is all zero is DEACTIVATED: it adds nothing to chi2, to the right-hand side or to any Hessian
+ * block, reports 0 in sgo_edge_chi2 and contributes 0 to sgo_chi2 -- the graph optimises as if the edge had been removed, while
+ * the row plan, the tiles, the elimination trees, the overlay and the multigrid hierarchy's aggregation stay as they are (no
+ * set-up; sgo_stats.seconds_setup does not change).  Its original row through the same call brings it back.  The first solve
+ * of the next sgo_optimize_gn / sgo_solve refreshes the hierarchy's coarse operators from the new blocks; an earlier
+ * sgo_linearize is void.  sgo_solver_description keeps naming the same path and ends in "; K edges inactive" while K > 0 edges
+ * carry a zero information.
+ * SGO_EINVAL, with nothing on the device changed: a multi-GPU context (sgo_debug_set_shard's emulation included), an id outside
+ * [0, E), a non-finite entry, and a change that would leave a free pose without any incident edge of non-zero information
+ * (sgo_last_error names the vertex; its diagonal block would be singular).  Disconnecting the graph in any other way is the
+ * caller's responsibility, as it is in g2o.  Of an id listed twice the later row counts.
+ * A later sgo_update_graph_se2 or sgo_set_graph_se2 takes its arrays at face value: pass zero rows there for the edges that
+ * are to stay inactive (an incremental update's resident prefix is not re-read: those edges keep what they have). */
+int sgo_set_edge_information(sgo_ctx* ctx, int32_t n, const int32_t* edge_ids, const double* info);
+
+/* Replaces: the chi2 gate of log_runner.cpp:182-189, on the device.  For the listed edges (edge_ids == NULL: every edge with
+ * phi >= 0, n then ignored) evaluates e^T Omega e at the current poses with the arithmetic of sgo_edge_chi2 and
+ * deactivates (information := 0) those with chi2 > chi2_max.  gated[n] (or [E] with NULL ids; may be NULL) = 1 for the
+ * edges it deactivated.  Returns how many (an id listed twice counts once; an edge that is inactive already is left alone), or a
+ * negative code.  The decision is taken first and nothing is written when the call refuses: rules, refusals and what the next
+ * solve does are sgo_set_edge_information's. */
+int sgo_gate_edges(sgo_ctx* ctx, int32_t n, const int32_t* edge_ids, double chi2_max, uint8_t* gated);
 
 /* Replaces: the covariance producer of a loop closure and its use as the edge information
  * (src/sparse_gslam/src/cartographer_bindings/fast_correlative_scan_matcher_2d.cc:537-561,

@@ -32,6 +32,7 @@ SYMBOLS = [
     "sgo_kernel_profile_samples", "sgo_update_graph_se2", "sgo_debug_lanczos", "sgo_debug_amg_array",
     "sgo_debug_overlay_array", "sgo_debug_overlay_linearize", "sgo_debug_overlay_apply",
     "sgo_debug_mfront_array", "sgo_mfront_plan_array", "sgo_debug_pcg_array", "sgo_debug_pcg_run",
+    "sgo_set_edge_information", "sgo_gate_edges",
 ]
 
 
@@ -114,6 +115,8 @@ def lib():
     L.sgo_optimize_gn.argtypes = [vp, C.c_int32, C.POINTER(Stats)]
     L.sgo_chi2.argtypes = [vp, d, d]
     L.sgo_edge_chi2.argtypes = [vp, d]
+    L.sgo_set_edge_information.argtypes = [vp, C.c_int32, i32, d]
+    L.sgo_gate_edges.argtypes = [vp, C.c_int32, i32, C.c_double, u8]
     L.sgo_num_free.argtypes = [vp]
     L.sgo_free_ids.argtypes = [vp, i32]
     L.sgo_linearize.argtypes = [vp, d, d, d, d]
@@ -444,6 +447,24 @@ class Optimizer:
         out = np.empty(self.E)
         self._check(lib().sgo_edge_chi2(self._h, _dp(out)), "sgo_edge_chi2")
         return out
+
+    def set_edge_information(self, edge_ids, info):
+        """sgo_set_edge_information: new information rows (n, 6) for resident edges; an all-zero row deactivates the edge.
+        No set-up runs; SgoError (rc=-2) with the device untouched when the call refuses."""
+        ids = np.ascontiguousarray(edge_ids, dtype=np.int32).reshape(-1)
+        o = np.ascontiguousarray(info, dtype=np.float64).reshape(-1, 6)
+        if o.shape[0] != ids.size:
+            raise ValueError("inconsistent array sizes")
+        self._check(lib().sgo_set_edge_information(self._h, ids.size, _ip(ids), _dp(o)), "sgo_set_edge_information")
+
+    def gate_edges(self, edge_ids, chi2_max: float):
+        """sgo_gate_edges: deactivates the listed edges (None: every edge with a robust kernel) whose chi2 at the current poses
+        exceeds chi2_max -> (how many, bool array over the listed edges / over all edges)."""
+        ids = None if edge_ids is None else np.ascontiguousarray(edge_ids, dtype=np.int32).reshape(-1)
+        gated = np.zeros(self.E if ids is None else ids.size, dtype=np.uint8)
+        k = self._check(lib().sgo_gate_edges(self._h, 0 if ids is None else ids.size, None if ids is None else _ip(ids),
+                                             float(chi2_max), gated.ctypes.data_as(C.POINTER(C.c_uint8))), "sgo_gate_edges")
+        return k, gated.astype(bool)
 
     def closure_information(self, windows, scores):
         """Covariance and information of a batch of scan-match windows (sgo_closure_information).

@@ -15,6 +15,183 @@ namespace sgo {
 thread_local std::string g_err;  // for ctx == NULL
 }
 
+// ---- edge activity: sgo_set_edge_information / sgo_gate_edges (include/sgo.h; kernels in sgo_gate.hip) -----------------------
+namespace {
+
+bool multi_gpu_context(const sgo_ctx* c) { return c->comm.nranks > 1 || c->comm.active(); }
+
+template <class T>
+int grow_scratch(sgo_ctx* c, T** p, size_t* cap, size_t count) {
+  if (count <= *cap) return SGO_OK;
+  if (*p) hipFree(*p);   // (every call that used it has synchronised the stream)
+  *p = nullptr;
+  *cap = 0;
+  const size_t want = count + count / 4 + 64;
+  if (hipMalloc((void**)p, want * sizeof(T)) != hipSuccess) {
+    c->err = "out of device memory (" + std::to_string(want * sizeof(T)) + " bytes of edge scratch)";
+    return SGO_ENOMEM;
+  }
+  *cap = want;
+  return SGO_OK;
+}
+
+bool zero_row(const double* r) { return r[0] == 0.0 && r[1] == 0.0 && r[2] == 0.0 && r[3] == 0.0 && r[4] == 0.0 && r[5] == 0.0; }
+
+// The host bookkeeping, made from what the device holds on the first call that needs it.
+int edge_activity_ensure(sgo_ctx* c) {
+  sgo_ctx::EdgeActivity& A = c->edges;
+  if (A.ready) return SGO_OK;
+  const int E0 = c->el.E, E1 = c->E - E0, V = c->V;
+  if (E1 < 0 || E1 != (c->ov.active ? c->ov.dev.el.cnt : 0) || (size_t)E1 > c->ov.ei.size() || c->ov.fixed.size() != (size_t)V) {
+    c->err = "internal error: the appended edges and the overlay's edge list disagree";
+    return SGO_EINVAL;
+  }
+  const size_t E = (size_t)c->E;
+  A.vi.resize(E);
+  A.vj.resize(E);
+  A.dead.resize(E);
+  // the endpoints as the device holds them, and one byte per edge from a sweep over the information (not its 48 bytes per edge)
+  int rc = grow_scratch(c, &A.d_flag, &A.flag_cap, E);
+  if (rc) return rc;
+  if (E > 0) {
+    launch_edge_dead_flags(c->stream, c->el, E1 > 0 ? &c->ov.dev.el : nullptr, A.d_flag);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(A.dead.data(), A.d_flag, E, hipMemcpyDeviceToHost, c->stream));
+  }
+  if (E0 > 0) {
+    HIP_TRY(c, hipMemcpyAsync(A.vi.data(), c->el.vi, sizeof(int32_t) * (size_t)E0, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(A.vj.data(), c->el.vj, sizeof(int32_t) * (size_t)E0, hipMemcpyDeviceToHost, c->stream));
+  }
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  const size_t ov0 = c->ov.ei.size() - (size_t)E1;
+  for (int k = 0; k < E1; ++k) {
+    A.vi[E0 + k] = c->ov.ei[ov0 + k];
+    A.vj[E0 + k] = c->ov.ej[ov0 + k];
+  }
+  A.live_deg.assign((size_t)V, 0);
+  A.n_inactive = 0;
+  for (size_t e = 0; e < E; ++e) {
+    const int a = A.vi[e], b = A.vj[e];
+    if (a < 0 || a >= V || b < 0 || b >= V) {
+      c->err = "internal error: the device's edge list references a vertex outside [0, V)";
+      return SGO_EINVAL;
+    }
+    if (A.dead[e]) {
+      A.n_inactive++;
+    } else {
+      A.live_deg[a]++;
+      A.live_deg[b]++;
+    }
+  }
+  A.ready = true;
+  return SGO_OK;
+}
+
+// An incremental update appended dE edges (rows info[dE][6]) and possibly vertices: the bookkeeping follows.
+void edge_activity_append(sgo_ctx* c, int V, int dE, const int32_t* ei, const int32_t* ej, const double* info) {
+  sgo_ctx::EdgeActivity& A = c->edges;
+  if (!A.ready) return;
+  A.live_deg.resize((size_t)V, 0);
+  for (int k = 0; k < dE; ++k) {
+    const bool zero = zero_row(info + 6 * (size_t)k);
+    A.vi.push_back(ei[k]);
+    A.vj.push_back(ej[k]);
+    A.dead.push_back(zero ? 1 : 0);
+    if (zero) {
+      A.n_inactive++;
+    } else {
+      A.live_deg[ei[k]]++;
+      A.live_deg[ej[k]]++;
+    }
+  }
+}
+
+// New information rows for the listed edges (every id once, all in [0, E), all entries finite).  The host decides first -- a change
+// that would leave a free pose without any incident edge of non-zero information is refused with nothing written -- then the
+// edge lists, and the per-slot copies where they exist, are rewritten and the next solve is told that the operator changed.
+int edge_info_apply(sgo_ctx* c, const char* who, const std::vector<int32_t>& ids, const std::vector<double>& rows) {
+  sgo_ctx::EdgeActivity& A = c->edges;
+  const size_t m = ids.size();
+  if (m == 0) return SGO_OK;
+  std::vector<uint8_t> now_dead(m);
+  // the live-edge counts with the change applied (sign +1) and as they were (sign -1)
+  auto count = [&](int sign) {
+    for (size_t t = 0; t < m; ++t) {
+      const int e = ids[t];
+      const int d = sign * ((int)A.dead[e] - (int)now_dead[t]);   // +1: comes back to life, -1: deactivated
+      A.live_deg[A.vi[e]] += d;
+      A.live_deg[A.vj[e]] += d;
+    }
+  };
+  auto undo = [&]() { count(-1); };
+  for (size_t t = 0; t < m; ++t) now_dead[t] = zero_row(&rows[6 * t]) ? 1 : 0;
+  count(+1);
+  int orphan = -1;
+  for (size_t t = 0; t < m && orphan < 0; ++t) {
+    const int e = ids[t];
+    if (!now_dead[t] || A.dead[e]) continue;
+    for (const int v : {A.vi[e], A.vj[e]})
+      if (!c->ov.fixed[v] && A.live_deg[v] == 0 && orphan < 0) orphan = v;
+  }
+  if (orphan >= 0) {
+    undo();
+    c->err = std::string(who) + ": free vertex " + std::to_string(orphan) +
+             " would be left without an incident edge of non-zero information (its Hessian block would be singular)";
+    return SGO_EINVAL;
+  }
+  int rc;
+  const bool slots = c->es.info != nullptr && !c->rows_pending && c->d_eidx != nullptr && c->el.E > 0;
+  if ((rc = grow_scratch(c, &A.d_ids, &A.ids_cap, m)) || (rc = grow_scratch(c, &A.d_rows, &A.rows_cap, 6 * m))) {
+    undo();
+    return rc;
+  }
+  if (slots && (size_t)c->el.E > A.mark_cap) {
+    if ((rc = grow_scratch(c, &A.d_mark, &A.mark_cap, (size_t)c->el.E))) {
+      undo();
+      return rc;
+    }
+    if (hipMemsetAsync(A.d_mark, 0, A.mark_cap, c->stream) != hipSuccess) {
+      A.mark_cap = 0;
+      undo();
+      c->err = std::string(who) + ": device error";
+      return SGO_EHIP;
+    }
+  }
+  hipError_t e = hipMemcpyAsync(A.d_ids, ids.data(), sizeof(int32_t) * m, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(A.d_rows, rows.data(), sizeof(double) * 6 * m, hipMemcpyHostToDevice, c->stream);
+  if (e != hipSuccess) {   // (nothing of the graph has been written yet)
+    undo();
+    c->err = std::string(who) + ": " + hipGetErrorString(e);
+    return SGO_EHIP;
+  }
+  launch_edge_info_scatter(c->stream, (int)m, A.d_ids, A.d_rows, c->el, c->ov.active ? &c->ov.dev.el : nullptr, slots ? A.d_mark : nullptr);
+  if (slots) {
+    launch_slot_info_refresh(c->stream, c->S0.ncs, c->d_eidx, A.d_mark, c->el, c->es);
+    e = hipMemsetAsync(A.d_mark, 0, (size_t)c->el.E, c->stream);
+  }
+  if (e == hipSuccess) e = hipGetLastError();
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);   // (ids / rows are the caller's frame's)
+  for (size_t t = 0; t < m; ++t) {
+    const int ed = ids[t];
+    A.n_inactive += (int)now_dead[t] - (int)A.dead[ed];
+    A.dead[ed] = now_dead[t];
+  }
+  // The operator changed under the resident structures: whatever was linearised is stale, the next solve refreshes the multigrid
+  // hierarchy's coarse operators from the new blocks (no kept operators across the change: the lagged refresh's reference goes),
+  // and its iteration count sets a new reference for the count rules, as after an incremental update.
+  c->linearized = false;
+  c->hier.ref_valid = false;
+  c->call.skip_update = false;
+  c->hier.new_rhs();
+  if (e != hipSuccess) {
+    c->err = std::string(who) + ": " + hipGetErrorString(e);
+    return SGO_EHIP;
+  }
+  return SGO_OK;
+}
+
+}  // namespace
+
 // =============================================================================== C-ABI
 extern "C" {
 
@@ -129,6 +306,11 @@ void sgo_destroy(sgo_ctx* c) {
   if (c->h_dres) hipHostFree(c->h_dres);
   if (c->d_dres) hipFree(c->d_dres);
   if (c->d_comm_flag) hipFree(c->d_comm_flag);
+  if (c->edges.d_ids) hipFree(c->edges.d_ids);
+  if (c->edges.d_rows) hipFree(c->edges.d_rows);
+  if (c->edges.d_flag) hipFree(c->edges.d_flag);
+  if (c->edges.d_mark) hipFree(c->edges.d_mark);
+  if (c->edges.d_parts) hipFree(c->edges.d_parts);
   if (c->stream) hipStreamDestroy(c->stream);
   delete c;
 }
@@ -145,6 +327,7 @@ const char* sgo_solver_description(sgo_ctx* c) {
                         std::to_string(c->ov.updates) + " updates)";
     if (!c->update_note.empty()) c->solver_text += "; last update: " + c->update_note;
     if (!c->lag_note.empty()) c->solver_text += "; " + c->lag_note;
+    if (c->edges.n_inactive > 0) c->solver_text += "; " + std::to_string(c->edges.n_inactive) + " edges inactive";
     return c->solver_text.c_str();
   } catch (...) {   // no C++ exception crosses the C boundary
     return "";
@@ -371,6 +554,7 @@ int sgo_update_graph_se2(sgo_ctx* c, int32_t V, const double* poses, const uint8
         c->V = V;
         c->E = E;
         c->linearized = false;
+        edge_activity_append(c, V, dE, ei + n_resident_edges, ej + n_resident_edges, info + 6 * (size_t)n_resident_edges);
         // the hierarchy's own staleness rule compares a solve with the best count seen so far (sgo_policy.h): the solves after
         // an update have another right-hand side (the appended poses' residual) -- their first one sets a new reference
         c->hier.new_rhs();
@@ -459,6 +643,104 @@ int sgo_edge_chi2(sgo_ctx* c, double* e2) {
     HIP_TRY(c, hipMemcpyAsync(e2, c->d_e2, sizeof(double) * (size_t)c->E, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return SGO_OK;
+  } SGO_CATCH(c)
+}
+
+int sgo_set_edge_information(sgo_ctx* c, int32_t n, const int32_t* edge_ids, const double* info) {
+  try {
+    int rc = check_graph(c);
+    if (rc) return rc;
+    if (n < 0 || (n > 0 && (!edge_ids || !info))) {
+      c->err = "sgo_set_edge_information: null buffer or negative count";
+      return SGO_EINVAL;
+    }
+    if (multi_gpu_context(c)) {
+      c->err = "sgo_set_edge_information: not available in a multi-GPU context (call sgo_set_graph_se2)";
+      return SGO_EINVAL;
+    }
+    for (int t = 0; t < n; ++t) {
+      if (edge_ids[t] < 0 || edge_ids[t] >= c->E) {
+        c->err = "sgo_set_edge_information: edge id " + std::to_string(edge_ids[t]) + " outside [0, " + std::to_string(c->E) + ")";
+        return SGO_EINVAL;
+      }
+      for (int q = 0; q < 6; ++q)
+        if (!std::isfinite(info[6 * (size_t)t + q])) {
+          c->err = "sgo_set_edge_information: non-finite information entry for edge " + std::to_string(edge_ids[t]);
+          return SGO_EINVAL;
+        }
+    }
+    if (n == 0) return SGO_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    if ((rc = edge_activity_ensure(c))) return rc;
+    // every id once: of an id listed twice the later row counts
+    std::vector<int32_t> order((size_t)n);
+    for (int t = 0; t < n; ++t) order[t] = t;
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return edge_ids[a] < edge_ids[b]; });
+    std::vector<int32_t> ids;
+    std::vector<double> rows;
+    for (int k = 0; k < n; ++k) {
+      const int t = order[k];
+      if (k + 1 < n && edge_ids[order[k + 1]] == edge_ids[t]) continue;
+      ids.push_back(edge_ids[t]);
+      rows.insert(rows.end(), info + 6 * (size_t)t, info + 6 * (size_t)t + 6);
+    }
+    return edge_info_apply(c, "sgo_set_edge_information", ids, rows);
+  } SGO_CATCH(c)
+}
+
+int sgo_gate_edges(sgo_ctx* c, int32_t n, const int32_t* edge_ids, double chi2_max, uint8_t* gated) {
+  try {
+    int rc = check_graph(c);
+    if (rc) return rc;
+    if (edge_ids && n < 0) {
+      c->err = "sgo_gate_edges: negative count";
+      return SGO_EINVAL;
+    }
+    if (multi_gpu_context(c)) {
+      c->err = "sgo_gate_edges: not available in a multi-GPU context (gate on the host and call sgo_set_graph_se2)";
+      return SGO_EINVAL;
+    }
+    const int items = edge_ids ? n : c->E;
+    for (int t = 0; edge_ids && t < n; ++t)
+      if (edge_ids[t] < 0 || edge_ids[t] >= c->E) {
+        c->err = "sgo_gate_edges: edge id " + std::to_string(edge_ids[t]) + " outside [0, " + std::to_string(c->E) + ")";
+        return SGO_EINVAL;
+      }
+    if (items == 0) return 0;
+    HIP_TRY(c, hipSetDevice(c->device));
+    if ((rc = edge_activity_ensure(c))) return rc;
+    sgo_ctx::EdgeActivity& A = c->edges;
+    if ((rc = grow_scratch(c, &A.d_flag, &A.flag_cap, (size_t)items)) || (rc = grow_scratch(c, &A.d_parts, &A.parts_cap, (size_t)kMaxPartials + 1)) ||
+        (edge_ids && (rc = grow_scratch(c, &A.d_ids, &A.ids_cap, (size_t)items))))
+      return rc;
+    if (edge_ids) HIP_TRY(c, hipMemcpyAsync(A.d_ids, edge_ids, sizeof(int32_t) * (size_t)items, hipMemcpyHostToDevice, c->stream));
+    // the decision first: flags and their count, the graph untouched
+    int* d_count = reinterpret_cast<int*>(A.d_parts + kMaxPartials);
+    launch_edge_gate(c->stream, c->el, c->ov.active ? &c->ov.dev.el : nullptr, items, edge_ids ? A.d_ids : nullptr, c->d_poses, chi2_max,
+                     A.d_flag, A.d_parts, d_count);
+    HIP_TRY(c, hipGetLastError());
+    int count = 0;
+    HIP_TRY(c, hipMemcpyAsync(&count, d_count, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    std::vector<uint8_t> flag((size_t)items, 0);
+    if (count > 0) {
+      HIP_TRY(c, hipMemcpyAsync(flag.data(), A.d_flag, (size_t)items, hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(c, hipStreamSynchronize(c->stream));
+    }
+    // then the host: the edges this call deactivates (an edge that is inactive already stays as it is; an id listed twice counts once)
+    std::vector<int32_t> ids;
+    for (int t = 0; t < items && count > 0; ++t) {
+      if (!flag[t]) continue;
+      const int e = edge_ids ? edge_ids[t] : t;
+      if (A.dead[e]) flag[t] = 0;
+      else ids.push_back(e);
+    }
+    std::sort(ids.begin(), ids.end());
+    ids.erase(std::unique(ids.begin(), ids.end()), ids.end());
+    const std::vector<double> rows(6 * ids.size(), 0.0);
+    if ((rc = edge_info_apply(c, "sgo_gate_edges", ids, rows))) return rc;
+    if (gated) std::copy(flag.begin(), flag.end(), gated);
+    return (int)ids.size();
   } SGO_CATCH(c)
 }
 

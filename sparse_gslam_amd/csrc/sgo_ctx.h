@@ -223,6 +223,23 @@ struct sgo_ctx {
   int its_last = 0;
   std::string update_note;        // what the last sgo_update_graph_se2 did (sgo_solver_description)
 
+  // Edge activity (sgo_set_edge_information / sgo_gate_edges): which edges carry an all-zero information, i.e. are deactivated.
+  // Host bookkeeping made on the first such call from the device's own arrays (a set-up pays nothing for it), kept current by
+  // those calls and by incremental updates, dropped with the graph; the device scratch is grown on demand and kept across graphs.
+  struct EdgeActivity {
+    bool ready = false;
+    std::vector<int32_t> vi, vj;      // [E] endpoints: the resident list's edges, then the overlay's
+    std::vector<uint8_t> dead;        // [E] the edge's information is all zero
+    std::vector<int32_t> live_deg;    // [V] incident edges with non-zero information
+    int n_inactive = 0;               // edges with dead[e]
+    int* d_ids = nullptr;             // listed edge ids
+    double* d_rows = nullptr;         // their information rows [.][6]
+    unsigned char* d_flag = nullptr;  // the gate's decisions
+    unsigned char* d_mark = nullptr;  // [el.E] edges whose per-slot copies are due (zero between calls)
+    double* d_parts = nullptr;        // [kMaxPartials] the gate's per-workgroup counts, then the count itself (one int)
+    size_t ids_cap = 0, rows_cap = 0, flag_cap = 0, mark_cap = 0, parts_cap = 0;
+  } edges;
+
   // profiling
   struct Rec { int kid; hipEvent_t a, b; };
   std::vector<hipEvent_t> ev_pool;

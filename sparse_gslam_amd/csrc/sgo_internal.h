@@ -523,6 +523,19 @@ void launch_reduce2(hipStream_t s, const double* partials, int nparts, double* o
 // meas / info: E raw rows; outputs at SoA positions [at, at + E) of arrays with component stride `stride`
 void launch_edge_prepare(hipStream_t s, int E, const double* meas, const double* info, double* zinv, double* info_soa, size_t stride, size_t at);
 void launch_slot_expand(hipStream_t s, int k0, int k1, const int* eidx, const EdgeListDev& el, const EdgeSlotsDev& es);   // slots [k0, k1)
+// ---- edge gate / information rewrite (sgo_gate.hip; sgo_gate_edges, sgo_set_edge_information) ----
+// item t = edge ids[t] (ids == nullptr: edge t, kernel-less edges never gated); ids >= el.E address the first el2->cnt edges of el2 (the
+// overlay's list).  flag[n] = chi2 > chi2_max with sgo_edge_chi2's arithmetic, *count = how many; partials: [kMaxPartials] scratch
+void launch_edge_gate(hipStream_t s, const EdgeListDev& el, const EdgeListDev* el2, int n, const int* ids, const double* poses,
+                      double chi2_max, unsigned char* flag, double* partials, int* count);
+// dead[el.E + el2->cnt] = the edge's information is all zero
+void launch_edge_dead_flags(hipStream_t s, const EdgeListDev& el, const EdgeListDev* el2, unsigned char* dead);
+// rows[n][6] -> the SoA information of the listed edges (every id once); mark (optional, [el.E]) = 1 for the resident ones
+void launch_edge_info_scatter(hipStream_t s, int n, const int* ids, const double* rows, const EdgeListDev& el, const EdgeListDev* el2,
+                              unsigned char* mark);
+// the per-slot copies (es.info) of the marked edges from el.info; eidx: slot -> edge
+void launch_slot_info_refresh(hipStream_t s, int ncs, const int* eidx, const unsigned char* mark, const EdgeListDev& el,
+                              const EdgeSlotsDev& es);
 // strength weights of the logical slots (hrowptr: logical row pointers) straight from the edge list (sgo_kernels.hip)
 void launch_early_strength(hipStream_t s, const EdgeListDev& el, const double* poses, int n, const int* rowptr, const int* eidx,
                            const unsigned char* flags, const int* hrowptr, double* w);

@@ -133,6 +133,8 @@ void free_graph(sgo_ctx* c) {
   c->its_base = c->its_last = 0;
   c->update_note.clear();
   c->lag_note.clear();
+  c->edges.ready = false;   // (the edge-activity bookkeeping belongs to the graph; its device scratch stays)
+  c->edges.n_inactive = 0;
 }
 
 // The edge arrays, poses and chi2 buffers of a graph: all that chi2 / per-edge chi2 / the single-launch direct path
