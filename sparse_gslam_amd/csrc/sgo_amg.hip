@@ -126,26 +126,13 @@ __global__ __launch_bounds__(kBlock) void k_galerkin(BsrDev F, BsrDev C, Galerki
       if (row1 > 0 && (i < row0 || i >= row1)) continue;
       const double dxi = d[2 * (size_t)i], dyi = d[2 * (size_t)i + 1];
       const double dxj = d[2 * (size_t)j], dyj = d[2 * (size_t)j + 1];
-      double b[9];
+      double b[9], m[3];
       load_block(F, (size_t)k, b);
-      // M = B T_j : third column = -dy_j * col0 + dx_j * col1 + col2
-      const double m02 = -dyj * b[0] + dxj * b[1] + b[2];
-      const double m12 = -dyj * b[3] + dxj * b[4] + b[5];
-      const double m22 = -dyj * b[6] + dxj * b[7] + b[8];
-      // C = T_i^T M : third row = -dy_i * row0 + dx_i * row1 + row2
-      acc[0] += b[0];
-      acc[1] += b[1];
-      acc[2] += m02;
-      acc[3] += b[3];
-      acc[4] += b[4];
-      acc[5] += m12;
-      acc[6] += -dyi * b[0] + dxi * b[3] + b[6];
-      acc[7] += -dyi * b[1] + dxi * b[4] + b[7];
-      acc[8] += -dyi * m02 + dxi * m12 + m22;
+      block_rigid_col(b, dxj, dyj, m);          // M = B T_j
+      rigid_t_block_acc(b, m, dxi, dyi, acc);   // C += T_i^T M
     }
-    seg_scan<9>(key, acc, lane);
-    const int kn = next_lane_key(key);
-    if (key >= 0 && (lane == 63 || kn != key)) {
+    seg_scan<9>(key, acc);
+    if (segment_end(key, lane)) {
 #pragma unroll
       for (int c = 0; c < 9; ++c) C.blk[blk_at(c, key, ncs)] = acc[c];
     }
@@ -283,13 +270,10 @@ __global__ __launch_bounds__(kBlock) void k_filtered_diag(BsrDev F, const int* _
       const double dx = pos[2 * (size_t)j] - pos[2 * (size_t)i], dy = pos[2 * (size_t)j + 1] - pos[2 * (size_t)i + 1];
       double b[9];
       load_block(F, (size_t)k, b);
-      acc[0] += b[0]; acc[1] += b[1]; acc[2] += -dy * b[0] + dx * b[1] + b[2];
-      acc[3] += b[3]; acc[4] += b[4]; acc[5] += -dy * b[3] + dx * b[4] + b[5];
-      acc[6] += b[6]; acc[7] += b[7]; acc[8] += -dy * b[6] + dx * b[7] + b[8];
+      block_rigid_acc(b, dx, dy, acc);   // A_k T(p_j - p_i)
     }
-    seg_scan<10>(key, acc, lane);
-    const int kn = next_lane_key(key);
-    if (key >= 0 && (lane == 63 || kn != key)) {
+    seg_scan<10>(key, acc);
+    if (segment_end(key, lane)) {
       double d[9];
       load_block(F, (size_t)F.rowptr[key], d);   // the diagonal slot comes first in its row
       // (a row without any kept connection keeps its whole diagonal block: with everything lumped D_F would be the row sum of
@@ -360,13 +344,10 @@ __global__ __launch_bounds__(kBlock) void k_p_values(BsrDev F, PDev P, const int
 #pragma unroll
         for (int c = 0; c < 9; ++c) b[c] = f[c];
       }
-      acc[0] += b[0]; acc[1] += b[1]; acc[2] += -dyj * b[0] + dxj * b[1] + b[2];
-      acc[3] += b[3]; acc[4] += b[4]; acc[5] += -dyj * b[3] + dxj * b[4] + b[5];
-      acc[6] += b[6]; acc[7] += b[7]; acc[8] += -dyj * b[6] + dxj * b[7] + b[8];
+      block_rigid_acc(b, dxj, dyj, acc);   // A_k T_col(k)
     }
-    seg_scan<9>(key, acc, lane);
-    const int kn = next_lane_key(key);
-    if (key >= 0 && (lane == 63 || kn != key)) {
+    seg_scan<9>(key, acc);
+    if (segment_end(key, lane)) {
       const size_t i = (size_t)P.row[key];
       double o[9];
       if (P.dinvF) {   // filtered smoothing: the general 3x3 inverse of D_F
@@ -465,9 +446,8 @@ __global__ __launch_bounds__(kBlock) void k_block_products(ProdMap mp, BsrDev XA
           else acc[3 * r + c] += x[3 * r] * y[c] + x[3 * r + 1] * y[3 + c] + x[3 * r + 2] * y[6 + c];
         }
     }
-    seg_scan<9>(key, acc, lane);
-    const int kn = next_lane_key(key);
-    if (key >= 0 && (lane == 63 || kn != key)) {
+    seg_scan<9>(key, acc);
+    if (segment_end(key, lane)) {
 #pragma unroll
       for (int c = 0; c < 9; ++c) {
         if (OUT_BSR) out[blk_at(c, (size_t)key, nout)] = acc[c];
@@ -507,12 +487,10 @@ __device__ __forceinline__ void restrict_groups(const PDev& P, const double* __r
     for (int t = gb + (int)threadIdx.x; t < ge; t += kBlock) {
       const size_t i = (size_t)P.t_row[t];
       if (row1 > 0 && ((int)i < row0 || (int)i >= row1)) continue;
-      const double r0 = r[3 * i], r1 = r[3 * i + 1], r2 = r[3 * i + 2];
+      const double ri[3] = {r[3 * i], r[3 * i + 1], r[3 * i + 2]};
       double b[9];
       load9_pairs(P.t_blk, P.t_blk8, (size_t)t, np, b, P.stream_nt != 0);
-      acc[0] += b[0] * r0 + b[3] * r1 + b[6] * r2;
-      acc[1] += b[1] * r0 + b[4] * r1 + b[7] * r2;
-      acc[2] += b[2] * r0 + b[5] * r1 + b[8] * r2;
+      block_tmul_acc(b, ri, acc);
     }
 #pragma unroll
     for (int q = 0; q < 3; ++q) {
@@ -527,18 +505,11 @@ __device__ __forceinline__ void restrict_groups(const PDev& P, const double* __r
     }
     return;
   }
-  // (as in k_spmv: the first group's bounds are requested before the stop flag is waited for -- one dependent
-  // round trip less in a launch that is a chain of four)
-  int g, gend, gstride;
-  group_walk_b(P.t_ngrp, nb_main, block, &g, &gend, &gstride);
-  int gb0 = 0, ge0 = 0;
-  if (g < gend) {
-    gb0 = P.t_grp[g];
-    ge0 = P.t_grp[g + 1];
-  }
+  GroupCursor gc = group_cursor(P.t_grp, P.t_ngrp, nb_main, block);
   if (S && S->stop) return;
-  for (bool first = true; g < gend; g += gstride, first = false) {
-    const int gb = first ? gb0 : P.t_grp[g], ge = first ? ge0 : P.t_grp[g + 1];
+  for (bool first = true; gc.g < gc.gend; gc.g += gc.gstride, first = false) {
+    int gb, ge;
+    group_bounds(gc, P.t_grp, first, gb, ge);
     if (P.t_nlong > 0 && ge - gb > kLongColumn) continue;   // a long column: the workgroups at the end of the grid
     double acc[3] = {0.0, 0.0, 0.0};
     int key = -1 - lane;
@@ -546,16 +517,13 @@ __device__ __forceinline__ void restrict_groups(const PDev& P, const double* __r
       key = P.t_col[t];
       const size_t i = (size_t)P.t_row[t];
       if (row1 > 0 && ((int)i < row0 || (int)i >= row1)) continue;
-      const double r0 = r[3 * i], r1 = r[3 * i + 1], r2 = r[3 * i + 2];
+      const double ri[3] = {r[3 * i], r[3 * i + 1], r[3 * i + 2]};
       double b[9];
       load9_pairs(P.t_blk, P.t_blk8, (size_t)t, np, b, P.stream_nt != 0);
-      acc[0] += b[0] * r0 + b[3] * r1 + b[6] * r2;
-      acc[1] += b[1] * r0 + b[4] * r1 + b[7] * r2;
-      acc[2] += b[2] * r0 + b[5] * r1 + b[8] * r2;
+      block_tmul_acc(b, ri, acc);
     }
-    seg_scan<3>(key, acc, lane);
-    const int kn = next_lane_key(key);
-    if (key >= 0 && (lane == 63 || kn != key)) {
+    seg_scan<3>(key, acc);
+    if (segment_end(key, lane)) {
       rc[3 * (size_t)key] = acc[0];
       rc[3 * (size_t)key + 1] = acc[1];
       rc[3 * (size_t)key + 2] = acc[2];
@@ -585,29 +553,16 @@ __global__ __launch_bounds__(kBlock) void k_prolong_p(int n, PDev P, const doubl
                                                       const double* __restrict__ u2, SpmvRatio r2,
                                                       double* __restrict__ x, const PcgScalars* S,
                                                       const double* __restrict__ xadd, int row0, int row1) {
-  int g, gend, gstride;
-  group_walk(P.r_ngrp, &g, &gend, &gstride);
-  int gb0 = 0, ge0 = 0;   // requested before the stop flag is waited for (see k_restrict_p)
-  if (g < gend) {
-    gb0 = P.r_grp[g];
-    ge0 = P.r_grp[g + 1];
-  }
+  GroupCursor gc = group_cursor(P.r_grp, P.r_ngrp, gridDim.x, blockIdx.x);
   if (S && S->stop) return;
-  double c1 = 1.0, c2 = 0.0;
-  if (r1.num || u2) {   // (the plain V-cycle prolongates an unscaled correction: no partial sums to reduce)
-    const double* const parts[4] = {r1.num ? r1.den : nullptr, r1.num, (u2 && r2.num) ? r2.den : nullptr,
-                                    u2 ? r2.num : nullptr};
-    const int cnt[4] = {r1.n_den, r1.n_num, r2.n_den, r2.n_num};
-    double v[4];
-    block_reduce_parts_n<4>(parts, cnt, v);
-    if (r1.num) c1 = (v[0] > 0.0 && isfinite(v[0]) && isfinite(v[1])) ? v[1] / v[0] : 0.0;
-    if (u2) c2 = (v[2] > 0.0 && isfinite(v[2]) && isfinite(v[3])) ? v[3] / v[2] : 0.0;
-  }
+  double c1, c2;
+  cycle_coefficients(r1, r2, u2 != nullptr, c1, c2);
   // one lane per entry (entries are sorted by fine row), wavefront segmented sum per row
   const int lane = threadIdx.x & 63;
   const size_t np = (size_t)P.r_n;
-  for (bool first = true; g < gend; g += gstride, first = false) {
-    const int gb = first ? gb0 : P.r_grp[g], ge = first ? ge0 : P.r_grp[g + 1];
+  for (bool first = true; gc.g < gc.gend; gc.g += gc.gstride, first = false) {
+    int gb, ge;
+    group_bounds(gc, P.r_grp, first, gb, ge);
     double acc[3] = {0.0, 0.0, 0.0};
     int key = -1 - lane;
     for (int e = gb + lane; e < ge; e += 64) {
@@ -616,20 +571,13 @@ __global__ __launch_bounds__(kBlock) void k_prolong_p(int n, PDev P, const doubl
         key = -1 - lane;
         continue;
       }
-      const size_t a = 3 * (size_t)P.col[e];
-      double w0 = c1 * u1[a], w1 = c1 * u1[a + 1], w2 = c1 * u1[a + 2];
-      if (u2) {
-        w0 += c2 * u2[a]; w1 += c2 * u2[a + 1]; w2 += c2 * u2[a + 2];
-      }
-      double b[9];
+      double w[3], b[9];
+      coarse_operand(u1, u2, c1, c2, 3 * (size_t)P.col[e], w);
       load9_pairs(P.r_blk, P.r_blk8, (size_t)e, np, b, P.stream_nt != 0);
-      acc[0] += b[0] * w0 + b[1] * w1 + b[2] * w2;
-      acc[1] += b[3] * w0 + b[4] * w1 + b[5] * w2;
-      acc[2] += b[6] * w0 + b[7] * w1 + b[8] * w2;
+      block_mul_acc(b, w, acc);
     }
-    seg_scan<3>(key, acc, lane);
-    const int kn = next_lane_key(key);
-    if (key >= 0 && (lane == 63 || kn != key)) {
+    seg_scan<3>(key, acc);
+    if (segment_end(key, lane)) {
       const size_t o = 3 * (size_t)key;
       if (xadd) {
         acc[0] += xadd[o]; acc[1] += xadd[o + 1]; acc[2] += xadd[o + 2];
@@ -787,19 +735,11 @@ __global__ __launch_bounds__(kFoldThreads) void k_prolong_fold(PDev P, const dou
   constexpr int NW = kFoldThreads / 64;
   __shared__ double sm[4][NW];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  // XCD-aware walk (group_walk's rule) for NW waves per workgroup
-  const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, per_xcd = gridDim.x >> 3;
-  const int glo = (int)(((long long)P.r_ngrp * xcd) >> 3), gend = (int)(((long long)P.r_ngrp * (xcd + 1)) >> 3);
-  const int gstride = per_xcd * NW;
-  int g = glo + slot * NW + wave;
-  int gb0 = 0, ge0 = 0;   // requested before the stop flag is waited for (see k_restrict_p)
-  if (g < gend) {
-    gb0 = P.r_grp[g];
-    ge0 = P.r_grp[g + 1];
-  }
+  GroupCursor gc = group_cursor<NW>(P.r_grp, P.r_ngrp, gridDim.x, blockIdx.x);
   if (S && S->stop) return;
   double c1 = 1.0, c2 = 0.0;
-  if (r1.num || u2) {   // ratios of partial sums (K-cycle below): every workgroup reduces them in the same fixed order
+  // cycle_coefficients (sgo_device.h) with a reduction of its own: 1024 threads, and sm is shared with the dot products below
+  if (r1.num || u2) {
     const double* const parts[4] = {r1.num ? r1.den : nullptr, r1.num, (u2 && r2.num) ? r2.den : nullptr, u2 ? r2.num : nullptr};
     const int cnt[4] = {r1.n_den, r1.n_num, r2.n_den, r2.n_num};
     double v[4];
@@ -820,27 +760,22 @@ __global__ __launch_bounds__(kFoldThreads) void k_prolong_fold(PDev P, const dou
       v[c] = t;
     }
     __syncthreads();
-    if (r1.num) c1 = (v[0] > 0.0 && isfinite(v[0]) && isfinite(v[1])) ? v[1] / v[0] : 0.0;
-    if (u2) c2 = (v[2] > 0.0 && isfinite(v[2]) && isfinite(v[3])) ? v[3] / v[2] : 0.0;
+    if (r1.num) c1 = cycle_ratio(v[0], v[1]);
+    if (u2) c2 = cycle_ratio(v[2], v[3]);
   }
   const size_t np = (size_t)P.r_n;
   double dotacc[2] = {0.0, 0.0};
-  for (bool first = true; g < gend; g += gstride, first = false) {
-    const int gb = first ? gb0 : P.r_grp[g], ge = first ? ge0 : P.r_grp[g + 1];
+  for (bool first = true; gc.g < gc.gend; gc.g += gc.gstride, first = false) {
+    int gb, ge;
+    group_bounds(gc, P.r_grp, first, gb, ge);
     double acc[3] = {0.0, 0.0, 0.0};
     int key = -1 - lane;
     for (int e = gb + lane; e < ge; e += 64) {
       key = P.row[e];
-      const size_t a = 3 * (size_t)P.col[e];
-      double w0 = c1 * u1[a], w1 = c1 * u1[a + 1], w2 = c1 * u1[a + 2];
-      if (u2) {
-        w0 += c2 * u2[a]; w1 += c2 * u2[a + 1]; w2 += c2 * u2[a + 2];
-      }
-      double b[9];
+      double w[3], b[9];
+      coarse_operand(u1, u2, c1, c2, 3 * (size_t)P.col[e], w);
       load9_pairs(P.r_blk, P.r_blk8, (size_t)e, np, b, P.stream_nt != 0);
-      acc[0] += b[0] * w0 + b[1] * w1 + b[2] * w2;
-      acc[1] += b[3] * w0 + b[4] * w1 + b[5] * w2;
-      acc[2] += b[6] * w0 + b[7] * w1 + b[8] * w2;
+      block_mul_acc(b, w, acc);
     }
     // the row's own term is requested before the scan (one dependent round trip less)
     double y0 = 0.0, y1 = 0.0, y2 = 0.0;
@@ -848,9 +783,8 @@ __global__ __launch_bounds__(kFoldThreads) void k_prolong_fold(PDev P, const dou
       const size_t o = 3 * (size_t)key;
       y0 = y[o]; y1 = y[o + 1]; y2 = y[o + 2];
     }
-    seg_scan<3>(key, acc, lane);
-    const int kn = next_lane_key(key);
-    if (key >= 0 && (lane == 63 || kn != key)) {
+    seg_scan<3>(key, acc);
+    if (segment_end(key, lane)) {
       const size_t o = 3 * (size_t)key;
       const double o0 = y0 + acc[0], o1 = y1 + acc[1], o2 = y2 + acc[2];
       out[o] = o0; out[o + 1] = o1; out[o + 2] = o2;
@@ -883,28 +817,15 @@ __global__ __launch_bounds__(kBlock) void k_up_fold(BsrDev A, UpDev U, PDev PS, 
                                                     const double* __restrict__ u1, SpmvRatio r1, const double* __restrict__ u2,
                                                     SpmvRatio r2, double* __restrict__ out, const PcgScalars* S,
                                                     const double* __restrict__ xadd) {
-  int g, gend, gstride;
-  group_walk(U.ngrp, &g, &gend, &gstride);
-  int gb0 = 0, ge0 = 0;
-  if (g < gend) {
-    gb0 = U.grp[g];
-    ge0 = U.grp[g + 1];
-  }
+  GroupCursor gc = group_cursor(U.grp, U.ngrp, gridDim.x, blockIdx.x);
   if (S && S->stop) return;
-  double c1 = 1.0, c2 = 0.0;
-  if (r1.num || u2) {
-    const double* const parts[4] = {r1.num ? r1.den : nullptr, r1.num, (u2 && r2.num) ? r2.den : nullptr,
-                                    u2 ? r2.num : nullptr};
-    const int cnt[4] = {r1.n_den, r1.n_num, r2.n_den, r2.n_num};
-    double v[4];
-    block_reduce_parts_n<4>(parts, cnt, v);
-    if (r1.num) c1 = (v[0] > 0.0 && isfinite(v[0]) && isfinite(v[1])) ? v[1] / v[0] : 0.0;
-    if (u2) c2 = (v[2] > 0.0 && isfinite(v[2]) && isfinite(v[3])) ? v[3] / v[2] : 0.0;
-  }
+  double c1, c2;
+  cycle_coefficients(r1, r2, u2 != nullptr, c1, c2);
   const int lane = threadIdx.x & 63;
   const size_t ns = (size_t)A.nslot, np = (size_t)PS.r_n;
-  for (bool first = true; g < gend; g += gstride, first = false) {
-    const int gb = first ? gb0 : U.grp[g], ge = first ? ge0 : U.grp[g + 1];
+  for (bool first = true; gc.g < gc.gend; gc.g += gc.gstride, first = false) {
+    int gb, ge;
+    group_bounds(gc, U.grp, first, gb, ge);
     double acc[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};   // [0..2] A x1, [3..5] P~ e
     int key = -1 - lane;
     for (int t = gb + lane; t < ge; t += 64) {
@@ -913,49 +834,40 @@ __global__ __launch_bounds__(kBlock) void k_up_fold(BsrDev A, UpDev U, PDev PS, 
       const size_t j = (size_t)U.col[t];
       if (idx >= 0) {
         const size_t k = (size_t)idx;
-        const double* dj = A.dinv + 6 * j;
-        const double b0 = b[3 * j], b1 = b[3 * j + 1], b2 = b[3 * j + 2];
-        const double x0 = omega * (dj[0] * b0 + dj[1] * b1 + dj[2] * b2);
-        const double x1 = omega * (dj[1] * b0 + dj[3] * b1 + dj[4] * b2);
-        const double x2 = omega * (dj[2] * b0 + dj[4] * b1 + dj[5] * b2);
+        const double bj[3] = {b[3 * j], b[3 * j + 1], b[3 * j + 2]};
+        double x[3];
+        dinv_apply(A.dinv + 6 * j, omega, bj, x);
         const double2* __restrict__ bp = reinterpret_cast<const double2*>(A.blk);
         const double2 p0 = bp[k], p1 = bp[ns + k], p2 = bp[2 * ns + k], p3 = bp[3 * ns + k];
         const double b8 = A.blk[8 * ns + k];
-        acc[0] += p0.x * x0 + p0.y * x1 + p1.x * x2;
-        acc[1] += p1.y * x0 + p2.x * x1 + p2.y * x2;
-        acc[2] += p3.x * x0 + p3.y * x1 + b8 * x2;
+        block_mul_acc(p0, p1, p2, p3, b8, x, acc);
       } else {
         const size_t f = (size_t)(~idx);
-        double w0 = c1 * u1[3 * j], w1 = c1 * u1[3 * j + 1], w2 = c1 * u1[3 * j + 2];
-        if (u2) {
-          w0 += c2 * u2[3 * j]; w1 += c2 * u2[3 * j + 1]; w2 += c2 * u2[3 * j + 2];
-        }
-        double q[9];
+        double w[3], q[9];
+        coarse_operand(u1, u2, c1, c2, 3 * j, w);
         load9_pairs(PS.r_blk, PS.r_blk8, f, np, q, false);
-        acc[3] += q[0] * w0 + q[1] * w1 + q[2] * w2;
-        acc[4] += q[3] * w0 + q[4] * w1 + q[5] * w2;
-        acc[5] += q[6] * w0 + q[7] * w1 + q[8] * w2;
+        block_mul_acc(q, w, acc + 3);
       }
     }
     // the row's own right-hand side and block-diagonal inverse, requested before the scan
-    double bi0 = 0.0, bi1 = 0.0, bi2 = 0.0, d0 = 0.0, d1 = 0.0, d2 = 0.0, d3 = 0.0, d4 = 0.0, d5 = 0.0;
+    double bi[3] = {0.0, 0.0, 0.0}, di[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     if (key >= 0) {
       const size_t i = (size_t)key;
-      bi0 = b[3 * i]; bi1 = b[3 * i + 1]; bi2 = b[3 * i + 2];
-      const double* di = A.dinv + 6 * i;
-      d0 = di[0]; d1 = di[1]; d2 = di[2]; d3 = di[3]; d4 = di[4]; d5 = di[5];
+      bi[0] = b[3 * i]; bi[1] = b[3 * i + 1]; bi[2] = b[3 * i + 2];
+#pragma unroll
+      for (int q = 0; q < 6; ++q) di[q] = A.dinv[6 * i + q];
     }
-    seg_scan<6>(key, acc, lane);
-    const int kn = next_lane_key(key);
-    if (key >= 0 && (lane == 63 || kn != key)) {
+    seg_scan<6>(key, acc);
+    if (segment_end(key, lane)) {
       const size_t o = 3 * (size_t)key;
       // x1 + w D^-1 (b - A x1) = w D^-1 (2 b - A x1) evaluated as the cycle does: x1 first, then the residual's sweep
-      const double x0 = omega * (d0 * bi0 + d1 * bi1 + d2 * bi2), x1 = omega * (d1 * bi0 + d3 * bi1 + d4 * bi2),
-                   x2 = omega * (d2 * bi0 + d4 * bi1 + d5 * bi2);
-      const double r0 = bi0 - acc[0], rr1 = bi1 - acc[1], rr2 = bi2 - acc[2];
-      double o0 = x0 + omega * (d0 * r0 + d1 * rr1 + d2 * rr2) + acc[3];
-      double o1 = x1 + omega * (d1 * r0 + d3 * rr1 + d4 * rr2) + acc[4];
-      double o2 = x2 + omega * (d2 * r0 + d4 * rr1 + d5 * rr2) + acc[5];
+      const double res[3] = {bi[0] - acc[0], bi[1] - acc[1], bi[2] - acc[2]};
+      double x[3], sw[3];
+      dinv_apply(di, omega, bi, x);
+      dinv_apply(di, omega, res, sw);
+      double o0 = x[0] + sw[0] + acc[3];
+      double o1 = x[1] + sw[1] + acc[4];
+      double o2 = x[2] + sw[2] + acc[5];
       if (xadd) {   // (an outer sweep's iterate the folded cycle corrects)
         o0 += xadd[o]; o1 += xadd[o + 1]; o2 += xadd[o + 2];
       }
@@ -970,15 +882,10 @@ __global__ __launch_bounds__(kBlock) void k_level_dinv(BsrDev A) {
   for (int i = blockIdx.x * kBlock + threadIdx.x; i < A.n; i += gridDim.x * kBlock) {
     const int k0 = A.rowptr[i];
     // symmetrise (the Galerkin sum is symmetric up to rounding)
-    const double d00 = A.blk[blk_at(0, k0, ns)], d01 = 0.5 * (A.blk[blk_at(1, k0, ns)] + A.blk[blk_at(3, k0, ns)]);
-    const double d02 = 0.5 * (A.blk[blk_at(2, k0, ns)] + A.blk[blk_at(6, k0, ns)]), d11 = A.blk[blk_at(4, k0, ns)];
-    const double d12 = 0.5 * (A.blk[blk_at(5, k0, ns)] + A.blk[blk_at(7, k0, ns)]), d22 = A.blk[blk_at(8, k0, ns)];
-    const double c00 = d11 * d22 - d12 * d12, c01 = d02 * d12 - d01 * d22, c02 = d01 * d12 - d02 * d11;
-    const double c11 = d00 * d22 - d02 * d02, c12 = d01 * d02 - d00 * d12, c22 = d00 * d11 - d01 * d01;
-    const double det = d00 * c00 + d01 * c01 + d02 * c02;
-    const double id = (det != 0.0 && isfinite(det)) ? 1.0 / det : 0.0;
-    double* di = A.dinv + 6 * (size_t)i;
-    di[0] = c00 * id; di[1] = c01 * id; di[2] = c02 * id; di[3] = c11 * id; di[4] = c12 * id; di[5] = c22 * id;
+    const double d[6] = {A.blk[blk_at(0, k0, ns)], 0.5 * (A.blk[blk_at(1, k0, ns)] + A.blk[blk_at(3, k0, ns)]),
+                         0.5 * (A.blk[blk_at(2, k0, ns)] + A.blk[blk_at(6, k0, ns)]), A.blk[blk_at(4, k0, ns)],
+                         0.5 * (A.blk[blk_at(5, k0, ns)] + A.blk[blk_at(7, k0, ns)]), A.blk[blk_at(8, k0, ns)]};
+    dinv_from_block(d, A.dinv + 6 * (size_t)i);
   }
 }
 
@@ -989,30 +896,22 @@ __global__ __launch_bounds__(kBlock) void k_restrict(int ngrp, const int* __rest
                                                      const double* __restrict__ r, double* __restrict__ rc,
                                                      const PcgScalars* S, int row0, int row1) {
   const int lane = threadIdx.x & 63;
-  int g, gend, gstride;
-  group_walk(ngrp, &g, &gend, &gstride);
-  int gb0 = 0, ge0 = 0;   // requested before the stop flag is waited for (see k_restrict_p)
-  if (g < gend) {
-    gb0 = grp[g];
-    ge0 = grp[g + 1];
-  }
+  GroupCursor gc = group_cursor(grp, ngrp, gridDim.x, blockIdx.x);
   if (S && S->stop) return;
-  for (bool first = true; g < gend; g += gstride, first = false) {
-    const int gb = first ? gb0 : grp[g], ge = first ? ge0 : grp[g + 1];
+  for (bool first = true; gc.g < gc.gend; gc.g += gc.gstride, first = false) {
+    int gb, ge;
+    group_bounds(gc, grp, first, gb, ge);
     double acc[3] = {0.0, 0.0, 0.0};
     int key = -1 - lane;
     for (int t = gb + lane; t < ge; t += 64) {
       const int i = mem[t];
       key = agg[i];
       if (row1 > 0 && (i < row0 || i >= row1)) continue;
-      const double r0 = r[3 * (size_t)i], r1 = r[3 * (size_t)i + 1], r2 = r[3 * (size_t)i + 2];
-      acc[0] += r0;
-      acc[1] += r1;
-      acc[2] += -d[2 * (size_t)i + 1] * r0 + d[2 * (size_t)i] * r1 + r2;
+      const double ri[3] = {r[3 * (size_t)i], r[3 * (size_t)i + 1], r[3 * (size_t)i + 2]};
+      rigid_t_acc(d[2 * (size_t)i], d[2 * (size_t)i + 1], ri, acc);
     }
-    seg_scan<3>(key, acc, lane);
-    const int kn = next_lane_key(key);
-    if (key >= 0 && (lane == 63 || kn != key)) {
+    seg_scan<3>(key, acc);
+    if (segment_end(key, lane)) {
       rc[3 * (size_t)key] = acc[0];
       rc[3 * (size_t)key + 1] = acc[1];
       rc[3 * (size_t)key + 2] = acc[2];
@@ -1027,30 +926,18 @@ __global__ __launch_bounds__(kBlock) void k_prolong_add(int n, const int* __rest
                                                         double* __restrict__ x, const PcgScalars* S,
                                                         const double* __restrict__ xadd, int row0, int row1) {
   if (S && S->stop) return;
-  double c1 = 1.0, c2 = 0.0;
-  {
-    const double* const parts[4] = {r1.num ? r1.den : nullptr, r1.num, (u2 && r2.num) ? r2.den : nullptr,
-                                    u2 ? r2.num : nullptr};
-    const int cnt[4] = {r1.n_den, r1.n_num, r2.n_den, r2.n_num};
-    double v[4];
-    block_reduce_parts_n<4>(parts, cnt, v);
-    if (r1.num) c1 = (v[0] > 0.0 && isfinite(v[0]) && isfinite(v[1])) ? v[1] / v[0] : 0.0;
-    if (u2) c2 = (v[2] > 0.0 && isfinite(v[2]) && isfinite(v[3])) ? v[3] / v[2] : 0.0;
-  }
+  double c1, c2;
+  cycle_coefficients(r1, r2, u2 != nullptr, c1, c2);
   const int ilo = row1 > 0 ? row0 : 0, ihi = row1 > 0 ? row1 : n;
   for (int i = ilo + blockIdx.x * kBlock + threadIdx.x; i < ihi; i += gridDim.x * kBlock) {
-    const size_t a = 3 * (size_t)agg[i], o = 3 * (size_t)i;
-    double w0 = c1 * u1[a], w1 = c1 * u1[a + 1], w = c1 * u1[a + 2];
-    if (u2) {
-      w0 += c2 * u2[a]; w1 += c2 * u2[a + 1]; w += c2 * u2[a + 2];
-    }
+    const size_t o = 3 * (size_t)i;
+    double w[3];
+    coarse_operand(u1, u2, c1, c2, 3 * (size_t)agg[i], w);
     if (xadd) {
-      w0 += xadd[o]; w1 += xadd[o + 1];
+      w[0] += xadd[o]; w[1] += xadd[o + 1];
       x[o + 2] += xadd[o + 2];
     }
-    x[o] += w0 - d[2 * (size_t)i + 1] * w;
-    x[o + 1] += w1 + d[2 * (size_t)i] * w;
-    x[o + 2] += w;
+    rigid_add(d[2 * (size_t)i], d[2 * (size_t)i + 1], w, x + o);
   }
 }
 
@@ -1065,43 +952,25 @@ __global__ __launch_bounds__(kBlock) void k_prolong_rows(int nrows, const int* _
                                                          const double* __restrict__ u2, SpmvRatio r2, double* __restrict__ x,
                                                          const PcgScalars* S) {
   if (S && S->stop) return;
-  double c1 = 1.0, c2 = 0.0;
-  if (r1.num || u2) {
-    const double* const parts[4] = {r1.num ? r1.den : nullptr, r1.num, (u2 && r2.num) ? r2.den : nullptr, u2 ? r2.num : nullptr};
-    const int cnt[4] = {r1.n_den, r1.n_num, r2.n_den, r2.n_num};
-    double v[4];
-    block_reduce_parts_n<4>(parts, cnt, v);
-    if (r1.num) c1 = (v[0] > 0.0 && isfinite(v[0]) && isfinite(v[1])) ? v[1] / v[0] : 0.0;
-    if (u2) c2 = (v[2] > 0.0 && isfinite(v[2]) && isfinite(v[3])) ? v[3] / v[2] : 0.0;
-  }
+  double c1, c2;
+  cycle_coefficients(r1, r2, u2 != nullptr, c1, c2);
   for (int t = blockIdx.x * kBlock + threadIdx.x; t < nrows; t += gridDim.x * kBlock) {
     const size_t i = (size_t)rows[t], o = 3 * i;
     if (P.np > 0) {
       double acc[3] = {0.0, 0.0, 0.0};
       for (int e = P.rowptr[i]; e < P.rowptr[i + 1]; ++e) {
-        const size_t a = 3 * (size_t)P.col[e];
-        double w0 = c1 * u1[a], w1 = c1 * u1[a + 1], w2 = c1 * u1[a + 2];
-        if (u2) {
-          w0 += c2 * u2[a]; w1 += c2 * u2[a + 1]; w2 += c2 * u2[a + 2];
-        }
+        double w[3], b[9];
+        coarse_operand(u1, u2, c1, c2, 3 * (size_t)P.col[e], w);
         const double* bl = P.blk + 9 * (size_t)e;
-        double b[9];
 #pragma unroll
         for (int q = 0; q < 9; ++q) b[q] = (double)(float)bl[q];
-        acc[0] += b[0] * w0 + b[1] * w1 + b[2] * w2;
-        acc[1] += b[3] * w0 + b[4] * w1 + b[5] * w2;
-        acc[2] += b[6] * w0 + b[7] * w1 + b[8] * w2;
+        block_mul_acc(b, w, acc);
       }
       x[o] += acc[0]; x[o + 1] += acc[1]; x[o + 2] += acc[2];
     } else {
-      const size_t a = 3 * (size_t)agg[i];
-      double w0 = c1 * u1[a], w1 = c1 * u1[a + 1], w = c1 * u1[a + 2];
-      if (u2) {
-        w0 += c2 * u2[a]; w1 += c2 * u2[a + 1]; w += c2 * u2[a + 2];
-      }
-      x[o] += w0 - d[2 * i + 1] * w;
-      x[o + 1] += w1 + d[2 * i] * w;
-      x[o + 2] += w;
+      double w[3];
+      coarse_operand(u1, u2, c1, c2, 3 * (size_t)agg[i], w);
+      rigid_add(d[2 * i], d[2 * i + 1], w, x + o);
     }
   }
 }

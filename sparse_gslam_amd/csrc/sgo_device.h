@@ -1,5 +1,6 @@
 // sgo_device.h -- device-side helpers shared by the HIP translation units (the arithmetic of EdgeSE2,
-// wave64 reductions, the wavefront segmented scan, the XCD-aware group walk).
+// wave64 reductions, the wavefront segmented scan, the XCD-aware group walk and its frame, the arithmetic of the
+// multigrid cycle).
 #pragma once
 #include "sgo_internal.h"
 
@@ -302,13 +303,18 @@ __device__ __forceinline__ void seg_scan_step(int row, double (&v)[N]) {
   }
 }
 template <int N>
-__device__ __forceinline__ void seg_scan(int row, double (&v)[N], int /*lane*/) {
+__device__ __forceinline__ void seg_scan(int row, double (&v)[N]) {
   seg_scan_step<N, 0x111, 0xF>(row, v);   // row_shr:1
   seg_scan_step<N, 0x112, 0xF>(row, v);   // row_shr:2
   seg_scan_step<N, 0x114, 0xF>(row, v);   // row_shr:4
   seg_scan_step<N, 0x118, 0xF>(row, v);   // row_shr:8
   seg_scan_step<N, 0x142, 0xA>(row, v);   // row_bcast15 into rows 1 and 3
   seg_scan_step<N, 0x143, 0xC>(row, v);   // row_bcast31 into rows 2 and 3
+}
+// After seg_scan: this lane is the last of its segment and holds the segment's sums (inactive lanes, key < 0: never).
+__device__ __forceinline__ bool segment_end(int key, int lane) {
+  const int kn = next_lane_key(key);
+  return key >= 0 && (lane == 63 || kn != key);
 }
 
 // Row-major 3x3 block of LOGICAL slot k of a level's operator: from the slot-indexed pair-SoA array on
@@ -351,21 +357,150 @@ __device__ __forceinline__ void load_block(const BsrDev& A, size_t k, double (&b
 // the observed round-robin dispatch; speed only, never correctness) walks the contiguous band
 // [x * ngrp / 8, (x + 1) * ngrp / 8) of groups.
 // (nblocks: the workgroups that walk -- a multiple of 8; block: this workgroup's index among them.  NB, B: int or unsigned
-// as the caller has them, so that a built-in index keeps its unsigned shift)
-template <class NB, class B>
+// as the caller has them, so that a built-in index keeps its unsigned shift.  WAVES: the waves of a workgroup)
+template <int WAVES = kWavesPerBlock, class NB, class B>
 __device__ __forceinline__ void group_walk_b(int ngrp, NB nblocks, B block, int* first, int* last, int* stride) {
   const int xcd = block & 7, slot = block >> 3, per_xcd = nblocks >> 3;
   const int lo = (int)(((long long)ngrp * xcd) >> 3), hi = (int)(((long long)ngrp * (xcd + 1)) >> 3);
-  *first = lo + slot * kWavesPerBlock + (threadIdx.x >> 6);
+  *first = lo + slot * WAVES + (threadIdx.x >> 6);
   *last = hi;
-  *stride = per_xcd * kWavesPerBlock;
-}
-// (the walkers are the launch's first nblocks workgroups; it may carry more behind them with another job)
-__device__ __forceinline__ void group_walk_n(int ngrp, int nblocks, int* first, int* last, int* stride) {
-  group_walk_b(ngrp, nblocks, blockIdx.x, first, last, stride);
+  *stride = per_xcd * WAVES;
 }
 __device__ __forceinline__ void group_walk(int ngrp, int* first, int* last, int* stride) {
   group_walk_b(ngrp, gridDim.x, blockIdx.x, first, last, stride);
+}
+
+// The frame of a row-group walk inside a replayed PCG iteration, where a launch is a chain of dependent memory round trips:
+// the cursor requests its wave's FIRST group's bounds when it is made -- before the kernel waits for the stop flag --, so
+// that the two round trips overlap; the later groups' bounds are read as the walk reaches them (group_bounds, in a loop
+// for (bool first = true; gc.g < gc.gend; gc.g += gc.gstride, first = false) that ends in seg_scan and segment_end).
+// (restrict_groups, k_prolong_p, k_prolong_fold, k_up_fold, k_restrict in sgo_amg.hip, spmv0_groups below; k_spmv in
+// sgo_kernels.hip spells the cursor out.  base: the walk covers the groups [base, base + ngrp).  The set-up and refresh
+// kernels -- k_linearize, k_galerkin, k_filtered_diag, k_p_values, k_block_products -- have no stop flag to overlap the
+// request with: they take group_walk and segment_end only.)
+struct GroupCursor {
+  int g, gend, gstride;   // this wave's group, the end of its XCD's band, the stride
+  int gb0, ge0;           // the first group's bounds
+};
+template <int WAVES = kWavesPerBlock, class NB, class B>
+__device__ __forceinline__ GroupCursor group_cursor(const int* __restrict__ grp, int ngrp, NB nblocks, B block, int base = 0) {
+  GroupCursor c = {0, 0, 0, 0, 0};
+  group_walk_b<WAVES>(ngrp, nblocks, block, &c.g, &c.gend, &c.gstride);
+  c.g += base;
+  c.gend += base;
+  if (c.g < c.gend) {
+    c.gb0 = grp[c.g];
+    c.ge0 = grp[c.g + 1];
+  }
+  return c;
+}
+__device__ __forceinline__ void group_bounds(const GroupCursor& c, const int* __restrict__ grp, bool first, int& gb, int& ge) {
+  gb = first ? c.gb0 : grp[c.g];
+  ge = first ? c.ge0 : grp[c.g + 1];
+}
+
+// ---------------------------------------------------------------------------- the arithmetic of the multigrid cycle
+// One statement of what the cycle's kernels share, in layers: coefficients -> coarse operand -> 3x3 block products -> rigid-body
+// transfer -> block-Jacobi pieces.  Loops, loads and epilogues stay in the kernels.  k_spmv keeps its own copy (reason there).
+// K-cycle coefficients (Notay's flexible-CG steps per level): c = sum(num) / sum(den) of per-workgroup partial sums that
+// every workgroup re-reduces in the same fixed order; not positive or not finite gives 0.  (k_prolong_fold calls only this.)
+__device__ __forceinline__ double cycle_ratio(double den, double num) {
+  return (den > 0.0 && isfinite(den) && isfinite(num)) ? num / den : 0.0;
+}
+// c1 = ratio r1 (no numerator: 1), c2 = ratio r2 when use2 (otherwise 0): all partial sums in ONE block reduction; none at
+// all for the plain V-cycle's unscaled correction.  Callers build a ratio full or leave it default, and a second vector
+// always comes with its ratio (fcg in sgo_amg.hip): a denominator alone, or use2 with an empty r2 (c2 = 0 here), is made by nobody.
+// (k_prolong_p, k_up_fold, k_prolong_add, k_prolong_rows in sgo_amg.hip; ratios2 in sgo_kernels.hip is k_spmv's own copy.)
+__device__ __forceinline__ void cycle_coefficients(const SpmvRatio& r1, const SpmvRatio& r2, bool use2, double& c1, double& c2) {
+  c1 = 1.0;
+  c2 = 0.0;
+  if (!r1.num && !use2) return;
+  const double* const parts[4] = {r1.num ? r1.den : nullptr, r1.num, (use2 && r2.num) ? r2.den : nullptr,
+                                  use2 ? r2.num : nullptr};
+  const int cnt[4] = {r1.n_den, r1.n_num, r2.n_den, r2.n_num};
+  double v[4];
+  block_reduce_parts_n<4>(parts, cnt, v);
+  if (r1.num) c1 = cycle_ratio(v[0], v[1]);
+  if (use2) c2 = cycle_ratio(v[2], v[3]);
+}
+
+// The coarse correction a level prolongates, itself the flexible-CG combination of the child level's two steps:
+//   w = c1 u1[a .. a+2] (+ c2 u2[a .. a+2] when there is a second step)        (a = 3 x the coarse node)
+// (k_prolong_p, k_prolong_fold, k_up_fold, k_prolong_add, k_prolong_rows)
+__device__ __forceinline__ void coarse_operand(const double* __restrict__ u1, const double* __restrict__ u2, double c1, double c2,
+                                               size_t a, double (&w)[3]) {
+  w[0] = c1 * u1[a]; w[1] = c1 * u1[a + 1]; w[2] = c1 * u1[a + 2];
+  if (u2) {
+    w[0] += c2 * u2[a]; w[1] += c2 * u2[a + 1]; w[2] += c2 * u2[a + 2];
+  }
+}
+
+// acc[0..2] += B x for a row-major 3x3 block B  (k_prolong_p, k_prolong_fold, k_up_fold, k_prolong_rows; tile_slot)
+__device__ __forceinline__ void block_mul_acc(const double (&b)[9], const double (&x)[3], double* acc) {
+  acc[0] += b[0] * x[0] + b[1] * x[1] + b[2] * x[2];
+  acc[1] += b[3] * x[0] + b[4] * x[1] + b[5] * x[2];
+  acc[2] += b[6] * x[0] + b[7] * x[1] + b[8] * x[2];
+}
+// the same with the block as a coarse level's pair-SoA storage hands it over: component pairs 01 23 45 67 and 8  (k_up_fold)
+__device__ __forceinline__ void block_mul_acc(double2 p0, double2 p1, double2 p2, double2 p3, double b8, const double (&x)[3], double* acc) {
+  acc[0] += p0.x * x[0] + p0.y * x[1] + p1.x * x[2];
+  acc[1] += p1.y * x[0] + p2.x * x[1] + p2.y * x[2];
+  acc[2] += p3.x * x[0] + p3.y * x[1] + b8 * x[2];
+}
+// acc[0..2] += B^T r  (restrict_groups: the restriction with the transfer's transpose)
+__device__ __forceinline__ void block_tmul_acc(const double (&b)[9], const double (&r)[3], double* acc) {
+  acc[0] += b[0] * r[0] + b[3] * r[1] + b[6] * r[2];
+  acc[1] += b[1] * r[0] + b[4] * r[1] + b[7] * r[2];
+  acc[2] += b[2] * r[0] + b[5] * r[1] + b[8] * r[2];
+}
+
+// The tentative transfer: a node at lever arm d = (d_x, d_y) from its aggregate's centre moves with the aggregate's rigid
+// motion, T(d) = [[1, 0, -d_y], [0, 1, d_x], [0, 0, 1]] (sgo_amg.hip's header).
+//   x += T(d) w             (k_prolong_add, k_prolong_rows)
+__device__ __forceinline__ void rigid_add(double dx, double dy, const double (&w)[3], double* x) {
+  x[0] += w[0] - dy * w[2]; x[1] += w[1] + dx * w[2]; x[2] += w[2];
+}
+//   acc[0..2] += T(d)^T r   (k_restrict)
+__device__ __forceinline__ void rigid_t_acc(double dx, double dy, const double (&r)[3], double* acc) {
+  acc[0] += r[0]; acc[1] += r[1]; acc[2] += -dy * r[0] + dx * r[1] + r[2];
+}
+//   B T(d) keeps B's first two columns; its third column is m = -d_y col0 + d_x col1 + col2
+//   (k_galerkin; k_filtered_diag and k_p_values accumulate it as it stands: block_rigid_acc)
+__device__ __forceinline__ void block_rigid_col(const double (&b)[9], double dx, double dy, double (&m)[3]) {
+  m[0] = -dy * b[0] + dx * b[1] + b[2];
+  m[1] = -dy * b[3] + dx * b[4] + b[5];
+  m[2] = -dy * b[6] + dx * b[7] + b[8];
+}
+__device__ __forceinline__ void block_rigid_acc(const double (&b)[9], double dx, double dy, double* acc) {
+  acc[0] += b[0]; acc[1] += b[1]; acc[2] += -dy * b[0] + dx * b[1] + b[2];
+  acc[3] += b[3]; acc[4] += b[4]; acc[5] += -dy * b[3] + dx * b[4] + b[5];
+  acc[6] += b[6]; acc[7] += b[7]; acc[8] += -dy * b[6] + dx * b[7] + b[8];
+}
+//   acc += T(d_i)^T M with M = B T(d_j) = [col0 col1 m]: M's first two rows as they are, the third row
+//   -d_y row0 + d_x row1 + row2  -- together T_i^T B T_j, one term of the Galerkin sum  (k_galerkin)
+__device__ __forceinline__ void rigid_t_block_acc(const double (&b)[9], const double (&m)[3], double dx, double dy, double* acc) {
+  acc[0] += b[0]; acc[1] += b[1]; acc[2] += m[0];
+  acc[3] += b[3]; acc[4] += b[4]; acc[5] += m[1];
+  acc[6] += -dy * b[0] + dx * b[3] + b[6]; acc[7] += -dy * b[1] + dx * b[4] + b[7];
+  acc[8] += -dy * m[0] + dx * m[1] + m[2];
+}
+
+// The block-Jacobi smoother's pieces; symmetric 3x3 blocks in the packing 00 01 02 11 12 22.
+//   o = omega Dinv v        (k_up_fold: operand and both sweeps; spmv0_groups' and k_spmv0t's Jacobi epilogue)
+__device__ __forceinline__ void dinv_apply(const double* __restrict__ di, double omega, const double (&v)[3], double (&o)[3]) {
+  o[0] = omega * (di[0] * v[0] + di[1] * v[1] + di[2] * v[2]);
+  o[1] = omega * (di[1] * v[0] + di[3] * v[1] + di[4] * v[2]);
+  o[2] = omega * (di[2] * v[0] + di[4] * v[1] + di[5] * v[2]);
+}
+//   Dinv = D^-1 by cofactors; a determinant that is zero or not finite gives the zero block (the row is then not smoothed)
+//   (k_finalize for level 0, k_level_dinv for the coarse levels)
+__device__ __forceinline__ void dinv_from_block(const double (&d)[6], double* __restrict__ di) {
+  const double d00 = d[0], d01 = d[1], d02 = d[2], d11 = d[3], d12 = d[4], d22 = d[5];
+  const double c00 = d11 * d22 - d12 * d12, c01 = d02 * d12 - d01 * d22, c02 = d01 * d12 - d02 * d11;
+  const double c11 = d00 * d22 - d02 * d02, c12 = d01 * d02 - d00 * d12, c22 = d00 * d11 - d01 * d01;
+  const double det = d00 * c00 + d01 * c01 + d02 * c02;
+  const double id = (det != 0.0 && isfinite(det)) ? 1.0 / det : 0.0;
+  di[0] = c00 * id; di[1] = c01 * id; di[2] = c02 * id; di[3] = c11 * id; di[4] = c12 * id; di[5] = c22 * id;
 }
 
 // Body of the wave-group level-0 product k_spmv0 (sgo_kernels.hip; modes and storage described there): the first
@@ -382,18 +517,17 @@ __device__ __forceinline__ void spmv0_groups(const Sym0Dev& A, const Spmv0Args& 
   const double2* __restrict__ bp = reinterpret_cast<const double2*>(A.ublk);
   double dotacc[2] = {0.0, 0.0};
   const int ulo = a.u1 > 0 ? a.u0 : 0, uhi = a.u1 > 0 ? a.u1 : A.ngrp;
-  int g, gend, gstride;
-  group_walk_n(uhi - ulo, nblocks, &g, &gend, &gstride);
-  g += ulo;
-  gend += ulo;
-  int f_gb = 0, f_ge = 0, f_r0 = 0, f_ob = 0, f_tb = 0;
-  if (g < gend) {
-    f_gb = A.grp[g]; f_ge = A.grp[g + 1]; f_r0 = A.grow[g]; f_ob = A.gown[g]; f_tb = A.gtr[g];
+  GroupCursor gc = group_cursor(A.grp, uhi - ulo, nblocks, blockIdx.x, ulo);
+  int f_r0 = 0, f_ob = 0, f_tb = 0;
+  if (gc.g < gc.gend) {
+    f_r0 = A.grow[gc.g]; f_ob = A.gown[gc.g]; f_tb = A.gtr[gc.g];
   }
   if (a.S && a.S->stop) return;
-  for (bool first = true; g < gend; g += gstride, first = false) {
-    const int gb = first ? f_gb : A.grp[g], ge = first ? f_ge : A.grp[g + 1], r0 = first ? f_r0 : A.grow[g];
-    int ob = first ? f_ob : A.gown[g], tb = first ? f_tb : A.gtr[g];
+  for (bool first = true; gc.g < gc.gend; gc.g += gc.gstride, first = false) {
+    int gb, ge;
+    group_bounds(gc, A.grp, first, gb, ge);
+    const int r0 = first ? f_r0 : A.grow[gc.g];
+    int ob = first ? f_ob : A.gown[gc.g], tb = first ? f_tb : A.gtr[gc.g];
     double acc[3] = {0.0, 0.0, 0.0};
     int row = -1 - lane;
     for (int kb = gb; kb < ge; kb += 64) {
@@ -427,7 +561,7 @@ __device__ __forceinline__ void spmv0_groups(const Sym0Dev& A, const Spmv0Args& 
     }
     // the row's own data, requested by every lane of the row (one address per row) before the scan
     double dd0 = 0, dd1 = 0, dd2 = 0, dd3 = 0, dd4 = 0, dd5 = 0, s0 = 0, s1 = 0, s2 = 0, rb0 = 0, rb1 = 0, rb2 = 0;
-    double di0 = 0, di1 = 0, di2 = 0, di3 = 0, di4 = 0, di5 = 0;
+    double di[6] = {0, 0, 0, 0, 0, 0};
     if (row >= 0) {
       const size_t o = 3 * (size_t)row;
       const double* dd = A.dblk + 6 * (size_t)row;
@@ -437,25 +571,24 @@ __device__ __forceinline__ void spmv0_groups(const Sym0Dev& A, const Spmv0Args& 
         rb0 = a.b[o]; rb1 = a.b[o + 1]; rb2 = a.b[o + 2];
       }
       if (MODE == S0_JACOBI) {
-        const double* di = A.dinv + 6 * (size_t)row;
-        di0 = di[0]; di1 = di[1]; di2 = di[2]; di3 = di[3]; di4 = di[4]; di5 = di[5];
+#pragma unroll
+        for (int q = 0; q < 6; ++q) di[q] = A.dinv[6 * (size_t)row + q];
       }
     }
-    seg_scan<3>(row, acc, lane);
-    const int rn = next_lane_key(row);
-    if (row >= 0 && (lane == 63 || rn != row)) {
+    seg_scan<3>(row, acc);
+    if (segment_end(row, lane)) {
       const size_t o = 3 * (size_t)row;
       double o0 = acc[0] + dd0 * s0 + dd1 * s1 + dd2 * s2;
       double o1 = acc[1] + dd1 * s0 + dd3 * s1 + dd4 * s2;
       double o2 = acc[2] + dd2 * s0 + dd4 * s1 + dd5 * s2;
       if (MODE != S0_AX) {
-        const double t0 = rb0 - o0, t1 = rb1 - o1, t2 = rb2 - o2;
+        const double t[3] = {rb0 - o0, rb1 - o1, rb2 - o2};
         if (MODE == S0_JACOBI) {
-          o0 = s0 + a.omega * (di0 * t0 + di1 * t1 + di2 * t2);
-          o1 = s1 + a.omega * (di1 * t0 + di3 * t1 + di4 * t2);
-          o2 = s2 + a.omega * (di2 * t0 + di4 * t1 + di5 * t2);
+          double sw[3];
+          dinv_apply(di, a.omega, t, sw);
+          o0 = s0 + sw[0]; o1 = s1 + sw[1]; o2 = s2 + sw[2];
         } else {
-          o0 = t0; o1 = t1; o2 = t2;
+          o0 = t[0]; o1 = t[1]; o2 = t[2];
         }
       }
       a.y[o] = o0; a.y[o + 1] = o1; a.y[o + 2] = o2;

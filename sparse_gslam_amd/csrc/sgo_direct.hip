@@ -407,7 +407,7 @@ __global__ __launch_bounds__(kDT) void k_direct(DirectDev D, EdgeListDev el, dou
         const double z9[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
         store9g(D.Wo + kBS * (size_t)D.zero_slots[q], z9);
       }
-    seg_scan<2>(0, acc, lane);
+    seg_scan<2>(0, acc);
     if (lane == 63) {
       red[wave] = acc[0];
       red[16 + wave] = acc[1];
@@ -660,9 +660,8 @@ __global__ __launch_bounds__(kDT) void k_direct(DirectDev D, EdgeListDev el, dou
           for (int q = 0; q < 3; ++q) v[q] = W[q] * x0 + W[3 + q] * x1 + W[6 + q] * x2;
         }
         const int key = col >= 0 ? col : -1 - lane;
-        seg_scan<3>(key, v, lane);
-        const int nk = next_lane_key(key);
-        if (col >= 0 && (lane == 63 || nk != key)) {
+        seg_scan<3>(key, v);
+        if (segment_end(key, lane)) {
           double iv[6];
           const bool ok = inv_sym3(d00, d01, d02, d11, d12, d22, iv);
           const double r0 = xb[3 * col] - v[0], r1 = xb[3 * col + 1] - v[1], r2 = xb[3 * col + 2] - v[2];

@@ -242,9 +242,8 @@ __global__ __launch_bounds__(kBlock) void k_linearize(Sym0Dev A, int g0, int g1,
         }
       }
     }
-    seg_scan<9>(row, acc, lane);
-    const int rn = next_lane_key(row);
-    if (row >= 0 && (lane == 63 || rn != row)) {
+    seg_scan<9>(row, acc);
+    if (segment_end(row, lane)) {
       double* d = dgb + 9 * (size_t)row;
 #pragma unroll
       for (int c = 0; c < 9; ++c) d[c] = acc[c];
@@ -264,21 +263,18 @@ __global__ __launch_bounds__(kBlock) void k_finalize(Sym0Dev A, int row0, int ro
   double acc[2] = {0.0, 0.0};
   for (int i = row0 + blockIdx.x * kBlock + threadIdx.x; i < row1; i += gridDim.x * kBlock) {   // (multi-GPU: this rank's rows)
     const double* d = dgb + 9 * (size_t)i;
-    const double d00 = d[0], d01 = d[1], d02 = d[2], d11 = d[3], d12 = d[4], d22 = d[5];
+    const double dg[6] = {d[0], d[1], d[2], d[3], d[4], d[5]};
     const double b0 = d[6], b1 = d[7], b2 = d[8];
-    double* dd = A.dblk + 6 * (size_t)i;
-    dd[0] = d00; dd[1] = d01; dd[2] = d02; dd[3] = d11; dd[4] = d12; dd[5] = d22;
-    // symmetric 3x3 inverse by cofactors
-    const double c00 = d11 * d22 - d12 * d12, c01 = d02 * d12 - d01 * d22, c02 = d01 * d12 - d02 * d11;
-    const double c11 = d00 * d22 - d02 * d02, c12 = d01 * d02 - d00 * d12, c22 = d00 * d11 - d01 * d01;
-    const double det = d00 * c00 + d01 * c01 + d02 * c02;
-    const double id = (det != 0.0 && isfinite(det)) ? 1.0 / det : 0.0;
-    const double i00 = c00 * id, i01 = c01 * id, i02 = c02 * id, i11 = c11 * id, i12 = c12 * id, i22 = c22 * id;
-    double* di = A.dinv + 6 * (size_t)i;
-    di[0] = i00; di[1] = i01; di[2] = i02; di[3] = i11; di[4] = i12; di[5] = i22;
-    const double z0 = i00 * b0 + i01 * b1 + i02 * b2;
-    const double z1 = i01 * b0 + i11 * b1 + i12 * b2;
-    const double z2 = i02 * b0 + i12 * b1 + i22 * b2;
+    double di[6];
+    dinv_from_block(dg, di);
+#pragma unroll
+    for (int q = 0; q < 6; ++q) {
+      A.dblk[6 * (size_t)i + q] = dg[q];
+      A.dinv[6 * (size_t)i + q] = di[q];
+    }
+    const double z0 = di[0] * b0 + di[1] * b1 + di[2] * b2;
+    const double z1 = di[1] * b0 + di[3] * b1 + di[4] * b2;
+    const double z2 = di[2] * b0 + di[4] * b1 + di[5] * b2;
     const size_t o = 3 * (size_t)i;
     b[o] = b0; b[o + 1] = b1; b[o + 2] = b2;
     if (x) {
@@ -413,11 +409,16 @@ __global__ __launch_bounds__(kBlock) void k_init_scalars(PcgScalars* S, const do
 //                     dots: partials[0] = x'.y, partials[1] = x'.dotC
 // Optional dot partials (row epilogue): partials[0] += dotA[row].out[row],
 // partials[1] += dotA2[row].out[row]  or  dotB[row].dotC[row].
+// (k_spmv keeps its own copy of the coefficients and of the arithmetic around them -- cycle_coefficients, dinv_apply,
+// coarse_operand, rigid_add, block_mul_acc in sgo_device.h.  Routed through those, at equal fp64 opcode counts, the dumped
+// poses of hierarchies with tentative levels (the K-cycle: modes 4..6) differed from the parent's on the MI355X; even
+// calling cycle_ratio for the division below compiles modes 4..6 to other code.  NOTES.md section 32.)
+// cycle_coefficients' rule with three differences, none for an input a caller makes: a denominator without a numerator
+// gives 0 (there 1); use2 with an empty r2 gives c2 = 1 (there 0); and it reduces even when both ratios are default.
 __device__ __forceinline__ double ratio_value(const SpmvRatio& r, double den, double num) {
   if (!r.num) return r.den ? 0.0 : 1.0;
   return (den > 0.0 && isfinite(den) && isfinite(num)) ? num / den : 0.0;
 }
-// c1 = ratio r1, c2 = ratio r2 (only when use2): all partial sums in one block reduction
 __device__ __forceinline__ void ratios2(const SpmvRatio& r1, const SpmvRatio& r2, bool use2, double& c1, double& c2) {
   const double* const parts[4] = {r1.num ? r1.den : nullptr, r1.num, (use2 && r2.num) ? r2.den : nullptr,
                                   use2 ? r2.num : nullptr};
@@ -495,9 +496,8 @@ void k_spmv(BsrDev A, SpmvArgs a) {
       acc[1] += b3 * x0 + b4 * x1 + b5 * x2;
       acc[2] += b6 * x0 + b7 * x1 + b8 * x2;
     }
-    seg_scan<3>(row, acc, lane);
-    const int rn = next_lane_key(row);
-    if (row >= 0 && (lane == 63 || rn != row)) {
+    seg_scan<3>(row, acc);
+    if (segment_end(row, lane)) {
       const size_t o = 3 * (size_t)row;
       double o0 = acc[0], o1 = acc[1], o2 = acc[2];
       if (MODE == SPMV_AX_C) {
@@ -621,10 +621,8 @@ __device__ __forceinline__ void tile_group_load(const Sym0Dev& A, const Tile0Dev
 __device__ __forceinline__ void tile_slot(const double* __restrict__ xs, double* __restrict__ vst, int rowl, unsigned cw,
                                           const double (&b)[9], double (&acc)[3]) {
   const double* xc = xs + 3 * (cw & 0xFFFFu);
-  const double x0 = xc[0], x1 = xc[1], x2 = xc[2];
-  acc[0] += b[0] * x0 + b[1] * x1 + b[2] * x2;
-  acc[1] += b[3] * x0 + b[4] * x1 + b[5] * x2;
-  acc[2] += b[6] * x0 + b[7] * x1 + b[8] * x2;
+  const double x[3] = {xc[0], xc[1], xc[2]};
+  block_mul_acc(b, x, acc);
   const unsigned vp = cw >> 16;
   if (vp != 0xFFFFu) {   // the twin row is in this tile: hand it B^T x_row through LDS
     const double* xr = xs + 3 * rowl;
@@ -741,9 +739,8 @@ __global__ __launch_bounds__(kTileThreads) void k_spmv0t(Sym0Dev A, Tile0Dev TL,
         bl.get(b);
         tile_slot(xs, vst, row - T.row0, cw, b, acc);
       }
-      seg_scan<3>(row, acc, lane);
-      const int rn = next_lane_key(row);
-      if (row >= 0 && (lane == 63 || rn != row)) {   // a row's owned slots sit in exactly one group: single writer
+      seg_scan<3>(row, acc);
+      if (segment_end(row, lane)) {   // a row's owned slots sit in exactly one group: single writer
         double* d = ys + 3 * (row - T.row0);
         d[0] = acc[0]; d[1] = acc[1]; d[2] = acc[2];
       }
@@ -788,14 +785,13 @@ __global__ __launch_bounds__(kTileThreads) void k_spmv0t(Sym0Dev A, Tile0Dev TL,
       o2 += dd2 * s0 + dd4 * s1 + dd5 * s2;
       const size_t o = 3 * (size_t)r;
       if (MODE != S0_AX) {
-        const double t0 = a.b[o] - o0, t1 = a.b[o + 1] - o1, t2 = a.b[o + 2] - o2;
+        const double tt[3] = {a.b[o] - o0, a.b[o + 1] - o1, a.b[o + 2] - o2};
         if (MODE == S0_JACOBI) {
-          const double* di = A.dinv + 6 * (size_t)r;
-          o0 = s0 + a.omega * (di[0] * t0 + di[1] * t1 + di[2] * t2);
-          o1 = s1 + a.omega * (di[1] * t0 + di[3] * t1 + di[4] * t2);
-          o2 = s2 + a.omega * (di[2] * t0 + di[4] * t1 + di[5] * t2);
+          double sw[3];
+          dinv_apply(A.dinv + 6 * (size_t)r, a.omega, tt, sw);
+          o0 = s0 + sw[0]; o1 = s1 + sw[1]; o2 = s2 + sw[2];
         } else {
-          o0 = t0; o1 = t1; o2 = t2;
+          o0 = tt[0]; o1 = tt[1]; o2 = tt[2];
         }
       }
       a.y[o] = o0; a.y[o + 1] = o1; a.y[o + 2] = o2;

@@ -12,7 +12,8 @@ np.longdouble (x86-64: eps 1.08e-19, asserted in kernel_reference), so the refer
 output entry y gets  |y_device - y_ref| <= C_stage * U * abs(y),  U = 2^-53, abs(y) the same expression evaluated on magnitudes.
 Large stages run in chunks of CHUNK block products.
 
-The stages, with the comment in sgo_amg.hip that states the formula:
+The stages, with the comment in sgo_amg.hip that states the formula (T(d), B T(d), T(d)^T M and the cofactor inverse of a
+symmetric block are stated once, in sgo_device.h under "the arithmetic of the multigrid cycle"):
 1 partition   agg maps onto [0, nc), every aggregate non-empty, (mem_ptr, mem) lists the same partition.
 2 geometry    (k_positions0, k_centres) level-0 pos = the free poses' xy, bitwise; pos_{l+1}[a] = mean of its members: the kernel
               forms sum * (1 / count), lanes then a wave tree: abs = sum |pos| / count; d_i = pos_i - c_agg(i) with the exported
@@ -34,7 +35,7 @@ The stages, with the comment in sgo_amg.hip that states the formula:
 6 Galerkin    (k_block_products) AP_f = sum A_k P_e over k = (i, j), e = (j, c): complete pattern; A_{l+1}(a, c) = sum P_e^T AP_f
               over e = (i, a), f = (i, c) on the slots c >= a, the others bitwise transposes; tentative levels (k_galerkin)
               A_{l+1}(a, c) = sum T_i^T A_k T_j over the slots with agg(i) = a, agg(j) = c.  abs: the same sums on magnitudes.
-              dinv of level l+1 (k_level_dinv): inverse of its SYMMETRISED diagonal blocks (D + D^T) / 2 -- the diagonal slot is
+              dinv of level l+1 (k_level_dinv, dinv_from_block): inverse of its SYMMETRISED diagonal blocks (D + D^T) / 2 -- the diagonal slot is
               summed in full, symmetric only up to the Galerkin sum's rounding, which is U abs of that sum and not U |D|: next to
               closures of 10^10 the two inverses differ by 10^4 U kappa --, bound as dinvF's.
 7 folded      (k_ptilde_values) P~_f = P_(row, col) - omega Dinv_i AP_f on A P's pattern; the two fp32 copies agree bitwise and lie
