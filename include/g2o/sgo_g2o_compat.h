@@ -18,7 +18,7 @@
 //   * activeChi2() is the un-robustified sum, activeRobustChi2() the robustified one.
 //
 // Backend: a graph whose active vertices are all VertexSE2 and whose active edges are all EdgeSE2
-// (robust kernel: none or RobustKernelDCS) optimised with OptimizationAlgorithmGaussNewton -- the
+// (robust kernel: none, RobustKernelDCS or another kernel of robust_kernel_impl.h) optimised with OptimizationAlgorithmGaussNewton -- the
 // reference's pose graph (graphs.cpp:17-23), the hot path -- ALWAYS runs on the GPU through
 // sgo_optimize_gn; if the device or libsgo is unavailable optimize() fails loudly, there is no
 // CPU fallback for it.  Every other combination (the reference's landmark graph: Levenberg,
@@ -259,6 +259,121 @@ class RobustKernelDCS : public RobustKernel {
     }
   }
 };
+// The other kernels of robust_kernel_impl.h that the GPU path evaluates (include/sgo.h lists the pairs rho[0], rho[1]; the
+// SGO_KERNEL_* number of a class is sgoRobustKernelKind's).  rho[2] as g2o has it: nothing here reads it (robustInformation is
+// rho[1] Omega, the second-order term is disabled upstream).
+class RobustKernelHuber : public RobustKernel {
+ public:
+  void robustify(double e, Vector3& rho) const override {
+    const double dsqr = _delta * _delta;
+    if (e <= dsqr) {
+      rho[0] = e;
+      rho[1] = 1.;
+      rho[2] = 0.;
+    } else {
+      const double sqrte = std::sqrt(e);
+      rho[0] = 2 * sqrte * _delta - dsqr;
+      rho[1] = _delta / sqrte;
+      rho[2] = -0.5 * rho[1] / e;
+    }
+  }
+};
+class RobustKernelPseudoHuber : public RobustKernel {
+ public:
+  void robustify(double e2, Vector3& rho) const override {
+    const double dsqr = _delta * _delta;
+    const double aux = std::sqrt(1 + e2 / dsqr);
+    rho[0] = 2 * dsqr * (aux - 1);
+    rho[1] = 1. / aux;
+    rho[2] = -0.5 / dsqr * rho[1] / (aux * aux);
+  }
+};
+class RobustKernelCauchy : public RobustKernel {
+ public:
+  void robustify(double e2, Vector3& rho) const override {
+    const double dsqr = _delta * _delta;
+    const double aux = 1 + e2 / dsqr;
+    rho[0] = dsqr * std::log(aux);
+    rho[1] = 1. / aux;
+    rho[2] = -1. / dsqr * rho[1] * rho[1];
+  }
+};
+class RobustKernelGemanMcClure : public RobustKernel {
+ public:
+  void robustify(double e2, Vector3& rho) const override {
+    const double aux = 1. / (1. + e2);
+    rho[0] = e2 * aux;
+    rho[1] = aux * aux;
+    rho[2] = -2. * rho[1] * aux;
+  }
+};
+class RobustKernelWelsch : public RobustKernel {
+ public:
+  void robustify(double e2, Vector3& rho) const override {
+    const double dsqr = _delta * _delta;
+    const double aux = std::exp(-e2 / dsqr);
+    rho[0] = dsqr * (1. - aux);
+    rho[1] = aux;
+    rho[2] = -aux / dsqr;
+  }
+};
+class RobustKernelFair : public RobustKernel {
+ public:
+  void robustify(double e2, Vector3& rho) const override {
+    const double sqrte = std::sqrt(e2);
+    const double aux = sqrte / _delta;
+    rho[0] = 2. * _delta * _delta * (aux - std::log1p(aux));
+    rho[1] = 1. / (1. + aux);
+    rho[2] = sqrte > 0. ? -0.5 / (sqrte * (_delta + sqrte) * (1. + aux)) : 0.;
+  }
+};
+class RobustKernelTukey : public RobustKernel {
+ public:
+  void robustify(double e2, Vector3& rho) const override {
+    const double e = std::sqrt(e2);
+    const double delta2 = _delta * _delta;
+    if (e <= _delta) {
+      const double aux = 1. - e2 / delta2;
+      rho[0] = delta2 * (1. - aux * aux * aux) / 3.;
+      rho[1] = aux * aux;
+      rho[2] = -2. * aux / delta2;
+    } else {
+      rho[0] = delta2 / 3.;
+      rho[1] = 0;
+      rho[2] = 0;
+    }
+  }
+};
+class RobustKernelSaturated : public RobustKernel {
+ public:
+  void robustify(double e2, Vector3& rho) const override {
+    const double dsqr = _delta * _delta;
+    if (e2 <= dsqr) {
+      rho[0] = e2;
+      rho[1] = 1.;
+      rho[2] = 0.;
+    } else {
+      rho[0] = dsqr;
+      rho[1] = 0.;
+      rho[2] = 0.;
+    }
+  }
+};
+// The SGO_KERNEL_* number of a kernel object (nullptr: SGO_KERNEL_NONE); -1 for a subclass the GPU path does not know.
+inline int sgoRobustKernelKind(const RobustKernel* k) {
+  if (!k) return SGO_KERNEL_NONE;
+  const std::type_info& t = typeid(*k);
+  if (t == typeid(RobustKernelDCS)) return SGO_KERNEL_DCS;
+  if (t == typeid(RobustKernelHuber)) return SGO_KERNEL_HUBER;
+  if (t == typeid(RobustKernelPseudoHuber)) return SGO_KERNEL_PSEUDO_HUBER;
+  if (t == typeid(RobustKernelCauchy)) return SGO_KERNEL_CAUCHY;
+  if (t == typeid(RobustKernelGemanMcClure)) return SGO_KERNEL_GEMAN_MCCLURE;
+  if (t == typeid(RobustKernelWelsch)) return SGO_KERNEL_WELSCH;
+  if (t == typeid(RobustKernelFair)) return SGO_KERNEL_FAIR;
+  if (t == typeid(RobustKernelTukey)) return SGO_KERNEL_TUKEY;
+  if (t == typeid(RobustKernelSaturated)) return SGO_KERNEL_SATURATED;
+  return -1;
+}
 
 // g2o/core/base_vertex.h
 template <int D, typename T>
@@ -909,11 +1024,11 @@ class SparseOptimizer : public OptimizableGraph {
     }
     if (n == 0) return -1;
     // This dense host solver exists for the landmark graph (<= a few hundred unknowns).  It is not a
-    // fallback for pose graphs: a large graph that is not (VertexSE2, EdgeSE2, no kernel or DCS,
+    // fallback for pose graphs: a large graph that is not (VertexSE2, EdgeSE2, no kernel or one of robust_kernel_impl.h,
     // Gauss-Newton) is refused instead of being solved in O(n^3) on the host.
     if (n > kHostSolverMaxUnknowns) {
       std::cerr << "SparseOptimizer::optimize: " << n << " unknowns in a graph the device path does not cover "
-                << "(only VertexSE2 / EdgeSE2 with no kernel or RobustKernelDCS under Gauss-Newton is); refusing"
+                << "(only VertexSE2 / EdgeSE2 with no kernel or a kernel of robust_kernel_impl.h under Gauss-Newton is); refusing"
                 << std::endl;
       return 0;
     }
@@ -991,7 +1106,13 @@ class SparseOptimizer : public OptimizableGraph {
       if (typeid(*v) != typeid(VertexSE2)) return false;
     for (auto* e : _activeEdges) {
       if (typeid(*e) != typeid(EdgeSE2)) return false;
-      if (e->robustKernel() && typeid(*e->robustKernel()) != typeid(RobustKernelDCS)) return false;
+      // (a kernel class the device does not evaluate, or a parameter sgo_set_robust_kernels would refuse: the host solver)
+      const int kind = sgoRobustKernelKind(e->robustKernel());
+      if (kind < 0) return false;
+      const double delta = e->robustKernel() ? e->robustKernel()->delta() : 1.0;
+      if (kind >= SGO_KERNEL_HUBER && kind != SGO_KERNEL_GEMAN_MCCLURE && !(std::isfinite(delta) && delta > 0.0)) return false;
+      // (a multi-GPU context knows DCS only: decided here, before a set-up that sgo_set_robust_kernels would then refuse)
+      if (kind >= SGO_KERNEL_HUBER && _ctx && sgo_comm_size(_ctx) > 1) return false;
     }
     return true;
   }
@@ -1036,6 +1157,7 @@ class SparseOptimizer : public OptimizableGraph {
     }
     std::vector<int32_t> ei(E), ej(E);
     std::vector<double> meas(3 * (size_t)E), info(6 * (size_t)E), phi(E);
+    std::vector<int32_t> kind(E);   // SGO_KERNEL_* of the edge's kernel; phi carries its delta whatever the kind
     for (int k = 0; k < E; ++k) {
       const EdgeSE2* e = static_cast<const EdgeSE2*>(_activeEdges[k]);
       ei[k] = static_cast<const OptimizableGraph::Vertex*>(e->vertex(0))->tempIndex();
@@ -1045,6 +1167,8 @@ class SparseOptimizer : public OptimizableGraph {
       double* o = &info[6 * (size_t)k];
       o[0] = O(0, 0); o[1] = O(0, 1); o[2] = O(0, 2); o[3] = O(1, 1); o[4] = O(1, 2); o[5] = O(2, 2);
       phi[k] = e->robustKernel() ? e->robustKernel()->delta() : -1.0;
+      kind[k] = sgoRobustKernelKind(e->robustKernel());
+      if (kind[k] == SGO_KERNEL_GEMAN_MCCLURE) phi[k] = 1.0;   // (the kernel has no parameter; the device wants a positive one)
     }
     // is the device's graph (the previous marshal) a prefix of this one?  Same vertex ids and fixed flags for its
     // vertices (compact numbers then agree), bit-identical edge records for its edges
@@ -1053,7 +1177,8 @@ class SparseOptimizer : public OptimizableGraph {
     const bool prefix = _graphOnDevice && _m.nDead == 0 && V >= dV && E >= dE && same(vid.data(), _m.vid.data(), sizeof(int32_t) * (size_t)dV) &&
                         same(fixed.data(), _m.fixed.data(), (size_t)dV) && same(ei.data(), _m.ei.data(), sizeof(int32_t) * (size_t)dE) &&
                         same(ej.data(), _m.ej.data(), sizeof(int32_t) * (size_t)dE) && same(meas.data(), _m.meas.data(), sizeof(double) * 3 * (size_t)dE) &&
-                        same(info.data(), _m.info.data(), sizeof(double) * 6 * (size_t)dE) && same(phi.data(), _m.phi.data(), sizeof(double) * (size_t)dE);
+                        same(info.data(), _m.info.data(), sizeof(double) * 6 * (size_t)dE) && same(phi.data(), _m.phi.data(), sizeof(double) * (size_t)dE) &&
+                        same(kind.data(), _m.kind.data(), sizeof(int32_t) * (size_t)dE);
     if (prefix && V == dV && E == dE) {
       if (sgo_set_poses(_ctx, poses.data()) == SGO_OK) return true;
       std::cerr << "SparseOptimizer: " << sgo_last_error(_ctx) << std::endl;
@@ -1069,7 +1194,8 @@ class SparseOptimizer : public OptimizableGraph {
       for (int r = 0; r < dE; ++r) {
         if (_m.dead[r]) continue;
         if (k < E && ei[k] == _m.ei[r] && ej[k] == _m.ej[r] && same(&meas[3 * (size_t)k], &_m.meas[3 * (size_t)r], sizeof(double) * 3) &&
-            same(&info[6 * (size_t)k], &_m.info[6 * (size_t)r], sizeof(double) * 6) && same(&phi[k], &_m.phi[r], sizeof(double)))
+            same(&info[6 * (size_t)k], &_m.info[6 * (size_t)r], sizeof(double) * 6) && same(&phi[k], &_m.phi[r], sizeof(double)) &&
+            kind[k] == _m.kind[r])
           ++k;
         else
           missing.push_back(r);
@@ -1095,6 +1221,22 @@ class SparseOptimizer : public OptimizableGraph {
       std::cerr << "SparseOptimizer: " << sgo_last_error(_ctx) << std::endl;
       return false;
     }
+    // The arrays describe every kernel as DCS with the edge's delta: the other kinds follow.  (After an update the resident
+    // prefix keeps its kinds on either of the call's routes: only the appended edges are sent.)
+    {
+      std::vector<int32_t> kid, kk;
+      std::vector<double> kd;
+      for (int k = prefix ? dE : 0; k < E; ++k)
+        if (kind[k] >= SGO_KERNEL_HUBER) {
+          kid.push_back(k);
+          kk.push_back(kind[k]);
+          kd.push_back(phi[k]);
+        }
+      if (!kid.empty() && sgo_set_robust_kernels(_ctx, (int32_t)kid.size(), kid.data(), kk.data(), kd.data()) != SGO_OK) {
+        std::cerr << "SparseOptimizer: " << sgo_last_error(_ctx) << std::endl;
+        return false;
+      }
+    }
     _graphOnDevice = true;
     _m.vid.swap(vid);
     _m.fixed.swap(fixed);
@@ -1103,6 +1245,7 @@ class SparseOptimizer : public OptimizableGraph {
     _m.meas.swap(meas);
     _m.info.swap(info);
     _m.phi.swap(phi);
+    _m.kind.swap(kind);
     _m.dead.assign((size_t)E, 0);
     _m.nDead = 0;
     return true;
@@ -1130,7 +1273,7 @@ class SparseOptimizer : public OptimizableGraph {
   sgo_ctx* _ctx = nullptr;
   bool _graphOnDevice = false;
   struct Marshalled {   // what the device holds, as it was marshalled
-    std::vector<int32_t> vid, ei, ej;
+    std::vector<int32_t> vid, ei, ej, kind;
     std::vector<uint8_t> fixed;
     std::vector<double> meas, info, phi;
     std::vector<uint8_t> dead;   // the record's edge left the graph since and is deactivated on the device (zero information)

@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define SGO_VERSION 107          /* 0.1.7: sgo_stats.pcg_converged may be 2 (a solve accepted at the floating-point floor of its system), the incremental overlay keeps 64 touched + hub rows, SGO_AMG_SETUP (no signature changed); 0.1.6: sgo_plan_rows takes the measurements (row order of graphs whose poses contradict their closures); 0.1.5: the multifrontal path for mid-size graphs (sgo_mfront_plan; sgo_solver_description names it); 0.1.4: sgo_kernel_profile_samples, sgo_update_graph_se2 (incremental set-up); 0.1.3: row-owner multi-GPU mode (sgo_comm_host_allgather, sgo_debug_level0_bytes); 0.1.2: sgo_comm_init_host; 0.1.1: sgo_opts.direct_rows (took a reserved slot), sgo_solver_description */
+#define SGO_VERSION 107          /* 0.1.7: (later additions under the same number, no signature changed: sgo_set_edge_information, sgo_gate_edges; sgo_set_robust_kernels, sgo_edge_robust, SGO_KERNEL_*); sgo_stats.pcg_converged may be 2 (a solve accepted at the floating-point floor of its system), the incremental overlay keeps 64 touched + hub rows, SGO_AMG_SETUP (no signature changed); 0.1.6: sgo_plan_rows takes the measurements (row order of graphs whose poses contradict their closures); 0.1.5: the multifrontal path for mid-size graphs (sgo_mfront_plan; sgo_solver_description names it); 0.1.4: sgo_kernel_profile_samples, sgo_update_graph_se2 (incremental set-up); 0.1.3: row-owner multi-GPU mode (sgo_comm_host_allgather, sgo_debug_level0_bytes); 0.1.2: sgo_comm_init_host; 0.1.1: sgo_opts.direct_rows (took a reserved slot), sgo_solver_description */
 #define SGO_MAX_ITERS 256        /* capacity of the per-iteration arrays in sgo_stats */
 
 /* error codes (negative).  -1 mirrors g2o's optimize() "nothing to optimise". */
@@ -244,6 +244,53 @@ int sgo_set_edge_information(sgo_ctx* ctx, int32_t n, const int32_t* edge_ids, c
  * negative code.  The decision is taken first and nothing is written when the call refuses: rules, refusals and what the next
  * solve does are sgo_set_edge_information's. */
 int sgo_gate_edges(sgo_ctx* ctx, int32_t n, const int32_t* edge_ids, double chi2_max, uint8_t* gated);
+
+/* The robust kernels of g2o's robust_kernel_impl.h, per edge.  With e = e^T Omega e, d = delta and s = sqrt(e), a kernel is the
+ * pair rho0 (what the edge adds to the robust chi2) and rho1 (the weight: g2o's robust Gauss-Newton scales the edge's
+ * information and Omega e by rho1 and uses nothing else):
+ *   NONE           e                                                 1
+ *   DCS            RobustKernelDCS, as phi >= 0 in sgo_set_graph_se2: with c = 2 d / (d + e), e and 1 if c >= 1, else c^2 e and c^2
+ *   HUBER          e if e <= d^2, else 2 s d - d^2                    1, else d / s
+ *   PSEUDO_HUBER   2 d^2 (a - 1), a = sqrt(1 + e / d^2)              1 / a
+ *   CAUCHY         d^2 log a, a = 1 + e / d^2                        1 / a
+ *   GEMAN_MCCLURE  e a, a = 1 / (1 + e)  (delta unused, as in g2o)   a^2
+ *   WELSCH         d^2 (1 - a), a = exp(-e / d^2)                    a
+ *   FAIR           2 d^2 (a - log1p a), a = s / d                    1 / (1 + a)
+ *   TUKEY          d^2 (1 - u^3) / 3, u = 1 - e / d^2, if s <= d; else d^2 / 3      u^2, else 0
+ *   SATURATED      e if e <= d^2, else d^2                           1, else 0 */
+#define SGO_KERNEL_NONE 0
+#define SGO_KERNEL_DCS 1
+#define SGO_KERNEL_HUBER 2
+#define SGO_KERNEL_PSEUDO_HUBER 3
+#define SGO_KERNEL_CAUCHY 4
+#define SGO_KERNEL_GEMAN_MCCLURE 5
+#define SGO_KERNEL_WELSCH 6
+#define SGO_KERNEL_FAIR 7
+#define SGO_KERNEL_TUKEY 8
+#define SGO_KERNEL_SATURATED 9
+
+/* Replaces: OptimizableGraph::Edge::setRobustKernel(new RobustKernelHuber / ...Cauchy / ...) with setDelta(delta) on resident
+ * edges.  edge_ids as for sgo_set_edge_information (NULL: edges 0 .. n-1; appended overlay edges included), kind[n] one of
+ * SGO_KERNEL_*, delta[n] the kernel's parameter (ignored by NONE, unused by GEMAN_MCCLURE).  Every solver path evaluates the
+ * kind where it evaluates phi; a graph that holds only NONE and DCS edges runs the kernels, and gives the bits, of one that never
+ * made this call.  Keeps every resident structure: no set-up, sgo_stats.seconds_setup does not change, an earlier sgo_linearize
+ * is void, and the first solve of the next sgo_optimize_gn / sgo_solve refreshes the hierarchy's coarse operators.  An edge whose
+ * information is zero has e = 0, where every kind gives rho0 = 0 and weight 1: deactivating and gating compose with any kind
+ * (sgo_gate_edges with NULL ids gates the edges with any kernel, all but NONE).
+ * SGO_EINVAL, with nothing on the device changed: a multi-GPU context (sgo_debug_set_shard's emulation included), an id outside
+ * [0, E), an unknown kind, a non-finite delta, delta < 0 for DCS, delta <= 0 for any other kind but NONE.  Of an id listed twice
+ * the later entry counts.
+ * sgo_set_graph_se2 resets every edge to what its phi says, NONE or DCS.  sgo_update_graph_se2 keeps the kinds of the edges
+ * [0, n_resident_edges) whichever way it takes -- as an overlay the resident prefix is not re-read; on a full set-up the context
+ * applies the kinds it remembers to those ids, with delta = the phi passed (an edge passed with phi < 0 has no kernel, an edge
+ * remembered as NONE keeps none) --, and appended edges start as NONE or DCS. */
+int sgo_set_robust_kernels(sgo_ctx* ctx, int32_t n, const int32_t* edge_ids, const int32_t* kind, const double* delta);
+
+/* Replaces: RobustKernel::robustify on every edge after computeActiveErrors().  rho0[E], weight[E] (either may be NULL) in the
+ * edge order of sgo_edge_chi2, at the current poses and with its arithmetic: the weight is DCS's switch value s^2, or any
+ * kernel's outlier score of a closure (1 = inlier, towards 0 = discounted).  Covers overlay edges; works while an overlay
+ * is resident. */
+int sgo_edge_robust(sgo_ctx* ctx, double* rho0, double* weight);
 
 /* Replaces: the covariance producer of a loop closure and its use as the edge information
  * (src/sparse_gslam/src/cartographer_bindings/fast_correlative_scan_matcher_2d.cc:537-561,

@@ -32,8 +32,12 @@ SYMBOLS = [
     "sgo_kernel_profile_samples", "sgo_update_graph_se2", "sgo_debug_lanczos", "sgo_debug_amg_array",
     "sgo_debug_overlay_array", "sgo_debug_overlay_linearize", "sgo_debug_overlay_apply",
     "sgo_debug_mfront_array", "sgo_mfront_plan_array", "sgo_debug_pcg_array", "sgo_debug_pcg_run",
-    "sgo_set_edge_information", "sgo_gate_edges",
+    "sgo_set_edge_information", "sgo_gate_edges", "sgo_set_robust_kernels", "sgo_edge_robust",
 ]
+
+# SGO_KERNEL_*: the robust kernels sgo_set_robust_kernels takes, in include/sgo.h's numbering
+KERNEL_NONE, KERNEL_DCS, KERNEL_HUBER, KERNEL_PSEUDO_HUBER, KERNEL_CAUCHY = 0, 1, 2, 3, 4
+KERNEL_GEMAN_MCCLURE, KERNEL_WELSCH, KERNEL_FAIR, KERNEL_TUKEY, KERNEL_SATURATED = 5, 6, 7, 8, 9
 
 
 class SgoError(RuntimeError):
@@ -117,6 +121,8 @@ def lib():
     L.sgo_edge_chi2.argtypes = [vp, d]
     L.sgo_set_edge_information.argtypes = [vp, C.c_int32, i32, d]
     L.sgo_gate_edges.argtypes = [vp, C.c_int32, i32, C.c_double, u8]
+    L.sgo_set_robust_kernels.argtypes = [vp, C.c_int32, i32, i32, d]
+    L.sgo_edge_robust.argtypes = [vp, d, d]
     L.sgo_num_free.argtypes = [vp]
     L.sgo_free_ids.argtypes = [vp, i32]
     L.sgo_linearize.argtypes = [vp, d, d, d, d]
@@ -465,6 +471,23 @@ class Optimizer:
         k = self._check(lib().sgo_gate_edges(self._h, 0 if ids is None else ids.size, None if ids is None else _ip(ids),
                                              float(chi2_max), gated.ctypes.data_as(C.POINTER(C.c_uint8))), "sgo_gate_edges")
         return k, gated.astype(bool)
+
+    def set_robust_kernels(self, edge_ids, kind, delta):
+        """sgo_set_robust_kernels: the robust kernel (KERNEL_*) and its parameter for resident edges (edge_ids None: edges
+        0 .. n-1); kind and delta broadcast over the edges.  No set-up runs; SgoError (rc=-2) with the device untouched when the
+        call refuses."""
+        ids = None if edge_ids is None else np.ascontiguousarray(edge_ids, dtype=np.int32).reshape(-1)
+        n = np.broadcast(np.asarray(kind), np.asarray(delta)).size if ids is None else ids.size
+        k = np.ascontiguousarray(np.broadcast_to(np.asarray(kind, dtype=np.int32).reshape(-1), (n,)))
+        dl = np.ascontiguousarray(np.broadcast_to(np.asarray(delta, dtype=np.float64).reshape(-1), (n,)))
+        self._check(lib().sgo_set_robust_kernels(self._h, n, None if ids is None else _ip(ids), _ip(k), _dp(dl)),
+                    "sgo_set_robust_kernels")
+
+    def edge_robust(self):
+        """sgo_edge_robust: (rho0, weight) of every edge at the current poses, in set-graph order."""
+        rho0, w = np.empty(self.E), np.empty(self.E)
+        self._check(lib().sgo_edge_robust(self._h, _dp(rho0), _dp(w)), "sgo_edge_robust")
+        return rho0, w
 
     def closure_information(self, windows, scores):
         """Covariance and information of a batch of scan-match windows (sgo_closure_information).

@@ -190,6 +190,71 @@ int edge_info_apply(sgo_ctx* c, const char* who, const std::vector<int32_t>& ids
   return SGO_OK;
 }
 
+// ---- robust kernels per edge: sgo_set_robust_kernels (include/sgo.h; kernels in sgo_gate.hip) ------------------------------------
+// What the device stores for an SGO_KERNEL_* number and its delta: the parameter beside a RobustKind byte (sgo_internal.h).
+double robust_phi(int kind, double delta) { return kind == SGO_KERNEL_NONE ? -1.0 : delta; }
+unsigned char robust_byte(int kind) { return kind >= SGO_KERNEL_HUBER ? (unsigned char)kind : (unsigned char)kRobustDcs; }
+
+// (kind, delta) for the listed edges (every id once, all in [0, E), every pair valid): the edge lists, the per-slot copies where
+// they exist, the host's record and the lists' `kinds` flag; the next solve is told that the operator changed.
+int robust_apply(sgo_ctx* c, const char* who, const std::vector<int32_t>& ids, const std::vector<int32_t>& kinds, const std::vector<double>& delta) {
+  sgo_ctx::EdgeActivity& A = c->edges;
+  sgo_ctx::RobustKinds& R = c->robust;
+  const size_t m = ids.size();
+  if (m == 0) return SGO_OK;
+  std::vector<double> phi(m);
+  std::vector<unsigned char> bytes(m);
+  for (size_t t = 0; t < m; ++t) {
+    phi[t] = robust_phi(kinds[t], delta[t]);
+    bytes[t] = robust_byte(kinds[t]);
+  }
+  int rc;
+  const bool slots = c->es.phi != nullptr && !c->rows_pending && c->d_eidx != nullptr && c->el.E > 0;
+  if ((rc = grow_scratch(c, &A.d_ids, &A.ids_cap, m)) || (rc = grow_scratch(c, &A.d_rows, &A.rows_cap, m)) ||
+      (rc = grow_scratch(c, &R.d_kind, &R.kind_cap, m)))
+    return rc;
+  if (slots && (size_t)c->el.E > A.mark_cap) {
+    if ((rc = grow_scratch(c, &A.d_mark, &A.mark_cap, (size_t)c->el.E))) return rc;
+    if (hipMemsetAsync(A.d_mark, 0, A.mark_cap, c->stream) != hipSuccess) {
+      A.mark_cap = 0;
+      c->err = std::string(who) + ": device error";
+      return SGO_EHIP;
+    }
+  }
+  hipError_t e = hipMemcpyAsync(A.d_ids, ids.data(), sizeof(int32_t) * m, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(A.d_rows, phi.data(), sizeof(double) * m, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(R.d_kind, bytes.data(), m, hipMemcpyHostToDevice, c->stream);
+  if (e != hipSuccess) {   // (nothing of the graph has been written yet)
+    c->err = std::string(who) + ": " + hipGetErrorString(e);
+    return SGO_EHIP;
+  }
+  launch_edge_kernel_scatter(c->stream, (int)m, A.d_ids, A.d_rows, R.d_kind, c->el, c->ov.active ? &c->ov.dev.el : nullptr, slots ? A.d_mark : nullptr);
+  if (slots) {
+    launch_slot_kernel_refresh(c->stream, c->S0.ncs, c->d_eidx, A.d_mark, c->el, c->es);
+    e = hipMemsetAsync(A.d_mark, 0, (size_t)c->el.E, c->stream);
+  }
+  if (e == hipSuccess) e = hipGetLastError();
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);   // (the staging vectors are this frame's)
+  // the host's record: made from what phi said (an edge never listed is NONE or DCS, and which of the two nobody asks)
+  if (R.kind.size() != (size_t)c->E) R.kind.resize((size_t)c->E, (uint8_t)SGO_KERNEL_DCS);
+  for (size_t t = 0; t < m; ++t) {
+    uint8_t& k = R.kind[ids[t]];
+    R.n_other += (int)(kinds[t] >= SGO_KERNEL_HUBER) - (int)(k >= SGO_KERNEL_HUBER);
+    k = (uint8_t)kinds[t];
+  }
+  c->el.kinds = c->es.kinds = c->ov.dev.el.kinds = R.n_other > 0 ? 1 : 0;
+  // as after sgo_set_edge_information: the operator changed under the resident structures
+  c->linearized = false;
+  c->hier.ref_valid = false;
+  c->call.skip_update = false;
+  c->hier.new_rhs();
+  if (e != hipSuccess) {
+    c->err = std::string(who) + ": " + hipGetErrorString(e);
+    return SGO_EHIP;
+  }
+  return SGO_OK;
+}
+
 }  // namespace
 
 // =============================================================================== C-ABI
@@ -311,6 +376,7 @@ void sgo_destroy(sgo_ctx* c) {
   if (c->edges.d_flag) hipFree(c->edges.d_flag);
   if (c->edges.d_mark) hipFree(c->edges.d_mark);
   if (c->edges.d_parts) hipFree(c->edges.d_parts);
+  if (c->robust.d_kind) hipFree(c->robust.d_kind);
   if (c->stream) hipStreamDestroy(c->stream);
   delete c;
 }
@@ -555,6 +621,8 @@ int sgo_update_graph_se2(sgo_ctx* c, int32_t V, const double* poses, const uint8
         c->E = E;
         c->linearized = false;
         edge_activity_append(c, V, dE, ei + n_resident_edges, ej + n_resident_edges, info + 6 * (size_t)n_resident_edges);
+        if (!c->robust.kind.empty()) c->robust.kind.resize((size_t)E, (uint8_t)SGO_KERNEL_DCS);   // (appended edges: what phi says)
+        ov.dev.el.kinds = c->el.kinds;
         // the hierarchy's own staleness rule compares a solve with the best count seen so far (sgo_policy.h): the solves after
         // an update have another right-hand side (the appended poses' residual) -- their first one sets a new reference
         c->hier.new_rhs();
@@ -573,7 +641,23 @@ int sgo_update_graph_se2(sgo_ctx* c, int32_t V, const double* poses, const uint8
       if (why.empty()) why = "overlay set-up failed";
     }
     if (c->opts.verbose) std::fprintf(stderr, "[sgo] update_graph: full set-up (%s)\n", why.c_str());
-    const int rc = sgo_set_graph_se2(c, V, poses, fixed, E, ei, ej, meas, info, phi);
+    // the kinds sgo_set_robust_kernels gave the resident prefix outlive the set-up, with delta from the phi passed now
+    std::vector<int32_t> kept_id, kept_kind;
+    std::vector<double> kept_delta;
+    if (c->has_graph && !multi_gpu_context(c))
+      for (size_t e = 0; e < c->robust.kind.size() && e < (size_t)n_resident_edges; ++e) {
+        const int k = c->robust.kind[e];
+        if (k == SGO_KERNEL_DCS || (k != SGO_KERNEL_NONE && !(phi[e] > 0.0 && std::isfinite(phi[e])))) continue;   // (what phi says already)
+        kept_id.push_back((int32_t)e);
+        kept_kind.push_back(k);
+        kept_delta.push_back(phi[e]);
+      }
+    int rc = sgo_set_graph_se2(c, V, poses, fixed, E, ei, ej, meas, info, phi);
+    if (rc == SGO_OK && !kept_id.empty()) {
+      const double ts = c->setup_seconds;
+      rc = robust_apply(c, "sgo_update_graph_se2", kept_id, kept_kind, kept_delta);
+      c->setup_seconds = ts;
+    }
     if (rc == SGO_OK) c->update_note = "full set-up (" + why + ")";
     return rc;
   } SGO_CATCH(c)
@@ -741,6 +825,73 @@ int sgo_gate_edges(sgo_ctx* c, int32_t n, const int32_t* edge_ids, double chi2_m
     if ((rc = edge_info_apply(c, "sgo_gate_edges", ids, rows))) return rc;
     if (gated) std::copy(flag.begin(), flag.end(), gated);
     return (int)ids.size();
+  } SGO_CATCH(c)
+}
+
+int sgo_set_robust_kernels(sgo_ctx* c, int32_t n, const int32_t* edge_ids, const int32_t* kind, const double* delta) {
+  try {
+    int rc = check_graph(c);
+    if (rc) return rc;
+    if (n < 0 || (n > 0 && (!kind || !delta))) {
+      c->err = "sgo_set_robust_kernels: null buffer or negative count";
+      return SGO_EINVAL;
+    }
+    if (multi_gpu_context(c)) {
+      c->err = "sgo_set_robust_kernels: not available in a multi-GPU context (only DCS through sgo_set_graph_se2's phi is)";
+      return SGO_EINVAL;
+    }
+    for (int t = 0; t < n; ++t) {
+      const int id = edge_ids ? edge_ids[t] : t;
+      if (id < 0 || id >= c->E) {
+        c->err = "sgo_set_robust_kernels: edge id " + std::to_string(id) + " outside [0, " + std::to_string(c->E) + ")";
+        return SGO_EINVAL;
+      }
+      if (kind[t] < SGO_KERNEL_NONE || kind[t] > SGO_KERNEL_SATURATED) {
+        c->err = "sgo_set_robust_kernels: unknown kind " + std::to_string(kind[t]) + " for edge " + std::to_string(id);
+        return SGO_EINVAL;
+      }
+      const bool bad = !std::isfinite(delta[t]) || (kind[t] == SGO_KERNEL_DCS && delta[t] < 0.0) || (kind[t] >= SGO_KERNEL_HUBER && !(delta[t] > 0.0));
+      if (bad) {
+        c->err = "sgo_set_robust_kernels: delta " + std::to_string(delta[t]) + " of edge " + std::to_string(id) +
+                 " is not finite or not in the kind's range (DCS: >= 0, the others: > 0)";
+        return SGO_EINVAL;
+      }
+    }
+    if (n == 0) return SGO_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    // every id once: of an id listed twice the later entry counts
+    std::vector<int32_t> order((size_t)n);
+    for (int t = 0; t < n; ++t) order[t] = t;
+    auto id_of = [&](int t) { return edge_ids ? edge_ids[t] : t; };
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return id_of(a) < id_of(b); });
+    std::vector<int32_t> ids, kinds;
+    std::vector<double> deltas;
+    for (int k = 0; k < n; ++k) {
+      const int t = order[k];
+      if (k + 1 < n && id_of(order[k + 1]) == id_of(t)) continue;
+      ids.push_back(id_of(t));
+      kinds.push_back(kind[t]);
+      deltas.push_back(delta[t]);
+    }
+    return robust_apply(c, "sgo_set_robust_kernels", ids, kinds, deltas);
+  } SGO_CATCH(c)
+}
+
+int sgo_edge_robust(sgo_ctx* c, double* rho0, double* weight) {
+  try {
+    int rc = check_graph(c);
+    if (rc) return rc;
+    if (c->E == 0 || (!rho0 && !weight)) return SGO_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    sgo_ctx::EdgeActivity& A = c->edges;
+    const size_t E = (size_t)c->E;
+    if ((rc = grow_scratch(c, &A.d_rows, &A.rows_cap, 2 * E))) return rc;
+    launch_edge_robust(c->stream, c->el, c->ov.active ? &c->ov.dev.el : nullptr, c->d_poses, A.d_rows, A.d_rows + E);
+    HIP_TRY(c, hipGetLastError());
+    if (rho0) HIP_TRY(c, hipMemcpyAsync(rho0, A.d_rows, sizeof(double) * E, hipMemcpyDeviceToHost, c->stream));
+    if (weight) HIP_TRY(c, hipMemcpyAsync(weight, A.d_rows + E, sizeof(double) * E, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return SGO_OK;
   } SGO_CATCH(c)
 }
 

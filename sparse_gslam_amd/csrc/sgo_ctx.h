@@ -239,6 +239,16 @@ struct sgo_ctx {
     double* d_parts = nullptr;        // [kMaxPartials] the gate's per-workgroup counts, then the count itself (one int)
     size_t ids_cap = 0, rows_cap = 0, flag_cap = 0, mark_cap = 0, parts_cap = 0;
   } edges;
+  // Robust kernels set per edge (sgo_set_robust_kernels): the SGO_KERNEL_* number of every edge, the resident list's and then the
+  // overlay's, once a call has set one -- empty until then: every edge is what its phi says.  What a full set-up inside
+  // sgo_update_graph_se2 re-applies to the resident prefix.  n_other: edges whose kind is neither NONE nor DCS (the device lists'
+  // `kinds` flag is n_other > 0).  The device scratch of `edges` serves these calls too.
+  struct RobustKinds {
+    std::vector<uint8_t> kind;
+    int n_other = 0;
+    unsigned char* d_kind = nullptr;  // listed kinds (device bytes, sgo_internal.h: RobustKind)
+    size_t kind_cap = 0;
+  } robust;
 
   // profiling
   struct Rec { int kid; hipEvent_t a, b; };

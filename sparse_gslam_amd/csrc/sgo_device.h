@@ -20,8 +20,8 @@ __device__ __forceinline__ double norm_theta(double t) {
 }
 
 // ---------------------------------------------------------------------------- the arithmetic of EdgeSE2
-// One statement of what every edge kernel evaluates, in layers: operands -> computeError -> Omega e, e^2 and the DCS
-// weight -> the Jacobians of linearizeOplus -> one side's terms of constructQuadraticForm.  k_chi2 stops after the
+// One statement of what every edge kernel evaluates, in layers: operands -> computeError -> Omega e, e^2 and the robust
+// kernel's weight -> the Jacobians of linearizeOplus -> one side's terms of constructQuadraticForm.  k_chi2 stops after the
 // weight; k_linearize and k_ov_lin take all of it (edge_side_terms).  Three kernels share the first layers and keep
 // a contraction of their own, because each rounds differently from edge_side:
 //   k_direct (sgo_direct.hip)        error from its one sincos, weight, Jacobians; then both sides at once, with the
@@ -81,13 +81,93 @@ __device__ __forceinline__ void dcs(double e2, double phi, double* rho0, double*
   *rho1 = r1;
 }
 
+// RobustKernel::robustify for an edge's kind (sgo_internal.h: RobustKind) and parameter d = phi: rho0 and the weight rho1 of
+// e2 = e^T Omega e as g2o's robust_kernel_impl.cpp has them (include/sgo.h lists the pairs); rho2 is not formed, g2o's
+// robustInformation is rho1 Omega.  kRobustDcs is dcs() itself.  The other kinds come with d > 0 (sgo_set_robust_kernels checks);
+// an edge without information has e2 = 0, for which every kind gives rho0 = 0 and weight 1.
+__device__ __forceinline__ void robustify(int kind, double e2, double d, double* rho0, double* rho1) {
+  if (kind == kRobustDcs) {
+    dcs(e2, d, rho0, rho1);
+    return;
+  }
+  double r0 = e2, r1 = 1.0;
+  if (d > 0.0) {
+    const double d2 = d * d;
+    switch (kind) {
+      case kRobustHuber:
+        if (!(e2 <= d2)) {
+          const double s = sqrt(e2);
+          r0 = 2.0 * s * d - d2;
+          r1 = d / s;
+        }
+        break;
+      case kRobustPseudoHuber: {
+        const double a = sqrt(1.0 + e2 / d2);
+        r0 = 2.0 * d2 * (a - 1.0);
+        r1 = 1.0 / a;
+        break;
+      }
+      case kRobustCauchy: {
+        const double a = 1.0 + e2 / d2;
+        r0 = d2 * log(a);
+        r1 = 1.0 / a;
+        break;
+      }
+      case kRobustGemanMcClure: {
+        const double a = 1.0 / (1.0 + e2);
+        r0 = e2 * a;
+        r1 = a * a;
+        break;
+      }
+      case kRobustWelsch: {
+        const double a = exp(-e2 / d2);
+        r0 = d2 * (1.0 - a);
+        r1 = a;
+        break;
+      }
+      case kRobustFair: {
+        const double a = sqrt(e2) / d;
+        r0 = 2.0 * d2 * (a - log1p(a));
+        r1 = 1.0 / (1.0 + a);
+        break;
+      }
+      case kRobustTukey:
+        if (sqrt(e2) <= d) {
+          const double u = 1.0 - e2 / d2;
+          r0 = d2 * (1.0 - u * u * u) / 3.0;
+          r1 = u * u;
+        } else {
+          r0 = d2 / 3.0;
+          r1 = 0.0;
+        }
+        break;
+      case kRobustSaturated:
+        if (!(e2 <= d2)) {
+          r0 = d2;
+          r1 = 0.0;
+        }
+        break;
+      default: break;
+    }
+  }
+  *rho0 = r0;
+  *rho1 = r1;
+}
+// KINDS: the graph holds kinds other than kRobustDcs (EdgeListDev::kinds), and the kind is read where phi is.  Without it the
+// kernels are the instruction sequences of a graph that knows DCS only.
+template <bool KINDS, class Src>
+__device__ __forceinline__ void edge_robustify(const Src& s, int k, double e2, double* rho0, double* rho1) {
+  if (KINDS) robustify(s.kind[k], e2, s.phi[k], rho0, rho1);
+  else dcs(e2, s.phi[k], rho0, rho1);
+}
+
 // The information's upper triangle, Omega e (unscaled), e^2 = e^T Omega e, and the robust kernel's rho0 and weight w = rho1.
 // (The information is loaded here, after the error, not with the operands: held across the error's sincos it costs
 // k_chi2 a step of occupancy.)
 struct EdgeWeight {
   double o00, o01, o02, o11, o12, o22, oe0, oe1, oe2, e2, rho0, w;
 };
-template <class Src>
+template <bool KINDS, class Src>
 __device__ __forceinline__ void edge_weight(const Src& s, size_t ns, int k, const double (&e)[3], EdgeWeight& W) {
   W.o00 = s.info[k]; W.o01 = s.info[ns + k]; W.o02 = s.info[2 * ns + k];
   W.o11 = s.info[3 * ns + k]; W.o12 = s.info[4 * ns + k]; W.o22 = s.info[5 * ns + k];
@@ -95,7 +175,7 @@ __device__ __forceinline__ void edge_weight(const Src& s, size_t ns, int k, cons
   W.oe1 = W.o01 * e[0] + W.o11 * e[1] + W.o12 * e[2];
   W.oe2 = W.o02 * e[0] + W.o12 * e[1] + W.o22 * e[2];
   W.e2 = e[0] * W.oe0 + e[1] * W.oe1 + e[2] * W.oe2;
-  dcs(W.e2, s.phi[k], &W.rho0, &W.w);
+  edge_robustify<KINDS>(s, k, W.e2, &W.rho0, &W.w);
 }
 
 // EdgeSE2::linearizeOplus: A = d e / d x_i = Rz a, B = d e / d x_j = Rz b (rows: error components), with Rz of the
@@ -157,7 +237,7 @@ __device__ __forceinline__ void edge_block(const EdgeSide& S, double (&blk)[9]) 
 }
 // All layers for edge (or slot) k of s, seen from the row on side `dir`.  The caller adds S.D, subtracts S.g and, where it
 // wants the block, calls edge_block.
-template <class Src>
+template <bool KINDS, class Src>
 __device__ __forceinline__ void edge_side_terms(const Src& s, size_t ns, int k, const double* __restrict__ poses, bool dir, EdgeSide& S) {
   EdgeOperands p;
   edge_operands(s, ns, k, poses, p);
@@ -165,7 +245,7 @@ __device__ __forceinline__ void edge_side_terms(const Src& s, size_t ns, int k, 
   sincos(p.zt, &sz, &cz);
   edge_error(p, sz, cz, e);
   EdgeWeight W;
-  edge_weight(s, ns, k, e, W);
+  edge_weight<KINDS>(s, ns, k, e, W);
   EdgeJac J;
   edge_jacobians(p, sz, cz, J);
   edge_side(W, J, dir, S);

@@ -135,6 +135,7 @@ __device__ __forceinline__ int tri_at(int i, int j) { return i * (i + 1) / 2 + j
 // (the layers of sgo_device.h up to the Jacobians, with sin / cos of the inverse measurement's angle taken from zsc and
 // sin(-t_i) = -sin(t_i), then constructQuadraticForm for both sides).
 // Returns e2 and rho0 for the chi2 sums.
+template <bool KINDS>
 __device__ __forceinline__ void edge_terms(const EdgeListDev& el, const double* __restrict__ zsc, int k,
                                            const double* __restrict__ poses, bool jac, double* __restrict__ rec,
                                            double (&hij)[9], double* e2_out, double* rho_out) {
@@ -146,7 +147,7 @@ __device__ __forceinline__ void edge_terms(const EdgeListDev& el, const double* 
   sincos(p.ti, &si, &ci);
   edge_error_sc(p, norm_theta(-p.ti), -si, ci, sz, cz, e);   // Xi^-1 = (R(-ti), -R(-ti) t_i) from the one sincos
   EdgeWeight W;
-  edge_weight(el, E, k, e, W);
+  edge_weight<KINDS>(el, E, k, e, W);
   *e2_out = W.e2;
   *rho_out = W.rho0;
   if (!jac) return;
@@ -300,8 +301,8 @@ __device__ __forceinline__ void run_task(const DirectDev& D, double* __restrict_
 constexpr int kPF = 1;   // forward tasks per thread whose records are fetched one level ahead
 
 // XG: the right-hand side / solution vector lives in global memory (graphs whose 24 n bytes do not fit the LDS
-// next to the separator block) instead of LDS.
-template <bool XG>
+// next to the separator block) instead of LDS.  KINDS: the edges carry robust kernels other than DCS (sgo_device.h).
+template <bool XG, bool KINDS>
 __global__ __launch_bounds__(kDT) void k_direct(DirectDev D, EdgeListDev el, double* __restrict__ poses, int iters,
                                                 double* __restrict__ hist, DirectResult* __restrict__ res) {
   extern __shared__ double lds[];
@@ -389,7 +390,7 @@ __global__ __launch_bounds__(kDT) void k_direct(DirectDev D, EdgeListDev el, dou
     for (int k = tq; k < D.E; k += kDT) {
       double e2, r0, hij[9];
       double* o = D.escr + k;   // SoA: component c of edge k at escr[c E + k] (coalesced stores)
-      edge_terms(el, D.zsc, k, poses, jac, o, hij, &e2, &r0);
+      edge_terms<KINDS>(el, D.zsc, k, poses, jac, o, hij, &e2, &r0);
       acc[0] += e2;
       acc[1] += r0;
       if (jac) {
@@ -1086,9 +1087,10 @@ Direct* direct_create(hipStream_t s, DevArena* arena, int V, int n, const int* f
   const bool attr_set_already = (attr_devices.load() & dev_bit) != 0;
   bool attr_set = attr_set_already;
   if (e == hipSuccess && !attr_set) {
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_direct<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBudget);
-    if (e == hipSuccess)
-      e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_direct<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBudget);
+    const void* const variants[4] = {reinterpret_cast<const void*>(&k_direct<false, false>), reinterpret_cast<const void*>(&k_direct<true, false>),
+                                     reinterpret_cast<const void*>(&k_direct<false, true>), reinterpret_cast<const void*>(&k_direct<true, true>)};
+    for (int v = 0; v < 4 && e == hipSuccess; ++v)
+      e = hipFuncSetAttribute(variants[v], hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBudget);
     attr_set = e == hipSuccess;
     if (attr_set) attr_devices.fetch_or(dev_bit);
   }
@@ -1108,8 +1110,11 @@ Direct* direct_create(hipStream_t s, DevArena* arena, int V, int n, const int* f
 
 hipError_t direct_optimize(Direct* d, hipStream_t s, const EdgeListDev& el, double* d_poses, int iters, double* d_hist,
                            DirectResult* d_res) {
-  if (d->xb_global) SGO_LAUNCH(k_direct<true>, dim3(1), dim3(kDT), d->info.lds_bytes, s, d->dev, el, d_poses, iters, d_hist, d_res);
-  else SGO_LAUNCH(k_direct<false>, dim3(1), dim3(kDT), d->info.lds_bytes, s, d->dev, el, d_poses, iters, d_hist, d_res);
+  if (el.kinds) {
+    if (d->xb_global) SGO_LAUNCH((k_direct<true, true>), dim3(1), dim3(kDT), d->info.lds_bytes, s, d->dev, el, d_poses, iters, d_hist, d_res);
+    else SGO_LAUNCH((k_direct<false, true>), dim3(1), dim3(kDT), d->info.lds_bytes, s, d->dev, el, d_poses, iters, d_hist, d_res);
+  } else if (d->xb_global) SGO_LAUNCH((k_direct<true, false>), dim3(1), dim3(kDT), d->info.lds_bytes, s, d->dev, el, d_poses, iters, d_hist, d_res);
+  else SGO_LAUNCH((k_direct<false, false>), dim3(1), dim3(kDT), d->info.lds_bytes, s, d->dev, el, d_poses, iters, d_hist, d_res);
   return hipGetLastError();
 }
 

@@ -153,6 +153,14 @@ struct Tile0Dev {
   int hstride = 0;                  // tile's own): their address does not depend on the tile descriptor, one round trip less
 };
 
+// The robust kernel of an edge, one byte beside its parameter phi (sgo_device.h: robustify).  0 is DCS -- or no kernel at all
+// when phi < 0 --, so zero-filled storage is the graph sgo_set_graph_se2 describes; the other values are include/sgo.h's
+// SGO_KERNEL_* numbers as sgo_set_robust_kernels takes them (SGO_KERNEL_NONE and SGO_KERNEL_DCS are stored as phi < 0 / phi >= 0).
+enum : int {
+  kRobustDcs = 0, kRobustHuber = 2, kRobustPseudoHuber = 3, kRobustCauchy = 4, kRobustGemanMcClure = 5, kRobustWelsch = 6,
+  kRobustFair = 7, kRobustTukey = 8, kRobustSaturated = 9
+};
+
 // Edge operands aligned with the level-0 compact slots (SoA over slots).  For a slot of row r that
 // came from edge e = (i, j):  dir = 0 when r is the i side (row Jacobian A), 1 when r is the j side
 // (row Jacobian B).
@@ -165,7 +173,9 @@ struct EdgeSlotsDev {
   unsigned char* flags = nullptr;
   double* zinv = nullptr; // [3][stride] cached inverse measurement (EdgeSE2::setMeasurement)
   double* info = nullptr; // [6][stride]
-  double* phi = nullptr;  // [ncs]
+  double* phi = nullptr;  // [ncs] the robust kernel's parameter delta; < 0: no kernel
+  unsigned char* kind = nullptr;  // [ncs] the robust kernel beside phi (RobustKind); read only when `kinds` is set
+  int kinds = 0;          // some edge carries a kind other than kRobustDcs: the launchers take the kernels' general instantiation
 };
 
 // Original edge list (edge order of sgo_set_graph_se2), SoA, for chi2 / per-edge chi2.
@@ -176,7 +186,9 @@ struct EdgeListDev {
   int* vj = nullptr;
   double* zinv = nullptr; // [3][E]
   double* info = nullptr; // [6][E]
-  double* phi = nullptr;  // [E]
+  double* phi = nullptr;  // [E] the robust kernel's parameter delta; < 0: no kernel
+  unsigned char* kind = nullptr;  // [E] the robust kernel beside phi (RobustKind); read only when `kinds` is set
+  int kinds = 0;          // some edge of the graph (either list) carries a kind other than kRobustDcs
 };
 
 // Device-resident scalars of the PCG recurrence (one cache line; read uniformly by kernels).
@@ -536,6 +548,14 @@ void launch_edge_info_scatter(hipStream_t s, int n, const int* ids, const double
 // the per-slot copies (es.info) of the marked edges from el.info; eidx: slot -> edge
 void launch_slot_info_refresh(hipStream_t s, int ncs, const int* eidx, const unsigned char* mark, const EdgeListDev& el,
                               const EdgeSlotsDev& es);
+// ---- robust kernels per edge (sgo_gate.hip; sgo_set_robust_kernels, sgo_edge_robust) ----
+// the listed edges' (phi, kind) = (delta[t], kind[t]) in the list that holds them; mark as for launch_edge_info_scatter
+void launch_edge_kernel_scatter(hipStream_t s, int n, const int* ids, const double* delta, const unsigned char* kind, const EdgeListDev& el,
+                                const EdgeListDev* el2, unsigned char* mark);
+void launch_slot_kernel_refresh(hipStream_t s, int ncs, const int* eidx, const unsigned char* mark, const EdgeListDev& el,
+                                const EdgeSlotsDev& es);
+// rho0[E + cnt2], w[E + cnt2] (either may be null) at `poses`, with launch_chi2's arithmetic
+void launch_edge_robust(hipStream_t s, const EdgeListDev& el, const EdgeListDev* el2, const double* poses, double* rho0, double* w);
 // strength weights of the logical slots (hrowptr: logical row pointers) straight from the edge list (sgo_kernels.hip)
 void launch_early_strength(hipStream_t s, const EdgeListDev& el, const double* poses, int n, const int* rowptr, const int* eidx,
                            const unsigned char* flags, const int* hrowptr, double* w);

@@ -43,6 +43,7 @@ const char* const kKernelNames[K_COUNT] = {
 namespace {
 
 // ---------------------------------------------------------------------------- k_chi2
+template <bool KINDS>
 __device__ __forceinline__ void chi2_range(const EdgeListDev& el, int e0, int e1, const double* __restrict__ poses,
                                            double* __restrict__ e2_out, double (&acc)[2]) {
   for (int k = e0 + blockIdx.x * kBlock + threadIdx.x; k < e1; k += gridDim.x * kBlock) {
@@ -52,18 +53,19 @@ __device__ __forceinline__ void chi2_range(const EdgeListDev& el, int e0, int e1
     sincos(p.zt, &sz, &cz);
     edge_error(p, sz, cz, e);
     EdgeWeight W;
-    edge_weight(el, (size_t)el.E, k, e, W);
+    edge_weight<KINDS>(el, (size_t)el.E, k, e, W);
     if (e2_out) e2_out[k] = W.e2;
     acc[0] += W.e2;
     acc[1] += W.rho0;
   }
 }
 // edges [e0, e1) of el, then the first el2.cnt edges of el2 (an empty list when there is no overlay)
+template <bool KINDS>
 __global__ __launch_bounds__(kBlock) void k_chi2(EdgeListDev el, int e0, int e1, EdgeListDev el2, const double* __restrict__ poses,
                                                  double* __restrict__ e2_out, double* __restrict__ partials) {
   double acc[2] = {0.0, 0.0};
-  chi2_range(el, e0, e1, poses, e2_out, acc);
-  if (el2.cnt > 0) chi2_range(el2, 0, el2.cnt, poses, e2_out ? e2_out + el.E : nullptr, acc);
+  chi2_range<KINDS>(el, e0, e1, poses, e2_out, acc);
+  if (el2.cnt > 0) chi2_range<KINDS>(el2, 0, el2.cnt, poses, e2_out ? e2_out + el.E : nullptr, acc);
   block_sum_store<2>(acc, partials, kMaxPartials);
 }
 
@@ -109,6 +111,7 @@ __global__ __launch_bounds__(kBlock) void k_slot_expand(int k0, int k1, const in
 #pragma unroll
     for (int q = 0; q < 6; ++q) es.info[q * ns + k] = el.info[q * E + e];
     es.phi[k] = el.phi[e];
+    es.kind[k] = el.kind[e];
   }
 }
 
@@ -121,6 +124,7 @@ __global__ __launch_bounds__(kBlock) void k_slot_expand(int k0, int k1, const in
 // with generic 3x3 loops of its own for e^2, Ow R = w (Omega R) and the products: the norms agree with those of
 // k_linearize's blocks to rounding, not to the bit.  w of the row's logical slots -- the diagonal
 // slot first (norm of the summed R^T Ow R), then ||R^T Ow C||_F for every slot whose column is free.
+template <bool KINDS>
 __global__ __launch_bounds__(kBlock) void k_row_strength(int n, const int* __restrict__ rowptr, const int* __restrict__ eidx,
                                                          const unsigned char* __restrict__ flags, const int* __restrict__ hrowptr,
                                                          EdgeListDev el, const double* __restrict__ poses, double* __restrict__ w) {
@@ -144,7 +148,7 @@ __global__ __launch_bounds__(kBlock) void k_row_strength(int n, const int* __res
 #pragma unroll
         for (int b = 0; b < 3; ++b) e2 += er[a] * O[a][b] * er[b];
       double r0_, wt;
-      dcs(e2, el.phi[e], &r0_, &wt);
+      edge_robustify<KINDS>(el, e, e2, &r0_, &wt);
       // (the Jacobians written out here, not through edge_jacobians: sgo_device.h says why)
       double si, ci;
       sincos(p.ti, &si, &ci);
@@ -194,6 +198,7 @@ __global__ __launch_bounds__(kBlock) void k_row_strength(int n, const int* __res
 // to dgb[r][0..8] -- and, when the slot OWNS the block, writes the off-diagonal block Jr^T Ow Jc into the
 // symmetric storage (the transposed slot of the other endpoint's row evaluates the same edge for its
 // own row sums and writes nothing: recompute instead of scatter).
+template <bool KINDS>
 __global__ __launch_bounds__(kBlock) void k_linearize(Sym0Dev A, int g0, int g1, EdgeSlotsDev es,
                                                       const double* __restrict__ poses, double* __restrict__ dgb) {
   const int lane = threadIdx.x & 63;
@@ -220,7 +225,7 @@ __global__ __launch_bounds__(kBlock) void k_linearize(Sym0Dev A, int g0, int g1,
       const int fl = es.flags[k];
       if (fl & kSlotNoEdge) continue;
       EdgeSide S;
-      edge_side_terms(es, ns, k, poses, (fl & kSlotDir) != 0, S);
+      edge_side_terms<KINDS>(es, ns, k, poses, (fl & kSlotDir) != 0, S);
 #pragma unroll
       for (int c = 0; c < 6; ++c) acc[c] += S.D[c];
 #pragma unroll
@@ -1142,7 +1147,8 @@ bool halo_gather_slices(const HaloDev& H, hipStream_t s, double* vec, int width,
 void launch_chi2(hipStream_t s, const EdgeListDev& el, int e0, int e1, const double* poses, double* e2_out,
                  double* partials, int* grid_out, const EdgeListDev* el2) {
   const int grid = grid_for(e1 - e0, kBlock);
-  SGO_LAUNCH(k_chi2, dim3(grid), dim3(kBlock), 0, s, el, e0, e1, el2 ? *el2 : EdgeListDev(), poses, e2_out, partials);
+  if (el.kinds) SGO_LAUNCH(k_chi2<true>, dim3(grid), dim3(kBlock), 0, s, el, e0, e1, el2 ? *el2 : EdgeListDev(), poses, e2_out, partials);
+  else SGO_LAUNCH(k_chi2<false>, dim3(grid), dim3(kBlock), 0, s, el, e0, e1, el2 ? *el2 : EdgeListDev(), poses, e2_out, partials);
   *grid_out = grid;
 }
 void launch_reduce2(hipStream_t s, const double* partials, int nparts, double* out2) {
@@ -1151,7 +1157,8 @@ void launch_reduce2(hipStream_t s, const double* partials, int nparts, double* o
 void launch_linearize(hipStream_t s, const Sym0Dev& A, int g0, int g1, const EdgeSlotsDev& es, const double* poses,
                       double* dgb) {
   const int grid = grid_for(g1 - g0, kWavesPerBlock);
-  SGO_LAUNCH(k_linearize, dim3(grid), dim3(kBlock), 0, s, A, g0, g1, es, poses, dgb);
+  if (es.kinds) SGO_LAUNCH(k_linearize<true>, dim3(grid), dim3(kBlock), 0, s, A, g0, g1, es, poses, dgb);
+  else SGO_LAUNCH(k_linearize<false>, dim3(grid), dim3(kBlock), 0, s, A, g0, g1, es, poses, dgb);
 }
 void launch_finalize(hipStream_t s, const Sym0Dev& A, int row0, int row1, const double* dgb, double* b, double* x, double* r, double* z,
                      double* p, double* xs, double omega, double* partials, int* grid_out) {
@@ -1184,7 +1191,8 @@ void launch_edge_prepare(hipStream_t s, int E, const double* meas, const double*
 }
 void launch_early_strength(hipStream_t s, const EdgeListDev& el, const double* poses, int n, const int* rowptr, const int* eidx,
                            const unsigned char* flags, const int* hrowptr, double* w) {
-  if (n > 0) SGO_LAUNCH(k_row_strength, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, s, n, rowptr, eidx, flags, hrowptr, el, poses, w);
+  if (n > 0 && el.kinds) SGO_LAUNCH(k_row_strength<true>, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, s, n, rowptr, eidx, flags, hrowptr, el, poses, w);
+  else if (n > 0) SGO_LAUNCH(k_row_strength<false>, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, s, n, rowptr, eidx, flags, hrowptr, el, poses, w);
 }
 void launch_slot_expand(hipStream_t s, int k0, int k1, const int* eidx, const EdgeListDev& el, const EdgeSlotsDev& es) {
   SGO_LAUNCH(k_slot_expand, dim3(grid_for(k1 - k0, kBlock)), dim3(kBlock), 0, s, k0, k1, eidx, el, es);

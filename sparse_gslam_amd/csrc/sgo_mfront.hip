@@ -124,6 +124,8 @@ __device__ __forceinline__ double mf_rsqrt(double x) {
 }
 
 // ---------------------------------------------------------------------------- k_mf_edges
+// (KINDS: the edges carry robust kernels other than DCS, sgo_device.h)
+template <bool KINDS>
 __global__ __launch_bounds__(kBlock) void k_mf_edges(MfDev M, EdgeListDev el, const double* __restrict__ poses, int it, int chi2_only,
                                                      double* __restrict__ hist, DirectResult* __restrict__ res) {
   if (blockIdx.x == 0 && threadIdx.x == 0) res->stamp[2 * it] = (unsigned long long)wall_clock64();
@@ -137,7 +139,7 @@ __global__ __launch_bounds__(kBlock) void k_mf_edges(MfDev M, EdgeListDev el, co
     sincos(p.zt, &sz, &cz);
     edge_error(p, sz, cz, er);
     EdgeWeight Wt;
-    edge_weight(el, ns, e, er, Wt);
+    edge_weight<KINDS>(el, ns, e, er, Wt);
     acc[0] += Wt.e2;
     acc[1] += Wt.rho0;
     if (chi2_only) continue;
@@ -915,7 +917,8 @@ hipError_t mfront_optimize(Mfront* m, hipStream_t s, const EdgeListDev& el, doub
   const int ugrid = std::max(1, std::min((D.n + kBlock - 1) / kBlock, 1024));
   for (int it = 0; it <= iters; ++it) {
     const bool last = it == iters;
-    hipLaunchKernelGGL(k_mf_edges, dim3(egrid), dim3(kBlock), 0, s, D, el, (const double*)d_poses, it, last ? 1 : 0, d_hist, d_res);
+    if (el.kinds) hipLaunchKernelGGL(k_mf_edges<true>, dim3(egrid), dim3(kBlock), 0, s, D, el, (const double*)d_poses, it, last ? 1 : 0, d_hist, d_res);
+    else hipLaunchKernelGGL(k_mf_edges<false>, dim3(egrid), dim3(kBlock), 0, s, D, el, (const double*)d_poses, it, last ? 1 : 0, d_hist, d_res);
     if (last) break;
     for (int h = 0; h <= P.height; ++h) {
       const int cnt = P.level_ptr[h + 1] - P.level_ptr[h];

@@ -18,10 +18,11 @@ static_assert(3 * kOvMaxHubs * (3 * kOvMaxTouched + 1) <= 3 * kOvTile * kOvCols,
 
 // What edge e contributes to the row on its `side` (0: vertices()[0], Jacobian A; 1: vertices()[1], Jacobian B):
 // D += R^T Ow R (symmetric packing), b -= R^T Ow e, blk = R^T Ow C (block towards the other endpoint).
+template <bool KINDS>
 __device__ __forceinline__ void ov_edge_terms(const EdgeListDev& el, int e, int side, const double* __restrict__ poses,
                                               double (&D)[6], double (&b)[3], double (&blk)[9]) {
   EdgeSide S;
-  edge_side_terms(el, (size_t)el.E, e, poses, side != 0, S);
+  edge_side_terms<KINDS>(el, (size_t)el.E, e, poses, side != 0, S);
 #pragma unroll
   for (int q = 0; q < 6; ++q) D[q] += S.D[q];
 #pragma unroll
@@ -33,6 +34,8 @@ __device__ __forceinline__ void ov_edge_terms(const EdgeListDev& el, int e, int 
 // One thread per overlay row (new rows, then touched rows): the row's appended edges in entry order.
 //   new row i:     Dn[i], b_N (last column of H0), Un[i] = H_{i,i+1}, H0 blocks towards touched rows
 //   touched row t: M0 rows 3t..3t+2 (its own diagonal contribution and blocks towards other touched rows), bt
+// (KINDS: the edges carry robust kernels other than DCS, sgo_device.h)
+template <bool KINDS>
 __global__ __launch_bounds__(kOvThreads) void k_ov_lin(OverlayDev O, const double* __restrict__ poses) {
   const int r = blockIdx.x * kOvThreads + threadIdx.x;
   const int k = O.k, nt = O.nt + O.nx, nc = O.ncol, nt3 = 3 * nt;   // (nt: the kept rows -- touched base rows, then hubs)
@@ -44,7 +47,7 @@ __global__ __launch_bounds__(kOvThreads) void k_ov_lin(OverlayDev O, const doubl
     double U[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
     for (int t = O.rp[r]; t < O.rp[r + 1]; ++t) {
       double blk[9];
-      ov_edge_terms(O.el, O.ent_edge[t], O.ent_side[t], poses, D, b, blk);
+      ov_edge_terms<KINDS>(O.el, O.ent_edge[t], O.ent_side[t], poses, D, b, blk);
       const int oth = O.ent_other[t];
       if (oth == kOvOtherFixed) continue;
       if (oth >= 0) {
@@ -72,7 +75,7 @@ __global__ __launch_bounds__(kOvThreads) void k_ov_lin(OverlayDev O, const doubl
     for (int q = 0; q < 3 * nt3; ++q) m[q] = 0.0;
     for (int t = O.rp[r]; t < O.rp[r + 1]; ++t) {
       double blk[9];
-      ov_edge_terms(O.el, O.ent_edge[t], O.ent_side[t], poses, D, b, blk);
+      ov_edge_terms<KINDS>(O.el, O.ent_edge[t], O.ent_side[t], poses, D, b, blk);
       const int oth = O.ent_other[t];
       if (oth == kOvOtherFixed || oth >= 0) continue;   // (blocks towards new rows come from the new rows' side)
       const int tc = 3 * (-1 - oth);
@@ -378,7 +381,8 @@ __global__ __launch_bounds__(kOvThreads) void k_ov_finish(OverlayDev O, const do
 
 void launch_ov_lin(hipStream_t s, const OverlayDev& O, const double* poses) {
   const int rows = O.k + O.nt + O.nx;
-  if (rows > 0) SGO_LAUNCH(k_ov_lin, dim3((rows + kOvThreads - 1) / kOvThreads), dim3(kOvThreads), 0, s, O, poses);
+  if (rows > 0 && O.el.kinds) SGO_LAUNCH(k_ov_lin<true>, dim3((rows + kOvThreads - 1) / kOvThreads), dim3(kOvThreads), 0, s, O, poses);
+  else if (rows > 0) SGO_LAUNCH(k_ov_lin<false>, dim3((rows + kOvThreads - 1) / kOvThreads), dim3(kOvThreads), 0, s, O, poses);
 }
 void launch_ov_solve(hipStream_t s, const OverlayDev& O, double* dgb) {
   if (O.k + O.nt + O.nx > 0) SGO_LAUNCH(k_ov_solve, dim3(1), dim3(kOvThreads), 0, s, O, dgb);
@@ -393,7 +397,7 @@ void launch_ov_finish(hipStream_t s, const OverlayDev& O, const double* x, doubl
 // ---------------------------------------------------------------------------- host side
 // Device buffers of an overlay, carved out of one allocation made at first use (capacities of sgo_overlay.h):
 //   ints:    header[4] = {k, nt, ncol, nnz} | rp | ent_edge | ent_other | vtx | trow | nz | el.vi | el.vj
-//   bytes:   ent_side
+//   bytes:   ent_side | el.kind
 //   doubles: el.phi, el.zinv[3], el.info[6], raw meas / info staging, Dn, Un, H0, Y, Sinv, Spiv, M0, bt, M
 namespace {
 struct Layout {
@@ -443,7 +447,7 @@ const Layout& layout() {
 static bool overlay_alloc(Overlay& ov, std::string* err) {
   if (ov.buf) return true;
   const Layout& L = layout();
-  const size_t bytes = sizeof(double) * L.n_dbl + sizeof(int) * L.int_total() + 2 * (size_t)kOvMaxEdges + 256;
+  const size_t bytes = sizeof(double) * L.n_dbl + sizeof(int) * L.int_total() + 3 * (size_t)kOvMaxEdges + 256;
   if (hipMalloc(&ov.buf, bytes) != hipSuccess) {
     ov.buf = nullptr;
     if (err) *err = "out of device memory (incremental set-up buffers)";
@@ -468,6 +472,7 @@ static bool overlay_alloc(Overlay& ov, std::string* err) {
   O.el.vi = ov.d_int + L.i_vi;
   O.el.vj = ov.d_int + L.i_vj;
   O.el.phi = d + L.d_phi;
+  O.el.kind = ov.d_side + 2 * (size_t)kOvMaxEdges;
   O.el.zinv = d + L.d_zinv;
   O.el.info = d + L.d_info;
   O.hdr = ov.d_int + L.i_hdr;
@@ -520,6 +525,7 @@ bool overlay_upload_edges(Overlay& ov, hipStream_t s, int at, int cnt, const int
   hipError_t e = hipMemcpyAsync(ov.dev.el.vi + at, hv, sizeof(int32_t) * (size_t)cnt, hipMemcpyHostToDevice, s);
   if (e == hipSuccess) e = hipMemcpyAsync(ov.dev.el.vj + at, hv + kOvMaxEdges, sizeof(int32_t) * (size_t)cnt, hipMemcpyHostToDevice, s);
   if (e == hipSuccess) e = hipMemcpyAsync(ov.dev.el.phi + at, hp, sizeof(double) * (size_t)cnt, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipMemsetAsync(ov.dev.el.kind + at, 0, (size_t)cnt, s);   // appended edges: what phi says, none or DCS
   if (e == hipSuccess) e = hipMemcpyAsync(raw, hm, sizeof(double) * 3 * (size_t)cnt, hipMemcpyHostToDevice, s);
   if (e == hipSuccess) e = hipMemcpyAsync(raw + 3 * (size_t)kOvMaxEdges, hi6, sizeof(double) * 6 * (size_t)cnt, hipMemcpyHostToDevice, s);
   if (e != hipSuccess) {

@@ -135,6 +135,9 @@ void free_graph(sgo_ctx* c) {
   c->lag_note.clear();
   c->edges.ready = false;   // (the edge-activity bookkeeping belongs to the graph; its device scratch stays)
   c->edges.n_inactive = 0;
+  c->robust.kind.clear();   // (every edge of the next graph is what its phi says)
+  c->robust.n_other = 0;
+  c->ov.dev.el.kinds = 0;
 }
 
 // The edge arrays, poses and chi2 buffers of a graph: all that chi2 / per-edge chi2 / the single-launch direct path
@@ -165,6 +168,7 @@ int build_edges(sgo_ctx* c, int V, const double* poses, const uint8_t* fixed, in
   c->el.E = E;
   double *d_meas = nullptr, *d_info = nullptr;
   if ((rc = dalloc(c, &c->el.vi, (size_t)E)) || (rc = dalloc(c, &c->el.vj, (size_t)E)) || (rc = dalloc(c, &c->el.phi, (size_t)E)) ||
+      (rc = dalloc(c, &c->el.kind, (size_t)E)) ||
       (rc = dalloc(c, &c->el.zinv, 3 * (size_t)E)) || (rc = dalloc(c, &c->el.info, 6 * (size_t)E)) ||
       (rc = dalloc(c, &d_meas, 3 * (size_t)E)) || (rc = dalloc(c, &d_info, 6 * (size_t)E)))
     return rc;
@@ -172,6 +176,7 @@ int build_edges(sgo_ctx* c, int V, const double* poses, const uint8_t* fixed, in
     HIP_TRY(c, hipMemcpyAsync(c->el.vi, ei, sizeof(int32_t) * (size_t)E, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemcpyAsync(c->el.vj, ej, sizeof(int32_t) * (size_t)E, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemcpyAsync(c->el.phi, phi, sizeof(double) * (size_t)E, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemsetAsync(c->el.kind, 0, (size_t)E, c->stream));   // every edge is what phi says: no kernel or DCS
     HIP_TRY(c, hipMemcpyAsync(d_meas, meas, sizeof(double) * 3 * (size_t)E, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemcpyAsync(d_info, info, sizeof(double) * 6 * (size_t)E, hipMemcpyHostToDevice, c->stream));
     launch_edge_prepare(c->stream, E, d_meas, d_info, c->el.zinv, c->el.info, (size_t)E, 0);
@@ -300,8 +305,10 @@ int build_structure(sgo_ctx* c, int V, const double* poses, const uint8_t* fixed
   // (with a communicator the operand arrays are allocated further down, for this rank's slots only in row-owner mode)
   const bool es_early = !c->comm.active();
   c->es.stride = ns;
+  c->es.kinds = c->el.kinds;   // (rows built on demand, after sgo_set_robust_kernels)
   if (es_early && ((rc = dalloc(c, &c->es.vi, (size_t)ns)) || (rc = dalloc(c, &c->es.vj, (size_t)ns)) || (rc = dalloc(c, &c->es.zinv, 3 * (size_t)ns)) ||
-                   (rc = dalloc(c, &c->es.info, 6 * (size_t)ns)) || (rc = dalloc(c, &c->es.phi, (size_t)ns))))
+                   (rc = dalloc(c, &c->es.info, 6 * (size_t)ns)) || (rc = dalloc(c, &c->es.phi, (size_t)ns)) ||
+                   (rc = dalloc(c, &c->es.kind, (size_t)ns))))
     return rc;
   // Large graphs: the multigrid's host analysis of level 0 (greedy aggregation + patterns / product lists of the
   // smoothed transfer: C4 11 + 17 ms, the longest sequential piece of the set-up) needs the strength weights and the
@@ -743,8 +750,9 @@ int build_structure(sgo_ctx* c, int V, const double* poses, const uint8_t* fixed
     const size_t nsl = K1 - K0;
     int *vi = nullptr, *vj = nullptr;
     double *zi = nullptr, *in = nullptr, *ph = nullptr;
+    unsigned char* kd = nullptr;
     if ((rc = dalloc(c, &vi, nsl)) || (rc = dalloc(c, &vj, nsl)) || (rc = dalloc(c, &zi, 3 * nsl)) || (rc = dalloc(c, &in, 6 * nsl)) ||
-        (rc = dalloc(c, &ph, nsl)))
+        (rc = dalloc(c, &ph, nsl)) || (rc = dalloc(c, &kd, nsl)))
       return rc;
     c->es.stride = (int)nsl;
     c->es.vi = vi - K0;
@@ -752,9 +760,10 @@ int build_structure(sgo_ctx* c, int V, const double* poses, const uint8_t* fixed
     c->es.zinv = zi - K0;
     c->es.info = in - K0;
     c->es.phi = ph - K0;
-    c->level0_bytes += (long long)(88 * nsl);
+    c->es.kind = kd - K0;
+    c->level0_bytes += (long long)(89 * nsl);
   } else {
-    c->level0_bytes += (long long)(88 * (size_t)ns);
+    c->level0_bytes += (long long)(89 * (size_t)ns);
   }
   c->unit_row0.clear();   // first row of every level-0 work unit (tiles, or wave groups without a tile view)
   if (tiles_ok && !tiles.empty()) {
