@@ -7,11 +7,13 @@
 // .inverse() (2x2 / 3x3), .transpose(), * + -, .norm(), .dot(), .cast<T>(), setZero, Zero,
 // Identity, comma initialiser, ostream <<; Rotation2D with .angle(), .inverse(), * Vector2,
 // .toRotationMatrix(), .cast<T>(); aligned_allocator; EIGEN_MAKE_ALIGNED_OPERATOR_NEW.
+// Matrix<S, Dynamic, Dynamic> (MatrixXd) has what the blocks of g2o::SparseBlockMatrix<MatrixX> need: rows, cols, operator()(i, j).
 #pragma once
 #include <cmath>
 #include <cstddef>
 #include <memory>
 #include <ostream>
+#include <vector>
 
 #define SGO_EIGEN_MIN 1
 #ifndef EIGEN_MAKE_ALIGNED_OPERATOR_NEW
@@ -198,6 +200,25 @@ std::ostream& operator<<(std::ostream& os, const Matrix<S, R, C>& a) {
   }
   return os;
 }
+
+constexpr int Dynamic = -1;
+// the dynamic matrix of SparseOptimizer::computeMarginals' result blocks
+template <class S>
+class Matrix<S, Dynamic, Dynamic> {
+ public:
+  using Scalar = S;
+  Matrix() {}
+  Matrix(int r, int c) : r_(r), c_(c), m_((size_t)r * (size_t)c, S(0)) {}
+  int rows() const { return r_; }
+  int cols() const { return c_; }
+  S& operator()(int r, int c) { return m_[(size_t)r * (size_t)c_ + (size_t)c]; }
+  const S& operator()(int r, int c) const { return m_[(size_t)r * (size_t)c_ + (size_t)c]; }
+
+ private:
+  int r_ = 0, c_ = 0;
+  std::vector<S> m_;
+};
+using MatrixXd = Matrix<double, Dynamic, Dynamic>;
 
 using Vector2d = Matrix<double, 2, 1>;
 using Vector3d = Matrix<double, 3, 1>;

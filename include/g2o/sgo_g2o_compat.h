@@ -76,6 +76,7 @@ using number_t = double;
 using Vector2 = Eigen::Matrix<double, 2, 1>;
 using Vector3 = Eigen::Matrix<double, 3, 1>;
 using Matrix3 = Eigen::Matrix<double, 3, 3>;
+using MatrixX = Eigen::Matrix<double, Eigen::Dynamic, Eigen::Dynamic>;
 using Rotation2D = Eigen::Rotation2D<double>;
 
 template <class T, class... A>
@@ -669,6 +670,32 @@ class OptimizationAlgorithmLevenberg : public OptimizationAlgorithm {
   explicit OptimizationAlgorithmLevenberg(std::unique_ptr<Solver> s) : OptimizationAlgorithm(Levenberg, std::move(s)) {}
 };
 
+// g2o/core/sparse_block_matrix.h, as far as SparseOptimizer::computeMarginals' result needs it: the blocks asked for, by hessian
+// block index; rows() / cols() count scalars, as upstream
+template <class MatrixType = MatrixX>
+class SparseBlockMatrix {
+ public:
+  using SparseMatrixBlock = MatrixType;
+  SparseBlockMatrix() {}
+  int rows() const { return _rows; }
+  int cols() const { return _cols; }
+  // the block at block row r, block column c; null when it is absent
+  MatrixType* block(int r, int c) {
+    auto it = _blocks.find(std::make_pair(r, c));
+    return it == _blocks.end() ? nullptr : it->second.get();
+  }
+  const MatrixType* block(int r, int c) const {
+    auto it = _blocks.find(std::make_pair(r, c));
+    return it == _blocks.end() ? nullptr : it->second.get();
+  }
+  void clear(bool = false) { _blocks.clear(); }
+
+ private:
+  friend class SparseOptimizer;
+  int _rows = 0, _cols = 0;
+  std::map<std::pair<int, int>, std::unique_ptr<MatrixType>> _blocks;
+};
+
 // ------------------------------------------------------------------------------- optimiser
 class SparseOptimizer : public OptimizableGraph {
  public:
@@ -845,6 +872,60 @@ class SparseOptimizer : public OptimizableGraph {
     downloadEstimates();
     return done;
   }
+  // ---- marginal covariances (SparseOptimizer::computeMarginals): the blocks (r, c) of H^-1 by HESSIAN index, as upstream, through
+  // sgo_marginals -- three solves per distinct column index (include/sgo.h).  The current estimates are uploaded as optimize()
+  // uploads them, and H is the system AT them (upstream inverts the system of its last iteration).  spinv holds the blocks asked
+  // for and nothing else.  A graph that takes the host solver has no marginals here: false, with one line on std::cerr.
+  bool computeMarginals(SparseBlockMatrix<MatrixX>& spinv, const std::vector<std::pair<int, int>>& blockIndices) {
+    if (!_algorithm || !gpuEligible()) {
+      std::cerr << "SparseOptimizer::computeMarginals: only the device path (VertexSE2 / EdgeSE2 under Gauss-Newton) computes marginals"
+                << std::endl;
+      return false;
+    }
+    std::vector<int32_t> ofHessian;   // hessian index -> compact vertex number (uploadGraph's numbering)
+    for (size_t k = 0; k < _activeVertices.size(); ++k)
+      if (_activeVertices[k]->hessianIndex() >= 0) ofHessian.push_back((int32_t)k);
+    const int n = (int)ofHessian.size();
+    std::vector<int32_t> vi, vj;
+    for (const auto& rc : blockIndices) {
+      if (rc.first < 0 || rc.first >= n || rc.second < 0 || rc.second >= n) {
+        std::cerr << "SparseOptimizer::computeMarginals: block (" << rc.first << ", " << rc.second << ") outside the " << n
+                  << " hessian blocks" << std::endl;
+        return false;
+      }
+      vi.push_back(ofHessian[rc.first]);
+      vj.push_back(ofHessian[rc.second]);
+    }
+    if (!uploadGraph()) return false;
+    std::vector<double> cov(9 * vi.size());
+    if (sgo_marginals(_ctx, (int32_t)vi.size(), vi.data(), vj.data(), cov.data()) < 0) {
+      std::cerr << "SparseOptimizer::computeMarginals: " << sgo_last_error(_ctx) << std::endl;
+      return false;
+    }
+    spinv.clear();
+    spinv._rows = spinv._cols = 3 * n;
+    for (size_t t = 0; t < blockIndices.size(); ++t) {
+      std::unique_ptr<MatrixX> B(new MatrixX(3, 3));
+      for (int a = 0; a < 3; ++a)
+        for (int b = 0; b < 3; ++b) (*B)(a, b) = cov[9 * t + 3 * a + b];
+      spinv._blocks[blockIndices[t]] = std::move(B);
+    }
+    return true;
+  }
+  // upstream's convenience overloads: the diagonal block of one vertex, of every vertex of a container (fixed ones are skipped)
+  bool computeMarginals(SparseBlockMatrix<MatrixX>& spinv, const OptimizableGraph::Vertex* vertex) {
+    if (!vertex || vertex->hessianIndex() < 0) return false;
+    return computeMarginals(spinv, std::vector<std::pair<int, int>>(1, std::make_pair(vertex->hessianIndex(), vertex->hessianIndex())));
+  }
+  bool computeMarginals(SparseBlockMatrix<MatrixX>& spinv, const VertexContainer& vertices) {
+    std::vector<std::pair<int, int>> indices;
+    for (const HyperGraph::Vertex* hv : vertices) {
+      const int h = static_cast<const OptimizableGraph::Vertex*>(hv)->hessianIndex();
+      if (h >= 0) indices.push_back(std::make_pair(h, h));
+    }
+    return computeMarginals(spinv, indices);
+  }
+
   // ---- graph files (OptimizableGraph::load / save of g2o, for the types of this backend's device path):
   //   VERTEX_SE2 id x y theta | EDGE_SE2 i j dx dy dtheta o11 o12 o13 o22 o23 o33 | FIX id...
   // load() creates the objects and keeps them alive for the optimiser's lifetime (everything the CALLER adds

@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define SGO_VERSION 107          /* 0.1.7: (later additions under the same number, no signature changed: sgo_set_edge_information, sgo_gate_edges; sgo_set_robust_kernels, sgo_edge_robust, SGO_KERNEL_*); sgo_stats.pcg_converged may be 2 (a solve accepted at the floating-point floor of its system), the incremental overlay keeps 64 touched + hub rows, SGO_AMG_SETUP (no signature changed); 0.1.6: sgo_plan_rows takes the measurements (row order of graphs whose poses contradict their closures); 0.1.5: the multifrontal path for mid-size graphs (sgo_mfront_plan; sgo_solver_description names it); 0.1.4: sgo_kernel_profile_samples, sgo_update_graph_se2 (incremental set-up); 0.1.3: row-owner multi-GPU mode (sgo_comm_host_allgather, sgo_debug_level0_bytes); 0.1.2: sgo_comm_init_host; 0.1.1: sgo_opts.direct_rows (took a reserved slot), sgo_solver_description */
+#define SGO_VERSION 107          /* 0.1.7: (later additions under the same number, no signature changed: sgo_set_edge_information, sgo_gate_edges; sgo_set_robust_kernels, sgo_edge_robust, SGO_KERNEL_*; sgo_solve_rhs, sgo_marginals); sgo_stats.pcg_converged may be 2 (a solve accepted at the floating-point floor of its system), the incremental overlay keeps 64 touched + hub rows, SGO_AMG_SETUP (no signature changed); 0.1.6: sgo_plan_rows takes the measurements (row order of graphs whose poses contradict their closures); 0.1.5: the multifrontal path for mid-size graphs (sgo_mfront_plan; sgo_solver_description names it); 0.1.4: sgo_kernel_profile_samples, sgo_update_graph_se2 (incremental set-up); 0.1.3: row-owner multi-GPU mode (sgo_comm_host_allgather, sgo_debug_level0_bytes); 0.1.2: sgo_comm_init_host; 0.1.1: sgo_opts.direct_rows (took a reserved slot), sgo_solver_description */
 #define SGO_MAX_ITERS 256        /* capacity of the per-iteration arrays in sgo_stats */
 
 /* error codes (negative).  -1 mirrors g2o's optimize() "nothing to optimise". */
@@ -330,6 +330,34 @@ int sgo_hessian_apply(sgo_ctx* ctx, const double* x, double* y);
 int sgo_solve(sgo_ctx* ctx, double* x, double* relres);
 /* z = M^-1 r with the configured preconditioner of the last sgo_linearize (r, z: [n][3]). */
 int sgo_precondition(sgo_ctx* ctx, const double* r, double* z);
+/* H x = b for the CALLER's right-hand side, with the Hessian of the last sgo_linearize. b, x: [n][3] in hessian order.
+ * Same solver, tolerance (pcg_tol, relative to |b|), cold start and failure rules as sgo_solve; returns PCG iterations.
+ * Refuses what sgo_solve refuses, and a null or non-finite b.  The linearisation's own right-hand side is untouched: a later
+ * sgo_solve returns what it would have returned without this call. */
+int sgo_solve_rhs(sgo_ctx* ctx, const double* b, double* x, double* relres);
+
+/* Replaces: SparseOptimizer::computeMarginals(spinv, blockIndices).  For pair t the 3x3 block of H^-1 with the rows of
+ * vertex vi[t] and the columns of vertex vj[t] (VERTEX ids, not hessian indices), row-major in cov[t][9].
+ * H is the robustified Gauss-Newton Hessian at the CURRENT poses: the call linearises there itself (the weights of every kernel
+ * kind; inactive edges add nothing).  g2o inverts the system of its last iteration, one update behind the estimates; this is the
+ * system at the estimates the caller sees.
+ * No factorisation: for every distinct FREE vertex among vj three unit right-hand sides are solved with the level-0 PCG machinery
+ * of the single-step entry points, and the rows of the vi that were asked for are gathered on the device; the blocks cross to
+ * the host once, at the end.  Cost: three solves per distinct column vertex -- the order of a pair is the caller's lever.  Each
+ * solve is cold, at pcg_tol relative to its own right-hand side (no pcg_tol_cap, no soft cap), and the hierarchy's coarse
+ * operators are refreshed once per call.  A graph on the single-launch direct path or the multifrontal path builds its row plan
+ * and hierarchy on the first call, as sgo_linearize does, and stays on its path for sgo_optimize_gn.
+ * A pair with a fixed vertex on either side yields the zero block (a fixed pose has no uncertainty; a fixed column vertex costs
+ * no solve).  Blocks with vi == vj are symmetrised, (S + S^T) / 2; off-diagonal blocks come as solved.  A pair listed twice is
+ * answered twice.
+ * Returns the number of solves run, or a negative code.  A column that neither reached pcg_tol nor stands at the floating-point
+ * floor of its system (sgo_stats.pcg_converged == 2's rule) fails the whole call: SGO_EINVAL, sgo_last_error names the vertex
+ * and the relative residual, cov is left untouched.  Afterwards the context is linearised at the current poses, as after
+ * sgo_linearize.
+ * SGO_EINVAL, with nothing on the device changed: npairs < 0 or a null buffer, an id outside [0, V), a vertex that is not
+ * active (it has no edge), an active overlay (as the single-step entry points), a multi-GPU context (sgo_debug_set_shard's
+ * emulation included). */
+int sgo_marginals(sgo_ctx* ctx, int32_t npairs, const int32_t* vi, const int32_t* vj, double* cov);
 
 /* ---- profiling (opts.profile = 1) ---------------------------------------------------------- */
 /* Per-kernel totals accumulated since the last sgo_profile_reset: for kernel slot k,

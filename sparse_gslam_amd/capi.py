@@ -33,6 +33,7 @@ SYMBOLS = [
     "sgo_debug_overlay_array", "sgo_debug_overlay_linearize", "sgo_debug_overlay_apply",
     "sgo_debug_mfront_array", "sgo_mfront_plan_array", "sgo_debug_pcg_array", "sgo_debug_pcg_run",
     "sgo_set_edge_information", "sgo_gate_edges", "sgo_set_robust_kernels", "sgo_edge_robust",
+    "sgo_solve_rhs", "sgo_marginals",
 ]
 
 # SGO_KERNEL_*: the robust kernels sgo_set_robust_kernels takes, in include/sgo.h's numbering
@@ -129,6 +130,8 @@ def lib():
     L.sgo_hessian_apply.argtypes = [vp, d, d]
     L.sgo_solve.argtypes = [vp, d, d]
     L.sgo_precondition.argtypes = [vp, d, d]
+    L.sgo_solve_rhs.argtypes = [vp, d, d, d]
+    L.sgo_marginals.argtypes = [vp, C.c_int32, i32, i32, d]
     L.sgo_kernel_profile.argtypes = [vp, C.POINTER(KernelStat), C.c_int]
     L.sgo_kernel_profile_samples.argtypes = [vp, C.c_int, C.POINTER(C.c_float), C.c_int]
     L.sgo_solver_description.restype = C.c_char_p
@@ -537,6 +540,25 @@ class Optimizer:
         rr = C.c_double()
         it = self._check(lib().sgo_solve(self._h, _dp(x), C.byref(rr)), "sgo_solve")
         return x, it, rr.value
+
+    def solve_rhs(self, b):
+        """sgo_solve_rhs: H x = b for the caller's b (n_free, 3) with the Hessian of the last linearize() -> (x, iters, relres)."""
+        b = np.ascontiguousarray(b, dtype=np.float64).reshape(self.n_free, 3)
+        x = np.empty_like(b)
+        rr = C.c_double()
+        it = self._check(lib().sgo_solve_rhs(self._h, _dp(b), _dp(x), C.byref(rr)), "sgo_solve_rhs")
+        return x, it, rr.value
+
+    def marginals(self, vi, vj):
+        """sgo_marginals: the 3x3 blocks of H^-1 (rows of vertex vi[t], columns of vertex vj[t]; vertex ids) at the current poses
+        -> cov (npairs, 3, 3).  Three solves per distinct free vertex among vj; their number is kept in ``last_marginal_solves``."""
+        a = np.ascontiguousarray(vi, dtype=np.int32).reshape(-1)
+        b = np.ascontiguousarray(vj, dtype=np.int32).reshape(-1)
+        if a.size != b.size:
+            raise ValueError("inconsistent array sizes")
+        cov = np.empty((a.size, 3, 3))
+        self.last_marginal_solves = self._check(lib().sgo_marginals(self._h, a.size, _ip(a), _ip(b), _dp(cov)), "sgo_marginals")
+        return cov
 
     def pcg_run(self, maxit: int, x_prev=None, bb_ref: float = 0.0, probe_k: int = 0, probe_max: float = 0.0) -> int:
         """sgo_debug_pcg_run: sgo_solve under the per-call fields of an optimize() call; returns the iterations run."""

@@ -18,8 +18,6 @@ thread_local std::string g_err;  // for ctx == NULL
 // ---- edge activity: sgo_set_edge_information / sgo_gate_edges (include/sgo.h; kernels in sgo_gate.hip) -----------------------
 namespace {
 
-bool multi_gpu_context(const sgo_ctx* c) { return c->comm.nranks > 1 || c->comm.active(); }
-
 template <class T>
 int grow_scratch(sgo_ctx* c, T** p, size_t* cap, size_t count) {
   if (count <= *cap) return SGO_OK;
@@ -377,6 +375,8 @@ void sgo_destroy(sgo_ctx* c) {
   if (c->edges.d_mark) hipFree(c->edges.d_mark);
   if (c->edges.d_parts) hipFree(c->edges.d_parts);
   if (c->robust.d_kind) hipFree(c->robust.d_kind);
+  if (c->marg.d_cov) hipFree(c->marg.d_cov);
+  if (c->marg.d_idx) hipFree(c->marg.d_idx);
   if (c->stream) hipStreamDestroy(c->stream);
   delete c;
 }
@@ -1031,19 +1031,6 @@ int sgo_precondition(sgo_ctx* c, const double* r, double* z) {
     if (c->owner && !halo_gather_slices(c->halo, c->stream, c->d_s2, 3, &c->err)) return SGO_ECOMM;
     return vec_from_device(c, c->d_s2, z);
   } SGO_CATCH(c)
-}
-
-// What sgo_solve and sgo_debug_pcg_run share: the start state of the last linearisation again (idempotent re-finalize), start_pcg
-// under the context's current `call` fields, then the solve (run == false: the start state alone, its scalars copied to h_S).
-static int solve_from_linearization(sgo_ctx* c, bool run) {
-  int rc, grid = 0;
-  launch_finalize(c->stream, c->S0, c->owner ? c->halo.row0 : 0, c->owner ? c->halo.row1 : c->n, c->d_dgb, c->d_b, c->d_x, c->d_r,
-                  c->d_z, c->d_p, c->amg ? amg_xs0(c->amg) : nullptr, c->amg ? amg_omega(c->amg) : 0.0, c->d_partials, &grid);
-  if ((rc = start_pcg(c, grid))) return rc;
-  if (run) return run_pcg(c);
-  HIP_TRY(c, hipMemcpyAsync(c->h_S, c->d_S, sizeof(PcgScalars), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  return SGO_OK;
 }
 
 int sgo_solve(sgo_ctx* c, double* x, double* relres) {

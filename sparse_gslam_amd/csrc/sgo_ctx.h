@@ -3,6 +3,7 @@
 //   sgo_structure.cpp  device-resident graph: edge arrays, level-0 storage, tile view, logical view
 //   sgo_solve.cpp      Gauss-Newton driver: chi2, linearise, PCG loop (hipGraph replay), multigrid set-up calls
 //   sgo_api.cpp        the C-ABI entry points
+//   sgo_marginals.cpp  sgo_marginals / sgo_solve_rhs: columns of H^-1 through the level-0 PCG machinery
 // Not part of the public ABI.
 #pragma once
 #include <chrono>
@@ -97,6 +98,7 @@ struct sgo_ctx {
   bool has_graph = false;
   int V = 0, E = 0, n = 0;
   std::vector<int> free_id;      // hessian index (g2o order: free active vertices in ascending id) -> vertex id
+  std::vector<int> fixed_active; // the fixed vertices that have an edge, ascending (with free_id: the active vertices)
   std::vector<int> row_of_asc;   // hessian index -> internal row (Hilbert order, build_structure)
   HostLevel H0;                  // logical level-0 structure on the host (multigrid set-up input)
   double setup_seconds = 0.0;
@@ -250,6 +252,14 @@ struct sgo_ctx {
     size_t kind_cap = 0;
   } robust;
 
+  // Device scratch of sgo_marginals (sgo_marginals.cpp): the result blocks [npairs][9], the pairs' internal rows and the pairs
+  // ordered by column vertex; grown on demand, kept across graphs.
+  struct Marginals {
+    double* d_cov = nullptr;
+    int* d_idx = nullptr;             // [2][npairs]: pair_row, then order
+    size_t cov_cap = 0, idx_cap = 0;
+  } marg;
+
   // profiling
   struct Rec { int kid; hipEvent_t a, b; };
   std::vector<hipEvent_t> ev_pool;
@@ -266,6 +276,8 @@ struct sgo_ctx {
 
 namespace sgo {
 
+// a context with a communicator or sgo_debug_set_shard's emulation (whatever the resident graph's mode)
+inline bool multi_gpu_context(const sgo_ctx* c) { return c->comm.nranks > 1 || c->comm.active(); }
 // does this graph's solve run sharded over the ranks of the context's communicator (or of the rank-emulation hook)?
 inline bool multi_rank(const sgo_ctx* c) { return (c->comm.nranks > 1 || c->comm.active()) && !c->replicated; }
 
@@ -428,6 +440,12 @@ int start_pcg(sgo_ctx* c, int grid);
 int do_linearize(sgo_ctx* c);
 int do_spmv(sgo_ctx* c, const double* x, double* y, bool dot, const PcgScalars* S, int* grid_out);
 int run_pcg(sgo_ctx* c);
+// What sgo_solve, sgo_debug_pcg_run and the columns of sgo_marginals share: the start state from dgb again (idempotent re-finalize),
+// start_pcg under the context's current `call` fields, then the solve (run == false: the start state alone, its scalars in h_S).
+int solve_from_linearization(sgo_ctx* c, bool run);
+// A solve that stopped short of pcg_tol (stagnated, or out of iterations): *accept = its x stands at the floating-point floor of
+// its system (scaled backward error <= rules::kFloorEta, *eta); false, nothing computed, for any other solve.  Single GPU.
+int solve_at_floor(sgo_ctx* c, bool* accept, double* eta);
 void read_call_knobs(sgo_ctx* c);   // the environment knobs of a solve, once per entry-point call
 int build_amg(sgo_ctx* c, bool keep_old = false, bool keep_agg = false);
 int revert_amg(sgo_ctx* c);

@@ -370,6 +370,9 @@ enum KernelId : int {
   K_PROLONG_FOLD0,
   K_JACOBI0_RESTRICT,
   K_MFRONT,             // the multifrontal path: all launches of one optimize() (sgo_mfront.h)
+  K_RHS_INJECT,         // sgo_marginals / sgo_solve_rhs (sgo_marginals.hip)
+  K_RHS_RESTORE,
+  K_COV_GATHER,
   K_COUNT
 };
 extern const char* const kKernelNames[K_COUNT];
@@ -556,6 +559,15 @@ void launch_slot_kernel_refresh(hipStream_t s, int ncs, const int* eidx, const u
                                 const EdgeSlotsDev& es);
 // rho0[E + cnt2], w[E + cnt2] (either may be null) at `poses`, with launch_chi2's arithmetic
 void launch_edge_robust(hipStream_t s, const EdgeListDev& el, const EdgeListDev* el2, const double* poses, double* rho0, double* w);
+// ---- columns of H^-1 (sgo_marginals.hip; sgo_marginals, sgo_solve_rhs) ----
+// the b slots of dgb [n][9] := src [n][3] (internal row order) or, without it, the unit vector e_{3 unit_row + unit_k}; save
+// (optional, [n][3]) receives what they held
+void launch_rhs_inject(hipStream_t s, int n, double* dgb, double* save, const double* src, int unit_row, int unit_k);
+void launch_rhs_restore(hipStream_t s, int n, double* dgb, const double* save);
+// x = H^-1 e_{3 col_row + k}: for the pairs t = order[q0 .. q1) cov[t][a][k] = x[3 pair_row[t] + a]; with k == 2 the block of a
+// pair with pair_row[t] == col_row is symmetrised
+void launch_cov_gather(hipStream_t s, int q0, int q1, const int* order, const int* pair_row, int col_row, int k, int n, const double* x,
+                       double* cov);
 // strength weights of the logical slots (hrowptr: logical row pointers) straight from the edge list (sgo_kernels.hip)
 void launch_early_strength(hipStream_t s, const EdgeListDev& el, const double* poses, int n, const int* rowptr, const int* eidx,
                            const unsigned char* flags, const int* hrowptr, double* w);

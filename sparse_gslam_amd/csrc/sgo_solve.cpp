@@ -679,6 +679,17 @@ int run_pcg(sgo_ctx* c) {
   return SGO_OK;
 }
 
+int solve_from_linearization(sgo_ctx* c, bool run) {
+  int rc, grid = 0;
+  launch_finalize(c->stream, c->S0, c->owner ? c->halo.row0 : 0, c->owner ? c->halo.row1 : c->n, c->d_dgb, c->d_b, c->d_x, c->d_r,
+                  c->d_z, c->d_p, c->amg ? amg_xs0(c->amg) : nullptr, c->amg ? amg_omega(c->amg) : 0.0, c->d_partials, &grid);
+  if ((rc = start_pcg(c, grid))) return rc;
+  if (run) return run_pcg(c);
+  HIP_TRY(c, hipMemcpyAsync(c->h_S, c->d_S, sizeof(PcgScalars), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return SGO_OK;
+}
+
 std::string multi_gpu_description(const sgo_ctx* c) {
   if (c->owner)
     return "; multi-GPU row-owner mode: rank " + std::to_string(c->halo.me) + " of " + std::to_string(c->halo.G) + " owns rows [" +
@@ -1087,12 +1098,20 @@ static int linearize_step(sgo_ctx* c, CallPolicy& pol, int it, int iters) {
 
 // A solve that STAGNATED (run_pcg's guard) or ran out of iterations with x at the floating-point floor of its system: accepted,
 // like a backward-stable direct solver's solution (solve_backward_error above).  Single GPU (the guard's domain).
-static int check_floor(sgo_ctx* c, CallPolicy& pol, int it, bool* accept) {
-  if (*accept || !(c->h_S->stop == 2 && (c->pcg_stalled || c->h_S->iter >= c->opts.pcg_maxit) && !c->owner && !multi_rank(c))) return SGO_OK;
-  double eta = 1.0;
-  const int rc = solve_backward_error(c, &eta);
+int solve_at_floor(sgo_ctx* c, bool* accept, double* eta) {
+  *accept = false;
+  *eta = 1.0;
+  if (!(c->h_S->stop == 2 && (c->pcg_stalled || c->h_S->iter >= c->opts.pcg_maxit) && !c->owner && !multi_rank(c))) return SGO_OK;
+  const int rc = solve_backward_error(c, eta);
   if (rc) return rc;
-  *accept = eta <= rules::kFloorEta;
+  *accept = *eta <= rules::kFloorEta;
+  return SGO_OK;
+}
+static int check_floor(sgo_ctx* c, CallPolicy& pol, int it, bool* accept) {
+  if (*accept) return SGO_OK;
+  double eta = 1.0;
+  const int rc = solve_at_floor(c, accept, &eta);
+  if (rc) return rc;
   if (*accept) {
     ++pol.floor_solves;
     c->call.floor_seen = true;

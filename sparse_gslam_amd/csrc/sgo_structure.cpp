@@ -159,8 +159,9 @@ int build_edges(sgo_ctx* c, int V, const double* poses, const uint8_t* fixed, in
     deg[b]++;
   }
   c->free_id.clear();
+  c->fixed_active.clear();
   for (int v = 0; v < V; ++v)
-    if (!fixed[v] && deg[v] > 0) c->free_id.push_back(v);
+    if (deg[v] > 0) (fixed[v] ? c->fixed_active : c->free_id).push_back(v);
   c->V = V;
   c->E = E;
   c->n = (int)c->free_id.size();
