@@ -873,9 +873,11 @@ class SparseOptimizer : public OptimizableGraph {
     return done;
   }
   // ---- marginal covariances (SparseOptimizer::computeMarginals): the blocks (r, c) of H^-1 by HESSIAN index, as upstream, through
-  // sgo_marginals -- three solves per distinct column index (include/sgo.h).  The current estimates are uploaded as optimize()
+  // sgo_marginals -- three solves per distinct column index (include/sgo.h) --, or through sgo_marginals_selected when more than
+  // kSelectedMinColumns distinct columns are asked for (a routing rule, not a measured crossover).  The current estimates are uploaded as optimize()
   // uploads them, and H is the system AT them (upstream inverts the system of its last iteration).  spinv holds the blocks asked
   // for and nothing else.  A graph that takes the host solver has no marginals here: false, with one line on std::cerr.
+  static constexpr size_t kSelectedMinColumns = 8;
   bool computeMarginals(SparseBlockMatrix<MatrixX>& spinv, const std::vector<std::pair<int, int>>& blockIndices) {
     if (!_algorithm || !gpuEligible()) {
       std::cerr << "SparseOptimizer::computeMarginals: only the device path (VertexSE2 / EdgeSE2 under Gauss-Newton) computes marginals"
@@ -898,7 +900,19 @@ class SparseOptimizer : public OptimizableGraph {
     }
     if (!uploadGraph()) return false;
     std::vector<double> cov(9 * vi.size());
-    if (sgo_marginals(_ctx, (int32_t)vi.size(), vi.data(), vj.data(), cov.data()) < 0) {
+    // Routing: a request with more than kSelectedMinColumns distinct column vertices asks the selected inversion of the
+    // multifrontal factor first (sgo_marginals_selected: about one factorisation whatever the count) and comes back here when the
+    // analysis refuses the graph (SGO_ENOTHING) or a pair lies outside the factor's pattern (SGO_EINVAL with nothing written);
+    // smaller requests keep the column solves.
+    bool answered = false;
+    {
+      std::vector<int32_t> cols(vj);
+      std::sort(cols.begin(), cols.end());
+      const size_t distinct = (size_t)(std::unique(cols.begin(), cols.end()) - cols.begin());
+      if (distinct > kSelectedMinColumns)
+        answered = sgo_marginals_selected(_ctx, nullptr, (int32_t)vi.size(), vi.data(), vj.data(), cov.data()) >= 0;
+    }
+    if (!answered && sgo_marginals(_ctx, (int32_t)vi.size(), vi.data(), vj.data(), cov.data()) < 0) {
       std::cerr << "SparseOptimizer::computeMarginals: " << sgo_last_error(_ctx) << std::endl;
       return false;
     }

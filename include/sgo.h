@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define SGO_VERSION 107          /* 0.1.7: (later additions under the same number, no signature changed: sgo_set_edge_information, sgo_gate_edges; sgo_set_robust_kernels, sgo_edge_robust, SGO_KERNEL_*; sgo_solve_rhs, sgo_marginals); sgo_stats.pcg_converged may be 2 (a solve accepted at the floating-point floor of its system), the incremental overlay keeps 64 touched + hub rows, SGO_AMG_SETUP (no signature changed); 0.1.6: sgo_plan_rows takes the measurements (row order of graphs whose poses contradict their closures); 0.1.5: the multifrontal path for mid-size graphs (sgo_mfront_plan; sgo_solver_description names it); 0.1.4: sgo_kernel_profile_samples, sgo_update_graph_se2 (incremental set-up); 0.1.3: row-owner multi-GPU mode (sgo_comm_host_allgather, sgo_debug_level0_bytes); 0.1.2: sgo_comm_init_host; 0.1.1: sgo_opts.direct_rows (took a reserved slot), sgo_solver_description */
+#define SGO_VERSION 107          /* 0.1.7: (later additions under the same number, no signature changed: sgo_set_edge_information, sgo_gate_edges; sgo_set_robust_kernels, sgo_edge_robust, SGO_KERNEL_*; sgo_solve_rhs, sgo_marginals; sgo_marginals_selected, SGO_MF_SEL); sgo_stats.pcg_converged may be 2 (a solve accepted at the floating-point floor of its system), the incremental overlay keeps 64 touched + hub rows, SGO_AMG_SETUP (no signature changed); 0.1.6: sgo_plan_rows takes the measurements (row order of graphs whose poses contradict their closures); 0.1.5: the multifrontal path for mid-size graphs (sgo_mfront_plan; sgo_solver_description names it); 0.1.4: sgo_kernel_profile_samples, sgo_update_graph_se2 (incremental set-up); 0.1.3: row-owner multi-GPU mode (sgo_comm_host_allgather, sgo_debug_level0_bytes); 0.1.2: sgo_comm_init_host; 0.1.1: sgo_opts.direct_rows (took a reserved slot), sgo_solver_description */
 #define SGO_MAX_ITERS 256        /* capacity of the per-iteration arrays in sgo_stats */
 
 /* error codes (negative).  -1 mirrors g2o's optimize() "nothing to optimise". */
@@ -359,6 +359,28 @@ int sgo_solve_rhs(sgo_ctx* ctx, const double* b, double* x, double* relres);
  * emulation included). */
 int sgo_marginals(sgo_ctx* ctx, int32_t npairs, const int32_t* vi, const int32_t* vj, double* cov);
 
+/* The covariance of EVERY pose, and of pairs of poses that share a front, by selected inversion of the multifrontal Cholesky
+ * factor (Takahashi's recurrence: a top-down pass over the elimination tree, about the arithmetic of one factorisation whatever
+ * the number of blocks asked for).  H is the robustified Gauss-Newton Hessian at the CURRENT poses, exactly
+ * as in sgo_marginals: the call assembles and factorises there itself (the weights of every kernel kind; inactive edges add nothing).
+ * diag (NULL: not wanted): [V][9], the 3x3 block Sigma_vv of every vertex id, row-major, exactly symmetric (one triangle is
+ *   computed, the other is its mirror); a fixed vertex and a vertex without an edge yield the zero block.
+ * pairs: cov[t][9] = the block with the rows of vi[t] and the columns of vj[t].  A pair is answered when one front of the
+ *   factorisation holds both poses -- always for vi == vj and for two free poses joined by an edge the graph was set up with
+ *   (active or deactivated).  A pair with a fixed vertex is the zero block; a pair listed twice is answered twice; the block
+ *   (vi, vj) is the transpose of (vj, vi) bit for bit.  A pair outside the pattern refuses the whole call (SGO_EINVAL, nothing
+ *   written; sgo_last_error names the pair): such blocks are sgo_marginals' to compute.
+ * The plan is the resident multifrontal one when sgo_optimize_gn takes that path.  A graph on the single-launch direct path or the
+ * PCG gets a multifrontal plan of its own, analysed once per set-up under the multifrontal path's admission limits (SGO_MFRONT_*
+ * of the environment included; SGO_MFRONT=0 only keeps optimize() off that path); sgo_optimize_gn keeps its path, and a later
+ * call has the chi2 history and the poses, bit for bit, of a context that never made this call.  SGO_ENOTHING with the analysis'
+ * reason in sgo_last_error when the analysis refuses the graph: use sgo_marginals then.
+ * SGO_EINVAL, with nothing on the device changed: npairs < 0 or a null buffer where one is needed, an id outside [0, V), a pair
+ * naming a vertex that is not active, an active overlay, a multi-GPU context (sgo_debug_set_shard's emulation included).
+ * SGO_EINVAL with the outputs untouched when the factorisation is not positive definite; the next sgo_optimize_gn is unaffected.
+ * Returns the number of fronts of the plan, or a negative code.  Two calls at the same poses give the same bits. */
+int sgo_marginals_selected(sgo_ctx* ctx, double* diag, int32_t npairs, const int32_t* vi, const int32_t* vj, double* cov);
+
 /* ---- profiling (opts.profile = 1) ---------------------------------------------------------- */
 /* Per-kernel totals accumulated since the last sgo_profile_reset: for kernel slot k,
  * name (static string), launches, total milliseconds (HIP events on the ctx stream), and the
@@ -584,7 +606,12 @@ int sgo_debug_overlay_apply(sgo_ctx* ctx, const double* x, double* y, double* do
  *                forward-substituted right-hand side; columns >= own3 the assembled boundary block and its right-hand side
  *   X            double[3 n]: the step by elimination position;  INVD double[3 n]: 1 / L[c][c];  YINV double[3 n][16]: row i of the
  *                inverse of its 16 x 16 diagonal block's factor
- *   FLAGS        int32[8]: fail, iteration of the failure, non-finite substitution, updates applied */
+ *   FLAGS        int32[8]: fail, iteration of the failure, non-finite substitution, updates applied
+ *   SEL          double, ARENA's size: every front's selected inverse as the last sgo_marginals_selected stored it -- the front's
+ *                own layout (same off and ld, lower triangle, row m unused); 0 bytes before the first such call.  After
+ *                sgo_marginals_selected the other arrays describe the factor at the current poses (ELEM, ARENA, INVD, YINV, FLAGS
+ *                are rewritten by its factor phase) and X is unchanged; on a graph that is not on the multifrontal path the hook
+ *                then reads the plan that call analysed for itself. */
 #define SGO_MF_INFO 0
 #define SGO_MF_FRONTS 1
 #define SGO_MF_LEVEL_PTR 2
@@ -600,6 +627,7 @@ int sgo_debug_overlay_apply(sgo_ctx* ctx, const double* x, double* y, double* do
 #define SGO_MF_INVD 12
 #define SGO_MF_YINV 13
 #define SGO_MF_FLAGS 14
+#define SGO_MF_SEL 15
 int64_t sgo_debug_mfront_array(sgo_ctx* ctx, int32_t what, void* out, int64_t cap_bytes);
 int64_t sgo_mfront_plan_array(int32_t V, const double* poses, const uint8_t* fixed, int32_t E, const int32_t* ei, const int32_t* ej,
                               int32_t leaf, double max_crit_mflop, int32_t what, void* out, int64_t cap_bytes);

@@ -33,7 +33,7 @@ SYMBOLS = [
     "sgo_debug_overlay_array", "sgo_debug_overlay_linearize", "sgo_debug_overlay_apply",
     "sgo_debug_mfront_array", "sgo_mfront_plan_array", "sgo_debug_pcg_array", "sgo_debug_pcg_run",
     "sgo_set_edge_information", "sgo_gate_edges", "sgo_set_robust_kernels", "sgo_edge_robust",
-    "sgo_solve_rhs", "sgo_marginals",
+    "sgo_solve_rhs", "sgo_marginals", "sgo_marginals_selected",
 ]
 
 # SGO_KERNEL_*: the robust kernels sgo_set_robust_kernels takes, in include/sgo.h's numbering
@@ -132,6 +132,7 @@ def lib():
     L.sgo_precondition.argtypes = [vp, d, d]
     L.sgo_solve_rhs.argtypes = [vp, d, d, d]
     L.sgo_marginals.argtypes = [vp, C.c_int32, i32, i32, d]
+    L.sgo_marginals_selected.argtypes = [vp, d, C.c_int32, i32, i32, d]
     L.sgo_kernel_profile.argtypes = [vp, C.POINTER(KernelStat), C.c_int]
     L.sgo_kernel_profile_samples.argtypes = [vp, C.c_int, C.POINTER(C.c_float), C.c_int]
     L.sgo_solver_description.restype = C.c_char_p
@@ -251,7 +252,8 @@ def mfront_plan(poses, fixed, ei, ej, leaf: int = 0, max_crit_mflop: float = 0.0
 MFRONT_ARRAYS = {"INFO": (0, np.int64, 0), "FRONTS": (1, np.int64, 14), "LEVEL_PTR": (2, np.int32, 0), "LEVEL_FRONT": (3, np.int32, 0),
                  "BND": (4, np.int32, 0), "PINV": (5, np.int32, 0), "TARGETS": (6, np.int32, 4), "CONTRIB": (7, np.int32, 0),
                  "ELIM_VERTEX": (8, np.int32, 0), "ELEM": (9, np.float64, 28), "ARENA": (10, np.float64, 0), "X": (11, np.float64, 0),
-                 "INVD": (12, np.float64, 0), "YINV": (13, np.float64, 16), "FLAGS": (14, np.int32, 0)}
+                 "INVD": (12, np.float64, 0), "YINV": (13, np.float64, 16), "FLAGS": (14, np.int32, 0),
+                 "SEL": (15, np.float64, 0)}
 MFRONT_PLAN_ARRAYS = ("INFO", "FRONTS", "LEVEL_PTR", "LEVEL_FRONT", "BND", "PINV", "TARGETS", "CONTRIB", "ELIM_VERTEX")
 
 
@@ -549,6 +551,24 @@ class Optimizer:
         it = self._check(lib().sgo_solve_rhs(self._h, _dp(b), _dp(x), C.byref(rr)), "sgo_solve_rhs")
         return x, it, rr.value
 
+    def marginals_selected(self, vi=None, vj=None, diag=True):
+        """sgo_marginals_selected: the 3x3 covariance block of every vertex (diag=True -> (V, 3, 3), zero blocks for fixed vertices
+        and vertices without an edge) and the blocks (rows of vi[t], columns of vj[t]) of pairs that share a front of the
+        multifrontal factorisation -> (diag or None, cov (npairs, 3, 3)).  One factorisation and one top-down pass whatever the
+        counts; the number of fronts is kept in ``last_selected_fronts``.  SgoError with rc=-1 when the multifrontal analysis
+        refuses the graph (use marginals then)."""
+        a = np.ascontiguousarray([] if vi is None else vi, dtype=np.int32).reshape(-1)
+        b = np.ascontiguousarray([] if vj is None else vj, dtype=np.int32).reshape(-1)
+        if a.size != b.size:
+            raise ValueError("inconsistent array sizes")
+        D = np.empty((self.V, 3, 3)) if diag else None
+        cov = np.empty((a.size, 3, 3))
+        rc = lib().sgo_marginals_selected(self._h, _dp(D) if diag else None, a.size, _ip(a), _ip(b), _dp(cov))
+        if rc < 0:
+            raise SgoError(f"sgo_marginals_selected: rc={rc}: " + lib().sgo_last_error(self._h).decode())
+        self.last_selected_fronts = rc
+        return D, cov
+
     def marginals(self, vi, vj):
         """sgo_marginals: the 3x3 blocks of H^-1 (rows of vertex vi[t], columns of vertex vj[t]; vertex ids) at the current poses
         -> cov (npairs, 3, 3).  Three solves per distinct free vertex among vj; their number is kept in ``last_marginal_solves``."""
@@ -590,8 +610,9 @@ class Optimizer:
         """Text of the last error on this context (sgo_last_error)."""
         return lib().sgo_last_error(self._h).decode()
 
-    def mfront_arrays(self, names=tuple(MFRONT_ARRAYS)):
-        """The resident multifrontal factorisation's arrays as the last optimize() left them (sgo_debug_mfront_array)."""
+    def mfront_arrays(self, names=tuple(k for k in MFRONT_ARRAYS if k != "SEL")):
+        """The resident multifrontal factorisation's arrays as the last optimize() left them (sgo_debug_mfront_array).  "SEL", the
+        selected inverse of the last marginals_selected (empty before the first), comes only when named."""
         return {k: _mfront_fetch(k, lambda what, out, cap: lib().sgo_debug_mfront_array(self._h, what, out, cap), self.last_error)
                 for k in names}
 

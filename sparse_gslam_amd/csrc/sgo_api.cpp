@@ -377,6 +377,8 @@ void sgo_destroy(sgo_ctx* c) {
   if (c->robust.d_kind) hipFree(c->robust.d_kind);
   if (c->marg.d_cov) hipFree(c->marg.d_cov);
   if (c->marg.d_idx) hipFree(c->marg.d_idx);
+  if (c->selinv.d_out) hipFree(c->selinv.d_out);
+  if (c->selinv.d_pairs) hipFree(c->selinv.d_pairs);
   if (c->stream) hipStreamDestroy(c->stream);
   delete c;
 }
@@ -1325,12 +1327,13 @@ int64_t sgo_debug_mfront_array(sgo_ctx* c, int32_t what, void* out, int64_t cap_
   try {
     int rc = check_graph(c);
     if (rc) return rc;
-    if (!c->mf) {
+    Mfront* mf = c->mf ? c->mf : c->selinv.mf;   // (a graph on another path: the plan sgo_marginals_selected made for itself, if any)
+    if (!mf) {
       c->err = "sgo_debug_mfront_array: the resident graph is not on the multifrontal path (" + c->solver_desc.substr(0, c->solver_desc.find(':')) + ")";
       return SGO_EINVAL;
     }
     if (cap_bytes < 0 || (cap_bytes > 0 && !out)) return SGO_EINVAL;
-    const long long r = mfront_debug_array(c->mf, c->stream, what, out, cap_bytes);
+    const long long r = mfront_debug_array(mf, c->stream, what, out, cap_bytes);
     if (r == SGO_ENOTHING) {
       c->err = "sgo_debug_mfront_array: no sgo_optimize_gn has run on the resident graph";
       return SGO_EINVAL;

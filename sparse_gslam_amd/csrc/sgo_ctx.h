@@ -4,6 +4,7 @@
 //   sgo_solve.cpp      Gauss-Newton driver: chi2, linearise, PCG loop (hipGraph replay), multigrid set-up calls
 //   sgo_api.cpp        the C-ABI entry points
 //   sgo_marginals.cpp  sgo_marginals / sgo_solve_rhs: columns of H^-1 through the level-0 PCG machinery
+//   sgo_selinv.cpp     sgo_marginals_selected: every block of H^-1 inside the multifrontal factor's pattern
 // Not part of the public ABI.
 #pragma once
 #include <chrono>
@@ -259,6 +260,17 @@ struct sgo_ctx {
     int* d_idx = nullptr;             // [2][npairs]: pair_row, then order
     size_t cov_cap = 0, idx_cap = 0;
   } marg;
+
+  // sgo_marginals_selected (sgo_selinv.cpp): the multifrontal plan analysed for this purpose when optimize() is on another path
+  // (once per set-up: `tried`, `why` the analysis' refusal), and the call's device scratch (grown on demand, kept across graphs)
+  struct SelInv {
+    Mfront* mf = nullptr;
+    bool tried = false;
+    std::string why;
+    double* d_out = nullptr;          // [V][9] + [npairs][9] + the failure flag
+    int4* d_pairs = nullptr;          // (front, local row pose, local column pose, transpose)
+    size_t out_cap = 0, pairs_cap = 0;
+  } selinv;
 
   // profiling
   struct Rec { int kid; hipEvent_t a, b; };

@@ -373,6 +373,10 @@ enum KernelId : int {
   K_RHS_INJECT,         // sgo_marginals / sgo_solve_rhs (sgo_marginals.hip)
   K_RHS_RESTORE,
   K_COV_GATHER,
+  K_MF_FACTOR,          // sgo_marginals_selected: the factor phase (all its launches), then the selected inversion's kernels (sgo_selinv.hip)
+  K_SI_GATHER,
+  K_SI_PANELS,
+  K_SI_RESULT,
   K_COUNT
 };
 extern const char* const kKernelNames[K_COUNT];

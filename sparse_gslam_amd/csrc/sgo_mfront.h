@@ -116,7 +116,11 @@ const MfrontInfo& mfront_info(const Mfront* m);
 hipError_t mfront_optimize(Mfront* m, hipStream_t s, const EdgeListDev& el, double* d_poses, int iters, double* d_hist,
                            DirectResult* d_res);
 double mfront_bytes(const Mfront* m, int E, int iters);
-// Test hook (sgo_debug_mfront_array): one resident array as stored after the last mfront_optimize; SGO_ENOTHING before the first.
+// The factor phase of one iteration alone, at the current poses: edges (elements, chi2 partials), then merge and panels per level --
+// mfront_optimize's own launches up to and excluding the substitution and the update.  Clears the failure flags first; x is untouched.
+hipError_t mfront_factorize(Mfront* m, hipStream_t s, const EdgeListDev& el, const double* d_poses, double* d_hist, DirectResult* d_res);
+// Test hook (sgo_debug_mfront_array): one resident array as stored after the last mfront_optimize or selected inversion;
+// SGO_ENOTHING before the first (SGO_MF_SEL: 0 bytes before the first selected inversion).
 long long mfront_debug_array(const Mfront* m, hipStream_t s, int what, void* out, long long cap_bytes);
 
 }  // namespace sgo

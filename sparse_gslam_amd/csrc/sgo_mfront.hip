@@ -24,45 +24,10 @@
 #include "sgo_device.h"
 #include "sgo_internal.h"
 #include "sgo_mfront.h"
+#include "sgo_mfront_dev.h"
 
 namespace sgo {
 namespace {
-
-constexpr int kMfNW = kMfThreads / 64;
-constexpr int kElemStride = 28;   // kMfElem padded to 16-byte multiples
-
-struct MfFrontDev {
-  int e0, own3, m, ld;
-  long long off;
-  int nb, bnd_off;
-  int kid[2];
-  int pinv_off[2];   // child k: pinv[pinv_off[k] + local pose] = its index among the child's boundary poses, -1: not there
-  int tgt0, tgt1;
-  int parent;
-};
-
-struct MfDev {
-  int n = 0, E = 0, nfront = 0;
-  const MfFrontDev* fronts = nullptr;
-  const int* level_front = nullptr;
-  const int* bnd = nullptr;
-  const int* pinv = nullptr;
-  const int2* mtile = nullptr;   // k_mf_merge's work list: (front, tile row | tile column << 16), level by level
-  const MfTarget* targets = nullptr;
-  const int* contrib = nullptr;
-  const int* elim_vertex = nullptr;
-  double* arena = nullptr;
-  double* elem = nullptr;      // [E][kElemStride]
-  double* x = nullptr;         // [3 n] by elimination position
-  double* invd = nullptr;      // [3 n] 1 / L[c][c] of every eliminated scalar row (k_mf_panels), for the substitution
-  double* yinv = nullptr;      // [3 n][16] row i of the inverse of its 16 x 16 diagonal block's factor (zeros right of the diagonal)
-  double* partials = nullptr;  // [2][kMaxPartials]
-  long long* dbg = nullptr;    // diagnostic runs (SGO_MFRONT_DEBUG): [nfront][8] s_memtime cycles of the factor kernel's phases
-  int* flags = nullptr;        // [0] fail (1 not positive definite, 2 non-finite update)  [1] iteration of the failure
-                               // [2] a back-substitution produced a non-finite value  [3] updates applied
-};
-
-typedef double mf_d4 __attribute__((ext_vector_type(4)));
 
 // acc += sum_{k < K} L[ra][k] L[rb][k] for the 16 x 16 tile whose operand rows this lane addresses through pa / pb (= the
 // front's matrix + (lane >> 4) * ld + row: rows beyond the front are CLAMPED by the caller, not masked -- a tile element
@@ -716,18 +681,6 @@ __global__ __launch_bounds__(64) void k_mf_finish(MfDev M, int iters, int nparts
 
 }  // namespace
 
-struct Mfront {
-  MfPlan plan;
-  MfrontInfo info;
-  MfDev dev;
-  void* buf = nullptr;
-  std::vector<int> level_lds;        // dynamic LDS of the panel launch of every level
-  std::vector<int> level_solve_lds;  // ... of the substitution launch
-  std::vector<int> mtile_ptr;        // k_mf_merge's tiles of level h: [mtile_ptr[h], mtile_ptr[h + 1])
-  size_t n_pinv = 0;                 // entries of dev.pinv
-  bool ran = false;                  // an mfront_optimize with iters > 0 has filled elem, the arena, x, invd and yinv
-};
-
 const MfrontInfo& mfront_info(const Mfront* m) { return m->info; }
 
 void mfront_destroy(Mfront* m) {
@@ -963,6 +916,30 @@ hipError_t mfront_optimize(Mfront* m, hipStream_t s, const EdgeListDev& el, doub
   return hipGetLastError();
 }
 
+// The factor phase alone: what one iteration of mfront_optimize does up to and excluding k_mf_solve / k_mf_update, at the current
+// poses -- k_mf_edges with the elements, then merge and panels level by level.  The same launches with the same arguments as
+// iteration 0 of mfront_optimize (d_hist[0 .. 1] and d_res->stamp[0 .. 1] are written as there); the flags are cleared first.
+hipError_t mfront_factorize(Mfront* m, hipStream_t s, const EdgeListDev& el, const double* d_poses, double* d_hist, DirectResult* d_res) {
+  const MfPlan& P = m->plan;
+  const MfDev& D = m->dev;
+  hipError_t he = hipMemsetAsync(D.flags, 0, sizeof(int) * 8, s);
+  if (he != hipSuccess) return he;
+  const int egrid = std::max(1, std::min((D.E + kBlock - 1) / kBlock, kMaxPartials));
+  if (el.kinds) hipLaunchKernelGGL(k_mf_edges<true>, dim3(egrid), dim3(kBlock), 0, s, D, el, d_poses, 0, 0, d_hist, d_res);
+  else hipLaunchKernelGGL(k_mf_edges<false>, dim3(egrid), dim3(kBlock), 0, s, D, el, d_poses, 0, 0, d_hist, d_res);
+  for (int h = 0; h <= P.height; ++h) {
+    const int cnt = P.level_ptr[h + 1] - P.level_ptr[h];
+    if (h > 0) {
+      const int nt = m->mtile_ptr[h + 1] - m->mtile_ptr[h];
+      const int grid = std::max(1, std::min((nt + kWavesPerBlock - 1) / kWavesPerBlock, 8192));
+      hipLaunchKernelGGL(k_mf_merge, dim3(grid), dim3(kBlock), 0, s, D, m->mtile_ptr[h], m->mtile_ptr[h + 1]);
+    }
+    hipLaunchKernelGGL(k_mf_panels, dim3(cnt), dim3(kMfThreads), (size_t)m->level_lds[h], s, D, P.level_ptr[h], 0, h == 0 ? 1 : -1,
+                       h == 0 ? egrid : 0, d_hist, d_res);
+  }
+  return hipGetLastError();
+}
+
 // The plan's arrays by their SGO_MF_* numbers, from the host's copy
 long long mfront_plan_array(const MfPlan& P, int E, int what, void* out, long long cap_bytes) {
   std::vector<long long> l64;
@@ -994,7 +971,8 @@ long long mfront_plan_array(const MfPlan& P, int E, int what, void* out, long lo
 // The test hook's copy: device memory as stored.  The front table is the one regrouping: MfFrontDev's fields as int64 columns.
 // INFO and LEVEL_PTR have no device copy (the host sizes the launches with them): they come from the host plan.
 long long mfront_debug_array(const Mfront* m, hipStream_t s, int what, void* out, long long cap_bytes) {
-  if (!m->ran) return SGO_ENOTHING;
+  if (what == SGO_MF_SEL && !m->sel_ran) return 0;
+  if (!m->ran && !m->sel_ran) return SGO_ENOTHING;
   const MfPlan& P = m->plan;
   const MfDev& D = m->dev;
   if (what == SGO_MF_INFO || what == SGO_MF_LEVEL_PTR) return mfront_plan_array(P, D.E, what, out, cap_bytes);
@@ -1015,6 +993,7 @@ long long mfront_debug_array(const Mfront* m, hipStream_t s, int what, void* out
     case SGO_MF_INVD: src = D.invd; bytes = F * n3; break;
     case SGO_MF_YINV: src = D.yinv; bytes = F * n3 * kMfPanel; break;
     case SGO_MF_FLAGS: src = D.flags; bytes = I * 8; break;
+    case SGO_MF_SEL: src = m->sel.S; bytes = F * P.arena_doubles; break;
     default: return SGO_EINVAL;
   }
   if (bytes == 0 || cap_bytes < bytes) return bytes;

@@ -1,0 +1,85 @@
+// sgo_mfront_dev.h -- what the multifrontal path's two device sources share: the device image of the plan and the resident
+// factorisation (sgo_mfront.hip makes and fills it; sgo_selinv.hip reads the factor for the selected inversion) and the opaque
+// Mfront behind sgo_mfront.h.  Not for the host-only sources.
+#pragma once
+#include <vector>
+
+#include <hip/hip_runtime.h>
+
+#include "sgo_mfront.h"
+
+namespace sgo {
+
+constexpr int kMfNW = kMfThreads / 64;
+constexpr int kElemStride = 28;   // kMfElem padded to 16-byte multiples
+
+struct MfFrontDev {
+  int e0, own3, m, ld;
+  long long off;
+  int nb, bnd_off;
+  int kid[2];
+  int pinv_off[2];   // child k: pinv[pinv_off[k] + local pose] = its index among the child's boundary poses, -1: not there
+  int tgt0, tgt1;
+  int parent;
+};
+
+struct MfDev {
+  int n = 0, E = 0, nfront = 0;
+  const MfFrontDev* fronts = nullptr;
+  const int* level_front = nullptr;
+  const int* bnd = nullptr;
+  const int* pinv = nullptr;
+  const int2* mtile = nullptr;   // k_mf_merge's work list: (front, tile row | tile column << 16), level by level
+  const MfTarget* targets = nullptr;
+  const int* contrib = nullptr;
+  const int* elim_vertex = nullptr;
+  double* arena = nullptr;
+  double* elem = nullptr;      // [E][kElemStride]
+  double* x = nullptr;         // [3 n] by elimination position
+  double* invd = nullptr;      // [3 n] 1 / L[c][c] of every eliminated scalar row (k_mf_panels), for the substitution
+  double* yinv = nullptr;      // [3 n][16] row i of the inverse of its 16 x 16 diagonal block's factor (zeros right of the diagonal)
+  double* partials = nullptr;  // [2][kMaxPartials]
+  long long* dbg = nullptr;    // diagnostic runs (SGO_MFRONT_DEBUG): [nfront][8] s_memtime cycles of the factor kernel's phases
+  int* flags = nullptr;        // [0] fail (1 not positive definite, 2 non-finite update)  [1] iteration of the failure
+                               // [2] a back-substitution produced a non-finite value  [3] updates applied
+};
+
+typedef double mf_d4 __attribute__((ext_vector_type(4)));
+
+// The selected inversion's share of the device image (sgo_selinv.hip, sgo_selinv.cpp): made by the first sgo_marginals_selected
+// on the graph, out of the same per-graph arena.
+struct MfSelDev {
+  double* S = nullptr;            // the second arena: front f's selected inverse at fronts[f].off, the front's own layout
+  const int* cmap = nullptr;      // the plan's extend-add maps: child boundary pose -> local pose of the parent
+  const int* cmap_off = nullptr;  // [nfront] where front f's map starts (a root: 0, unused)
+  const int2* gtile = nullptr;    // k_si_gather's work list: (front, tile row | tile column << 16) of the boundary block, level by level
+  const int* pos_front = nullptr; // [n] elimination position -> the front that owns it
+};
+
+struct Mfront {
+  MfPlan plan;
+  MfrontInfo info;
+  MfDev dev;
+  void* buf = nullptr;
+  std::vector<int> level_lds;        // dynamic LDS of the panel launch of every level
+  std::vector<int> level_solve_lds;  // ... of the substitution launch
+  std::vector<int> mtile_ptr;        // k_mf_merge's tiles of level h: [mtile_ptr[h], mtile_ptr[h + 1])
+  size_t n_pinv = 0;                 // entries of dev.pinv
+  bool ran = false;                  // an mfront_optimize with iters > 0 has filled elem, the arena, x, invd and yinv
+  // selected inversion
+  MfSelDev sel;
+  bool sel_ready = false;            // sel's arrays exist
+  bool sel_ran = false;              // a selected inversion has filled sel.S (and mfront_factorize the factor's arrays)
+  std::vector<int> gtile_ptr;        // k_si_gather's tiles of level h: [gtile_ptr[h], gtile_ptr[h + 1])
+  std::vector<int> pos_front;        // host copy of sel.pos_front
+};
+
+// ---- kernels of the selected inversion (sgo_selinv.hip), one launch each; the host driver is sgo_selinv.cpp ----
+void launch_si_gather(hipStream_t s, const MfDev& M, const MfSelDev& Z, int t0, int t1);
+void launch_si_panels(hipStream_t s, const MfDev& M, const MfSelDev& Z, int lvl0, int count, size_t lds);
+// out: [V][9] diagonal blocks by vertex id, then [npairs][9], then one double: the factorisation's failure flag.  pairs[t] =
+// (front, local row pose, local column pose, transpose), front < 0: the zero block.  The caller has zeroed out.
+void launch_si_result(hipStream_t s, const MfDev& M, const MfSelDev& Z, int V, int npairs, const int4* pairs, double* out);
+bool si_prepare_device();   // the panel kernel's dynamic LDS; false: the device does not grant it
+
+}  // namespace sgo

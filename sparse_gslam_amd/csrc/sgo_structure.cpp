@@ -97,6 +97,12 @@ void free_graph(sgo_ctx* c) {
     mfront_destroy(c->mf);
     c->mf = nullptr;
   }
+  if (c->selinv.mf) {
+    mfront_destroy(c->selinv.mf);
+    c->selinv.mf = nullptr;
+  }
+  c->selinv.tried = false;
+  c->selinv.why.clear();
   c->amg_pending = false;
   c->order_xy.clear();
   c->rows_pending = false;
