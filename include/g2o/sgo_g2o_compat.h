@@ -717,6 +717,7 @@ class SparseOptimizer : public OptimizableGraph {
     if (!v || v->id() < 0) return false;
     if (_vertices.find(v->id()) != _vertices.end()) return false;
     _vertices[v->id()] = v;
+    ++_revision;
     return true;
   }
   bool addEdge(HyperGraph::Edge* e) {
@@ -726,6 +727,7 @@ class SparseOptimizer : public OptimizableGraph {
     if (!_edges.insert(e).second) return false;
     e->_internalId = _nextEdgeId++;
     for (auto* v : e->vertices()) v->edges().insert(e);
+    ++_revision;
     return true;
   }
   bool removeEdge(HyperGraph::Edge* e) {
@@ -734,6 +736,7 @@ class SparseOptimizer : public OptimizableGraph {
     _edges.erase(it);
     for (auto* v : e->vertices())
       if (v) v->edges().erase(e);
+    ++_revision;
     return true;
   }
   bool removeVertex(HyperGraph::Vertex* v, bool = false) {
@@ -742,6 +745,7 @@ class SparseOptimizer : public OptimizableGraph {
     std::set<HyperGraph::Edge*> tmp(v->edges());
     for (auto* e : tmp) removeEdge(e);
     _vertices.erase(it);
+    ++_revision;
     return true;
   }
   OptimizableGraph::Vertex* vertex(int id) {
@@ -758,6 +762,7 @@ class SparseOptimizer : public OptimizableGraph {
     _activeVertices.clear();
     _activeEdges.clear();
     _graphOnDevice = false;
+    ++_revision;
   }
 
   // ---- optimisation
@@ -797,6 +802,7 @@ class SparseOptimizer : public OptimizableGraph {
               [](OptimizableGraph::Vertex* a, OptimizableGraph::Vertex* b) { return a->id() < b->id(); });
     int h = 0;
     for (auto* v : _activeVertices) v->setHessianIndex(v->fixed() ? -1 : h++);
+    _activeRevision = _revision;
     // (what the device holds stays known: optimize() marshals the active sets again and compares -- an unchanged graph
     // uploads poses only, a graph that grew by a chain and a closure becomes an incremental update)
     return true;
@@ -836,6 +842,7 @@ class SparseOptimizer : public OptimizableGraph {
       _activeVertices.push_back(v);
     }
     for (auto* e : ne) _activeEdges.push_back(e);
+    _activeRevision = _revision;
     return true;
   }
 
@@ -938,6 +945,51 @@ class SparseOptimizer : public OptimizableGraph {
       if (h >= 0) indices.push_back(std::make_pair(h, h));
     }
     return computeMarginals(spinv, indices);
+  }
+
+  // ---- the innovation gate for candidate closures (extension; sgo_candidate_gate of include/sgo.h): is a candidate compatible with
+  // the current estimates AND their uncertainty, before it is inserted?  The candidates are EdgeSE2 objects as the reference builds
+  // them before addEdge (slc.cpp:273-280): both vertices set, measurement, information; they are not added to the graph.  (*d2)[t] =
+  // e^T (Omega^-1 + J Sigma J^T)^-1 e at the current estimates, (*pass)[t] = d2 <= chi2Max; returns how many pass.  Returns -1 without
+  // touching the outputs when the backend does not hold the graph as it stands (vertices or edges added or removed since the last
+  // initializeOptimization / updateInitialization), when the graph takes the host solver (Levenberg, other types), when a
+  // candidate's vertex is not an active vertex of the graph, or when the call itself refuses (one line on std::cerr).
+  int sgoCandidateGate(const std::vector<EdgeSE2*>& candidates, double chi2Max, std::vector<double>* d2, std::vector<bool>* pass) {
+    if (!_algorithm || _activeRevision != _revision || _activeVertices.empty() || !gpuEligible()) return -1;
+    const size_t n = candidates.size();
+    std::vector<int32_t> ci(n), cj(n);
+    std::vector<double> meas(3 * n), info(6 * n);
+    for (size_t t = 0; t < n; ++t) {
+      const EdgeSE2* e = candidates[t];
+      if (!e) return -1;
+      for (int side = 0; side < 2; ++side) {
+        const HyperGraph::Vertex* v = e->vertex(side);
+        if (!v) return -1;
+        // (the compact number uploadGraph gives: the vertex's place among the active vertices, which are sorted by id)
+        auto it = std::lower_bound(_activeVertices.begin(), _activeVertices.end(), v->id(),
+                                   [](const OptimizableGraph::Vertex* a, int id) { return a->id() < id; });
+        if (it == _activeVertices.end() || *it != v) return -1;
+        (side ? cj : ci)[t] = (int32_t)(it - _activeVertices.begin());
+      }
+      for (int q = 0; q < 3; ++q) meas[3 * t + q] = e->measurement()[q];
+      const auto& O = e->information();
+      double* o = &info[6 * t];
+      o[0] = O(0, 0); o[1] = O(0, 1); o[2] = O(0, 2); o[3] = O(1, 1); o[4] = O(1, 2); o[5] = O(2, 2);
+    }
+    if (!uploadGraph()) return -1;
+    std::vector<double> dd(n);
+    std::vector<uint8_t> ok(n);
+    const int rc = sgo_candidate_gate(_ctx, (int32_t)n, ci.data(), cj.data(), meas.data(), info.data(), chi2Max, dd.data(), nullptr, ok.data());
+    if (rc < 0) {
+      std::cerr << "SparseOptimizer::sgoCandidateGate: " << sgo_last_error(_ctx) << std::endl;
+      return -1;
+    }
+    if (d2) d2->assign(dd.begin(), dd.end());
+    if (pass) {
+      pass->resize(n);
+      for (size_t t = 0; t < n; ++t) (*pass)[t] = ok[t] != 0;
+    }
+    return rc;
   }
 
   // ---- graph files (OptimizableGraph::load / save of g2o, for the types of this backend's device path):
@@ -1363,6 +1415,7 @@ class SparseOptimizer : public OptimizableGraph {
   VertexIDMap _vertices;
   EdgeSet _edges;
   long long _nextEdgeId = 0;
+  long long _revision = 0, _activeRevision = -1;   // container changes so far | ... when the active sets were last made
   std::vector<OptimizableGraph::Vertex*> _activeVertices;
   std::vector<OptimizableGraph::Edge*> _activeEdges;
   sgo_ctx* _ctx = nullptr;

@@ -381,6 +381,46 @@ int sgo_marginals(sgo_ctx* ctx, int32_t npairs, const int32_t* vi, const int32_t
  * Returns the number of fronts of the plan, or a negative code.  Two calls at the same poses give the same bits. */
 int sgo_marginals_selected(sgo_ctx* ctx, double* diag, int32_t npairs, const int32_t* vi, const int32_t* vj, double* cov);
 
+/* (later additions, version 107) Panels of right-hand sides through the multifrontal factor, and the innovation gate for candidate
+ * closures built on them.
+ *
+ * H X = B for nrhs right-hand sides through the multifrontal Cholesky factor.  H: the robustified Gauss-Newton Hessian at the
+ * CURRENT poses, as in sgo_marginals_selected (the call assembles and factorises there itself).  B, X: [nrhs][n][3], every
+ * right-hand side contiguous, hessian order (sgo_free_ids), as sgo_solve_rhs's b and x.  X may alias B.
+ * Forward and backward substitution run for 16 right-hand sides at a time on the fp64 matrix cores; long requests are processed
+ * in chunks of 256.  A right-hand side's solution does not depend on nrhs or on which other columns share its panel, and two calls
+ * at the same poses give the same bits.  The plan is sgo_marginals_selected's (the resident multifrontal one, or one analysed once
+ * per set-up); sgo_optimize_gn keeps its path and a later call has the chi2 history and the poses, bit for bit, of a context that
+ * never made this call.  SGO_ENOTHING with the analysis' reason in sgo_last_error when the analysis refuses the graph: use
+ * sgo_solve_rhs then.
+ * SGO_EINVAL, with nothing on the device changed and X untouched: nrhs < 0 or a null buffer, a non-finite entry of B, an active
+ * overlay, a multi-GPU context (sgo_debug_set_shard's emulation included).  SGO_EINVAL with X untouched when the factorisation is
+ * not positive definite; the next sgo_optimize_gn is unaffected.
+ * Returns the number of fronts of the plan (0 for nrhs == 0 or a graph without a free pose), or a negative code. */
+int sgo_factor_solve(sgo_ctx* ctx, int32_t nrhs, const double* B, double* X);
+
+/* The innovation gate: is a candidate closure compatible with the current estimate AND its uncertainty, before it is inserted?
+ * For candidate t -- an EdgeSE2 between vertices ci[t] and cj[t] with measurement meas[t][3] and information info[t][6] (upper
+ * triangle by rows, as sgo_set_graph_se2's) that is NOT part of the graph --: e = its error at the current poses, A, B = its
+ * Jacobians (EdgeSE2::linearizeOplus),
+ *   cov_pred[t][9] = P = 1/2 (Q + Q^T),  Q = [A B] Sigma_{(i,j),(i,j)} [A B]^T   (a fixed endpoint drops out; both fixed: 0)
+ *   d2[t] = e^T (Omega^-1 + P)^-1 e,   pass[t] = d2[t] <= chi2_max
+ * with Sigma = H^-1 of sgo_marginals_selected's H.  No block of Sigma is formed: Q = R^T H^-1 R with A^T and B^T at the rows of the
+ * two poses, three right-hand sides per candidate through sgo_factor_solve's substitution (the pair need not share a front, which
+ * sgo_marginals_selected requires).  When the multifrontal analysis refuses the graph the same right-hand sides go through the
+ * PCG machinery of sgo_solve_rhs under sgo_marginals' rules (cold, pcg_tol relative to each right-hand side's own norm, the floor
+ * rule, one refresh of the coarse operators per call; a column that neither converges nor stands at the floor fails the call:
+ * SGO_EINVAL, candidate and residual named, outputs untouched): the call answers on every single-GPU graph.
+ * Returns how many pass, or a negative code.  The graph, the poses and every resident structure stay as they are; a candidate
+ * listed twice is answered twice; two calls at the same poses give the same bits.
+ * SGO_EINVAL, with nothing on the device changed and no output written: n < 0 or a null ci, cj, meas or info, a non-finite entry of
+ * meas or info, chi2_max not finite, a vertex id outside [0, V), a vertex without an edge, ci[t] == cj[t], an information matrix
+ * that is not symmetric positive definite (leading minors), an active overlay, a multi-GPU context.  SGO_EINVAL with the outputs
+ * untouched when the Hessian is not positive definite; the next sgo_optimize_gn is unaffected. */
+int sgo_candidate_gate(sgo_ctx* ctx, int32_t n, const int32_t* ci, const int32_t* cj, const double* meas, const double* info,
+                       double chi2_max, double* d2 /*[n], may be NULL*/, double* cov_pred /*[n][9], may be NULL*/,
+                       uint8_t* pass /*[n], may be NULL*/);
+
 /* ---- profiling (opts.profile = 1) ---------------------------------------------------------- */
 /* Per-kernel totals accumulated since the last sgo_profile_reset: for kernel slot k,
  * name (static string), launches, total milliseconds (HIP events on the ctx stream), and the
@@ -611,7 +651,10 @@ int sgo_debug_overlay_apply(sgo_ctx* ctx, const double* x, double* y, double* do
  *                own layout (same off and ld, lower triangle, row m unused); 0 bytes before the first such call.  After
  *                sgo_marginals_selected the other arrays describe the factor at the current poses (ELEM, ARENA, INVD, YINV, FLAGS
  *                are rewritten by its factor phase) and X is unchanged; on a graph that is not on the multifrontal path the hook
- *                then reads the plan that call analysed for itself. */
+ *                then reads the plan that call analysed for itself.
+ *   FS_Y, FS_X   double[columns][3 n] by elimination position: the last chunk of the last sgo_factor_solve / sgo_candidate_gate after
+ *                the forward pass (L Y = B) and after the backward pass (L^T X = Y); 0 bytes before the first such call (and after
+ *                a call that went through the PCG).  Those calls rewrite the factor's arrays as SEL's note says, X is unchanged. */
 #define SGO_MF_INFO 0
 #define SGO_MF_FRONTS 1
 #define SGO_MF_LEVEL_PTR 2
@@ -628,6 +671,8 @@ int sgo_debug_overlay_apply(sgo_ctx* ctx, const double* x, double* y, double* do
 #define SGO_MF_YINV 13
 #define SGO_MF_FLAGS 14
 #define SGO_MF_SEL 15
+#define SGO_MF_FS_Y 16
+#define SGO_MF_FS_X 17
 int64_t sgo_debug_mfront_array(sgo_ctx* ctx, int32_t what, void* out, int64_t cap_bytes);
 int64_t sgo_mfront_plan_array(int32_t V, const double* poses, const uint8_t* fixed, int32_t E, const int32_t* ei, const int32_t* ej,
                               int32_t leaf, double max_crit_mflop, int32_t what, void* out, int64_t cap_bytes);

@@ -13,7 +13,13 @@ nine warm calls --, beside it one Gauss-Newton iteration of the same graph (the 
 time per vertex, from the 8- and 64-vertex figures), and from a second, profiled context the new kernels' slots: milliseconds per
 call and the median single launch.
 
-usage: python scripts/marginals_timing.py [--selected] [C1i C1 C3s C2 C4]   -> one JSON line per config"""
+--candidates (NOTES.md section 36): sgo_candidate_gate for 1, 5, 16, 64 and 256 candidate closures -- revisits of the true
+trajectory that are not edges of the graph, measured with noise, at the estimates of optimize(8); first call and median of nine warm
+calls --, beside it, in the same session, the only other way to the same numbers: sgo_marginals for the candidates' Sigma_ii,
+Sigma_jj and Sigma_ij (six solves per candidate), one Gauss-Newton iteration of the same graph, and from a second, profiled context
+the four kernels' slots for the 5- and the 256-candidate call.
+
+usage: python scripts/marginals_timing.py [--selected | --candidates] [C1i C1 C3s C2 C4]   -> one JSON line per config"""
 import json
 import os
 import sys
@@ -105,9 +111,64 @@ def run_selected(name):
                                  median_launch_us=prof[k].get("median_us")) for k in SLOTS if k in prof})
 
 
+FS_SLOTS = (SLOTS[0], "k_fs_rhs", "k_fs_forward", "k_fs_backward", "k_fs_gate")
+COUNTS = (1, 5, 16, 64, 256)
+
+
+def _closure_candidates(g, k, seed=9):
+    rng = np.random.default_rng(seed)
+    truth = g.truth if g.truth is not None else g.poses
+    ci, cj, _ = synth._closure_candidates(truth, 100000, 2.0, 10)
+    own = set(zip(g.ei.tolist(), g.ej.tolist())) | set(zip(g.ej.tolist(), g.ei.tolist()))
+    keep = np.array([(a, b) not in own and not (g.fixed[a] and g.fixed[b]) for a, b in zip(ci.tolist(), cj.tolist())])
+    ci, cj = ci[keep], cj[keep]
+    pick = rng.choice(ci.size, size=k, replace=ci.size < k)
+    ci, cj = ci[pick].astype(np.int32), cj[pick].astype(np.int32)
+    sig = np.array([0.05, 0.05, 0.02])
+    meas = synth._rel(truth[ci], truth[cj]) + rng.standard_normal((k, 3)) * sig
+    meas[:, 2] = synth._wrap(meas[:, 2])
+    info = np.tile(np.array([1 / sig[0]**2, 0, 0, 1 / sig[1]**2, 0, 1 / sig[2]**2]), (k, 1))
+    return ci, cj, meas, info
+
+
+def run_candidates(name):
+    g = synth.config(name)
+    ci, cj, meas, info = _closure_candidates(g, max(COUNTS))
+    gate = lambda opt, k: opt.candidate_gate(ci[:k], cj[:k], meas[:k], info[:k], 11.345)
+    with capi.Optimizer(0) as opt:
+        opt.set_graph(*g.arrays())
+        path = opt.solver_description().split(":")[0]
+        done, st = opt.optimize(8)
+        t0 = time.perf_counter()
+        gate(opt, 1)
+        first = 1e3 * (time.perf_counter() - t0)
+        warm = {k: _warm(lambda k=k: gate(opt, k), 9) for k in COUNTS}
+        npass = gate(opt, max(COUNTS))[0]
+        opt.marginals(ci[:1], ci[:1])      # (the first call builds the PCG structures of a graph on a factorisation path)
+        old = {k: _warm(lambda k=k: opt.marginals(np.r_[ci[:k], cj[:k], ci[:k]], np.r_[ci[:k], cj[:k], cj[:k]]), 3) for k in COUNTS[:3]}
+    kernels = {}
+    with capi.Optimizer(0, profile=1) as opt:
+        opt.set_graph(*g.arrays())
+        opt.optimize(8)
+        for k in (5, 256):
+            gate(opt, k)
+            opt.profile_reset()
+            for _ in range(9):
+                gate(opt, k)
+            prof = opt.kernel_profile(quantiles=True)
+            kernels[k] = {s: dict(ms_per_call=prof[s]["ms"] / 9.0, launches_per_call=prof[s]["launches"] / 9.0,
+                                  median_launch_us=prof[s].get("median_us")) for s in FS_SLOTS if s in prof}
+    gn = 1e3 * float(np.median(st["seconds"][:done]))
+    return dict(config=name, V=g.V, E=g.E, path=path, gn_iteration_ms=gn, gate_first_call_ms=first, gate_warm_ms=warm,
+                marginals_route_warm_ms=old, gate_5_over_gn_iteration=warm[5] / gn, pass_of_256=npass, kernels=kernels)
+
+
 if __name__ == "__main__":
-    args = [a for a in sys.argv[1:] if a != "--selected"]
-    if "--selected" in sys.argv[1:]:
+    args = [a for a in sys.argv[1:] if a not in ("--selected", "--candidates")]
+    if "--candidates" in sys.argv[1:]:
+        for name in args or ["C1i", "C1", "C3s"]:
+            print(json.dumps(run_candidates(name)), flush=True)
+    elif "--selected" in sys.argv[1:]:
         for name in args or ["C1i", "C1", "C3s"]:
             print(json.dumps(run_selected(name)), flush=True)
     else:

@@ -33,7 +33,7 @@ SYMBOLS = [
     "sgo_debug_overlay_array", "sgo_debug_overlay_linearize", "sgo_debug_overlay_apply",
     "sgo_debug_mfront_array", "sgo_mfront_plan_array", "sgo_debug_pcg_array", "sgo_debug_pcg_run",
     "sgo_set_edge_information", "sgo_gate_edges", "sgo_set_robust_kernels", "sgo_edge_robust",
-    "sgo_solve_rhs", "sgo_marginals", "sgo_marginals_selected",
+    "sgo_solve_rhs", "sgo_marginals", "sgo_marginals_selected", "sgo_factor_solve", "sgo_candidate_gate",
 ]
 
 # SGO_KERNEL_*: the robust kernels sgo_set_robust_kernels takes, in include/sgo.h's numbering
@@ -133,6 +133,8 @@ def lib():
     L.sgo_solve_rhs.argtypes = [vp, d, d, d]
     L.sgo_marginals.argtypes = [vp, C.c_int32, i32, i32, d]
     L.sgo_marginals_selected.argtypes = [vp, d, C.c_int32, i32, i32, d]
+    L.sgo_factor_solve.argtypes = [vp, C.c_int32, d, d]
+    L.sgo_candidate_gate.argtypes = [vp, C.c_int32, i32, i32, d, d, C.c_double, d, d, u8]
     L.sgo_kernel_profile.argtypes = [vp, C.POINTER(KernelStat), C.c_int]
     L.sgo_kernel_profile_samples.argtypes = [vp, C.c_int, C.POINTER(C.c_float), C.c_int]
     L.sgo_solver_description.restype = C.c_char_p
@@ -253,7 +255,7 @@ MFRONT_ARRAYS = {"INFO": (0, np.int64, 0), "FRONTS": (1, np.int64, 14), "LEVEL_P
                  "BND": (4, np.int32, 0), "PINV": (5, np.int32, 0), "TARGETS": (6, np.int32, 4), "CONTRIB": (7, np.int32, 0),
                  "ELIM_VERTEX": (8, np.int32, 0), "ELEM": (9, np.float64, 28), "ARENA": (10, np.float64, 0), "X": (11, np.float64, 0),
                  "INVD": (12, np.float64, 0), "YINV": (13, np.float64, 16), "FLAGS": (14, np.int32, 0),
-                 "SEL": (15, np.float64, 0)}
+                 "SEL": (15, np.float64, 0), "FS_Y": (16, np.float64, 0), "FS_X": (17, np.float64, 0)}
 MFRONT_PLAN_ARRAYS = ("INFO", "FRONTS", "LEVEL_PTR", "LEVEL_FRONT", "BND", "PINV", "TARGETS", "CONTRIB", "ELIM_VERTEX")
 
 
@@ -569,6 +571,38 @@ class Optimizer:
         self.last_selected_fronts = rc
         return D, cov
 
+    def factor_solve(self, B):
+        """sgo_factor_solve: H X = B for the right-hand sides B (nrhs, n_free, 3) (or one, (n_free, 3)) through the multifrontal
+        factor at the current poses -> X of B's shape.  The number of fronts is kept in ``last_selected_fronts``; SgoError with rc=-1
+        when the multifrontal analysis refuses the graph (use solve_rhs then)."""
+        B = np.ascontiguousarray(B, dtype=np.float64)
+        nrhs = B.size // max(3 * self.n_free, 1) if self.n_free else 0
+        if nrhs * 3 * self.n_free != B.size:
+            raise ValueError("B is not a whole number of right-hand sides")
+        X = np.empty_like(B)
+        rc = lib().sgo_factor_solve(self._h, nrhs, _dp(B), _dp(X))
+        if rc < 0:
+            raise SgoError(f"sgo_factor_solve: rc={rc}: " + lib().sgo_last_error(self._h).decode())
+        self.last_selected_fronts = rc
+        return X
+
+    def candidate_gate(self, ci, cj, meas, info, chi2_max):
+        """sgo_candidate_gate: the innovation gate for candidate edges (ci[t], cj[t]) with measurements meas (n, 3) and information
+        info (n, 6) that are not part of the graph -> (npass, d2 (n,), cov_pred (n, 3, 3), passed (n,) bool):
+        d2 = e^T (Omega^-1 + J Sigma J^T)^-1 e at the current poses, passed = d2 <= chi2_max."""
+        a = np.ascontiguousarray(ci, dtype=np.int32).reshape(-1)
+        b = np.ascontiguousarray(cj, dtype=np.int32).reshape(-1)
+        z = np.ascontiguousarray(meas, dtype=np.float64).reshape(-1, 3)
+        w = np.ascontiguousarray(info, dtype=np.float64).reshape(-1, 6)
+        if not (a.size == b.size == z.shape[0] == w.shape[0]):
+            raise ValueError("inconsistent array sizes")
+        d2, P, ok = np.empty(a.size), np.empty((a.size, 3, 3)), np.zeros(a.size, dtype=np.uint8)
+        rc = lib().sgo_candidate_gate(self._h, a.size, _ip(a), _ip(b), _dp(z), _dp(w), float(chi2_max), _dp(d2), _dp(P),
+                                      ok.ctypes.data_as(C.POINTER(C.c_uint8)))
+        if rc < 0:
+            raise SgoError(f"sgo_candidate_gate: rc={rc}: " + lib().sgo_last_error(self._h).decode())
+        return rc, d2, P, ok.astype(bool)
+
     def marginals(self, vi, vj):
         """sgo_marginals: the 3x3 blocks of H^-1 (rows of vertex vi[t], columns of vertex vj[t]; vertex ids) at the current poses
         -> cov (npairs, 3, 3).  Three solves per distinct free vertex among vj; their number is kept in ``last_marginal_solves``."""
@@ -610,9 +644,11 @@ class Optimizer:
         """Text of the last error on this context (sgo_last_error)."""
         return lib().sgo_last_error(self._h).decode()
 
-    def mfront_arrays(self, names=tuple(k for k in MFRONT_ARRAYS if k != "SEL")):
+    def mfront_arrays(self, names=tuple(k for k in MFRONT_ARRAYS if k not in ("SEL", "FS_Y", "FS_X"))):
         """The resident multifrontal factorisation's arrays as the last optimize() left them (sgo_debug_mfront_array).  "SEL", the
-        selected inverse of the last marginals_selected (empty before the first), comes only when named."""
+        selected inverse of the last marginals_selected, and "FS_Y" / "FS_X", the last chunk of the last factor_solve or
+        candidate_gate after the forward / backward pass as flat [columns * 3 n] (all empty before the first such call), come
+        only when named."""
         return {k: _mfront_fetch(k, lambda what, out, cap: lib().sgo_debug_mfront_array(self._h, what, out, cap), self.last_error)
                 for k in names}
 

@@ -379,6 +379,9 @@ void sgo_destroy(sgo_ctx* c) {
   if (c->marg.d_idx) hipFree(c->marg.d_idx);
   if (c->selinv.d_out) hipFree(c->selinv.d_out);
   if (c->selinv.d_pairs) hipFree(c->selinv.d_pairs);
+  if (c->selinv.d_fs) hipFree(c->selinv.d_fs);
+  if (c->selinv.d_cand) hipFree(c->selinv.d_cand);
+  if (c->selinv.d_cidx) hipFree(c->selinv.d_cidx);
   if (c->stream) hipStreamDestroy(c->stream);
   delete c;
 }
@@ -1327,7 +1330,7 @@ int64_t sgo_debug_mfront_array(sgo_ctx* c, int32_t what, void* out, int64_t cap_
   try {
     int rc = check_graph(c);
     if (rc) return rc;
-    Mfront* mf = c->mf ? c->mf : c->selinv.mf;   // (a graph on another path: the plan sgo_marginals_selected made for itself, if any)
+    Mfront* mf = c->mf ? c->mf : c->selinv.mf;   // (a graph on another path: the plan the factor's calls made for themselves, if any)
     if (!mf) {
       c->err = "sgo_debug_mfront_array: the resident graph is not on the multifrontal path (" + c->solver_desc.substr(0, c->solver_desc.find(':')) + ")";
       return SGO_EINVAL;

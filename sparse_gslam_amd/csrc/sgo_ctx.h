@@ -5,6 +5,7 @@
 //   sgo_api.cpp        the C-ABI entry points
 //   sgo_marginals.cpp  sgo_marginals / sgo_solve_rhs: columns of H^-1 through the level-0 PCG machinery
 //   sgo_selinv.cpp     sgo_marginals_selected: every block of H^-1 inside the multifrontal factor's pattern
+//   sgo_fsolve.cpp     sgo_factor_solve / sgo_candidate_gate: panels of right-hand sides through the multifrontal factor
 // Not part of the public ABI.
 #pragma once
 #include <chrono>
@@ -270,6 +271,12 @@ struct sgo_ctx {
     double* d_out = nullptr;          // [V][9] + [npairs][9] + the failure flag
     int4* d_pairs = nullptr;          // (front, local row pose, local column pose, transpose)
     size_t out_cap = 0, pairs_cap = 0;
+    // sgo_factor_solve / sgo_candidate_gate (sgo_fsolve.cpp): one chunk's panels after the forward and after the backward pass
+    // and the fronts' update buffers; the candidates' arrays and results; their index arrays
+    double* d_fs = nullptr;
+    double* d_cand = nullptr;
+    int* d_cidx = nullptr;
+    size_t fs_cap = 0, cand_cap = 0, cidx_cap = 0;
   } selinv;
 
   // profiling
@@ -333,6 +340,37 @@ int upload(sgo_ctx* c, T** p, const std::vector<T>& v) {
   if (!v.empty()) HIP_TRY(c, hipMemcpyAsync(*p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, c->stream));
   return SGO_OK;
 }
+
+// Device scratch of the marginals' and the factor's calls that is kept across graphs: grown on demand, hipMalloc.
+template <class T>
+int grow_device(sgo_ctx* c, T** p, size_t* cap, size_t count) {
+  if (count <= *cap) return SGO_OK;
+  if (*p) hipFree(*p);   // (every call that used it has synchronised the stream)
+  *p = nullptr;
+  *cap = 0;
+  const size_t want = count + count / 4 + 64;
+  if (hipMalloc((void**)p, want * sizeof(T)) != hipSuccess) {
+    (void)hipGetLastError();
+    c->err = "out of device memory (" + std::to_string(want * sizeof(T)) + " bytes of marginal scratch)";
+    return SGO_ENOMEM;
+  }
+  *cap = want;
+  return SGO_OK;
+}
+
+// The per-call fields of a solve and the probe, put back whatever happens (as sgo_debug_pcg_run does).
+struct RestoreCall {
+  sgo_ctx* c;
+  sgo_ctx::CallState call;
+  int probe_k;
+  double probe_max;
+  explicit RestoreCall(sgo_ctx* c_) : c(c_), call(c_->call), probe_k(c_->hier.probe_k), probe_max(c_->hier.probe_max) {}
+  ~RestoreCall() {
+    c->call = call;
+    c->hier.probe_k = probe_k;
+    c->hier.probe_max = probe_max;
+  }
+};
 
 // Host staging buffer WITHOUT value-initialisation: the structure build writes every element it
 // later reads, and zero-filling ~300 MB of std::vector storage was a third of its time on C4.

@@ -377,6 +377,10 @@ enum KernelId : int {
   K_SI_GATHER,
   K_SI_PANELS,
   K_SI_RESULT,
+  K_FS_RHS,             // sgo_factor_solve / sgo_candidate_gate: the multi-right-hand-side substitution's kernels (sgo_fsolve.hip)
+  K_FS_FORWARD,
+  K_FS_BACKWARD,
+  K_FS_GATE,
   K_COUNT
 };
 extern const char* const kKernelNames[K_COUNT];

@@ -16,35 +16,6 @@ namespace {
 const char* const kOverlayRefusal =
     "single-step entry points need a full set-up: the resident graph carries an incremental overlay (call sgo_set_graph_se2)";
 
-template <class T>
-int grow(sgo_ctx* c, T** p, size_t* cap, size_t count) {
-  if (count <= *cap) return SGO_OK;
-  if (*p) hipFree(*p);   // (every call that used it has synchronised the stream)
-  *p = nullptr;
-  *cap = 0;
-  const size_t want = count + count / 4 + 64;
-  if (hipMalloc((void**)p, want * sizeof(T)) != hipSuccess) {
-    c->err = "out of device memory (" + std::to_string(want * sizeof(T)) + " bytes of marginal scratch)";
-    return SGO_ENOMEM;
-  }
-  *cap = want;
-  return SGO_OK;
-}
-
-// The per-call fields of a solve and the probe, put back whatever happens (as sgo_debug_pcg_run does).
-struct RestoreCall {
-  sgo_ctx* c;
-  sgo_ctx::CallState call;
-  int probe_k;
-  double probe_max;
-  explicit RestoreCall(sgo_ctx* c_) : c(c_), call(c_->call), probe_k(c_->hier.probe_k), probe_max(c_->hier.probe_max) {}
-  ~RestoreCall() {
-    c->call = call;
-    c->hier.probe_k = probe_k;
-    c->hier.probe_max = probe_max;
-  }
-};
-
 void inject(sgo_ctx* c, double* save, const double* src, int unit_row, int unit_k) {
   Scope sc(c, K_RHS_INJECT, (src ? 48.0 : 24.0) * c->n + (save ? 48.0 : 0.0) * c->n);
   launch_rhs_inject(c->stream, c->n, c->d_dgb, save, src, unit_row, unit_k);
@@ -189,7 +160,7 @@ int sgo_marginals(sgo_ctx* c, int32_t npairs, const int32_t* vi, const int32_t* 
       }
     std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return hj[a] < hj[b]; });
     sgo_ctx::Marginals& M = c->marg;
-    if ((rc = grow(c, &M.d_cov, &M.cov_cap, 9 * (size_t)npairs)) || (rc = grow(c, &M.d_idx, &M.idx_cap, 2 * (size_t)npairs))) return rc;
+    if ((rc = grow_device(c, &M.d_cov, &M.cov_cap, 9 * (size_t)npairs)) || (rc = grow_device(c, &M.d_idx, &M.idx_cap, 2 * (size_t)npairs))) return rc;
     int* d_pair_row = M.d_idx;
     int* d_order = M.d_idx + npairs;
     HIP_TRY(c, hipMemsetAsync(M.d_cov, 0, sizeof(double) * 9 * (size_t)npairs, c->stream));   // (a pair with a fixed vertex: the zero block)

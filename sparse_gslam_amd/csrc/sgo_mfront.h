@@ -120,7 +120,8 @@ double mfront_bytes(const Mfront* m, int E, int iters);
 // mfront_optimize's own launches up to and excluding the substitution and the update.  Clears the failure flags first; x is untouched.
 hipError_t mfront_factorize(Mfront* m, hipStream_t s, const EdgeListDev& el, const double* d_poses, double* d_hist, DirectResult* d_res);
 // Test hook (sgo_debug_mfront_array): one resident array as stored after the last mfront_optimize or selected inversion;
-// SGO_ENOTHING before the first (SGO_MF_SEL: 0 bytes before the first selected inversion).
+// SGO_ENOTHING before the first (SGO_MF_SEL: 0 bytes before the first selected inversion; SGO_MF_FS_Y / _X: before the first
+// multi-right-hand-side substitution).
 long long mfront_debug_array(const Mfront* m, hipStream_t s, int what, void* out, long long cap_bytes);
 
 }  // namespace sgo

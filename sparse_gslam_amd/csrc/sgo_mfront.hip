@@ -972,7 +972,8 @@ long long mfront_plan_array(const MfPlan& P, int E, int what, void* out, long lo
 // INFO and LEVEL_PTR have no device copy (the host sizes the launches with them): they come from the host plan.
 long long mfront_debug_array(const Mfront* m, hipStream_t s, int what, void* out, long long cap_bytes) {
   if (what == SGO_MF_SEL && !m->sel_ran) return 0;
-  if (!m->ran && !m->sel_ran) return SGO_ENOTHING;
+  if ((what == SGO_MF_FS_Y || what == SGO_MF_FS_X) && m->fs_cols == 0) return 0;
+  if (!m->ran && !m->sel_ran && m->fs_cols == 0) return SGO_ENOTHING;
   const MfPlan& P = m->plan;
   const MfDev& D = m->dev;
   if (what == SGO_MF_INFO || what == SGO_MF_LEVEL_PTR) return mfront_plan_array(P, D.E, what, out, cap_bytes);
@@ -994,6 +995,8 @@ long long mfront_debug_array(const Mfront* m, hipStream_t s, int what, void* out
     case SGO_MF_YINV: src = D.yinv; bytes = F * n3 * kMfPanel; break;
     case SGO_MF_FLAGS: src = D.flags; bytes = I * 8; break;
     case SGO_MF_SEL: src = m->sel.S; bytes = F * P.arena_doubles; break;
+    case SGO_MF_FS_Y: src = m->fs_Y; bytes = F * n3 * m->fs_cols; break;
+    case SGO_MF_FS_X: src = m->fs_X; bytes = F * n3 * m->fs_cols; break;
     default: return SGO_EINVAL;
   }
   if (bytes == 0 || cap_bytes < bytes) return bytes;

@@ -1,12 +1,14 @@
 // sgo_mfront_dev.h -- what the multifrontal path's two device sources share: the device image of the plan and the resident
-// factorisation (sgo_mfront.hip makes and fills it; sgo_selinv.hip reads the factor for the selected inversion) and the opaque
-// Mfront behind sgo_mfront.h.  Not for the host-only sources.
+// factorisation (sgo_mfront.hip makes and fills it; sgo_selinv.hip reads the factor for the selected inversion, sgo_fsolve.hip for
+// the multi-right-hand-side substitution) and the opaque Mfront behind sgo_mfront.h.  Not for the host-only sources.
 #pragma once
 #include <vector>
 
 #include <hip/hip_runtime.h>
 
 #include "sgo_mfront.h"
+
+struct sgo_ctx;
 
 namespace sgo {
 
@@ -56,6 +58,27 @@ struct MfSelDev {
   const int* pos_front = nullptr; // [n] elimination position -> the front that owns it
 };
 
+// The multi-right-hand-side substitution's share (sgo_fsolve.hip, sgo_fsolve.cpp): made by the first sgo_factor_solve /
+// sgo_candidate_gate on the graph, out of the same per-graph arena.
+struct MfFsDev {
+  const int* uoff = nullptr;      // [nfront] first row of front f's boundary rows in a panel's update buffer [U3][16]
+  const int* pos_h = nullptr;     // [n] elimination position -> hessian index
+  int U3 = 0;                     // boundary scalar rows of all fronts
+};
+// The candidates of one sgo_candidate_gate call on the device (n: their number = the component stride of zinv / info)
+constexpr int kFsRec = 13;        // per-candidate record: e (3), A00 A01 A02 A10 A11 A12, B00 B01 B10 B11
+constexpr int kFsOut = 11;        // per-candidate result: d2, P (9), the decision
+constexpr int kFsChunkPanels = 16;   // panels of 16 columns per pass over the factor (bounds the scratch: 2 x 256 x 3 n doubles + updates)
+struct FsCandDev {
+  int n = 0;
+  const int* vi = nullptr;
+  const int* vj = nullptr;
+  const int* row = nullptr;       // [n][2] the pose's place in a right-hand side (elimination position; hessian index on the PCG route), -1: fixed
+  const double* zinv = nullptr;   // [3][n]
+  const double* info = nullptr;   // [6][n]
+  double* rec = nullptr;          // [n][kFsRec]
+};
+
 struct Mfront {
   MfPlan plan;
   MfrontInfo info;
@@ -72,6 +95,11 @@ struct Mfront {
   bool sel_ran = false;              // a selected inversion has filled sel.S (and mfront_factorize the factor's arrays)
   std::vector<int> gtile_ptr;        // k_si_gather's tiles of level h: [gtile_ptr[h], gtile_ptr[h + 1])
   std::vector<int> pos_front;        // host copy of sel.pos_front
+  // multi-right-hand-side substitution
+  MfFsDev fs;
+  bool fs_ready = false;             // fs's arrays and sel.cmap / sel.cmap_off exist
+  const double *fs_Y = nullptr, *fs_X = nullptr;   // the last call's last chunk after the forward / backward pass (the context's scratch)
+  int fs_cols = 0;                   // its columns (0: no call yet)
 };
 
 // ---- kernels of the selected inversion (sgo_selinv.hip), one launch each; the host driver is sgo_selinv.cpp ----
@@ -81,5 +109,21 @@ void launch_si_panels(hipStream_t s, const MfDev& M, const MfSelDev& Z, int lvl0
 // (front, local row pose, local column pose, transpose), front < 0: the zero block.  The caller has zeroed out.
 void launch_si_result(hipStream_t s, const MfDev& M, const MfSelDev& Z, int V, int npairs, const int4* pairs, double* out);
 bool si_prepare_device();   // the panel kernel's dynamic LDS; false: the device does not grant it
+
+
+// ---- what the calls that work through the factor share (sgo_selinv.cpp) ----
+// The plan: the resident one, or one analysed for these calls (once per set-up; a refusal is cached too: SGO_ENOTHING, the reason
+// in the context's error text, which names `who` and points to `instead`).
+int selinv_plan(sgo_ctx* c, Mfront** out, const char* who, const char* instead);
+int mfront_maps_prepare(sgo_ctx* c, Mfront* m);   // sel.cmap / sel.cmap_off on the device, once per plan
+
+// ---- kernels of the multi-right-hand-side substitution (sgo_fsolve.hip), one launch each; the host driver is sgo_fsolve.cpp ----
+void launch_fs_rhs_columns(hipStream_t s, int ncols, int n3, const double* src, const int* pos_h, double* panel);
+void launch_fs_rhs_candidates(hipStream_t s, const FsCandDev& C, int t0, int t1, const double* poses, int n3, double* panel);   // panel: zeroed
+void launch_fs_forward(hipStream_t s, const MfDev& M, const MfSelDev& Z, const MfFsDev& Fs, int lvl0, int count, int panels, size_t lds, double* Y,
+                       double* U, int n3);
+void launch_fs_backward(hipStream_t s, const MfDev& M, int lvl0, int count, int panels, size_t lds, const double* Y, double* X, int n3);
+void launch_fs_gate(hipStream_t s, const FsCandDev& C, int t0, int t1, const double* W, int n3, double chi2_max, const int* flags, double* out);
+bool fs_prepare_device();   // the two substitution kernels' dynamic LDS
 
 }  // namespace sgo

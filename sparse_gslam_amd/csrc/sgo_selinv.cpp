@@ -14,26 +14,12 @@
 
 using namespace sgo;
 
-namespace {
+namespace sgo {
 
-template <class T>
-int grow(sgo_ctx* c, T** p, size_t* cap, size_t count) {
-  if (count <= *cap) return SGO_OK;
-  if (*p) hipFree(*p);   // (every call that used it has synchronised the stream)
-  *p = nullptr;
-  *cap = 0;
-  const size_t want = count + count / 4 + 64;
-  if (hipMalloc((void**)p, want * sizeof(T)) != hipSuccess) {
-    (void)hipGetLastError();
-    c->err = "out of device memory (" + std::to_string(want * sizeof(T)) + " bytes of marginal scratch)";
-    return SGO_ENOMEM;
-  }
-  *cap = want;
-  return SGO_OK;
-}
-
-// The plan the call inverts through: the resident one, or one analysed for this purpose (once per set-up; a refusal is cached too).
-int selinv_plan(sgo_ctx* c, Mfront** out) {
+// The plan the factor's calls work through (sgo_marginals_selected, sgo_factor_solve, sgo_candidate_gate): the resident one, or one
+// analysed for this purpose (once per set-up; a refusal is cached too).  who / instead: the entry point and what its caller is
+// pointed to, for the refusal's text.
+int selinv_plan(sgo_ctx* c, Mfront** out, const char* who, const char* instead) {
   if (c->mf) {
     *out = c->mf;
     return SGO_OK;
@@ -62,28 +48,53 @@ int selinv_plan(sgo_ctx* c, Mfront** out) {
     Z.tried = true;
   }
   if (!Z.mf) {
-    c->err = "sgo_marginals_selected: the multifrontal analysis refuses this graph (" + Z.why + "): use sgo_marginals";
+    c->err = std::string(who) + ": the multifrontal analysis refuses this graph (" + Z.why + "): use " + instead;
     return SGO_ENOTHING;
   }
   *out = Z.mf;
   return SGO_OK;
 }
 
+// The extend-add maps in the child -> parent direction on the device (sel.cmap, sel.cmap_off), once per plan: the selected
+// inversion gathers through them, the multi-right-hand-side substitution adds the children's updates through them.
+int mfront_maps_prepare(sgo_ctx* c, Mfront* m) {
+  if (m->sel.cmap) return SGO_OK;
+  const MfPlan& P = m->plan;
+  const int nf = (int)P.fronts.size();
+  std::vector<int> cmap_off((size_t)nf, 0);
+  for (int f = 0; f < nf; ++f)
+    for (int k = 0; k < 2; ++k)
+      if (P.fronts[f].kid[k] >= 0) cmap_off[P.fronts[f].kid[k]] = P.fronts[f].map_off[k];
+  std::vector<int> cmap = P.cmap;
+  if (cmap.empty()) cmap.push_back(0);
+  int *d_cmap = nullptr, *d_off = nullptr;
+  int rc;
+  if ((rc = upload(c, &d_cmap, cmap)) || (rc = upload(c, &d_off, cmap_off))) return rc;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));   // (the host vectors above go out of scope)
+  m->sel.cmap = d_cmap;
+  m->sel.cmap_off = d_off;
+  return SGO_OK;
+}
+
+}  // namespace sgo
+
+namespace {
+
 // The selected inversion's own device arrays, once per plan: the second arena (zeroed once: the entries no kernel writes stay
-// zero), the extend-add maps in the child -> parent direction, the gather's tiles and the front of every elimination position.
+// zero), the extend-add maps, the gather's tiles and the front of every elimination position.
 int selinv_prepare(sgo_ctx* c, Mfront* m) {
   if (m->sel_ready) return SGO_OK;
   if (!si_prepare_device()) {
     c->err = "sgo_marginals_selected: the device does not grant the kernel's dynamic LDS";
     return SGO_EHIP;
   }
+  int rc;
+  if ((rc = mfront_maps_prepare(c, m))) return rc;
   const MfPlan& P = m->plan;
   const int nf = (int)P.fronts.size();
-  std::vector<int> cmap_off((size_t)nf, 0), pos_front((size_t)std::max(P.n, 1), 0);
+  std::vector<int> pos_front((size_t)std::max(P.n, 1), 0);
   for (int f = 0; f < nf; ++f) {
     const MfFront& F = P.fronts[f];
-    for (int k = 0; k < 2; ++k)
-      if (F.kid[k] >= 0) cmap_off[F.kid[k]] = F.map_off[k];
     for (int p = F.e0; p < F.e0 + F.own; ++p) pos_front[p] = f;
   }
   std::vector<int2> gtile;
@@ -99,21 +110,14 @@ int selinv_prepare(sgo_ctx* c, Mfront* m) {
     }
   }
   m->gtile_ptr[(size_t)P.height + 1] = (int)gtile.size();
-  int *d_cmap = nullptr, *d_off = nullptr, *d_pf = nullptr;
+  int* d_pf = nullptr;
   int2* d_gt = nullptr;
   double* d_S = nullptr;
-  int rc;
-  std::vector<int> cmap = P.cmap;
-  if (cmap.empty()) cmap.push_back(0);
   if (gtile.empty()) gtile.push_back(make_int2(0, 0));
-  if ((rc = upload(c, &d_cmap, cmap)) || (rc = upload(c, &d_off, cmap_off)) || (rc = upload(c, &d_pf, pos_front)) || (rc = upload(c, &d_gt, gtile)) ||
-      (rc = dalloc(c, &d_S, (size_t)P.arena_doubles)))
-    return rc;
+  if ((rc = upload(c, &d_pf, pos_front)) || (rc = upload(c, &d_gt, gtile)) || (rc = dalloc(c, &d_S, (size_t)P.arena_doubles))) return rc;
   HIP_TRY(c, hipMemsetAsync(d_S, 0, sizeof(double) * (size_t)std::max<long long>(P.arena_doubles, 1), c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));   // (the host vectors above go out of scope)
   m->sel.S = d_S;
-  m->sel.cmap = d_cmap;
-  m->sel.cmap_off = d_off;
   m->sel.gtile = d_gt;
   m->sel.pos_front = d_pf;
   m->pos_front = pos_front;
@@ -165,7 +169,7 @@ int sgo_marginals_selected(sgo_ctx* c, double* diag, int32_t npairs, const int32
       return 0;
     }
     Mfront* m = nullptr;
-    if ((rc = selinv_plan(c, &m))) return rc;
+    if ((rc = selinv_plan(c, &m, "sgo_marginals_selected", "sgo_marginals"))) return rc;
     const MfPlan& P = m->plan;
     // the pairs in the plan's terms: the front of the endpoint eliminated first holds the block, if any front does
     std::vector<int> pos_of((size_t)c->n, -1);   // hessian index -> elimination position
@@ -201,7 +205,7 @@ int sgo_marginals_selected(sgo_ctx* c, double* diag, int32_t npairs, const int32
     }
     sgo_ctx::SelInv& Z = c->selinv;
     const size_t nout = 9 * ((size_t)c->V + (size_t)npairs) + 1;
-    if ((rc = grow(c, &Z.d_out, &Z.out_cap, nout)) || (rc = grow(c, &Z.d_pairs, &Z.pairs_cap, (size_t)std::max(npairs, 1)))) return rc;
+    if ((rc = grow_device(c, &Z.d_out, &Z.out_cap, nout)) || (rc = grow_device(c, &Z.d_pairs, &Z.pairs_cap, (size_t)std::max(npairs, 1)))) return rc;
     HIP_TRY(c, hipMemsetAsync(Z.d_out, 0, sizeof(double) * nout, c->stream));
     if (npairs > 0) HIP_TRY(c, hipMemcpyAsync(Z.d_pairs, pairs.data(), sizeof(int4) * (size_t)npairs, hipMemcpyHostToDevice, c->stream));
 
