@@ -696,6 +696,45 @@ class SparseBlockMatrix {
   std::map<std::pair<int, int>, std::unique_ptr<MatrixType>> _blocks;
 };
 
+// ------------------------------------------------------------------------------- actions
+// g2o/core/hyper_graph_action.h and sparse_optimizer_terminate_action.h.  The device path does not come back to the host between
+// its iterations, so the one post-iteration action there is is the one whose decision the device can take itself:
+// SparseOptimizerTerminateAction, evaluated inside sgo_optimize_gn_until (include/sgo.h says the rule); SparseOptimizer refuses any
+// other class at addPostIterationAction.
+class HyperGraphAction {
+ public:
+  class Parameters {
+   public:
+    virtual ~Parameters() {}
+  };
+  class ParametersIteration : public Parameters {
+   public:
+    explicit ParametersIteration(int iter) : iteration(iter) {}
+    int iteration;
+  };
+  virtual ~HyperGraphAction() {}
+  virtual HyperGraphAction* operator()(const HyperGraph*, Parameters* = nullptr) { return nullptr; }
+};
+
+// Stops optimize() once the relative gain of the robust chi2 between two iterations is in [0, gainThreshold), and after the
+// iteration with index maxIterations at the latest; the first iteration only records its chi2, so two always run.
+class SparseOptimizerTerminateAction : public HyperGraphAction {
+ public:
+  double gainThreshold() const { return _gainThreshold; }
+  void setGainThreshold(double g) { _gainThreshold = g; }
+  int maxIterations() const { return _maxIterations; }
+  void setMaxIterations(int m) { _maxIterations = m; }
+  // how many iterations optimize(n) may run at most: upstream stops AFTER iteration index maxIterations
+  int iterationCap(int n) const {
+    const int cap = _maxIterations < 0 ? 1 : (_maxIterations < std::numeric_limits<int>::max() ? _maxIterations + 1 : _maxIterations);
+    return std::min(n, cap);
+  }
+
+ private:
+  double _gainThreshold = 1e-6;
+  int _maxIterations = std::numeric_limits<int>::max();
+};
+
 // ------------------------------------------------------------------------------- optimiser
 class SparseOptimizer : public OptimizableGraph {
  public:
@@ -711,6 +750,28 @@ class SparseOptimizer : public OptimizableGraph {
   void setVerbose(bool v) { _verbose = v; }
   bool verbose() const { return _verbose; }
   void setComputeBatchStatistics(bool) {}
+
+  // Post-iteration actions: a SparseOptimizerTerminateAction (one at a time; caller-owned, as upstream) makes optimize() end at
+  // convergence -- on the device through sgo_optimize_gn_until, on the host solver by the same rule after every iteration.  Any
+  // other class is refused: false and one line on std::cerr.
+  bool addPostIterationAction(HyperGraphAction* a) {
+    if (!a || typeid(*a) != typeid(SparseOptimizerTerminateAction)) {
+      std::cerr << "SparseOptimizer::addPostIterationAction: only SparseOptimizerTerminateAction is supported (the device path does not return to the host between iterations); refused" << std::endl;
+      return false;
+    }
+    if (_terminateAction == a) return false;   // (upstream: already in the set)
+    if (_terminateAction) {
+      std::cerr << "SparseOptimizer::addPostIterationAction: a SparseOptimizerTerminateAction is registered already; refused" << std::endl;
+      return false;
+    }
+    _terminateAction = static_cast<SparseOptimizerTerminateAction*>(a);
+    return true;
+  }
+  bool removePostIterationAction(HyperGraphAction* a) {
+    if (!a || a != _terminateAction) return false;
+    _terminateAction = nullptr;
+    return true;
+  }
 
   // ---- container (OptimizableGraph / HyperGraph)
   bool addVertex(HyperGraph::Vertex* v) {
@@ -863,7 +924,8 @@ class SparseOptimizer : public OptimizableGraph {
     if (!gpuEligible()) return hostOptimize(iterations, online);
     if (!uploadGraph()) return 0;
     sgo_stats* st = new sgo_stats();
-    int done = sgo_optimize_gn(_ctx, iterations, st);
+    int done = _terminateAction ? sgo_optimize_gn_until(_ctx, _terminateAction->iterationCap(iterations), _terminateAction->gainThreshold(), st, nullptr)
+                                : sgo_optimize_gn(_ctx, iterations, st);
     if (done < 0 && done != SGO_ENOTHING) {
       std::cerr << "SparseOptimizer::optimize: " << sgo_last_error(_ctx) << std::endl;
       done = 0;
@@ -1184,6 +1246,17 @@ class SparseOptimizer : public OptimizableGraph {
     std::vector<double> H((size_t)n * n), b(n), x(n);
     int cjIterations = 0;
     bool ok = true, failed = false;
+    // a registered terminate action: sgo_optimize_gn_until's rule after every iteration (the first one only records its chi2)
+    if (_terminateAction) iterations = _terminateAction->iterationCap(iterations);
+    double lastChi = 0.0;
+    auto converged = [&]() {
+      if (!_terminateAction) return false;
+      computeActiveErrors();
+      const double chi = activeRobustChi2();
+      const bool stop = cjIterations >= 2 && sgo_gain_stop(lastChi, chi, _terminateAction->gainThreshold()) != 0;
+      lastChi = chi;
+      return stop;
+    };
     for (int it = 0; it < iterations && ok; ++it) {
       computeActiveErrors();
       double currentChi = activeRobustChi2();
@@ -1196,6 +1269,7 @@ class SparseOptimizer : public OptimizableGraph {
         }
         hostUpdate(x);
         ++cjIterations;
+        if (converged()) break;
         continue;
       }
       if (it == 0) {  // computeLambdaInit: tau * max diagonal, tau = 1e-5
@@ -1239,6 +1313,7 @@ class SparseOptimizer : public OptimizableGraph {
       ++cjIterations;
       _lmTrace.push_back({_lmLambda, currentChi, qmax});
       if (qmax == 10 || rho == 0 || !std::isfinite(_lmLambda)) ok = false;  // Terminate
+      if (ok && converged()) break;
     }
     if (failed) return 0;
     return cjIterations;
@@ -1428,6 +1503,7 @@ class SparseOptimizer : public OptimizableGraph {
     int nDead = 0;
   } _m;
   std::unique_ptr<sgo_stats> _lastStats;
+  SparseOptimizerTerminateAction* _terminateAction = nullptr;
   std::deque<VertexSE2> _loadedVertices;   // objects created by load(): the optimiser's own
   std::deque<EdgeSE2> _loadedEdges;
 };

@@ -212,7 +212,36 @@ int sgo_get_poses(sgo_ctx* ctx, double* poses);
  * `out` may be NULL. */
 int sgo_optimize_gn(sgo_ctx* ctx, int32_t iters, sgo_stats* out);
 
-/* Replaces: computeActiveErrors(); activeChi2(); activeRobustChi2() (slc.cpp:288, drone.cpp:162-165). */
+/* (later additions, version 107) Gauss-Newton that ends at convergence: g2o's SparseOptimizerTerminateAction as one call
+ * (DESIGN.md section 5h).
+ *
+ * The gain rule, a pure function (no context, no GPU): with last_robust_chi2 and robust_chi2 the robust chi2 at the start of the
+ * previous and of the current iteration,
+ *     gain = (last_robust_chi2 - robust_chi2) / robust_chi2;   returns 1 iff gain >= 0 && gain < gain_tol, else 0.
+ * A negative gain does not stop (DCS makes chi2 non-monotone), gain_tol <= 0 never stops, and robust_chi2 == 0 or a non-finite
+ * argument gives NaN or inf, for which a comparison is false: 0. */
+int sgo_gain_stop(double last_robust_chi2, double robust_chi2, double gain_tol);
+
+/* sgo_optimize_gn(ctx, max_iters, out) that ends early: before iteration `it` with 2 <= it < max_iters the call stops iff
+ * sgo_gain_stop(robust_chi2[it - 1], robust_chi2[it], gain_tol).  At least two updates always run (g2o's action stores chi2 only
+ * after the first).  A stop before iteration `it` ends the call with `it` updates applied: out->iters_done = it, chi2[it] and
+ * robust_chi2[it] are the final values, only the entries of applied iterations are filled, out->iters_requested = max_iters.
+ * Every iteration before the stop is the one sgo_optimize_gn(max_iters) runs: the histories agree bit for bit up to the stop.  On
+ * the factorisation paths the rule is applied on the device (no host round trip inside the call), and the poses and the factor are
+ * bit for bit those of sgo_optimize_gn(it); on the PCG path, an active incremental overlay included, the host reads chi2 once per
+ * iteration and starts no solve for the stopped iteration.
+ * *stop_reason (may be NULL; written when the return value is >= 0) is one of SGO_STOP_*: max_iters updates applied, the gain rule,
+ * or a failed linear solve (return value 0, the step not applied, as sgo_optimize_gn).
+ * Return values and argument checks are sgo_optimize_gn's; SGO_EINVAL in addition, with the poses untouched, for a gain_tol that
+ * is not finite and for a multi-GPU context (sgo_debug_set_shard's emulation included). */
+#define SGO_STOP_MAX_ITERS 0
+#define SGO_STOP_GAIN 1
+#define SGO_STOP_FAILED 2
+int sgo_optimize_gn_until(sgo_ctx* ctx, int32_t max_iters, double gain_tol, sgo_stats* out, int32_t* stop_reason);
+
+/* Replaces: computeActiveErrors(); activeChi2(); activeRobustChi2() (slc.cpp:288, drone.cpp:162-165).
+ * Called right after sgo_optimize_gn or sgo_optimize_gn_until it returns the final entries of that call's history bit for bit
+ * (on a direct_ldlt context the sums come from the single-launch kernel's own closing pass). */
 int sgo_chi2(sgo_ctx* ctx, double* plain, double* robust);
 /* Replaces: EdgeSE2::computeError(); chi2() per edge (log_runner.cpp:183-184, the 11.345 gate).
  * e2[E] in the edge order given to sgo_set_graph_se2. */
@@ -642,6 +671,9 @@ int sgo_debug_overlay_apply(sgo_ctx* ctx, const double* x, double* y, double* do
  *                tgt0 .. tgt1; CONTRIB int32: edge << 2 | part (0: D_ii and b_i, 1: D_jj and b_j, 2: H_ij as stored, 3: its transpose)
  *   ELIM_VERTEX  int32[n]: the vertex at every elimination position
  *   ELEM         double[E][28]: D_ii (upper triangle by rows, 6), D_jj (6), H_ij (9, by rows), b_i (3), b_j (3), one pad
+ *                (after an sgo_optimize_gn_until that stopped by the gain rule: the elements at the FINAL poses -- the stopped
+ *                iteration's edge pass had run --, where sgo_optimize_gn leaves those of its last factorisation; every other array
+ *                is the plain call's)
  *   ARENA        double: every front's matrix after its factorisation: columns < own3 hold L11, L21 and (row m) the
  *                forward-substituted right-hand side; columns >= own3 the assembled boundary block and its right-hand side
  *   X            double[3 n]: the step by elimination position;  INVD double[3 n]: 1 / L[c][c];  YINV double[3 n][16]: row i of the

@@ -34,7 +34,11 @@ SYMBOLS = [
     "sgo_debug_mfront_array", "sgo_mfront_plan_array", "sgo_debug_pcg_array", "sgo_debug_pcg_run",
     "sgo_set_edge_information", "sgo_gate_edges", "sgo_set_robust_kernels", "sgo_edge_robust",
     "sgo_solve_rhs", "sgo_marginals", "sgo_marginals_selected", "sgo_factor_solve", "sgo_candidate_gate",
+    "sgo_gain_stop", "sgo_optimize_gn_until",
 ]
+
+# SGO_STOP_*: why sgo_optimize_gn_until ended
+STOP_MAX_ITERS, STOP_GAIN, STOP_FAILED = 0, 1, 2
 
 # SGO_KERNEL_*: the robust kernels sgo_set_robust_kernels takes, in include/sgo.h's numbering
 KERNEL_NONE, KERNEL_DCS, KERNEL_HUBER, KERNEL_PSEUDO_HUBER, KERNEL_CAUCHY = 0, 1, 2, 3, 4
@@ -43,6 +47,11 @@ KERNEL_GEMAN_MCCLURE, KERNEL_WELSCH, KERNEL_FAIR, KERNEL_TUKEY, KERNEL_SATURATED
 
 class SgoError(RuntimeError):
     pass
+
+
+def gain_stop(last_robust_chi2: float, robust_chi2: float, gain_tol: float) -> bool:
+    """sgo_gain_stop: the rule sgo_optimize_gn_until stops by, as the library computes it (no context, no GPU)."""
+    return bool(lib().sgo_gain_stop(last_robust_chi2, robust_chi2, gain_tol))
 
 
 class Opts(C.Structure):
@@ -118,6 +127,8 @@ def lib():
     L.sgo_set_poses.argtypes = [vp, d]
     L.sgo_get_poses.argtypes = [vp, d]
     L.sgo_optimize_gn.argtypes = [vp, C.c_int32, C.POINTER(Stats)]
+    L.sgo_optimize_gn_until.argtypes = [vp, C.c_int32, C.c_double, C.POINTER(Stats), i32]
+    L.sgo_gain_stop.argtypes = [C.c_double, C.c_double, C.c_double]
     L.sgo_chi2.argtypes = [vp, d, d]
     L.sgo_edge_chi2.argtypes = [vp, d]
     L.sgo_set_edge_information.argtypes = [vp, C.c_int32, i32, d]
@@ -439,6 +450,17 @@ class Optimizer:
         """optimize(iters) -> (iterations done, stats dict)."""
         st = Stats()
         rc = self._check(lib().sgo_optimize_gn(self._h, iters, C.byref(st)), "sgo_optimize_gn")
+        return rc, self._stats_dict(rc, st, iters)
+
+    def optimize_until(self, max_iters: int = 20, gain_tol: float = 1e-6):
+        """sgo_optimize_gn_until: optimize(max_iters) that ends before the first iteration (from the third on) at which the relative
+        gain of the robust chi2 is in [0, gain_tol) -> (iterations done, stats dict, stop reason: one of STOP_*)."""
+        st = Stats()
+        why = C.c_int32(-1)
+        rc = self._check(lib().sgo_optimize_gn_until(self._h, max_iters, gain_tol, C.byref(st), C.byref(why)), "sgo_optimize_gn_until")
+        return rc, self._stats_dict(rc, st, max_iters), why.value
+
+    def _stats_dict(self, rc, st, iters):
         d = max(st.iters_done, 0)
         stats = dict(
             rc=rc, iters_done=st.iters_done, chi2=list(st.chi2[: d + 1]),
@@ -448,7 +470,7 @@ class Optimizer:
             seconds_solve=list(st.seconds_solve[:iters]), seconds_total=st.seconds_total,
             seconds_setup=st.seconds_setup)
         self.last_stats = stats
-        return rc, stats
+        return stats
 
     def chi2(self):
         a = C.c_double()

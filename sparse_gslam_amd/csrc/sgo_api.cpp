@@ -8,6 +8,7 @@
 #include <new>
 
 #include "sgo_ctx.h"
+#include "sgo_rules.h"
 
 using namespace sgo;
 
@@ -714,7 +715,20 @@ int sgo_chi2(sgo_ctx* c, double* plain, double* robust) {
   try {
     int rc = check_graph(c);
     if (rc) return rc;
-    if ((rc = do_chi2(c, c->d_hist, nullptr))) return rc;
+    if (c->direct && !c->ov.active) {
+      // Single-launch path: the sums are k_direct's own closing pass (a call of 0 iterations: it writes the two sums and its scratch
+      // result record, nothing else), so that they equal the final entry of the history of the call before, sgo_optimize_gn's or
+      // sgo_optimize_gn_until's, bit for bit -- as they do on the other paths, whose histories are do_chi2's.  k_chi2 forms the
+      // edge error from another sincos and adds in another order: the same sums to rounding, not to the bit.
+      Scope sc(c, K_DIRECT, direct_bytes(c->direct, c->E, 0));
+      const hipError_t he = direct_optimize(c->direct, c->stream, c->el, c->d_poses, 0, c->d_hist, c->d_dres, nullptr);
+      if (he != hipSuccess) {
+        c->err = std::string("k_direct launch: ") + hipGetErrorString(he);
+        return SGO_EHIP;
+      }
+    } else if ((rc = do_chi2(c, c->d_hist, nullptr))) {
+      return rc;
+    }
     HIP_TRY(c, hipMemcpyAsync(c->h_hist, c->d_hist, 2 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (plain) *plain = c->h_hist[0];
@@ -1194,6 +1208,29 @@ int sgo_debug_pcg_run(sgo_ctx* c, int32_t maxit, const double* x_prev, double bb
 int sgo_optimize_gn(sgo_ctx* c, int32_t iters, sgo_stats* out) {
   try {
     return optimize_gn(c, iters, out);
+  } SGO_CATCH(c)
+}
+
+int sgo_gain_stop(double last_robust_chi2, double robust_chi2, double gain_tol) {
+  return rules::gain_stop(last_robust_chi2, robust_chi2, gain_tol) ? 1 : 0;
+}
+
+int sgo_optimize_gn_until(sgo_ctx* c, int32_t max_iters, double gain_tol, sgo_stats* out, int32_t* stop_reason) {
+  try {
+    const int rc = check_graph(c);
+    if (rc) return rc;
+    if (!std::isfinite(gain_tol)) {
+      c->err = "sgo_optimize_gn_until: gain_tol is not finite";
+      return SGO_EINVAL;
+    }
+    if (multi_gpu_context(c)) {
+      c->err = "sgo_optimize_gn_until: not available in a multi-GPU context (call sgo_optimize_gn)";
+      return SGO_EINVAL;
+    }
+    UntilGain until{gain_tol, SGO_STOP_MAX_ITERS};
+    const int done = optimize_gn(c, max_iters, out, &until);
+    if (stop_reason && done >= 0) *stop_reason = until.stop_reason;
+    return done;
   } SGO_CATCH(c)
 }
 

@@ -506,7 +506,12 @@ int ensure_amg(sgo_ctx* c);
 int vec_to_device(sgo_ctx* c, const double* host_asc, double* dev);
 int vec_from_device(sgo_ctx* c, const double* dev, double* host_asc);
 int check_graph(sgo_ctx* c);
-int optimize_gn(sgo_ctx* c, int32_t iters, sgo_stats* out);   // sgo_optimize_gn behind its argument checks
+// sgo_optimize_gn_until's mode of optimize_gn: the tolerance of rules::gain_stop in, why the call ended (SGO_STOP_*) out
+struct UntilGain {
+  double gain_tol;
+  int32_t stop_reason;
+};
+int optimize_gn(sgo_ctx* c, int32_t iters, sgo_stats* out, UntilGain* until = nullptr);   // sgo_optimize_gn behind its argument checks
 double debug_spmv0_us(sgo_ctx* c, int mode, int variant, int reps);
 
 }  // namespace sgo

@@ -48,8 +48,10 @@ const DirectInfo& direct_info(const Direct* d);
 
 // iters x { chi2, linearise, factorise, solve, update } + the final chi2 on the stream; d_hist[2 (iters + 1)] gets
 // (chi2, robust chi2) at the start of every iteration and at the end; d_res is a device DirectResult.
+// until != nullptr (sgo_optimize_gn_until): the kernel ends the call before the first iteration at which rules::gain_stop holds for
+// *until and leaves d_res, the history and the poses as a call of that many iterations does.
 hipError_t direct_optimize(Direct* d, hipStream_t s, const EdgeListDev& el, double* d_poses, int iters, double* d_hist,
-                           DirectResult* d_res);
+                           DirectResult* d_res, const double* until = nullptr);
 // algorithmic bytes of one call (profile table)
 double direct_bytes(const Direct* d, int E, int iters);
 

@@ -33,6 +33,7 @@
 
 #include "sgo_device.h"
 #include "sgo_direct.h"
+#include "sgo_rules.h"
 #include "sgo_internal.h"
 
 namespace sgo {
@@ -302,9 +303,11 @@ constexpr int kPF = 1;   // forward tasks per thread whose records are fetched o
 
 // XG: the right-hand side / solution vector lives in global memory (graphs whose 24 n bytes do not fit the LDS
 // next to the separator block) instead of LDS.  KINDS: the edges carry robust kernels other than DCS (sgo_device.h).
-template <bool XG, bool KINDS>
+// UNTIL: sgo_optimize_gn_until -- the call ends before the first iteration at which rules::gain_stop holds for gain_tol (thread 0
+// decides from the two sums it holds, the workgroup leaves the loop together); the plain instantiations never read gain_tol.
+template <bool XG, bool KINDS, bool UNTIL>
 __global__ __launch_bounds__(kDT) void k_direct(DirectDev D, EdgeListDev el, double* __restrict__ poses, int iters,
-                                                double* __restrict__ hist, DirectResult* __restrict__ res) {
+                                                double* __restrict__ hist, DirectResult* __restrict__ res, double gain_tol) {
   extern __shared__ double lds[];
   double* xb;                             // [3 n] right-hand side, then the solution, by elimination position
   double* Sd;                             // [tri] packed lower triangle of the separator block
@@ -321,6 +324,7 @@ __global__ __launch_bounds__(kDT) void k_direct(DirectDev D, EdgeListDev el, dou
   int* lmeta = reinterpret_cast<int*>(red + 32);   // [2 (NL + 1)]
   unsigned short* dpl = reinterpret_cast<unsigned short*>(lmeta + 2 * (D.NL + 1));   // [ns (ns + 1) / 2] dense block pairs
   __shared__ int fail_flag;
+  __shared__ int stop_flag;   // (UNTIL) thread 0's decision of this iteration
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int n = D.n, nI = D.nI, ns = D.ns, NL = D.NL;
   const size_t E = (size_t)D.E;
@@ -422,8 +426,19 @@ __global__ __launch_bounds__(kDT) void k_direct(DirectDev D, EdgeListDev el, dou
       }
       hist[2 * it] = a;
       hist[2 * it + 1] = b;
+      if constexpr (UNTIL) stop_flag = rules::gain_stop_applies(it, iters) && rules::gain_stop(hist[2 * it - 1], b, gain_tol);
     }
     if (!jac) break;
+    if constexpr (UNTIL) {
+      // The stopped iteration has written its edge terms only: scratch every iteration (and every call) rewrites before it reads.
+      // What the host reads is what the call of `it` iterations leaves: done = it, hist[2 it] the final sums, stamp[2 it] the start
+      // of the last pass and stamp[2 it + 1] the end of the call, phase[0] the start of the last iteration that ran.
+      __syncthreads();
+      if (stop_flag) {
+        if (tid == 0) res->phase[0] = res->stamp[2 * it - 2];
+        break;
+      }
+    }
     if (tid == 0) res->phase[1] = (unsigned long long)wall_clock64();
     // ---- assembly: diagonal blocks and right-hand sides (sums over a pose's incident edges), multi-edge pairs
     for (int f = tq; f < n; f += kDT) {
@@ -699,7 +714,7 @@ __global__ __launch_bounds__(kDT) void k_direct(DirectDev D, EdgeListDev el, dou
     res->done = done;
     res->cycles = __builtin_amdgcn_s_memtime() - clk0;
     res->fail = (fail & 1) ? 1 : (fail ? 2 : 0);
-    res->stamp[fail ? 2 * done + 2 : 2 * iters + 1] = (unsigned long long)wall_clock64();   // end of the call
+    res->stamp[fail ? 2 * done + 2 : 2 * (UNTIL ? done : iters) + 1] = (unsigned long long)wall_clock64();   // end of the call
   }
 }
 
@@ -1087,9 +1102,11 @@ Direct* direct_create(hipStream_t s, DevArena* arena, int V, int n, const int* f
   const bool attr_set_already = (attr_devices.load() & dev_bit) != 0;
   bool attr_set = attr_set_already;
   if (e == hipSuccess && !attr_set) {
-    const void* const variants[4] = {reinterpret_cast<const void*>(&k_direct<false, false>), reinterpret_cast<const void*>(&k_direct<true, false>),
-                                     reinterpret_cast<const void*>(&k_direct<false, true>), reinterpret_cast<const void*>(&k_direct<true, true>)};
-    for (int v = 0; v < 4 && e == hipSuccess; ++v)
+    const void* const variants[8] = {reinterpret_cast<const void*>(&k_direct<false, false, false>), reinterpret_cast<const void*>(&k_direct<true, false, false>),
+                                     reinterpret_cast<const void*>(&k_direct<false, true, false>), reinterpret_cast<const void*>(&k_direct<true, true, false>),
+                                     reinterpret_cast<const void*>(&k_direct<false, false, true>), reinterpret_cast<const void*>(&k_direct<true, false, true>),
+                                     reinterpret_cast<const void*>(&k_direct<false, true, true>), reinterpret_cast<const void*>(&k_direct<true, true, true>)};
+    for (int v = 0; v < 8 && e == hipSuccess; ++v)
       e = hipFuncSetAttribute(variants[v], hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBudget);
     attr_set = e == hipSuccess;
     if (attr_set) attr_devices.fetch_or(dev_bit);
@@ -1108,13 +1125,23 @@ Direct* direct_create(hipStream_t s, DevArena* arena, int V, int n, const int* f
   return owner.release();
 }
 
+// (until: the call ends early by rules::gain_stop with *until as its tolerance -- the UNTIL instantiations; nullptr: sgo_optimize_gn)
 hipError_t direct_optimize(Direct* d, hipStream_t s, const EdgeListDev& el, double* d_poses, int iters, double* d_hist,
-                           DirectResult* d_res) {
-  if (el.kinds) {
-    if (d->xb_global) SGO_LAUNCH((k_direct<true, true>), dim3(1), dim3(kDT), d->info.lds_bytes, s, d->dev, el, d_poses, iters, d_hist, d_res);
-    else SGO_LAUNCH((k_direct<false, true>), dim3(1), dim3(kDT), d->info.lds_bytes, s, d->dev, el, d_poses, iters, d_hist, d_res);
-  } else if (d->xb_global) SGO_LAUNCH((k_direct<true, false>), dim3(1), dim3(kDT), d->info.lds_bytes, s, d->dev, el, d_poses, iters, d_hist, d_res);
-  else SGO_LAUNCH((k_direct<false, false>), dim3(1), dim3(kDT), d->info.lds_bytes, s, d->dev, el, d_poses, iters, d_hist, d_res);
+                           DirectResult* d_res, const double* until) {
+#define SGO_DIRECT_LAUNCH(XG, KINDS, UNTIL, tol) \
+  SGO_LAUNCH((k_direct<XG, KINDS, UNTIL>), dim3(1), dim3(kDT), d->info.lds_bytes, s, d->dev, el, d_poses, iters, d_hist, d_res, tol)
+  if (until) {
+    if (el.kinds) {
+      if (d->xb_global) SGO_DIRECT_LAUNCH(true, true, true, *until);
+      else SGO_DIRECT_LAUNCH(false, true, true, *until);
+    } else if (d->xb_global) SGO_DIRECT_LAUNCH(true, false, true, *until);
+    else SGO_DIRECT_LAUNCH(false, false, true, *until);
+  } else if (el.kinds) {
+    if (d->xb_global) SGO_DIRECT_LAUNCH(true, true, false, 0.0);
+    else SGO_DIRECT_LAUNCH(false, true, false, 0.0);
+  } else if (d->xb_global) SGO_DIRECT_LAUNCH(true, false, false, 0.0);
+  else SGO_DIRECT_LAUNCH(false, false, false, 0.0);
+#undef SGO_DIRECT_LAUNCH
   return hipGetLastError();
 }
 

@@ -112,9 +112,12 @@ Mfront* mfront_create(hipStream_t s, DevArena* arena, int V, int n, const int* f
 void mfront_destroy(Mfront* m);
 const MfrontInfo& mfront_info(const Mfront* m);
 // iters x { edges + chi2, factorise (levels up), substitute (levels down), update } + the closing chi2 on the stream; outputs
-// as direct_optimize (d_hist[2 (iters + 1)], DirectResult: done / fail / fail_iter / stamps)
+// as direct_optimize (d_hist[2 (iters + 1)], DirectResult: done / fail / fail_iter / stamps).  until != nullptr
+// (sgo_optimize_gn_until): one more single-wave launch per iteration from the third on applies rules::gain_stop with *until on the
+// device; after a stop the call's remaining launches return at once, and the arena, x, invd, yinv and the flags are those of the
+// plain call of as many iterations (the elements: those at the final poses).
 hipError_t mfront_optimize(Mfront* m, hipStream_t s, const EdgeListDev& el, double* d_poses, int iters, double* d_hist,
-                           DirectResult* d_res);
+                           DirectResult* d_res, const double* until = nullptr);
 double mfront_bytes(const Mfront* m, int E, int iters);
 // The factor phase of one iteration alone, at the current poses: edges (elements, chi2 partials), then merge and panels per level --
 // mfront_optimize's own launches up to and excluding the substitution and the update.  Clears the failure flags first; x is untouched.

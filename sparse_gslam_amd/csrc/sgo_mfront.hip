@@ -25,6 +25,7 @@
 #include "sgo_internal.h"
 #include "sgo_mfront.h"
 #include "sgo_mfront_dev.h"
+#include "sgo_rules.h"
 
 namespace sgo {
 namespace {
@@ -679,6 +680,37 @@ __global__ __launch_bounds__(64) void k_mf_finish(MfDev M, int iters, int nparts
   else res->stamp[2 * iters + 1] = now;
 }
 
+// ---------------------------------------------------------------------------- sgo_optimize_gn_until
+// The value flags[0] takes when the gain rule ends the call: every later launch returns on it as on a failure's 1 or 2, and
+// k_mf_finish_until puts 0 back, so that FLAGS reads as after the plain call of as many iterations.
+constexpr int kMfStopped = 3;
+
+// One wave, between k_mf_edges and the first level's k_mf_panels of iteration `it` (2 <= it < iters): chi2 of this iteration from
+// the partial sums in mf_chi2_sum's order -- the bits the panel kernel would write --, then rules::gain_stop against the iteration
+// before.  A stop precedes every write of this iteration to the arena, x, invd and yinv; the elements are k_mf_edges' already.
+__global__ __launch_bounds__(64) void k_mf_gain_stop(MfDev M, int it, int nparts, double gain_tol, double* __restrict__ hist) {
+  if (M.flags[0]) return;
+  mf_chi2_sum(M.partials, nparts, hist, it, threadIdx.x);
+  if (threadIdx.x == 0 && rules::gain_stop(hist[2 * it - 1], hist[2 * it + 1], gain_tol)) M.flags[0] = kMfStopped;
+}
+
+// k_mf_finish after a call that may have stopped: done = the updates applied, hist[2 done] stays what k_mf_gain_stop wrote (the
+// closing sum is not redone), the call's end goes where the plain call of `done` iterations puts it, and the stop word is cleared.
+__global__ __launch_bounds__(64) void k_mf_finish_until(MfDev M, int iters, int nparts, double* __restrict__ hist, DirectResult* __restrict__ res) {
+  const int f0 = M.flags[0];
+  if (!f0) mf_chi2_sum(M.partials, nparts, hist, iters, threadIdx.x);   // the closing pass
+  if (threadIdx.x != 0) return;
+  const unsigned long long now = (unsigned long long)wall_clock64();
+  const bool failed = f0 && f0 != kMfStopped;
+  res->done = M.flags[3];
+  res->fail = failed ? f0 : 0;
+  res->fail_iter = M.flags[1];
+  res->cycles = 0;
+  if (failed) res->stamp[2 * M.flags[3] + 2] = now;
+  else res->stamp[2 * M.flags[3] + 1] = now;   // (not stopped: flags[3] == iters)
+  if (f0 == kMfStopped) M.flags[0] = 0;
+}
+
 }  // namespace
 
 const MfrontInfo& mfront_info(const Mfront* m) { return m->info; }
@@ -861,7 +893,7 @@ Mfront* mfront_create(hipStream_t s, DevArena* arena, int V, int n, const int* f
 }
 
 hipError_t mfront_optimize(Mfront* m, hipStream_t s, const EdgeListDev& el, double* d_poses, int iters, double* d_hist,
-                           DirectResult* d_res) {
+                           DirectResult* d_res, const double* until) {
   const MfPlan& P = m->plan;
   const MfDev& D = m->dev;
   hipError_t he = hipMemsetAsync(D.flags, 0, sizeof(int) * 8, s);
@@ -873,6 +905,7 @@ hipError_t mfront_optimize(Mfront* m, hipStream_t s, const EdgeListDev& el, doub
     if (el.kinds) hipLaunchKernelGGL(k_mf_edges<true>, dim3(egrid), dim3(kBlock), 0, s, D, el, (const double*)d_poses, it, last ? 1 : 0, d_hist, d_res);
     else hipLaunchKernelGGL(k_mf_edges<false>, dim3(egrid), dim3(kBlock), 0, s, D, el, (const double*)d_poses, it, last ? 1 : 0, d_hist, d_res);
     if (last) break;
+    if (until && rules::gain_stop_applies(it, iters)) hipLaunchKernelGGL(k_mf_gain_stop, dim3(1), dim3(64), 0, s, D, it, egrid, *until, d_hist);
     for (int h = 0; h <= P.height; ++h) {
       const int cnt = P.level_ptr[h + 1] - P.level_ptr[h];
       if (h > 0) {
@@ -889,7 +922,8 @@ hipError_t mfront_optimize(Mfront* m, hipStream_t s, const EdgeListDev& el, doub
     }
     hipLaunchKernelGGL(k_mf_update, dim3(ugrid), dim3(kBlock), 0, s, D, d_poses, it);
   }
-  hipLaunchKernelGGL(k_mf_finish, dim3(1), dim3(64), 0, s, D, iters, egrid, d_hist, d_res);
+  if (until) hipLaunchKernelGGL(k_mf_finish_until, dim3(1), dim3(64), 0, s, D, iters, egrid, d_hist, d_res);
+  else hipLaunchKernelGGL(k_mf_finish, dim3(1), dim3(64), 0, s, D, iters, egrid, d_hist, d_res);
   if (iters > 0) m->ran = true;
   if (D.dbg && iters > 0) {   // diagnostic: phases of the LAST factorisation, per level the front with the longest total
     std::vector<long long> h(8 * P.fronts.size());

@@ -11,8 +11,28 @@
 #include <cmath>
 #include <cstddef>
 
+// A rule the kernels compile too carries SGO_RULE_HD: the compiler's own attributes under a HIP compilation, nothing for a host
+// compiler -- no HIP header either way.
+#if defined(__HIP__)
+#define SGO_RULE_HD __attribute__((host)) __attribute__((device))
+#else
+#define SGO_RULE_HD
+#endif
+
 namespace sgo {
 namespace rules {
+
+// The gain rule of sgo_optimize_gn_until (g2o's SparseOptimizerTerminateAction): with `last` and `cur` the
+// robust chi2 at the start of the previous and of this iteration, the call stops before this iteration iff the relative gain
+// (last - cur) / cur is in [0, gain_tol).  A negative gain does not stop (DCS makes chi2 non-monotone), gain_tol <= 0 never does,
+// and cur == 0 or a non-finite argument gives NaN or inf, for which both comparisons are false.  The caller applies it from the
+// third iteration on (gain_stop_applies).  `double` and comparisons only: the host, k_direct and k_mf_gain_stop compile this text.
+SGO_RULE_HD inline bool gain_stop(double last, double cur, double gain_tol) {
+  const double gain = (last - cur) / cur;
+  return gain >= 0.0 && gain < gain_tol;
+}
+// ... and the iterations before which it is asked: at least two updates always run, and the closing pass decides nothing.
+SGO_RULE_HD inline bool gain_stop_applies(int it, int max_iters) { return it >= 2 && it < max_iters; }
 
 // Iteration counts are compared at EQUAL tolerance: a solve that stopped at the absolute criterion (a looser relative tolerance
 // tolk > tol0, pcg_tol_cap) is scaled to what tol0 would have cost -- PCG converges linearly, iterations ~ log(1 / tolerance).

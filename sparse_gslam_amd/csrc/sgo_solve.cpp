@@ -1015,14 +1015,16 @@ static void copy_history(const sgo_ctx* c, int done, sgo_stats* out) {
 
 // Small-graph path: the whole call is one launch (sgo_direct.h); mid-size path: one launch per level of the elimination tree and
 // Gauss-Newton iteration, no host round trip inside the call (sgo_mfront.h).
-static int optimize_factored(sgo_ctx* c, int32_t iters, sgo_stats* out, double t0) {
+// until (sgo_optimize_gn_until): the gain rule is applied on the device, no host round trip inside the call either.
+static int optimize_factored(sgo_ctx* c, int32_t iters, sgo_stats* out, double t0, UntilGain* until) {
   hipError_t he;
+  const double* tol = until ? &until->gain_tol : nullptr;
   if (c->direct) {
     Scope sc(c, K_DIRECT, direct_bytes(c->direct, c->E, iters));
-    he = direct_optimize(c->direct, c->stream, c->el, c->d_poses, iters, c->d_hist, c->d_dres);
+    he = direct_optimize(c->direct, c->stream, c->el, c->d_poses, iters, c->d_hist, c->d_dres, tol);
   } else {
     Scope sc(c, K_MFRONT, mfront_bytes(c->mf, c->E, iters), true);
-    he = mfront_optimize(c->mf, c->stream, c->el, c->d_poses, iters, c->d_hist, c->d_dres);
+    he = mfront_optimize(c->mf, c->stream, c->el, c->d_poses, iters, c->d_hist, c->d_dres, tol);
   }
   if (he != hipSuccess) {
     c->err = std::string(c->direct ? "k_direct launch: " : "multifrontal launch: ") + hipGetErrorString(he);
@@ -1035,6 +1037,8 @@ static int optimize_factored(sgo_ctx* c, int32_t iters, sgo_stats* out, double t
   c->linearized = false;
   const DirectResult& R = *c->h_dres;
   const int done = R.done;
+  if (until) until->stop_reason = R.fail ? SGO_STOP_FAILED : (done < iters ? SGO_STOP_GAIN : SGO_STOP_MAX_ITERS);
+  const int ran = R.fail ? iters : done;   // (the stamps of a call that stopped are those of the call of `done` iterations)
   if (R.fail) {
     c->err = std::string(c->direct ? "direct" : "multifrontal") + " factorisation failed in GN iteration " + std::to_string(done) +
              (R.fail == 1 ? " (a pivot block is not positive definite: Hessian not positive definite)"
@@ -1042,7 +1046,7 @@ static int optimize_factored(sgo_ctx* c, int32_t iters, sgo_stats* out, double t
   }
   if (out) {
     copy_history(c, done, out);
-    const int timed = std::min(iters, done + (R.fail ? 1 : 0));
+    const int timed = std::min(ran, done + (R.fail ? 1 : 0));
     for (int k = 0; k < timed; ++k) {
       out->pcg_iters[k] = 0;
       out->pcg_converged[k] = (k < done) ? 1 : 0;
@@ -1054,7 +1058,7 @@ static int optimize_factored(sgo_ctx* c, int32_t iters, sgo_stats* out, double t
   }
   if (c->opts.verbose && done > 0 && c->direct)
     std::fprintf(stderr, "[sgo] direct: %.0f MHz shader clock during the call\n",
-                 (double)R.cycles / (1e-2 * (double)(R.stamp[R.fail ? 2 * done + 2 : 2 * iters + 1] - R.stamp[0])));
+                 (double)R.cycles / (1e-2 * (double)(R.stamp[R.fail ? 2 * done + 2 : 2 * ran + 1] - R.stamp[0])));
   if (c->opts.verbose && done > 0 && c->direct)
     std::fprintf(stderr, "[sgo] direct, last iteration [us]: edges %.1f, assembly %.1f, sparse forward %.1f, separators %.1f + %.1f, "
                  "sparse backward %.1f, update %.1f\n", 1e-2 * (double)(R.phase[1] - R.phase[0]), 1e-2 * (double)(R.phase[2] - R.phase[1]),
@@ -1068,10 +1072,19 @@ static int optimize_factored(sgo_ctx* c, int32_t iters, sgo_stats* out, double t
 
 // chi2, buildSystem and the PCG start state of iteration `it`, with the set-up the policy asked for: the movement since the
 // aggregation is measured in the call's first iteration, and a pending rebuild -- a re-aggregation trial's included -- is done here.
-static int linearize_step(sgo_ctx* c, CallPolicy& pol, int it, int iters) {
+// until (sgo_optimize_gn_until): the gain rule is asked between the two -- the host reads this iteration's chi2 and the one before
+// behind one small synchronisation, and a stop (*stopped) returns BEFORE the linearisation: no solve is started whose count would
+// reach the policy or the hierarchy's state, and d_hist[2 it] is the call's final value (the closing do_chi2 rewrites the same sums).
+static int linearize_step(sgo_ctx* c, CallPolicy& pol, int it, int iters, const UntilGain* until, bool* stopped) {
   if (pol.trial == CallPolicy::kTrialJudging || pol.rebuild_next) c->hier.ref_valid = false;   // (the trial's solves are fresh ones)
   int rc;
-  if ((rc = do_chi2(c, c->d_hist + 2 * it, nullptr)) || (rc = do_linearize(c))) return rc;
+  if ((rc = do_chi2(c, c->d_hist + 2 * it, nullptr))) return rc;
+  if (until && rules::gain_stop_applies(it, iters)) {
+    HIP_TRY(c, hipMemcpyAsync(c->h_hist + 2 * (it - 1), c->d_hist + 2 * (it - 1), sizeof(double) * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if ((*stopped = rules::gain_stop(c->h_hist[2 * it - 1], c->h_hist[2 * it + 1], until->gain_tol))) return SGO_OK;
+  }
+  if ((rc = do_linearize(c))) return rc;
   c->agg_grid = 0;
   if (it == 0 && c->amg && c->call.lag_on && c->hier.agg_ref_valid && !c->owner && iters > 1)   // (read behind the first solve's synchronisation)
     c->agg_grid = launch_diag_change(c->stream, 0, c->n, c->S0.dblk, c->d_dref_agg, false, c->h_dchg_dev + 3 * (size_t)kMaxPartials);
@@ -1199,7 +1212,9 @@ static std::string failure_message(sgo_ctx* c, const PcgScalars& S, int it) {
 
 // g2o's optimize(iters) on the PCG path: per iteration linearise (with any rebuild the policy asked for),
 // solve, recover, check the floor, record the solve in the call's policy (sgo_policy.h), then fail or apply the step.
-int optimize_gn(sgo_ctx* c, int32_t iters, sgo_stats* out) {
+// until != nullptr: sgo_optimize_gn_until -- the call ends before the first iteration at which rules::gain_stop holds (the
+// factorisation paths decide on the device, this loop in linearize_step); the policy is built for `iters` either way.
+int optimize_gn(sgo_ctx* c, int32_t iters, sgo_stats* out, UntilGain* until) {
   int rc = check_graph(c);
   if (rc) return rc;
   if (iters < 0 || iters > SGO_MAX_ITERS) {
@@ -1214,7 +1229,8 @@ int optimize_gn(sgo_ctx* c, int32_t iters, sgo_stats* out) {
   if (c->n == 0) return SGO_ENOTHING;
   const double t0 = wall_s();
   read_call_knobs(c);
-  if (c->direct || c->mf) return optimize_factored(c, iters, out, t0);
+  if (until) until->stop_reason = SGO_STOP_MAX_ITERS;
+  if (c->direct || c->mf) return optimize_factored(c, iters, out, t0, until);
   if ((rc = ensure_amg(c))) return rc;
   // per-iteration time stamps: events are kept in the context and reused by later calls
   while (c->iter_events.size() < 3 * (size_t)iters + 1) {
@@ -1235,13 +1251,14 @@ int optimize_gn(sgo_ctx* c, int32_t iters, sgo_stats* out) {
   c->tol_cap = c->opts.pcg_tol_cap > 0.0 ? std::max(c->opts.pcg_tol_cap, c->opts.pcg_tol * c->tol_scale) : 0.0;
   CallPolicy pol(iters, c->knobs.rebuild_cost, c->knobs.force_rebuild && c->amg != nullptr);   // (test hook: a rebuild first)
   int done = 0;
-  bool failed = false;
+  bool failed = false, stopped = false;
   for (int it = 0; it < iters; ++it) {
     hipEventRecord(ev[3 * it], c->stream);
     c->call.pcg_softcap = pol.solve_cap(c->hier, c->amg != nullptr, c->knobs.first_solve_cap);
     c->call.lag_cap = pol.lag_cap();
     c->call.force_keep = c->knobs.lag_force_from >= 0 && it > c->knobs.lag_force_from;   // (calibration hook, scripts/lag_calib.py)
-    if ((rc = linearize_step(c, pol, it, iters))) return rc;
+    if ((rc = linearize_step(c, pol, it, iters, until, &stopped))) return rc;
+    if (stopped) break;
     hipEventRecord(ev[3 * it + 1], c->stream);
     int wasted = 0;
     bool interrupted = false, floor_accept = false;
@@ -1289,6 +1306,7 @@ int optimize_gn(sgo_ctx* c, int32_t iters, sgo_stats* out) {
                    c->call.skip_update ? " coarse operators kept" : "");
   }
   c->lag_note = pol.note(done);
+  if (until) until->stop_reason = failed ? SGO_STOP_FAILED : (stopped ? SGO_STOP_GAIN : SGO_STOP_MAX_ITERS);
   if ((rc = do_chi2(c, c->d_hist + 2 * done, nullptr))) return rc;
   HIP_TRY(c, hipMemcpyAsync(c->h_hist, c->d_hist, sizeof(double) * 2 * (size_t)(done + 1), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -1300,7 +1318,7 @@ int optimize_gn(sgo_ctx* c, int32_t iters, sgo_stats* out) {
   prof_flush(c);
   if (out) {
     copy_history(c, done, out);
-    const int timed = std::min(iters, done + 1);
+    const int timed = std::min(iters, done + (stopped ? 0 : 1));   // (a stopped iteration has no solve to time)
     for (int k = 0; k < timed; ++k) {
       float a = 0.f, b = 0.f;
       hipEventElapsedTime(&a, ev[3 * k], ev[3 * k + 1]);
