@@ -46,6 +46,23 @@ int main(void) {
   printf("iterations %d  chi2 %.6g -> %.3g\n", done, st->chi2[0], st->chi2[done]);
   for (int v = 0; v < 4; ++v) printf("pose %d: %.6f %.6f %.6f\n", v, poses[3 * v], poses[3 * v + 1], poses[3 * v + 2]);
   int ok = done == 10 && st->chi2[done] < 1e-16;
+  /* leave-one-out over the closures, one call: hypothesis 0 keeps every edge, hypothesis 1 switches the closing edge off.  Each is
+   * optimised from the resident poses; edge_chi2 says what the left-out closure would cost at the poses found without it, and the
+   * context is left as it was */
+  {
+    const uint8_t off[2 * 4] = {0, 0, 0, 0, 0, 0, 0, 1};
+    sgo_hypothesis_result res[2];
+    double e2[2 * 4];
+    const int route = sgo_optimize_gn_hypotheses(ctx, 2, 10, 0.0, off, NULL, res, NULL, NULL, e2);
+    if (route < 0) {
+      fprintf(stderr, "sgo_optimize_gn_hypotheses: %s\n", sgo_last_error(ctx));
+      return 1;
+    }
+    printf("leave-one-out (%s): with the closure chi2 %.3g after %d iterations; without it chi2 %.3g, the closure would cost %.3g\n",
+           route == SGO_HYP_BATCHED ? "one launch" : "sequential", res[0].chi2, (int)res[0].iters_done, res[1].chi2, e2[4 + 3]);
+    ok = ok && res[0].stop_reason == SGO_STOP_MAX_ITERS && res[1].stop_reason == SGO_STOP_MAX_ITERS && res[1].chi2 < 1e-16 &&
+         sgo_hypothesis_isolated_vertex(4, fixed, 4, ei, ej, info, off + 4) == -1;
+  }
   /* the graph grows -- one more pose a step further along, with its odometry edge --: the new graph's first four edges are the
    * resident graph, which sgo_update_graph_se2 is told; where the resident structures can take the appended part (graphs of the
    * multigrid path, include/sgo.h) they are kept, otherwise -- as for this toy -- the call is sgo_set_graph_se2 */

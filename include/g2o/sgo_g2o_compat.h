@@ -736,6 +736,15 @@ class SparseOptimizerTerminateAction : public HyperGraphAction {
 };
 
 // ------------------------------------------------------------------------------- optimiser
+// What SparseOptimizer::sgoOptimizeHypotheses returns per hypothesis (extension; sgo_optimize_gn_hypotheses of include/sgo.h).
+struct SgoHypothesis {
+  int iterations = 0;        // updates applied
+  int stopReason = 0;        // SGO_STOP_MAX_ITERS / SGO_STOP_GAIN / SGO_STOP_FAILED
+  double chi2 = 0.0, robustChi2 = 0.0;                      // at the hypothesis' final poses
+  std::map<const OptimizableGraph::Edge*, double> edgeChi2; // e^T Omega e of every active edge there, with the edge's own information
+  std::map<int, SE2> poses;                                 // the final poses by vertex id
+};
+
 class SparseOptimizer : public OptimizableGraph {
  public:
   SparseOptimizer() {}
@@ -1052,6 +1061,60 @@ class SparseOptimizer : public OptimizableGraph {
       for (size_t t = 0; t < n; ++t) (*pass)[t] = ok[t] != 0;
     }
     return rc;
+  }
+
+  // ---- many closure hypotheses of the graph in one call (extension; sgo_optimize_gn_hypotheses of include/sgo.h): hypothesis b is
+  // the graph without the edges of off[b], optimised from the current estimates as optimize(iters) under a
+  // SparseOptimizerTerminateAction of gain threshold gainTol would (gainTol <= 0: plain optimize(iters)).  Valid after
+  // initializeOptimization() on a graph the device holds or can take; out[b] gets the iterations, the stop reason, both chi2, every
+  // active edge's chi2 and the poses.  No vertex estimate changes.  false with one line on std::cerr for a graph that takes the host
+  // solver (Levenberg, landmark types), for an edge that is not an active edge, and when the call itself refuses.
+  bool sgoOptimizeHypotheses(const std::vector<std::vector<OptimizableGraph::Edge*>>& off, int iters, double gainTol,
+                             std::vector<SgoHypothesis>& out) {
+    if (!_algorithm || _activeRevision != _revision || _activeVertices.empty() || !gpuEligible()) {
+      std::cerr << "SparseOptimizer::sgoOptimizeHypotheses: only the device path (VertexSE2 / EdgeSE2 under Gauss-Newton, after initializeOptimization) optimises hypotheses"
+                << std::endl;
+      return false;
+    }
+    if (!uploadGraph()) return false;
+    // the device's record of every active edge (records of edges that left the graph since are deactivated there and stay so)
+    const size_t dE = _m.ei.size(), V = _activeVertices.size(), B = off.size();
+    std::unordered_map<const OptimizableGraph::Edge*, size_t> record;
+    {
+      size_t k = 0;
+      for (size_t r = 0; r < dE && k < _activeEdges.size(); ++r)
+        if (!_m.dead[r]) record[_activeEdges[k++]] = r;
+    }
+    std::vector<uint8_t> mask(std::max<size_t>(B * dE, 1), 0);
+    for (size_t b = 0; b < B; ++b)
+      for (const OptimizableGraph::Edge* e : off[b]) {
+        const auto it = record.find(e);
+        if (it == record.end()) {
+          std::cerr << "SparseOptimizer::sgoOptimizeHypotheses: hypothesis " << b << " lists an edge that is not an active edge" << std::endl;
+          return false;
+        }
+        mask[b * dE + it->second] = 1;
+      }
+    std::vector<sgo_hypothesis_result> res(std::max<size_t>(B, 1));
+    std::vector<double> poses(std::max<size_t>(3 * B * V, 1)), e2(std::max<size_t>(B * dE, 1));
+    if (sgo_optimize_gn_hypotheses(_ctx, (int32_t)B, iters, gainTol, mask.data(), nullptr, res.data(), nullptr, poses.data(), e2.data()) < 0) {
+      std::cerr << "SparseOptimizer::sgoOptimizeHypotheses: " << sgo_last_error(_ctx) << std::endl;
+      return false;
+    }
+    out.assign(B, SgoHypothesis());
+    for (size_t b = 0; b < B; ++b) {
+      SgoHypothesis& h = out[b];
+      h.iterations = res[b].iters_done;
+      h.stopReason = res[b].stop_reason;
+      h.chi2 = res[b].chi2;
+      h.robustChi2 = res[b].robust_chi2;
+      for (const auto& er : record) h.edgeChi2[er.first] = e2[b * dE + er.second];
+      for (size_t k = 0; k < V; ++k) {
+        const double* p = &poses[3 * (b * V + k)];
+        h.poses.emplace(_activeVertices[k]->id(), SE2(p[0], p[1], p[2]));
+      }
+    }
+    return true;
   }
 
   // ---- graph files (OptimizableGraph::load / save of g2o, for the types of this backend's device path):

@@ -239,6 +239,51 @@ int sgo_gain_stop(double last_robust_chi2, double robust_chi2, double gain_tol);
 #define SGO_STOP_FAILED 2
 int sgo_optimize_gn_until(sgo_ctx* ctx, int32_t max_iters, double gain_tol, sgo_stats* out, int32_t* stop_reason);
 
+/* (later additions, version 107) Many closure hypotheses of the resident graph in one call: "is this set of
+ * closures consistent", leave-one-out over a round's closures, cluster tests -- the same graph optimised once per hypothesis.
+ *
+ * Hypothesis b is the resident graph with every edge k with edge_off[b][k] != 0 deactivated, as sgo_set_edge_information does with
+ * an all-zero row; an edge the context holds inactive already stays inactive in every hypothesis.  It starts from poses0[b] -- taken
+ * as sgo_set_poses takes its argument: every entry as given, those of fixed vertices included, so pass the resident values there
+ * -- or, with poses0 == NULL, from the resident poses, and runs sgo_optimize_gn_until(max_iters, gain_tol); gain_tol <= 0 never
+ * stops, which is sgo_optimize_gn(max_iters).
+ *   res[b]          updates applied, SGO_STOP_*, and (chi2, robust chi2) at the hypothesis' final poses
+ *   hist[b]         (chi2, robust chi2) at the start of every applied iteration and at the end; the entries behind them are NaN
+ *   poses_out[b]    the final poses (of a failed hypothesis: the last applied update)
+ *   edge_chi2[b][k] e^T Omega e of edge k at those poses with the RESIDENT information: an edge the hypothesis switched off reports
+ *                   what it would cost (the number a consistency test needs), an edge the context holds inactive reports 0
+ * hist, poses_out and edge_chi2 may be NULL.  On the factorisation paths everything but edge_chi2 is, bit for bit, what the host
+ * loop { sgo_set_edge_information(zero rows); sgo_set_poses; sgo_optimize_gn_until; read back; restore the rows } returns.
+ * A linear solve that fails -- a pivot that is not positive definite, a non-finite update -- fails its hypothesis alone
+ * (SGO_STOP_FAILED, iters_done the updates applied before); the call still returns >= 0.
+ * The context is left as it was: resident poses, informations, kernel kinds, edge activity, sgo_stats.seconds_setup and
+ * sgo_solver_description.
+ * Returns the route taken: SGO_HYP_BATCHED on a direct_ldlt context -- ONE launch of B workgroups of the single-launch kernel,
+ * each on its own copy of what the kernel writes (workspaces of the context's, grown on demand; SGO_ENOMEM with the context intact
+ * when they do not fit), the resident factor untouched -- and SGO_HYP_SEQUENTIAL on every other single-GPU path: the host loop
+ * above inside the call, the resident solver's own arrays serving every hypothesis and the hierarchy's coarse operators refreshed
+ * by the next solve as after any sgo_set_edge_information.  B == 0 returns SGO_HYP_BATCHED and does nothing.
+ * SGO_EINVAL, with nothing changed and no output written: B < 0, max_iters outside [0, SGO_MAX_ITERS], a NULL edge_off or res
+ * with B > 0, a non-finite gain_tol or poses0 entry, a multi-GPU context (sgo_debug_set_shard's emulation included), an active
+ * incremental overlay, and a hypothesis that would leave a free pose without any incident edge of non-zero information
+ * (sgo_set_edge_information's rule, decided on the host before anything is queued; sgo_last_error names hypothesis and vertex). */
+typedef struct sgo_hypothesis_result {
+  int32_t iters_done;      /* updates applied */
+  int32_t stop_reason;     /* SGO_STOP_MAX_ITERS / SGO_STOP_GAIN / SGO_STOP_FAILED */
+  double chi2, robust_chi2;/* at the hypothesis' final poses */
+} sgo_hypothesis_result;
+#define SGO_HYP_BATCHED 1     /* all hypotheses in one launch */
+#define SGO_HYP_SEQUENTIAL 2  /* one after the other through the resident solver */
+int sgo_optimize_gn_hypotheses(sgo_ctx* ctx, int32_t B, int32_t max_iters, double gain_tol,
+                               const uint8_t* edge_off /*[B][E]*/, const double* poses0 /*[B][V][3] or NULL*/,
+                               sgo_hypothesis_result* res /*[B]*/, double* hist /*[B][max_iters+1][2] or NULL*/,
+                               double* poses_out /*[B][V][3] or NULL*/, double* edge_chi2 /*[B][E] or NULL*/);
+/* That rule as a pure function (no context, no GPU): info[E][6] the resident rows, off[E] one hypothesis' mask.  Returns the lowest
+ * free vertex that an edge the mask switches off (one whose resident row is not all zero) leaves without any incident edge of
+ * non-zero information, -1 when there is none, SGO_EINVAL for a NULL buffer, a negative count or an endpoint outside [0, V). */
+int32_t sgo_hypothesis_isolated_vertex(int32_t V, const uint8_t* fixed, int32_t E, const int32_t* ei, const int32_t* ej,
+                                       const double* info, const uint8_t* off);
+
 /* Replaces: computeActiveErrors(); activeChi2(); activeRobustChi2() (slc.cpp:288, drone.cpp:162-165).
  * Called right after sgo_optimize_gn or sgo_optimize_gn_until it returns the final entries of that call's history bit for bit
  * (on a direct_ldlt context the sums come from the single-launch kernel's own closing pass). */

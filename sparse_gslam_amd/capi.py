@@ -34,11 +34,14 @@ SYMBOLS = [
     "sgo_debug_mfront_array", "sgo_mfront_plan_array", "sgo_debug_pcg_array", "sgo_debug_pcg_run",
     "sgo_set_edge_information", "sgo_gate_edges", "sgo_set_robust_kernels", "sgo_edge_robust",
     "sgo_solve_rhs", "sgo_marginals", "sgo_marginals_selected", "sgo_factor_solve", "sgo_candidate_gate",
-    "sgo_gain_stop", "sgo_optimize_gn_until",
+    "sgo_gain_stop", "sgo_optimize_gn_until", "sgo_optimize_gn_hypotheses", "sgo_hypothesis_isolated_vertex",
 ]
 
 # SGO_STOP_*: why sgo_optimize_gn_until ended
 STOP_MAX_ITERS, STOP_GAIN, STOP_FAILED = 0, 1, 2
+
+# SGO_HYP_*: the route sgo_optimize_gn_hypotheses took
+HYP_BATCHED, HYP_SEQUENTIAL = 1, 2
 
 # SGO_KERNEL_*: the robust kernels sgo_set_robust_kernels takes, in include/sgo.h's numbering
 KERNEL_NONE, KERNEL_DCS, KERNEL_HUBER, KERNEL_PSEUDO_HUBER, KERNEL_CAUCHY = 0, 1, 2, 3, 4
@@ -72,6 +75,28 @@ class Stats(C.Structure):
                 ("seconds_linearize", C.c_double * SGO_MAX_ITERS),
                 ("seconds_solve", C.c_double * SGO_MAX_ITERS),
                 ("seconds_total", C.c_double), ("seconds_setup", C.c_double)]
+
+
+class HypothesisResult(C.Structure):
+    """sgo_hypothesis_result (include/sgo.h)."""
+    _fields_ = [("iters_done", C.c_int32), ("stop_reason", C.c_int32), ("chi2", C.c_double), ("robust_chi2", C.c_double)]
+
+
+def hypothesis_isolated_vertex(fixed, ei, ej, info, off) -> int:
+    """sgo_hypothesis_isolated_vertex: the lowest free vertex the mask `off` (E,) leaves without an incident edge of non-zero
+    information, or -1 (no context, no GPU)."""
+    f = np.ascontiguousarray(fixed, dtype=np.uint8)
+    a = np.ascontiguousarray(ei, dtype=np.int32)
+    b = np.ascontiguousarray(ej, dtype=np.int32)
+    o = np.ascontiguousarray(info, dtype=np.float64).reshape(-1, 6)
+    m = np.ascontiguousarray(off, dtype=np.uint8).reshape(-1)
+    if not (a.size == b.size == o.shape[0] == m.size):
+        raise ValueError("inconsistent array sizes")
+    u8 = C.POINTER(C.c_uint8)
+    rc = lib().sgo_hypothesis_isolated_vertex(f.size, f.ctypes.data_as(u8), a.size, _ip(a), _ip(b), _dp(o), m.ctypes.data_as(u8))
+    if rc < -1:
+        raise SgoError(f"sgo_hypothesis_isolated_vertex: rc={rc}: " + lib().sgo_last_error(None).decode())
+    return rc
 
 
 class MatchWindow(C.Structure):
@@ -129,6 +154,9 @@ def lib():
     L.sgo_optimize_gn.argtypes = [vp, C.c_int32, C.POINTER(Stats)]
     L.sgo_optimize_gn_until.argtypes = [vp, C.c_int32, C.c_double, C.POINTER(Stats), i32]
     L.sgo_gain_stop.argtypes = [C.c_double, C.c_double, C.c_double]
+    L.sgo_optimize_gn_hypotheses.argtypes = [vp, C.c_int32, C.c_int32, C.c_double, u8, d, C.POINTER(HypothesisResult), d, d, d]
+    L.sgo_hypothesis_isolated_vertex.restype = C.c_int32
+    L.sgo_hypothesis_isolated_vertex.argtypes = [C.c_int32, u8, C.c_int32, i32, i32, d, u8]
     L.sgo_chi2.argtypes = [vp, d, d]
     L.sgo_edge_chi2.argtypes = [vp, d]
     L.sgo_set_edge_information.argtypes = [vp, C.c_int32, i32, d]
@@ -459,6 +487,47 @@ class Optimizer:
         why = C.c_int32(-1)
         rc = self._check(lib().sgo_optimize_gn_until(self._h, max_iters, gain_tol, C.byref(st), C.byref(why)), "sgo_optimize_gn_until")
         return rc, self._stats_dict(rc, st, max_iters), why.value
+
+    def optimize_hypotheses(self, edge_off, max_iters: int = 20, gain_tol: float = 0.0, poses0=None,
+                            want=("hist", "poses", "edge_chi2"), out=None):
+        """sgo_optimize_gn_hypotheses: the resident graph optimised once per row of edge_off (B, E) -- non-zero: that edge is
+        switched off in that hypothesis -- from poses0 (B, V, 3) or the resident poses, each as optimize_until(max_iters, gain_tol).
+        -> dict: route (HYP_*), iters_done (B,), stop_reason (B,), chi2 (B,), robust_chi2 (B,) and, as `want` names them,
+        hist (B, max_iters + 1, 2; NaN behind the applied iterations), poses (B, V, 3), edge_chi2 (B, E; with the resident
+        information).  The context is left as it was.  out: arrays to write into instead of fresh ones, by those names and
+        "res" (a HypothesisResult array)."""
+        m = np.ascontiguousarray(edge_off, dtype=np.uint8)
+        if m.ndim != 2 or m.shape[1] != self.E:
+            raise ValueError("edge_off must be (B, E)")
+        B = m.shape[0]
+        p0 = None
+        if poses0 is not None:
+            p0 = np.ascontiguousarray(poses0, dtype=np.float64)
+            if p0.shape != (B, self.V, 3):
+                raise ValueError("poses0 must be (B, V, 3)")
+        out = dict(out or {})
+        res = out.get("res")
+        if res is None:
+            res = (HypothesisResult * max(B, 1))()
+        shapes = dict(hist=(B, max_iters + 1, 2), poses=(B, self.V, 3), edge_chi2=(B, self.E))
+        arr = {}
+        for k in ("hist", "poses", "edge_chi2"):
+            if k in want:
+                a = out.get(k)
+                arr[k] = np.empty(shapes[k]) if a is None else a
+                if arr[k].shape != shapes[k] or arr[k].dtype != np.float64 or not arr[k].flags.c_contiguous:
+                    raise ValueError(f"out[{k!r}] must be a contiguous float64 array of shape {shapes[k]}")
+        ptr = {k: (_dp(arr[k]) if k in arr else None) for k in shapes}
+        route = self._check(lib().sgo_optimize_gn_hypotheses(
+            self._h, B, max_iters, float(gain_tol), m.ctypes.data_as(C.POINTER(C.c_uint8)), None if p0 is None else _dp(p0),
+            res, ptr["hist"], ptr["poses"], ptr["edge_chi2"]), "sgo_optimize_gn_hypotheses")
+        r = dict(route=route,
+                 iters_done=np.array([res[b].iters_done for b in range(B)], dtype=np.int32),
+                 stop_reason=np.array([res[b].stop_reason for b in range(B)], dtype=np.int32),
+                 chi2=np.array([res[b].chi2 for b in range(B)], dtype=np.float64),
+                 robust_chi2=np.array([res[b].robust_chi2 for b in range(B)], dtype=np.float64))
+        r.update(arr)
+        return r
 
     def _stats_dict(self, rc, st, iters):
         d = max(st.iters_done, 0)

@@ -383,6 +383,7 @@ void sgo_destroy(sgo_ctx* c) {
   if (c->selinv.d_fs) hipFree(c->selinv.d_fs);
   if (c->selinv.d_cand) hipFree(c->selinv.d_cand);
   if (c->selinv.d_cidx) hipFree(c->selinv.d_cidx);
+  if (c->hyp.d_ws) hipFree(c->hyp.d_ws);
   if (c->stream) hipStreamDestroy(c->stream);
   delete c;
 }
@@ -1231,6 +1232,190 @@ int sgo_optimize_gn_until(sgo_ctx* c, int32_t max_iters, double gain_tol, sgo_st
     const int done = optimize_gn(c, max_iters, out, &until);
     if (stop_reason && done >= 0) *stop_reason = until.stop_reason;
     return done;
+  } SGO_CATCH(c)
+}
+
+int32_t sgo_hypothesis_isolated_vertex(int32_t V, const uint8_t* fixed, int32_t E, const int32_t* ei, const int32_t* ej, const double* info,
+                                       const uint8_t* off) {
+  try {
+    if (V < 0 || E < 0 || (V > 0 && !fixed) || (E > 0 && (!ei || !ej || !info || !off))) {
+      g_err = "sgo_hypothesis_isolated_vertex: null buffer or negative count";
+      return SGO_EINVAL;
+    }
+    for (int e = 0; e < E; ++e)
+      if (ei[e] < 0 || ei[e] >= V || ej[e] < 0 || ej[e] >= V) {
+        g_err = "sgo_hypothesis_isolated_vertex: edge " + std::to_string(e) + " references a vertex outside [0, V)";
+        return SGO_EINVAL;
+      }
+    auto dead = [&](int e) { return zero_row(info + 6 * (size_t)e); };
+    std::vector<int> deg((size_t)V, 0);
+    for (int e = 0; e < E; ++e)
+      if (!dead(e)) {
+        deg[ei[e]]++;
+        deg[ej[e]]++;
+      }
+    return rules::hypothesis_isolated_vertex(fixed, E, ei, ej, dead, off, deg.data());
+  } SGO_CATCH((sgo_ctx*)nullptr)
+}
+
+namespace {
+
+// What the two routes of sgo_optimize_gn_hypotheses share of their outputs: hypothesis b's record and the history's NaN tail.
+void hypothesis_record(int b, int max_iters, int done, int fail, const double* hist_b, sgo_hypothesis_result* res, double* hist) {
+  res[b].iters_done = done;
+  res[b].stop_reason = fail ? SGO_STOP_FAILED : (done < max_iters ? SGO_STOP_GAIN : SGO_STOP_MAX_ITERS);
+  res[b].chi2 = hist_b[2 * done];
+  res[b].robust_chi2 = hist_b[2 * done + 1];
+  if (!hist) return;
+  double* h = hist + 2 * ((size_t)max_iters + 1) * (size_t)b;
+  for (int k = 0; k <= max_iters; ++k) {
+    h[2 * k] = k <= done ? hist_b[2 * k] : std::nan("");
+    h[2 * k + 1] = k <= done ? hist_b[2 * k + 1] : std::nan("");
+  }
+}
+
+// The single-launch path: one launch of B workgroups (sgo_direct.h), every result read once behind it.
+int hypotheses_batched(sgo_ctx* c, int B, int max_iters, double gain_tol, const uint8_t* edge_off, const double* poses0,
+                       sgo_hypothesis_result* res, double* hist, double* poses_out, double* edge_chi2) {
+  const size_t E = (size_t)c->E, V3 = 3 * (size_t)c->V, H = 2 * ((size_t)max_iters + 1);
+  const DirectBatchLayout L = direct_batch_layout(c->direct, c->V, B, max_iters);
+  int rc;
+  if (L.bytes > c->hyp.ws_cap) {
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if ((rc = grow_device(c, &c->hyp.d_ws, &c->hyp.ws_cap, L.bytes))) {
+      c->err = "sgo_optimize_gn_hypotheses: out of device memory (" + std::to_string(L.bytes) + " bytes for " + std::to_string(B) + " hypotheses)";
+      return rc;
+    }
+  }
+  char* ws = c->hyp.d_ws;
+  HIP_TRY(c, hipMemcpyAsync(ws + L.o_off, edge_off, (size_t)B * E, hipMemcpyHostToDevice, c->stream));
+  if (poses0) HIP_TRY(c, hipMemcpyAsync(ws + L.o_poses, poses0, sizeof(double) * (size_t)B * V3, hipMemcpyHostToDevice, c->stream));
+  {
+    Scope sc(c, K_DIRECT, (double)B * direct_bytes(c->direct, c->E, max_iters), true);
+    const hipError_t he = direct_optimize_batch(c->direct, c->stream, c->el, c->d_poses, poses0 != nullptr, L, ws, max_iters, gain_tol,
+                                                edge_chi2 != nullptr);
+    if (he != hipSuccess) {
+      c->err = std::string("k_direct (batched) launch: ") + hipGetErrorString(he);
+      return SGO_EHIP;
+    }
+  }
+  std::vector<double> h_hist((size_t)B * H);
+  std::vector<int> h_brief(2 * (size_t)B);
+  HIP_TRY(c, hipMemcpyAsync(h_hist.data(), ws + L.o_hist, sizeof(double) * h_hist.size(), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(h_brief.data(), ws + L.o_brief, sizeof(int) * h_brief.size(), hipMemcpyDeviceToHost, c->stream));
+  if (poses_out) HIP_TRY(c, hipMemcpyAsync(poses_out, ws + L.o_poses, sizeof(double) * (size_t)B * V3, hipMemcpyDeviceToHost, c->stream));
+  if (edge_chi2) HIP_TRY(c, hipMemcpyAsync(edge_chi2, ws + L.o_echi2, sizeof(double) * (size_t)B * E, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  prof_flush(c);
+  for (int b = 0; b < B; ++b) {
+    const int done = std::min(std::max(h_brief[2 * (size_t)b], 0), max_iters);
+    hypothesis_record(b, max_iters, done, h_brief[2 * (size_t)b + 1], h_hist.data() + H * (size_t)b, res, hist);
+  }
+  return SGO_HYP_BATCHED;
+}
+
+// Every other single-GPU path: the host loop itself -- zero rows, the start, optimise, read back, the rows again -- and the
+// resident poses at the end.
+int hypotheses_sequential(sgo_ctx* c, int B, int max_iters, double gain_tol, const uint8_t* edge_off, const double* poses0,
+                          sgo_hypothesis_result* res, double* hist, double* poses_out, double* edge_chi2) {
+  const size_t E = (size_t)c->E, V3 = 3 * (size_t)c->V, E0 = (size_t)c->el.E;
+  sgo_ctx::EdgeActivity& A = c->edges;
+  std::vector<double> resident(V3), info(6 * E0);
+  HIP_TRY(c, hipMemcpyAsync(resident.data(), c->d_poses, sizeof(double) * V3, hipMemcpyDeviceToHost, c->stream));
+  if (E0) HIP_TRY(c, hipMemcpyAsync(info.data(), c->el.info, sizeof(double) * 6 * E0, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  const std::string lag_note = c->lag_note;
+  std::unique_ptr<sgo_stats> st(new sgo_stats);
+  std::vector<int32_t> ids;
+  std::vector<double> zero, rows, e2(edge_chi2 ? E : 0);
+  int rc = SGO_OK;
+  for (int b = 0; b < B && rc == SGO_OK; ++b) {
+    const uint8_t* off = edge_off + (size_t)b * E;
+    ids.clear();
+    rows.clear();
+    for (size_t k = 0; k < E; ++k)
+      if (off[k] && !A.dead[k]) {
+        ids.push_back((int32_t)k);
+        for (int q = 0; q < 6; ++q) rows.push_back(info[(size_t)q * E0 + k]);
+      }
+    zero.assign(rows.size(), 0.0);
+    if ((rc = edge_info_apply(c, "sgo_optimize_gn_hypotheses", ids, zero))) break;
+    UntilGain until{gain_tol, SGO_STOP_MAX_ITERS};
+    int done = 0;
+    rc = upload_poses(c, poses0 ? poses0 + V3 * (size_t)b : resident.data(), c->V);
+    if (rc == SGO_OK) {
+      c->linearized = false;
+      done = optimize_gn(c, max_iters, st.get(), &until);
+      if (done < 0 && done != SGO_ENOTHING) rc = done;
+    }
+    if (rc == SGO_OK) {
+      std::vector<double> hb(2 * ((size_t)max_iters + 1), 0.0);
+      const int applied = std::min(std::max(st->iters_done, 0), max_iters);
+      for (int k = 0; k <= applied; ++k) {
+        hb[2 * k] = st->chi2[k];
+        hb[2 * k + 1] = st->robust_chi2[k];
+      }
+      hypothesis_record(b, max_iters, applied, until.stop_reason == SGO_STOP_FAILED, hb.data(), res, hist);
+      res[b].stop_reason = until.stop_reason;
+      if (poses_out) {
+        HIP_TRY(c, hipMemcpyAsync(poses_out + V3 * (size_t)b, c->d_poses, sizeof(double) * V3, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+      }
+    }
+    // the rows come back whatever happened, and the per-edge values are formed behind them: with the resident information
+    const int rb = edge_info_apply(c, "sgo_optimize_gn_hypotheses", ids, rows);
+    if (rc == SGO_OK) rc = rb;
+    if (rc == SGO_OK && edge_chi2) {
+      if ((rc = do_chi2(c, c->d_hist, c->d_e2))) break;
+      HIP_TRY(c, hipMemcpyAsync(edge_chi2 + E * (size_t)b, c->d_e2, sizeof(double) * E, hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(c, hipStreamSynchronize(c->stream));
+    }
+  }
+  const int rp = upload_poses(c, resident.data(), c->V);
+  if (rp == SGO_OK) HIP_TRY(c, hipStreamSynchronize(c->stream));
+  c->linearized = false;
+  c->lag_note = lag_note;
+  if (rc == SGO_OK) rc = rp;
+  return rc ? rc : SGO_HYP_SEQUENTIAL;
+}
+
+}  // namespace
+
+int sgo_optimize_gn_hypotheses(sgo_ctx* c, int32_t B, int32_t max_iters, double gain_tol, const uint8_t* edge_off, const double* poses0,
+                               sgo_hypothesis_result* res, double* hist, double* poses_out, double* edge_chi2) {
+  try {
+    int rc = check_graph(c);
+    if (rc) return rc;
+    auto refuse = [&](const std::string& why) {
+      c->err = "sgo_optimize_gn_hypotheses: " + why;
+      return SGO_EINVAL;
+    };
+    if (B < 0) return refuse("negative number of hypotheses");
+    if (max_iters < 0 || max_iters > SGO_MAX_ITERS) return refuse("max_iters must be in [0, SGO_MAX_ITERS]");
+    if (!std::isfinite(gain_tol)) return refuse("gain_tol is not finite");
+    if (B > 0 && (!edge_off || !res)) return refuse("null edge_off or res");
+    if (multi_gpu_context(c)) return refuse("not available in a multi-GPU context");
+    if (c->ov.active) return refuse("not available while an incremental overlay is active (call sgo_set_graph_se2)");
+    if (B == 0) return SGO_HYP_BATCHED;
+    if (c->n == 0) return refuse("the graph has no free pose");
+    const size_t E = (size_t)c->E, V3 = 3 * (size_t)c->V;
+    if (poses0)
+      for (size_t k = 0; k < (size_t)B * V3; ++k)
+        if (!std::isfinite(poses0[k]))
+          return refuse("non-finite starting pose of hypothesis " + std::to_string(k / V3) + " (vertex " + std::to_string((k % V3) / 3) + ")");
+    HIP_TRY(c, hipSetDevice(c->device));
+    if ((rc = edge_activity_ensure(c))) return rc;
+    sgo_ctx::EdgeActivity& A = c->edges;
+    for (int b = 0; b < B; ++b) {
+      const int v = rules::hypothesis_isolated_vertex(c->ov.fixed.data(), c->E, A.vi.data(), A.vj.data(), [&](int e) { return A.dead[e] != 0; },
+                                                      edge_off + (size_t)b * E, A.live_deg.data());
+      if (v >= 0)
+        return refuse("hypothesis " + std::to_string(b) + " leaves free vertex " + std::to_string(v) +
+                      " without an incident edge of non-zero information (its Hessian block would be singular)");
+    }
+    read_call_knobs(c);
+    if (c->direct) return hypotheses_batched(c, B, max_iters, gain_tol, edge_off, poses0, res, hist, poses_out, edge_chi2);
+    return hypotheses_sequential(c, B, max_iters, gain_tol, edge_off, poses0, res, hist, poses_out, edge_chi2);
   } SGO_CATCH(c)
 }
 

@@ -254,6 +254,13 @@ struct sgo_ctx {
     size_t kind_cap = 0;
   } robust;
 
+  // sgo_optimize_gn_hypotheses on the single-launch path: every hypothesis' copy of what k_direct writes, its information rows and
+  // its results (sgo_direct.h: DirectBatchLayout); grown on demand, kept across graphs.
+  struct Hypotheses {
+    char* d_ws = nullptr;
+    size_t ws_cap = 0;
+  } hyp;
+
   // Device scratch of sgo_marginals (sgo_marginals.cpp): the result blocks [npairs][9], the pairs' internal rows and the pairs
   // ordered by column vertex; grown on demand, kept across graphs.
   struct Marginals {

@@ -52,6 +52,22 @@ const DirectInfo& direct_info(const Direct* d);
 // *until and leaves d_res, the history and the poses as a call of that many iterations does.
 hipError_t direct_optimize(Direct* d, hipStream_t s, const EdgeListDev& el, double* d_poses, int iters, double* d_hist,
                            DirectResult* d_res, const double* until = nullptr);
+// sgo_optimize_gn_hypotheses on this path: B hypotheses of the resident graph as ONE launch of B workgroups of the batched
+// instantiation of the same kernel (always with the gain rule; gain_tol <= 0 never stops).  Workgroup b works on copy b of everything
+// the kernel writes; the copies live in one workspace of the caller's, laid out by direct_batch_layout (offsets in bytes, strides
+// in doubles from one hypothesis to the next).  The caller puts the masks [B][E] at o_off and, with own_poses, the starting poses
+// [B][V][3] at o_poses before the call; after it, it reads hist [B][iters + 1][2] at o_hist, {updates applied, DirectResult::fail}
+// [B] at o_brief, the poses at o_poses and, if asked for, e^T Omega e with the resident rows [B][E] at o_echi2.
+struct DirectBatchLayout {
+  int B = 0, V = 0, E = 0;
+  size_t hist_stride = 0;
+  size_t s_Wd = 0, s_Wo = 0, s_escr = 0, s_zsc = 0, s_xbg = 0, s_info = 0, s_poses = 0;
+  size_t o_off = 0, o_info = 0, o_poses = 0, o_hist = 0, o_echi2 = 0, o_brief = 0, o_res = 0, o_Wd = 0, o_Wo = 0, o_escr = 0, o_zsc = 0, o_xbg = 0;
+  size_t bytes = 0;
+};
+DirectBatchLayout direct_batch_layout(const Direct* d, int V, int B, int iters);
+hipError_t direct_optimize_batch(Direct* d, hipStream_t s, const EdgeListDev& el, const double* d_poses_res, bool own_poses,
+                                 const DirectBatchLayout& L, char* ws, int iters, double gain_tol, bool want_edge_chi2);
 // algorithmic bytes of one call (profile table)
 double direct_bytes(const Direct* d, int E, int iters);
 

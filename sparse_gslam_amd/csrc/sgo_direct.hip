@@ -29,6 +29,7 @@
 #include <atomic>
 #include <cstring>
 #include <numeric>
+#include <type_traits>
 #include <vector>
 
 #include "sgo_device.h"
@@ -73,6 +74,16 @@ struct DirectDev {
   double* escr;               // [E][27] per-edge terms of the current linearisation: Hii(6) bi(3) Hjj(6) bj(3) [Hij(9)]
   double* zsc;                // [2][E] sin / cos of the inverse measurement's angle (constant per edge)
 };
+
+// The batched instantiation (sgo_optimize_gn_hypotheses): workgroup b runs hypothesis b on its own copy of everything the kernel
+// writes -- the element strides from one copy to the next -- and reads its own information rows; the plan arrays stay shared.
+struct DirectBatch {
+  size_t Wd, Wo, escr, zsc, xbg, info, poses, hist;
+  const double* info_res;   // [6][E] the resident information rows (edge_chi2 is formed with these)
+  double* edge_chi2;        // [B][E] e^T Omega e at the final poses, or nullptr
+  int2* brief;              // [B] {updates applied, failure code}: what the host reads of a hypothesis' DirectResult
+};
+struct DirectSingle {};     // the dim3(1) instantiations take nothing
 
 // 1 / x by the hardware reciprocal + two Newton steps (the IEEE division sequence is 3x longer and sits on the
 // critical path of every pivot)
@@ -305,10 +316,24 @@ constexpr int kPF = 1;   // forward tasks per thread whose records are fetched o
 // next to the separator block) instead of LDS.  KINDS: the edges carry robust kernels other than DCS (sgo_device.h).
 // UNTIL: sgo_optimize_gn_until -- the call ends before the first iteration at which rules::gain_stop holds for gain_tol (thread 0
 // decides from the two sums it holds, the workgroup leaves the loop together); the plain instantiations never read gain_tol.
-template <bool XG, bool KINDS, bool UNTIL>
+// BATCH: one workgroup per hypothesis (DirectBatch above); always with UNTIL, whose gain_tol <= 0 never stops.
+template <bool XG, bool KINDS, bool UNTIL, bool BATCH = false>
 __global__ __launch_bounds__(kDT) void k_direct(DirectDev D, EdgeListDev el, double* __restrict__ poses, int iters,
-                                                double* __restrict__ hist, DirectResult* __restrict__ res, double gain_tol) {
+                                                double* __restrict__ hist, DirectResult* __restrict__ res, double gain_tol,
+                                                std::conditional_t<BATCH, DirectBatch, DirectSingle> bt) {
   extern __shared__ double lds[];
+  if constexpr (BATCH) {
+    const size_t b = blockIdx.x;
+    D.Wd += b * bt.Wd;
+    D.Wo += b * bt.Wo;
+    D.escr += b * bt.escr;
+    D.zsc += b * bt.zsc;
+    if constexpr (XG) D.xbg += b * bt.xbg;
+    el.info += b * bt.info;
+    poses += b * bt.poses;
+    hist += b * bt.hist;
+    res += b;
+  }
   double* xb;                             // [3 n] right-hand side, then the solution, by elimination position
   double* Sd;                             // [tri] packed lower triangle of the separator block
   if constexpr (XG) {
@@ -716,6 +741,40 @@ __global__ __launch_bounds__(kDT) void k_direct(DirectDev D, EdgeListDev el, dou
     res->fail = (fail & 1) ? 1 : (fail ? 2 : 0);
     res->stamp[fail ? 2 * done + 2 : 2 * (UNTIL ? done : iters) + 1] = (unsigned long long)wall_clock64();   // end of the call
   }
+  if constexpr (BATCH) {
+    if (tid == 0) bt.brief[blockIdx.x] = make_int2(done, (fail & 1) ? 1 : (fail ? 2 : 0));
+    // e^T Omega e of every edge at the poses that stay, with the RESIDENT rows: an edge the hypothesis switched off reports what it
+    // would cost, an active one the very e2 of the last pass (same operands, same instructions)
+    if (bt.edge_chi2) {
+      __syncthreads();
+      EdgeListDev er = el;
+      er.info = const_cast<double*>(bt.info_res);
+      double* __restrict__ out = bt.edge_chi2 + (size_t)blockIdx.x * E;
+      for (int k = tid; k < D.E; k += kDT) {
+        double e2, r0, hij[9];
+        edge_terms<KINDS>(er, D.zsc, k, poses, false, nullptr, hij, &e2, &r0);
+        out[k] = e2;
+      }
+    }
+  }
+}
+
+// What the batched launch needs before it starts: hypothesis b's information rows (off ? 0 : resident) and, when the caller gave no
+// starting poses, its copy of the resident ones.
+__global__ __launch_bounds__(256) void k_hyp_prepare(int B, int E, int V3, const double* __restrict__ info_res,
+                                                     const unsigned char* __restrict__ off, double* __restrict__ info_b, size_t info_stride,
+                                                     const double* __restrict__ poses_res, double* __restrict__ poses_b, size_t poses_stride) {
+  const int b = blockIdx.x;
+  const size_t items = (size_t)(E > V3 ? E : V3);
+  for (size_t t = (size_t)blockIdx.y * blockDim.x + threadIdx.x; t < items; t += (size_t)gridDim.y * blockDim.x) {
+    if (t < (size_t)E) {
+      const bool dead = off[(size_t)b * E + t] != 0;
+      double* o = info_b + (size_t)b * info_stride + t;
+#pragma unroll
+      for (int c = 0; c < 6; ++c) o[(size_t)c * E] = dead ? 0.0 : info_res[(size_t)c * E + t];
+    }
+    if (poses_res && t < (size_t)V3) poses_b[(size_t)b * poses_stride + t] = poses_res[t];
+  }
 }
 
 // ------------------------------------------------------------------------------------------------ host
@@ -1102,11 +1161,13 @@ Direct* direct_create(hipStream_t s, DevArena* arena, int V, int n, const int* f
   const bool attr_set_already = (attr_devices.load() & dev_bit) != 0;
   bool attr_set = attr_set_already;
   if (e == hipSuccess && !attr_set) {
-    const void* const variants[8] = {reinterpret_cast<const void*>(&k_direct<false, false, false>), reinterpret_cast<const void*>(&k_direct<true, false, false>),
+    const void* const variants[12] = {reinterpret_cast<const void*>(&k_direct<false, false, false>), reinterpret_cast<const void*>(&k_direct<true, false, false>),
                                      reinterpret_cast<const void*>(&k_direct<false, true, false>), reinterpret_cast<const void*>(&k_direct<true, true, false>),
                                      reinterpret_cast<const void*>(&k_direct<false, false, true>), reinterpret_cast<const void*>(&k_direct<true, false, true>),
-                                     reinterpret_cast<const void*>(&k_direct<false, true, true>), reinterpret_cast<const void*>(&k_direct<true, true, true>)};
-    for (int v = 0; v < 8 && e == hipSuccess; ++v)
+                                     reinterpret_cast<const void*>(&k_direct<false, true, true>), reinterpret_cast<const void*>(&k_direct<true, true, true>),
+                                     reinterpret_cast<const void*>(&k_direct<false, false, true, true>), reinterpret_cast<const void*>(&k_direct<true, false, true, true>),
+                                     reinterpret_cast<const void*>(&k_direct<false, true, true, true>), reinterpret_cast<const void*>(&k_direct<true, true, true, true>)};
+    for (int v = 0; v < 12 && e == hipSuccess; ++v)
       e = hipFuncSetAttribute(variants[v], hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBudget);
     attr_set = e == hipSuccess;
     if (attr_set) attr_devices.fetch_or(dev_bit);
@@ -1129,7 +1190,7 @@ Direct* direct_create(hipStream_t s, DevArena* arena, int V, int n, const int* f
 hipError_t direct_optimize(Direct* d, hipStream_t s, const EdgeListDev& el, double* d_poses, int iters, double* d_hist,
                            DirectResult* d_res, const double* until) {
 #define SGO_DIRECT_LAUNCH(XG, KINDS, UNTIL, tol) \
-  SGO_LAUNCH((k_direct<XG, KINDS, UNTIL>), dim3(1), dim3(kDT), d->info.lds_bytes, s, d->dev, el, d_poses, iters, d_hist, d_res, tol)
+  SGO_LAUNCH((k_direct<XG, KINDS, UNTIL>), dim3(1), dim3(kDT), d->info.lds_bytes, s, d->dev, el, d_poses, iters, d_hist, d_res, tol, DirectSingle{})
   if (until) {
     if (el.kinds) {
       if (d->xb_global) SGO_DIRECT_LAUNCH(true, true, true, *until);
@@ -1142,6 +1203,78 @@ hipError_t direct_optimize(Direct* d, hipStream_t s, const EdgeListDev& el, doub
   } else if (d->xb_global) SGO_DIRECT_LAUNCH(true, false, false, 0.0);
   else SGO_DIRECT_LAUNCH(false, false, false, 0.0);
 #undef SGO_DIRECT_LAUNCH
+  return hipGetLastError();
+}
+
+DirectBatchLayout direct_batch_layout(const Direct* d, int V, int B, int iters) {
+  const DirectDev& D = d->dev;
+  DirectBatchLayout L;
+  L.B = B;
+  L.V = V;
+  L.E = D.E;
+  L.hist_stride = 2 * ((size_t)iters + 1);
+  const size_t E = (size_t)std::max(D.E, 1), nb = (size_t)B;
+  size_t total = 0;
+  auto put = [&](size_t bytes) {   // 256-byte aligned pieces (the 16-byte loads of the stored blocks need 16)
+    const size_t at = total;
+    total += (bytes + 255) & ~(size_t)255;
+    return at;
+  };
+  // every stride a multiple of two doubles: a copy keeps the 16-byte alignment of its first
+  L.s_Wd = kBS * (size_t)std::max(D.nI, 1);
+  L.s_Wo = kBS * (size_t)std::max(D.NB, 1);
+  L.s_escr = 27 * E + (E & 1);
+  L.s_zsc = 2 * E;
+  L.s_xbg = d->xb_global ? 3 * (size_t)D.n + (D.n & 1) : 0;
+  L.s_info = 6 * E;
+  L.s_poses = 3 * (size_t)V;
+  L.o_off = put(nb * E);
+  L.o_info = put(sizeof(double) * nb * L.s_info);
+  L.o_poses = put(sizeof(double) * nb * L.s_poses);
+  L.o_hist = put(sizeof(double) * nb * L.hist_stride);
+  L.o_echi2 = put(sizeof(double) * nb * E);
+  L.o_brief = put(sizeof(int2) * nb);
+  L.o_res = put(sizeof(DirectResult) * nb);
+  L.o_Wd = put(sizeof(double) * nb * L.s_Wd);
+  L.o_Wo = put(sizeof(double) * nb * L.s_Wo);
+  L.o_escr = put(sizeof(double) * nb * L.s_escr);
+  L.o_zsc = put(sizeof(double) * nb * L.s_zsc);
+  L.o_xbg = put(sizeof(double) * nb * L.s_xbg);
+  L.bytes = total;
+  return L;
+}
+
+hipError_t direct_optimize_batch(Direct* d, hipStream_t s, const EdgeListDev& el, const double* d_poses_res, bool own_poses,
+                                 const DirectBatchLayout& L, char* ws, int iters, double gain_tol, bool want_edge_chi2) {
+  if (L.B <= 0) return hipSuccess;
+  DirectDev D = d->dev;
+  D.Wd = reinterpret_cast<double*>(ws + L.o_Wd);
+  D.Wo = reinterpret_cast<double*>(ws + L.o_Wo);
+  D.escr = reinterpret_cast<double*>(ws + L.o_escr);
+  D.zsc = reinterpret_cast<double*>(ws + L.o_zsc);
+  D.xbg = d->xb_global ? reinterpret_cast<double*>(ws + L.o_xbg) : nullptr;
+  EdgeListDev eb = el;
+  eb.info = reinterpret_cast<double*>(ws + L.o_info);
+  double* poses = reinterpret_cast<double*>(ws + L.o_poses);
+  DirectBatch bt;
+  bt.Wd = L.s_Wd; bt.Wo = L.s_Wo; bt.escr = L.s_escr; bt.zsc = L.s_zsc; bt.xbg = L.s_xbg; bt.info = L.s_info; bt.poses = L.s_poses;
+  bt.hist = L.hist_stride;
+  bt.info_res = el.info;
+  bt.edge_chi2 = want_edge_chi2 ? reinterpret_cast<double*>(ws + L.o_echi2) : nullptr;
+  bt.brief = reinterpret_cast<int2*>(ws + L.o_brief);
+  const int items = std::max(std::max(L.E, 3 * L.V), 1);
+  SGO_LAUNCH(k_hyp_prepare, dim3((unsigned)L.B, (unsigned)std::min((items + 255) / 256, 1024)), dim3(256), 0, s, L.B, L.E, 3 * L.V, el.info,
+             reinterpret_cast<const unsigned char*>(ws + L.o_off), eb.info, L.s_info, own_poses ? nullptr : d_poses_res, poses, L.s_poses);
+  double* hist = reinterpret_cast<double*>(ws + L.o_hist);
+  DirectResult* res = reinterpret_cast<DirectResult*>(ws + L.o_res);
+#define SGO_DIRECT_BATCH(XG, KINDS) \
+  SGO_LAUNCH((k_direct<XG, KINDS, true, true>), dim3((unsigned)L.B), dim3(kDT), d->info.lds_bytes, s, D, eb, poses, iters, hist, res, gain_tol, bt)
+  if (el.kinds) {
+    if (d->xb_global) SGO_DIRECT_BATCH(true, true);
+    else SGO_DIRECT_BATCH(false, true);
+  } else if (d->xb_global) SGO_DIRECT_BATCH(true, false);
+  else SGO_DIRECT_BATCH(false, false);
+#undef SGO_DIRECT_BATCH
   return hipGetLastError();
 }
 

@@ -10,6 +10,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstddef>
+#include <initializer_list>
 
 // A rule the kernels compile too carries SGO_RULE_HD: the compiler's own attributes under a HIP compilation, nothing for a host
 // compiler -- no HIP header either way.
@@ -33,6 +34,31 @@ SGO_RULE_HD inline bool gain_stop(double last, double cur, double gain_tol) {
 }
 // ... and the iterations before which it is asked: at least two updates always run, and the closing pass decides nothing.
 SGO_RULE_HD inline bool gain_stop_applies(int it, int max_iters) { return it >= 2 && it < max_iters; }
+
+// The mask rule of sgo_optimize_gn_hypotheses, which is sgo_set_edge_information's: a hypothesis may not leave a free pose without any
+// incident edge of non-zero information.  live_deg[V] holds every vertex' count of such edges in the resident graph, dead(e) says
+// whether edge e carries an all-zero information already, off[E] is the hypothesis' mask.  Returns the lowest free vertex that an
+// edge the mask switches off leaves without a live edge, or -1; live_deg is used as scratch and put back.
+template <class Dead>
+inline int hypothesis_isolated_vertex(const unsigned char* fixed, int E, const int* ei, const int* ej, Dead dead, const unsigned char* off,
+                                      int* live_deg) {
+  for (int e = 0; e < E; ++e)
+    if (off[e] && !dead(e)) {
+      --live_deg[ei[e]];
+      --live_deg[ej[e]];
+    }
+  int lowest = -1;
+  for (int e = 0; e < E; ++e)
+    if (off[e] && !dead(e))
+      for (const int v : {ei[e], ej[e]})
+        if (!fixed[v] && live_deg[v] <= 0 && (lowest < 0 || v < lowest)) lowest = v;
+  for (int e = 0; e < E; ++e)
+    if (off[e] && !dead(e)) {
+      ++live_deg[ei[e]];
+      ++live_deg[ej[e]];
+    }
+  return lowest;
+}
 
 // Iteration counts are compared at EQUAL tolerance: a solve that stopped at the absolute criterion (a looser relative tolerance
 // tolk > tol0, pcg_tol_cap) is scaled to what tol0 would have cost -- PCG converges linearly, iterations ~ log(1 / tolerance).
