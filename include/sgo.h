@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define SGO_VERSION 107          /* 0.1.7: (later additions under the same number, no signature changed: sgo_set_edge_information, sgo_gate_edges; sgo_set_robust_kernels, sgo_edge_robust, SGO_KERNEL_*; sgo_solve_rhs, sgo_marginals; sgo_marginals_selected, SGO_MF_SEL); sgo_stats.pcg_converged may be 2 (a solve accepted at the floating-point floor of its system), the incremental overlay keeps 64 touched + hub rows, SGO_AMG_SETUP (no signature changed); 0.1.6: sgo_plan_rows takes the measurements (row order of graphs whose poses contradict their closures); 0.1.5: the multifrontal path for mid-size graphs (sgo_mfront_plan; sgo_solver_description names it); 0.1.4: sgo_kernel_profile_samples, sgo_update_graph_se2 (incremental set-up); 0.1.3: row-owner multi-GPU mode (sgo_comm_host_allgather, sgo_debug_level0_bytes); 0.1.2: sgo_comm_init_host; 0.1.1: sgo_opts.direct_rows (took a reserved slot), sgo_solver_description */
+#define SGO_VERSION 107          /* 0.1.7: (later additions under the same number, no signature changed: sgo_set_edge_information, sgo_gate_edges; sgo_set_robust_kernels, sgo_edge_robust, SGO_KERNEL_*; sgo_solve_rhs, sgo_marginals; sgo_marginals_selected, SGO_MF_SEL; sgo_direct_plan_array, sgo_debug_direct_array, SGO_DR_*); sgo_stats.pcg_converged may be 2 (a solve accepted at the floating-point floor of its system), the incremental overlay keeps 64 touched + hub rows, SGO_AMG_SETUP (no signature changed); 0.1.6: sgo_plan_rows takes the measurements (row order of graphs whose poses contradict their closures); 0.1.5: the multifrontal path for mid-size graphs (sgo_mfront_plan; sgo_solver_description names it); 0.1.4: sgo_kernel_profile_samples, sgo_update_graph_se2 (incremental set-up); 0.1.3: row-owner multi-GPU mode (sgo_comm_host_allgather, sgo_debug_level0_bytes); 0.1.2: sgo_comm_init_host; 0.1.1: sgo_opts.direct_rows (took a reserved slot), sgo_solver_description */
 #define SGO_MAX_ITERS 256        /* capacity of the per-iteration arrays in sgo_stats */
 
 /* error codes (negative).  -1 mirrors g2o's optimize() "nothing to optimise". */
@@ -753,6 +753,83 @@ int sgo_debug_overlay_apply(sgo_ctx* ctx, const double* x, double* y, double* do
 int64_t sgo_debug_mfront_array(sgo_ctx* ctx, int32_t what, void* out, int64_t cap_bytes);
 int64_t sgo_mfront_plan_array(int32_t V, const double* poses, const uint8_t* fixed, int32_t E, const int32_t* ei, const int32_t* ej,
                               int32_t leaf, double max_crit_mflop, int32_t what, void* out, int64_t cap_bytes);
+/* Test hooks for the single-launch direct path (small graphs: DESIGN.md section 5a; tests/direct_reference.py checks every stage
+ * of one Gauss-Newton iteration of k_direct from these arrays).
+ * sgo_direct_plan_array: one table of the host analysis sgo_set_graph_se2 makes for this graph (max_rows: sgo_opts.direct_rows;
+ *   <= 0: its default), on the host alone -- no GPU is touched.  Same convention as sgo_debug_amg_array: returns the table's size in
+ *   bytes (0: it has no entries) and copies it when cap_bytes holds it.  SGO_ENOTHING when the graph does not qualify, with the
+ *   reason sgo_solver_description gives after "direct path not used: " in sgo_last_error(NULL).  Tables: SGO_DR_INFO .. SGO_DR_DPAIR,
+ *   each exactly the array that is uploaded.
+ * sgo_debug_direct_array: the same tables read back from the device, and what the last sgo_optimize_gn left -- device memory as
+ *   stored, nothing recomputed.  SGO_EINVAL with a message when the resident graph is not on the direct path
+ *   (sgo_solver_description does not start with direct_ldlt) or no sgo_optimize_gn with iters > 0 has run on it.
+ *   ESCR, ZSC, WD, WO are the kernel's own work arrays and are there after every call (the closing chi2 pass writes none of them;
+ *   sgo_optimize_gn_until leaves its last iteration's, sgo_optimize_gn_hypotheses works on copies of its own).  The snapshots A_*,
+ *   F_*, D_*, X exist only in a DEBUG RUN: the environment variable SGO_DIRECT_DEBUG set when the graph is set makes
+ *   sgo_optimize_gn launch an instantiation of the same kernel that copies out, in every iteration, the state that otherwise lives
+ *   and dies in the LDS, so that they hold the LAST iteration that ran; outside a debug run (and after an sgo_optimize_gn_until,
+ *   which has no such instantiation) each returns 0 bytes.  A debug run leaves the poses, the history and ESCR / WD / WO bit for
+ *   bit as the production kernel does.
+ * `what` is one of SGO_DR_* (positions are ELIMINATION positions 0 .. n: the nI poses of the sparse levels, then the ns separators):
+ *   INFO         int64[13] { free poses n, sparse columns nI, separators ns, levels NL, edges E, slots NB, doubles of the packed
+ *                separator triangle tri = 3 ns (3 ns + 1) / 2, zero slots, multi-edge pairs, forward tasks, contributions, bytes of
+ *                dynamic LDS, 1 when the vector lives in global memory (the XG instantiations) } (the host's sizes)
+ *   POS_VERTEX   int32[n]: the vertex at every position
+ *   VREC         int32[n][4]: the incident (edge << 1 | side) of a position, -1: none; [3] <= -2: more at VOVER[-2 - [3]]
+ *   VOVER        int32: the overflow lists, each { count, entries }
+ *   EDGE_TGT     uint32[max(E, 1)]: where an edge's H_ij goes: kind << 30 | transposed << 29 | index; kind 0 nowhere (a fixed
+ *                endpoint), 1 slot `index`, 2 separator block (row << 12 | column), 3 a pair with several edges (see MULTI)
+ *   ZERO_SLOTS   int32: the slots that are pure fill (cleared before every factorisation)
+ *   MULTI        int32[pairs][2] { target as EDGE_TGT's (kind 1 / 2, no transposed bit), first edge << 1 | transposed }; ENEXT
+ *                int32[max(E, 1)]: the next edge of the same pair in that encoding, -1: the last
+ *   SLOT_RC      int32[NB][2] { row position (-1: the dummy slot of an empty column), column position (-1: padding) }
+ *   LMETA        int32[2 (NL + 1)]: the slot range (multiples of 64) and then the task range of every level
+ *   TK           int32[tasks][4] { kind << 28 | index, first contribution, end, 0 }: kind 0 slot, 1 diagonal block of a sparse
+ *                column (with its right-hand side), 2 separator block (row << 12 | column; a diagonal one with its right-hand side)
+ *   CTR          int32[contributions][4] { slot of W_ik, slot of W_jk, k, 0 }
+ *   DPAIR        uint16[ns (ns + 1) / 2]: separator block pairs bi << 8 | bj, bi >= bj, by bj descending
+ *   ESCR         double[27][E]: per edge Hii (6, upper triangle by rows), bi (3), Hjj (6), bj (3) and -- only for the edges of
+ *                multi pairs, the rest is never written -- Hij (9, by rows)
+ *   ZSC          double[2][E]: sin and cos of the inverse measurement's angle
+ *   WD           double[nI][10], WO double[NB][10]: the diagonal and the stored blocks after the forward levels (9 by rows, one pad)
+ *   A_WD A_WO    the same two after the assembly barrier;  A_SD double[tri] the packed lower triangle of the separator block,
+ *                A_XB double[3 n] the right-hand side by position, at that point
+ *   F_SD F_XB    after the last forward level
+ *   D_SD         after the dense elimination: block column p below the diagonal holds W_ip (the panel stays); the diagonal blocks
+ *                of pivots >= 1 are NOT the pivots (only their factor is kept);  D_PINV double[ns][6] { l10, l20, l21, 1 / p0,
+ *                1 / p1, 1 / p2 } of every pivot block D = L diag(p) L^T;  D_BS double[3 ns] the separators' forward-substituted
+ *                right-hand side
+ *   X            double[3 n]: the step by position, after the backward levels */
+#define SGO_DR_INFO 0
+#define SGO_DR_POS_VERTEX 1
+#define SGO_DR_VREC 2
+#define SGO_DR_VOVER 3
+#define SGO_DR_EDGE_TGT 4
+#define SGO_DR_ZERO_SLOTS 5
+#define SGO_DR_MULTI 6
+#define SGO_DR_ENEXT 7
+#define SGO_DR_SLOT_RC 8
+#define SGO_DR_LMETA 9
+#define SGO_DR_TK 10
+#define SGO_DR_CTR 11
+#define SGO_DR_DPAIR 12
+#define SGO_DR_ESCR 13
+#define SGO_DR_ZSC 14
+#define SGO_DR_WD 15
+#define SGO_DR_WO 16
+#define SGO_DR_A_WD 17
+#define SGO_DR_A_WO 18
+#define SGO_DR_A_SD 19
+#define SGO_DR_A_XB 20
+#define SGO_DR_F_SD 21
+#define SGO_DR_F_XB 22
+#define SGO_DR_D_SD 23
+#define SGO_DR_D_PINV 24
+#define SGO_DR_D_BS 25
+#define SGO_DR_X 26
+int64_t sgo_direct_plan_array(int32_t V, const uint8_t* fixed, int32_t E, const int32_t* ei, const int32_t* ej, int32_t max_rows,
+                              int32_t what, void* out, int64_t cap_bytes);
+int64_t sgo_debug_direct_array(sgo_ctx* ctx, int32_t what, void* out, int64_t cap_bytes);
 /* Test hooks for the PCG recurrence (tests/pcg_reference.py checks every stage of one iteration and of the start from them).
  * Both need sgo_linearize and refuse a multi-GPU context and an active overlay, as the sibling hooks do.
  * sgo_debug_pcg_array: a read-only copy of one array of the recurrence as the last start / solve left it -- device memory as

@@ -32,6 +32,7 @@ SYMBOLS = [
     "sgo_kernel_profile_samples", "sgo_update_graph_se2", "sgo_debug_lanczos", "sgo_debug_amg_array",
     "sgo_debug_overlay_array", "sgo_debug_overlay_linearize", "sgo_debug_overlay_apply",
     "sgo_debug_mfront_array", "sgo_mfront_plan_array", "sgo_debug_pcg_array", "sgo_debug_pcg_run",
+    "sgo_direct_plan_array", "sgo_debug_direct_array",
     "sgo_set_edge_information", "sgo_gate_edges", "sgo_set_robust_kernels", "sgo_edge_robust",
     "sgo_solve_rhs", "sgo_marginals", "sgo_marginals_selected", "sgo_factor_solve", "sgo_candidate_gate",
     "sgo_gain_stop", "sgo_optimize_gn_until", "sgo_optimize_gn_hypotheses", "sgo_hypothesis_isolated_vertex",
@@ -197,6 +198,10 @@ def lib():
     L.sgo_debug_pcg_array.restype = C.c_int64
     L.sgo_debug_pcg_array.argtypes = [vp, C.c_int32, vp, C.c_int64]
     L.sgo_debug_pcg_run.argtypes = [vp, C.c_int32, d, C.c_double, C.c_int32, C.c_double]
+    L.sgo_debug_direct_array.restype = C.c_int64
+    L.sgo_debug_direct_array.argtypes = [vp, C.c_int32, vp, C.c_int64]
+    L.sgo_direct_plan_array.restype = C.c_int64
+    L.sgo_direct_plan_array.argtypes = [C.c_int32, u8, C.c_int32, i32, i32, C.c_int32, C.c_int32, vp, C.c_int64]
     L.sgo_mfront_plan_array.restype = C.c_int64
     L.sgo_mfront_plan_array.argtypes = [C.c_int32, d, u8, C.c_int32, i32, i32, C.c_int32, C.c_double, C.c_int32, vp, C.c_int64]
     L.sgo_debug_level0_bytes.restype = C.c_int64
@@ -324,6 +329,45 @@ def mfront_plan_arrays(poses, fixed, ei, ej, leaf: int = 0, max_crit_mflop: floa
         return L.sgo_mfront_plan_array(p.shape[0], _dp(p), f.ctypes.data_as(C.POINTER(C.c_uint8)), a.size, _ip(a), _ip(b), leaf,
                                        max_crit_mflop, what, out, cap)
     return {k: _mfront_fetch(k, call, lambda: L.sgo_last_error(None).decode()) for k in MFRONT_PLAN_ARRAYS}
+
+
+# SGO_DR_* of include/sgo.h: name -> (number, dtype, columns); the first thirteen are the host plan's as well
+DIRECT_ARRAYS = {"INFO": (0, np.int64, 0), "POS_VERTEX": (1, np.int32, 0), "VREC": (2, np.int32, 4), "VOVER": (3, np.int32, 0),
+                 "EDGE_TGT": (4, np.uint32, 0), "ZERO_SLOTS": (5, np.int32, 0), "MULTI": (6, np.int32, 2), "ENEXT": (7, np.int32, 0),
+                 "SLOT_RC": (8, np.int32, 2), "LMETA": (9, np.int32, 0), "TK": (10, np.int32, 4), "CTR": (11, np.int32, 4),
+                 "DPAIR": (12, np.uint16, 0), "ESCR": (13, np.float64, 0), "ZSC": (14, np.float64, 0), "WD": (15, np.float64, 10),
+                 "WO": (16, np.float64, 10), "A_WD": (17, np.float64, 10), "A_WO": (18, np.float64, 10), "A_SD": (19, np.float64, 0),
+                 "A_XB": (20, np.float64, 0), "F_SD": (21, np.float64, 0), "F_XB": (22, np.float64, 0), "D_SD": (23, np.float64, 0),
+                 "D_PINV": (24, np.float64, 6), "D_BS": (25, np.float64, 0), "X": (26, np.float64, 0)}
+DIRECT_PLAN_ARRAYS = tuple(DIRECT_ARRAYS)[:13]
+DIRECT_INFO = ("n", "nI", "ns", "NL", "E", "NB", "tri", "nzero", "nmulti", "tasks", "contributions", "lds_bytes", "xb_global")
+
+
+def _direct_fetch(name, call, err):
+    what, dtype, cols = DIRECT_ARRAYS[name]
+    size = call(what, None, 0)
+    if size < 0:
+        raise SgoError(f"{name}: rc={size}: " + err())
+    out = np.empty(size // np.dtype(dtype).itemsize, dtype=dtype)
+    if size:
+        got = call(what, out.ctypes.data_as(C.c_void_p), out.nbytes)
+        if got != size:
+            raise SgoError(f"{name}: {got} bytes after {size}: " + err())
+    return out.reshape(-1, cols) if cols else out
+
+
+def direct_plan_arrays(fixed, ei, ej, max_rows: int = 0, names=DIRECT_PLAN_ARRAYS):
+    """The host analysis of the single-launch direct path (sgo_direct_plan_array; needs no GPU): {name: array} for
+    DIRECT_PLAN_ARRAYS, the very tables sgo_set_graph_se2 uploads for this graph.  SgoError when the graph does not qualify: its
+    text ends with the reason sgo_solver_description gives."""
+    f = np.ascontiguousarray(fixed, dtype=np.uint8)
+    a = np.ascontiguousarray(ei, dtype=np.int32)
+    b = np.ascontiguousarray(ej, dtype=np.int32)
+    L = lib()
+
+    def call(what, out, cap):
+        return L.sgo_direct_plan_array(f.size, f.ctypes.data_as(C.POINTER(C.c_uint8)), a.size, _ip(a), _ip(b), max_rows, what, out, cap)
+    return {k: _direct_fetch(k, call, lambda: L.sgo_last_error(None).decode()) for k in names}
 
 
 # SGO_PCG_* of include/sgo.h: name -> (number, dtype, columns); SCALARS / HOST_SCALARS / MIRROR are PcgScalars records
@@ -741,6 +785,14 @@ class Optimizer:
         candidate_gate after the forward / backward pass as flat [columns * 3 n] (all empty before the first such call), come
         only when named."""
         return {k: _mfront_fetch(k, lambda what, out, cap: lib().sgo_debug_mfront_array(self._h, what, out, cap), self.last_error)
+                for k in names}
+
+    def direct_arrays(self, names=None):
+        """The single-launch direct path's tables as the device holds them and what the last optimize() left
+        (sgo_debug_direct_array); the snapshots A_*, F_*, D_*, X are empty outside a debug run (SGO_DIRECT_DEBUG set when the graph
+        was set).  names=None: all of DIRECT_ARRAYS."""
+        names = tuple(DIRECT_ARRAYS) if names is None else names
+        return {k: _direct_fetch(k, lambda what, out, cap: lib().sgo_debug_direct_array(self._h, what, out, cap), self.last_error)
                 for k in names}
 
     def solver_description(self) -> str:

@@ -1569,6 +1569,27 @@ int64_t sgo_debug_mfront_array(sgo_ctx* c, int32_t what, void* out, int64_t cap_
   } SGO_CATCH(c)
 }
 
+// Test hook for the single-launch direct path (include/sgo.h): the plan tables and k_direct's arrays as stored (direct_debug_array).
+int64_t sgo_debug_direct_array(sgo_ctx* c, int32_t what, void* out, int64_t cap_bytes) {
+  try {
+    int rc = check_graph(c);
+    if (rc) return rc;
+    if (!c->direct) {
+      c->err = "sgo_debug_direct_array: the resident graph is not on the direct path (" + c->solver_desc.substr(0, c->solver_desc.find(':')) + ")";
+      return SGO_EINVAL;
+    }
+    if (cap_bytes < 0 || (cap_bytes > 0 && !out)) return SGO_EINVAL;
+    const long long r = direct_debug_array(c->direct, c->stream, what, out, cap_bytes);
+    if (r == SGO_ENOTHING) {
+      c->err = "sgo_debug_direct_array: no sgo_optimize_gn has run on the resident graph";
+      return SGO_EINVAL;
+    }
+    if (r == SGO_EINVAL) c->err = "sgo_debug_direct_array: unknown array";
+    if (r == SGO_EHIP) c->err = "sgo_debug_direct_array: device copy failed";
+    return r;
+  } SGO_CATCH(c)
+}
+
 // Diagnostic (env SGO_LANCZOS=1 at sgo_set_graph_se2): alpha / beta of every PCG iteration of the last solve, pairs in
 // iteration order; returns the number of iterations written (the Lanczos matrix of the preconditioned operator follows
 // from them: scripts/ritz_probe.py), < 0 on error.

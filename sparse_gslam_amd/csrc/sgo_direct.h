@@ -39,7 +39,7 @@ struct DirectResult {
                                                      // iteration k the call ends at [2k + 2]
 };
 
-// Host analysis + upload.  nullptr with *why set: the graph does not qualify (too many separators / levels /
+// Host analysis, then the upload of what it made.  nullptr with *why set: the graph does not qualify (too many separators / levels /
 // rows; the caller uses the multigrid path); nullptr with *err set: HIP failure.
 Direct* direct_create(hipStream_t s, DevArena* arena, int V, int n, const int* free_id, int E, const int* ei, const int* ej,
                       int max_rows, std::string* why, std::string* err);
@@ -68,6 +68,12 @@ struct DirectBatchLayout {
 DirectBatchLayout direct_batch_layout(const Direct* d, int V, int B, int iters);
 hipError_t direct_optimize_batch(Direct* d, hipStream_t s, const EdgeListDev& el, const double* d_poses_res, bool own_poses,
                                  const DirectBatchLayout& L, char* ws, int iters, double gain_tol, bool want_edge_chi2);
+// Test hooks (include/sgo.h, SGO_DR_*; size-query convention of the other hooks).  direct_plan_array: one table of the host
+// analysis alone -- no stream, no arena; SGO_ENOTHING with *why set when the graph does not qualify.  direct_debug_array: the
+// same tables read back from the device and what the last direct_optimize left; SGO_ENOTHING before the first with iters > 0.
+long long direct_plan_array(int V, int n, const int* free_id, int E, const int* ei, const int* ej, int max_rows, int what, void* out,
+                            long long cap_bytes, std::string* why);
+long long direct_debug_array(const Direct* d, hipStream_t s, int what, void* out, long long cap_bytes);
 // algorithmic bytes of one call (profile table)
 double direct_bytes(const Direct* d, int E, int iters);
 

@@ -27,6 +27,7 @@
 #include <algorithm>
 #include <memory>
 #include <atomic>
+#include <cstdlib>
 #include <cstring>
 #include <numeric>
 #include <type_traits>
@@ -84,6 +85,13 @@ struct DirectBatch {
   int2* brief;              // [B] {updates applied, failure code}: what the host reads of a hypothesis' DirectResult
 };
 struct DirectSingle {};     // the dim3(1) instantiations take nothing
+// The DUMP instantiations (a debug run, sgo_debug_direct_array): where the snapshots of an iteration's LDS-resident state go.
+struct DirectDump {
+  double *a_wd, *a_wo, *a_sd, *a_xb;   // after the assembly barrier: Wd [nI][10], Wo [NB][10], the separator triangle [tri], xb [3 n]
+  double *f_sd, *f_xb;                 // after the last forward level
+  double *d_sd, *d_pinv, *d_bs;        // after the dense elimination: the triangle (W panels), the pivot factors [ns][6], bs [3 ns]
+  double *x;                           // after the backward levels: the step by elimination position [3 n]
+};
 
 // 1 / x by the hardware reciprocal + two Newton steps (the IEEE division sequence is 3x longer and sits on the
 // critical path of every pivot)
@@ -317,10 +325,14 @@ constexpr int kPF = 1;   // forward tasks per thread whose records are fetched o
 // UNTIL: sgo_optimize_gn_until -- the call ends before the first iteration at which rules::gain_stop holds for gain_tol (thread 0
 // decides from the two sums it holds, the workgroup leaves the loop together); the plain instantiations never read gain_tol.
 // BATCH: one workgroup per hypothesis (DirectBatch above); always with UNTIL, whose gain_tol <= 0 never stops.
-template <bool XG, bool KINDS, bool UNTIL, bool BATCH = false>
+// DUMP: a debug run (SGO_DIRECT_DEBUG at set-up; plain instantiations only): every iteration copies the state that otherwise lives
+// and dies in the LDS to DirectDump's arrays at four points, so that the last iteration that ran can be checked stage by stage
+// (tests/direct_reference.py).  Everything it adds is under `if constexpr (DUMP)`: the other instantiations compile as without it.
+template <bool XG, bool KINDS, bool UNTIL, bool BATCH = false, bool DUMP = false>
 __global__ __launch_bounds__(kDT) void k_direct(DirectDev D, EdgeListDev el, double* __restrict__ poses, int iters,
                                                 double* __restrict__ hist, DirectResult* __restrict__ res, double gain_tol,
-                                                std::conditional_t<BATCH, DirectBatch, DirectSingle> bt) {
+                                                std::conditional_t<BATCH, DirectBatch, std::conditional_t<DUMP, DirectDump, DirectSingle>> bt) {
+  static_assert(!DUMP || (!UNTIL && !BATCH), "the snapshots exist for the plain instantiations only");
   extern __shared__ double lds[];
   if constexpr (BATCH) {
     const size_t b = blockIdx.x;
@@ -506,6 +518,13 @@ __global__ __launch_bounds__(kDT) void k_direct(DirectDev D, EdgeListDev el, dou
       store_offdiag(D, Sd, (unsigned)m.x, b);
     }
     __syncthreads();
+    if constexpr (DUMP) {   // the assembled system, before any Schur update touches it
+      for (int k = tid; k < kBS * nI; k += kDT) bt.a_wd[k] = D.Wd[k];
+      for (int k = tid; k < kBS * D.NB; k += kDT) bt.a_wo[k] = D.Wo[k];
+      for (int k = tid; k < D.tri; k += kDT) bt.a_sd[k] = Sd[k];
+      for (int k = tid; k < 3 * n; k += kDT) bt.a_xb[k] = xb[k];
+      __syncthreads();
+    }
     if (tid == 0) res->phase[2] = res->stamp[2 * it + 1] = (unsigned long long)wall_clock64();
     // ---- sparse levels, forward: Schur updates and right-hand sides of the level's columns
     for (int l = 0; l < NL; ++l) {
@@ -525,6 +544,10 @@ __global__ __launch_bounds__(kDT) void k_direct(DirectDev D, EdgeListDev el, dou
         run_task(D, xb, Sd, tk, D.ctr[tk.y]);
       }
       __syncthreads();
+    }
+    if constexpr (DUMP) {   // (nothing writes Sd or xb between the last level's barrier and the one after the first pivot's factor)
+      for (int k = tid; k < D.tri; k += kDT) bt.f_sd[k] = Sd[k];
+      for (int k = tid; k < 3 * n; k += kDT) bt.f_xb[k] = xb[k];
     }
     if (tid == 0) res->phase[3] = (unsigned long long)wall_clock64();
     // ---- separators: right-looking block LDL^T on the packed triangle, 3x3 pivots, W form (the panel stays);
@@ -638,6 +661,11 @@ __global__ __launch_bounds__(kDT) void k_direct(DirectDev D, EdgeListDev el, dou
       }
       __syncthreads();
     }
+    if constexpr (DUMP) {   // (the back substitution below reads these three and writes xb alone)
+      for (int k = tid; k < D.tri; k += kDT) bt.d_sd[k] = Sd[k];
+      for (int k = tid; k < 6 * ns; k += kDT) bt.d_pinv[k] = pinv[k];
+      for (int k = tid; k < 3 * ns; k += kDT) bt.d_bs[k] = bs[k];
+    }
     if (tid == 0) res->phase[4] = (unsigned long long)wall_clock64();
     // back substitution of the separators by ONE wave, column oriented: lane p owns b_p; step i: x_i = D_i^-1 b_i is
     // broadcast from lane i and every lane p < i takes W_ip^T x_i off its b_p.  No barriers, no reductions.
@@ -716,6 +744,9 @@ __global__ __launch_bounds__(kDT) void k_direct(DirectDev D, EdgeListDev el, dou
       }
       __syncthreads();
     }
+    if constexpr (DUMP) {   // (xb is final: the update reads it)
+      for (int k = tid; k < 3 * n; k += kDT) bt.x[k] = xb[k];
+    }
     if (tid == 0) res->phase[6] = (unsigned long long)wall_clock64();
     // ---- update (VertexSE2::oplusImpl) unless the factorisation failed or the step is not finite
     bool bad = false;
@@ -780,17 +811,29 @@ __global__ __launch_bounds__(256) void k_hyp_prepare(int B, int E, int V3, const
 // ------------------------------------------------------------------------------------------------ host
 }  // namespace
 
-struct Direct {
-  DirectDev dev{};
-  DirectInfo info{};
-  // host copies of the uploaded lists must outlive the asynchronous copies
+// What the host analysis makes of a graph (direct_analyze): sizes and the lists the kernel works from.  No device involved.
+struct DirectPlan {
+  int n = 0, nI = 0, ns = 0, NL = 0, E = 0, NB = 0, tri = 0;
+  long long contributions = 0;
+  size_t lds_bytes = 0;
+  bool xb_global = false;
   std::vector<int> h_pos_vertex, h_vover, h_zero, h_enext, h_lmeta;
   std::vector<int4> h_vrec, h_tk, h_ctr;
   std::vector<int2> h_multi, h_slot_rc;
   std::vector<unsigned> h_edge_tgt;
   std::vector<unsigned short> h_dpair;
+};
+
+struct Direct {
+  DirectDev dev{};
+  DirectInfo info{};
+  DirectPlan plan;            // (the uploaded lists' sizes; sgo_debug_direct_array reads the device copies back by them)
   std::vector<char> h_blob;   // what is uploaded: must outlive the asynchronous copy
   bool xb_global = false;
+  bool debug = false;         // SGO_DIRECT_DEBUG at set-up: sgo_optimize_gn launches the DUMP instantiations
+  DirectDump dump{};
+  bool ran = false;           // a direct_optimize with iters > 0 has run
+  bool dumped = false;        // ... and the last one was a DUMP launch
 };
 
 const DirectInfo& direct_info(const Direct* d) { return d->info; }
@@ -801,11 +844,13 @@ double direct_bytes(const Direct* d, int E, int iters) {
   return (double)iters * (96.0 * E + 2.0 * 216.0 * E + 2.0 * 72.0 * (d->info.slots + d->info.n_chain) + 72.0 * d->info.n);
 }
 
-Direct* direct_create(hipStream_t s, DevArena* arena, int V, int n, const int* free_id, int E, const int* ei, const int* ej,
-                      int max_rows, std::string* why, std::string* err) {
-  auto no = [&](const char* w) -> Direct* {
+// The host analysis: elimination order, symbolic factorisation, the assembly and gather lists.  false with *why set: the graph
+// does not qualify.
+static bool direct_analyze(int V, int n, const int* free_id, int E, const int* ei, const int* ej, int max_rows, DirectPlan* d,
+                           std::string* why) {
+  auto no = [&](const char* w) -> bool {
     *why = w;
-    return nullptr;
+    return false;
   };
   if (n <= 0) return no("no free pose");
   if (n > max_rows) return no("more free poses than direct_rows");
@@ -930,8 +975,6 @@ Direct* direct_create(hipStream_t s, DevArena* arena, int V, int n, const int* f
   const size_t lds_bytes = lds_fixed + (xb_global ? 0 : sizeof(double) * 3 * (size_t)n);
   if (lds_bytes > kLdsBudget) return no("separator block exceeds the LDS");
 
-  std::unique_ptr<Direct> owner(new Direct());   // released to the caller at the end: a throwing std::vector below frees it
-  Direct* d = owner.get();
   std::vector<std::vector<int>> lcols((size_t)NL);
   for (int k = 0; k < nI; ++k) lcols[level[k]].push_back(k);
   // ---- slots: per level, per column (ascending), a column's blocks inside one wave
@@ -1099,14 +1142,29 @@ Direct* direct_create(hipStream_t s, DevArena* arena, int V, int n, const int* f
   // ---- dense pair table: bj descending so that the trailing blocks of pivot p are a prefix
   for (int bj = ns - 1; bj >= 0; --bj)
     for (int bi = bj; bi < ns; ++bi) d->h_dpair.push_back((unsigned short)(bi << 8 | bj));
+  d->n = n; d->nI = nI; d->ns = ns; d->NL = NL; d->E = E; d->NB = NB; d->tri = tri;
+  d->contributions = total_contrib;
+  d->lds_bytes = lds_bytes;
+  d->xb_global = xb_global;
+  return true;
+}
 
+// The upload: the analysis' lists as one blob, the kernel's work arrays, the LDS limit of the instantiations.
+Direct* direct_create(hipStream_t s, DevArena* arena, int V, int n, const int* free_id, int E, const int* ei, const int* ej,
+                      int max_rows, std::string* why, std::string* err) {
+  std::unique_ptr<Direct> owner(new Direct());   // released to the caller at the end
+  if (!direct_analyze(V, n, free_id, E, ei, ej, max_rows, &owner->plan, why)) return nullptr;
+  Direct* const dd = owner.get();
+  DirectPlan* const d = &dd->plan;
+  const int nI = d->nI, NB = d->NB;
+  const bool xb_global = d->xb_global;
   hipError_t e = hipSuccess;
-  DirectDev& D = d->dev;
-  D.n = n; D.nI = nI; D.ns = ns; D.NL = NL; D.E = E; D.NB = NB; D.tri = tri;
+  DirectDev& D = dd->dev;
+  D.n = n; D.nI = nI; D.ns = d->ns; D.NL = d->NL; D.E = E; D.NB = NB; D.tri = d->tri;
   D.nzero = (int)d->h_zero.size();
   D.nmulti = (int)d->h_multi.size();
   {   // all lists in ONE host blob, one allocation, one copy (a dozen small pageable copies cost 0.1 ms)
-    std::vector<char>& blob = d->h_blob;
+    std::vector<char>& blob = dd->h_blob;
     size_t off[12], total = 0;
     int q = 0;
     auto put = [&](const void* src, size_t bytes) {
@@ -1152,8 +1210,25 @@ Direct* direct_create(hipStream_t s, DevArena* arena, int V, int n, const int* f
   D.zsc = (double*)arena->take(sizeof(double) * 2 * (size_t)std::max(E, 1));
   D.xbg = xb_global ? (double*)arena->take(sizeof(double) * 3 * (size_t)n) : nullptr;
   if (xb_global && !D.xbg && e == hipSuccess) e = hipErrorOutOfMemory;
-  d->xb_global = xb_global;
+  dd->xb_global = xb_global;
   if (e == hipSuccess && (!D.Wd || !D.Wo || !D.escr || !D.zsc)) e = hipErrorOutOfMemory;
+  dd->debug = std::getenv("SGO_DIRECT_DEBUG") != nullptr;
+  if (dd->debug && e == hipSuccess) {   // the snapshots of a debug run, one allocation
+    const size_t wd = kBS * (size_t)nI, wo = kBS * (size_t)NB, tr = (size_t)D.tri, n3 = 3 * (size_t)n, ns6 = 6 * (size_t)D.ns, ns3 = 3 * (size_t)D.ns;
+    double* p = (double*)arena->take(sizeof(double) * std::max<size_t>(wd + wo + 3 * tr + 3 * n3 + ns6 + ns3, 2));
+    if (!p) e = hipErrorOutOfMemory;
+    DirectDump& U = dd->dump;
+    U.a_wd = p; p += wd;
+    U.a_wo = p; p += wo;
+    U.a_sd = p; p += tr;
+    U.a_xb = p; p += n3;
+    U.f_sd = p; p += tr;
+    U.f_xb = p; p += n3;
+    U.d_sd = p; p += tr;
+    U.d_pinv = p; p += ns6;
+    U.d_bs = p; p += ns3;
+    U.x = p;
+  }
   static std::atomic<unsigned long long> attr_devices{0};   // devices on which the LDS limit of the two kernels is raised
   int dev_id = 0;
   hipGetDevice(&dev_id);
@@ -1161,13 +1236,15 @@ Direct* direct_create(hipStream_t s, DevArena* arena, int V, int n, const int* f
   const bool attr_set_already = (attr_devices.load() & dev_bit) != 0;
   bool attr_set = attr_set_already;
   if (e == hipSuccess && !attr_set) {
-    const void* const variants[12] = {reinterpret_cast<const void*>(&k_direct<false, false, false>), reinterpret_cast<const void*>(&k_direct<true, false, false>),
+    const void* const variants[16] = {reinterpret_cast<const void*>(&k_direct<false, false, false>), reinterpret_cast<const void*>(&k_direct<true, false, false>),
                                      reinterpret_cast<const void*>(&k_direct<false, true, false>), reinterpret_cast<const void*>(&k_direct<true, true, false>),
                                      reinterpret_cast<const void*>(&k_direct<false, false, true>), reinterpret_cast<const void*>(&k_direct<true, false, true>),
                                      reinterpret_cast<const void*>(&k_direct<false, true, true>), reinterpret_cast<const void*>(&k_direct<true, true, true>),
                                      reinterpret_cast<const void*>(&k_direct<false, false, true, true>), reinterpret_cast<const void*>(&k_direct<true, false, true, true>),
-                                     reinterpret_cast<const void*>(&k_direct<false, true, true, true>), reinterpret_cast<const void*>(&k_direct<true, true, true, true>)};
-    for (int v = 0; v < 12 && e == hipSuccess; ++v)
+                                     reinterpret_cast<const void*>(&k_direct<false, true, true, true>), reinterpret_cast<const void*>(&k_direct<true, true, true, true>),
+                                     reinterpret_cast<const void*>(&k_direct<false, false, false, false, true>), reinterpret_cast<const void*>(&k_direct<true, false, false, false, true>),
+                                     reinterpret_cast<const void*>(&k_direct<false, true, false, false, true>), reinterpret_cast<const void*>(&k_direct<true, true, false, false, true>)};
+    for (int v = 0; v < 16 && e == hipSuccess; ++v)
       e = hipFuncSetAttribute(variants[v], hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBudget);
     attr_set = e == hipSuccess;
     if (attr_set) attr_devices.fetch_or(dev_bit);
@@ -1176,13 +1253,13 @@ Direct* direct_create(hipStream_t s, DevArena* arena, int V, int n, const int* f
     *err = std::string("direct_create: ") + hipGetErrorString(e);
     return nullptr;
   }
-  d->info.n = n;
-  d->info.n_chain = nI;
-  d->info.n_sep = ns;
-  d->info.levels = NL;
-  d->info.slots = NB;
-  d->info.contributions = (int)total_contrib;
-  d->info.lds_bytes = lds_bytes;
+  dd->info.n = n;
+  dd->info.n_chain = nI;
+  dd->info.n_sep = d->ns;
+  dd->info.levels = d->NL;
+  dd->info.slots = NB;
+  dd->info.contributions = (int)d->contributions;
+  dd->info.lds_bytes = d->lds_bytes;
   return owner.release();
 }
 
@@ -1191,7 +1268,20 @@ hipError_t direct_optimize(Direct* d, hipStream_t s, const EdgeListDev& el, doub
                            DirectResult* d_res, const double* until) {
 #define SGO_DIRECT_LAUNCH(XG, KINDS, UNTIL, tol) \
   SGO_LAUNCH((k_direct<XG, KINDS, UNTIL>), dim3(1), dim3(kDT), d->info.lds_bytes, s, d->dev, el, d_poses, iters, d_hist, d_res, tol, DirectSingle{})
-  if (until) {
+  if (iters > 0) {
+    d->ran = true;
+    d->dumped = d->debug && !until;
+  }
+  if (d->debug && !until) {
+#define SGO_DIRECT_DUMP(XG, KINDS) \
+  SGO_LAUNCH((k_direct<XG, KINDS, false, false, true>), dim3(1), dim3(kDT), d->info.lds_bytes, s, d->dev, el, d_poses, iters, d_hist, d_res, 0.0, d->dump)
+    if (el.kinds) {
+      if (d->xb_global) SGO_DIRECT_DUMP(true, true);
+      else SGO_DIRECT_DUMP(false, true);
+    } else if (d->xb_global) SGO_DIRECT_DUMP(true, false);
+    else SGO_DIRECT_DUMP(false, false);
+#undef SGO_DIRECT_DUMP
+  } else if (until) {
     if (el.kinds) {
       if (d->xb_global) SGO_DIRECT_LAUNCH(true, true, true, *until);
       else SGO_DIRECT_LAUNCH(false, true, true, *until);
@@ -1276,6 +1366,109 @@ hipError_t direct_optimize_batch(Direct* d, hipStream_t s, const EdgeListDev& el
   else SGO_DIRECT_BATCH(false, false);
 #undef SGO_DIRECT_BATCH
   return hipGetLastError();
+}
+
+// ---- the test hooks' tables (include/sgo.h, SGO_DR_*)
+static long long direct_info_row(const DirectPlan& P, long long* row) {
+  const long long v[13] = {P.n, P.nI, P.ns, P.NL, P.E, P.NB, P.tri, (long long)P.h_zero.size(), (long long)P.h_multi.size(),
+                           (long long)P.h_tk.size(), P.contributions, (long long)P.lds_bytes, P.xb_global ? 1 : 0};
+  std::copy(v, v + 13, row);
+  return 13 * (long long)sizeof(long long);
+}
+// host pointer and bytes of plan table `what` (SGO_DR_POS_VERTEX .. SGO_DR_DPAIR); false: not a plan table
+static bool direct_plan_table(const DirectPlan& P, int what, const void** src, long long* bytes) {
+#define SGO_T(vec) \
+  *src = (vec).data(); \
+  *bytes = (long long)(sizeof((vec)[0]) * (vec).size()); \
+  return true
+  switch (what) {
+    case SGO_DR_POS_VERTEX: SGO_T(P.h_pos_vertex);
+    case SGO_DR_VREC: SGO_T(P.h_vrec);
+    case SGO_DR_VOVER: SGO_T(P.h_vover);
+    case SGO_DR_EDGE_TGT: SGO_T(P.h_edge_tgt);
+    case SGO_DR_ZERO_SLOTS: SGO_T(P.h_zero);
+    case SGO_DR_MULTI: SGO_T(P.h_multi);
+    case SGO_DR_ENEXT: SGO_T(P.h_enext);
+    case SGO_DR_SLOT_RC: SGO_T(P.h_slot_rc);
+    case SGO_DR_LMETA: SGO_T(P.h_lmeta);
+    case SGO_DR_TK: SGO_T(P.h_tk);
+    case SGO_DR_CTR: SGO_T(P.h_ctr);
+    case SGO_DR_DPAIR: SGO_T(P.h_dpair);
+    default: return false;
+  }
+#undef SGO_T
+}
+
+long long direct_plan_array(int V, int n, const int* free_id, int E, const int* ei, const int* ej, int max_rows, int what, void* out,
+                            long long cap_bytes, std::string* why) {
+  DirectPlan P;
+  if (!direct_analyze(V, n, free_id, E, ei, ej, max_rows, &P, why)) return SGO_ENOTHING;
+  const void* src = nullptr;
+  long long bytes = 0, info[13];
+  if (what == SGO_DR_INFO) {
+    bytes = direct_info_row(P, info);
+    src = info;
+  } else if (!direct_plan_table(P, what, &src, &bytes)) {
+    return SGO_EINVAL;
+  }
+  if (bytes == 0 || cap_bytes < bytes) return bytes;
+  std::memcpy(out, src, (size_t)bytes);
+  return bytes;
+}
+
+// The device's copies as stored (INFO alone has none: the kernel takes the sizes by value).
+long long direct_debug_array(const Direct* d, hipStream_t s, int what, void* out, long long cap_bytes) {
+  if (!d->ran) return SGO_ENOTHING;
+  const DirectPlan& P = d->plan;
+  const DirectDev& D = d->dev;
+  const long long F = sizeof(double), tri = F * D.tri, n3 = F * 3 * (long long)D.n;
+  const void* src = nullptr;
+  long long bytes = 0;
+  if (what == SGO_DR_INFO) {
+    long long info[13];
+    bytes = direct_info_row(P, info);
+    if (cap_bytes >= bytes) std::memcpy(out, info, (size_t)bytes);
+    return bytes;
+  }
+  if (direct_plan_table(P, what, &src, &bytes)) {
+    switch (what) {   // the same bytes from where the kernel reads them
+      case SGO_DR_POS_VERTEX: src = D.pos_vertex; break;
+      case SGO_DR_VREC: src = D.vrec; break;
+      case SGO_DR_VOVER: src = D.vover; break;
+      case SGO_DR_EDGE_TGT: src = D.edge_tgt; break;
+      case SGO_DR_ZERO_SLOTS: src = D.zero_slots; break;
+      case SGO_DR_MULTI: src = D.multi; break;
+      case SGO_DR_ENEXT: src = D.enext; break;
+      case SGO_DR_SLOT_RC: src = D.slot_rc; break;
+      case SGO_DR_LMETA: src = D.lmeta; break;
+      case SGO_DR_TK: src = D.tk; break;
+      case SGO_DR_CTR: src = D.ctr; break;
+      default: src = D.dpair; break;
+    }
+  } else {
+    const bool dm = d->dumped;
+    const DirectDump& U = d->dump;
+    switch (what) {
+      case SGO_DR_ESCR: src = D.escr; bytes = F * 27 * D.E; break;
+      case SGO_DR_ZSC: src = D.zsc; bytes = F * 2 * D.E; break;
+      case SGO_DR_WD: src = D.Wd; bytes = F * kBS * D.nI; break;
+      case SGO_DR_WO: src = D.Wo; bytes = F * kBS * D.NB; break;
+      case SGO_DR_A_WD: src = U.a_wd; bytes = dm ? F * kBS * D.nI : 0; break;
+      case SGO_DR_A_WO: src = U.a_wo; bytes = dm ? F * kBS * D.NB : 0; break;
+      case SGO_DR_A_SD: src = U.a_sd; bytes = dm ? tri : 0; break;
+      case SGO_DR_A_XB: src = U.a_xb; bytes = dm ? n3 : 0; break;
+      case SGO_DR_F_SD: src = U.f_sd; bytes = dm ? tri : 0; break;
+      case SGO_DR_F_XB: src = U.f_xb; bytes = dm ? n3 : 0; break;
+      case SGO_DR_D_SD: src = U.d_sd; bytes = dm ? tri : 0; break;
+      case SGO_DR_D_PINV: src = U.d_pinv; bytes = dm ? F * 6 * D.ns : 0; break;
+      case SGO_DR_D_BS: src = U.d_bs; bytes = dm ? F * 3 * D.ns : 0; break;
+      case SGO_DR_X: src = U.x; bytes = dm ? n3 : 0; break;
+      default: return SGO_EINVAL;
+    }
+  }
+  if (bytes == 0 || cap_bytes < bytes) return bytes;
+  if (hipMemcpyAsync(out, src, (size_t)bytes, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) return SGO_EHIP;
+  return bytes;
 }
 
 }  // namespace sgo

@@ -622,6 +622,37 @@ int64_t sgo_mfront_plan_array(int32_t V, const double* poses, const uint8_t* fix
   }
 }
 
+int64_t sgo_direct_plan_array(int32_t V, const uint8_t* fixed, int32_t E, const int32_t* ei, const int32_t* ej, int32_t max_rows,
+                              int32_t what, void* out, int64_t cap_bytes) {
+  if (V <= 0 || E < 0 || !fixed || (E > 0 && (!ei || !ej)) || cap_bytes < 0 || (cap_bytes > 0 && !out)) return SGO_EINVAL;
+  try {
+    std::vector<int> deg((size_t)V, 0), free_id;
+    for (int e = 0; e < E; ++e) {
+      if (ei[e] < 0 || ei[e] >= V || ej[e] < 0 || ej[e] >= V) {
+        g_err = "sgo_direct_plan_array: bad edge " + std::to_string(e);
+        return SGO_EINVAL;
+      }
+      deg[ei[e]]++;
+      deg[ej[e]]++;
+    }
+    for (int v = 0; v < V; ++v)
+      if (!fixed[v] && deg[v] > 0) free_id.push_back(v);
+    if (max_rows <= 0) {
+      sgo_opts o;
+      sgo_default_opts(&o);
+      max_rows = o.direct_rows;
+    }
+    std::string why;
+    const long long r = direct_plan_array(V, (int)free_id.size(), free_id.data(), E, ei, ej, max_rows, what, out, cap_bytes, &why);
+    if (r == SGO_ENOTHING) g_err = why;
+    if (r == SGO_EINVAL) g_err = "sgo_direct_plan_array: not a table of the plan";
+    return r;
+  } catch (const std::bad_alloc&) {
+    g_err = "sgo_direct_plan_array: out of host memory";
+    return SGO_ENOMEM;
+  }
+}
+
 void sgo_shard_range(int32_t count, int32_t nranks, int32_t rank, int32_t* begin, int32_t* end) {
   if (nranks < 1) nranks = 1;
   if (rank < 0) rank = 0;

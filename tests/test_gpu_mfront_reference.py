@@ -60,7 +60,8 @@ def test_hook_refuses_a_graph_on_another_path():
 
 @pytest.mark.parametrize("V,closures,seed", [(2, 0, 1), (3, 1, 2), (17, 2, 3), (64, 5, 4), (65, 0, 5), (300, 10, 6)])
 def test_direct_step_meets_the_composed_bound(V, closures, seed):
-    """k_direct has no stage export: its step x = P1 (-) P0 after optimize(1), on test_gpu_direct.py's size ladder, held to the
+    """k_direct's step from the poses alone (its stages, from sgo_debug_direct_array's export, and this residual with the kernel's
+    own factor in the last term: tests/test_gpu_direct_reference.py): x = P1 (-) P0 after optimize(1), on test_gpu_direct.py's size ladder, held to the
     composed bound of the multifrontal reference -- |b - H x| <= C U (abs(b) + abs(H x) + |L| |L^T| |x|), C the composed stage's,
     L the dense Cholesky factor of np_oracle's H in hessian order (the reference's own: the kernel's factor is not exported) --
     plus U abs(H (|P1| + 2 pi on the angles)) for having read x through the rounded poses."""
