@@ -1063,6 +1063,68 @@ class SparseOptimizer : public OptimizableGraph {
     return rc;
   }
 
+  // ---- joint compatibility of a set of candidate closures (extension; sgo_candidate_joint / sgo_joint_subsets of include/sgo.h):
+  // the candidates are EdgeSE2 objects as sgoCandidateGate takes them; subsets[b] lists the candidates (indices into `candidates`,
+  // any order, a repeated index counts once) of subset b.  (*d2)[b] = e_s^T (S_ss)^-1 e_s with the candidates' cross-covariances at
+  // the current estimates, 3 |s| degrees of freedom; chi2Max empty: no decisions (returns 0, *pass is emptied), else one bound per
+  // subset and (*pass)[b] = d2 <= chi2Max[b]; returns how many pass.  Returns -1 without touching the outputs in the situations where
+  // sgoCandidateGate does, for an index outside the candidates, for a chi2Max of another length than subsets, and when a call
+  // itself refuses (more than SGO_JOINT_MAX_CANDIDATES candidates, a subset of more than SGO_JOINT_MAX_SUBSET; one line on std::cerr).
+  int sgoCandidateJoint(const std::vector<EdgeSE2*>& candidates, const std::vector<std::vector<int>>& subsets, const std::vector<double>& chi2Max,
+                        std::vector<double>* d2, std::vector<bool>* pass) {
+    if (!_algorithm || _activeRevision != _revision || _activeVertices.empty() || !gpuEligible()) return -1;
+    const size_t n = candidates.size(), B = subsets.size();
+    if (!chi2Max.empty() && chi2Max.size() != B) return -1;
+    std::vector<int32_t> ci(n), cj(n);
+    std::vector<double> meas(3 * n), info(6 * n);
+    for (size_t t = 0; t < n; ++t) {
+      const EdgeSE2* e = candidates[t];
+      if (!e) return -1;
+      for (int side = 0; side < 2; ++side) {
+        const HyperGraph::Vertex* v = e->vertex(side);
+        if (!v) return -1;
+        auto it = std::lower_bound(_activeVertices.begin(), _activeVertices.end(), v->id(),
+                                   [](const OptimizableGraph::Vertex* a, int id) { return a->id() < id; });
+        if (it == _activeVertices.end() || *it != v) return -1;
+        (side ? cj : ci)[t] = (int32_t)(it - _activeVertices.begin());
+      }
+      for (int q = 0; q < 3; ++q) meas[3 * t + q] = e->measurement()[q];
+      const auto& O = e->information();
+      double* o = &info[6 * t];
+      o[0] = O(0, 0); o[1] = O(0, 1); o[2] = O(0, 2); o[3] = O(1, 1); o[4] = O(1, 2); o[5] = O(2, 2);
+    }
+    std::vector<uint8_t> mask(std::max<size_t>(B * n, 1), 0);
+    for (size_t b = 0; b < B; ++b)
+      for (int t : subsets[b]) {
+        if (t < 0 || (size_t)t >= n) return -1;
+        mask[b * n + (size_t)t] = 1;
+      }
+    if (!uploadGraph()) return -1;
+    int rc = sgo_candidate_joint(_ctx, (int32_t)n, ci.data(), cj.data(), meas.data(), info.data(), nullptr, nullptr);
+    std::vector<double> dd(std::max<size_t>(B, 1));
+    std::vector<uint8_t> ok(std::max<size_t>(B, 1), 0);
+    if (rc >= 0 && n > 0)
+      rc = sgo_joint_subsets(_ctx, (int32_t)n, (int32_t)B, mask.data(), chi2Max.empty() ? nullptr : chi2Max.data(), dd.data(), nullptr, ok.data());
+    else if (rc >= 0) {   // (no candidates: every subset is the empty one, d2 = 0)
+      rc = 0;
+      for (size_t b = 0; b < B; ++b) {
+        dd[b] = 0.0;
+        ok[b] = !chi2Max.empty() && 0.0 <= chi2Max[b];
+        rc += ok[b];
+      }
+    }
+    if (rc < 0) {
+      std::cerr << "SparseOptimizer::sgoCandidateJoint: " << sgo_last_error(_ctx) << std::endl;
+      return -1;
+    }
+    if (d2) d2->assign(dd.begin(), dd.begin() + B);
+    if (pass) {
+      pass->resize(chi2Max.empty() ? 0 : B);
+      for (size_t b = 0; b < pass->size(); ++b) (*pass)[b] = ok[b] != 0;
+    }
+    return rc;
+  }
+
   // ---- many closure hypotheses of the graph in one call (extension; sgo_optimize_gn_hypotheses of include/sgo.h): hypothesis b is
   // the graph without the edges of off[b], optimised from the current estimates as optimize(iters) under a
   // SparseOptimizerTerminateAction of gain threshold gainTol would (gainTol <= 0: plain optimize(iters)).  Valid after

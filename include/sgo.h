@@ -495,6 +495,47 @@ int sgo_candidate_gate(sgo_ctx* ctx, int32_t n, const int32_t* ci, const int32_t
                        double chi2_max, double* d2 /*[n], may be NULL*/, double* cov_pred /*[n][9], may be NULL*/,
                        uint8_t* pass /*[n], may be NULL*/);
 
+/* (later additions, version 107) Joint compatibility of a SET of candidate closures: sgo_candidate_gate
+ * judges every candidate alone, but the innovations of a burst of candidates that cross the same drift are correlated.  For the n
+ * stacked candidates (arguments as sgo_candidate_gate's), with R = their Jacobians' columns and H as there,
+ *   S = blockdiag(Omega_t^-1) + 1/2 (G + G^T),   G = R^T H^-1 R   (3 n x 3 n),   e = (e_1 ... e_n)
+ *   d2(s) = e_s^T (S_ss)^-1 e_s   for a subset s of the candidates: 3 |s| degrees of freedom.
+ * The diagonal blocks are sgo_candidate_gate's Omega^-1 + P; the cross blocks G_st = [A_s B_s] (H^-1 R_t)[rows of i_s, j_s] come from
+ * the same three columns per candidate (through the factor, or through the PCG where the analysis refuses the graph, under
+ * sgo_candidate_gate's rules: a failing column fails the call, candidate and residual named), so the table costs the gate plus one
+ * small product.  One triangle is computed and mirrored: S is exactly symmetric.  A fixed endpoint drops out of R; a candidate
+ * between two fixed vertices has S_tt = Omega_t^-1 and zero cross blocks; a candidate listed twice is two rows of the table.
+ *
+ * sgo_candidate_joint builds the table at the CURRENT poses, copies S and e out where asked and keeps the table in the context.
+ * Returns n.  The table is a SNAPSHOT: later changes of the poses (sgo_set_poses, sgo_optimize_gn) do not touch or invalidate it; it
+ * lasts until the next successful sgo_candidate_joint, sgo_set_graph_se2, sgo_update_graph_se2 or sgo_destroy.  n == 0 drops the
+ * table and returns 0.  Refusals are sgo_candidate_gate's (SGO_EINVAL, nothing on the device changed, no output written, a resident
+ * table kept: n < 0 or a null ci, cj, meas or info, a non-finite entry, an id outside [0, V), a vertex without an edge,
+ * ci[t] == cj[t], an information matrix that is not symmetric positive definite, an active overlay, a multi-GPU context) and
+ * n > SGO_JOINT_MAX_CANDIDATES.  SGO_EINVAL with the outputs untouched and the resident table kept when the Hessian is not positive
+ * definite; the next sgo_optimize_gn is unaffected.  Like sgo_candidate_gate the call writes only what every Gauss-Newton iteration
+ * recomputes, and scratch: a later sgo_optimize_gn has the bits of a context that never called.
+ *
+ * sgo_joint_subsets evaluates B subsets of the resident table, one workgroup each (Cholesky of S_ss in LDS): subset[b][t] != 0
+ * selects candidate t, the selected ones are taken in ascending t; d2[b] as above, dof[b] = 3 |s|, pass[b] = d2[b] <= chi2_max[b]
+ * (the chi2 quantile for dof[b] is the caller's to look up).  Returns how many pass, 0 with chi2_max == NULL (no decisions; pass
+ * is not written).  The empty subset gives 0 exactly; an S_ss that is not positive definite gives NaN, which does not pass.  d2[b]
+ * depends on the table and the subset alone -- not on B, its place in the batch or the other subsets --, and two calls give the
+ * same bits.  It touches no graph structure.  SGO_EINVAL, nothing written: no resident table, n not the table's n, B < 0, a null
+ * subset or d2 with B > 0, a non-finite chi2_max entry, a subset of more than SGO_JOINT_MAX_SUBSET candidates (the subset is
+ * named in sgo_last_error).  B == 0 returns 0.
+ *
+ * sgo_joint_pairs: d2 of every pair {s, t} by the same kernel, the index pairs made on the device; d2[s][t] == d2[t][s] bit for bit
+ * (evaluated once, stored twice), the diagonal holds the single candidates' d2.  Returns n.  SGO_EINVAL: no resident table, n not
+ * the table's n, a null d2. */
+#define SGO_JOINT_MAX_CANDIDATES 256   /* S is 768 x 768 doubles = 4.7 MB */
+#define SGO_JOINT_MAX_SUBSET 40        /* 120 rows: 120 x 121 doubles = 116 KB of LDS, one workgroup (160 KiB per CU) */
+int sgo_candidate_joint(sgo_ctx* ctx, int32_t n, const int32_t* ci, const int32_t* cj, const double* meas, const double* info,
+                        double* S /*[3n][3n] row-major, may be NULL*/, double* e /*[n][3], may be NULL*/);
+int sgo_joint_subsets(sgo_ctx* ctx, int32_t n, int32_t B, const uint8_t* subset /*[B][n]*/, const double* chi2_max /*[B] or NULL*/,
+                      double* d2 /*[B]*/, int32_t* dof /*[B] or NULL*/, uint8_t* pass /*[B] or NULL*/);
+int sgo_joint_pairs(sgo_ctx* ctx, int32_t n, double* d2 /*[n][n]*/);
+
 /* ---- profiling (opts.profile = 1) ---------------------------------------------------------- */
 /* Per-kernel totals accumulated since the last sgo_profile_reset: for kernel slot k,
  * name (static string), launches, total milliseconds (HIP events on the ctx stream), and the

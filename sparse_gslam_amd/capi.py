@@ -36,7 +36,11 @@ SYMBOLS = [
     "sgo_set_edge_information", "sgo_gate_edges", "sgo_set_robust_kernels", "sgo_edge_robust",
     "sgo_solve_rhs", "sgo_marginals", "sgo_marginals_selected", "sgo_factor_solve", "sgo_candidate_gate",
     "sgo_gain_stop", "sgo_optimize_gn_until", "sgo_optimize_gn_hypotheses", "sgo_hypothesis_isolated_vertex",
+    "sgo_candidate_joint", "sgo_joint_subsets", "sgo_joint_pairs",
 ]
+
+# SGO_JOINT_MAX_*: the limits of sgo_candidate_joint's table and of a subset of it
+JOINT_MAX_CANDIDATES, JOINT_MAX_SUBSET = 256, 40
 
 # SGO_STOP_*: why sgo_optimize_gn_until ended
 STOP_MAX_ITERS, STOP_GAIN, STOP_FAILED = 0, 1, 2
@@ -175,6 +179,9 @@ def lib():
     L.sgo_marginals_selected.argtypes = [vp, d, C.c_int32, i32, i32, d]
     L.sgo_factor_solve.argtypes = [vp, C.c_int32, d, d]
     L.sgo_candidate_gate.argtypes = [vp, C.c_int32, i32, i32, d, d, C.c_double, d, d, u8]
+    L.sgo_candidate_joint.argtypes = [vp, C.c_int32, i32, i32, d, d, d, d]
+    L.sgo_joint_subsets.argtypes = [vp, C.c_int32, C.c_int32, u8, d, d, i32, u8]
+    L.sgo_joint_pairs.argtypes = [vp, C.c_int32, d]
     L.sgo_kernel_profile.argtypes = [vp, C.POINTER(KernelStat), C.c_int]
     L.sgo_kernel_profile_samples.argtypes = [vp, C.c_int, C.POINTER(C.c_float), C.c_int]
     L.sgo_solver_description.restype = C.c_char_p
@@ -737,6 +744,47 @@ class Optimizer:
         if rc < 0:
             raise SgoError(f"sgo_candidate_gate: rc={rc}: " + lib().sgo_last_error(self._h).decode())
         return rc, d2, P, ok.astype(bool)
+
+    def candidate_joint(self, ci, cj, meas, info):
+        """sgo_candidate_joint: the joint table of the candidate edges (arguments as candidate_gate's) at the current poses ->
+        (S (3 n, 3 n), e (n, 3)): S = blockdiag(Omega^-1) + 1/2 (G + G^T), G = R^T H^-1 R.  The table stays resident in the context
+        (a snapshot: later pose changes do not touch it) for joint_subsets / joint_pairs; no candidates drop it."""
+        a = np.ascontiguousarray(ci, dtype=np.int32).reshape(-1)
+        b = np.ascontiguousarray(cj, dtype=np.int32).reshape(-1)
+        z = np.ascontiguousarray(meas, dtype=np.float64).reshape(-1, 3)
+        w = np.ascontiguousarray(info, dtype=np.float64).reshape(-1, 6)
+        if not (a.size == b.size == z.shape[0] == w.shape[0]):
+            raise ValueError("inconsistent array sizes")
+        S, e = np.empty((3 * a.size, 3 * a.size)), np.empty((a.size, 3))
+        rc = lib().sgo_candidate_joint(self._h, a.size, _ip(a), _ip(b), _dp(z), _dp(w), _dp(S), _dp(e))
+        if rc < 0:
+            raise SgoError(f"sgo_candidate_joint: rc={rc}: " + lib().sgo_last_error(self._h).decode())
+        self.joint_n = rc
+        return S, e
+
+    def joint_subsets(self, subset, chi2_max=None):
+        """sgo_joint_subsets: d2 = e_s^T (S_ss)^-1 e_s of the subsets subset (B, n) (non-zero: selected) of the resident table ->
+        (npass, d2 (B,), dof (B,), passed (B,) bool); passed = d2 <= chi2_max[b] (chi2_max None: no decisions, npass 0)."""
+        m = np.ascontiguousarray(np.asarray(subset) != 0, dtype=np.uint8)
+        m = m.reshape(-1, m.shape[-1]) if m.ndim else m.reshape(0, 0)
+        B, n = m.shape
+        chi = None if chi2_max is None else np.ascontiguousarray(np.broadcast_to(np.asarray(chi2_max, dtype=np.float64), (B,)))
+        d2, dof, ok = np.empty(B), np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.uint8)
+        u8p = C.POINTER(C.c_uint8)
+        rc = lib().sgo_joint_subsets(self._h, n, B, m.ctypes.data_as(u8p), None if chi is None else _dp(chi), _dp(d2), _ip(dof), ok.ctypes.data_as(u8p))
+        if rc < 0:
+            raise SgoError(f"sgo_joint_subsets: rc={rc}: " + lib().sgo_last_error(self._h).decode())
+        return rc, d2, dof, ok.astype(bool)
+
+    def joint_pairs(self):
+        """sgo_joint_pairs: d2 of every pair {s, t} of the resident table -> (n, n), bitwise symmetric; the diagonal holds the single
+        candidates' d2."""
+        n = int(getattr(self, "joint_n", 0))
+        d2 = np.empty((n, n))
+        rc = lib().sgo_joint_pairs(self._h, n, _dp(d2))
+        if rc < 0:
+            raise SgoError(f"sgo_joint_pairs: rc={rc}: " + lib().sgo_last_error(self._h).decode())
+        return d2
 
     def marginals(self, vi, vj):
         """sgo_marginals: the 3x3 blocks of H^-1 (rows of vertex vi[t], columns of vertex vj[t]; vertex ids) at the current poses

@@ -286,6 +286,19 @@ struct sgo_ctx {
     size_t fs_cap = 0, cand_cap = 0, cidx_cap = 0;
   } selinv;
 
+  // sgo_candidate_joint's table (sgo_fsolve.cpp): S [3 n][3 n], e [n][3] and the failure flag in tab[cur]; a call builds in the
+  // other buffer and switches when it has succeeded, so a refusal or a failure keeps the resident table.  n < 0: no table.
+  struct Joint {
+    double* d_tab[2] = {nullptr, nullptr};
+    size_t tab_cap[2] = {0, 0};
+    int cur = 0, n = -1;
+    double* d_raw = nullptr;          // the Gram blocks before they are symmetrised
+    double* d_d2 = nullptr;           // sgo_joint_subsets / sgo_joint_pairs: results and the uploaded masks
+    uint8_t* d_mask = nullptr;
+    size_t raw_cap = 0, d2_cap = 0, mask_cap = 0;
+    bool lds_ready = false;
+  } joint;
+
   // profiling
   struct Rec { int kid; hipEvent_t a, b; };
   std::vector<hipEvent_t> ev_pool;

@@ -1,5 +1,5 @@
-// sgo_fsolve.cpp -- sgo_factor_solve and sgo_candidate_gate (include/sgo.h): H X = B for panels of 16
-// right-hand sides through the multifrontal factor (kernels in sgo_fsolve.hip), and on top of it the innovation gate for candidate
+// sgo_fsolve.cpp -- sgo_factor_solve, sgo_candidate_gate and the joint table's calls (include/sgo.h; DESIGN.md sections 5g, 5j):
+// H X = B for panels of 16 right-hand sides through the multifrontal factor (kernels in sgo_fsolve.hip), and on top of it the innovation gate for candidate
 // edges -- d2 = e^T (Omega^-1 + J Sigma J^T)^-1 e from three right-hand sides per candidate and no block of Sigma at all.  One call is
 //   factor phase at the current poses (mfront_factorize: the multifrontal path's own launches) ->
 //   per chunk of kFsChunkPanels panels: right-hand sides -> forward pass per level, bottom-up -> backward pass per level, top-down
@@ -7,6 +7,9 @@
 // The plan is the one sgo_marginals_selected works through (selinv_plan: the resident one, or one analysed once per set-up); like
 // that call this one writes only what every Gauss-Newton iteration recomputes from the poses, and scratch.  On a graph the analysis
 // refuses sgo_candidate_gate sends the same right-hand sides through the PCG machinery of sgo_solve_rhs under sgo_marginals' rules.
+// sgo_candidate_joint is the gate's driver with another contraction: the same checks (check_candidates) and
+// the same columns (cand_columns), every chunk contracted with ALL candidates' records into the stacked innovation covariance S,
+// which stays in the context (sgo_ctx::Joint) for sgo_joint_subsets / sgo_joint_pairs.
 #include <algorithm>
 #include <cmath>
 
@@ -144,8 +147,8 @@ constexpr int kChunkCands = kFsChunkPanels * kMfPanel / 3;   // candidates per c
 // The analysis refuses the graph: the candidates' right-hand sides through the PCG, one solve per column under sgo_marginals' rules
 // (cold, pcg_tol relative to the column's own norm, the floor rule, one refresh of the coarse operators per call).  The columns
 // are made and contracted by the same kernels, with the poses' hessian indices as their rows.
-int gate_by_pcg(sgo_ctx* c, int n, const FsCandDev& C, const std::vector<int>& row, const int32_t* ci, const int32_t* cj, double chi2_max,
-                double* d_out) {
+template <class Use>
+int gate_by_pcg(sgo_ctx* c, const char* name, int n, const FsCandDev& C, const std::vector<int>& row, const int32_t* ci, const int32_t* cj, Use&& use) {
   int rc;
   if ((rc = ensure_amg(c))) return rc;
   read_call_knobs(c);
@@ -191,7 +194,7 @@ int gate_by_pcg(sgo_ctx* c, int n, const FsCandDev& C, const std::vector<int>& r
       if (!ok) {
         char buf[64];
         std::snprintf(buf, sizeof buf, "%.3e", R.bb > 0 ? std::sqrt(R.rr / R.bb) : 0.0);
-        c->err = "sgo_candidate_gate: column " + std::to_string(k % 3) + " of candidate " + std::to_string(t) + " (" + std::to_string(ci[t]) + ", " +
+        c->err = std::string(name) + ": column " + std::to_string(k % 3) + " of candidate " + std::to_string(t) + " (" + std::to_string(ci[t]) + ", " +
                  std::to_string(cj[t]) + ")" + (R.stop == 3 ? " broke down (Hessian not positive definite)" : " did not reach pcg_tol") + " after " +
                  std::to_string(R.iter) + " PCG iterations (relative residual " + buf + ")";
         failed = true;
@@ -201,10 +204,7 @@ int gate_by_pcg(sgo_ctx* c, int n, const FsCandDev& C, const std::vector<int>& r
     }
     if (rc || failed) break;
     HIP_TRY(c, hipMemcpyAsync(S.X, sols.data(), bytes, hipMemcpyHostToDevice, c->stream));
-    {
-      Scope sc(c, K_FS_GATE, 8.0 * (kFsRec + kFsOut + 24) * (t1 - t0));
-      launch_fs_gate(c->stream, C, t0, t1, S.X, n3, chi2_max, nullptr, d_out);
-    }
+    use(t0, t1, S.X, n3, nullptr);
     HIP_TRY(c, hipStreamSynchronize(c->stream));   // (sols is rewritten by the next chunk)
   }
   // the linearisation's own right-hand side and its start state again: the context is as after sgo_linearize
@@ -225,6 +225,115 @@ bool spd3(const double* o) {   // leading minors of the symmetric matrix 00 01 0
   const double m3 = o[0] * (o[3] * o[5] - o[4] * o[4]) - o[1] * (o[1] * o[5] - o[4] * o[2]) + o[2] * (o[1] * o[4] - o[3] * o[2]);
   return m1 > 0.0 && m2 > 0.0 && m3 > 0.0;
 }
+
+// What sgo_candidate_gate and sgo_candidate_joint refuse in their candidates.  row[t][side]: hessian index of a free active vertex,
+// -1 for a fixed active one.
+int check_candidates(sgo_ctx* c, const char* name, int n, const int32_t* ci, const int32_t* cj, const double* meas, const double* info,
+                     std::vector<int>* rowp) {
+  // (anything but a free or a fixed active vertex is refused)
+  std::vector<int>& row = *rowp;
+  row.assign(2 * (size_t)n, -1);
+  for (int t = 0; t < n; ++t) {
+    const std::string who = std::string(name) + ": candidate " + std::to_string(t);
+    for (int side = 0; side < 2; ++side) {
+      const int v = side ? cj[t] : ci[t];
+      if (v < 0 || v >= c->V) {
+        c->err = who + ": vertex id " + std::to_string(v) + " outside [0, " + std::to_string(c->V) + ")";
+        return SGO_EINVAL;
+      }
+      const auto f = std::lower_bound(c->free_id.begin(), c->free_id.end(), v);
+      if (f != c->free_id.end() && *f == v) row[2 * (size_t)t + side] = (int)(f - c->free_id.begin());
+      else if (!std::binary_search(c->fixed_active.begin(), c->fixed_active.end(), v)) {
+        c->err = who + ": vertex " + std::to_string(v) + " is not active (it has no edge)";
+        return SGO_EINVAL;
+      }
+    }
+    if (ci[t] == cj[t]) {
+      c->err = who + " joins vertex " + std::to_string(ci[t]) + " to itself";
+      return SGO_EINVAL;
+    }
+    for (int q = 0; q < 9; ++q)
+      if (!std::isfinite(q < 3 ? meas[3 * (size_t)t + q] : info[6 * (size_t)t + q - 3])) {
+        c->err = who + ": non-finite entry in its " + (q < 3 ? "measurement" : "information");
+        return SGO_EINVAL;
+      }
+    if (!spd3(info + 6 * (size_t)t)) {
+      c->err = who + ": its information matrix is not symmetric positive definite";
+      return SGO_EINVAL;
+    }
+  }
+  return SGO_OK;
+}
+
+// The candidates' columns X = H^-1 R at the current poses, a chunk at a time: through the factor of selinv_plan's plan, or through
+// the PCG where the analysis refuses the graph.  use(t0, t1, X, n3, flags) queues what the caller makes of the chunk [t0, t1)
+// (X: its 3 (t1 - t0) columns, rows as C.row says; flags: the factorisation's, nullptr without one); *Cp and *d_out are set before
+// the first chunk.  row: check_candidates' (rewritten to elimination positions on the factor's route).  records_first: every
+// candidate's record (C.rec) is made before the first chunk, not chunk by chunk.
+template <class Use>
+int cand_columns(sgo_ctx* c, const char* name, int n, const int32_t* ci, const int32_t* cj, const double* meas, const double* info,
+                 std::vector<int>& row, bool records_first, FsCandDev* Cp, double** d_out, Use&& use) {
+  int rc;
+  Mfront* m = nullptr;
+  bool by_pcg = false;
+  if (c->n > 0) {
+    rc = selinv_plan(c, &m, name, "the PCG route");
+    if (rc == SGO_ENOTHING) by_pcg = true;   // (the analysis refuses the graph: the same columns through the PCG)
+    else if (rc) return rc;
+  }
+  if (m) {
+    if ((rc = fs_prepare(c, m, name))) return rc;
+    const MfPlan& P = m->plan;
+    std::vector<int> pos_of((size_t)c->n, -1);   // hessian index -> elimination position
+    for (int p = 0; p < P.n; ++p)
+      pos_of[(size_t)(std::lower_bound(c->free_id.begin(), c->free_id.end(), P.elim_vertex[p]) - c->free_id.begin())] = p;
+    for (int& r : row)
+      if (r >= 0) r = pos_of[(size_t)r];
+  }
+  if ((rc = cand_upload(c, n, ci, cj, row, meas, info, Cp, d_out))) return rc;
+  const FsCandDev& C = *Cp;
+  if (records_first) {   // (a chunk's columns are contracted with the records of ALL candidates, later chunks' included)
+    Scope sc(c, K_FS_RHS, 8.0 * (kFsRec + 9) * n);
+    launch_fs_records(c->stream, C, c->d_poses);
+  }
+  if (by_pcg) {
+    if ((rc = gate_by_pcg(c, name, n, C, row, ci, cj, use))) return rc;
+  } else {
+    const int n3 = 3 * c->n;
+    FsScratch S;
+    if (m) {
+      if ((rc = fs_scratch(c, n3, m->fs.U3, std::min(kFsChunkPanels, (3 * n + kMfPanel - 1) / kMfPanel), &S))) return rc;
+      if ((rc = factorize(c, m))) return rc;
+    }
+    for (int t0 = 0; t0 < n; t0 += kChunkCands) {
+      const int t1 = std::min(n, t0 + kChunkCands), nc = 3 * (t1 - t0), panels = (nc + kMfPanel - 1) / kMfPanel;
+      if (m) HIP_TRY(c, hipMemsetAsync(S.Y, 0, sizeof(double) * (size_t)panels * kMfPanel * n3, c->stream));
+      {
+        Scope sc(c, K_FS_RHS, 8.0 * (kFsRec + 18) * (t1 - t0));
+        launch_fs_rhs_candidates(c->stream, C, t0, t1, c->d_poses, n3, S.Y);
+      }
+      if (m) fs_passes(c, m, S, panels, nc);
+      use(t0, t1, S.X, n3, m ? m->dev.flags : nullptr);
+    }
+  }
+  return SGO_OK;
+}
+
+// what sgo_joint_subsets and sgo_joint_pairs refuse alike
+int joint_table_check(sgo_ctx* c, const char* name, int32_t n) {
+  int rc = check_graph(c);
+  if (rc) return rc;
+  if (c->joint.n < 0) {
+    c->err = std::string(name) + ": no resident table (call sgo_candidate_joint; a new or updated graph drops the table)";
+    return SGO_EINVAL;
+  }
+  if (n != c->joint.n) {
+    c->err = std::string(name) + ": n = " + std::to_string(n) + ", the resident table holds " + std::to_string(c->joint.n) + " candidates";
+    return SGO_EINVAL;
+  }
+  return SGO_OK;
+}
+constexpr int kJointLaunch = 1 << 20;   // subsets (workgroups) per launch
 
 }  // namespace
 
@@ -307,79 +416,17 @@ int sgo_candidate_gate(sgo_ctx* c, int32_t n, const int32_t* ci, const int32_t* 
       return SGO_EINVAL;
     }
     if ((rc = refuse_context(c, "sgo_candidate_gate"))) return rc;
-    // hessian index of a free active vertex, -1 for a fixed active one; anything else is refused
-    std::vector<int> row(2 * (size_t)n, -1);
-    for (int t = 0; t < n; ++t) {
-      const std::string who = "sgo_candidate_gate: candidate " + std::to_string(t);
-      for (int side = 0; side < 2; ++side) {
-        const int v = side ? cj[t] : ci[t];
-        if (v < 0 || v >= c->V) {
-          c->err = who + ": vertex id " + std::to_string(v) + " outside [0, " + std::to_string(c->V) + ")";
-          return SGO_EINVAL;
-        }
-        const auto f = std::lower_bound(c->free_id.begin(), c->free_id.end(), v);
-        if (f != c->free_id.end() && *f == v) row[2 * (size_t)t + side] = (int)(f - c->free_id.begin());
-        else if (!std::binary_search(c->fixed_active.begin(), c->fixed_active.end(), v)) {
-          c->err = who + ": vertex " + std::to_string(v) + " is not active (it has no edge)";
-          return SGO_EINVAL;
-        }
-      }
-      if (ci[t] == cj[t]) {
-        c->err = who + " joins vertex " + std::to_string(ci[t]) + " to itself";
-        return SGO_EINVAL;
-      }
-      for (int q = 0; q < 9; ++q)
-        if (!std::isfinite(q < 3 ? meas[3 * (size_t)t + q] : info[6 * (size_t)t + q - 3])) {
-          c->err = who + ": non-finite entry in its " + (q < 3 ? "measurement" : "information");
-          return SGO_EINVAL;
-        }
-      if (!spd3(info + 6 * (size_t)t)) {
-        c->err = who + ": its information matrix is not symmetric positive definite";
-        return SGO_EINVAL;
-      }
-    }
+    std::vector<int> row;
+    if ((rc = check_candidates(c, "sgo_candidate_gate", n, ci, cj, meas, info, &row))) return rc;
     if (n == 0) return 0;
-    Mfront* m = nullptr;
-    bool by_pcg = false;
-    if (c->n > 0) {
-      rc = selinv_plan(c, &m, "sgo_candidate_gate", "the PCG route");
-      if (rc == SGO_ENOTHING) by_pcg = true;   // (the analysis refuses the graph: the same columns through the PCG)
-      else if (rc) return rc;
-    }
-    if (m) {
-      if ((rc = fs_prepare(c, m, "sgo_candidate_gate"))) return rc;
-      const MfPlan& P = m->plan;
-      std::vector<int> pos_of((size_t)c->n, -1);   // hessian index -> elimination position
-      for (int p = 0; p < P.n; ++p)
-        pos_of[(size_t)(std::lower_bound(c->free_id.begin(), c->free_id.end(), P.elim_vertex[p]) - c->free_id.begin())] = p;
-      for (int& r : row)
-        if (r >= 0) r = pos_of[(size_t)r];
-    }
     FsCandDev C;
     double* d_out = nullptr;
-    if ((rc = cand_upload(c, n, ci, cj, row, meas, info, &C, &d_out))) return rc;
+    if ((rc = cand_columns(c, "sgo_candidate_gate", n, ci, cj, meas, info, row, false, &C, &d_out, [&](int t0, int t1, const double* X, int n3, const int* flags) {
+          Scope sc(c, K_FS_GATE, 8.0 * (kFsRec + kFsOut + 24) * (t1 - t0));
+          launch_fs_gate(c->stream, C, t0, t1, X, n3, chi2_max, flags, d_out);
+        })))
+      return rc;
     const size_t nout = (size_t)kFsOut * n + 1;
-    if (by_pcg) {
-      if ((rc = gate_by_pcg(c, n, C, row, ci, cj, chi2_max, d_out))) return rc;
-    } else {
-      const int n3 = 3 * c->n;
-      FsScratch S;
-      if (m) {
-        if ((rc = fs_scratch(c, n3, m->fs.U3, std::min(kFsChunkPanels, (3 * n + kMfPanel - 1) / kMfPanel), &S))) return rc;
-        if ((rc = factorize(c, m))) return rc;
-      }
-      for (int t0 = 0; t0 < n; t0 += kChunkCands) {
-        const int t1 = std::min(n, t0 + kChunkCands), nc = 3 * (t1 - t0), panels = (nc + kMfPanel - 1) / kMfPanel;
-        if (m) HIP_TRY(c, hipMemsetAsync(S.Y, 0, sizeof(double) * (size_t)panels * kMfPanel * n3, c->stream));
-        {
-          Scope sc(c, K_FS_RHS, 8.0 * (kFsRec + 18) * (t1 - t0));
-          launch_fs_rhs_candidates(c->stream, C, t0, t1, c->d_poses, n3, S.Y);
-        }
-        if (m) fs_passes(c, m, S, panels, nc);
-        Scope sc(c, K_FS_GATE, 8.0 * (kFsRec + kFsOut + 24) * (t1 - t0));
-        launch_fs_gate(c->stream, C, t0, t1, S.X, n3, chi2_max, m ? m->dev.flags : nullptr, d_out);
-      }
-    }
     HIP_TRY(c, hipGetLastError());
     std::vector<double> out(nout);
     HIP_TRY(c, hipMemcpyAsync(out.data(), d_out, sizeof(double) * nout, hipMemcpyDeviceToHost, c->stream));
@@ -398,6 +445,154 @@ int sgo_candidate_gate(sgo_ctx* c, int32_t n, const int32_t* ci, const int32_t* 
       npass += o[10] != 0.0;
     }
     return npass;
+  } SGO_CATCH(c)
+}
+
+int sgo_candidate_joint(sgo_ctx* c, int32_t n, const int32_t* ci, const int32_t* cj, const double* meas, const double* info, double* S, double* e) {
+  try {
+    int rc = check_graph(c);
+    if (rc) return rc;
+    if (n < 0 || (n > 0 && (!ci || !cj || !meas || !info))) {
+      c->err = "sgo_candidate_joint: null buffer or negative count";
+      return SGO_EINVAL;
+    }
+    if (n > SGO_JOINT_MAX_CANDIDATES) {
+      c->err = "sgo_candidate_joint: " + std::to_string(n) + " candidates, more than SGO_JOINT_MAX_CANDIDATES = " + std::to_string(SGO_JOINT_MAX_CANDIDATES);
+      return SGO_EINVAL;
+    }
+    if ((rc = refuse_context(c, "sgo_candidate_joint"))) return rc;
+    std::vector<int> row;
+    if ((rc = check_candidates(c, "sgo_candidate_joint", n, ci, cj, meas, info, &row))) return rc;
+    sgo_ctx::Joint& J = c->joint;
+    if (n == 0) {
+      J.n = -1;
+      return 0;
+    }
+    if (!J.lds_ready) {
+      if (!joint_prepare_device()) {
+        c->err = "sgo_candidate_joint: the device does not grant the subset kernel's dynamic LDS";
+        return SGO_EHIP;
+      }
+      J.lds_ready = true;
+    }
+    // built beside the resident table, which stays until this call has succeeded
+    const int other = J.n < 0 ? J.cur : 1 - J.cur;
+    const size_t N3 = 3 * (size_t)n, ntab = joint_table_doubles(n);
+    if ((rc = grow_device(c, &J.d_raw, &J.raw_cap, N3 * N3)) || (rc = grow_device(c, &J.d_tab[other], &J.tab_cap[other], ntab))) return rc;
+    double* const tab = J.d_tab[other];
+    FsCandDev C;
+    double* d_out = nullptr;
+    const int* fl = nullptr;
+    if ((rc = cand_columns(c, "sgo_candidate_joint", n, ci, cj, meas, info, row, true, &C, &d_out, [&](int t0, int t1, const double* X, int n3, const int* flags) {
+          Scope sc(c, K_FS_GRAM, 8.0 * (kFsRec + 18 + 9) * (double)n * (t1 - t0));
+          launch_fs_gram(c->stream, C, t0, t1, X, n3, J.d_raw);
+          fl = flags;
+        })))
+      return rc;
+    {
+      Scope sc(c, K_FS_JOINT_TABLE, 8.0 * 18 * (double)n * n);
+      launch_fs_joint_table(c->stream, C, J.d_raw, fl, tab);
+    }
+    HIP_TRY(c, hipGetLastError());
+    // the failure flag first: the outputs stay untouched when the Hessian is not positive definite; then S and e straight into the
+    // caller's arrays (4.7 MB at 256 candidates: no staging copy)
+    double failed = 0.0;
+    HIP_TRY(c, hipMemcpyAsync(&failed, tab + ntab - 1, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    prof_flush(c);
+    if (failed != 0.0) {
+      c->err = std::string("sgo_candidate_joint") + kNotPd;
+      return SGO_EINVAL;
+    }
+    if (S) HIP_TRY(c, hipMemcpyAsync(S, tab, sizeof(double) * N3 * N3, hipMemcpyDeviceToHost, c->stream));
+    if (e) HIP_TRY(c, hipMemcpyAsync(e, tab + N3 * N3, sizeof(double) * N3, hipMemcpyDeviceToHost, c->stream));
+    if (S || e) HIP_TRY(c, hipStreamSynchronize(c->stream));
+    J.cur = other;
+    J.n = n;
+    return n;
+  } SGO_CATCH(c)
+}
+
+
+int sgo_joint_subsets(sgo_ctx* c, int32_t n, int32_t B, const uint8_t* subset, const double* chi2_max, double* d2, int32_t* dof, uint8_t* pass) {
+  try {
+    int rc = joint_table_check(c, "sgo_joint_subsets", n);
+    if (rc) return rc;
+    if (B < 0 || (B > 0 && (!subset || !d2))) {
+      c->err = "sgo_joint_subsets: null buffer or negative count";
+      return SGO_EINVAL;
+    }
+    if (chi2_max)
+      for (int b = 0; b < B; ++b)
+        if (!std::isfinite(chi2_max[b])) {
+          c->err = "sgo_joint_subsets: chi2_max of subset " + std::to_string(b) + " is not finite";
+          return SGO_EINVAL;
+        }
+    std::vector<int> cnt((size_t)B);
+    int largest = 0;
+    for (int b = 0; b < B; ++b) {
+      int k = 0;
+      for (int t = 0; t < n; ++t) k += subset[(size_t)b * n + t] != 0;
+      if (k > SGO_JOINT_MAX_SUBSET) {
+        c->err = "sgo_joint_subsets: subset " + std::to_string(b) + " selects " + std::to_string(k) + " candidates, more than SGO_JOINT_MAX_SUBSET = " +
+                 std::to_string(SGO_JOINT_MAX_SUBSET);
+        return SGO_EINVAL;
+      }
+      cnt[(size_t)b] = k;
+      largest = std::max(largest, k);
+    }
+    if (B == 0) return 0;
+    sgo_ctx::Joint& J = c->joint;
+    const size_t nm = (size_t)B * n;
+    if ((rc = grow_device(c, &J.d_d2, &J.d2_cap, (size_t)B)) || (rc = grow_device(c, &J.d_mask, &J.mask_cap, nm))) return rc;
+    HIP_TRY(c, hipMemcpyAsync(J.d_mask, subset, nm, hipMemcpyHostToDevice, c->stream));
+    for (int b0 = 0; b0 < B; b0 += kJointLaunch) {
+      const int nb = std::min(kJointLaunch, B - b0);
+      Scope sc(c, K_JOINT_SUBSETS, (double)nb * (n + 8.0 + 4.0 * (3.0 * largest + 1) * (3.0 * largest + 2)));
+      launch_joint_subsets(c->stream, J.d_tab[J.cur], n, J.d_mask, b0, nb, std::max(3 * largest, 3), J.d_d2);
+    }
+    HIP_TRY(c, hipGetLastError());
+    std::vector<double> res((size_t)B);
+    HIP_TRY(c, hipMemcpyAsync(res.data(), J.d_d2, sizeof(double) * (size_t)B, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    prof_flush(c);
+    int npass = 0;
+    for (int b = 0; b < B; ++b) {
+      d2[b] = res[(size_t)b];
+      if (dof) dof[b] = 3 * cnt[(size_t)b];
+      if (chi2_max) {
+        const bool ok = res[(size_t)b] <= chi2_max[b];
+        if (pass) pass[b] = ok;
+        npass += ok;
+      }
+    }
+    return npass;
+  } SGO_CATCH(c)
+}
+
+int sgo_joint_pairs(sgo_ctx* c, int32_t n, double* d2) {
+  try {
+    int rc = joint_table_check(c, "sgo_joint_pairs", n);
+    if (rc) return rc;
+    if (n > 0 && !d2) {
+      c->err = "sgo_joint_pairs: null buffer";
+      return SGO_EINVAL;
+    }
+    sgo_ctx::Joint& J = c->joint;
+    const size_t nn = (size_t)n * n;
+    const int B = n * (n + 1) / 2;
+    if ((rc = grow_device(c, &J.d_d2, &J.d2_cap, nn))) return rc;
+    {
+      Scope sc(c, K_JOINT_SUBSETS, (double)B * (16.0 + 8.0 * 7 * 8));
+      launch_joint_subsets(c->stream, J.d_tab[J.cur], n, nullptr, 0, B, 6, J.d_d2);
+    }
+    HIP_TRY(c, hipGetLastError());
+    std::vector<double> res(nn);
+    HIP_TRY(c, hipMemcpyAsync(res.data(), J.d_d2, sizeof(double) * nn, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    prof_flush(c);
+    std::copy(res.begin(), res.end(), d2);
+    return n;
   } SGO_CATCH(c)
 }
 

@@ -13,6 +13,10 @@
 //                  does; the contraction over R is split over the eight waves in fixed shares and added in wave order
 //   k_fs_gate      per candidate: Q = R^T W from at most six rows of W, P = (Q + Q^T) / 2, S = Omega^-1 + P (cofactors),
 //                  d2 = e^T S^-1 e by a 3 x 3 Cholesky; d2, P, the decision and the factorisation's failure flag in one buffer
+// and the joint table of a candidate SET (sgo_candidate_joint / sgo_joint_subsets / sgo_joint_pairs):
+//   k_fs_gram         per chunk of columns: G_st = [A_s B_s] W_t[rows of i_s, j_s] for ALL candidates s against the chunk's t
+//   k_fs_joint_table  S = blockdiag(Omega^-1) + (G + G^T) / 2, one triangle computed and mirrored; e; the failure flag
+//   k_joint_subsets   one workgroup per subset of the resident table: d2 = e_s^T (S_ss)^-1 e_s by a Cholesky in LDS
 // All products run on the fp64 matrix cores (v_mfma_f64_16x16x4_f64: lane (lr, lk) = (lane & 15, lane >> 4) holds A[lr][lk] and
 // B[lk][lr] of a step and the results D[lk + 4 q][lr]); a column of the panel is a column of B and of D in every product, so a
 // right-hand side's solution does not depend on what shares its panel.  Operands beyond a tail are masked to zero on both sides,
@@ -36,9 +40,10 @@ struct CandSrc {
   const double* zinv;
 };
 
-// GATE: one thread per candidate of [t0, t1) -- record, then A^T / B^T into the (zeroed) panel; otherwise one thread per entry of
-// the caller's columns src[ncols][3 n] (hessian order) -> panel[ncols][3 n] (elimination position).
-template <bool GATE>
+// GATE 1: one thread per candidate of [t0, t1) -- record, then A^T / B^T into the (zeroed) panel; GATE 2: the record alone
+// (sgo_candidate_joint needs every candidate's record before the first chunk's columns are contracted); GATE 0: one thread per
+// entry of the caller's columns src[ncols][3 n] (hessian order) -> panel[ncols][3 n] (elimination position).
+template <int GATE>
 __global__ __launch_bounds__(kBlock) void k_fs_rhs(FsCandDev C, int t0, int t1, const double* __restrict__ poses, const double* __restrict__ src,
                                                    const int* __restrict__ pos_h, int ncols, int n3, double* __restrict__ panel) {
   if (GATE) {
@@ -56,6 +61,7 @@ __global__ __launch_bounds__(kBlock) void k_fs_rhs(FsCandDev C, int t0, int t1, 
     rec[0] = e[0]; rec[1] = e[1]; rec[2] = e[2];
     rec[3] = J.A00; rec[4] = J.A01; rec[5] = J.A02; rec[6] = J.A10; rec[7] = J.A11; rec[8] = J.A12;
     rec[9] = J.B00; rec[10] = J.B01; rec[11] = J.B10; rec[12] = J.B11;
+    if (GATE == 2) return;
     const int ri = C.row[2 * t], rj = C.row[2 * t + 1];
     double* col = panel + 3 * (size_t)(t - t0) * n3;   // column a of R: row a of A at the rows of i, row a of B at the rows of j
     if (ri >= 0) {
@@ -242,24 +248,8 @@ __global__ __launch_bounds__(kBlock) void k_fs_gate(FsCandDev C, int t0, int t1,
   if (t >= t1) return;
   const double* rec = C.rec + (size_t)kFsRec * t;
   const double e[3] = {rec[0], rec[1], rec[2]};
-  const double A[3][3] = {{rec[3], rec[4], rec[5]}, {rec[6], rec[7], rec[8]}, {0.0, 0.0, -1.0}};
-  const double B[3][3] = {{rec[9], rec[10], 0.0}, {rec[11], rec[12], 0.0}, {0.0, 0.0, 1.0}};
-  const int ri = C.row[2 * t], rj = C.row[2 * t + 1];
-  const double* col = W + 3 * (size_t)(t - t0) * n3;
   double Q[3][3];
-#pragma unroll
-  for (int b = 0; b < 3; ++b) {
-    double wi[3] = {0.0, 0.0, 0.0}, wj[3] = {0.0, 0.0, 0.0};
-    if (ri >= 0)
-#pragma unroll
-      for (int r = 0; r < 3; ++r) wi[r] = col[(size_t)b * n3 + 3 * (size_t)ri + r];
-    if (rj >= 0)
-#pragma unroll
-      for (int r = 0; r < 3; ++r) wj[r] = col[(size_t)b * n3 + 3 * (size_t)rj + r];
-#pragma unroll
-    for (int a = 0; a < 3; ++a)
-      Q[a][b] = ((A[a][0] * wi[0] + A[a][1] * wi[1]) + A[a][2] * wi[2]) + ((B[a][0] * wj[0] + B[a][1] * wj[1]) + B[a][2] * wj[2]);
-  }
+  fs_candidate_q(rec, C.row + 2 * t, W + 3 * (size_t)(t - t0) * n3, n3, Q);
   double P[3][3];
 #pragma unroll
   for (int a = 0; a < 3; ++a)
@@ -289,16 +279,160 @@ __global__ __launch_bounds__(kBlock) void k_fs_gate(FsCandDev C, int t0, int t1,
   o[10] = d2 <= chi2_max ? 1.0 : 0.0;
 }
 
+// One thread per block G_st: candidate s of all n (x), candidate t of the chunk [t0, t1) (y), whose three columns of H^-1 R are W's
+// columns 3 (t - t0) ...; G: raw [3 n][3 n], every block written once over the chunks of a call
+__global__ __launch_bounds__(kBlock) void k_fs_gram(FsCandDev C, int t0, int t1, const double* __restrict__ W, int n3, double* __restrict__ G) {
+  const int s = blockIdx.x * kBlock + threadIdx.x, t = t0 + blockIdx.y;
+  if (s >= C.n || t >= t1) return;
+  double Q[3][3];
+  fs_candidate_q(C.rec + (size_t)kFsRec * s, C.row + 2 * s, W + 3 * (size_t)(t - t0) * n3, n3, Q);
+  const size_t ld = 3 * (size_t)C.n;
+#pragma unroll
+  for (int a = 0; a < 3; ++a)
+#pragma unroll
+    for (int b = 0; b < 3; ++b) G[(3 * (size_t)s + a) * ld + 3 * (size_t)t + b] = Q[a][b];
+}
+
+// One thread per block pair s <= t: S_st = (G_st + G_ts^T) / 2, stored at both places (S is exactly symmetric); the diagonal block
+// adds Omega^-1 by cofactors as k_fs_gate does and the thread stores e_s; then the factorisation's failure flag
+__global__ __launch_bounds__(kBlock) void k_fs_joint_table(FsCandDev C, const double* __restrict__ G, const int* __restrict__ flags,
+                                                           double* __restrict__ table) {
+  const int n = C.n;
+  const int s = blockIdx.x * kBlock + threadIdx.x, t = blockIdx.y;
+  const size_t ld = 3 * (size_t)n;
+  if (s == 0 && t == 0) table[ld * ld + ld] = flags ? (double)flags[0] : 0.0;
+  if (s > t || t >= n) return;
+  double P[3][3];
+#pragma unroll
+  for (int a = 0; a < 3; ++a)
+#pragma unroll
+    for (int b = 0; b < 3; ++b) P[a][b] = 0.5 * (G[(3 * (size_t)s + a) * ld + 3 * (size_t)t + b] + G[(3 * (size_t)t + b) * ld + 3 * (size_t)s + a]);
+  if (s == t) {
+    const size_t ns = (size_t)n;
+    const double o00 = C.info[t], o01 = C.info[ns + t], o02 = C.info[2 * ns + t], o11 = C.info[3 * ns + t], o12 = C.info[4 * ns + t],
+                 o22 = C.info[5 * ns + t];
+    const double c00 = o11 * o22 - o12 * o12, c01 = o02 * o12 - o01 * o22, c02 = o01 * o12 - o02 * o11;
+    const double c11 = o00 * o22 - o02 * o02, c12 = o01 * o02 - o00 * o12, c22 = o00 * o11 - o01 * o01;
+    const double idet = 1.0 / (o00 * c00 + o01 * c01 + o02 * c02);
+    // (the lower triangle's values, mirrored: P is symmetric bit for bit, so the block is)
+    const double s00 = c00 * idet + P[0][0], s10 = c01 * idet + P[1][0], s20 = c02 * idet + P[2][0];
+    const double s11 = c11 * idet + P[1][1], s21 = c12 * idet + P[2][1], s22 = c22 * idet + P[2][2];
+    P[0][0] = s00; P[1][0] = s10; P[2][0] = s20; P[1][1] = s11; P[2][1] = s21; P[2][2] = s22;
+    P[0][1] = s10; P[0][2] = s20; P[1][2] = s21;
+    const double* rec = C.rec + (size_t)kFsRec * t;
+    double* e = table + ld * ld + 3 * (size_t)t;
+    e[0] = rec[0]; e[1] = rec[1]; e[2] = rec[2];
+  }
+#pragma unroll
+  for (int a = 0; a < 3; ++a)
+#pragma unroll
+    for (int b = 0; b < 3; ++b) {
+      table[(3 * (size_t)s + a) * ld + 3 * (size_t)t + b] = P[a][b];
+      table[(3 * (size_t)t + b) * ld + 3 * (size_t)s + a] = P[a][b];
+    }
+}
+
+// One workgroup per subset of the resident table: the selected candidates ascending (a mask row compacted by ballot and prefix
+// count, or the pair number decoded), S_ss's lower triangle over the row e_s gathered into LDS (leading dimension odd: a row's
+// elements, and a column's, fall in distinct banks), then a right-looking Cholesky that carries e_s along as row m -- after step k
+// row m holds e_s - L[:, :k] z[:k] --, so z_k = row m's entry k over L_kk and d2 = sum z_k^2, added in ascending k by one thread.
+// Step k, one barrier: every thread takes r = 1 / sqrt(a_kk) itself (a_kk is final since step k - 1's barrier; a_kk not above
+// zero: NaN, which spreads to d2) and element (i, j), k < j <= i <= m, loses (a_ik r) (a_jk r); column k stays unscaled, nobody reads it again
+// but z_k.  Thread (ty, tx) of 16 x 16 owns the elements i = ty mod 16, j = tx mod 16 of the trailing block: an element's updates
+// are its own thread's, in ascending k.  No atomics.  A subset's arithmetic depends on the table and its index list alone: not on
+// the launch's LDS size (rows_cap sets the leading dimension, which moves nothing but addresses), its place in the grid or the batch.
+template <bool PAIRS>
+__global__ __launch_bounds__(kJointThreads) void k_joint_subsets(const double* __restrict__ table, int n, const uint8_t* __restrict__ mask, int b0,
+                                                                 int rows_cap, double* __restrict__ d2) {
+  extern __shared__ double Lm[];   // [rows_cap + 1][ld], then zz [rows_cap]
+  __shared__ int idx[SGO_JOINT_MAX_SUBSET];
+  __shared__ int wcnt[kJointThreads / 64];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, tx = tid & 15, ty = tid >> 4;
+  const long long b = (long long)b0 + blockIdx.x;
+  const int ld = rows_cap | 1;
+  double* __restrict__ zz = Lm + (size_t)(rows_cap + 1) * ld;
+  int cnt, ps = 0, pt = 0;
+  if (PAIRS) {
+    // b = pt (pt + 1) / 2 + ps, ps <= pt
+    pt = (int)((sqrt(8.0 * (double)b + 1.0) - 1.0) * 0.5);
+    while ((long long)pt * (pt + 1) / 2 > b) --pt;
+    while ((long long)(pt + 1) * (pt + 2) / 2 <= b) ++pt;
+    ps = (int)(b - (long long)pt * (pt + 1) / 2);
+    cnt = ps == pt ? 1 : 2;
+    if (tid == 0) {
+      idx[0] = ps;
+      idx[1] = pt;
+    }
+  } else {
+    const bool on = tid < n && mask[(size_t)b * n + tid] != 0;
+    const unsigned long long bal = __ballot(on);
+    if (lane == 0) wcnt[wave] = __popcll(bal);
+    __syncthreads();
+    int base = 0;
+    cnt = 0;
+#pragma unroll
+    for (int w = 0; w < kJointThreads / 64; ++w) {
+      if (w < wave) base += wcnt[w];
+      cnt += wcnt[w];
+    }
+    const int pos = base + __popcll(bal & ((1ull << lane) - 1ull));
+    if (on && pos < SGO_JOINT_MAX_SUBSET) idx[pos] = tid;
+  }
+  const int m = 3 * cnt;
+  if (cnt > SGO_JOINT_MAX_SUBSET || m > rows_cap) {   // (the driver refuses such a subset before the launch)
+    if (tid == 0) d2[b] = __builtin_nan("");
+    return;
+  }
+  __syncthreads();
+  const size_t ldS = 3 * (size_t)n;
+  const double* __restrict__ ev = table + ldS * ldS;
+  for (int i = ty; i <= m; i += 16) {
+    const double* __restrict__ src = i < m ? table + (3 * (size_t)idx[i / 3] + i % 3) * ldS : ev;
+    for (int j = tx; j <= i && j < m; j += 16) Lm[i * ld + j] = src[3 * (size_t)idx[j / 3] + j % 3];
+  }
+  __syncthreads();
+  for (int k = 0; k < m; ++k) {
+    const double akk = Lm[k * ld + k];
+    const double r = akk > 0.0 ? 1.0 / sqrt(akk) : __builtin_nan("");
+    const int i0 = k + 1 + ((ty - (k + 1)) & 15), j0 = k + 1 + ((tx - (k + 1)) & 15);   // the first i >= k + 1 with i mod 16 == ty
+    for (int i = i0; i <= m; i += 16) {
+      const double li = Lm[i * ld + k] * r;
+      for (int j = j0; j <= i && j < m; j += 16) Lm[i * ld + j] -= li * (Lm[j * ld + k] * r);
+    }
+    __syncthreads();
+  }
+  if (tid < m) {
+    const double akk = Lm[tid * ld + tid];
+    const double z = Lm[m * ld + tid] * (akk > 0.0 ? 1.0 / sqrt(akk) : __builtin_nan(""));
+    zz[tid] = z * z;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    double sum = 0.0;
+    for (int k = 0; k < m; ++k) sum += zz[k];
+    if (PAIRS) {
+      d2[(size_t)ps * n + pt] = sum;
+      d2[(size_t)pt * n + ps] = sum;
+    } else {
+      d2[b] = sum;
+    }
+  }
+}
+
 }  // namespace
 
 void launch_fs_rhs_columns(hipStream_t s, int ncols, int n3, const double* src, const int* pos_h, double* panel) {
   const long long tot = (long long)ncols * n3;
   const int grid = (int)std::max<long long>(1, std::min<long long>((tot + kBlock - 1) / kBlock, 4096));
-  SGO_LAUNCH((k_fs_rhs<false>), dim3(grid), dim3(kBlock), 0, s, FsCandDev(), 0, 0, (const double*)nullptr, src, pos_h, ncols, n3, panel);
+  SGO_LAUNCH((k_fs_rhs<0>), dim3(grid), dim3(kBlock), 0, s, FsCandDev(), 0, 0, (const double*)nullptr, src, pos_h, ncols, n3, panel);
 }
 void launch_fs_rhs_candidates(hipStream_t s, const FsCandDev& C, int t0, int t1, const double* poses, int n3, double* panel) {
-  SGO_LAUNCH((k_fs_rhs<true>), dim3((t1 - t0 + kBlock - 1) / kBlock), dim3(kBlock), 0, s, C, t0, t1, poses, (const double*)nullptr, (const int*)nullptr,
+  SGO_LAUNCH((k_fs_rhs<1>), dim3((t1 - t0 + kBlock - 1) / kBlock), dim3(kBlock), 0, s, C, t0, t1, poses, (const double*)nullptr, (const int*)nullptr,
              3 * (t1 - t0), n3, panel);
+}
+void launch_fs_records(hipStream_t s, const FsCandDev& C, const double* poses) {
+  SGO_LAUNCH((k_fs_rhs<2>), dim3((C.n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, C, 0, C.n, poses, (const double*)nullptr, (const int*)nullptr, 0, 0,
+             (double*)nullptr);
 }
 void launch_fs_forward(hipStream_t s, const MfDev& M, const MfSelDev& Z, const MfFsDev& Fs, int lvl0, int count, int panels, size_t lds, double* Y,
                        double* U, int n3) {
@@ -309,6 +443,26 @@ void launch_fs_backward(hipStream_t s, const MfDev& M, int lvl0, int count, int 
 }
 void launch_fs_gate(hipStream_t s, const FsCandDev& C, int t0, int t1, const double* W, int n3, double chi2_max, const int* flags, double* out) {
   SGO_LAUNCH(k_fs_gate, dim3((t1 - t0 + kBlock - 1) / kBlock), dim3(kBlock), 0, s, C, t0, t1, W, n3, chi2_max, flags, out);
+}
+void launch_fs_gram(hipStream_t s, const FsCandDev& C, int t0, int t1, const double* W, int n3, double* G) {
+  SGO_LAUNCH(k_fs_gram, dim3((C.n + kBlock - 1) / kBlock, t1 - t0), dim3(kBlock), 0, s, C, t0, t1, W, n3, G);
+}
+void launch_fs_joint_table(hipStream_t s, const FsCandDev& C, const double* G, const int* flags, double* table) {
+  SGO_LAUNCH(k_fs_joint_table, dim3((C.n + kBlock - 1) / kBlock, C.n), dim3(kBlock), 0, s, C, G, flags, table);
+}
+void launch_joint_subsets(hipStream_t s, const double* table, int n, const uint8_t* mask, int b0, int count, int rows_cap, double* d2) {
+  const size_t lds = joint_lds_bytes(rows_cap);
+  if (mask) SGO_LAUNCH((k_joint_subsets<false>), dim3(count), dim3(kJointThreads), lds, s, table, n, mask, b0, rows_cap, d2);
+  else SGO_LAUNCH((k_joint_subsets<true>), dim3(count), dim3(kJointThreads), lds, s, table, n, mask, b0, rows_cap, d2);
+}
+bool joint_prepare_device() {
+  const int lds = (int)joint_lds_bytes(3 * SGO_JOINT_MAX_SUBSET);
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_joint_subsets<false>), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess ||
+      hipFuncSetAttribute(reinterpret_cast<const void*>(&k_joint_subsets<true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) {
+    (void)hipGetLastError();
+    return false;
+  }
+  return true;
 }
 bool fs_prepare_device() {
   const int lds = (int)sizeof(double) * kMfPanel * ((kMfMaxDim + 2) | 1);

@@ -381,6 +381,9 @@ enum KernelId : int {
   K_FS_FORWARD,
   K_FS_BACKWARD,
   K_FS_GATE,
+  K_FS_GRAM,            // sgo_candidate_joint / sgo_joint_subsets / sgo_joint_pairs (sgo_fsolve.hip)
+  K_FS_JOINT_TABLE,
+  K_JOINT_SUBSETS,
   K_COUNT
 };
 extern const char* const kKernelNames[K_COUNT];

@@ -2,6 +2,8 @@
 // factorisation (sgo_mfront.hip makes and fills it; sgo_selinv.hip reads the factor for the selected inversion, sgo_fsolve.hip for
 // the multi-right-hand-side substitution) and the opaque Mfront behind sgo_mfront.h.  Not for the host-only sources.
 #pragma once
+#include <algorithm>
+#include <cstdint>
 #include <vector>
 
 #include <hip/hip_runtime.h>
@@ -79,6 +81,33 @@ struct FsCandDev {
   double* rec = nullptr;          // [n][kFsRec]
 };
 
+// Q = [A_s B_s] W[rows of i_s, j_s] (3 x 3): candidate s' record against three columns `col` of W = H^-1 R (column b at col + b n3;
+// rows[0], rows[1]: the rows of its poses, -1 for a fixed endpoint, which drops out).  The one statement of this arithmetic: k_fs_gate takes a
+// candidate's own columns, k_fs_gram every other candidate's.
+__device__ __forceinline__ void fs_candidate_q(const double* rec, const int* rows, const double* col, int n3, double (&Q)[3][3]) {
+  const double A[3][3] = {{rec[3], rec[4], rec[5]}, {rec[6], rec[7], rec[8]}, {0.0, 0.0, -1.0}};
+  const double B[3][3] = {{rec[9], rec[10], 0.0}, {rec[11], rec[12], 0.0}, {0.0, 0.0, 1.0}};
+  const int ri = rows[0], rj = rows[1];
+#pragma unroll
+  for (int b = 0; b < 3; ++b) {
+    double wi[3] = {0.0, 0.0, 0.0}, wj[3] = {0.0, 0.0, 0.0};
+    if (ri >= 0)
+#pragma unroll
+      for (int r = 0; r < 3; ++r) wi[r] = col[(size_t)b * n3 + 3 * (size_t)ri + r];
+    if (rj >= 0)
+#pragma unroll
+      for (int r = 0; r < 3; ++r) wj[r] = col[(size_t)b * n3 + 3 * (size_t)rj + r];
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+      Q[a][b] = ((A[a][0] * wi[0] + A[a][1] * wi[1]) + A[a][2] * wi[2]) + ((B[a][0] * wj[0] + B[a][1] * wj[1]) + B[a][2] * wj[2]);
+  }
+}
+
+// The joint table of sgo_candidate_joint (sgo_fsolve.hip): S [3 n][3 n] row-major, then e [n][3], then one double: the
+// factorisation's failure flag
+constexpr int kJointThreads = 256;   // k_joint_subsets' workgroup: 16 x 16 over a trailing block; one thread per candidate of a mask
+inline size_t joint_table_doubles(int n) { return 9 * (size_t)n * n + 3 * (size_t)n + 1; }
+
 struct Mfront {
   MfPlan plan;
   MfrontInfo info;
@@ -120,10 +149,22 @@ int mfront_maps_prepare(sgo_ctx* c, Mfront* m);   // sel.cmap / sel.cmap_off on 
 // ---- kernels of the multi-right-hand-side substitution (sgo_fsolve.hip), one launch each; the host driver is sgo_fsolve.cpp ----
 void launch_fs_rhs_columns(hipStream_t s, int ncols, int n3, const double* src, const int* pos_h, double* panel);
 void launch_fs_rhs_candidates(hipStream_t s, const FsCandDev& C, int t0, int t1, const double* poses, int n3, double* panel);   // panel: zeroed
+void launch_fs_records(hipStream_t s, const FsCandDev& C, const double* poses);   // every candidate's record, no panel
 void launch_fs_forward(hipStream_t s, const MfDev& M, const MfSelDev& Z, const MfFsDev& Fs, int lvl0, int count, int panels, size_t lds, double* Y,
                        double* U, int n3);
 void launch_fs_backward(hipStream_t s, const MfDev& M, int lvl0, int count, int panels, size_t lds, const double* Y, double* X, int n3);
 void launch_fs_gate(hipStream_t s, const FsCandDev& C, int t0, int t1, const double* W, int n3, double chi2_max, const int* flags, double* out);
 bool fs_prepare_device();   // the two substitution kernels' dynamic LDS
+// ---- the joint table of a candidate set and its subsets (sgo_candidate_joint / sgo_joint_subsets / sgo_joint_pairs) ----
+// G[3 s + a][3 t + b] = Q_st[a][b] for every candidate s of C and the candidates t of [t0, t1), whose columns are W
+void launch_fs_gram(hipStream_t s, const FsCandDev& C, int t0, int t1, const double* W, int n3, double* G);
+// table = S (symmetrised G + blockdiag(Omega^-1)), e, the failure flag (flags == nullptr: 0)
+void launch_fs_joint_table(hipStream_t s, const FsCandDev& C, const double* G, const int* flags, double* table);
+// d2 of `count` subsets of the table of n candidates, one workgroup each: mask rows [count][n], or (mask == nullptr) the one- and
+// two-element subsets number b0 .. b0 + count of the pairs' triangle, written to both places of d2 [n][n].  rows_cap: the scalar
+// rows the dynamic LDS holds.
+void launch_joint_subsets(hipStream_t s, const double* table, int n, const uint8_t* mask, int b0, int count, int rows_cap, double* d2);
+bool joint_prepare_device();   // the subset kernel's dynamic LDS
+inline size_t joint_lds_bytes(int rows) { return sizeof(double) * (size_t)(rows + 1) * (size_t)(rows | 1) + sizeof(double) * (size_t)std::max(rows, 1); }
 
 }  // namespace sgo
