@@ -1179,6 +1179,16 @@ class SparseOptimizer : public OptimizableGraph {
     return true;
   }
 
+  // sgoSetHypothesesWorkspace(bytes): the device memory sgoOptimizeHypotheses may take for per-hypothesis copies on a graph of the
+  // multifrontal path, where it then shares every launch among many hypotheses (sgo_set_hypotheses_workspace of include/sgo.h; 0,
+  // the default: one hypothesis after the other; never more than `bytes` is allocated).  Kept by the optimiser and forwarded
+  // whenever the graph goes to the device; false for a negative value.
+  bool sgoSetHypothesesWorkspace(long long bytes) {
+    if (bytes < 0) return false;
+    _hypothesesWorkspace = bytes;
+    return true;
+  }
+
   // ---- graph files (OptimizableGraph::load / save of g2o, for the types of this backend's device path):
   //   VERTEX_SE2 id x y theta | EDGE_SE2 i j dx dy dtheta o11 o12 o13 o22 o23 o33 | FIX id...
   // load() creates the objects and keeps them alive for the optimiser's lifetime (everything the CALLER adds
@@ -1487,6 +1497,7 @@ class SparseOptimizer : public OptimizableGraph {
         return false;
       }
     }
+    sgo_set_hypotheses_workspace(_ctx, (int64_t)_hypothesesWorkspace);
     const int V = (int)_activeVertices.size(), E = (int)_activeEdges.size();
     std::vector<double> poses(3 * (size_t)V);
     for (int k = 0; k < V; ++k) {
@@ -1619,6 +1630,7 @@ class SparseOptimizer : public OptimizableGraph {
   std::vector<OptimizableGraph::Vertex*> _activeVertices;
   std::vector<OptimizableGraph::Edge*> _activeEdges;
   sgo_ctx* _ctx = nullptr;
+  long long _hypothesesWorkspace = 0;   // sgoSetHypothesesWorkspace
   bool _graphOnDevice = false;
   struct Marshalled {   // what the device holds, as it was marshalled
     std::vector<int32_t> vid, ei, ej, kind;

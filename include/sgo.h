@@ -262,7 +262,8 @@ int sgo_optimize_gn_until(sgo_ctx* ctx, int32_t max_iters, double gain_tol, sgo_
  * each on its own copy of what the kernel writes (workspaces of the context's, grown on demand; SGO_ENOMEM with the context intact
  * when they do not fit), the resident factor untouched -- and SGO_HYP_SEQUENTIAL on every other single-GPU path: the host loop
  * above inside the call, the resident solver's own arrays serving every hypothesis and the hierarchy's coarse operators refreshed
- * by the next solve as after any sgo_set_edge_information.  B == 0 returns SGO_HYP_BATCHED and does nothing.
+ * by the next solve as after any sgo_set_edge_information (a multifrontal_cholesky context that has been granted memory batches
+ * too: sgo_set_hypotheses_workspace below).  B == 0 returns SGO_HYP_BATCHED and does nothing.
  * SGO_EINVAL, with nothing changed and no output written: B < 0, max_iters outside [0, SGO_MAX_ITERS], a NULL edge_off or res
  * with B > 0, a non-finite gain_tol or poses0 entry, a multi-GPU context (sgo_debug_set_shard's emulation included), an active
  * incremental overlay, and a hypothesis that would leave a free pose without any incident edge of non-zero information
@@ -283,6 +284,39 @@ int sgo_optimize_gn_hypotheses(sgo_ctx* ctx, int32_t B, int32_t max_iters, doubl
  * non-zero information, -1 when there is none, SGO_EINVAL for a NULL buffer, a negative count or an endpoint outside [0, V). */
 int32_t sgo_hypothesis_isolated_vertex(int32_t V, const uint8_t* fixed, int32_t E, const int32_t* ei, const int32_t* ej,
                                        const double* info, const uint8_t* off);
+
+/* (later additions, version 107) The batched route of sgo_optimize_gn_hypotheses on a multifrontal_cholesky context (DESIGN.md
+ * section 5i-2).  It is opt-in: every hypothesis of a launch chain owns a copy of everything the factorisation writes -- the frontal
+ * arena above all, up to 1 GiB -- and the library does not take that memory unasked.
+ *
+ * sgo_set_hypotheses_workspace grants the context max_bytes of device memory for those copies; 0 (the default) is the behaviour
+ * described above, exactly.  The grant is the context's: it survives sgo_set_graph_se2, the workspace is allocated by the first call
+ * that uses it, grown on demand and freed by sgo_destroy.  A negative value is refused (SGO_EINVAL).  It has no effect on direct_ldlt
+ * contexts (always SGO_HYP_BATCHED) or on PCG contexts (always SGO_HYP_SEQUENTIAL).
+ *
+ * With chunk = sgo_hypotheses_chunk(sgo_hypotheses_bytes(ctx, max_iters, edge_chi2 != NULL), max_bytes, B) >= 2,
+ * sgo_optimize_gn_hypotheses on a multifrontal context runs its B hypotheses in ceil(B / chunk) launch chains -- the launches of one
+ * sgo_optimize_gn_until, each shared by the chain's hypotheses, so that the upper levels of the elimination tree fill the chip -- and
+ * returns SGO_HYP_BATCHED; otherwise it takes the sequential route.  Argument checks and refusals are the same on both routes and
+ * come first.  Everything a hypothesis returns but edge_chi2 is bit for bit what the sequential route returns, whatever the chunk;
+ * edge_chi2 is e^T Omega e with the resident rows in one pass behind the chain (an active edge: the very term of the hypothesis'
+ * final chi2).  A hypothesis that fails or that the gain rule stops costs its chain nothing more and disturbs no neighbour.
+ * UNLIKE the sequential route, the batched one writes nothing of the resident solver: the factor and its arrays (sgo_debug_mfront_array),
+ * the poses and the informations are not those of the last hypothesis afterwards but what they were before the call.
+ * SGO_ENOMEM, with the context intact, when the workspace cannot be allocated.
+ * The grant is a hard bound: the workspace this route allocates is chunk * sgo_hypotheses_bytes(...) bytes exactly, with no head-room,
+ * and so never more than max_bytes.  (A workspace the context already holds -- from a larger grant or from a direct_ldlt graph -- is
+ * reused as it is and not shrunk.)  sgo_hypotheses_workspace_bytes: the bytes the context's hypotheses workspace holds now, 0 before
+ * the first call that needed it, < 0 for a NULL context.
+ *
+ * sgo_hypotheses_bytes: the device memory one hypothesis takes on the resident graph for these arguments; 0 where there is no batched
+ * multifrontal route (another solver path, an active incremental overlay, a multi-GPU context), < 0 for a bad context or max_iters.
+ * sgo_hypotheses_chunk (pure: no context, no GPU): hypotheses per launch chain, min(B, budget / per, 65535); 0 -- the sequential
+ * route -- when that is below 2 or per_hypothesis_bytes <= 0. */
+int sgo_set_hypotheses_workspace(sgo_ctx* ctx, int64_t max_bytes);
+int64_t sgo_hypotheses_bytes(sgo_ctx* ctx, int32_t max_iters, int32_t want_edge_chi2);
+int64_t sgo_hypotheses_workspace_bytes(sgo_ctx* ctx);
+int32_t sgo_hypotheses_chunk(int64_t per_hypothesis_bytes, int64_t budget_bytes, int32_t B);
 
 /* Replaces: computeActiveErrors(); activeChi2(); activeRobustChi2() (slc.cpp:288, drone.cpp:162-165).
  * Called right after sgo_optimize_gn or sgo_optimize_gn_until it returns the final entries of that call's history bit for bit

@@ -9,7 +9,11 @@ With --loop the call itself is left out and nothing newer than sgo_optimize_gn_u
 checkout (built) of the commit to compare against, alternating with this one in one session.
 At B = 1 the call is also timed with the history alone read back: what it costs beside the bare sgo_optimize_gn_until, which returns
 no poses either.  --max-b N leaves the larger Bs out.
-Usage: python scripts/hypotheses_timing.py [--loop] [--root DIR] [--reps 15] [--round N] [--max-b N]"""
+With --mfront the multifrontal leg runs instead (NOTES.md section 41): on 2 500 / 3 400 and C3s, for B = 16, 64, 256 and gain_tol 0 and
+1e-6, the call on the batched route -- sgo_set_hypotheses_workspace(--budget-gib, default 16) -- against the same call on the
+sequential route of the same context (a grant of 0), with the bytes one hypothesis takes and the chunk the grant gives; fewer
+repetitions at the large Bs (640 / B, at least 3).
+Usage: python scripts/hypotheses_timing.py [--loop | --mfront] [--root DIR] [--reps 15] [--round N] [--max-b N] [--budget-gib G]"""
 import json
 import os
 import sys
@@ -61,11 +65,47 @@ def host_loop(opt, g, masks):
     return done
 
 
+MFRONT_GRAPHS = [("2500/3400", lambda: synth.manhattan(2500, 3400, seed=31, info_mode="full", phi=10.0)),
+                 ("C3s", lambda: synth.config("C3s"))]
+
+
+def mfront_leg(reps, rnd, max_b):
+    budget = int(float(ARGS[ARGS.index("--budget-gib") + 1]) * 2 ** 30) if "--budget-gib" in ARGS else 16 << 30
+    for name, make in MFRONT_GRAPHS:
+        g = make()
+        clo = np.arange(g.V - 1, g.E)
+        with capi.Optimizer(0) as opt:
+            opt.set_graph(*g.arrays())
+            path = opt.solver_description().split(":")[0]
+            per = opt.hypotheses_bytes(20, False)
+            emit(graph=name, path=path, round=rnd, what="bytes per hypothesis", bytes=per, V=int(g.V), E=int(g.E))
+            t, r = timed(lambda: (opt.set_poses(g.poses), opt.optimize_until(20, 0.0))[1], reps)
+            emit(graph=name, path=path, round=rnd, what="until(20, 0.0)", done=r[0], **t)
+            opt.set_poses(g.poses)   # every hypothesis starts from the graph's own poses, not from the optimum the call above left
+            for tol in (0.0, 1e-6):
+                for B in [b for b in (16, 64, 256) if b <= max_b]:
+                    masks = np.zeros((B, g.E), dtype=np.uint8)
+                    masks[np.arange(B), clo[np.arange(B) % clo.size]] = 1
+                    n = max(3, min(reps, 640 // B))
+                    row = {}
+                    for route, grant in (("batched", budget), ("sequential", 0)):
+                        opt.set_hypotheses_workspace(grant)
+                        t, r = timed(lambda: opt.optimize_hypotheses(masks, 20, tol, want=("hist", "poses")), n)
+                        row[route] = t["median_ms"]
+                        emit(graph=name, path=path, round=rnd, what="hypotheses", B=B, gain_tol=tol, grant=grant,
+                             chunk=capi.hypotheses_chunk(per, grant, B), route=int(r["route"]), done_min=int(r["iters_done"].min()),
+                             done_mean=float(r["iters_done"].mean()), **t)
+                    emit(graph=name, path=path, round=rnd, what="sequential / batched", B=B, gain_tol=tol,
+                         ratio=round(row["sequential"] / row["batched"], 2))
+
+
 def main():
     loop_only = "--loop" in ARGS
     reps = int(ARGS[ARGS.index("--reps") + 1]) if "--reps" in ARGS else 15
     rnd = int(ARGS[ARGS.index("--round") + 1]) if "--round" in ARGS else 0
     max_b = int(ARGS[ARGS.index("--max-b") + 1]) if "--max-b" in ARGS else 1 << 30
+    if "--mfront" in ARGS:
+        return mfront_leg(reps, rnd, max_b)
     lib = "loop-only library" if loop_only else "this library"
     for name, make, opts, Bs in GRAPHS:
         g = make()

@@ -37,6 +37,7 @@ SYMBOLS = [
     "sgo_solve_rhs", "sgo_marginals", "sgo_marginals_selected", "sgo_factor_solve", "sgo_candidate_gate",
     "sgo_gain_stop", "sgo_optimize_gn_until", "sgo_optimize_gn_hypotheses", "sgo_hypothesis_isolated_vertex",
     "sgo_candidate_joint", "sgo_joint_subsets", "sgo_joint_pairs",
+    "sgo_set_hypotheses_workspace", "sgo_hypotheses_bytes", "sgo_hypotheses_chunk", "sgo_hypotheses_workspace_bytes",
 ]
 
 # SGO_JOINT_MAX_*: the limits of sgo_candidate_joint's table and of a subset of it
@@ -104,6 +105,12 @@ def hypothesis_isolated_vertex(fixed, ei, ej, info, off) -> int:
     return rc
 
 
+def hypotheses_chunk(per_hypothesis_bytes: int, budget_bytes: int, B: int) -> int:
+    """sgo_hypotheses_chunk: hypotheses per launch chain of the batched multifrontal route, 0 = the sequential route (no context,
+    no GPU)."""
+    return int(lib().sgo_hypotheses_chunk(int(per_hypothesis_bytes), int(budget_bytes), int(B)))
+
+
 class MatchWindow(C.Structure):
     """sgo_match_window (include/sgo.h): one scan-match score window."""
     _fields_ = [("x_index_offset", C.c_int32), ("y_index_offset", C.c_int32), ("scan_index", C.c_int32),
@@ -161,6 +168,13 @@ def lib():
     L.sgo_gain_stop.argtypes = [C.c_double, C.c_double, C.c_double]
     L.sgo_optimize_gn_hypotheses.argtypes = [vp, C.c_int32, C.c_int32, C.c_double, u8, d, C.POINTER(HypothesisResult), d, d, d]
     L.sgo_hypothesis_isolated_vertex.restype = C.c_int32
+    L.sgo_set_hypotheses_workspace.argtypes = [vp, C.c_int64]
+    L.sgo_hypotheses_bytes.restype = C.c_int64
+    L.sgo_hypotheses_bytes.argtypes = [vp, C.c_int32, C.c_int32]
+    L.sgo_hypotheses_workspace_bytes.restype = C.c_int64
+    L.sgo_hypotheses_workspace_bytes.argtypes = [vp]
+    L.sgo_hypotheses_chunk.restype = C.c_int32
+    L.sgo_hypotheses_chunk.argtypes = [C.c_int64, C.c_int64, C.c_int32]
     L.sgo_hypothesis_isolated_vertex.argtypes = [C.c_int32, u8, C.c_int32, i32, i32, d, u8]
     L.sgo_chi2.argtypes = [vp, d, d]
     L.sgo_edge_chi2.argtypes = [vp, d]
@@ -538,6 +552,19 @@ class Optimizer:
         why = C.c_int32(-1)
         rc = self._check(lib().sgo_optimize_gn_until(self._h, max_iters, gain_tol, C.byref(st), C.byref(why)), "sgo_optimize_gn_until")
         return rc, self._stats_dict(rc, st, max_iters), why.value
+
+    def set_hypotheses_workspace(self, max_bytes: int) -> None:
+        """sgo_set_hypotheses_workspace: the device memory optimize_hypotheses may take for per-hypothesis copies on a
+        multifrontal_cholesky context (0, the default: the sequential route)."""
+        self._check(lib().sgo_set_hypotheses_workspace(self._h, int(max_bytes)), "sgo_set_hypotheses_workspace")
+
+    def hypotheses_bytes(self, max_iters: int = 20, want_edge_chi2: bool = True) -> int:
+        """sgo_hypotheses_bytes: bytes one hypothesis takes on the resident graph; 0 where there is no batched multifrontal route."""
+        return int(self._check(lib().sgo_hypotheses_bytes(self._h, max_iters, 1 if want_edge_chi2 else 0), "sgo_hypotheses_bytes"))
+
+    def hypotheses_workspace_bytes(self) -> int:
+        """sgo_hypotheses_workspace_bytes: the device bytes the context's hypotheses workspace holds now."""
+        return int(self._check(lib().sgo_hypotheses_workspace_bytes(self._h), "sgo_hypotheses_workspace_bytes"))
 
     def optimize_hypotheses(self, edge_off, max_iters: int = 20, gain_tol: float = 0.0, poses0=None,
                             want=("hist", "poses", "edge_chi2"), out=None):

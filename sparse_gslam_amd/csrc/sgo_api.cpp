@@ -1317,6 +1317,50 @@ int hypotheses_batched(sgo_ctx* c, int B, int max_iters, double gain_tol, const 
   return SGO_HYP_BATCHED;
 }
 
+// The multifrontal path with a granted workspace (sgo_set_hypotheses_workspace): chains of `chunk` hypotheses, each one pass through
+// mfront_optimize's launches with every grid x chunk (sgo_mfront.h), every result of a chain read once behind it.
+int hypotheses_mfront_batched(sgo_ctx* c, int chunk, int B, int max_iters, double gain_tol, const uint8_t* edge_off, const double* poses0,
+                              sgo_hypothesis_result* res, double* hist, double* poses_out, double* edge_chi2) {
+  const size_t E = (size_t)c->E, V3 = 3 * (size_t)c->V, H = 2 * ((size_t)max_iters + 1);
+  const size_t need = mfront_batch_layout(c->mf, c->V, chunk, max_iters, edge_chi2 != nullptr).bytes;
+  int rc;
+  if (need > c->hyp.ws_cap) {   // need = chunk x per-hypothesis bytes <= the grant, and exactly that is allocated: no head-room
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if ((rc = grow_device(c, &c->hyp.d_ws, &c->hyp.ws_cap, need, false))) {
+      c->err = "sgo_optimize_gn_hypotheses: out of device memory (" + std::to_string(need) + " bytes for chains of " + std::to_string(chunk) + " hypotheses)";
+      return rc;
+    }
+  }
+  char* ws = c->hyp.d_ws;
+  std::vector<double> h_hist((size_t)chunk * H);
+  std::vector<int> h_brief(2 * (size_t)chunk);
+  for (int b0 = 0; b0 < B; b0 += chunk) {
+    const int nb = std::min(chunk, B - b0);
+    const MfBatchLayout L = mfront_batch_layout(c->mf, c->V, nb, max_iters, edge_chi2 != nullptr);
+    HIP_TRY(c, hipMemcpyAsync(ws + L.o_off, edge_off + (size_t)b0 * E, (size_t)nb * E, hipMemcpyHostToDevice, c->stream));
+    if (poses0) HIP_TRY(c, hipMemcpyAsync(ws + L.o_poses, poses0 + V3 * (size_t)b0, sizeof(double) * (size_t)nb * V3, hipMemcpyHostToDevice, c->stream));
+    {
+      Scope sc(c, K_MFRONT_BATCH, (double)nb * mfront_bytes(c->mf, c->E, max_iters), true);
+      const hipError_t he = mfront_optimize_batch(c->mf, c->stream, c->el, c->d_poses, poses0 != nullptr, L, ws, max_iters, gain_tol, edge_chi2 != nullptr);
+      if (he != hipSuccess) {
+        c->err = std::string("multifrontal (batched) launch: ") + hipGetErrorString(he);
+        return SGO_EHIP;
+      }
+    }
+    HIP_TRY(c, hipMemcpyAsync(h_hist.data(), ws + L.o_hist, sizeof(double) * (size_t)nb * H, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(h_brief.data(), ws + L.o_brief, sizeof(int) * 2 * (size_t)nb, hipMemcpyDeviceToHost, c->stream));
+    if (poses_out) HIP_TRY(c, hipMemcpyAsync(poses_out + V3 * (size_t)b0, ws + L.o_poses, sizeof(double) * (size_t)nb * V3, hipMemcpyDeviceToHost, c->stream));
+    if (edge_chi2) HIP_TRY(c, hipMemcpyAsync(edge_chi2 + E * (size_t)b0, ws + L.o_echi2, sizeof(double) * (size_t)nb * E, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    for (int b = 0; b < nb; ++b) {
+      const int done = std::min(std::max(h_brief[2 * (size_t)b], 0), max_iters);
+      hypothesis_record(b0 + b, max_iters, done, h_brief[2 * (size_t)b + 1], h_hist.data() + H * (size_t)b, res, hist);
+    }
+  }
+  prof_flush(c);
+  return SGO_HYP_BATCHED;
+}
+
 // Every other single-GPU path: the host loop itself -- zero rows, the start, optimise, read back, the rows again -- and the
 // resident poses at the end.
 int hypotheses_sequential(sgo_ctx* c, int B, int max_iters, double gain_tol, const uint8_t* edge_off, const double* poses0,
@@ -1418,8 +1462,44 @@ int sgo_optimize_gn_hypotheses(sgo_ctx* c, int32_t B, int32_t max_iters, double 
     }
     read_call_knobs(c);
     if (c->direct) return hypotheses_batched(c, B, max_iters, gain_tol, edge_off, poses0, res, hist, poses_out, edge_chi2);
+    if (c->mf && c->hyp.mf_budget > 0) {
+      const long long per = (long long)mfront_batch_layout(c->mf, c->V, 1, max_iters, edge_chi2 != nullptr).per_hypothesis;
+      const int chunk = rules::hypotheses_chunk(per, c->hyp.mf_budget, B);
+      if (chunk >= 2) return hypotheses_mfront_batched(c, chunk, B, max_iters, gain_tol, edge_off, poses0, res, hist, poses_out, edge_chi2);
+    }
     return hypotheses_sequential(c, B, max_iters, gain_tol, edge_off, poses0, res, hist, poses_out, edge_chi2);
   } SGO_CATCH(c)
+}
+
+int sgo_set_hypotheses_workspace(sgo_ctx* c, int64_t max_bytes) {
+  try {
+    if (!c) return SGO_EINVAL;
+    if (max_bytes < 0) {
+      c->err = "sgo_set_hypotheses_workspace: negative number of bytes";
+      return SGO_EINVAL;
+    }
+    c->hyp.mf_budget = max_bytes;
+    return SGO_OK;
+  } SGO_CATCH(c)
+}
+
+int64_t sgo_hypotheses_bytes(sgo_ctx* c, int32_t max_iters, int32_t want_edge_chi2) {
+  try {
+    const int rc = check_graph(c);
+    if (rc) return rc;
+    if (max_iters < 0 || max_iters > SGO_MAX_ITERS) {
+      c->err = "sgo_hypotheses_bytes: max_iters must be in [0, SGO_MAX_ITERS]";
+      return SGO_EINVAL;
+    }
+    if (!c->mf || c->direct || c->ov.active || multi_gpu_context(c)) return 0;
+    return (int64_t)mfront_batch_layout(c->mf, c->V, 1, max_iters, want_edge_chi2 != 0).per_hypothesis;
+  } SGO_CATCH(c)
+}
+
+int64_t sgo_hypotheses_workspace_bytes(sgo_ctx* c) { return c ? (int64_t)c->hyp.ws_cap : (int64_t)SGO_EINVAL; }
+
+int32_t sgo_hypotheses_chunk(int64_t per_hypothesis_bytes, int64_t budget_bytes, int32_t B) {
+  return rules::hypotheses_chunk(per_hypothesis_bytes, budget_bytes, B);
 }
 
 double sgo_debug_spmv0_us(sgo_ctx* c, int mode, int variant, int reps) { return debug_spmv0_us(c, mode, variant, reps); }

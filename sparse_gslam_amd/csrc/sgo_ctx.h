@@ -256,9 +256,13 @@ struct sgo_ctx {
 
   // sgo_optimize_gn_hypotheses on the single-launch path: every hypothesis' copy of what k_direct writes, its information rows and
   // its results (sgo_direct.h: DirectBatchLayout); grown on demand, kept across graphs.
+  // On the multifrontal path the same workspace holds the copies of one launch chain (sgo_mfront.h: MfBatchLayout) when the caller
+  // has granted mf_budget bytes for them (sgo_set_hypotheses_workspace; 0: the sequential route); the grant is the context's and
+  // outlives its graphs.
   struct Hypotheses {
     char* d_ws = nullptr;
     size_t ws_cap = 0;
+    int64_t mf_budget = 0;
   } hyp;
 
   // Device scratch of sgo_marginals (sgo_marginals.cpp): the result blocks [npairs][9], the pairs' internal rows and the pairs
@@ -362,13 +366,15 @@ int upload(sgo_ctx* c, T** p, const std::vector<T>& v) {
 }
 
 // Device scratch of the marginals' and the factor's calls that is kept across graphs: grown on demand, hipMalloc.
+// headroom: a quarter more than asked for, so that a slowly growing demand does not allocate at every call; false where the caller
+// of the library has bounded the allocation (sgo_set_hypotheses_workspace) -- then `count` elements exactly.
 template <class T>
-int grow_device(sgo_ctx* c, T** p, size_t* cap, size_t count) {
+int grow_device(sgo_ctx* c, T** p, size_t* cap, size_t count, bool headroom = true) {
   if (count <= *cap) return SGO_OK;
   if (*p) hipFree(*p);   // (every call that used it has synchronised the stream)
   *p = nullptr;
   *cap = 0;
-  const size_t want = count + count / 4 + 64;
+  const size_t want = headroom ? count + count / 4 + 64 : count;
   if (hipMalloc((void**)p, want * sizeof(T)) != hipSuccess) {
     (void)hipGetLastError();
     c->err = "out of device memory (" + std::to_string(want * sizeof(T)) + " bytes of marginal scratch)";

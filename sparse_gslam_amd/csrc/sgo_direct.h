@@ -68,6 +68,11 @@ struct DirectBatchLayout {
 DirectBatchLayout direct_batch_layout(const Direct* d, int V, int B, int iters);
 hipError_t direct_optimize_batch(Direct* d, hipStream_t s, const EdgeListDev& el, const double* d_poses_res, bool own_poses,
                                  const DirectBatchLayout& L, char* ws, int iters, double gain_tol, bool want_edge_chi2);
+// What a batched launch of either factorisation path (this one, sgo_mfront.h) needs before it starts, one launch of k_hyp_prepare:
+// hypothesis b's information rows at info_b + b info_stride ([6][E]: 0 where off[b][E] is set, info_res elsewhere) and, with
+// poses_res != nullptr (the caller gave no starting poses), its copy of the resident poses at poses_b + b poses_stride.
+void launch_hyp_prepare(hipStream_t s, int B, int E, int V, const double* info_res, const unsigned char* off, double* info_b, size_t info_stride,
+                        const double* poses_res, double* poses_b, size_t poses_stride);
 // Test hooks (include/sgo.h, SGO_DR_*; size-query convention of the other hooks).  direct_plan_array: one table of the host
 // analysis alone -- no stream, no arena; SGO_ENOTHING with *why set when the graph does not qualify.  direct_debug_array: the
 // same tables read back from the device and what the last direct_optimize left; SGO_ENOTHING before the first with iters > 0.

@@ -1334,6 +1334,13 @@ DirectBatchLayout direct_batch_layout(const Direct* d, int V, int B, int iters) 
   return L;
 }
 
+void launch_hyp_prepare(hipStream_t s, int B, int E, int V, const double* info_res, const unsigned char* off, double* info_b, size_t info_stride,
+                        const double* poses_res, double* poses_b, size_t poses_stride) {
+  const int items = std::max(std::max(E, 3 * V), 1);
+  SGO_LAUNCH(k_hyp_prepare, dim3((unsigned)B, (unsigned)std::min((items + 255) / 256, 1024)), dim3(256), 0, s, B, E, 3 * V, info_res, off, info_b,
+             info_stride, poses_res, poses_b, poses_stride);
+}
+
 hipError_t direct_optimize_batch(Direct* d, hipStream_t s, const EdgeListDev& el, const double* d_poses_res, bool own_poses,
                                  const DirectBatchLayout& L, char* ws, int iters, double gain_tol, bool want_edge_chi2) {
   if (L.B <= 0) return hipSuccess;
@@ -1352,9 +1359,8 @@ hipError_t direct_optimize_batch(Direct* d, hipStream_t s, const EdgeListDev& el
   bt.info_res = el.info;
   bt.edge_chi2 = want_edge_chi2 ? reinterpret_cast<double*>(ws + L.o_echi2) : nullptr;
   bt.brief = reinterpret_cast<int2*>(ws + L.o_brief);
-  const int items = std::max(std::max(L.E, 3 * L.V), 1);
-  SGO_LAUNCH(k_hyp_prepare, dim3((unsigned)L.B, (unsigned)std::min((items + 255) / 256, 1024)), dim3(256), 0, s, L.B, L.E, 3 * L.V, el.info,
-             reinterpret_cast<const unsigned char*>(ws + L.o_off), eb.info, L.s_info, own_poses ? nullptr : d_poses_res, poses, L.s_poses);
+  launch_hyp_prepare(s, L.B, L.E, L.V, el.info, reinterpret_cast<const unsigned char*>(ws + L.o_off), eb.info, L.s_info,
+                     own_poses ? nullptr : d_poses_res, poses, L.s_poses);
   double* hist = reinterpret_cast<double*>(ws + L.o_hist);
   DirectResult* res = reinterpret_cast<DirectResult*>(ws + L.o_res);
 #define SGO_DIRECT_BATCH(XG, KINDS) \

@@ -384,6 +384,7 @@ enum KernelId : int {
   K_FS_GRAM,            // sgo_candidate_joint / sgo_joint_subsets / sgo_joint_pairs (sgo_fsolve.hip)
   K_FS_JOINT_TABLE,
   K_JOINT_SUBSETS,
+  K_MFRONT_BATCH,       // sgo_optimize_gn_hypotheses' batched route on the multifrontal path: all launches of one chain (sgo_mfront.h)
   K_COUNT
 };
 extern const char* const kKernelNames[K_COUNT];

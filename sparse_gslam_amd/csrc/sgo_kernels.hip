@@ -40,7 +40,8 @@ const char* const kKernelNames[K_COUNT] = {
     "k_ptilde_values", "k_ptilde_values @level0", "k_up_fold", "k_prolong_fold @level0", "k_jacobi0_restrict @level0",
     "k_mf_edges + k_mf_factor + k_mf_solve + k_mf_update (multifrontal optimize)", "k_rhs_inject", "k_rhs_restore", "k_cov_gather",
     "k_mf_edges + k_mf_merge + k_mf_panels (multifrontal factor phase)", "k_si_gather", "k_si_panels", "k_si_result",
-    "k_fs_rhs", "k_fs_forward", "k_fs_backward", "k_fs_gate", "k_fs_gram", "k_fs_joint_table", "k_joint_subsets"};
+    "k_fs_rhs", "k_fs_forward", "k_fs_backward", "k_fs_gate", "k_fs_gram", "k_fs_joint_table", "k_joint_subsets",
+    "mfront_batch"};
 
 namespace {
 

@@ -119,6 +119,28 @@ const MfrontInfo& mfront_info(const Mfront* m);
 hipError_t mfront_optimize(Mfront* m, hipStream_t s, const EdgeListDev& el, double* d_poses, int iters, double* d_hist,
                            DirectResult* d_res, const double* until = nullptr);
 double mfront_bytes(const Mfront* m, int E, int iters);
+// sgo_optimize_gn_hypotheses on this path when the caller has granted the memory (sgo_set_hypotheses_workspace): L.B hypotheses of
+// the resident graph as ONE chain of launches -- mfront_optimize's in until-mode, every grid x L.B, the kernels' batched
+// instantiations (always with the gain rule; gain_tol <= 0 never stops).  Hypothesis b works on copy b of everything mfront_optimize
+// writes -- elem, x, invd, yinv, the partial sums, the flags, the arena, its information rows, poses, history and DirectResult --
+// in one workspace of the caller's laid out by mfront_batch_layout (offsets in bytes, strides in doubles from one hypothesis to the
+// next; bytes = B x per_hypothesis whatever B is); the plan's tables are shared and the resident image is not written.  It obeys
+// its own flags word: after a failure or a stop its workgroups return at once, no host read inside the chain.  The caller puts
+// the masks [B][E] at o_off and, with own_poses, the starting poses [B][V][3] at o_poses before the call; after it, it reads hist
+// [B][iters + 1][2] at o_hist, {updates applied, DirectResult::fail} [B] at o_brief, the poses at o_poses and, if asked for (in the
+// layout too), e^T Omega e with the resident rows [B][E] at o_echi2.  The arithmetic, the grids in x and the order of every sum are
+// mfront_optimize's: hypothesis b is bit for bit that call on the graph with its rows zeroed.
+struct MfBatchLayout {
+  int B = 0, V = 0, E = 0;
+  size_t hist_stride = 0;
+  size_t s_elem = 0, s_x = 0, s_yinv = 0, s_arena = 0, s_info = 0, s_poses = 0;
+  size_t o_off = 0, o_info = 0, o_poses = 0, o_hist = 0, o_echi2 = 0, o_brief = 0, o_res = 0, o_elem = 0, o_x = 0, o_invd = 0, o_yinv = 0,
+         o_partials = 0, o_flags = 0, o_arena = 0;
+  size_t per_hypothesis = 0, bytes = 0;
+};
+MfBatchLayout mfront_batch_layout(const Mfront* m, int V, int B, int iters, bool want_edge_chi2);
+hipError_t mfront_optimize_batch(Mfront* m, hipStream_t s, const EdgeListDev& el, const double* d_poses_res, bool own_poses,
+                                 const MfBatchLayout& L, char* ws, int iters, double gain_tol, bool want_edge_chi2);
 // The factor phase of one iteration alone, at the current poses: edges (elements, chi2 partials), then merge and panels per level --
 // mfront_optimize's own launches up to and excluding the substitution and the update.  Clears the failure flags first; x is untouched.
 hipError_t mfront_factorize(Mfront* m, hipStream_t s, const EdgeListDev& el, const double* d_poses, double* d_hist, DirectResult* d_res);

@@ -8,6 +8,8 @@
 //                 columns factorised in panels of 16                                                  } factorisation, graphs.cpp:19
 //   k_mf_solve    one launch per level, top-down: backward substitution
 //   k_mf_update   SparseOptimizer::update -> VertexSE2::oplusImpl
+// Every kernel has a batched instantiation (blockIdx.y = one closure hypothesis of sgo_optimize_gn_hypotheses on its own copy of what
+// the kernels write: mfront_optimize_batch, MfBatch in sgo_mfront_dev.h); the unbatched one is the text below without its first line.
 // A front's matrix is column-major with leading dimension ld, lower triangle, rows 0 .. m-1 = its poses' scalar rows (own
 // first, then boundary, both in elimination order) and row m = the right-hand side: the Cholesky factor of [[H, b], [b^T, .]]
 // carries L^-1 b in its last row, and the Schur complement's last row is the children's contribution to the parent's
@@ -19,6 +21,7 @@
 #include <cstdio>
 #include <cstring>
 #include <memory>
+#include <type_traits>
 #include <vector>
 
 #include "sgo_device.h"
@@ -90,10 +93,12 @@ __device__ __forceinline__ double mf_rsqrt(double x) {
 }
 
 // ---------------------------------------------------------------------------- k_mf_edges
-// (KINDS: the edges carry robust kernels other than DCS, sgo_device.h)
-template <bool KINDS>
+// (KINDS: the edges carry robust kernels other than DCS, sgo_device.h; BATCH: blockIdx.y is the hypothesis, MfBatch in
+// sgo_mfront_dev.h -- in every kernel below the slice is the one thing the batched instantiation adds)
+template <bool KINDS, bool BATCH>
 __global__ __launch_bounds__(kBlock) void k_mf_edges(MfDev M, EdgeListDev el, const double* __restrict__ poses, int it, int chi2_only,
-                                                     double* __restrict__ hist, DirectResult* __restrict__ res) {
+                                                     double* __restrict__ hist, DirectResult* __restrict__ res, std::conditional_t<BATCH, MfBatch, MfSingle> bt) {
+  if constexpr (BATCH) mf_slice(bt, M, &el, &poses, &hist, &res);
   if (blockIdx.x == 0 && threadIdx.x == 0) res->stamp[2 * it] = (unsigned long long)wall_clock64();
   if (M.flags[0]) return;
   const size_t ns = (size_t)el.E;
@@ -177,7 +182,9 @@ __device__ __forceinline__ void mf_chi2_sum(const double* __restrict__ partials,
 // operand row is the child row its parent row maps to), so no update matrix is ever written or read back, and elements no
 // child reaches are written as zeros (no clearing pass).  The edges' own contributions are added by k_mf_panels afterwards.
 // One wave per tile; fixed order of the two children: bitwise reproducible.
-__global__ __launch_bounds__(kBlock) void k_mf_merge(MfDev M, int t0, int t1) {
+template <bool BATCH>
+__global__ __launch_bounds__(kBlock) void k_mf_merge(MfDev M, int t0, int t1, std::conditional_t<BATCH, MfBatch, MfSingle> bt) {
+  if constexpr (BATCH) mf_slice(bt, M);
   if (M.flags[0]) return;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, lr = lane & 15, lk = lane >> 4;
   for (int t = t0 + (int)blockIdx.x * kWavesPerBlock + wave; t < t1; t += (int)gridDim.x * kWavesPerBlock) {
@@ -228,8 +235,10 @@ __global__ __launch_bounds__(kBlock) void k_mf_merge(MfDev M, int t0, int t1) {
 //   D2  the 16 x 16 Cholesky on wave 0 and the inverse of its factor on wave 1, one pivot behind (rows on the lanes, columns in
 //       registers, broadcasts by v_readlane; wave 0 hands every finished column and pivot to wave 1 through LDS);
 //   D3  L21 = P21 L11^-T on the matrix cores, refined once against L11, straight to the front's matrix.
+template <bool BATCH>
 __global__ __launch_bounds__(kMfThreads) void k_mf_panels(MfDev M, int lvl0, int it, int stamp_slot, int nparts, double* __restrict__ hist,
-                                                         DirectResult* __restrict__ res) {
+                                                         DirectResult* __restrict__ res, std::conditional_t<BATCH, MfBatch, MfSingle> bt) {
+  if constexpr (BATCH) mf_slice<double*>(bt, M, nullptr, nullptr, &hist, &res);
   extern __shared__ double Pn[];               // panel: column c at Pn + c * ldp, rows relative to k0 
   __shared__ double Yt[kMfPanel * kMfPanel];   // Yt[t * 16 + c] = (L11^-1)[c][t]
   __shared__ double LX[kMfPanel][kMfPanel];    // LX[j][i] = L11[i][j]: column j as wave 0 finishes it
@@ -534,7 +543,9 @@ __global__ __launch_bounds__(kMfThreads) void k_mf_panels(MfDev M, int lvl0, int
 constexpr int kMfSolveOwn = 144;   // own scalar rows up to which L11 is held in LDS (packed: 83.5 KB)
 constexpr int kMfSolveBnd = 256;   // ... and boundary scalar rows up to which the whole block L21 is requested in one go
 constexpr int kMfSolveCols = (kMfSolveOwn + kMfNW - 1) / kMfNW;   // columns per wave
-__global__ __launch_bounds__(kMfThreads) void k_mf_solve(MfDev M, int lvl0) {
+template <bool BATCH>
+__global__ __launch_bounds__(kMfThreads) void k_mf_solve(MfDev M, int lvl0, std::conditional_t<BATCH, MfBatch, MfSingle> bt) {
+  if constexpr (BATCH) mf_slice(bt, M);
   extern __shared__ double Ls[];               // row r of L11 at r (r + 1) / 2
   __shared__ double xs[kMfMaxDim + 1];
   __shared__ double tt[kMfSolveOwn];
@@ -650,7 +661,9 @@ __global__ __launch_bounds__(kMfThreads) void k_mf_solve(MfDev M, int lvl0) {
 }
 
 // ---------------------------------------------------------------------------- k_mf_update
-__global__ __launch_bounds__(kBlock) void k_mf_update(MfDev M, double* __restrict__ poses, int it) {
+template <bool BATCH>
+__global__ __launch_bounds__(kBlock) void k_mf_update(MfDev M, double* __restrict__ poses, int it, std::conditional_t<BATCH, MfBatch, MfSingle> bt) {
+  if constexpr (BATCH) mf_slice(bt, M, nullptr, &poses);
   if (M.flags[0]) return;
   if (M.flags[2]) {   // (set by the launches before this one: every workgroup sees the same value)
     if (blockIdx.x == 0 && threadIdx.x == 0) {
@@ -688,7 +701,9 @@ constexpr int kMfStopped = 3;
 // One wave, between k_mf_edges and the first level's k_mf_panels of iteration `it` (2 <= it < iters): chi2 of this iteration from
 // the partial sums in mf_chi2_sum's order -- the bits the panel kernel would write --, then rules::gain_stop against the iteration
 // before.  A stop precedes every write of this iteration to the arena, x, invd and yinv; the elements are k_mf_edges' already.
-__global__ __launch_bounds__(64) void k_mf_gain_stop(MfDev M, int it, int nparts, double gain_tol, double* __restrict__ hist) {
+template <bool BATCH>
+__global__ __launch_bounds__(64) void k_mf_gain_stop(MfDev M, int it, int nparts, double gain_tol, double* __restrict__ hist, std::conditional_t<BATCH, MfBatch, MfSingle> bt) {
+  if constexpr (BATCH) mf_slice<double*>(bt, M, nullptr, nullptr, &hist);
   if (M.flags[0]) return;
   mf_chi2_sum(M.partials, nparts, hist, it, threadIdx.x);
   if (threadIdx.x == 0 && rules::gain_stop(hist[2 * it - 1], hist[2 * it + 1], gain_tol)) M.flags[0] = kMfStopped;
@@ -696,7 +711,10 @@ __global__ __launch_bounds__(64) void k_mf_gain_stop(MfDev M, int it, int nparts
 
 // k_mf_finish after a call that may have stopped: done = the updates applied, hist[2 done] stays what k_mf_gain_stop wrote (the
 // closing sum is not redone), the call's end goes where the plain call of `done` iterations puts it, and the stop word is cleared.
-__global__ __launch_bounds__(64) void k_mf_finish_until(MfDev M, int iters, int nparts, double* __restrict__ hist, DirectResult* __restrict__ res) {
+template <bool BATCH>
+__global__ __launch_bounds__(64) void k_mf_finish_until(MfDev M, int iters, int nparts, double* __restrict__ hist, DirectResult* __restrict__ res,
+                                                        std::conditional_t<BATCH, MfBatch, MfSingle> bt) {
+  if constexpr (BATCH) mf_slice<double*>(bt, M, nullptr, nullptr, &hist, &res);
   const int f0 = M.flags[0];
   if (!f0) mf_chi2_sum(M.partials, nparts, hist, iters, threadIdx.x);   // the closing pass
   if (threadIdx.x != 0) return;
@@ -709,6 +727,28 @@ __global__ __launch_bounds__(64) void k_mf_finish_until(MfDev M, int iters, int 
   if (failed) res->stamp[2 * M.flags[3] + 2] = now;
   else res->stamp[2 * M.flags[3] + 1] = now;   // (not stopped: flags[3] == iters)
   if (f0 == kMfStopped) M.flags[0] = 0;
+  if constexpr (BATCH) bt.brief[blockIdx.y] = make_int2(M.flags[3], failed ? f0 : 0);
+}
+
+// e^T Omega e of every edge at hypothesis blockIdx.y's final poses with the RESIDENT rows `el.info` (one pass behind the chain): an
+// edge the hypothesis switched off reports what it would cost, an active one the very e2 of its closing k_mf_edges pass (same
+// operands, same statements), an edge whose resident row is zero reports 0.
+template <bool KINDS>
+__global__ __launch_bounds__(kBlock) void k_mf_edge_chi2(EdgeListDev el, int E, const double* __restrict__ poses, size_t poses_stride,
+                                                         double* __restrict__ out) {
+  const size_t ns = (size_t)el.E;
+  poses += blockIdx.y * poses_stride;
+  out += blockIdx.y * (size_t)E;
+  for (int e = blockIdx.x * kBlock + threadIdx.x; e < E; e += gridDim.x * kBlock) {
+    EdgeOperands p;
+    edge_operands(el, ns, e, poses, p);
+    double sz, cz, er[3];
+    sincos(p.zt, &sz, &cz);
+    edge_error(p, sz, cz, er);
+    EdgeWeight Wt;
+    edge_weight<KINDS>(el, ns, e, er, Wt);
+    out[e] = Wt.e2;
+  }
 }
 
 }  // namespace
@@ -881,10 +921,11 @@ Mfront* mfront_create(hipStream_t s, DevArena* arena, int V, int n, const int* f
   D.arena = (double*)(base + parts[i_ar].at);
   D.dbg = debug ? (long long*)(base + parts[i_db].at) : nullptr;
   // (per call: the attribute belongs to the current device's copy of the kernel, and a process may hold contexts on several)
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_mf_panels), hipFuncAttributeMaxDynamicSharedMemorySize,
-                          (int)sizeof(double) * kMfPanel * ((kMfMaxDim + 2) | 1)) != hipSuccess ||
-      hipFuncSetAttribute(reinterpret_cast<const void*>(&k_mf_solve), hipFuncAttributeMaxDynamicSharedMemorySize,
-                          (int)sizeof(double) * kMfSolveOwn * (kMfSolveOwn + 1) / 2) != hipSuccess) {
+  constexpr int kPanelLds = (int)sizeof(double) * kMfPanel * ((kMfMaxDim + 2) | 1), kSolveLds = (int)sizeof(double) * kMfSolveOwn * (kMfSolveOwn + 1) / 2;
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_mf_panels<false>), hipFuncAttributeMaxDynamicSharedMemorySize, kPanelLds) != hipSuccess ||
+      hipFuncSetAttribute(reinterpret_cast<const void*>(&k_mf_solve<false>), hipFuncAttributeMaxDynamicSharedMemorySize, kSolveLds) != hipSuccess ||
+      hipFuncSetAttribute(reinterpret_cast<const void*>(&k_mf_panels<true>), hipFuncAttributeMaxDynamicSharedMemorySize, kPanelLds) != hipSuccess ||
+      hipFuncSetAttribute(reinterpret_cast<const void*>(&k_mf_solve<true>), hipFuncAttributeMaxDynamicSharedMemorySize, kSolveLds) != hipSuccess) {
     (void)hipGetLastError();
     if (why) *why = "the device does not grant the kernels' dynamic LDS";
     return nullptr;
@@ -902,27 +943,27 @@ hipError_t mfront_optimize(Mfront* m, hipStream_t s, const EdgeListDev& el, doub
   const int ugrid = std::max(1, std::min((D.n + kBlock - 1) / kBlock, 1024));
   for (int it = 0; it <= iters; ++it) {
     const bool last = it == iters;
-    if (el.kinds) hipLaunchKernelGGL(k_mf_edges<true>, dim3(egrid), dim3(kBlock), 0, s, D, el, (const double*)d_poses, it, last ? 1 : 0, d_hist, d_res);
-    else hipLaunchKernelGGL(k_mf_edges<false>, dim3(egrid), dim3(kBlock), 0, s, D, el, (const double*)d_poses, it, last ? 1 : 0, d_hist, d_res);
+    if (el.kinds) hipLaunchKernelGGL((k_mf_edges<true, false>), dim3(egrid), dim3(kBlock), 0, s, D, el, (const double*)d_poses, it, last ? 1 : 0, d_hist, d_res, MfSingle{});
+    else hipLaunchKernelGGL((k_mf_edges<false, false>), dim3(egrid), dim3(kBlock), 0, s, D, el, (const double*)d_poses, it, last ? 1 : 0, d_hist, d_res, MfSingle{});
     if (last) break;
-    if (until && rules::gain_stop_applies(it, iters)) hipLaunchKernelGGL(k_mf_gain_stop, dim3(1), dim3(64), 0, s, D, it, egrid, *until, d_hist);
+    if (until && rules::gain_stop_applies(it, iters)) hipLaunchKernelGGL(k_mf_gain_stop<false>, dim3(1), dim3(64), 0, s, D, it, egrid, *until, d_hist, MfSingle{});
     for (int h = 0; h <= P.height; ++h) {
       const int cnt = P.level_ptr[h + 1] - P.level_ptr[h];
       if (h > 0) {
         const int nt = m->mtile_ptr[h + 1] - m->mtile_ptr[h];
         const int grid = std::max(1, std::min((nt + kWavesPerBlock - 1) / kWavesPerBlock, 8192));
-        hipLaunchKernelGGL(k_mf_merge, dim3(grid), dim3(kBlock), 0, s, D, m->mtile_ptr[h], m->mtile_ptr[h + 1]);
+        hipLaunchKernelGGL(k_mf_merge<false>, dim3(grid), dim3(kBlock), 0, s, D, m->mtile_ptr[h], m->mtile_ptr[h + 1], MfSingle{});
       }
-      hipLaunchKernelGGL(k_mf_panels, dim3(cnt), dim3(kMfThreads), (size_t)m->level_lds[h], s, D, P.level_ptr[h], it, h == 0 ? 2 * it + 1 : -1,
-                         h == 0 ? egrid : 0, d_hist, d_res);
+      hipLaunchKernelGGL(k_mf_panels<false>, dim3(cnt), dim3(kMfThreads), (size_t)m->level_lds[h], s, D, P.level_ptr[h], it, h == 0 ? 2 * it + 1 : -1,
+                         h == 0 ? egrid : 0, d_hist, d_res, MfSingle{});
     }
     for (int h = P.height; h >= 0; --h) {
       const int cnt = P.level_ptr[h + 1] - P.level_ptr[h];
-      hipLaunchKernelGGL(k_mf_solve, dim3(cnt), dim3(kMfThreads), (size_t)m->level_solve_lds[h], s, D, P.level_ptr[h]);
+      hipLaunchKernelGGL(k_mf_solve<false>, dim3(cnt), dim3(kMfThreads), (size_t)m->level_solve_lds[h], s, D, P.level_ptr[h], MfSingle{});
     }
-    hipLaunchKernelGGL(k_mf_update, dim3(ugrid), dim3(kBlock), 0, s, D, d_poses, it);
+    hipLaunchKernelGGL(k_mf_update<false>, dim3(ugrid), dim3(kBlock), 0, s, D, d_poses, it, MfSingle{});
   }
-  if (until) hipLaunchKernelGGL(k_mf_finish_until, dim3(1), dim3(64), 0, s, D, iters, egrid, d_hist, d_res);
+  if (until) hipLaunchKernelGGL(k_mf_finish_until<false>, dim3(1), dim3(64), 0, s, D, iters, egrid, d_hist, d_res, MfSingle{});
   else hipLaunchKernelGGL(k_mf_finish, dim3(1), dim3(64), 0, s, D, iters, egrid, d_hist, d_res);
   if (iters > 0) m->ran = true;
   if (D.dbg && iters > 0) {   // diagnostic: phases of the LAST factorisation, per level the front with the longest total
@@ -950,6 +991,110 @@ hipError_t mfront_optimize(Mfront* m, hipStream_t s, const EdgeListDev& el, doub
   return hipGetLastError();
 }
 
+MfBatchLayout mfront_batch_layout(const Mfront* m, int V, int B, int iters, bool want_edge_chi2) {
+  const MfDev& D = m->dev;
+  MfBatchLayout L;
+  L.B = B;
+  L.V = V;
+  L.E = D.E;
+  const size_t E = (size_t)std::max(D.E, 1), n3 = 3 * (size_t)std::max(D.n, 1), nb = (size_t)B;
+  auto pad = [](size_t bytes) { return (bytes + 255) & ~(size_t)255; };
+  // one hypothesis' share of every piece is a multiple of 256 bytes, so that the whole is B times one hypothesis' bytes and every
+  // piece starts 256-byte aligned whatever B is; the pieces the host copies in one go ([B][..] of the caller's) stay dense
+  size_t per = 0;
+  auto put = [&](size_t bytes_one) {
+    const size_t at = nb * per;
+    per += pad(bytes_one);
+    return at;
+  };
+  L.hist_stride = 2 * ((size_t)iters + 1);
+  L.s_info = 6 * E;
+  L.s_poses = 3 * (size_t)V;
+  L.s_elem = pad(sizeof(double) * kElemStride * E) / sizeof(double);
+  L.s_x = pad(sizeof(double) * n3) / sizeof(double);
+  L.s_yinv = pad(sizeof(double) * n3 * kMfPanel) / sizeof(double);
+  L.s_arena = pad(sizeof(double) * (size_t)std::max<long long>(m->plan.arena_doubles, 1)) / sizeof(double);
+  L.o_off = put(E);
+  L.o_info = put(sizeof(double) * L.s_info);
+  L.o_poses = put(sizeof(double) * L.s_poses);
+  L.o_hist = put(sizeof(double) * L.hist_stride);
+  L.o_echi2 = put(want_edge_chi2 ? sizeof(double) * E : 0);
+  L.o_brief = put(sizeof(int2));
+  L.o_res = put(sizeof(DirectResult));
+  L.o_elem = put(sizeof(double) * L.s_elem);
+  L.o_x = put(sizeof(double) * L.s_x);
+  L.o_invd = put(sizeof(double) * L.s_x);
+  L.o_yinv = put(sizeof(double) * L.s_yinv);
+  L.o_partials = put(sizeof(double) * 2 * kMaxPartials);
+  L.o_flags = put(sizeof(int) * 8);
+  L.o_arena = put(sizeof(double) * L.s_arena);
+  L.per_hypothesis = per;
+  L.bytes = nb * per;
+  return L;
+}
+
+// mfront_optimize's loop of launches in until-mode with every grid x L.B in y: the same kernels' batched instantiations on the
+// copies `ws` holds.  Nothing of the resident image is written, and m->ran stays what it was.
+hipError_t mfront_optimize_batch(Mfront* m, hipStream_t s, const EdgeListDev& el, const double* d_poses_res, bool own_poses,
+                                 const MfBatchLayout& L, char* ws, int iters, double gain_tol, bool want_edge_chi2) {
+  if (L.B <= 0) return hipSuccess;
+  const MfPlan& P = m->plan;
+  MfDev D = m->dev;
+  D.elem = reinterpret_cast<double*>(ws + L.o_elem);
+  D.x = reinterpret_cast<double*>(ws + L.o_x);
+  D.invd = reinterpret_cast<double*>(ws + L.o_invd);
+  D.yinv = reinterpret_cast<double*>(ws + L.o_yinv);
+  D.partials = reinterpret_cast<double*>(ws + L.o_partials);
+  D.flags = reinterpret_cast<int*>(ws + L.o_flags);
+  D.arena = reinterpret_cast<double*>(ws + L.o_arena);
+  D.dbg = nullptr;
+  EdgeListDev eb = el;
+  eb.info = reinterpret_cast<double*>(ws + L.o_info);
+  double* poses = reinterpret_cast<double*>(ws + L.o_poses);
+  double* hist = reinterpret_cast<double*>(ws + L.o_hist);
+  DirectResult* res = reinterpret_cast<DirectResult*>(ws + L.o_res);
+  MfBatch bt;
+  bt.elem = L.s_elem; bt.x = L.s_x; bt.yinv = L.s_yinv; bt.arena = L.s_arena;
+  bt.info = L.s_info; bt.poses = L.s_poses; bt.hist = L.hist_stride;
+  bt.brief = reinterpret_cast<int2*>(ws + L.o_brief);
+  const unsigned nb = (unsigned)L.B;
+  launch_hyp_prepare(s, L.B, L.E, L.V, el.info, reinterpret_cast<const unsigned char*>(ws + L.o_off), eb.info, L.s_info,
+                     own_poses ? nullptr : d_poses_res, poses, L.s_poses);
+  hipError_t he = hipMemsetAsync(D.flags, 0, sizeof(int) * 8 * (size_t)L.B, s);
+  if (he != hipSuccess) return he;
+  const int egrid = std::max(1, std::min((D.E + kBlock - 1) / kBlock, kMaxPartials));
+  const int ugrid = std::max(1, std::min((D.n + kBlock - 1) / kBlock, 1024));
+  for (int it = 0; it <= iters; ++it) {
+    const bool last = it == iters;
+    if (el.kinds) hipLaunchKernelGGL((k_mf_edges<true, true>), dim3(egrid, nb), dim3(kBlock), 0, s, D, eb, (const double*)poses, it, last ? 1 : 0, hist, res, bt);
+    else hipLaunchKernelGGL((k_mf_edges<false, true>), dim3(egrid, nb), dim3(kBlock), 0, s, D, eb, (const double*)poses, it, last ? 1 : 0, hist, res, bt);
+    if (last) break;
+    if (rules::gain_stop_applies(it, iters)) hipLaunchKernelGGL(k_mf_gain_stop<true>, dim3(1, nb), dim3(64), 0, s, D, it, egrid, gain_tol, hist, bt);
+    for (int h = 0; h <= P.height; ++h) {
+      const int cnt = P.level_ptr[h + 1] - P.level_ptr[h];
+      if (h > 0) {
+        const int nt = m->mtile_ptr[h + 1] - m->mtile_ptr[h];
+        const int grid = std::max(1, std::min((nt + kWavesPerBlock - 1) / kWavesPerBlock, 8192));
+        hipLaunchKernelGGL(k_mf_merge<true>, dim3(grid, nb), dim3(kBlock), 0, s, D, m->mtile_ptr[h], m->mtile_ptr[h + 1], bt);
+      }
+      hipLaunchKernelGGL(k_mf_panels<true>, dim3(cnt, nb), dim3(kMfThreads), (size_t)m->level_lds[h], s, D, P.level_ptr[h], it, h == 0 ? 2 * it + 1 : -1,
+                         h == 0 ? egrid : 0, hist, res, bt);
+    }
+    for (int h = P.height; h >= 0; --h) {
+      const int cnt = P.level_ptr[h + 1] - P.level_ptr[h];
+      hipLaunchKernelGGL(k_mf_solve<true>, dim3(cnt, nb), dim3(kMfThreads), (size_t)m->level_solve_lds[h], s, D, P.level_ptr[h], bt);
+    }
+    hipLaunchKernelGGL(k_mf_update<true>, dim3(ugrid, nb), dim3(kBlock), 0, s, D, poses, it, bt);
+  }
+  hipLaunchKernelGGL(k_mf_finish_until<true>, dim3(1, nb), dim3(64), 0, s, D, iters, egrid, hist, res, bt);
+  if (want_edge_chi2) {
+    double* out = reinterpret_cast<double*>(ws + L.o_echi2);
+    if (el.kinds) hipLaunchKernelGGL(k_mf_edge_chi2<true>, dim3(egrid, nb), dim3(kBlock), 0, s, el, D.E, (const double*)poses, L.s_poses, out);
+    else hipLaunchKernelGGL(k_mf_edge_chi2<false>, dim3(egrid, nb), dim3(kBlock), 0, s, el, D.E, (const double*)poses, L.s_poses, out);
+  }
+  return hipGetLastError();
+}
+
 // The factor phase alone: what one iteration of mfront_optimize does up to and excluding k_mf_solve / k_mf_update, at the current
 // poses -- k_mf_edges with the elements, then merge and panels level by level.  The same launches with the same arguments as
 // iteration 0 of mfront_optimize (d_hist[0 .. 1] and d_res->stamp[0 .. 1] are written as there); the flags are cleared first.
@@ -959,17 +1104,17 @@ hipError_t mfront_factorize(Mfront* m, hipStream_t s, const EdgeListDev& el, con
   hipError_t he = hipMemsetAsync(D.flags, 0, sizeof(int) * 8, s);
   if (he != hipSuccess) return he;
   const int egrid = std::max(1, std::min((D.E + kBlock - 1) / kBlock, kMaxPartials));
-  if (el.kinds) hipLaunchKernelGGL(k_mf_edges<true>, dim3(egrid), dim3(kBlock), 0, s, D, el, d_poses, 0, 0, d_hist, d_res);
-  else hipLaunchKernelGGL(k_mf_edges<false>, dim3(egrid), dim3(kBlock), 0, s, D, el, d_poses, 0, 0, d_hist, d_res);
+  if (el.kinds) hipLaunchKernelGGL((k_mf_edges<true, false>), dim3(egrid), dim3(kBlock), 0, s, D, el, d_poses, 0, 0, d_hist, d_res, MfSingle{});
+  else hipLaunchKernelGGL((k_mf_edges<false, false>), dim3(egrid), dim3(kBlock), 0, s, D, el, d_poses, 0, 0, d_hist, d_res, MfSingle{});
   for (int h = 0; h <= P.height; ++h) {
     const int cnt = P.level_ptr[h + 1] - P.level_ptr[h];
     if (h > 0) {
       const int nt = m->mtile_ptr[h + 1] - m->mtile_ptr[h];
       const int grid = std::max(1, std::min((nt + kWavesPerBlock - 1) / kWavesPerBlock, 8192));
-      hipLaunchKernelGGL(k_mf_merge, dim3(grid), dim3(kBlock), 0, s, D, m->mtile_ptr[h], m->mtile_ptr[h + 1]);
+      hipLaunchKernelGGL(k_mf_merge<false>, dim3(grid), dim3(kBlock), 0, s, D, m->mtile_ptr[h], m->mtile_ptr[h + 1], MfSingle{});
     }
-    hipLaunchKernelGGL(k_mf_panels, dim3(cnt), dim3(kMfThreads), (size_t)m->level_lds[h], s, D, P.level_ptr[h], 0, h == 0 ? 1 : -1,
-                       h == 0 ? egrid : 0, d_hist, d_res);
+    hipLaunchKernelGGL(k_mf_panels<false>, dim3(cnt), dim3(kMfThreads), (size_t)m->level_lds[h], s, D, P.level_ptr[h], 0, h == 0 ? 1 : -1,
+                       h == 0 ? egrid : 0, d_hist, d_res, MfSingle{});
   }
   return hipGetLastError();
 }

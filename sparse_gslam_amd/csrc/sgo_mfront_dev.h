@@ -50,6 +50,34 @@ struct MfDev {
 
 typedef double mf_d4 __attribute__((ext_vector_type(4)));
 
+// The batched instantiations of sgo_mfront.hip's kernels (mfront_optimize_batch): blockIdx.y is the hypothesis, which works on copy
+// blockIdx.y of everything mfront_optimize writes -- the strides, in doubles, from one copy to the next -- while the plan's tables
+// stay shared.  The partial sums stride by 2 kMaxPartials doubles, the flags by 8 ints, the DirectResult by one.
+struct MfBatch {
+  size_t elem, x, yinv, arena;   // MfDev's arrays (invd strides like x)
+  size_t info, poses, hist;      // the information rows [6][E], the poses [V][3], the history [iters + 1][2]
+  int2* brief;                   // [B] {updates applied, failure code}: what the host reads of a hypothesis' DirectResult
+};
+struct MfSingle {};              // the unbatched instantiations take nothing
+
+// Hypothesis blockIdx.y's view of a batched kernel's arguments; el / poses / hist / res: those the kernel has (nullptr: not one of its).
+template <class P = double*, class H = double*, class R = DirectResult*>
+__device__ __forceinline__ void mf_slice(const MfBatch& bt, MfDev& M, EdgeListDev* el = nullptr, P* poses = nullptr, H* hist = nullptr,
+                                         R* res = nullptr) {
+  const size_t b = blockIdx.y;
+  M.elem += b * bt.elem;
+  M.x += b * bt.x;
+  M.invd += b * bt.x;
+  M.yinv += b * bt.yinv;
+  M.arena += b * bt.arena;
+  M.partials += b * (2 * (size_t)kMaxPartials);
+  M.flags += b * 8;
+  if (el) el->info += b * bt.info;
+  if (poses) *poses += b * bt.poses;
+  if (hist) *hist += b * bt.hist;
+  if (res) *res += b;
+}
+
 // The selected inversion's share of the device image (sgo_selinv.hip, sgo_selinv.cpp): made by the first sgo_marginals_selected
 // on the graph, out of the same per-graph arena.
 struct MfSelDev {

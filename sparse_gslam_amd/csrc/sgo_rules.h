@@ -60,6 +60,15 @@ inline int hypothesis_isolated_vertex(const unsigned char* fixed, int E, const i
   return lowest;
 }
 
+// How many hypotheses of sgo_optimize_gn_hypotheses share one chain of launches on a multifrontal context (sgo_hypotheses_chunk):
+// as many as the caller's budget holds copies for, at most B and at most the 65535 a grid's y dimension takes.  0: the sequential
+// route -- a chain of fewer than two shares nothing, and per <= 0 says there is no batched route.
+inline int hypotheses_chunk(long long per_hypothesis_bytes, long long budget_bytes, int B) {
+  if (per_hypothesis_bytes <= 0 || budget_bytes <= 0 || B <= 0) return 0;
+  const long long k = std::min<long long>(std::min<long long>(B, budget_bytes / per_hypothesis_bytes), 65535);
+  return k < 2 ? 0 : (int)k;
+}
+
 // Iteration counts are compared at EQUAL tolerance: a solve that stopped at the absolute criterion (a looser relative tolerance
 // tolk > tol0, pcg_tol_cap) is scaled to what tol0 would have cost -- PCG converges linearly, iterations ~ log(1 / tolerance).
 inline int equal_tolerance_count(int iter, double tol0, double tolk) {
