@@ -1063,6 +1063,60 @@ class SparseOptimizer : public OptimizableGraph {
     return rc;
   }
 
+  // ---- the leave-one-out test of edges that ARE in the graph (extension; sgo_edge_leave_one_out of include/sgo.h): (*d2)[t] is
+  // what sgoCandidateGate would say about edges[t] had it never been inserted, at the current estimates, all edges from one selected
+  // inversion; (*redundancy)[t] in [0, 1] is 0 for a bridge edge (removing it disconnects the graph), whose d2 is NaN and which
+  // never fails; (*fail)[t] = redundancy >= minRedundancy && d2 > chi2Max.  Returns how many fail.  Returns -1 with one line on
+  // std::cerr, the outputs untouched, when the graph takes the host solver (Levenberg, other types), when the backend does not hold
+  // the graph as it stands (an addVertex / addEdge without initializeOptimization), for an edge that is not an active edge of the
+  // graph, and when the call itself refuses (sgo_last_error's text).
+  int sgoEdgeLeaveOneOut(const std::vector<OptimizableGraph::Edge*>& edges, double chi2Max, double minRedundancy, std::vector<double>* d2,
+                         std::vector<double>* redundancy, std::vector<bool>* fail) {
+    if (!_algorithm || !gpuEligible()) {
+      std::cerr << "SparseOptimizer::sgoEdgeLeaveOneOut: only the device path (VertexSE2 / EdgeSE2 under Gauss-Newton) has this test" << std::endl;
+      return -1;
+    }
+    if (_activeRevision != _revision || _activeVertices.empty()) {
+      std::cerr << "SparseOptimizer::sgoEdgeLeaveOneOut: the graph changed since the last initializeOptimization" << std::endl;
+      return -1;
+    }
+    std::vector<std::pair<const OptimizableGraph::Edge*, int32_t>> place(_activeEdges.size());   // active edge -> its place in _activeEdges
+    for (size_t k = 0; k < _activeEdges.size(); ++k) place[k] = std::make_pair((const OptimizableGraph::Edge*)_activeEdges[k], (int32_t)k);
+    std::sort(place.begin(), place.end());
+    const size_t n = edges.size();
+    std::vector<int32_t> ids(n);
+    for (size_t t = 0; t < n; ++t) {
+      auto it = std::lower_bound(place.begin(), place.end(), std::make_pair((const OptimizableGraph::Edge*)edges[t], (int32_t)0));
+      if (!edges[t] || it == place.end() || it->first != edges[t]) {
+        std::cerr << "SparseOptimizer::sgoEdgeLeaveOneOut: edge " << t << " of the list is not an active edge of the graph" << std::endl;
+        return -1;
+      }
+      ids[t] = it->second;
+    }
+    if (!uploadGraph()) return -1;
+    // the device's numbering: the records it was set up with, of which the edges that left since are deactivated, not renumbered
+    if (_m.nDead > 0) {
+      std::vector<int32_t> record;
+      for (size_t r = 0; r < _m.dead.size(); ++r)
+        if (!_m.dead[r]) record.push_back((int32_t)r);
+      for (int32_t& id : ids) id = record[(size_t)id];
+    }
+    std::vector<double> dd(n + 1), rr(n + 1);   // (never a null d2, whatever n)
+    std::vector<uint8_t> ff(n + 1);
+    const int rc = sgo_edge_leave_one_out(_ctx, (int32_t)n, ids.data(), chi2Max, minRedundancy, dd.data(), rr.data(), nullptr, ff.data());
+    if (rc < 0) {
+      std::cerr << "SparseOptimizer::sgoEdgeLeaveOneOut: " << sgo_last_error(_ctx) << std::endl;
+      return -1;
+    }
+    if (d2) d2->assign(dd.begin(), dd.begin() + n);
+    if (redundancy) redundancy->assign(rr.begin(), rr.begin() + n);
+    if (fail) {
+      fail->resize(n);
+      for (size_t t = 0; t < n; ++t) (*fail)[t] = ff[t] != 0;
+    }
+    return rc;
+  }
+
   // ---- joint compatibility of a set of candidate closures (extension; sgo_candidate_joint / sgo_joint_subsets of include/sgo.h):
   // the candidates are EdgeSE2 objects as sgoCandidateGate takes them; subsets[b] lists the candidates (indices into `candidates`,
   // any order, a repeated index counts once) of subset b.  (*d2)[b] = e_s^T (S_ss)^-1 e_s with the candidates' cross-covariances at

@@ -570,6 +570,45 @@ int sgo_joint_subsets(sgo_ctx* ctx, int32_t n, int32_t B, const uint8_t* subset 
                       double* d2 /*[B]*/, int32_t* dof /*[B] or NULL*/, uint8_t* pass /*[B] or NULL*/);
 int sgo_joint_pairs(sgo_ctx* ctx, int32_t n, double* d2 /*[n][n]*/);
 
+/* (later additions, version 107) Leave-one-out test of the edges ALREADY in the graph, all from one selected inversion (DESIGN.md
+ * section 5k).  sgo_gate_edges compares the raw e^T Omega e, which is under-dispersed after the fit (its covariance is
+ * Omega^-1 - J Sigma J^T, not Omega^-1) and changes meaning once a robust kernel down-weights the edge.  For resident edge k with
+ * error e, Jacobians A, B (a fixed endpoint drops out), resident information Omega and kernel weight w (sgo_edge_robust's),
+ * H and Sigma = H^-1 exactly sgo_marginals_selected's (the call assembles, factorises and selectively inverts at the CURRENT poses):
+ *   P  = 1/2 (Q + Q^T),  Q = [A B] Sigma_{(i,j),(i,j)} [A B]^T                   (both endpoints fixed: P = 0)
+ *   Omega = G G^T (lower Cholesky),  N = G^T P G = V diag(nu) V^T,  c = V^T G^T e
+ *   redundancy[t] = 1 - w nu_max                          (lambda_min of I - w N, in [0, 1] up to rounding)
+ *   d2[t]         = sum_q c_q^2 / ((1 + (1 - w) nu_q) (1 - w nu_q))
+ *   cov_loo[t]    = G^-T V diag(nu_q / (1 - w nu_q)) V^T G^-1                    (row-major, exactly symmetric)
+ * d2 is e~^T (Omega^-1 + P_)^-1 e~ with P_ = J H_^-1 J^T the predicted covariance of the graph WITHOUT the edge (H_ = H - J^T (w Omega) J),
+ * = cov_loo, and e~ the edge's error after the one linear step its removal causes: what sgo_candidate_gate would say about the edge
+ * had it never been inserted.  w = 1 gives the normalised-residual test e^T (Omega^-1 - P)^-1 e, w = 0 the gate's own formula.
+ * An edge with all-zero information (deactivated): d2 = 0, redundancy = 1, cov_loo = P, no fail.  An information that is not
+ * positive definite: d2 = redundancy = NaN, no fail.  A BRIDGE edge (its removal disconnects the graph: the odometry tail, a chain
+ * stretch inside no loop) has redundancy 0 up to rounding and the test is 0 / 0: whenever redundancy < min_redundancy or is not finite,
+ * d2 and cov_loo are NaN, redundancy is reported as computed and the edge does not fail.
+ * fail[t] = redundancy >= min_redundancy && d2 > chi2_max; returns how many fail, or a negative code.  edge_ids == NULL: edges
+ * 0 .. n-1.  An edge's result does not depend on n or on its place in the list, an id listed twice is answered twice, two calls at
+ * the same poses give the same bits.  Nothing of Sigma crosses to the host: one kernel reads the 21 doubles per edge in place.
+ * The plan is sgo_marginals_selected's, whose factor and selected-inversion launches the call shares; like that call it writes only
+ * what every Gauss-Newton iteration recomputes, and scratch: a later sgo_optimize_gn has the bits of a context that never called.
+ * SGO_ENOTHING with the analysis' reason when the multifrontal analysis refuses the graph: use sgo_optimize_gn_hypotheses (one
+ * hypothesis per edge) then.
+ * SGO_EINVAL, with nothing on the device changed and no output written: n < 0 or a null d2 (n > E without ids), an id outside
+ * [0, E), chi2_max not finite, min_redundancy outside (0, 1] (zero is refused so that a bridge's 0 / 0 can never decide), an active
+ * overlay, a multi-GPU context (sgo_debug_set_shard's emulation included).  SGO_EINVAL with the outputs untouched when the
+ * factorisation is not positive definite; the next sgo_optimize_gn is unaffected.
+ * Not covered: groups of edges (their cross blocks are the joint table's), deactivation inside the call (sgo_set_edge_information).
+ *
+ * sgo_edge_loo_rule: the per-edge arithmetic alone, as the kernel compiles it (sgo_rules.h; no context, no GPU, like sgo_gain_stop):
+ * info6 = Omega's upper triangle by rows, P9 row-major, e3, w -> d2, redundancy, cov_loo (may be NULL); no min_redundancy is applied.
+ * Returns 0, 1 for an all-zero information, 2 for an information that is not positive definite. */
+int sgo_edge_leave_one_out(sgo_ctx* ctx, int32_t n, const int32_t* edge_ids /*NULL: edges 0..n-1*/, double chi2_max,
+                           double min_redundancy, double* d2 /*[n]*/, double* redundancy /*[n], may be NULL*/,
+                           double* cov_loo /*[n][9], may be NULL*/, uint8_t* fail /*[n], may be NULL*/);
+int sgo_edge_loo_rule(const double* info6, const double* P9, const double* e3, double w, double* d2, double* redundancy,
+                      double* cov_loo /*[9] or NULL*/);
+
 /* ---- profiling (opts.profile = 1) ---------------------------------------------------------- */
 /* Per-kernel totals accumulated since the last sgo_profile_reset: for kernel slot k,
  * name (static string), launches, total milliseconds (HIP events on the ctx stream), and the

@@ -36,7 +36,7 @@ SYMBOLS = [
     "sgo_set_edge_information", "sgo_gate_edges", "sgo_set_robust_kernels", "sgo_edge_robust",
     "sgo_solve_rhs", "sgo_marginals", "sgo_marginals_selected", "sgo_factor_solve", "sgo_candidate_gate",
     "sgo_gain_stop", "sgo_optimize_gn_until", "sgo_optimize_gn_hypotheses", "sgo_hypothesis_isolated_vertex",
-    "sgo_candidate_joint", "sgo_joint_subsets", "sgo_joint_pairs",
+    "sgo_candidate_joint", "sgo_joint_subsets", "sgo_joint_pairs", "sgo_edge_leave_one_out", "sgo_edge_loo_rule",
     "sgo_set_hypotheses_workspace", "sgo_hypotheses_bytes", "sgo_hypotheses_chunk", "sgo_hypotheses_workspace_bytes",
 ]
 
@@ -61,6 +61,18 @@ class SgoError(RuntimeError):
 def gain_stop(last_robust_chi2: float, robust_chi2: float, gain_tol: float) -> bool:
     """sgo_gain_stop: the rule sgo_optimize_gn_until stops by, as the library computes it (no context, no GPU)."""
     return bool(lib().sgo_gain_stop(last_robust_chi2, robust_chi2, gain_tol))
+
+
+def edge_loo_rule(info6, P, e, w: float):
+    """sgo_edge_loo_rule: the per-edge arithmetic of sgo_edge_leave_one_out as the library (and its kernel) computes it, no context
+    and no GPU: info6 = Omega's upper triangle by rows, P (3, 3), e (3,), the kernel weight w -> (rc, d2, redundancy, cov_loo (3, 3));
+    rc 0, 1 for an all-zero information, 2 for one that is not positive definite.  No min_redundancy is applied."""
+    o = np.ascontiguousarray(info6, dtype=np.float64).reshape(6)
+    Pm = np.ascontiguousarray(P, dtype=np.float64).reshape(9)
+    ev = np.ascontiguousarray(e, dtype=np.float64).reshape(3)
+    d2, red, cov = C.c_double(), C.c_double(), np.empty((3, 3))
+    rc = lib().sgo_edge_loo_rule(_dp(o), _dp(Pm), _dp(ev), float(w), C.byref(d2), C.byref(red), _dp(cov))
+    return rc, d2.value, red.value, cov
 
 
 class Opts(C.Structure):
@@ -196,6 +208,8 @@ def lib():
     L.sgo_candidate_joint.argtypes = [vp, C.c_int32, i32, i32, d, d, d, d]
     L.sgo_joint_subsets.argtypes = [vp, C.c_int32, C.c_int32, u8, d, d, i32, u8]
     L.sgo_joint_pairs.argtypes = [vp, C.c_int32, d]
+    L.sgo_edge_leave_one_out.argtypes = [vp, C.c_int32, i32, C.c_double, C.c_double, d, d, d, u8]
+    L.sgo_edge_loo_rule.argtypes = [d, d, d, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double), d]
     L.sgo_kernel_profile.argtypes = [vp, C.POINTER(KernelStat), C.c_int]
     L.sgo_kernel_profile_samples.argtypes = [vp, C.c_int, C.POINTER(C.c_float), C.c_int]
     L.sgo_solver_description.restype = C.c_char_p
@@ -771,6 +785,21 @@ class Optimizer:
         if rc < 0:
             raise SgoError(f"sgo_candidate_gate: rc={rc}: " + lib().sgo_last_error(self._h).decode())
         return rc, d2, P, ok.astype(bool)
+
+    def edge_leave_one_out(self, edge_ids, chi2_max: float, min_redundancy: float = 1e-3):
+        """sgo_edge_leave_one_out: the leave-one-out test of the listed resident edges (None: every edge) from one selected
+        inversion -> (nfail, d2 (n,), redundancy (n,), cov_loo (n, 3, 3), fail (n,) bool): d2 is what candidate_gate would say about
+        the edge had it never been inserted, fail = redundancy >= min_redundancy and d2 > chi2_max; a bridge edge (redundancy below
+        min_redundancy) has d2 = cov_loo = NaN and does not fail.  SgoError with rc=-1 when the multifrontal analysis refuses the
+        graph (use optimize_hypotheses then)."""
+        ids = None if edge_ids is None else np.ascontiguousarray(edge_ids, dtype=np.int32).reshape(-1)
+        n = self.E if ids is None else ids.size
+        d2, red, cov, fl = np.empty(n), np.empty(n), np.empty((n, 3, 3)), np.zeros(n, dtype=np.uint8)
+        rc = lib().sgo_edge_leave_one_out(self._h, n, None if ids is None else _ip(ids), float(chi2_max), float(min_redundancy),
+                                          _dp(d2), _dp(red), _dp(cov), fl.ctypes.data_as(C.POINTER(C.c_uint8)))
+        if rc < 0:
+            raise SgoError(f"sgo_edge_leave_one_out: rc={rc}: " + lib().sgo_last_error(self._h).decode())
+        return rc, d2, red, cov, fl.astype(bool)
 
     def candidate_joint(self, ci, cj, meas, info):
         """sgo_candidate_joint: the joint table of the candidate edges (arguments as candidate_gate's) at the current poses ->

@@ -383,6 +383,8 @@ void sgo_destroy(sgo_ctx* c) {
   if (c->selinv.d_fs) hipFree(c->selinv.d_fs);
   if (c->selinv.d_cand) hipFree(c->selinv.d_cand);
   if (c->selinv.d_cidx) hipFree(c->selinv.d_cidx);
+  if (c->selinv.d_loo) hipFree(c->selinv.d_loo);
+  if (c->selinv.d_loo_ids) hipFree(c->selinv.d_loo_ids);
   for (void* p : {(void*)c->joint.d_tab[0], (void*)c->joint.d_tab[1], (void*)c->joint.d_raw, (void*)c->joint.d_d2, (void*)c->joint.d_mask})
     if (p) hipFree(p);
   if (c->hyp.d_ws) hipFree(c->hyp.d_ws);
@@ -1217,6 +1219,10 @@ int sgo_optimize_gn(sgo_ctx* c, int32_t iters, sgo_stats* out) {
 
 int sgo_gain_stop(double last_robust_chi2, double robust_chi2, double gain_tol) {
   return rules::gain_stop(last_robust_chi2, robust_chi2, gain_tol) ? 1 : 0;
+}
+
+int sgo_edge_loo_rule(const double* info6, const double* P9, const double* e3, double w, double* d2, double* redundancy, double* cov_loo) {
+  return rules::edge_loo(info6, P9, e3, w, d2, redundancy, cov_loo);
 }
 
 int sgo_optimize_gn_until(sgo_ctx* c, int32_t max_iters, double gain_tol, sgo_stats* out, int32_t* stop_reason) {

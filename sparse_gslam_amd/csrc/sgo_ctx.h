@@ -288,6 +288,11 @@ struct sgo_ctx {
     double* d_cand = nullptr;
     int* d_cidx = nullptr;
     size_t fs_cap = 0, cand_cap = 0, cidx_cap = 0;
+    // sgo_edge_leave_one_out (sgo_loo.cpp): the results [n][kLooOut], the failure flag, the count, then the per-workgroup counts
+    // [kMaxPartials]; the listed edge ids
+    double* d_loo = nullptr;
+    int* d_loo_ids = nullptr;
+    size_t loo_cap = 0, loo_ids_cap = 0;
   } selinv;
 
   // sgo_candidate_joint's table (sgo_fsolve.cpp): S [3 n][3 n], e [n][3] and the failure flag in tab[cur]; a call builds in the

@@ -88,6 +88,17 @@ struct MfSelDev {
   const int* pos_front = nullptr; // [n] elimination position -> the front that owns it
 };
 
+// Where the selected inverse holds a resident edge's three blocks (sgo_edge_leave_one_out; made on the host once per plan):
+// pair = sgo_marginals_selected's descriptor of the block (vertices()[0], vertices()[1]) -- (front, local row pose, local column
+// pose, transposed); front < 0: an endpoint is fixed, no block --, pi / pj = the endpoints' elimination positions (-1: fixed), whose
+// diagonal blocks sit in the fronts that own them (MfSelDev::pos_front).  Duplicate edges of a pair, in either orientation, name the
+// same stored block and differ in `transposed` alone.
+struct LooEdgeDev {
+  int4 pair;
+  int pi, pj;
+};
+constexpr int kLooOut = 12;       // per listed edge: d2, redundancy, cov_loo (9, row-major), fail
+
 // The multi-right-hand-side substitution's share (sgo_fsolve.hip, sgo_fsolve.cpp): made by the first sgo_factor_solve /
 // sgo_candidate_gate on the graph, out of the same per-graph arena.
 struct MfFsDev {
@@ -152,6 +163,9 @@ struct Mfront {
   bool sel_ran = false;              // a selected inversion has filled sel.S (and mfront_factorize the factor's arrays)
   std::vector<int> gtile_ptr;        // k_si_gather's tiles of level h: [gtile_ptr[h], gtile_ptr[h + 1])
   std::vector<int> pos_front;        // host copy of sel.pos_front
+  // leave-one-out test of the resident edges (sgo_loo.cpp): where sel.S holds every edge's blocks, once per plan
+  const LooEdgeDev* loo = nullptr;   // [loo_E]
+  int loo_E = -1;                    // the edges the descriptors were made for (-1: none yet)
   // multi-right-hand-side substitution
   MfFsDev fs;
   bool fs_ready = false;             // fs's arrays and sel.cmap / sel.cmap_off exist
@@ -173,6 +187,21 @@ bool si_prepare_device();   // the panel kernel's dynamic LDS; false: the device
 // in the context's error text, which names `who` and points to `instead`).
 int selinv_plan(sgo_ctx* c, Mfront** out, const char* who, const char* instead);
 int mfront_maps_prepare(sgo_ctx* c, Mfront* m);   // sel.cmap / sel.cmap_off on the device, once per plan
+// The two phases sgo_marginals_selected and sgo_edge_leave_one_out share: selinv_prepare makes the selected inversion's own device
+// arrays (once per plan; `who` for the error text), selinv_run queues the factor phase at the current poses and the top-down
+// selected inversion, after which sel.S holds every front's selected inverse (dev.flags[0] != 0: the factorisation failed and the
+// later launches did nothing).  selinv_positions: hessian index -> elimination position; selinv_pair: sgo_marginals_selected's
+// descriptor of the block with the rows of position pi and the columns of pj, false when no front holds both.
+int selinv_prepare(sgo_ctx* c, Mfront* m, const char* who);
+int selinv_run(sgo_ctx* c, Mfront* m);
+std::vector<int> selinv_positions(const sgo_ctx* c, const Mfront* m);
+bool selinv_pair(const Mfront* m, int pi, int pj, int4* out);
+
+// ---- the leave-one-out kernel (sgo_loo.hip); the host driver is sgo_loo.cpp ----
+// out: [n][kLooOut], then the factorisation's failure flag, then the count of failing edges; partials: [kMaxPartials].  ids ==
+// nullptr: edges 0 .. n-1.  desc == nullptr: a graph without a free pose (every P is zero; M, Z and flags are not read).
+void launch_loo_edges(hipStream_t s, const MfDev& M, const MfSelDev& Z, const LooEdgeDev* desc, const EdgeListDev& el, const double* poses, int n,
+                      const int* ids, double chi2_max, double min_redundancy, double* out, double* partials);
 
 // ---- kernels of the multi-right-hand-side substitution (sgo_fsolve.hip), one launch each; the host driver is sgo_fsolve.cpp ----
 void launch_fs_rhs_columns(hipStream_t s, int ncols, int n3, const double* src, const int* pos_h, double* panel);

@@ -35,6 +35,113 @@ SGO_RULE_HD inline bool gain_stop(double last, double cur, double gain_tol) {
 // ... and the iterations before which it is asked: at least two updates always run, and the closing pass decides nothing.
 SGO_RULE_HD inline bool gain_stop_applies(int it, int max_iters) { return it >= 2 && it < max_iters; }
 
+// The leave-one-out rule of sgo_edge_leave_one_out: what sgo_candidate_gate would say about a resident edge
+// had it never been inserted, from the edge's own quantities alone.  info: Omega's upper triangle by rows; P = J Sigma J^T at the
+// current poses WITH the edge in H (row-major, symmetric); e its error; w its kernel weight.  With Omega = G G^T (lower Cholesky),
+// N = G^T P G = V diag(nu) V^T, c = V^T G^T e:
+//   redundancy = 1 - w nu_max                       (lambda_min of I - w N: 0 for a bridge, whose test is 0 / 0)
+//   d2         = sum_q c_q^2 / ((1 + (1 - w) nu_q) (1 - w nu_q))
+//   cov_loo    = G^-T V diag(nu_q / (1 - w nu_q)) V^T G^-1    (exactly symmetric: one triangle is computed and mirrored)
+// Everything goes through G and N, never through a factor of w Omega: w reaches 4e-9 under DCS.  Returns 0; 1 for an all-zero Omega
+// (a deactivated edge: d2 = 0, redundancy = 1, cov_loo = P); 2 for an Omega that is not positive definite (NaN everywhere).  The
+// caller decides what a small redundancy means.  cov_loo may be null.  `double` and comparisons only: the host and k_loo_edges
+// compile this text.
+// jacobi3: a symmetric 3 x 3 matrix (a: overwritten by the rotated matrix; its diagonal ends as the eigenvalues) by kJacobiSweeps
+// cyclic sweeps; V's COLUMNS are the eigenvectors.  A fixed count, not a convergence test: after five sweeps a 3 x 3 matrix is
+// diagonal to rounding (the convergence is quadratic), and an exactly zero entry is not rotated.
+constexpr int kJacobiSweeps = 8;
+template <int p, int q>
+SGO_RULE_HD inline void jacobi3_rotate(double (&a)[3][3], double (&V)[3][3]) {
+  const double apq = a[p][q];
+  if (apq == 0.0) return;
+  const double theta = (a[q][q] - a[p][p]) / (2.0 * apq);
+  const double at = theta < 0.0 ? -theta : theta;
+  double t = 1.0 / (at + sqrt(theta * theta + 1.0));   // (a huge theta: t = 0, the entry is negligible already)
+  if (theta < 0.0) t = -t;
+  const double cs = 1.0 / sqrt(t * t + 1.0), sn = t * cs;
+  a[p][p] -= t * apq;
+  a[q][q] += t * apq;
+  a[p][q] = a[q][p] = 0.0;
+  constexpr int r = 3 - p - q;   // the third index
+  const double arp = a[r][p], arq = a[r][q];
+  a[r][p] = a[p][r] = cs * arp - sn * arq;
+  a[r][q] = a[q][r] = sn * arp + cs * arq;
+  for (int k = 0; k < 3; ++k) {
+    const double vkp = V[k][p], vkq = V[k][q];
+    V[k][p] = cs * vkp - sn * vkq;
+    V[k][q] = sn * vkp + cs * vkq;
+  }
+}
+SGO_RULE_HD inline void jacobi3(double (&a)[3][3], double (&V)[3][3]) {
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) V[i][j] = i == j ? 1.0 : 0.0;
+  for (int sweep = 0; sweep < kJacobiSweeps; ++sweep) {
+    jacobi3_rotate<0, 1>(a, V);
+    jacobi3_rotate<0, 2>(a, V);
+    jacobi3_rotate<1, 2>(a, V);
+  }
+}
+SGO_RULE_HD inline int edge_loo(const double* info, const double* P, const double* e, double w, double* d2, double* redundancy, double* cov_loo) {
+  const double o00 = info[0], o01 = info[1], o02 = info[2], o11 = info[3], o12 = info[4], o22 = info[5];
+  if (o00 == 0.0 && o01 == 0.0 && o02 == 0.0 && o11 == 0.0 && o12 == 0.0 && o22 == 0.0) {
+    *d2 = 0.0;
+    *redundancy = 1.0;
+    if (cov_loo)
+      for (int q = 0; q < 9; ++q) cov_loo[q] = P[q];
+    return 1;
+  }
+  // Omega = G G^T
+  const double g00 = sqrt(o00), g10 = o01 / g00, g20 = o02 / g00;
+  const double t11 = o11 - g10 * g10, g11 = sqrt(t11), g21 = (o12 - g20 * g10) / g11;
+  const double t22 = o22 - g20 * g20 - g21 * g21, g22 = sqrt(t22);
+  if (!(o00 > 0.0) || !(t11 > 0.0) || !(t22 > 0.0) || !(g22 - g22 == 0.0)) {   // (the last: a non-finite entry)
+    const double nan = sqrt(-1.0);
+    *d2 = nan;
+    *redundancy = nan;
+    if (cov_loo)
+      for (int q = 0; q < 9; ++q) cov_loo[q] = nan;
+    return 2;
+  }
+  const double G[3][3] = {{g00, 0.0, 0.0}, {g10, g11, 0.0}, {g20, g21, g22}};
+  // N = G^T Ps G with Ps = (P + P^T) / 2
+  double Ps[3][3], PG[3][3], N[3][3], V[3][3];
+  for (int a = 0; a < 3; ++a)
+    for (int b = 0; b < 3; ++b) Ps[a][b] = 0.5 * (P[3 * a + b] + P[3 * b + a]);
+  for (int a = 0; a < 3; ++a)
+    for (int b = 0; b < 3; ++b) PG[a][b] = Ps[a][0] * G[0][b] + Ps[a][1] * G[1][b] + Ps[a][2] * G[2][b];
+  for (int a = 0; a < 3; ++a)
+    for (int b = a; b < 3; ++b) N[a][b] = N[b][a] = G[0][a] * PG[0][b] + G[1][a] * PG[1][b] + G[2][a] * PG[2][b];
+  jacobi3(N, V);
+  const double nu[3] = {N[0][0], N[1][1], N[2][2]};
+  const double u[3] = {g00 * e[0] + g10 * e[1] + g20 * e[2], g11 * e[1] + g21 * e[2], g22 * e[2]};
+  double numax = nu[0] > nu[1] ? nu[0] : nu[1];
+  if (nu[2] > numax) numax = nu[2];
+  *redundancy = 1.0 - w * numax;
+  double sum = 0.0, s[3];
+  for (int q = 0; q < 3; ++q) {
+    const double c = V[0][q] * u[0] + V[1][q] * u[1] + V[2][q] * u[2];
+    const double r = 1.0 - w * nu[q];
+    sum += c * c / ((1.0 + (1.0 - w) * nu[q]) * r);
+    s[q] = nu[q] / r;
+  }
+  *d2 = sum;
+  if (cov_loo) {
+    // Y = G^-T V (column q: back substitution with G^T), cov_loo = Y diag(s) Y^T
+    double Y[3][3];
+    for (int q = 0; q < 3; ++q) {
+      Y[2][q] = V[2][q] / g22;
+      Y[1][q] = (V[1][q] - g21 * Y[2][q]) / g11;
+      Y[0][q] = (V[0][q] - g10 * Y[1][q] - g20 * Y[2][q]) / g00;
+    }
+    for (int a = 0; a < 3; ++a)
+      for (int b = a; b < 3; ++b) {
+        const double v = Y[a][0] * s[0] * Y[b][0] + Y[a][1] * s[1] * Y[b][1] + Y[a][2] * s[2] * Y[b][2];
+        cov_loo[3 * a + b] = cov_loo[3 * b + a] = v;
+      }
+  }
+  return 0;
+}
+
 // The mask rule of sgo_optimize_gn_hypotheses, which is sgo_set_edge_information's: a hypothesis may not leave a free pose without any
 // incident edge of non-zero information.  live_deg[V] holds every vertex' count of such edges in the resident graph, dead(e) says
 // whether edge e carries an all-zero information already, off[E] is the hypothesis' mask.  Returns the lowest free vertex that an

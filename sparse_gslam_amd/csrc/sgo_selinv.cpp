@@ -6,6 +6,8 @@
 // The plan is the resident one when optimize() takes the multifrontal path; a graph on another path gets a plan of its own,
 // analysed once per set-up under the multifrontal path's admission limits.  sgo_optimize_gn keeps its path either way: the call
 // writes the factor's arrays (which every Gauss-Newton iteration recomputes from the poses) and the scratch d_hist / d_dres.
+// The first two phases (selinv_prepare, selinv_run) and the pairs' descriptors (selinv_pair) are sgo_edge_leave_one_out's too
+// (sgo_loo.cpp), which reads the selected inverse in place instead of gathering it.
 #include <algorithm>
 #include <cstdlib>
 
@@ -76,16 +78,12 @@ int mfront_maps_prepare(sgo_ctx* c, Mfront* m) {
   return SGO_OK;
 }
 
-}  // namespace sgo
-
-namespace {
-
 // The selected inversion's own device arrays, once per plan: the second arena (zeroed once: the entries no kernel writes stay
 // zero), the extend-add maps, the gather's tiles and the front of every elimination position.
-int selinv_prepare(sgo_ctx* c, Mfront* m) {
+int selinv_prepare(sgo_ctx* c, Mfront* m, const char* who) {
   if (m->sel_ready) return SGO_OK;
   if (!si_prepare_device()) {
-    c->err = "sgo_marginals_selected: the device does not grant the kernel's dynamic LDS";
+    c->err = std::string(who) + ": the device does not grant the kernel's dynamic LDS";
     return SGO_EHIP;
   }
   int rc;
@@ -125,7 +123,60 @@ int selinv_prepare(sgo_ctx* c, Mfront* m) {
   return SGO_OK;
 }
 
-}  // namespace
+// hessian index -> elimination position
+std::vector<int> selinv_positions(const sgo_ctx* c, const Mfront* m) {
+  const MfPlan& P = m->plan;
+  std::vector<int> pos_of((size_t)c->n, -1);
+  for (int p = 0; p < P.n; ++p) {
+    const auto f = std::lower_bound(c->free_id.begin(), c->free_id.end(), P.elim_vertex[p]);
+    pos_of[(size_t)(f - c->free_id.begin())] = p;
+  }
+  return pos_of;
+}
+
+// The block with the rows of elimination position pi and the columns of pj in the plan's terms: the front of the endpoint
+// eliminated first holds it, if any front does (m->pos_front: selinv_prepare's).
+bool selinv_pair(const Mfront* m, int pi, int pj, int4* out) {
+  const MfPlan& P = m->plan;
+  const int plo = std::min(pi, pj), phi = std::max(pi, pj);
+  const int f = m->pos_front[plo];
+  const MfFront& F = P.fronts[f];
+  int lrow = -1;
+  if (phi < F.e0 + F.own) lrow = phi - F.e0;
+  else {
+    const int* b0 = P.bnd.data() + F.bnd_off;
+    const int* b = std::lower_bound(b0, b0 + F.nb, phi);
+    if (b != b0 + F.nb && *b == phi) lrow = F.own + (int)(b - b0);
+  }
+  if (lrow < 0) return false;
+  // stored block: rows of the later-eliminated pose, columns of the earlier one; the caller's rows are pi's
+  *out = make_int4(f, lrow, plo - F.e0, pi < pj ? 1 : 0);
+  return true;
+}
+
+// The factor phase at the current poses (mfront_factorize: the multifrontal path's own launches), then the selected inversion top-down.
+int selinv_run(sgo_ctx* c, Mfront* m) {
+  const MfPlan& P = m->plan;
+  const MfDev& D = m->dev;
+  {
+    Scope sc(c, K_MF_FACTOR, mfront_bytes(m, c->E, 1), true);
+    HIP_TRY(c, mfront_factorize(m, c->stream, c->el, c->d_poses, c->d_hist, c->d_dres));
+  }
+  for (int h = P.height; h >= 0; --h) {
+    const int cnt = P.level_ptr[h + 1] - P.level_ptr[h];
+    const int t0 = m->gtile_ptr[h], t1 = m->gtile_ptr[h + 1];
+    if (t1 > t0) {
+      Scope sc(c, K_SI_GATHER, 16.0 * 256.0 * (t1 - t0));
+      launch_si_gather(c->stream, D, m->sel, t0, t1);
+    }
+    Scope sc(c, K_SI_PANELS, 0.0);
+    launch_si_panels(c->stream, D, m->sel, P.level_ptr[h], cnt, (size_t)m->level_lds[h]);
+  }
+  m->sel_ran = true;
+  return SGO_OK;
+}
+
+}  // namespace sgo
 
 extern "C" {
 
@@ -171,37 +222,20 @@ int sgo_marginals_selected(sgo_ctx* c, double* diag, int32_t npairs, const int32
     Mfront* m = nullptr;
     if ((rc = selinv_plan(c, &m, "sgo_marginals_selected", "sgo_marginals"))) return rc;
     const MfPlan& P = m->plan;
-    // the pairs in the plan's terms: the front of the endpoint eliminated first holds the block, if any front does
-    std::vector<int> pos_of((size_t)c->n, -1);   // hessian index -> elimination position
-    for (int p = 0; p < P.n; ++p) {
-      const auto f = std::lower_bound(c->free_id.begin(), c->free_id.end(), P.elim_vertex[p]);
-      pos_of[(size_t)(f - c->free_id.begin())] = p;
-    }
-    if ((rc = selinv_prepare(c, m))) return rc;
+    // the pairs in the plan's terms
+    const std::vector<int> pos_of = selinv_positions(c, m);
+    if ((rc = selinv_prepare(c, m, "sgo_marginals_selected"))) return rc;
     std::vector<int4> pairs((size_t)npairs);
     for (int t = 0; t < npairs; ++t) {
       if (hi[t] < 0 || hj[t] < 0) {
         pairs[t] = make_int4(-1, 0, 0, 0);
         continue;
       }
-      const int pi = pos_of[hi[t]], pj = pos_of[hj[t]];
-      const int plo = std::min(pi, pj), phi = std::max(pi, pj);
-      const int f = m->pos_front[plo];
-      const MfFront& F = P.fronts[f];
-      int lrow = -1;
-      if (phi < F.e0 + F.own) lrow = phi - F.e0;
-      else {
-        const int* b0 = P.bnd.data() + F.bnd_off;
-        const int* b = std::lower_bound(b0, b0 + F.nb, phi);
-        if (b != b0 + F.nb && *b == phi) lrow = F.own + (int)(b - b0);
-      }
-      if (lrow < 0) {
+      if (!selinv_pair(m, pos_of[hi[t]], pos_of[hj[t]], &pairs[t])) {
         c->err = "sgo_marginals_selected: the pair (" + std::to_string(vi[t]) + ", " + std::to_string(vj[t]) +
                  ") lies outside the factor's pattern (no front holds both poses): use sgo_marginals for it";
         return SGO_EINVAL;
       }
-      // stored block: rows of the later-eliminated pose, columns of the earlier one; the caller's rows are vi's
-      pairs[t] = make_int4(f, lrow, plo - F.e0, pi < pj ? 1 : 0);
     }
     sgo_ctx::SelInv& Z = c->selinv;
     const size_t nout = 9 * ((size_t)c->V + (size_t)npairs) + 1;
@@ -209,26 +243,11 @@ int sgo_marginals_selected(sgo_ctx* c, double* diag, int32_t npairs, const int32
     HIP_TRY(c, hipMemsetAsync(Z.d_out, 0, sizeof(double) * nout, c->stream));
     if (npairs > 0) HIP_TRY(c, hipMemcpyAsync(Z.d_pairs, pairs.data(), sizeof(int4) * (size_t)npairs, hipMemcpyHostToDevice, c->stream));
 
-    const MfDev& D = m->dev;
-    {
-      Scope sc(c, K_MF_FACTOR, mfront_bytes(m, c->E, 1), true);
-      HIP_TRY(c, mfront_factorize(m, c->stream, c->el, c->d_poses, c->d_hist, c->d_dres));
-    }
-    for (int h = P.height; h >= 0; --h) {
-      const int cnt = P.level_ptr[h + 1] - P.level_ptr[h];
-      const int t0 = m->gtile_ptr[h], t1 = m->gtile_ptr[h + 1];
-      if (t1 > t0) {
-        Scope sc(c, K_SI_GATHER, 16.0 * 256.0 * (t1 - t0));
-        launch_si_gather(c->stream, D, m->sel, t0, t1);
-      }
-      Scope sc(c, K_SI_PANELS, 0.0);
-      launch_si_panels(c->stream, D, m->sel, P.level_ptr[h], cnt, (size_t)m->level_lds[h]);
-    }
+    if ((rc = selinv_run(c, m))) return rc;
     {
       Scope sc(c, K_SI_RESULT, 16.0 * 9.0 * ((double)c->n + npairs));
-      launch_si_result(c->stream, D, m->sel, c->V, npairs, Z.d_pairs, Z.d_out);
+      launch_si_result(c->stream, m->dev, m->sel, c->V, npairs, Z.d_pairs, Z.d_out);
     }
-    m->sel_ran = true;
     HIP_TRY(c, hipGetLastError());
     std::vector<double> out(nout);
     HIP_TRY(c, hipMemcpyAsync(out.data(), Z.d_out, sizeof(double) * nout, hipMemcpyDeviceToHost, c->stream));
