@@ -1117,6 +1117,32 @@ class SparseOptimizer : public OptimizableGraph {
     return rc;
   }
 
+  // the candidates of sgoCandidateJoint / sgoJointGreedy / sgoJointExtend as the C-ABI takes them; false: a null edge or vertex, a vertex
+  // that is not an active one
+  bool jointCandidates(const std::vector<EdgeSE2*>& candidates, std::vector<int32_t>& ci, std::vector<int32_t>& cj, std::vector<double>& meas,
+                       std::vector<double>& info) const {
+    const size_t n = candidates.size();
+    ci.assign(n, 0), cj.assign(n, 0);
+    meas.assign(3 * n, 0.0), info.assign(6 * n, 0.0);
+    for (size_t t = 0; t < n; ++t) {
+      const EdgeSE2* e = candidates[t];
+      if (!e) return false;
+      for (int side = 0; side < 2; ++side) {
+        const HyperGraph::Vertex* v = e->vertex(side);
+        if (!v) return false;
+        auto it = std::lower_bound(_activeVertices.begin(), _activeVertices.end(), v->id(),
+                                   [](const OptimizableGraph::Vertex* a, int id) { return a->id() < id; });
+        if (it == _activeVertices.end() || *it != v) return false;
+        (side ? cj : ci)[t] = (int32_t)(it - _activeVertices.begin());
+      }
+      for (int q = 0; q < 3; ++q) meas[3 * t + q] = e->measurement()[q];
+      const auto& O = e->information();
+      double* o = &info[6 * t];
+      o[0] = O(0, 0); o[1] = O(0, 1); o[2] = O(0, 2); o[3] = O(1, 1); o[4] = O(1, 2); o[5] = O(2, 2);
+    }
+    return true;
+  }
+
   // ---- joint compatibility of a set of candidate closures (extension; sgo_candidate_joint / sgo_joint_subsets of include/sgo.h):
   // the candidates are EdgeSE2 objects as sgoCandidateGate takes them; subsets[b] lists the candidates (indices into `candidates`,
   // any order, a repeated index counts once) of subset b.  (*d2)[b] = e_s^T (S_ss)^-1 e_s with the candidates' cross-covariances at
@@ -1129,24 +1155,9 @@ class SparseOptimizer : public OptimizableGraph {
     if (!_algorithm || _activeRevision != _revision || _activeVertices.empty() || !gpuEligible()) return -1;
     const size_t n = candidates.size(), B = subsets.size();
     if (!chi2Max.empty() && chi2Max.size() != B) return -1;
-    std::vector<int32_t> ci(n), cj(n);
-    std::vector<double> meas(3 * n), info(6 * n);
-    for (size_t t = 0; t < n; ++t) {
-      const EdgeSE2* e = candidates[t];
-      if (!e) return -1;
-      for (int side = 0; side < 2; ++side) {
-        const HyperGraph::Vertex* v = e->vertex(side);
-        if (!v) return -1;
-        auto it = std::lower_bound(_activeVertices.begin(), _activeVertices.end(), v->id(),
-                                   [](const OptimizableGraph::Vertex* a, int id) { return a->id() < id; });
-        if (it == _activeVertices.end() || *it != v) return -1;
-        (side ? cj : ci)[t] = (int32_t)(it - _activeVertices.begin());
-      }
-      for (int q = 0; q < 3; ++q) meas[3 * t + q] = e->measurement()[q];
-      const auto& O = e->information();
-      double* o = &info[6 * t];
-      o[0] = O(0, 0); o[1] = O(0, 1); o[2] = O(0, 2); o[3] = O(1, 1); o[4] = O(1, 2); o[5] = O(2, 2);
-    }
+    std::vector<int32_t> ci, cj;
+    std::vector<double> meas, info;
+    if (!jointCandidates(candidates, ci, cj, meas, info)) return -1;
     std::vector<uint8_t> mask(std::max<size_t>(B * n, 1), 0);
     for (size_t b = 0; b < B; ++b)
       for (int t : subsets[b]) {
@@ -1175,6 +1186,92 @@ class SparseOptimizer : public OptimizableGraph {
     if (pass) {
       pass->resize(chi2Max.empty() ? 0 : B);
       for (size_t b = 0; b < pass->size(); ++b) (*pass)[b] = ok[b] != 0;
+    }
+    return rc;
+  }
+
+  // ---- greedy search for a large jointly compatible set (extension; sgo_joint_greedy / sgo_joint_extend of include/sgo.h): the
+  // candidates are sgoCandidateJoint's; seeds[b] lists the candidates (indices into `candidates`, in this order) forced into search b,
+  // chi2Max[k] bounds the d2 of a set of k candidates (SGO_JOINT_MAX_SUBSET + 1 entries, [0] ignored; empty: no growth), allow[b][t]
+  // false keeps candidate t out of search b's growth (allow empty: all).  (*out)[b]: the order (seed, then the chosen ones), why the
+  // search stopped (SGO_JSTOP_*), d2 after every pivot (order.size() + 1 entries) and d2 of the final set with each candidate added.
+  // Returns how many searches ran; -1 without touching the outputs where sgoCandidateJoint returns it, for an allow of another shape
+  // and when the call itself refuses (an index outside the candidates or listed twice, maxLen below a seed's length or above
+  // SGO_JOINT_MAX_SUBSET, a chi2Max of another length; one line on std::cerr).
+  struct SgoJointPath {
+    std::vector<int> order;
+    int stop = 0;
+    std::vector<double> d2Path, d2Ext;
+  };
+  int sgoJointGreedy(const std::vector<EdgeSE2*>& candidates, const std::vector<std::vector<int>>& seeds, const std::vector<double>& chi2Max, int maxLen,
+                     const std::vector<std::vector<bool>>& allow, std::vector<SgoJointPath>* out) {
+    return jointSearch(candidates, seeds, &chi2Max, maxLen, allow, out, nullptr, nullptr);
+  }
+  // ... and its primitive without growth: (*d2)[b] of list b and (*d2Ext)[b][t] = d2 of the list with candidate t added
+  int sgoJointExtend(const std::vector<EdgeSE2*>& candidates, const std::vector<std::vector<int>>& lists, std::vector<double>* d2,
+                     std::vector<std::vector<double>>* d2Ext) {
+    return jointSearch(candidates, lists, nullptr, -1, std::vector<std::vector<bool>>(), nullptr, d2, d2Ext);
+  }
+
+  int jointSearch(const std::vector<EdgeSE2*>& candidates, const std::vector<std::vector<int>>& seeds, const std::vector<double>* chi2Max, int maxLen,
+                  const std::vector<std::vector<bool>>& allow, std::vector<SgoJointPath>* out, std::vector<double>* d2, std::vector<std::vector<double>>* d2Ext) {
+    if (!_algorithm || _activeRevision != _revision || _activeVertices.empty() || !gpuEligible()) return -1;
+    const size_t n = candidates.size(), B = seeds.size(), kS = SGO_JOINT_MAX_SUBSET;
+    const char* who = chi2Max ? "SparseOptimizer::sgoJointGreedy: " : "SparseOptimizer::sgoJointExtend: ";
+    if (chi2Max && !chi2Max->empty() && chi2Max->size() != kS + 1) {
+      std::cerr << who << "chi2Max needs SGO_JOINT_MAX_SUBSET + 1 entries" << std::endl;
+      return -1;
+    }
+    if (!allow.empty() && allow.size() != B) return -1;
+    std::vector<int32_t> ci, cj;
+    std::vector<double> meas, info;
+    if (!jointCandidates(candidates, ci, cj, meas, info)) return -1;
+    std::vector<int32_t> rows(std::max<size_t>(B, 1) * kS, -1);
+    std::vector<uint8_t> mask(std::max<size_t>(B * n, 1), 1);
+    for (size_t b = 0; b < B; ++b) {
+      if (seeds[b].size() > kS) {
+        std::cerr << who << "list " << b << " names more than SGO_JOINT_MAX_SUBSET candidates" << std::endl;
+        return -1;
+      }
+      for (size_t k = 0; k < seeds[b].size(); ++k) {
+        if (seeds[b][k] < 0 || (size_t)seeds[b][k] >= n) return -1;
+        rows[b * kS + k] = seeds[b][k];
+      }
+      if (!allow.empty()) {
+        if (allow[b].size() != n) return -1;
+        for (size_t t = 0; t < n; ++t) mask[b * n + t] = allow[b][t] ? 1 : 0;
+      }
+    }
+    if (n == 0) {
+      std::cerr << who << "no candidates" << std::endl;
+      return -1;
+    }
+    if (!uploadGraph()) return -1;
+    int rc = sgo_candidate_joint(_ctx, (int32_t)n, ci.data(), cj.data(), meas.data(), info.data(), nullptr, nullptr);
+    std::vector<int32_t> order(rows.size()), count(std::max<size_t>(B, 1)), stop(std::max<size_t>(B, 1));
+    std::vector<double> path(std::max<size_t>(B, 1) * (kS + 1)), ext(std::max<size_t>(B * n, 1)), dd(std::max<size_t>(B, 1));
+    if (rc >= 0)
+      rc = chi2Max ? sgo_joint_greedy(_ctx, (int32_t)n, (int32_t)B, rows.data(), allow.empty() ? nullptr : mask.data(), chi2Max->empty() ? nullptr : chi2Max->data(),
+                                      maxLen, order.data(), count.data(), stop.data(), path.data(), ext.data())
+                   : sgo_joint_extend(_ctx, (int32_t)n, (int32_t)B, rows.data(), dd.data(), ext.data());
+    if (rc < 0) {
+      std::cerr << who << sgo_last_error(_ctx) << std::endl;
+      return -1;
+    }
+    if (out) {
+      out->assign(B, SgoJointPath());
+      for (size_t b = 0; b < B; ++b) {
+        SgoJointPath& p = (*out)[b];
+        p.order.assign(order.begin() + b * kS, order.begin() + b * kS + count[b]);
+        p.stop = stop[b];
+        p.d2Path.assign(path.begin() + b * (kS + 1), path.begin() + b * (kS + 1) + count[b] + 1);
+        p.d2Ext.assign(ext.begin() + b * n, ext.begin() + (b + 1) * n);
+      }
+    }
+    if (d2) d2->assign(dd.begin(), dd.begin() + B);
+    if (d2Ext) {
+      d2Ext->assign(B, std::vector<double>());
+      for (size_t b = 0; b < B; ++b) (*d2Ext)[b].assign(ext.begin() + b * n, ext.begin() + (b + 1) * n);
     }
     return rc;
   }

@@ -609,6 +609,46 @@ int sgo_edge_leave_one_out(sgo_ctx* ctx, int32_t n, const int32_t* edge_ids /*NU
 int sgo_edge_loo_rule(const double* info6, const double* P9, const double* e3, double w, double* d2, double* redundancy,
                       double* cov_loo /*[9] or NULL*/);
 
+/* (later additions, version 107) Greedy search for a large jointly compatible set on the resident table of sgo_candidate_joint
+ * (DESIGN.md section 5l): "which of these candidates form the largest consistent set?" without a from-scratch factorisation per
+ * extension.  Growing a subset by one candidate is one step of a block-pivoted Cholesky of S.  After the ordered pivots t_1 .. t_k
+ * (m = 3 k rows) every candidate c holds W_c (m x 3), C_c = S_cc - W_c^T W_c and q_c = e_c - W_c^T z; z (m) and d2 = z^T z are the set's.
+ *   extension value  v_c = d2 + q_c^T C_c^-1 q_c by a 3 x 3 lower Cholesky of C_c: the d2 of the set with c added.  NaN where C_c is
+ *                    not positive definite; d2 itself, bit for bit, for a c that is a pivot already.
+ *   pivot step p     G = chol(C_p), z+ = G^-1 q_p; for every c that is not a pivot w = G^-1 (S_pc - W_p^T W_c), C_c -= w^T w,
+ *                    q_c -= w^T z+, w appended to W_c; d2 += z+^T z+.  Every sum runs in ascending row order.
+ *   greedy rule      at count k < max_len the candidates that are not pivots, have allow[c] != 0 and a finite v_c <= chi2_max[k + 1]
+ *                    are eligible; the smallest v_c is chosen, ties go to the lowest c; none eligible: the search stops.
+ * sgo_joint_greedy runs B searches in one call, one workgroup each.  seed[b]: the candidates forced in, in this order, -1 padded; they are
+ * never tested against chi2_max.  Outputs: order[b] = the seed, then the chosen candidates, then -1; count[b]; stop[b] (SGO_JSTOP_*);
+ * d2_path[b][k] = d2 after k pivots ([0] = 0, NaN behind count); d2_ext[b][c] = v_c at the final set (members: d2_path[b][count] bit for
+ * bit).  A seed pivot whose block is not positive definite ends that seed alone: count = the pivots done before it, order holds those and
+ * -1, SGO_JSTOP_NOT_PD, d2_ext and d2_path behind count NaN.  chi2_max == NULL: no growth (stop is SGO_JSTOP_MAX_LEN when the seed has
+ * max_len candidates, else SGO_JSTOP_NONE).  Returns B.
+ * sgo_joint_extend is sgo_joint_greedy without growth, the primitive of a caller's own branch-and-bound: d2[b] of list b (NaN where
+ * a pivot block is not positive definite) and d2_ext[b][c], the d2 of the list with c added.
+ * Bit for bit: a seed's results depend on the table, its seed, its allow row, chi2_max and max_len alone -- not on B, its place in the
+ * batch or the slicing --; two calls agree; sgo_joint_extend on a returned order gives d2 == d2_path[count] and the same d2_ext.  The
+ * calls read the table and write scratch of their own: a later sgo_optimize_gn has the bits of a context that never called, and
+ * sgo_joint_subsets returns what it returned before.
+ * SGO_EINVAL, nothing written, the table kept: no resident table or n not the table's; B < 0; a null seed, order or count (lists, d2,
+ * d2_ext) with B > 0; a seed entry outside [0, n); a candidate listed twice in a seed; an entry after a -1; max_len outside [the longest
+ * seed's length, SGO_JOINT_MAX_SUBSET]; a non-finite chi2_max[1 ..].  B == 0 returns 0.  SGO_ENOMEM when the scratch (at most 192 MiB:
+ * B is cut into slices of at most 256 seeds) cannot be allocated; the context and the table stay intact.
+ * sgo_joint_greedy_rule: one seed's search on the host through the same arithmetic text as the kernel (sgo_rules.h; no context, no GPU,
+ * like sgo_edge_loo_rule): S (3 n x 3 n row-major), e (3 n), one seed row, one allow row.  Returns 1, or SGO_EINVAL as above. */
+#define SGO_JSTOP_MAX_LEN 0   /* max_len candidates chosen */
+#define SGO_JSTOP_NONE    1   /* no eligible candidate */
+#define SGO_JSTOP_NOT_PD  2   /* a seed pivot's block was not positive definite */
+int sgo_joint_greedy(sgo_ctx* ctx, int32_t n, int32_t B, const int32_t* seed /*[B][SGO_JOINT_MAX_SUBSET], -1 padded*/,
+                     const uint8_t* allow /*[B][n] or NULL = all*/,
+                     const double* chi2_max /*[SGO_JOINT_MAX_SUBSET+1] by count, [0] ignored; NULL = no growth*/, int32_t max_len,
+                     int32_t* order /*[B][SGO_JOINT_MAX_SUBSET]*/, int32_t* count /*[B]*/, int32_t* stop /*[B] or NULL*/,
+                     double* d2_path /*[B][SGO_JOINT_MAX_SUBSET+1] or NULL*/, double* d2_ext /*[B][n] or NULL*/);
+int sgo_joint_extend(sgo_ctx* ctx, int32_t n, int32_t B, const int32_t* lists /*as seed*/, double* d2 /*[B]*/, double* d2_ext /*[B][n]*/);
+int sgo_joint_greedy_rule(int32_t n, const double* S, const double* e, const int32_t* seed, const uint8_t* allow, const double* chi2_max,
+                          int32_t max_len, int32_t* order, int32_t* count, int32_t* stop, double* d2_path, double* d2_ext);
+
 /* ---- profiling (opts.profile = 1) ---------------------------------------------------------- */
 /* Per-kernel totals accumulated since the last sgo_profile_reset: for kernel slot k,
  * name (static string), launches, total milliseconds (HIP events on the ctx stream), and the

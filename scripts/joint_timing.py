@@ -10,7 +10,12 @@ Host clock around calls that end in a synchronise, median of nine warm calls, on
     has to the same decision: the candidates inserted as edges of the graph and masked off per hypothesis,
     sgo_optimize_gn_hypotheses(20, gain 0) over --hyp-b (default 8) of the subsets of 10.
   * profile mode: the per-launch medians of k_fs_gram, k_fs_joint_table and k_joint_subsets.
-Usage: python scripts/joint_timing.py [--gate] [--root DIR] [--hyp-b N] [C1i C1 C3s]   -> one JSON line per config"""
+  * --search (NOTES.md section 43), at n = 64 and 256 candidates, median [min, max] of the warm calls:
+    (a) sgo_joint_extend over B = 1, 64, 1 024 parents of 2, 10 and 39 candidates beside sgo_joint_subsets over the same B (n - k)
+    extended sets (the route without the search's calls: every extension factorised from scratch by its own workgroup);
+    (b) sgo_joint_greedy from the n singleton seeds under the 99 % chi2 ladder beside the host loop that calls sgo_joint_subsets once
+    per step over every live path's extensions; and k_joint_grow's per-launch median in profile mode.
+Usage: python scripts/joint_timing.py [--gate | --search] [--root DIR] [--hyp-b N] [C1i C1 C3s]   -> one JSON line per config"""
 import json
 import os
 import sys
@@ -86,6 +91,104 @@ def run_gate(name):
         opt.optimize(8)
         warm = {k: _warm(lambda k=k: opt.candidate_gate(ci[:k], cj[:k], meas[:k], info[:k], 11.345)) for k in COUNTS}
     return dict(config=name, lib=ROOT, path=path, what="gate alone", gate_warm_ms=warm)
+
+
+def _spread(fn, reps=REPS):
+    """median [min, max] of `reps` warm calls, milliseconds"""
+    fn()
+    t = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        fn()
+        t.append(1e3 * (time.perf_counter() - t0))
+    return [round(float(np.median(t)), 4), round(min(t), 4), round(max(t), 4)]
+
+
+def _extension_masks(parents, n):
+    """the sets parent + {c}, c not in the parent: [B (n - k)][n]"""
+    rows = []
+    for p in parents:
+        base = np.zeros(n, dtype=np.uint8)
+        base[p] = 1
+        free = np.flatnonzero(base == 0)
+        M = np.repeat(base[None, :], free.size, axis=0)
+        M[np.arange(free.size), free] = 1
+        rows.append(M)
+    return np.concatenate(rows)
+
+
+def _host_greedy(opt, n, chi, max_len=40):
+    """the greedy search of the n singleton seeds driven from the host: one sgo_joint_subsets per step over every live path's
+    extensions -> (orders, steps)"""
+    sets = [[s] for s in range(n)]
+    live = list(range(n))
+    steps = 0
+    while live:
+        M = _extension_masks([sets[b] for b in live], n)
+        d2 = opt.joint_subsets(M)[1]
+        steps += 1
+        nxt, at = [], 0
+        for b in live:
+            k = len(sets[b])
+            v = d2[at:at + n - k]
+            at += n - k
+            free = np.setdiff1d(np.arange(n), sets[b])
+            ok = v <= chi[k + 1]
+            if ok.any():
+                sets[b].append(int(free[np.argmin(np.where(ok, v, np.inf))]))
+                if len(sets[b]) < max_len:
+                    nxt.append(b)
+        live = nxt
+    return sets, steps
+
+
+def run_search(name):
+    from scipy.stats import chi2 as chi2_dist
+    g = synth.config(name)
+    ci, cj, meas, info = _closure_candidates(g, 256)
+    chi = np.concatenate([[0.0], chi2_dist.ppf(0.99, 3 * np.arange(1, 41))])
+    out = dict(config=name, lib=ROOT, V=g.V, E=g.E, what="search: median [min, max] ms")
+    with capi.Optimizer(0) as opt:
+        opt.set_graph(*g.arrays())
+        out["path"] = opt.solver_description().split(":")[0]
+        opt.optimize(8)
+        for n in (64, 256):
+            opt.candidate_joint(ci[:n], cj[:n], meas[:n], info[:n])
+            rng = np.random.default_rng(17)
+            ext, sub, agree = {}, {}, 0.0
+            for k in (2, 10, 39):
+                for B in (1, 64, 1024):
+                    parents = [rng.permutation(n)[:k] for _ in range(B)]
+                    M = _extension_masks(parents, n)
+                    ext[f"{k}x{B}"] = _spread(lambda parents=parents: opt.joint_extend(parents))
+                    sub[f"{k}x{B}"] = _spread(lambda M=M: opt.joint_subsets(M), 3 if M.shape[0] > 20000 else REPS)
+                    if B <= 64:
+                        a, b = opt.joint_extend(parents)[1], opt.joint_subsets(M)[1]
+                        free = np.concatenate([np.setdiff1d(np.arange(n), p) + n * i for i, p in enumerate(parents)])
+                        agree = max(agree, float(np.nanmax(np.abs(a.reshape(-1)[free] - b) / b)))
+            seeds = [[t] for t in range(n)]
+            order, count, _, _, _ = opt.joint_greedy(seeds, chi)
+            host_sets, steps = _host_greedy(opt, n, chi)
+            same = sum(list(order[b, :count[b]]) == host_sets[b] for b in range(n))
+            out[f"n={n}"] = dict(extend_ms=ext, subsets_same_sets_ms=sub, worst_disagreement=agree,
+                                 greedy_ms=_spread(lambda: opt.joint_greedy(seeds, chi)), host_loop_ms=_spread(lambda: _host_greedy(opt, n, chi), 2),
+                                 host_loop_steps=steps, path_lengths=[int(count.min()), int(np.median(count)), int(count.max())],
+                                 paths_equal_to_host_loop=f"{same}/{n}")
+    with capi.Optimizer(0, profile=1) as opt:
+        opt.set_graph(*g.arrays())
+        opt.optimize(8)
+        kernels = {}
+        for n in (64, 256):
+            opt.candidate_joint(ci[:n], cj[:n], meas[:n], info[:n])
+            seeds = [[t] for t in range(n)]
+            opt.joint_greedy(seeds, chi)
+            opt.profile_reset()
+            for _ in range(REPS):
+                opt.joint_greedy(seeds, chi)
+            prof = opt.kernel_profile(quantiles=True)
+            kernels[f"n={n}, {n} singleton seeds"] = dict(ms_per_call=prof["k_joint_grow"]["ms"] / REPS, median_launch_us=prof["k_joint_grow"].get("median_us"))
+        out["kernels"] = kernels
+    return out
 
 
 def run(name, hyp_b):
@@ -165,4 +268,4 @@ if __name__ == "__main__":
     names = [a for a in ARGS if a in ("C1i", "C1", "C3s", "C2", "C4")] or ["C1i", "C1", "C3s"]
     hyp_b = int(ARGS[ARGS.index("--hyp-b") + 1]) if "--hyp-b" in ARGS else 8
     for name in names:
-        print(json.dumps(run_gate(name) if "--gate" in ARGS else run(name, hyp_b)), flush=True)
+        print(json.dumps(run_gate(name) if "--gate" in ARGS else run_search(name) if "--search" in ARGS else run(name, hyp_b)), flush=True)

@@ -37,6 +37,7 @@ SYMBOLS = [
     "sgo_solve_rhs", "sgo_marginals", "sgo_marginals_selected", "sgo_factor_solve", "sgo_candidate_gate",
     "sgo_gain_stop", "sgo_optimize_gn_until", "sgo_optimize_gn_hypotheses", "sgo_hypothesis_isolated_vertex",
     "sgo_candidate_joint", "sgo_joint_subsets", "sgo_joint_pairs", "sgo_edge_leave_one_out", "sgo_edge_loo_rule",
+    "sgo_joint_greedy", "sgo_joint_extend", "sgo_joint_greedy_rule",
     "sgo_set_hypotheses_workspace", "sgo_hypotheses_bytes", "sgo_hypotheses_chunk", "sgo_hypotheses_workspace_bytes",
 ]
 
@@ -73,6 +74,52 @@ def edge_loo_rule(info6, P, e, w: float):
     d2, red, cov = C.c_double(), C.c_double(), np.empty((3, 3))
     rc = lib().sgo_edge_loo_rule(_dp(o), _dp(Pm), _dp(ev), float(w), C.byref(d2), C.byref(red), _dp(cov))
     return rc, d2.value, red.value, cov
+
+
+# SGO_JSTOP_*: why a search of sgo_joint_greedy ended
+JSTOP_MAX_LEN, JSTOP_NONE, JSTOP_NOT_PD = 0, 1, 2
+
+
+def joint_lists(lists):
+    """index lists (or a (B, 40) array, -1 padded) -> the [B][SGO_JOINT_MAX_SUBSET] int32 rows sgo_joint_greedy / sgo_joint_extend take"""
+    if isinstance(lists, np.ndarray) and lists.ndim == 2 and lists.shape[1] == JOINT_MAX_SUBSET:
+        return np.ascontiguousarray(lists, dtype=np.int32)
+    out = np.full((len(lists), JOINT_MAX_SUBSET), -1, dtype=np.int32)
+    for b, idx in enumerate(lists):
+        idx = np.asarray(idx, dtype=np.int32).reshape(-1)
+        if idx.size > JOINT_MAX_SUBSET:
+            raise ValueError(f"list {b} has {idx.size} entries, more than SGO_JOINT_MAX_SUBSET = {JOINT_MAX_SUBSET}")
+        out[b, :idx.size] = idx
+    return out
+
+
+def _chi2_ladder(chi2_max):
+    if chi2_max is None:
+        return None
+    chi = np.ascontiguousarray(chi2_max, dtype=np.float64).reshape(-1)
+    if chi.size != JOINT_MAX_SUBSET + 1:
+        raise ValueError(f"chi2_max needs {JOINT_MAX_SUBSET + 1} entries by count ([0] is ignored)")
+    return chi
+
+
+def joint_greedy_rule(S, e, seed, chi2_max, max_len: int = JOINT_MAX_SUBSET, allow=None):
+    """sgo_joint_greedy_rule: one seed's greedy search as the library (and its kernel) computes it, no context and no GPU: S (3 n, 3 n),
+    e (n, 3), seed an index list, chi2_max (41,) by count or None -> (rc, order (40,), count, stop, d2_path (41,), d2_ext (n,));
+    rc 1, or SGO_EINVAL (-2) for what sgo_joint_greedy refuses in its lists and thresholds."""
+    Sm = np.ascontiguousarray(S, dtype=np.float64)
+    ev = np.ascontiguousarray(e, dtype=np.float64).reshape(-1)
+    n = ev.size // 3
+    if Sm.shape != (3 * n, 3 * n):
+        raise ValueError("inconsistent array sizes")
+    sd, chi = joint_lists([seed]), _chi2_ladder(chi2_max)
+    al = None if allow is None else np.ascontiguousarray(np.asarray(allow) != 0, dtype=np.uint8).reshape(n)
+    order, cnt, stop = np.full(JOINT_MAX_SUBSET, -2, dtype=np.int32), C.c_int32(-1), C.c_int32(-1)
+    path, ext = np.empty(JOINT_MAX_SUBSET + 1), np.empty(n)
+    u8p = C.POINTER(C.c_uint8)
+    rc = lib().sgo_joint_greedy_rule(n, _dp(Sm), _dp(ev), _ip(sd), None if al is None else al.ctypes.data_as(u8p), None if chi is None else _dp(chi),
+                                     int(max_len), _ip(order), C.byref(cnt), C.byref(stop),
+                                     _dp(path), _dp(ext))
+    return rc, order, cnt.value, stop.value, path, ext
 
 
 class Opts(C.Structure):
@@ -210,6 +257,9 @@ def lib():
     L.sgo_joint_pairs.argtypes = [vp, C.c_int32, d]
     L.sgo_edge_leave_one_out.argtypes = [vp, C.c_int32, i32, C.c_double, C.c_double, d, d, d, u8]
     L.sgo_edge_loo_rule.argtypes = [d, d, d, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double), d]
+    L.sgo_joint_greedy.argtypes = [vp, C.c_int32, C.c_int32, i32, u8, d, C.c_int32, i32, i32, i32, d, d]
+    L.sgo_joint_extend.argtypes = [vp, C.c_int32, C.c_int32, i32, d, d]
+    L.sgo_joint_greedy_rule.argtypes = [C.c_int32, d, d, i32, u8, d, C.c_int32, i32, i32, i32, d, d]
     L.sgo_kernel_profile.argtypes = [vp, C.POINTER(KernelStat), C.c_int]
     L.sgo_kernel_profile_samples.argtypes = [vp, C.c_int, C.POINTER(C.c_float), C.c_int]
     L.sgo_solver_description.restype = C.c_char_p
@@ -841,6 +891,33 @@ class Optimizer:
         if rc < 0:
             raise SgoError(f"sgo_joint_pairs: rc={rc}: " + lib().sgo_last_error(self._h).decode())
         return d2
+
+    def joint_greedy(self, seeds, chi2_max, max_len: int = JOINT_MAX_SUBSET, allow=None):
+        """sgo_joint_greedy: one greedy search per seed (index lists, or a (B, 40) array, -1 padded) on the resident table: from the
+        forced seed the candidate with the smallest extension value v_c <= chi2_max[count + 1] is added (ties to the lowest index)
+        until none is eligible or max_len are chosen -> (order (B, 40), count (B,), stop (B,), d2_path (B, 41), d2_ext (B, n)).
+        allow (B, n): zero excludes a candidate from a seed's growth; chi2_max None: no growth."""
+        sd, chi = joint_lists(seeds), _chi2_ladder(chi2_max)
+        B, n = sd.shape[0], int(getattr(self, "joint_n", 0))
+        al = None if allow is None else np.ascontiguousarray(np.asarray(allow) != 0, dtype=np.uint8).reshape(B, n)
+        order, cnt, stop = np.empty((B, JOINT_MAX_SUBSET), dtype=np.int32), np.empty(B, dtype=np.int32), np.empty(B, dtype=np.int32)
+        path, ext = np.empty((B, JOINT_MAX_SUBSET + 1)), np.empty((B, n))
+        rc = lib().sgo_joint_greedy(self._h, n, B, _ip(sd), None if al is None else al.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                    None if chi is None else _dp(chi), int(max_len), _ip(order), _ip(cnt), _ip(stop), _dp(path), _dp(ext))
+        if rc < 0:
+            raise SgoError(f"sgo_joint_greedy: rc={rc}: " + lib().sgo_last_error(self._h).decode())
+        return order, cnt, stop, path, ext
+
+    def joint_extend(self, lists):
+        """sgo_joint_extend: for every ordered list of candidates of the resident table, d2 of the list and d2 of the list with each
+        candidate added -> (d2 (B,), d2_ext (B, n)); members of a list hold its d2 bit for bit."""
+        sd = joint_lists(lists)
+        B, n = sd.shape[0], int(getattr(self, "joint_n", 0))
+        d2, ext = np.empty(B), np.empty((B, n))
+        rc = lib().sgo_joint_extend(self._h, n, B, _ip(sd), _dp(d2), _dp(ext))
+        if rc < 0:
+            raise SgoError(f"sgo_joint_extend: rc={rc}: " + lib().sgo_last_error(self._h).decode())
+        return d2, ext
 
     def marginals(self, vi, vj):
         """sgo_marginals: the 3x3 blocks of H^-1 (rows of vertex vi[t], columns of vertex vj[t]; vertex ids) at the current poses

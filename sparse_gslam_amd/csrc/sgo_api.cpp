@@ -385,7 +385,8 @@ void sgo_destroy(sgo_ctx* c) {
   if (c->selinv.d_cidx) hipFree(c->selinv.d_cidx);
   if (c->selinv.d_loo) hipFree(c->selinv.d_loo);
   if (c->selinv.d_loo_ids) hipFree(c->selinv.d_loo_ids);
-  for (void* p : {(void*)c->joint.d_tab[0], (void*)c->joint.d_tab[1], (void*)c->joint.d_raw, (void*)c->joint.d_d2, (void*)c->joint.d_mask})
+  for (void* p : {(void*)c->joint.d_tab[0], (void*)c->joint.d_tab[1], (void*)c->joint.d_raw, (void*)c->joint.d_d2, (void*)c->joint.d_mask,
+                  (void*)c->joint.d_grow, (void*)c->joint.d_gout, (void*)c->joint.d_gint})
     if (p) hipFree(p);
   if (c->hyp.d_ws) hipFree(c->hyp.d_ws);
   if (c->stream) hipStreamDestroy(c->stream);

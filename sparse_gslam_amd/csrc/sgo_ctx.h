@@ -306,6 +306,12 @@ struct sgo_ctx {
     uint8_t* d_mask = nullptr;
     size_t raw_cap = 0, d2_cap = 0, mask_cap = 0;
     bool lds_ready = false;
+    // sgo_joint_greedy / sgo_joint_extend (sgo_jsearch.cpp): the slice's slabs of W; chi2_max, then d2_path and d2_ext of every
+    // seed; the seeds, then order, count and stop.  The allow rows go through d_mask.
+    double* d_grow = nullptr;
+    double* d_gout = nullptr;
+    int* d_gint = nullptr;
+    size_t grow_cap = 0, gout_cap = 0, gint_cap = 0;
   } joint;
 
   // profiling

@@ -319,8 +319,12 @@ int cand_columns(sgo_ctx* c, const char* name, int n, const int32_t* ci, const i
   return SGO_OK;
 }
 
-// what sgo_joint_subsets and sgo_joint_pairs refuse alike
-int joint_table_check(sgo_ctx* c, const char* name, int32_t n) {
+constexpr int kJointLaunch = 1 << 20;   // subsets (workgroups) per launch
+
+}  // namespace
+
+// what sgo_joint_subsets, sgo_joint_pairs and the search's calls (sgo_jsearch.cpp) refuse alike
+int sgo::joint_table_check(sgo_ctx* c, const char* name, int32_t n) {
   int rc = check_graph(c);
   if (rc) return rc;
   if (c->joint.n < 0) {
@@ -333,9 +337,6 @@ int joint_table_check(sgo_ctx* c, const char* name, int32_t n) {
   }
   return SGO_OK;
 }
-constexpr int kJointLaunch = 1 << 20;   // subsets (workgroups) per launch
-
-}  // namespace
 
 extern "C" {
 

@@ -386,6 +386,7 @@ enum KernelId : int {
   K_JOINT_SUBSETS,
   K_MFRONT_BATCH,       // sgo_optimize_gn_hypotheses' batched route on the multifrontal path: all launches of one chain (sgo_mfront.h)
   K_LOO_EDGES,          // sgo_edge_leave_one_out: the edge kernel after sgo_marginals_selected's two phases (sgo_loo.hip)
+  K_JOINT_GROW,         // sgo_joint_greedy / sgo_joint_extend: one launch per slice of seeds (sgo_jsearch.hip)
   K_COUNT
 };
 extern const char* const kKernelNames[K_COUNT];

@@ -223,5 +223,30 @@ void launch_fs_joint_table(hipStream_t s, const FsCandDev& C, const double* G, c
 void launch_joint_subsets(hipStream_t s, const double* table, int n, const uint8_t* mask, int b0, int count, int rows_cap, double* d2);
 bool joint_prepare_device();   // the subset kernel's dynamic LDS
 inline size_t joint_lds_bytes(int rows) { return sizeof(double) * (size_t)(rows + 1) * (size_t)(rows | 1) + sizeof(double) * (size_t)std::max(rows, 1); }
+// what sgo_joint_subsets, sgo_joint_pairs and the search's calls refuse alike: no resident table, n not the table's (sgo_fsolve.cpp)
+int joint_table_check(sgo_ctx* c, const char* name, int32_t n);
+
+// ---- the greedy search on the joint table (sgo_joint_greedy / sgo_joint_extend; kernel in sgo_jsearch.hip, driver in sgo_jsearch.cpp) ----
+// One workgroup per seed of a slice, each with its own slab of W [3 max_len][3 n].  A slice holds at most kJointGrowSlabs slabs (one
+// per compute unit) and at most kJointGrowScratchBytes of them: 256 slabs at the caps are 256 x 3 x 40 x 3 x 256 x 8 = 180 MiB.
+constexpr int kJointGrowSlabs = 256;
+constexpr size_t kJointGrowScratchBytes = (size_t)192 << 20;
+inline size_t joint_grow_slab_doubles(int n, int max_len) { return std::max<size_t>(9 * (size_t)max_len * (size_t)n, 1); }
+inline int joint_grow_slice(int n, int max_len, int B) {
+  const size_t fit = kJointGrowScratchBytes / (sizeof(double) * joint_grow_slab_doubles(n, max_len));
+  return (int)std::max<size_t>(1, std::min<size_t>(std::min<size_t>(fit, kJointGrowSlabs), (size_t)std::max(B, 1)));
+}
+struct JointGrowDev {
+  const double* table = nullptr;   // S, e, the flag (joint_table_doubles)
+  int n = 0, max_len = 0, b0 = 0;  // candidates; pivots at most; the slice's first seed
+  const int* seed = nullptr;       // [B][SGO_JOINT_MAX_SUBSET], -1 padded
+  const uint8_t* allow = nullptr;  // [B][n] or nullptr: all
+  const double* chi2 = nullptr;    // [SGO_JOINT_MAX_SUBSET + 1] by count, or nullptr: no growth
+  double* slabs = nullptr;         // [slice][slab]
+  size_t slab = 0;                 // doubles per slab
+  int *order = nullptr, *count = nullptr, *stop = nullptr;   // [B][SGO_JOINT_MAX_SUBSET], [B], [B]
+  double *d2_path = nullptr, *d2_ext = nullptr;              // [B][SGO_JOINT_MAX_SUBSET + 1], [B][n]
+};
+void launch_joint_grow(hipStream_t s, const JointGrowDev& A, int count);   // seeds A.b0 .. A.b0 + count, count <= the slice
 
 }  // namespace sgo

@@ -142,6 +142,88 @@ SGO_RULE_HD inline int edge_loo(const double* info, const double* P, const doubl
   return 0;
 }
 
+// The 3 x 3 pieces of sgo_joint_greedy's block-pivoted Cholesky.  A candidate c keeps C_c = S_cc - W_c^T W_c
+// as its lower triangle C6 = [c00 c10 c11 c20 c21 c22] and q_c = e_c - W_c^T z.  `double`, comparisons and sqrt only: the host
+// (sgo_joint_greedy_rule) and k_joint_grow compile this text.
+// jgrow_chol3: C = G G^T, G6 packed as C6; false (G6 not to be used) when C is not positive definite or not finite.
+SGO_RULE_HD inline bool jgrow_chol3(const double* C6, double* G6) {
+  const double g00 = sqrt(C6[0]), g10 = C6[1] / g00, g20 = C6[3] / g00;
+  const double t11 = C6[2] - g10 * g10, g11 = sqrt(t11), g21 = (C6[4] - g20 * g10) / g11;
+  const double t22 = C6[5] - g20 * g20 - g21 * g21, g22 = sqrt(t22);
+  G6[0] = g00, G6[1] = g10, G6[2] = g11, G6[3] = g20, G6[4] = g21, G6[5] = g22;
+  return C6[0] > 0.0 && t11 > 0.0 && t22 > 0.0 && g22 - g22 == 0.0;   // (the last: a non-finite entry)
+}
+// x = G^-1 b (forward substitution)
+SGO_RULE_HD inline void jgrow_solve3(const double* G6, double b0, double b1, double b2, double* x) {
+  x[0] = b0 / G6[0];
+  x[1] = (b1 - G6[1] * x[0]) / G6[2];
+  x[2] = (b2 - G6[3] * x[0] - G6[4] * x[1]) / G6[5];
+}
+// The extension value v_c = d2 + q_c^T C_c^-1 q_c; NaN where C_c is not positive definite.
+SGO_RULE_HD inline double jgrow_value(double d2, const double* C6, const double* q) {
+  double G6[6], x[3];
+  if (!jgrow_chol3(C6, G6)) return sqrt(-1.0);
+  jgrow_solve3(G6, q[0], q[1], q[2], x);
+  return d2 + ((x[0] * x[0] + x[1] * x[1]) + x[2] * x[2]);
+}
+// The update of candidate c by the pivot p whose factor is G6 and whose z+ = G^-1 q_p is zp.  Sp: S's block (rows of p, columns of
+// c), element (a, b) at Sp[a ld + b].  Wp, Wc: the m rows so far of W_p and W_c, row r's three entries at Wp[r wps], Wc[r wcs].
+// R = S_pc - W_p^T W_c (every sum in ascending row order), w = G^-1 R, C_c -= w^T w, q_c -= w^T z+; w becomes rows m .. m + 2 of W_c.
+constexpr int kJgrowRows = 6;   // (m is a multiple of 3: the tail is none or three rows)
+SGO_RULE_HD inline void jgrow_update(const double* G6, const double* zp, const double* Sp, std::size_t ld, const double* Wp, std::size_t wps,
+                                     double* Wc, std::size_t wcs, int m, double* C6, double* q) {
+  double R[3][3];
+  for (int a = 0; a < 3; ++a)
+    for (int b = 0; b < 3; ++b) R[a][b] = Sp[a * ld + b];
+  // (full batches of kJgrowRows rows of W_c are read before the first is used, so that their loads are in flight together; the
+  // subtractions keep their ascending row order)
+  int r = 0;
+  for (; r + kJgrowRows <= m; r += kJgrowRows) {
+    double wc[kJgrowRows][3];
+    for (int u = 0; u < kJgrowRows; ++u) {
+      const double* src = Wc + (std::size_t)(r + u) * wcs;
+      wc[u][0] = src[0], wc[u][1] = src[1], wc[u][2] = src[2];
+    }
+    for (int u = 0; u < kJgrowRows; ++u) {
+      const double* wp = Wp + (std::size_t)(r + u) * wps;
+      for (int a = 0; a < 3; ++a) {
+        R[a][0] -= wp[a] * wc[u][0];
+        R[a][1] -= wp[a] * wc[u][1];
+        R[a][2] -= wp[a] * wc[u][2];
+      }
+    }
+  }
+  for (; r < m; ++r) {
+    const double* wp = Wp + (std::size_t)r * wps;
+    const double* wc = Wc + (std::size_t)r * wcs;
+    const double c0 = wc[0], c1 = wc[1], c2 = wc[2];
+    for (int a = 0; a < 3; ++a) {
+      R[a][0] -= wp[a] * c0;
+      R[a][1] -= wp[a] * c1;
+      R[a][2] -= wp[a] * c2;
+    }
+  }
+  double w[3][3];   // w[a][b]: row a of the pivot's block, column b of the candidate
+  for (int b = 0; b < 3; ++b) {
+    double x[3];
+    jgrow_solve3(G6, R[0][b], R[1][b], R[2][b], x);
+    w[0][b] = x[0], w[1][b] = x[1], w[2][b] = x[2];
+  }
+  C6[0] -= (w[0][0] * w[0][0] + w[1][0] * w[1][0]) + w[2][0] * w[2][0];
+  C6[1] -= (w[0][1] * w[0][0] + w[1][1] * w[1][0]) + w[2][1] * w[2][0];
+  C6[2] -= (w[0][1] * w[0][1] + w[1][1] * w[1][1]) + w[2][1] * w[2][1];
+  C6[3] -= (w[0][2] * w[0][0] + w[1][2] * w[1][0]) + w[2][2] * w[2][0];
+  C6[4] -= (w[0][2] * w[0][1] + w[1][2] * w[1][1]) + w[2][2] * w[2][1];
+  C6[5] -= (w[0][2] * w[0][2] + w[1][2] * w[1][2]) + w[2][2] * w[2][2];
+  for (int b = 0; b < 3; ++b) q[b] -= (w[0][b] * zp[0] + w[1][b] * zp[1]) + w[2][b] * zp[2];
+  for (int a = 0; a < 3; ++a) {
+    double* o = Wc + (std::size_t)(m + a) * wcs;
+    o[0] = w[a][0], o[1] = w[a][1], o[2] = w[a][2];
+  }
+}
+// The greedy rule's order on (v, c): the smaller v, ties to the lower c.  NaN never reaches it (an ineligible candidate is left out).
+SGO_RULE_HD inline bool jgrow_better(double v, int c, double vbest, int cbest) { return v < vbest || (v == vbest && c < cbest); }
+
 // The mask rule of sgo_optimize_gn_hypotheses, which is sgo_set_edge_information's: a hypothesis may not leave a free pose without any
 // incident edge of non-zero information.  live_deg[V] holds every vertex' count of such edges in the resident graph, dead(e) says
 // whether edge e carries an all-zero information already, off[E] is the hypothesis' mask.  Returns the lowest free vertex that an
