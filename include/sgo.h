@@ -765,7 +765,15 @@ double sgo_debug_spmv0_us(sgo_ctx* ctx, int mode, int variant, int reps);
  * SGO_AMG_INFO: SGO_AMG_INFO_COUNT doubles { n, nslot, nc, smoothed, filtered, folded, cycle form (0 unfolded, 1 folded,
  * 2 folded in two sweeps), sweeps per side, omega, omega_p, entries of P, of A P, products of P's values, of A P, of
  * P^T A P, levels, level-0 passes read fp32, N, Np of the coarsest inverse, long columns of P, of P~, K-cycle depth,
- * theta_filter, slots of the next level }.
+ * theta_filter, slots of the next level, fcg2_depth (levels <= it take two flexible-CG steps under the K-cycle) }.
+ * SGO_AMG_W_*: the cycle's work vectors [n][3] as the last sgo_precondition left them -- XS, RS, TR (smoother state and its two
+ * residual buffers; every level), and on the levels >= 1 BK, XK, Z1, Q, BK2, Z2, P2, Q2 (the flexible-CG steps of fcg(), sgo_amg.hip),
+ * the partial-sum buffers PA = (z1.q | z1.bk), PB = (p2.q2 | p2.bk2), PC = (q.z2 | unused) as [2][2048] doubles, and GRIDS: three
+ * int32 { gA, gB, gC }, how many entries of each half their consumers reduce (0: that step did not run on this level; entries
+ * beyond are never read).  A level >= 2 is visited more than once per cycle: the arrays are those of its LAST visit, which is
+ * self-consistent -- every level's last visit lies inside its parent's last visit, so the exported residual of level l (RS, or TR
+ * after two pre-smoothing sweeps) is what BK of level l + 1 was restricted from, and the exported Z1 / P2 (or XK) of level l + 1
+ * are what level l's last post-smoothing launch prolongated.
  * Returns the array's size in bytes (copied when cap_bytes suffices), 0 when the level has no such array, < 0 on error.
  * Requires sgo_linearize; refuses the row-owner mode and an active overlay, as sgo_debug_coarse_rhs does. */
 #define SGO_AMG_INFO 0
@@ -804,7 +812,22 @@ double sgo_debug_spmv0_us(sgo_ctx* ctx, int mode, int variant, int reps);
 #define SGO_AMG_PS_STPOS 33
 #define SGO_AMG_INV 34
 #define SGO_AMG_ROW_ORDER 35
-#define SGO_AMG_INFO_COUNT 24
+#define SGO_AMG_W_XS 36
+#define SGO_AMG_W_RS 37
+#define SGO_AMG_W_TR 38
+#define SGO_AMG_W_BK 39
+#define SGO_AMG_W_XK 40
+#define SGO_AMG_W_Z1 41
+#define SGO_AMG_W_Q 42
+#define SGO_AMG_W_BK2 43
+#define SGO_AMG_W_Z2 44
+#define SGO_AMG_W_P2 45
+#define SGO_AMG_W_Q2 46
+#define SGO_AMG_W_PA 47
+#define SGO_AMG_W_PB 48
+#define SGO_AMG_W_PC 49
+#define SGO_AMG_W_GRIDS 50
+#define SGO_AMG_INFO_COUNT 25
 int64_t sgo_debug_amg_array(sgo_ctx* ctx, int32_t level, int32_t what, void* out, int64_t cap_bytes);
 /* Test hooks for the incremental overlay (sgo_update_graph_se2; tests/overlay_reference.py names every array's type and shape).
  * All three return SGO_EINVAL when no overlay is resident and in a multi-GPU context; the single-step entry points above keep

@@ -1530,6 +1530,7 @@ struct AmgLevel {
   double *bk = nullptr, *xk = nullptr, *z1 = nullptr, *z2 = nullptr, *q = nullptr;  // K-cycle FCG (levels >= 1)
   double *bk2 = nullptr, *p2 = nullptr, *q2 = nullptr;     // residual after the first FCG step; second direction; A p2
   double *pA = nullptr, *pB = nullptr, *pC = nullptr;      // [2][kMaxPartials] each
+  int gA = 0, gB = 0, gC = 0;   // partial sums the last fcg() left in pA / pB / pC (fixed by the level's size; read by the test hook only)
 };
 
 // Level 0 of a multi-GPU run (the coarser levels are replicated on every rank), as one value:
@@ -1962,6 +1963,8 @@ CoarseSol fcg(Amg* m, hipStream_t s, int l, const PcgScalars* S) {
     Scope sc(m->prof, K_SPMV_AX, bytes_spmv(L.A));
     gA = launch_spmv_ex(s, L.A, SPMV_AX, a);
   }
+  L.gA = gA;
+  L.gB = L.gC = 0;  // the second step has not run (the export's "0: that step did not run")
   CoarseSol cs;
   cs.u1 = L.z1;
   cs.c1 = SpmvRatio{L.pA + kMaxPartials, gA, L.pA, gA};
@@ -1976,6 +1979,8 @@ CoarseSol fcg(Amg* m, hipStream_t s, int l, const PcgScalars* S) {
     Scope sc(m->prof, K_SPMV_AX_C, 80.0 * L.A.nslot + 120.0 * L.A.n);
     gB = launch_spmv_ex(s, L.A, SPMV_AX_C, a);
   }
+  L.gB = gB;
+  L.gC = gC;
   cs.u2 = L.p2;
   cs.c2 = SpmvRatio{L.pB + kMaxPartials, gB, L.pB, gB};
   return cs;
@@ -2146,7 +2151,7 @@ long long amg_debug_array(Amg* m, hipStream_t s, int level, int what, void* out,
                                             sm ? (double)P.np : 0.0, sm ? (double)P.nap : 0.0, sm ? (double)P.val.n : 0.0,
                                             sm ? (double)P.ap.n : 0.0, sm ? (double)P.rap.n : 0.0, (double)(last + 1), f32 ? 1.0 : 0.0,
                                             (double)m->N, (double)m->Np, sm ? (double)P.t_nlong : 0.0, fo ? (double)PS.t_nlong : 0.0,
-                                            (double)m->kdepth, m->cfg.theta_filter, (double)nsc};
+                                            (double)m->kdepth, m->cfg.theta_filter, (double)nsc, (double)m->fcg2_depth};
       if (cap_bytes >= (long long)sizeof v) std::memcpy(out, v, sizeof v);
       return (long long)sizeof v;
     }
@@ -2196,6 +2201,27 @@ long long amg_debug_array(Amg* m, hipStream_t s, int level, int what, void* out,
     case SGO_AMG_PS_TCOL: arr(fo, PS.t_col, (size_t)PS.np, I); break;
     case SGO_AMG_PS_STPOS: arr(fo, L.F.st_pos, (size_t)PS.np, I); break;
     case SGO_AMG_INV: arr(level == last, m->inv, (size_t)m->Np * m->Np, Dd); break;
+    // the cycle's work vectors as the last amg_apply left them (a level >= 2 is visited several times per cycle: its LAST visit)
+    case SGO_AMG_W_XS: arr(true, L.xs, 3 * n, Dd); break;
+    case SGO_AMG_W_RS: arr(true, L.rs, 3 * n, Dd); break;
+    case SGO_AMG_W_TR: arr(true, L.tR, 3 * n, Dd); break;
+    case SGO_AMG_W_BK: arr(level > 0, L.bk, 3 * n, Dd); break;
+    case SGO_AMG_W_XK: arr(level > 0, L.xk, 3 * n, Dd); break;
+    case SGO_AMG_W_Z1: arr(level > 0, L.z1, 3 * n, Dd); break;
+    case SGO_AMG_W_Q: arr(level > 0, L.q, 3 * n, Dd); break;
+    case SGO_AMG_W_BK2: arr(level > 0, L.bk2, 3 * n, Dd); break;
+    case SGO_AMG_W_Z2: arr(level > 0, L.z2, 3 * n, Dd); break;
+    case SGO_AMG_W_P2: arr(level > 0, L.p2, 3 * n, Dd); break;
+    case SGO_AMG_W_Q2: arr(level > 0, L.q2, 3 * n, Dd); break;
+    case SGO_AMG_W_PA: arr(level > 0, L.pA, 2 * (size_t)kMaxPartials, Dd); break;
+    case SGO_AMG_W_PB: arr(level > 0, L.pB, 2 * (size_t)kMaxPartials, Dd); break;
+    case SGO_AMG_W_PC: arr(level > 0, L.pC, 2 * (size_t)kMaxPartials, Dd); break;
+    case SGO_AMG_W_GRIDS: {
+      if (level == 0) return 0;
+      const int g[3] = {L.gA, L.gB, L.gC};
+      if (cap_bytes >= (long long)sizeof g) std::memcpy(out, g, sizeof g);
+      return (long long)sizeof g;
+    }
     default: return SGO_EINVAL;
   }
   if (!src || bytes == 0) return 0;

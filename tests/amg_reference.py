@@ -51,11 +51,46 @@ symmetric block are stated once, in sgo_device.h under "the arithmetic of the mu
                                             nu x [x += w Dinv (r - A x)];
               folded:               z = x1 + w Dinv (r - A x1) + P~ cycle(P~^T r), x1 = w Dinv r;
               folded in two sweeps: x1 = w Dinv r; t = x1 + folded(r - A x1); z = t + w Dinv (r - A t);
-              coarsest level: the exported inverse.  V-cycle hierarchies only: a tentative level runs the K-cycle's flexible CG,
-              a driver and not a formula -- stage 9 raises NotImplementedError there.
+              coarsest level: the exported inverse.  A tentative transfer restricts with sum_{i in a} T(d_i)^T res_i and
+              prolongates with x_i += T(d_i) w[agg(i)], on the exported fp64 lever arms.
+              The driver is coarse_solve()'s, read from the exported flags: the last level is the dense inverse; a smoothed level
+              l > kdepth is walked by the V-cycle; every other level (a tentative one always) by fcg(), Notay's flexible CG:
+                z1 = cycle(bk), q = A z1, a1 = (z1.bk)/(z1.q);  one step, x = a1 z1, where l > fcg2_depth;  otherwise
+                bk2 = bk - a1 q, z2 = cycle'(bk2), b = (q.z2)/(z1.q), p2 = z2 - b z1, q2 = A p2, a2 = (p2.bk2)/(p2.q2), x = a1 z1 + a2 p2;
+              a coefficient whose denominator is not positive, or not finite, is 0 (cycle_ratio).  The form of each inner cycle
+              follows cycle_form by call site: cycle' (it carries the right-hand-side update and a dot request) is unfolded with
+              nu sweeps per side, the first cycle of a folded level stays folded.
               There is no entry-wise bound through a composition with an inverse: per case the measure is
-              |z_gpu - z_ref|_2 / |z_ref|_2 against K_CYCLE * eps_case, eps_case the same norm between this reference in plain fp64
-              and in long double (the rounding scale of the hierarchy, from the reference alone).
+              |z_gpu - z_ref|_2 / |z_ref|_2 against K_CYCLE * eps_case (K_KCYCLE where a level runs fcg(): the K-cycle is
+              nonlinear in r), eps_case the same norm between this reference in plain fp64 and in long double (the rounding
+              scale of the hierarchy, from the reference alone).
+10 kcycle     per-step checks on the work vectors sgo_debug_amg_array exports (SGO_AMG_W_*) as the last sgo_precondition left
+              them: every level's LAST visit (a level >= 2 is visited several times per cycle; every level's last visit lies
+              inside its parent's last visit, so the chain below is self-consistent).  Each step takes the DEVICE's exported
+              inputs: |got - ref| <= C U abs entry-wise, abs the same expression on magnitudes.
+              restrict   bk_{l+1} against the residual the level's last cycle restricted (which buffer: _last_visit), tentative:
+                         abs = sum |T|^T |res|; smoothed / folded: through the exported fp32 copies t_blk / ps_t as stored.
+              product    q = A z1, q2 = A p2.
+              dots       the long-double sum of the exported partial sums [0, g) against the long-double dot product:
+                         |delta| <= C_DOT U sum |a_i b_i| for pA = (z1.q | z1.bk), pC = (q.z2), pB = (p2.q2 | p2.bk2); entries
+                         beyond the exported grid counts are not read; a step that ran has g > 0, one that did not has g = 0.
+              bk2, p2    bk2 = bk - a1 q, p2 = z2 - b z1 with a1, b recomputed from the exported partial sums in fp64 IN THE
+                         KERNEL'S ORDER (block_reduce_parts_n: thread t of 256 adds entries t, t + 256, ... serially from 0.0;
+                         wave_sum is a balanced tree over adjacent lanes; thread 0 adds the four waves' sums in order): reduce_parts.
+                         That order is k_spmv's (ratios2), which makes bk2 and p2: there the coefficient is reproduced bit for bit.
+                         k_prolong_fold (level 0's folded last launch) reduces the same partial sums in a loop of its own over
+                         kFoldThreads = 1024 threads and 16 waves; the reference does not restate that order, so in that launch
+                         the coefficients agree to a few ulps only, which C_K['last'] holds with the launch's own rounding.
+              last       the level's last launch(es), out = x' + w Dinv (rhs - A x'), x' = xs + T (c1 u1 + c2 u2), abs = |x'| +
+                         w |Dinv| (|rhs| + |A| |x'|); out is the parent's z1 / z2 / xk, on level 0 the returned z.  Which buffer
+                         holds what: a tentative level >= 1 below kUnfuseSlots slots fuses the prolongation into the sweep
+                         (SPMV_JACOBI_P) and leaves xs as the pre-smoothing left it; everywhere else (level 0, k_prolong_p,
+                         k_prolong_add on a large level) the prolongation updates xs IN PLACE, the exported xs is x' itself and
+                         is checked against the pre-smoothing sweeps recomputed from rhs; with nu = 2 the first post-smoothing
+                         sweep lands in rs (the restricted residual is then tR's).  Folded forms: out = M2 rhs + P~ w (k_up_fold),
+                         on level 0 z = rs + P~ w with rs = M2 r (k_prolong_fold).
+              coarsest   xk = inv bk entry-wise, abs = |inv| |bk|.
+              rules      r = 0 leaves every exported vector and z exactly zero; a denominator <= 0 gives the coefficient 0.
 
 Constants.  Each C is a small multiple of the worst error / (U abs) measured on the MI355X over the cases of
 tests/test_gpu_amg_reference.py (recorded there per case class), at least 2 x and at most 8 x of it; the CPU mutation tests
@@ -89,13 +124,40 @@ F32_TINY = 2.0 ** -126     # smallest normal fp32: below it a conversion from fp
 # forward-built CPU hierarchy with such closures (blocks of kappa ~ 1e8) measures 2.25 of the same bound: 4 holds both.
 MEASURED = dict(geometry=3.34, filtered=1.85, inverse=1.39, transfer=4.37, galerkin=5.72, folded=0.447, cycle=1.72)
 C_STAGE = dict(geometry=8.0, filtered=6.0, inverse=4.0, transfer=16.0, galerkin=16.0, folded=2.0)   # 2.4, 3.2, 2.9, 3.7, 2.8, 4.5 x measured
+# Stage 10 and the K-cycle's end-to-end figure, measured on the MI355X (tests/test_gpu_kcycle_reference.py, the three tentative cases
+# of tests/test_gpu_amg_reference.py and amg_c2_kcycle of tests/test_gpu_pcg_reference.py), worst error / (U abs) per step and case class:
+#   class      restrict  product  dots   bk2    p2     last   coarsest  cycle / eps_case
+#   tentative  2.72      2.80     0.58   1.00   0.99   3.31   1.92      6.25    (SGO_AMG_SMOOTH=0: C2, 20k random closures, the same with
+#                                                                               fcg2_depth 0 and 9, C4r with its 627-member aggregate)
+#   smoothed   3.01      2.51     0.64   1.00   1.00   4.92   0.68      20.27   (SGO_AMG_KDEPTH = 2, 1 on C2 and on 30k / 300k, and with
+#                                                                               two steps on level 2; amg_c2_kcycle over its caps: 7.35)
+#   mixed      3.33      2.79     0.44   1.00   0.99   3.79   0.98      4.07    (defaults: 20k random closures, hubs, C4r)
+# (every case with the full vector set: two random vectors, rows scaled by 10^+-6, a single non-zero row.)
+# bk2, p2: one fused multiply-add per entry with the coefficient reproduced bit for bit (reduce_parts): half an ulp of the result, 1 in
+# these units only where the two terms cancel; the fp64 forward model of the CPU tests, which rounds twice, measures 1.6.  cycle: the
+# V-cycle measures 1.72; the K-cycle's coefficients are ratios of dot products, so z is not linear in r and one fp64 evaluation lies
+# further from another than a V-cycle's does -- the CPU forward model, fp64 with other summation orders and no kernel in it, lies
+# 4.9 eps_case from the long-double reference on the 600-pose mixed hierarchy.  eps_case is ONE fp64 evaluation's distance from the
+# reference, a sample of the rounding scale and not a bound on it: over the four vectors of 30k / 300k under SGO_AMG_KDEPTH=1 it is
+# 2.7e-7, 1.5e-7, 6.1e-9 and 1.2e-7.  20.27 is that case's vector with rows scaled by 10^+-6, the one whose sample came out at 6.1e-9:
+# the device's error there is 1.2e-7, inside the spread of the same case's other samples, and every step of that run is within
+# 4.87 U abs, so the figure is the measure's, not a step's.  The same holds for C2's scaled vector under SGO_AMG_KDEPTH=2 (9.31,
+# eps_case 1.3e-10 against 5e-10 to 9e-10 on its other vectors, every step within 4.85 U abs).
+MEASURED_K = dict(restrict=3.33, product=2.80, dots=0.644, bk2=0.996, p2=0.996, last=4.92, coarsest=1.92, cycle=20.27)
+C_K = dict(restrict=8.0, product=8.0, dots=2.0, bk2=2.5, p2=2.5, last=12.0, coarsest=4.0, grids=1.0)   # 2.4, 2.9, 3.1, 2.5, 2.5, 2.4, 2.1 x measured
+C_DOT = C_K["dots"]
+K_KCYCLE = 48.0                                                                                     # 2.4 x measured
 K_CYCLE = 8.0                                                                                       # 4.6 x measured
 
 NAMES = ("INFO A_ROWPTR A_COL A_BLK A_BLK_F32 A_DINV POS D AGG MEM_PTR MEM P_ROWPTR P_ROW P_COL P_BLK P_RBLK P_TBLK P_TPOS P_TROW "
-         "P_TCOL STRONG DF DINVF AP_A AP_B AP_TGT AP_BLK PS_ROW PS_COL PS_RBLK PS_TBLK PS_TROW PS_TCOL PS_STPOS INV ROW_ORDER").split()
+         "P_TCOL STRONG DF DINVF AP_A AP_B AP_TGT AP_BLK PS_ROW PS_COL PS_RBLK PS_TBLK PS_TROW PS_TCOL PS_STPOS INV ROW_ORDER "
+         "W_XS W_RS W_TR W_BK W_XK W_Z1 W_Q W_BK2 W_Z2 W_P2 W_Q2 W_PA W_PB W_PC W_GRIDS").split()
 WHAT = {k: i for i, k in enumerate(NAMES)}           # SGO_AMG_* of include/sgo.h
 INFO = ("n nslot nc smoothed filtered folded kind nu omega omega_p np nap nval n_ap_prod n_rap_prod levels f32 N Np t_nlong "
-        "ps_t_nlong kdepth theta_filter nslot_c").split()
+        "ps_t_nlong kdepth theta_filter nslot_c fcg2_depth").split()
+WORK = ("xs rs tR bk xk z1 q bk2 z2 p2 q2").split()           # SGO_AMG_W_* vectors [n][3]; pA pB pC [2][MAX_PARTS]; grids (gA, gB, gC)
+MAX_PARTS = 2048                                              # kMaxPartials
+UNFUSE_SLOTS = 400000                                         # kUnfuseSlots (sgo_amg.hip)
 UNFOLDED, FOLDED, FOLDED2 = 0, 1, 2
 
 
@@ -593,14 +655,59 @@ def _rowsum(rows, vals, n):
     return out
 
 
-class Cycle:
-    """z = M r from the exported levels in `dtype` arithmetic (np.longdouble: the reference; np.float64: the rounding scale)."""
+def cycle_coefficient(num, den):
+    """cycle_ratio's rule (sgo_device.h): num / den, 0 where the denominator is not positive or either is not finite."""
+    return num / den if (den > 0 and np.isfinite(den) and np.isfinite(num)) else 0.0
 
-    def __init__(self, levels, dtype=LD, skip_post=False):
+
+def reduce_parts(p, g):
+    """The fp64 sum of p[0 .. g) in block_reduce_parts_n's order: thread t of 256 adds the entries t, t + 256, ... serially from 0.0,
+    wave_sum adds adjacent lanes as a balanced tree, thread 0 adds the four waves' sums in order.  Entries beyond g are not read."""
+    v = np.zeros(MAX_PARTS)
+    v[:g] = np.asarray(p, dtype=np.float64)[:g]
+    s = np.zeros(256)
+    for k in range(MAX_PARTS // 256):
+        s = s + v[256 * k:256 * (k + 1)]
+    w = s.reshape(4, 64)
+    while w.shape[1] > 1:
+        w = w[:, 0::2] + w[:, 1::2]
+    return float(((w[0, 0] + w[1, 0]) + w[2, 0]) + w[3, 0])
+
+
+def solve_kind(levels, l):
+    """How coarse_solve() solves for level l >= 1's right-hand side: "dense" | "V" | "fcg1" | "fcg2", from the exported flags."""
+    kdepth, fcg2 = levels[0].get("kdepth", 0), levels[0].get("fcg2_depth", 1)
+    if l == len(levels) - 1:
+        return "dense"
+    if l > kdepth and levels[l]["smoothed"]:
+        return "V"
+    return "fcg1" if l > fcg2 else "fcg2"
+
+
+def has_kcycle(levels):
+    return any(solve_kind(levels, l).startswith("fcg") for l in range(1, len(levels)))
+
+
+def model_grid(n):
+    """How many partial sums the forward model leaves for a level of n rows (the device: its k_spmv grid)."""
+    return max(1, min(MAX_PARTS, (n + 15) // 16))
+
+
+class Cycle:
+    """z = M r from the exported levels in `dtype` arithmetic (np.longdouble: the reference; np.float64: the rounding scale).
+    record: keep every level's work vectors as the device's buffers hold them after the cycle (self.W: the forward model of the
+    SGO_AMG_W_* export; coefficients then come from partial sums reduced in the kernel's order).  inner(l, rhs): a stand-in for
+    the inner cycles of fcg().  (The CPU mutation tests subclass it with mistakes built in: tests/test_amg_reference.py.)"""
+
+    def __init__(self, levels, dtype=LD, skip_post=False, record=False, inner=None):
         self.lv, self.dt, self.skip_post = levels, dtype, skip_post
-        for l, L in enumerate(levels[:-1]):
-            if not L["smoothed"]:
-                raise NotImplementedError(f"level {l} keeps the tentative transfer: the K-cycle is outside stage 9")
+        self.inner = inner
+        self.trace = {}
+        self.W = None
+        if record:
+            self.W = [{k: np.zeros((L["n"], 3)) for k in (WORK if l else WORK[:3])} for l, L in enumerate(levels)]
+            for l, w in enumerate(self.W[1:], 1):
+                w.update(pA=np.zeros((2, MAX_PARTS)), pB=np.zeros((2, MAX_PARTS)), pC=np.zeros((2, MAX_PARTS)), grids=np.zeros(3, dtype=np.int32))
         self.c = []
         for l, L in enumerate(levels):
             c = dict(row=slot_rows(L), col=L["col"].astype(np.int64), dinv=sym6(L["dinv"], dtype))
@@ -617,45 +724,125 @@ class Cycle:
 
     def restrict(self, l, res, folded):
         L = self.lv[l]
+        if not L["smoothed"]:
+            return _rowsum(L["agg"].astype(np.int64), np.einsum("kji,kj->ki", T_of(L["d"], self.dt), res), L["nc"])
         t, trow, tcol = (L["ps_t"], L["ps_trow"], L["ps_tcol"]) if folded else (L["t_blk"], L["t_row"], L["t_col"])
         B = t.reshape(-1, 3, 3).astype(self.dt)
         return _rowsum(tcol.astype(np.int64), np.einsum("kji,kj->ki", B, res[trow]), L["nc"])
 
     def prolong(self, l, xc, folded):
         L = self.lv[l]
+        if not L["smoothed"]:
+            return np.einsum("kij,kj->ki", T_of(L["d"], self.dt), xc[L["agg"]])
         r, row, col = (L["ps_r"], L["ap_row"], L["ap_col"]) if folded else (L["r_blk"], L["p_row"], L["p_col"])
         B = r.reshape(-1, 3, 3).astype(self.dt)
         return _rowsum(np.asarray(row, dtype=np.int64), np.einsum("kij,kj->ki", B, xc[col]), L["n"])
 
-    def folded(self, l, r):
-        x1 = self.jac(l, r)
-        m2 = x1 + self.jac(l, r - self.A(l, x1))
-        return m2 + self.prolong(l, self(l + 1, self.restrict(l, r, True)), True)
+    def _rec(self, l, **kw):
+        if self.W is not None:
+            for k, v in kw.items():
+                self.W[l][k] = np.array(v, dtype=np.float64)
 
-    def __call__(self, l, r):
+    def dot(self, l, a, b, buf, half):
+        """a . b; recording: per-chunk partial sums left in W[l][buf][half] and reduced in the kernel's order."""
+        if self.W is None:
+            return (a * b).sum()
+        g = model_grid(self.lv[l]["n"])
+        p = np.array([c.sum() for c in np.array_split((a * b).sum(axis=1), g)], dtype=np.float64)
+        self.W[l][buf][half, :] = 0.0
+        self.W[l][buf][half, :g] = p
+        return reduce_parts(p, g)
+
+    def fcg(self, l, bk):
+        """fcg() of sgo_amg.hip for A x = bk on level l; the steps' vectors are kept in self.trace[l] (in self.dt)."""
+        fcg2 = self.lv[0].get("fcg2_depth", 1)
+        two = l <= fcg2
+        g = model_grid(self.lv[l]["n"])
+        z1 = self.inner(l, bk) if self.inner else self.cycle(l, bk)
+        q = self.A(l, z1)
+        zq, zb = self.dot(l, z1, q, "pA", 0), self.dot(l, z1, bk, "pA", 1)
+        a1 = cycle_coefficient(zb, zq)
+        self._rec(l, z1=z1, q=q)
+        if self.W is not None:
+            self.W[l]["grids"][:] = (g, 0, 0)
+        self.trace[l] = dict(bk=bk, z1=z1, q=q, a1=a1, x=a1 * z1)
+        if not two:
+            return a1 * z1
+        bk2 = bk - a1 * q
+        self._rec(l, bk2=bk2)
+        z2 = self.inner(l, bk2) if self.inner else self.cycle(l, bk2, unfolded=True)
+        b = cycle_coefficient(self.dot(l, q, z2, "pC", 0), zq)
+        p2 = z2 - b * z1
+        q2 = self.A(l, p2)
+        a2 = cycle_coefficient(self.dot(l, p2, bk2, "pB", 1), self.dot(l, p2, q2, "pB", 0))
+        self._rec(l, z2=z2, p2=p2, q2=q2)
+        if self.W is not None:
+            self.W[l]["grids"][:] = (g, g, g)
+        x = a1 * z1 + a2 * p2
+        self.trace[l].update(bk2=bk2, z2=z2, b=b, p2=p2, q2=q2, a2=a2, x=x)
+        return x
+
+    def coarse_solve(self, l, bk):
+        """coarse_solve() of sgo_amg.hip: the solution for level l + 1's right-hand side as level l prolongates it."""
+        C = l + 1
+        self._rec(C, bk=bk)
+        kind = solve_kind(self.lv, C)
+        if kind.startswith("fcg"):
+            return self.fcg(C, bk)
+        if kind == "dense":
+            N = 3 * self.lv[C]["n"]
+            xk = (self.lv[C]["inv"][:N, :N].astype(self.dt) @ bk.reshape(N)).reshape(-1, 3)
+        else:
+            xk = self.cycle(C, bk)
+        self._rec(C, xk=xk)
+        return xk
+
+    def cycle(self, l, rhs, unfolded=False):
+        """cycle0 / cycle_coarse: one cycle of level l for rhs, in the level's exported form or unfolded (cycle_form with an
+        RhsSub or a dot request), leaving the work vectors where the device's launches leave them."""
         L = self.lv[l]
-        r = np.asarray(r, dtype=self.dt)
-        if l == len(self.lv) - 1:
-            N = 3 * L["n"]
-            return (L["inv"][:N, :N].astype(self.dt) @ r.reshape(N)).reshape(-1, 3)
-        kind, nu = L["kind"], L["nu"]
+        kind, nu = (UNFOLDED if unfolded else L["kind"]), L["nu"]
         if kind == FOLDED:
-            return self.folded(l, r)
+            cs = self.coarse_solve(l, self.restrict(l, rhs, True))
+            x1 = self.jac(l, rhs)
+            m2 = x1 + self.jac(l, rhs - self.A(l, x1))
+            if l == 0:
+                self._rec(0, xs=x1, rs=m2)
+            return m2 + self.prolong(l, cs, True)
         if kind == FOLDED2:
-            x1 = self.jac(l, r)
-            t = x1 + self.folded(l, r - self.A(l, x1))
-            return t + self.jac(l, r - self.A(l, t))
-        x = np.zeros_like(r)
-        res = r
-        for _ in range(nu):
+            xs = self.jac(l, rhs)
+            rs = rhs - self.A(l, xs)
+            cs = self.coarse_solve(l, self.restrict(l, rs, True))
+            x1 = self.jac(l, rs)
+            tR = xs + (x1 + self.jac(l, rs - self.A(l, x1)) + self.prolong(l, cs, True))
+            self._rec(l, xs=xs, rs=rs, tR=tR)
+            return tR + self.jac(l, rhs - self.A(l, tR))
+        x = np.zeros_like(rhs)
+        res = rhs
+        for sw in range(nu):
             dx = self.jac(l, res)
             x = x + dx
             res = res - self.A(l, dx)
-        x = x + self.prolong(l, self(l + 1, self.restrict(l, res, False)), False)
+            self._rec(l, **{"tR" if sw % 2 else "rs": res})
+        cs = self.coarse_solve(l, self.restrict(l, res, False))
+        xp = x + self.prolong(l, cs, False)
+        # the fused launch (SPMV_JACOBI_P) leaves xs as the pre-smoothing made it; every other path prolongates in place
+        self._rec(l, xs=x if (not L["smoothed"] and l >= 1 and L["nslot"] < UNFUSE_SLOTS) else xp)
         if not self.skip_post:
-            for _ in range(nu):
-                x = x + self.jac(l, r - self.A(l, x))
-        return x
+            src = "xs"
+            for sw in range(nu):
+                xp = xp + self.jac(l, rhs - self.A(l, xp))
+                if sw < nu - 1:
+                    src = "tR" if src == "rs" else "rs"
+                    self._rec(l, **{src: xp})
+        return xp
+
+    def __call__(self, l, r):
+        r = np.asarray(r, dtype=self.dt)
+        if l == len(self.lv) - 1:
+            N = 3 * self.lv[l]["n"]
+            return (self.lv[l]["inv"][:N, :N].astype(self.dt) @ r.reshape(N)).reshape(-1, 3)
+        return self.cycle(l, r)
 
 
 def cycle_scale(levels, r):
@@ -669,6 +856,245 @@ def cycle_scale(levels, r):
 def cycle_ratio(z_got, z_ref, eps):
     d = np.asarray(z_got, dtype=LD) - z_ref
     return float(np.sqrt((d * d).sum()) / np.sqrt((z_ref * z_ref).sum())) / eps
+
+
+# ------------------------------------------------------------------ stage 10: the K-cycle's steps on the exported work vectors
+def export_work(opt, levels):
+    """Per level the SGO_AMG_W_* arrays as the last sgo_precondition left them (keys: WORK, pA pB pC (2, MAX_PARTS), grids)."""
+    out = []
+    for l, L in enumerate(levels):
+        w = {}
+        for k in WORK:
+            a = _fetch(opt, l, "W_" + k.upper(), np.float64)
+            if a is not None:
+                w[k] = a.reshape(L["n"], 3)
+        for k in ("pA", "pB", "pC"):
+            a = _fetch(opt, l, "W_" + k.upper(), np.float64)
+            if a is not None:
+                w[k] = a.reshape(2, MAX_PARTS)
+        g = _fetch(opt, l, "W_GRIDS", np.int32)
+        if g is not None:
+            w["grids"] = g
+        out.append(w)
+    return out
+
+
+class _Ops:
+    """One level's operator and block-Jacobi sweep in long double, each with the same expression on magnitudes."""
+
+    def __init__(self, levels, l):
+        L = levels[l]
+        self.n, self.w = L["n"], L["omega"]
+        self.row, self.col = slot_rows(L), L["col"].astype(np.int64)
+        A = L["blk32"] if (l == 0 and L["f32"] and "blk32" in L) else L["blk"]      # (what the level's passes read: Cycle's rule)
+        self.Ab, self.Aa = np.asarray(A, dtype=LD), np.abs(np.asarray(A, dtype=np.float64))
+        D = sym6(L["dinv"])
+        self.D, self.Da = D.astype(LD), np.abs(D)
+
+    def A(self, x):
+        return _rowsum(self.row, np.einsum("kij,kj->ki", self.Ab, x[self.col]), self.n)
+
+    def Aabs(self, xa):
+        return _rowsum(self.row, np.einsum("kij,kj->ki", self.Aa, xa[self.col]), self.n)
+
+    def jac(self, v):
+        return LD(self.w) * np.einsum("nij,nj->ni", self.D, v)
+
+    def jacabs(self, va):
+        return self.w * np.einsum("nij,nj->ni", self.Da, va)
+
+    def sweep(self, x, xa, rhs):
+        """x + w Dinv (rhs - A x) for an iterate x of magnitudes xa, and its magnitudes."""
+        return x + self.jac(rhs.astype(LD) - self.A(x)), xa + self.jacabs(np.abs(rhs) + self.Aabs(xa))
+
+
+def _ld(a):
+    return np.asarray(a, dtype=LD)
+
+
+def _restrict10(L, res, folded):
+    """(P^T res | P~^T res | sum_{i in a} T(d_i)^T res_i, the same on magnitudes) for the level's transfer as stored."""
+    if not L["smoothed"]:
+        agg = L["agg"].astype(np.int64)
+        return (_rowsum(agg, np.einsum("kji,kj->ki", T_of(L["d"], LD), _ld(res)), L["nc"]),
+                _rowsum(agg, np.einsum("kji,kj->ki", np.abs(T_of(L["d"])), np.abs(res)), L["nc"]))
+    t, trow, tcol = (L["ps_t"], L["ps_trow"], L["ps_tcol"]) if folded else (L["t_blk"], L["t_row"], L["t_col"])
+    B = t.reshape(-1, 3, 3)
+    tcol = tcol.astype(np.int64)
+    return (_rowsum(tcol, np.einsum("kji,kj->ki", B.astype(LD), _ld(res)[trow]), L["nc"]),
+            _rowsum(tcol, np.einsum("kji,kj->ki", np.abs(B).astype(np.float64), np.abs(res)[trow]), L["nc"]))
+
+
+def _prolong10(L, w, wa, folded):
+    if not L["smoothed"]:
+        return np.einsum("kij,kj->ki", T_of(L["d"], LD), w[L["agg"]]), np.einsum("kij,kj->ki", np.abs(T_of(L["d"])), wa[L["agg"]])
+    r, row, col = (L["ps_r"], L["ap_row"], L["ap_col"]) if folded else (L["r_blk"], L["p_row"], L["p_col"])
+    B = r.reshape(-1, 3, 3)
+    row = np.asarray(row, dtype=np.int64)
+    return (_rowsum(row, np.einsum("kij,kj->ki", B.astype(LD), w[col]), L["n"]),
+            _rowsum(row, np.einsum("kij,kj->ki", np.abs(B).astype(np.float64), wa[col]), L["n"]))
+
+
+def exported_coefficients(w):
+    """(a1, b, a2) from a level's exported partial sums and grid counts, in fp64 in the kernels' order (cycle_ratio's rule)."""
+    gA, gB, gC = (int(x) for x in w["grids"])
+    den = reduce_parts(w["pA"][0], gA)
+    return (cycle_coefficient(reduce_parts(w["pA"][1], gA), den), cycle_coefficient(reduce_parts(w["pC"][0], gC), den),
+            cycle_coefficient(reduce_parts(w["pB"][1], gB), reduce_parts(w["pB"][0], gB)))
+
+
+def _coarse_solution(levels, W, C):
+    """c1 u1 + c2 u2 as level C - 1's last launch prolongates it (long double from the exported vectors), and its magnitudes."""
+    kind, w = solve_kind(levels, C), W[C]
+    if kind in ("dense", "V"):
+        return _ld(w["xk"]), np.abs(w["xk"])
+    a1, _, a2 = exported_coefficients(w)
+    ref, ab = LD(a1) * _ld(w["z1"]), abs(a1) * np.abs(w["z1"])
+    if kind == "fcg2":
+        ref, ab = ref + LD(a2) * _ld(w["p2"]), ab + abs(a2) * np.abs(w["p2"])
+    return ref, ab
+
+
+def _dot_ratio(parts, g, a, b):
+    s = _ld(parts[:g]).sum()
+    ref, ab = (_ld(a) * _ld(b)).sum(), float((np.abs(a) * np.abs(b)).sum())
+    err = float(abs(s - ref))
+    if not np.isfinite(err):
+        return float("inf"), None
+    return (err / (U * ab) if ab > 0 else (float("inf") if err > 0 else 0.0)), None
+
+
+def stage10_kcycle(levels, W, r, z):
+    """{(level, check): (error / (U abs), where)} over the steps of every level's last visit; r, z: sgo_precondition's input and
+    result in the internal row order.  Check names begin with the step (restrict, product, dots, bk2, p2, last, coarsest, grids)."""
+    R = {}
+    last = len(levels) - 1
+    for l in range(last):
+        L, w, ops = levels[l], W[l], _Ops(levels, l)
+        sk = solve_kind(levels, l) if l else "top"
+        nu = L["nu"]
+        # ---- the flexible-CG steps of this level
+        if sk.startswith("fcg"):
+            gA, gB, gC = (int(x) for x in w["grids"])
+            R[(l, "grids")] = (0.0 if (0 < gA <= MAX_PARTS and ((0 < gB <= MAX_PARTS and 0 < gC <= MAX_PARTS) if sk == "fcg2" else gB == gC == 0))
+                               else float("inf"), (gA, gB, gC))
+            a1, b, _ = exported_coefficients(w)
+            z1, q, bk = w["z1"], w["q"], w["bk"]
+            R[(l, "product.q")] = entry_ratio(q, ops.A(_ld(z1)), ops.Aabs(np.abs(z1)))
+            R[(l, "dots.z1_q")] = _dot_ratio(w["pA"][0], gA, z1, q)
+            R[(l, "dots.z1_bk")] = _dot_ratio(w["pA"][1], gA, z1, bk)
+            if sk == "fcg2":
+                bk2, z2, p2, q2 = w["bk2"], w["z2"], w["p2"], w["q2"]
+                R[(l, "bk2")] = entry_ratio(bk2, _ld(bk) - LD(a1) * _ld(q), np.abs(bk) + abs(a1) * np.abs(q))
+                R[(l, "dots.q_z2")] = _dot_ratio(w["pC"][0], gC, q, z2)
+                R[(l, "p2")] = entry_ratio(p2, _ld(z2) - LD(b) * _ld(z1), np.abs(z2) + abs(b) * np.abs(z1))
+                R[(l, "product.q2")] = entry_ratio(q2, ops.A(_ld(p2)), ops.Aabs(np.abs(p2)))
+                R[(l, "dots.p2_q2")] = _dot_ratio(w["pB"][0], gB, p2, q2)
+                R[(l, "dots.p2_bk2")] = _dot_ratio(w["pB"][1], gB, p2, bk2)
+        # ---- the level's last cycle: its form, right-hand side and result (_last_visit)
+        if l == 0:
+            kind, rhs, out = L["kind"], r, z
+        elif sk == "fcg2":
+            kind, rhs, out = UNFOLDED, w["bk2"], w["z2"]       # cycle': unfolded whatever the level's own form
+        else:
+            kind, rhs, out = L["kind"], w["bk"], (w["xk"] if sk == "V" else w["z1"])
+        rhs = np.asarray(rhs, dtype=np.float64)
+        rhsa = np.abs(rhs)
+        cw, cwa = _coarse_solution(levels, W, l + 1)
+        bkc = W[l + 1]["bk"]
+        if kind == FOLDED:
+            R[(l, "restrict")] = entry_ratio(bkc, *_restrict10(L, rhs, True))
+            x1, x1a = ops.jac(_ld(rhs)), ops.jacabs(rhsa)
+            m2, m2a = ops.sweep(x1, x1a, rhs)
+            if l == 0:      # (level 0 keeps the two-sweep term: xs = w Dinv r, rs = M2 r)
+                R[(l, "last.first_sweep")] = entry_ratio(w["xs"], x1, x1a)
+                R[(l, "last.sweep")] = entry_ratio(w["rs"], *ops.sweep(_ld(w["xs"]), np.abs(w["xs"]), rhs))
+                m2, m2a = _ld(w["rs"]), np.abs(w["rs"])
+            pw, pwa = _prolong10(L, cw, cwa, True)
+            R[(l, "last.out")] = entry_ratio(out, m2 + pw, m2a + pwa)
+        elif kind == FOLDED2:
+            xs, rs, tR = w["xs"], w["rs"], w["tR"]
+            R[(l, "restrict")] = entry_ratio(bkc, *_restrict10(L, rs, True))
+            R[(l, "last.first_sweep")] = entry_ratio(xs, ops.jac(_ld(rhs)), ops.jacabs(rhsa))
+            R[(l, "last.resid")] = entry_ratio(rs, _ld(rhs) - ops.A(_ld(xs)), rhsa + ops.Aabs(np.abs(xs)))
+            m2, m2a = ops.sweep(ops.jac(_ld(rs)), ops.jacabs(np.abs(rs)), rs)
+            pw, pwa = _prolong10(L, cw, cwa, True)
+            R[(l, "last.fold")] = entry_ratio(tR, _ld(xs) + m2 + pw, np.abs(xs) + m2a + pwa)
+            R[(l, "last.out")] = entry_ratio(out, *ops.sweep(_ld(tR), np.abs(tR), rhs))
+        else:
+            if nu <= 2:     # (nu = 1: rs; nu = 2: tR, rs then holds the first post-smoothing sweep; beyond: overwritten)
+                R[(l, "restrict")] = entry_ratio(bkc, *_restrict10(L, w["rs"] if nu == 1 else w["tR"], False))
+            pw, pwa = _prolong10(L, cw, cwa, False)
+            xs = w["xs"]
+            if not L["smoothed"] and l >= 1 and L["nslot"] < UNFUSE_SLOTS:      # fused: xs is the pre-smoothing's
+                xp, xpa = _ld(xs) + pw, np.abs(xs) + pwa
+            else:           # in place: xs is x' itself, checked against the pre-smoothing recomputed from rhs
+                x, xa, rr, rra = np.zeros((L["n"], 3), dtype=LD), np.zeros((L["n"], 3)), _ld(rhs), rhsa
+                for _ in range(nu):
+                    dx, dxa = ops.jac(rr), ops.jacabs(rra)
+                    x, xa, rr, rra = x + dx, xa + dxa, rr - ops.A(dx), rra + ops.Aabs(dxa)
+                R[(l, "last.prolong")] = entry_ratio(xs, x + pw, xa + pwa)
+                xp, xpa = _ld(xs), np.abs(xs)
+            if nu == 2:
+                R[(l, "last.sweep")] = entry_ratio(w["rs"], *ops.sweep(xp, xpa, rhs))
+                xp, xpa = _ld(w["rs"]), np.abs(w["rs"])
+            elif nu > 2:
+                for _ in range(nu - 1):
+                    xp, xpa = ops.sweep(xp, xpa, rhs)
+            R[(l, "last.out")] = entry_ratio(out, *ops.sweep(xp, xpa, rhs))
+    wl = W[last]
+    N = 3 * levels[last]["n"]
+    inv = levels[last]["inv"][:N, :N]
+    R[(last, "coarsest")] = entry_ratio(wl["xk"].reshape(N), matmul_ld(inv, wl["bk"].reshape(N, 1)).reshape(N),
+                                        np.abs(inv) @ np.abs(wl["bk"].reshape(N)))
+    return R
+
+
+def written_vectors(levels, l):
+    """The work vectors some launch of a cycle writes on level l (the others keep whatever the arena held: nothing reads them)."""
+    L, last = levels[l], len(levels) - 1
+    sk = solve_kind(levels, l) if l else "top"
+    if l == last:
+        return {"bk", "xk"} if l else set()
+    forms = {"top": [L["kind"]], "V": [L["kind"]], "fcg1": [L["kind"]], "fcg2": [L["kind"], UNFOLDED]}[sk]
+    out = set() if l == 0 else ({"bk", "xk"} if sk == "V" else ({"bk", "z1", "q"} | ({"bk2", "z2", "p2", "q2"} if sk == "fcg2" else set())))
+    for f in forms:
+        if f == FOLDED2 or (f == UNFOLDED and L["nu"] >= 2):
+            out |= {"xs", "rs", "tR"}
+        elif f == UNFOLDED or l == 0:
+            out |= {"xs", "rs"}
+    return out
+
+
+def kcycle_all_zero(levels, W, z):
+    """The rule case r = 0: every exported work vector the cycle writes, and z, exactly zero (and so finite); the partial sums
+    that were read too."""
+    bad = [(l, k) for l, w in enumerate(W) for k in sorted(written_vectors(levels, l)) if k in w and np.any(w[k] != 0.0)]
+    for l, w in enumerate(W):
+        if "grids" in w:
+            bad += [(l, p) for p, g in zip(("pA", "pB", "pC"), w["grids"]) if np.any(w[p][:, :int(g)] != 0.0)]
+    if np.any(np.asarray(z) != 0.0):
+        bad.append(("z",))
+    return bad
+
+
+def step_of(check):
+    return check.split(".")[0]
+
+
+def check_kcycle(levels, W, r, z):
+    """{(level, check): (ratio / C_K[step], raw ratio, where)}: a value above 1 fails."""
+    return {k: ((v if v in (0.0, float("inf")) else v / C_K[step_of(k[1])]), v, at) for k, (v, at) in stage10_kcycle(levels, W, r, z).items()}
+
+
+def worst_by_step(res):
+    """{step: (worst raw ratio, level, check)} of a check_kcycle result."""
+    w = {}
+    for (l, k), (_, raw, at) in res.items():
+        s = step_of(k)
+        if s not in w or raw > w[s][0]:
+            w[s] = (raw, l, k)
+    return w
 
 
 # ------------------------------------------------------------------ all applicable stages of a hierarchy

@@ -1,13 +1,15 @@
 """The resident multigrid hierarchy and its cycle against tests/amg_reference.py, stage by stage.
 
 Every case linearises, exports the hierarchy through sgo_debug_amg_array (exactly what the next sgo_precondition and the next
-refresh read), runs every applicable stage of the reference and, on V-cycle hierarchies, compares sgo_precondition on three
-vectors -- two random, one with rows scaled by 10^+-6 -- with stage 9.  A case asserts the shape it exists for, read from the
+refresh read), runs every applicable stage of the reference and compares sgo_precondition on three vectors -- two random, one with rows scaled
+by 10^+-6 -- with stage 9; where a level runs the K-cycle's flexible CG (a tentative level always does), also with stage 10 on the
+exported work vectors (test_gpu_kcycle_reference.py has the K-cycle's own cases).  A case asserts the shape it exists for, read from the
 export and sgo_solver_description, and a failing case reports every stage's worst ratio and where it was.  Each case prints its
 figures before it asserts (run with -s to see them).
 
 Measured on the MI355X, worst error / (U abs) per stage over the case classes (constants in amg_reference.C_STAGE / K_CYCLE):
-the table above amg_reference.MEASURED.  The file adds about 70 s of GPU-machine time (C4: 15 s).
+the table above amg_reference.MEASURED.  The file adds about 75 s of GPU-machine time (C4: 15 s;
+C4r with its K-cycle stages: 7 s).
 """
 import json
 
@@ -16,6 +18,7 @@ import pytest
 
 import amg_reference as ar
 from sparse_gslam_amd import capi, synth
+from test_gpu_kcycle_reference import kcycle_vectors
 from test_gpu_kernel_reference import _hubs, _vectors
 from test_gpu_setup_pipeline import _graph as _fixed_and_duplicates
 
@@ -35,9 +38,10 @@ def check(case, o, fixed, cycle=True, check_mask=True, seed=0):
     res = ar.check_hierarchy(lv, poses_xy=xy, check_mask=check_mask)
     worst = {k: (round(v[0], 3), v[1], v[2], v[3]) for k, v in ar.worst_by_stage(res).items()}
     tentative = [l for l, L in enumerate(lv[:-1]) if not L["smoothed"]]
-    # cycle=True: a V-cycle hierarchy is expected and stage 9 must run; False: a tentative level is expected (K-cycle, no stage 9)
-    assert bool(tentative) != bool(cycle), (case, "tentative levels", tentative, desc)
-    cyc = []
+    # cycle=True: a V-cycle hierarchy is expected (stage 9 against K_CYCLE); False: a tentative level is expected, whose cycle is
+    # the K-cycle (stage 9 with the flexible-CG driver against K_KCYCLE, and stage 10 on the exported work vectors)
+    assert bool(tentative) != bool(cycle) and ar.has_kcycle(lv) != bool(cycle), (case, "tentative levels", tentative, desc)
+    cyc, kstep, kbad = [], {}, {}
     if cycle:
         for r in _vectors(n, seed):
             z = o.precondition(r)
@@ -45,16 +49,20 @@ def check(case, o, fixed, cycle=True, check_mask=True, seed=0):
             ri[order], zi[order] = r, z
             zr, eps = ar.cycle_scale(lv, ri)
             cyc.append((ar.cycle_ratio(zi, zr, eps), eps))
+    else:
+        kstep, kc, kbad, _ = kcycle_vectors(o, lv, list(zip(("random", "uniform", "scaled"), _vectors(n, seed))))
+        cyc = [(c[1], c[2]) for c in kc]
     shape = [dict(l=l, n=L["n"], nslot=L["nslot"], smoothed=L["smoothed"], filtered=L["filtered"], kind=L["kind"], nu=L["nu"],
                   t_nlong=L["t_nlong"], ps_t_nlong=L["ps_t_nlong"], f32=L["f32"], max_row=int(np.diff(L["rowptr"]).max()),
                   max_aggregate=int(np.diff(L["mem_ptr"]).max()) if "mem_ptr" in L else 0,
                   max_p_column=int(np.bincount(L["p_col"]).max()) if "p_col" in L else 0,
                   folded_worst=L.get("_folded_worst")) for l, L in enumerate(lv)]
-    report = dict(case=case, desc=desc, worst=worst, cycle=cyc, kappa_coarsest=lv[-1].get("_kappa"), shape=shape)
+    report = dict(case=case, desc=desc, worst=worst, cycle=cyc, kcycle_steps=kstep, kappa_coarsest=lv[-1].get("_kappa"), shape=shape)
     print("AMGREF " + json.dumps(report, default=str))
     bad = ar.failures(res)
     assert not bad, (case, bad, worst)
-    assert len(cyc) == (3 if cycle else 0) and all(r <= ar.K_CYCLE for r, _ in cyc), (case, cyc, worst)
+    assert not kbad, (case, kbad, kstep)
+    assert len(cyc) == 3 and all(r <= (ar.K_CYCLE if cycle else ar.K_KCYCLE) for r, _ in cyc), (case, cyc, worst)
     return lv, desc, report
 
 
@@ -143,24 +151,25 @@ def test_c4_two_sweeps_around_the_folded_cycle_and_long_columns_of_p():
 
 
 def test_tentative_levels_of_a_graph_with_random_closures():
-    """Stages 1, 2, 6 and 8 (a tentative level's cycle is the K-cycle: outside stage 9)."""
+    """Stages 1, 2, 6 and 8, and the K-cycle of its tentative levels: stages 9 and 10."""
     lv, desc, rep = _run("manhattan_20k_random_closures", synth.manhattan(20000, 120000, seed=21, p_random=0.05, info_mode="full"),
                          cycle=False)
     assert any(not L["smoothed"] for L in lv[:-1]), desc
-    assert rep["cycle"] == []
+    assert len(rep["cycle"]) == 3 and rep["kcycle_steps"]
 
 
 def test_c4r_stalled_hierarchy_with_a_large_aggregate():
     """C4 with 5 % random closures: tentative levels whose coarsening stalls, the last one collapsing into aggregates of more than
-    64 members (k_centres' wave-per-aggregate sums, k_restrict's long groups).  Stages 1, 2, 6 and 8."""
+    64 members (k_centres' wave-per-aggregate sums, k_restrict's long groups).  Stages 1, 2, 6 and 8, and the K-cycle: stages 9 and 10
+    (three vectors: the reference takes about as long as C4's)."""
     lv, desc, rep = _run("C4r", synth.config("C4r"), cycle=False)
     assert any(not L["smoothed"] for L in lv[:-1]), desc
     assert max(int(np.diff(L["mem_ptr"]).max()) for L in lv[:-1]) > 64, desc
-    assert rep["cycle"] == []
+    assert len(rep["cycle"]) == 3 and rep["kcycle_steps"]
 
 
 def test_hubs_rows_longer_than_a_wave():
-    """Hubs of 65, 130 and 1000 edges: rows longer than 64 slots on level 0 and above (a tentative hierarchy: stages 1, 2, 6, 8).
+    """Hubs of 65, 130 and 1000 edges: rows longer than 64 slots on level 0 and above (a tentative hierarchy: stages 1, 2, 6, 8, and 9, 10 for its K-cycle).
     Its largest aggregate has 19 members (measured on the MI355X; asserted, so that a change of it is seen): the aggregate of
     more than 64 members is asserted where one occurs, on C4r's stalled last level (627 members)."""
     lv, desc, _ = _run("hubs_65_130_1000", _hubs(), cycle=False)

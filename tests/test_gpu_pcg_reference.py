@@ -124,8 +124,8 @@ def test_every_stage(name, monkeypatch):
                 assert s["iter"] == N - 1 and s["stop"] == (2 if N > 1 else 0) and s["rr"] > s["tol2"] * s["bb"], s
                 assert f"drift@{N}" in res and f"frozen@{N + 1}" in res, sorted(res)[:40]
                 extra["drift_at_N"] = float(f"{res[f'drift@{N}'].raw:.3g}")
-        # stage 4: the cycle inside the loop at every cap (V-cycle hierarchies and the dense single level: amg_reference's stage 9;
-        # the K-cycle's inner flexible-CG steps are outside it, which the report says)
+        # stage 4: the cycle inside the loop at every cap against amg_reference's stage 9 (V-cycle hierarchies and the dense single
+        # level: K_CYCLE; the K-cycle, whose flexible-CG steps are nonlinear in r: K_KCYCLE)
         if case.solver == pc.AMG and "SGO_AMG_KDEPTH" not in case.env:
             cyc = _cycle_figures(o, {c: st[c] for c in caps if st[c]["S"]["iter"] == c})
             assert len(cyc) >= min(len(caps) - 1, 2)
@@ -136,7 +136,10 @@ def test_every_stage(name, monkeypatch):
         elif case.solver == pc.AMG:
             kd = dict(zip(ar.INFO, ar._fetch(o, 0, "INFO", np.float64)))["kdepth"]
             assert kd > 0, kd
-            extra["cycle"] = "K-cycle (depth %d): outside amg_reference's stage 9" % kd
+            cyc = _cycle_figures(o, {c: st[c] for c in caps if st[c]["S"]["iter"] == c})
+            assert len(cyc) >= min(len(caps) - 1, 2)
+            res.update({f"cycle@{c}": v / ar.K_KCYCLE for c, v in cyc.items()})
+            extra["cycle"], extra["kdepth"] = max(cyc.values()), int(kd)
             o.pcg_run(caps[-1])
             extra["cycle_bitwise_with_sgo_precondition"] = bool(np.array_equal(o.precondition(last["r"]), last["z"]))
             assert extra["cycle_bitwise_with_sgo_precondition"], "the K-cycle in the loop and sgo_precondition differ on the same r"
