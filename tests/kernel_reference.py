@@ -121,7 +121,7 @@ def edge_terms(xi, xj, meas, info, phi, x_i=(), x_j=(), e=None):
              bi_abs=np.einsum("nij,nj->ni", Abt, Wea), bj_abs=np.einsum("nij,nj->ni", Bbt, Wea),
              Hii=At @ W @ A, Hjj=Bt @ W @ B, Hii_abs=Abt @ Wa @ Ab, Hjj_abs=Bbt @ Wa @ Bb,
              Hij=At @ W @ B, Hij_abs=Abt @ Wa @ Bb,      # (the off-diagonal block towards the second vertex; its transpose the other way)
-             yi=[], yj=[], yi_abs=[], yj_abs=[])
+             yi=[], yj=[], yi_abs=[], yj_abs=[], A_abs=Ab, B_abs=Bb, e_abs=ebar)
     for a, c in zip(x_i, x_j):
         v = np.einsum("nij,nj->ni", W, np.einsum("nij,nj->ni", A, a) + np.einsum("nij,nj->ni", B, c))
         va = np.einsum("nij,nj->ni", Wa, np.einsum("nij,nj->ni", Ab, np.abs(a)) + np.einsum("nij,nj->ni", Bb, np.abs(c)))

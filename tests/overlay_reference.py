@@ -556,9 +556,9 @@ def _wrap_ld(t):
     return np.where((t >= -two_pi / 2) & (t < two_pi / 2), t, u)
 
 
-def edge_blocks_ld(P, ei, ej, meas, info, phi):
-    """np_oracle's edge algebra (edge_error, edge_jacobians, dcs_rho, the quadratic form) evaluated in long double throughout:
-    (b_i, b_j, H_ii, H_jj, H_ij) per edge.  np_oracle itself returns fp64 for any input, and forward() shares those fp64 terms."""
+def edge_parts_ld(P, ei, ej, meas):
+    """(e, A, B) per edge in long double: np_oracle's edge_error and edge_jacobians, the part of edge_blocks_ld's algebra before
+    the information matrix (the candidates of sgo_candidate_gate have no more than this: tests/fsolve_reference.py)."""
     xi, xj, z = (np.asarray(a, dtype=np.float64).astype(LD) for a in (P[ei], P[ej], meas))
     m = xi.shape[0]
     ci, si = np.cos(xi[:, 2]), np.sin(xi[:, 2])
@@ -575,6 +575,13 @@ def edge_blocks_ld(P, ei, ej, meas, info, phi):
     Rz = np.zeros((m, 3, 3), dtype=LD)
     Rz[:, 0, 0], Rz[:, 0, 1], Rz[:, 1, 0], Rz[:, 1, 1], Rz[:, 2, 2] = cz, -sz, sz, cz, 1
     A, B = Rz @ A0, Rz @ B0
+    return e, A, B
+
+
+def edge_blocks_ld(P, ei, ej, meas, info, phi):
+    """np_oracle's edge algebra (edge_error, edge_jacobians, dcs_rho, the quadratic form) evaluated in long double throughout:
+    (b_i, b_j, H_ii, H_jj, H_ij) per edge.  np_oracle itself returns fp64 for any input, and forward() shares those fp64 terms."""
+    e, A, B = edge_parts_ld(P, ei, ej, meas)
     O = npo.info_full(info).astype(LD)
     e2 = np.einsum("ni,nij,nj->n", e, O, e)
     ph = np.asarray(phi, dtype=np.float64).astype(LD)
