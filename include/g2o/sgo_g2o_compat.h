@@ -1063,6 +1063,41 @@ class SparseOptimizer : public OptimizableGraph {
     return rc;
   }
 
+  // the listed edges as the device numbers them (sgoEdgeLeaveOneOut, sgoEdgeJoint); false with one line on std::cerr in the
+  // situations sgoEdgeLeaveOneOut names
+  bool residentEdgeIds(const char* who, const std::vector<OptimizableGraph::Edge*>& edges, std::vector<int32_t>& ids) {
+    if (!_algorithm || !gpuEligible()) {
+      std::cerr << "SparseOptimizer::" << who << ": only the device path (VertexSE2 / EdgeSE2 under Gauss-Newton) has this test" << std::endl;
+      return false;
+    }
+    if (_activeRevision != _revision || _activeVertices.empty()) {
+      std::cerr << "SparseOptimizer::" << who << ": the graph changed since the last initializeOptimization" << std::endl;
+      return false;
+    }
+    std::vector<std::pair<const OptimizableGraph::Edge*, int32_t>> place(_activeEdges.size());   // active edge -> its place in _activeEdges
+    for (size_t k = 0; k < _activeEdges.size(); ++k) place[k] = std::make_pair((const OptimizableGraph::Edge*)_activeEdges[k], (int32_t)k);
+    std::sort(place.begin(), place.end());
+    const size_t n = edges.size();
+    ids.assign(n, 0);
+    for (size_t t = 0; t < n; ++t) {
+      auto it = std::lower_bound(place.begin(), place.end(), std::make_pair((const OptimizableGraph::Edge*)edges[t], (int32_t)0));
+      if (!edges[t] || it == place.end() || it->first != edges[t]) {
+        std::cerr << "SparseOptimizer::" << who << ": edge " << t << " of the list is not an active edge of the graph" << std::endl;
+        return false;
+      }
+      ids[t] = it->second;
+    }
+    if (!uploadGraph()) return false;
+    // the device's numbering: the records it was set up with, of which the edges that left since are deactivated, not renumbered
+    if (_m.nDead > 0) {
+      std::vector<int32_t> record;
+      for (size_t r = 0; r < _m.dead.size(); ++r)
+        if (!_m.dead[r]) record.push_back((int32_t)r);
+      for (int32_t& id : ids) id = record[(size_t)id];
+    }
+    return true;
+  }
+
   // ---- the leave-one-out test of edges that ARE in the graph (extension; sgo_edge_leave_one_out of include/sgo.h): (*d2)[t] is
   // what sgoCandidateGate would say about edges[t] had it never been inserted, at the current estimates, all edges from one selected
   // inversion; (*redundancy)[t] in [0, 1] is 0 for a bridge edge (removing it disconnects the graph), whose d2 is NaN and which
@@ -1072,35 +1107,9 @@ class SparseOptimizer : public OptimizableGraph {
   // graph, and when the call itself refuses (sgo_last_error's text).
   int sgoEdgeLeaveOneOut(const std::vector<OptimizableGraph::Edge*>& edges, double chi2Max, double minRedundancy, std::vector<double>* d2,
                          std::vector<double>* redundancy, std::vector<bool>* fail) {
-    if (!_algorithm || !gpuEligible()) {
-      std::cerr << "SparseOptimizer::sgoEdgeLeaveOneOut: only the device path (VertexSE2 / EdgeSE2 under Gauss-Newton) has this test" << std::endl;
-      return -1;
-    }
-    if (_activeRevision != _revision || _activeVertices.empty()) {
-      std::cerr << "SparseOptimizer::sgoEdgeLeaveOneOut: the graph changed since the last initializeOptimization" << std::endl;
-      return -1;
-    }
-    std::vector<std::pair<const OptimizableGraph::Edge*, int32_t>> place(_activeEdges.size());   // active edge -> its place in _activeEdges
-    for (size_t k = 0; k < _activeEdges.size(); ++k) place[k] = std::make_pair((const OptimizableGraph::Edge*)_activeEdges[k], (int32_t)k);
-    std::sort(place.begin(), place.end());
+    std::vector<int32_t> ids;
+    if (!residentEdgeIds("sgoEdgeLeaveOneOut", edges, ids)) return -1;
     const size_t n = edges.size();
-    std::vector<int32_t> ids(n);
-    for (size_t t = 0; t < n; ++t) {
-      auto it = std::lower_bound(place.begin(), place.end(), std::make_pair((const OptimizableGraph::Edge*)edges[t], (int32_t)0));
-      if (!edges[t] || it == place.end() || it->first != edges[t]) {
-        std::cerr << "SparseOptimizer::sgoEdgeLeaveOneOut: edge " << t << " of the list is not an active edge of the graph" << std::endl;
-        return -1;
-      }
-      ids[t] = it->second;
-    }
-    if (!uploadGraph()) return -1;
-    // the device's numbering: the records it was set up with, of which the edges that left since are deactivated, not renumbered
-    if (_m.nDead > 0) {
-      std::vector<int32_t> record;
-      for (size_t r = 0; r < _m.dead.size(); ++r)
-        if (!_m.dead[r]) record.push_back((int32_t)r);
-      for (int32_t& id : ids) id = record[(size_t)id];
-    }
     std::vector<double> dd(n + 1), rr(n + 1);   // (never a null d2, whatever n)
     std::vector<uint8_t> ff(n + 1);
     const int rc = sgo_edge_leave_one_out(_ctx, (int32_t)n, ids.data(), chi2Max, minRedundancy, dd.data(), rr.data(), nullptr, ff.data());
@@ -1113,6 +1122,69 @@ class SparseOptimizer : public OptimizableGraph {
     if (fail) {
       fail->resize(n);
       for (size_t t = 0; t < n; ++t) (*fail)[t] = ff[t] != 0;
+    }
+    return rc;
+  }
+
+  // ---- the leave-GROUP-out test of clusters of edges that are in the graph (extension; sgo_edge_joint / sgo_edge_groups of
+  // include/sgo.h).  sgoEdgeJoint builds the table of the listed edges (at most SGO_JOINT_MAX_CANDIDATES, none twice) at the current
+  // estimates and keeps it in the backend; returns their number.  sgoEdgeGroups: groups[b] lists the members of group b (indices
+  // into the edges given to sgoEdgeJoint, any order, a repeated index counts once; at most SGO_JOINT_MAX_SUBSET); (*d2)[b] is what
+  // sgoCandidateJoint would say about the cluster had it never been inserted, 3 |g| degrees of freedom; (*pivot)[b] in [0, 1] is 0 for a
+  // cluster whose removal disconnects the graph, whose d2 is NaN and which never fails; chi2Max empty: no decisions (returns 0,
+  // *fail is emptied), else one bound per group and (*fail)[b] = pivot >= minPivot && d2 > chi2Max[b]; returns how many fail.  Both
+  // return -1 with one line on std::cerr, the outputs untouched, where sgoEdgeLeaveOneOut does, and sgoEdgeGroups also for an index
+  // outside the table and a chi2Max of another length than groups.
+  int sgoEdgeJoint(const std::vector<OptimizableGraph::Edge*>& edges) {
+    std::vector<int32_t> ids;
+    _edgeJointN = 0;
+    if (!residentEdgeIds("sgoEdgeJoint", edges, ids)) return -1;
+    ids.push_back(0);   // (never a null list, whatever n)
+    const int rc = sgo_edge_joint(_ctx, (int32_t)edges.size(), ids.data(), nullptr, nullptr, nullptr);
+    if (rc < 0) {
+      std::cerr << "SparseOptimizer::sgoEdgeJoint: " << sgo_last_error(_ctx) << std::endl;
+      return -1;
+    }
+    _edgeJointN = edges.size();
+    return rc;
+  }
+  int sgoEdgeGroups(const std::vector<std::vector<int>>& groups, const std::vector<double>& chi2Max, double minPivot, std::vector<double>* d2,
+                    std::vector<double>* pivot, std::vector<bool>* fail) {
+    if (!_algorithm || !gpuEligible()) {
+      std::cerr << "SparseOptimizer::sgoEdgeGroups: only the device path (VertexSE2 / EdgeSE2 under Gauss-Newton) has this test" << std::endl;
+      return -1;
+    }
+    if (_activeRevision != _revision || _activeVertices.empty()) {
+      std::cerr << "SparseOptimizer::sgoEdgeGroups: the graph changed since the last initializeOptimization" << std::endl;
+      return -1;
+    }
+    const size_t n = _edgeJointN, B = groups.size();
+    if (!chi2Max.empty() && chi2Max.size() != B) {
+      std::cerr << "SparseOptimizer::sgoEdgeGroups: " << chi2Max.size() << " bounds for " << B << " groups" << std::endl;
+      return -1;
+    }
+    std::vector<uint8_t> member(B * n + 1, 0);
+    for (size_t b = 0; b < B; ++b)
+      for (int t : groups[b]) {
+        if (t < 0 || (size_t)t >= n) {
+          std::cerr << "SparseOptimizer::sgoEdgeGroups: group " << b << " names row " << t << ", the table holds " << n << " edges" << std::endl;
+          return -1;
+        }
+        member[b * n + (size_t)t] = 1;
+      }
+    std::vector<double> dd(B + 1), pp(B + 1);
+    std::vector<uint8_t> ff(B + 1);
+    const int rc = sgo_edge_groups(_ctx, (int32_t)n, (int32_t)B, member.data(), chi2Max.empty() ? nullptr : chi2Max.data(), minPivot, dd.data(), nullptr,
+                                   pp.data(), ff.data());
+    if (rc < 0) {
+      std::cerr << "SparseOptimizer::sgoEdgeGroups: " << sgo_last_error(_ctx) << std::endl;
+      return -1;
+    }
+    if (d2) d2->assign(dd.begin(), dd.begin() + B);
+    if (pivot) pivot->assign(pp.begin(), pp.begin() + B);
+    if (fail) {
+      fail->assign(chi2Max.empty() ? 0 : B, false);
+      for (size_t b = 0; b < fail->size(); ++b) (*fail)[b] = ff[b] != 0;
     }
     return rc;
   }
@@ -1778,6 +1850,7 @@ class SparseOptimizer : public OptimizableGraph {
   EdgeSet _edges;
   long long _nextEdgeId = 0;
   long long _revision = 0, _activeRevision = -1;   // container changes so far | ... when the active sets were last made
+  size_t _edgeJointN = 0;                          // the edges of the table sgoEdgeJoint built last (0: none)
   std::vector<OptimizableGraph::Vertex*> _activeVertices;
   std::vector<OptimizableGraph::Edge*> _activeEdges;
   sgo_ctx* _ctx = nullptr;

@@ -598,7 +598,8 @@ int sgo_joint_pairs(sgo_ctx* ctx, int32_t n, double* d2 /*[n][n]*/);
  * [0, E), chi2_max not finite, min_redundancy outside (0, 1] (zero is refused so that a bridge's 0 / 0 can never decide), an active
  * overlay, a multi-GPU context (sgo_debug_set_shard's emulation included).  SGO_EINVAL with the outputs untouched when the
  * factorisation is not positive definite; the next sgo_optimize_gn is unaffected.
- * Not covered: groups of edges (their cross blocks are the joint table's), deactivation inside the call (sgo_set_edge_information).
+ * Groups of edges (several wrong closures that vouch for each other) are sgo_edge_joint / sgo_edge_groups' below.  Not covered:
+ * deactivation inside the call (sgo_set_edge_information).
  *
  * sgo_edge_loo_rule: the per-edge arithmetic alone, as the kernel compiles it (sgo_rules.h; no context, no GPU, like sgo_gain_stop):
  * info6 = Omega's upper triangle by rows, P9 row-major, e3, w -> d2, redundancy, cov_loo (may be NULL); no min_redundancy is applied.
@@ -608,6 +609,56 @@ int sgo_edge_leave_one_out(sgo_ctx* ctx, int32_t n, const int32_t* edge_ids /*NU
                            double* cov_loo /*[n][9], may be NULL*/, uint8_t* fail /*[n], may be NULL*/);
 int sgo_edge_loo_rule(const double* info6, const double* P9, const double* e3, double w, double* d2, double* redundancy,
                       double* cov_loo /*[9] or NULL*/);
+
+/* (later additions, version 107) Leave-GROUP-out test of clusters of resident edges on a joint table.
+ * Closures arrive in bursts: several matches against the same submap are wrong together and vouch for each other, which the
+ * single-edge test above cannot see.  A group g of k resident edges at the current poses, stacked: e (3 k), J the Jacobian rows (a
+ * fixed endpoint drops out), Omega = blockdiag(Omega_t) the resident information, w_t the kernel weights (sgo_edge_robust's),
+ * D = blockdiag(w_t I3), H sgo_marginals_selected's robustified Hessian, N = 1/2 (Q + Q^T) with Q = J H^-1 J^T.  With
+ * Omega_t = G_t G_t^T (lower Cholesky), G = blockdiag(G_t), Nt = G^T N G, c = G^T e, T = D^1/2:
+ *   K     = I + Nt - D Nt - Nt D - Nt D (I - D) Nt        (symmetric)
+ *   d2    = c^T K^-1 c,   dof = 3 k
+ *   pivot = the smallest squared diagonal entry of the Cholesky factor of I - T Nt T
+ * d2 is e~^T (Omega^-1 + P_)^-1 e~ with H_ = H - J^T (D Omega) J, P_ = J H_^-1 J^T and e~ = e + J H_^-1 J^T D Omega e:
+ * sgo_edge_leave_one_out's definition with a group in the edge's place, what sgo_joint_subsets would say about the cluster had it
+ * never been inserted.  k = 1 is that call's closed form, w = 1 gives K = I - Nt, w = 0 gives K = I + Nt (the joint test's S).  pivot
+ * lies in [0, 1], bounds lambda_min(I - T Nt T) from above and is 0 up to rounding exactly when removing the group disconnects the graph.
+ * A member with all-zero information is dropped from its group and adds nothing to dof; an information that is not positive
+ * definite gives d2 = pivot = NaN, no fail; the empty group gives d2 = 0 exactly, dof = 0, pivot = 1.  Whenever pivot is not finite
+ * or pivot < min_pivot, d2 is NaN, pivot is reported as computed and the group does not fail.  Otherwise fail = d2 > chi2_max[b].
+ *
+ * sgo_edge_joint builds the table of the n <= SGO_JOINT_MAX_CANDIDATES listed resident edges at the CURRENT poses -- N, e, w and the
+ * resident Omega --, copies N, e and w out where asked and keeps the table in the context.  Returns n.  The columns H^-1 J^T are
+ * sgo_candidate_joint's (through the factor, or through the PCG where the analysis refuses the graph, under its rules); the
+ * per-edge records are filled on the device from the resident edge list, no edge data crosses to the host.  One triangle of N is
+ * computed and mirrored: N is exactly symmetric.  The table is a SNAPSHOT with the lifetime of the candidates' table (until the
+ * next successful sgo_edge_joint, sgo_set_graph_se2, sgo_update_graph_se2 or sgo_destroy; n == 0 drops it and returns 0), and it is
+ * a SECOND table: neither sgo_edge_joint nor sgo_candidate_joint drops or changes the other's.  SGO_EINVAL with nothing on the
+ * device changed, no output written and the resident tables kept: n < 0, null edge_ids with n > 0, n > SGO_JOINT_MAX_CANDIDATES, an
+ * id outside [0, E), an id listed twice (removing an edge twice has no meaning), an active overlay, a multi-GPU context; with the
+ * outputs untouched and the tables kept when the Hessian is not positive definite.
+ *
+ * sgo_edge_groups evaluates B groups of the resident table, one workgroup each: member[b][t] != 0 puts table row t into group b,
+ * members are taken in ascending t, at most SGO_JOINT_MAX_SUBSET per group.  Returns how many fail, 0 with chi2_max == NULL (no
+ * decisions; fail is not written).  A group's result depends on the table and its member row alone -- not on B or its place in
+ * the batch --, and two calls give the same bits.  SGO_EINVAL, nothing written: no resident table, n not the table's n, B < 0, a
+ * null member or d2 with B > 0, a non-finite chi2_max entry, min_pivot outside (0, 1], a group above the cap (named in
+ * sgo_last_error).  B == 0 returns 0.
+ * Both calls write only scratch and what every Gauss-Newton iteration recomputes: a later sgo_optimize_gn has the bits of a context
+ * that never called, and sgo_joint_subsets returns the bits it returned before.
+ *
+ * sgo_edge_group_rule: one group's arithmetic alone, as the kernel compiles it (sgo_rules.h; no context, no GPU, like
+ * sgo_edge_loo_rule): the k members' info6 (Omega's upper triangle by rows), N (3 k x 3 k row-major), e, w -> d2, pivot, dof; no
+ * min_pivot is applied (d2 is NaN only where pivot is not above zero or K is not positive definite).  Returns 0, 1 when a member
+ * with all-zero information was dropped, 2 when pivot is NaN (an information that is not positive definite), SGO_EINVAL for
+ * k outside [0, SGO_JOINT_MAX_SUBSET] or a null argument. */
+int sgo_edge_joint(sgo_ctx* ctx, int32_t n, const int32_t* edge_ids, double* N /*[3n][3n] or NULL*/, double* e /*[n][3] or NULL*/,
+                   double* w /*[n] or NULL*/);
+int sgo_edge_groups(sgo_ctx* ctx, int32_t n, int32_t B, const uint8_t* member /*[B][n]*/, const double* chi2_max /*[B] or NULL*/,
+                    double min_pivot, double* d2 /*[B]*/, int32_t* dof /*[B] or NULL*/, double* pivot /*[B] or NULL*/,
+                    uint8_t* fail /*[B] or NULL*/);
+int sgo_edge_group_rule(int32_t k, const double* info6 /*[k][6]*/, const double* N /*[3k][3k]*/, const double* e /*[3k]*/,
+                        const double* w /*[k]*/, double* d2, double* pivot, int32_t* dof);
 
 /* (later additions, version 107) Greedy search for a large jointly compatible set on the resident table of sgo_candidate_joint
  * (DESIGN.md section 5l): "which of these candidates form the largest consistent set?" without a from-scratch factorisation per

@@ -38,6 +38,7 @@ SYMBOLS = [
     "sgo_gain_stop", "sgo_optimize_gn_until", "sgo_optimize_gn_hypotheses", "sgo_hypothesis_isolated_vertex",
     "sgo_candidate_joint", "sgo_joint_subsets", "sgo_joint_pairs", "sgo_edge_leave_one_out", "sgo_edge_loo_rule",
     "sgo_joint_greedy", "sgo_joint_extend", "sgo_joint_greedy_rule",
+    "sgo_edge_joint", "sgo_edge_groups", "sgo_edge_group_rule",
     "sgo_set_hypotheses_workspace", "sgo_hypotheses_bytes", "sgo_hypotheses_chunk", "sgo_hypotheses_workspace_bytes",
 ]
 
@@ -74,6 +75,21 @@ def edge_loo_rule(info6, P, e, w: float):
     d2, red, cov = C.c_double(), C.c_double(), np.empty((3, 3))
     rc = lib().sgo_edge_loo_rule(_dp(o), _dp(Pm), _dp(ev), float(w), C.byref(d2), C.byref(red), _dp(cov))
     return rc, d2.value, red.value, cov
+
+
+def edge_group_rule(info6, N, e, w):
+    """sgo_edge_group_rule: one group's arithmetic of sgo_edge_groups as the library (and its kernel) computes it, no context and no
+    GPU: info6 (k, 6) = the members' Omega, upper triangle by rows, N (3 k, 3 k), e (k, 3), w (k,) -> (rc, d2, pivot, dof); rc 0, 1 when
+    a member with all-zero information was dropped, 2 when an information is not positive definite, SGO_EINVAL (-2) for k above
+    SGO_JOINT_MAX_SUBSET.  No min_pivot is applied."""
+    o = np.ascontiguousarray(info6, dtype=np.float64).reshape(-1, 6)
+    k = o.shape[0]
+    Nm = np.ascontiguousarray(N, dtype=np.float64).reshape(3 * k, 3 * k)
+    ev = np.ascontiguousarray(e, dtype=np.float64).reshape(3 * k)
+    wv = np.ascontiguousarray(w, dtype=np.float64).reshape(k)
+    d2, piv, dof = C.c_double(), C.c_double(), C.c_int32(-1)
+    rc = lib().sgo_edge_group_rule(k, _dp(o), _dp(Nm), _dp(ev), _dp(wv), C.byref(d2), C.byref(piv), C.byref(dof))
+    return rc, d2.value, piv.value, dof.value
 
 
 # SGO_JSTOP_*: why a search of sgo_joint_greedy ended
@@ -259,6 +275,9 @@ def lib():
     L.sgo_edge_loo_rule.argtypes = [d, d, d, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double), d]
     L.sgo_joint_greedy.argtypes = [vp, C.c_int32, C.c_int32, i32, u8, d, C.c_int32, i32, i32, i32, d, d]
     L.sgo_joint_extend.argtypes = [vp, C.c_int32, C.c_int32, i32, d, d]
+    L.sgo_edge_joint.argtypes = [vp, C.c_int32, i32, d, d, d]
+    L.sgo_edge_groups.argtypes = [vp, C.c_int32, C.c_int32, u8, d, C.c_double, d, i32, d, u8]
+    L.sgo_edge_group_rule.argtypes = [C.c_int32, d, d, d, d, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32)]
     L.sgo_joint_greedy_rule.argtypes = [C.c_int32, d, d, i32, u8, d, C.c_int32, i32, i32, i32, d, d]
     L.sgo_kernel_profile.argtypes = [vp, C.POINTER(KernelStat), C.c_int]
     L.sgo_kernel_profile_samples.argtypes = [vp, C.c_int, C.POINTER(C.c_float), C.c_int]
@@ -850,6 +869,36 @@ class Optimizer:
         if rc < 0:
             raise SgoError(f"sgo_edge_leave_one_out: rc={rc}: " + lib().sgo_last_error(self._h).decode())
         return rc, d2, red, cov, fl.astype(bool)
+
+    def edge_joint(self, edge_ids):
+        """sgo_edge_joint: the table of the listed resident edges at the current poses -> (N (3 n, 3 n), e (n, 3), w (n,)):
+        N = 1/2 (Q + Q^T), Q = J H^-1 J^T, e the errors, w the kernel weights.  The table (with the edges' resident information) stays
+        in the context, a snapshot beside candidate_joint's table, for edge_groups; no edges drop it."""
+        ids = np.ascontiguousarray(edge_ids, dtype=np.int32).reshape(-1)
+        n = ids.size
+        N, e, w = np.empty((3 * n, 3 * n)), np.empty((n, 3)), np.empty(n)
+        rc = lib().sgo_edge_joint(self._h, n, _ip(ids), _dp(N), _dp(e), _dp(w))
+        if rc < 0:
+            raise SgoError(f"sgo_edge_joint: rc={rc}: " + lib().sgo_last_error(self._h).decode())
+        self.edge_joint_n = rc
+        return N, e, w
+
+    def edge_groups(self, member, chi2_max=None, min_pivot: float = 1e-3):
+        """sgo_edge_groups: the leave-group-out test of the groups member (B, n) (non-zero: table row t belongs to the group) of the
+        resident edge table -> (nfail, d2 (B,), dof (B,), pivot (B,), fail (B,) bool): d2 is what joint_subsets would say about the
+        cluster had it never been inserted, fail = pivot >= min_pivot and d2 > chi2_max[b] (chi2_max None: no decisions, nfail 0); a
+        cluster whose removal disconnects the graph (pivot below min_pivot) has d2 = NaN and does not fail."""
+        m = np.ascontiguousarray(np.asarray(member) != 0, dtype=np.uint8)
+        m = m.reshape(-1, m.shape[-1]) if m.ndim else m.reshape(0, 0)
+        B, n = m.shape
+        chi = None if chi2_max is None else np.ascontiguousarray(np.broadcast_to(np.asarray(chi2_max, dtype=np.float64), (B,)))
+        d2, dof, piv, fl = np.empty(B), np.zeros(B, dtype=np.int32), np.empty(B), np.zeros(B, dtype=np.uint8)
+        u8p = C.POINTER(C.c_uint8)
+        rc = lib().sgo_edge_groups(self._h, n, B, m.ctypes.data_as(u8p), None if chi is None else _dp(chi), float(min_pivot), _dp(d2), _ip(dof),
+                                   _dp(piv), fl.ctypes.data_as(u8p))
+        if rc < 0:
+            raise SgoError(f"sgo_edge_groups: rc={rc}: " + lib().sgo_last_error(self._h).decode())
+        return rc, d2, dof, piv, fl.astype(bool)
 
     def candidate_joint(self, ci, cj, meas, info):
         """sgo_candidate_joint: the joint table of the candidate edges (arguments as candidate_gate's) at the current poses ->

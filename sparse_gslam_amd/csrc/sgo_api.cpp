@@ -386,7 +386,8 @@ void sgo_destroy(sgo_ctx* c) {
   if (c->selinv.d_loo) hipFree(c->selinv.d_loo);
   if (c->selinv.d_loo_ids) hipFree(c->selinv.d_loo_ids);
   for (void* p : {(void*)c->joint.d_tab[0], (void*)c->joint.d_tab[1], (void*)c->joint.d_raw, (void*)c->joint.d_d2, (void*)c->joint.d_mask,
-                  (void*)c->joint.d_grow, (void*)c->joint.d_gout, (void*)c->joint.d_gint})
+                  (void*)c->joint.d_grow, (void*)c->joint.d_gout, (void*)c->joint.d_gint, (void*)c->ejoint.d_tab[0], (void*)c->ejoint.d_tab[1],
+                  (void*)c->ejoint.d_out, (void*)c->ejoint.d_mask})
     if (p) hipFree(p);
   if (c->hyp.d_ws) hipFree(c->hyp.d_ws);
   if (c->stream) hipStreamDestroy(c->stream);
@@ -633,6 +634,7 @@ int sgo_update_graph_se2(sgo_ctx* c, int32_t V, const double* poses, const uint8
         c->E = E;
         c->linearized = false;
         c->joint.n = -1;   // (sgo_candidate_joint's table described the graph before the update)
+        c->ejoint.n = -1;  // (... and sgo_edge_joint's)
         edge_activity_append(c, V, dE, ei + n_resident_edges, ej + n_resident_edges, info + 6 * (size_t)n_resident_edges);
         if (!c->robust.kind.empty()) c->robust.kind.resize((size_t)E, (uint8_t)SGO_KERNEL_DCS);   // (appended edges: what phi says)
         ov.dev.el.kinds = c->el.kinds;

@@ -314,6 +314,19 @@ struct sgo_ctx {
     size_t grow_cap = 0, gout_cap = 0, gint_cap = 0;
   } joint;
 
+  // sgo_edge_joint's table of resident edges (sgo_egroup.cpp): N [3 n][3 n], e [n][3], w [n], Omega [n][6] and the failure flag, kept
+  // as the candidates' table is (two buffers, a call builds in the other one); the Gram blocks go through joint.d_raw, which is
+  // scratch.  sgo_edge_groups: the results [B][kEgOut] and the uploaded member rows.
+  struct EdgeJoint {
+    double* d_tab[2] = {nullptr, nullptr};
+    size_t tab_cap[2] = {0, 0};
+    int cur = 0, n = -1;
+    double* d_out = nullptr;
+    uint8_t* d_mask = nullptr;
+    size_t out_cap = 0, mask_cap = 0;
+    bool lds_ready = false;
+  } ejoint;
+
   // profiling
   struct Rec { int kid; hipEvent_t a, b; };
   std::vector<hipEvent_t> ev_pool;

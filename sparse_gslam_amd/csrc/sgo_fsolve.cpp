@@ -9,7 +9,9 @@
 // refuses sgo_candidate_gate sends the same right-hand sides through the PCG machinery of sgo_solve_rhs under sgo_marginals' rules.
 // sgo_candidate_joint is the gate's driver with another contraction: the same checks (check_candidates) and
 // the same columns (cand_columns), every chunk contracted with ALL candidates' records into the stacked innovation covariance S,
-// which stays in the context (sgo_ctx::Joint) for sgo_joint_subsets / sgo_joint_pairs.
+// which stays in the context (sgo_ctx::Joint) for sgo_joint_subsets / sgo_joint_pairs.  sgo_edge_joint is
+// that driver again for RESIDENT edges: the records' sources filled on the device (edge_columns), the same columns and Gram blocks,
+// a table of its own (sgo_ctx::EdgeJoint) for sgo_edge_groups (sgo_egroup.cpp).
 #include <algorithm>
 #include <cmath>
 
@@ -267,12 +269,13 @@ int check_candidates(sgo_ctx* c, const char* name, int n, const int32_t* ci, con
 
 // The candidates' columns X = H^-1 R at the current poses, a chunk at a time: through the factor of selinv_plan's plan, or through
 // the PCG where the analysis refuses the graph.  use(t0, t1, X, n3, flags) queues what the caller makes of the chunk [t0, t1)
-// (X: its 3 (t1 - t0) columns, rows as C.row says; flags: the factorisation's, nullptr without one); *Cp and *d_out are set before
-// the first chunk.  row: check_candidates' (rewritten to elimination positions on the factor's route).  records_first: every
-// candidate's record (C.rec) is made before the first chunk, not chunk by chunk.
-template <class Use>
-int cand_columns(sgo_ctx* c, const char* name, int n, const int32_t* ci, const int32_t* cj, const double* meas, const double* info,
-                 std::vector<int>& row, bool records_first, FsCandDev* Cp, double** d_out, Use&& use) {
+// (X: its 3 (t1 - t0) columns, rows as C.row says; flags: the factorisation's, nullptr without one).  fill(pos_of, by_pcg, C, &row,
+// &ci, &cj) puts the candidates on the device before the first chunk (*Cp) -- pos_of: hessian index -> elimination position on the
+// factor's route, nullptr where a right-hand side's rows are the hessian indices themselves -- and names the host's view of rows
+// and endpoints, which the PCG route alone reads.  records_first: every candidate's record (C.rec) is made before the first chunk,
+// not chunk by chunk.
+template <class Fill, class Use>
+int columns_of(sgo_ctx* c, const char* name, int n, Fill&& fill, bool records_first, FsCandDev* Cp, Use&& use) {
   int rc;
   Mfront* m = nullptr;
   bool by_pcg = false;
@@ -281,23 +284,24 @@ int cand_columns(sgo_ctx* c, const char* name, int n, const int32_t* ci, const i
     if (rc == SGO_ENOTHING) by_pcg = true;   // (the analysis refuses the graph: the same columns through the PCG)
     else if (rc) return rc;
   }
+  std::vector<int> pos_of;   // hessian index -> elimination position
   if (m) {
     if ((rc = fs_prepare(c, m, name))) return rc;
     const MfPlan& P = m->plan;
-    std::vector<int> pos_of((size_t)c->n, -1);   // hessian index -> elimination position
+    pos_of.assign((size_t)c->n, -1);
     for (int p = 0; p < P.n; ++p)
       pos_of[(size_t)(std::lower_bound(c->free_id.begin(), c->free_id.end(), P.elim_vertex[p]) - c->free_id.begin())] = p;
-    for (int& r : row)
-      if (r >= 0) r = pos_of[(size_t)r];
   }
-  if ((rc = cand_upload(c, n, ci, cj, row, meas, info, Cp, d_out))) return rc;
+  const std::vector<int>* rowp = nullptr;
+  const int32_t *ci = nullptr, *cj = nullptr;
+  if ((rc = fill(m ? &pos_of : nullptr, by_pcg, Cp, &rowp, &ci, &cj))) return rc;
   const FsCandDev& C = *Cp;
   if (records_first) {   // (a chunk's columns are contracted with the records of ALL candidates, later chunks' included)
     Scope sc(c, K_FS_RHS, 8.0 * (kFsRec + 9) * n);
     launch_fs_records(c->stream, C, c->d_poses);
   }
   if (by_pcg) {
-    if ((rc = gate_by_pcg(c, name, n, C, row, ci, cj, use))) return rc;
+    if ((rc = gate_by_pcg(c, name, n, C, *rowp, ci, cj, use))) return rc;
   } else {
     const int n3 = 3 * c->n;
     FsScratch S;
@@ -317,6 +321,77 @@ int cand_columns(sgo_ctx* c, const char* name, int n, const int32_t* ci, const i
     }
   }
   return SGO_OK;
+}
+
+// ... for candidates the caller describes: row is check_candidates' (rewritten to elimination positions on the factor's route);
+// *d_out: the results' place
+template <class Use>
+int cand_columns(sgo_ctx* c, const char* name, int n, const int32_t* ci, const int32_t* cj, const double* meas, const double* info,
+                 std::vector<int>& row, bool records_first, FsCandDev* Cp, double** d_out, Use&& use) {
+  return columns_of(c, name, n, [&](const std::vector<int>* pos_of, bool, FsCandDev* C, const std::vector<int>** rowp, const int32_t** cip, const int32_t** cjp) {
+    if (pos_of)
+      for (int& r : row)
+        if (r >= 0) r = (*pos_of)[(size_t)r];
+    *rowp = &row;
+    *cip = ci;
+    *cjp = cj;
+    return cand_upload(c, n, ci, cj, row, meas, info, C, d_out);
+  }, records_first, Cp, use);
+}
+
+// ... for resident edges (sgo_edge_joint): the records' sources are copied out of the resident edge list ON THE DEVICE (k_edge_cands:
+// endpoints, rows through a vertex -> row map made here from the plan, inverse measurement, information, kernel weight), so no edge
+// data crosses to the host.  *d_w: the weights [n].  The PCG route reads the endpoints' ids and rows back (3 n integers) for its
+// messages and to skip a column between two fixed poses.
+struct EdgeCandHost {
+  std::vector<int> row;
+  std::vector<int32_t> vi, vj;
+};
+template <class Use>
+int edge_columns(sgo_ctx* c, const char* name, int n, const int32_t* ids, EdgeCandHost* H, FsCandDev* Cp, double** d_w, Use&& use) {
+  return columns_of(c, name, n, [&](const std::vector<int>* pos_of, bool by_pcg, FsCandDev* C, const std::vector<int>** rowp, const int32_t** cip, const int32_t** cjp) {
+    sgo_ctx::SelInv& Z = c->selinv;
+    const size_t N = (size_t)n, V = (size_t)c->V;
+    int rc;
+    if ((rc = grow_device(c, &Z.d_cand, &Z.cand_cap, (3 + 6 + kFsRec + 1) * N + 1)) || (rc = grow_device(c, &Z.d_cidx, &Z.cidx_cap, 5 * N + V))) return rc;
+    double* d_zinv = Z.d_cand;
+    double* d_soa = d_zinv + 3 * N;
+    double* d_rec = d_soa + 6 * N;
+    *d_w = d_rec + kFsRec * N;
+    int* d_vi = Z.d_cidx;
+    int* d_vj = d_vi + N;
+    int* d_row = d_vj + N;
+    int* d_ids = d_row + 2 * N;
+    int* d_vrow = d_ids + N;
+    std::vector<int> vrow(V, -1);   // vertex -> its place in a right-hand side; -1: fixed (or without an edge)
+    for (size_t h = 0; h < c->free_id.size(); ++h) vrow[(size_t)c->free_id[h]] = pos_of ? (*pos_of)[h] : (int)h;
+    HIP_TRY(c, hipMemcpyAsync(d_ids, ids, sizeof(int) * N, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(d_vrow, vrow.data(), sizeof(int) * V, hipMemcpyHostToDevice, c->stream));
+    C->n = n;
+    C->vi = d_vi;
+    C->vj = d_vj;
+    C->row = d_row;
+    C->zinv = d_zinv;
+    C->info = d_soa;
+    C->rec = d_rec;
+    {
+      Scope sc(c, K_EDGE_TABLE, 8.0 * (9 + 9 + 1 + 6) * n + 4.0 * 7 * n);
+      launch_edge_cands(c->stream, *C, c->el, d_ids, d_vrow, c->d_poses, d_vi, d_vj, d_row, d_zinv, d_soa, *d_w);
+    }
+    if (by_pcg) {
+      H->row.resize(2 * N);
+      H->vi.resize(N);
+      H->vj.resize(N);
+      HIP_TRY(c, hipMemcpyAsync(H->row.data(), d_row, sizeof(int) * 2 * N, hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(c, hipMemcpyAsync(H->vi.data(), d_vi, sizeof(int) * N, hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(c, hipMemcpyAsync(H->vj.data(), d_vj, sizeof(int) * N, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIP_TRY(c, hipStreamSynchronize(c->stream));   // (vrow goes out of scope; the PCG route's host view is complete)
+    *rowp = &H->row;
+    *cip = H->vi.data();
+    *cjp = H->vj.data();
+    return SGO_OK;
+  }, true, Cp, use);
 }
 
 constexpr int kJointLaunch = 1 << 20;   // subsets (workgroups) per launch
@@ -514,6 +589,85 @@ int sgo_candidate_joint(sgo_ctx* c, int32_t n, const int32_t* ci, const int32_t*
   } SGO_CATCH(c)
 }
 
+
+int sgo_edge_joint(sgo_ctx* c, int32_t n, const int32_t* edge_ids, double* N, double* e, double* w) {
+  try {
+    int rc = check_graph(c);
+    if (rc) return rc;
+    if (n < 0 || (n > 0 && !edge_ids)) {
+      c->err = "sgo_edge_joint: null edge_ids or negative count";
+      return SGO_EINVAL;
+    }
+    if (n > SGO_JOINT_MAX_CANDIDATES) {
+      c->err = "sgo_edge_joint: " + std::to_string(n) + " edges, more than SGO_JOINT_MAX_CANDIDATES = " + std::to_string(SGO_JOINT_MAX_CANDIDATES);
+      return SGO_EINVAL;
+    }
+    if ((rc = refuse_context(c, "sgo_edge_joint"))) return rc;
+    {
+      std::vector<int32_t> seen(edge_ids, edge_ids + n);
+      std::sort(seen.begin(), seen.end());
+      for (int t = 0; t < n; ++t) {
+        if (seen[(size_t)t] < 0 || seen[(size_t)t] >= c->E) {
+          c->err = "sgo_edge_joint: edge id " + std::to_string(seen[(size_t)t]) + " outside [0, " + std::to_string(c->E) + ")";
+          return SGO_EINVAL;
+        }
+        if (t > 0 && seen[(size_t)t] == seen[(size_t)t - 1]) {
+          c->err = "sgo_edge_joint: edge " + std::to_string(seen[(size_t)t]) + " is listed twice (removing an edge twice has no meaning)";
+          return SGO_EINVAL;
+        }
+      }
+    }
+    sgo_ctx::EdgeJoint& J = c->ejoint;
+    if (n == 0) {
+      J.n = -1;
+      return 0;
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (!J.lds_ready) {
+      if (!edge_groups_prepare_device()) {
+        c->err = "sgo_edge_joint: the device does not grant the group kernel's dynamic LDS";
+        return SGO_EHIP;
+      }
+      J.lds_ready = true;
+    }
+    // built beside the resident table, which stays until this call has succeeded; the Gram blocks go through the candidates'
+    // table's scratch (joint.d_raw), which holds nothing between calls
+    const int other = J.n < 0 ? J.cur : 1 - J.cur;
+    const size_t N3 = 3 * (size_t)n, ntab = edge_table_doubles(n);
+    if ((rc = grow_device(c, &c->joint.d_raw, &c->joint.raw_cap, N3 * N3)) || (rc = grow_device(c, &J.d_tab[other], &J.tab_cap[other], ntab))) return rc;
+    double* const tab = J.d_tab[other];
+    FsCandDev C;
+    EdgeCandHost host;
+    double* d_w = nullptr;
+    const int* fl = nullptr;
+    if ((rc = edge_columns(c, "sgo_edge_joint", n, edge_ids, &host, &C, &d_w, [&](int t0, int t1, const double* X, int n3, const int* flags) {
+          Scope sc(c, K_FS_GRAM, 8.0 * (kFsRec + 18 + 9) * (double)n * (t1 - t0));
+          launch_fs_gram(c->stream, C, t0, t1, X, n3, c->joint.d_raw);
+          fl = flags;
+        })))
+      return rc;
+    {
+      Scope sc(c, K_EDGE_TABLE, 8.0 * 18 * (double)n * n);
+      launch_edge_table(c->stream, C, d_w, c->joint.d_raw, fl, tab);
+    }
+    HIP_TRY(c, hipGetLastError());
+    double failed = 0.0;   // the failure flag first: the outputs stay untouched when the Hessian is not positive definite
+    HIP_TRY(c, hipMemcpyAsync(&failed, tab + ntab - 1, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    prof_flush(c);
+    if (failed != 0.0) {
+      c->err = std::string("sgo_edge_joint") + kNotPd;
+      return SGO_EINVAL;
+    }
+    if (N) HIP_TRY(c, hipMemcpyAsync(N, tab, sizeof(double) * N3 * N3, hipMemcpyDeviceToHost, c->stream));
+    if (e) HIP_TRY(c, hipMemcpyAsync(e, tab + N3 * N3, sizeof(double) * N3, hipMemcpyDeviceToHost, c->stream));
+    if (w) HIP_TRY(c, hipMemcpyAsync(w, tab + N3 * N3 + N3, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    if (N || e || w) HIP_TRY(c, hipStreamSynchronize(c->stream));
+    J.cur = other;
+    J.n = n;
+    return n;
+  } SGO_CATCH(c)
+}
 
 int sgo_joint_subsets(sgo_ctx* c, int32_t n, int32_t B, const uint8_t* subset, const double* chi2_max, double* d2, int32_t* dof, uint8_t* pass) {
   try {

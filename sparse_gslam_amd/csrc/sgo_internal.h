@@ -387,6 +387,8 @@ enum KernelId : int {
   K_MFRONT_BATCH,       // sgo_optimize_gn_hypotheses' batched route on the multifrontal path: all launches of one chain (sgo_mfront.h)
   K_LOO_EDGES,          // sgo_edge_leave_one_out: the edge kernel after sgo_marginals_selected's two phases (sgo_loo.hip)
   K_JOINT_GROW,         // sgo_joint_greedy / sgo_joint_extend: one launch per slice of seeds (sgo_jsearch.hip)
+  K_EDGE_TABLE,         // sgo_edge_joint / sgo_edge_groups: the resident-edge table's own kernels (sgo_egroup.hip)
+  K_EDGE_GROUPS,
   K_COUNT
 };
 extern const char* const kKernelNames[K_COUNT];

@@ -249,4 +249,21 @@ struct JointGrowDev {
 };
 void launch_joint_grow(hipStream_t s, const JointGrowDev& A, int count);   // seeds A.b0 .. A.b0 + count, count <= the slice
 
+// ---- the resident-edge table and its groups (sgo_edge_joint / sgo_edge_groups; kernels in sgo_egroup.hip, drivers in sgo_fsolve.cpp
+// and sgo_egroup.cpp) ----
+// The table: N [3 n][3 n] row-major, e [n][3], w [n], Omega's upper triangle [n][6], then one double: the factorisation's failure flag
+inline size_t edge_table_doubles(int n) { return 9 * (size_t)n * n + 10 * (size_t)n + 1; }
+constexpr int kEgOut = 4;   // per-group result: d2, pivot, dof, the decision
+// The listed resident edges as candidates' records, filled on the device: endpoints, rows (vrow[v]: vertex v's place in a
+// right-hand side, -1 for a fixed one), inverse measurement and information in C's arrays (stride C.n), the kernel weights in w
+void launch_edge_cands(hipStream_t s, const FsCandDev& C, const EdgeListDev& el, const int* ids, const int* vrow, const double* poses, int* vi, int* vj,
+                       int* row, double* zinv, double* info, double* w);
+// table = N (G symmetrised, one triangle computed and mirrored), e, w, Omega, the failure flag (flags == nullptr: 0)
+void launch_edge_table(hipStream_t s, const FsCandDev& C, const double* w, const double* G, const int* flags, double* table);
+// `count` groups of the table of n edges, one workgroup each: member rows mask [count][n]; out [count][kEgOut].  kmax: the members
+// the dynamic LDS holds.
+void launch_edge_groups(hipStream_t s, const double* table, int n, const uint8_t* mask, const double* chi2_max, double min_pivot, int count, int kmax,
+                        double* out);
+bool edge_groups_prepare_device();   // the group kernel's dynamic LDS
+
 }  // namespace sgo

@@ -142,6 +142,158 @@ SGO_RULE_HD inline int edge_loo(const double* info, const double* P, const doubl
   return 0;
 }
 
+// The leave-group-out rule of sgo_edge_groups: sgo_edge_leave_one_out's question about k resident edges
+// removed together, from the rows idx[0 .. k) of a resident-edge table: N (symmetric, leading dimension ld; block (s, t) at
+// N[(3 idx[s] + a) ld + 3 idx[t] + b]) = 1/2 (Q + Q^T) with Q = J H^-1 J^T, e (3 per row), w (the kernel weights) and info6 (Omega's
+// upper triangle by rows, 6 per row).  With Omega_t = G_t G_t^T (lower Cholesky), G = blockdiag(G_t), Nt = G^T N G, c = G^T e,
+// D = blockdiag(w_t I3), T = D^1/2:
+//   pivot = the smallest pivot of the Cholesky factorisation of I - T Nt T (the smallest squared diagonal entry of its factor; the
+//           factorisation stops at the first pivot that is not above zero, which is then the answer)
+//   K     = I + Nt - D Nt - Nt D - Nt D (I - D) Nt,   d2 = c^T K^-1 c by a Cholesky of K that carries c along as its last row
+// d2 is NaN where pivot is not above zero, where K is not positive definite and where an Omega_t is not (pivot NaN too).  k = 0:
+// d2 = 0, pivot = 1.  The caller leaves all-zero informations out of idx and decides what a small pivot means.
+// The text is written for a square of ns x ns workers (ty, tx) that meet at sync(): the host runs it as one worker (ns = 1, a sync
+// that does nothing), k_edge_groups as 16 x 16 threads of a workgroup with ws in LDS.  Every element of every stage is computed by
+// ONE worker with its sums in ascending order, so the result does not depend on ns.  ns: a power of two.  ws: edge_group_ws_doubles(k)
+// doubles -- two packed lower triangles (Nt: 3 k rows; the factorised matrix: 3 k + 1 rows, c the last), the G_t, w, sqrt(w) and
+// the squares whose sum is d2.  d2 and pivot are written by worker (0, 0) alone.  `double`, comparisons and sqrt only.
+struct EdgeGroupNoSync {
+  void operator()() const {}
+};
+SGO_RULE_HD inline std::size_t edge_group_tri(int i, int j) { return (std::size_t)i * (std::size_t)(i + 1) / 2 + (std::size_t)j; }   // j <= i
+SGO_RULE_HD inline std::size_t edge_group_ws_doubles(int k) {
+  const int m = 3 * k;
+  return edge_group_tri(m, 0) + edge_group_tri(m + 1, 0) + 8 * (std::size_t)k + (std::size_t)m;
+}
+template <class Sync>
+SGO_RULE_HD inline void edge_group(int k, const int* idx, const double* N, std::size_t ld, const double* e, const double* w, const double* info6,
+                                   double* ws, int ty, int tx, int ns, Sync&& sync, double* d2, double* pivot) {
+  const int m = 3 * k, lin = ty * ns + tx, nt = ns * ns;
+  if (k == 0) {
+    if (lin == 0) {
+      *d2 = 0.0;
+      *pivot = 1.0;
+    }
+    return;
+  }
+  double* A = ws;                            // Nt, packed lower
+  double* Bm = A + edge_group_tri(m, 0);     // I - T Nt T, then K; row m: c
+  double* g = Bm + edge_group_tri(m + 1, 0); // [k][6] g00 g10 g11 g20 g21 g22
+  double* wv = g + 6 * (std::size_t)k;
+  double* sw = wv + k;
+  double* zz = sw + k;
+  for (int t = lin; t < k; t += nt) {
+    const double* o = info6 + 6 * (std::size_t)idx[t];
+    const double o00 = o[0], o01 = o[1], o02 = o[2], o11 = o[3], o12 = o[4], o22 = o[5];
+    double g00 = sqrt(o00), g10 = o01 / g00, g20 = o02 / g00;
+    const double t11 = o11 - g10 * g10;
+    double g11 = sqrt(t11), g21 = (o12 - g20 * g10) / g11;
+    const double t22 = o22 - g20 * g20 - g21 * g21;
+    double g22 = sqrt(t22);
+    if (!(o00 > 0.0) || !(t11 > 0.0) || !(t22 > 0.0) || !(g22 - g22 == 0.0)) g00 = g10 = g20 = g11 = g21 = g22 = sqrt(-1.0);
+    double* gt = g + 6 * (std::size_t)t;
+    gt[0] = g00, gt[1] = g10, gt[2] = g11, gt[3] = g20, gt[4] = g21, gt[5] = g22;
+    wv[t] = w[idx[t]];
+    sw[t] = sqrt(wv[t]);
+  }
+  sync();
+  // Nt's blocks (s, t), t <= s: G_s^T N_st G_t; the diagonal block's worker adds c_s = G_s^T e_s
+  for (int s = ty; s < k; s += ns)
+    for (int t = tx; t <= s; t += ns) {
+      const double* gs = g + 6 * (std::size_t)s;
+      const double* gt = g + 6 * (std::size_t)t;
+      const double Gs[3][3] = {{gs[0], 0.0, 0.0}, {gs[1], gs[2], 0.0}, {gs[3], gs[4], gs[5]}};
+      const double Gt[3][3] = {{gt[0], 0.0, 0.0}, {gt[1], gt[2], 0.0}, {gt[3], gt[4], gt[5]}};
+      const double* Nb = N + 3 * (std::size_t)idx[s] * ld + 3 * (std::size_t)idx[t];
+      double X[3][3];
+      for (int a = 0; a < 3; ++a) {
+        const double n0 = Nb[a * ld], n1 = Nb[a * ld + 1], n2 = Nb[a * ld + 2];
+        X[a][0] = n0 * Gt[0][0] + n1 * Gt[1][0] + n2 * Gt[2][0];
+        X[a][1] = n1 * Gt[1][1] + n2 * Gt[2][1];
+        X[a][2] = n2 * Gt[2][2];
+      }
+      for (int b = 0; b < 3; ++b) {
+        const double y0 = Gs[0][0] * X[0][b] + Gs[1][0] * X[1][b] + Gs[2][0] * X[2][b];
+        const double y1 = Gs[1][1] * X[1][b] + Gs[2][1] * X[2][b];
+        const double y2 = Gs[2][2] * X[2][b];
+        if (s > t || b <= 0) A[edge_group_tri(3 * s, 3 * t + b)] = y0;
+        if (s > t || b <= 1) A[edge_group_tri(3 * s + 1, 3 * t + b)] = y1;
+        A[edge_group_tri(3 * s + 2, 3 * t + b)] = y2;
+      }
+      if (s == t) {
+        const double* es = e + 3 * (std::size_t)idx[s];
+        Bm[edge_group_tri(m, 3 * s)] = Gs[0][0] * es[0] + Gs[1][0] * es[1] + Gs[2][0] * es[2];
+        Bm[edge_group_tri(m, 3 * s + 1)] = Gs[1][1] * es[1] + Gs[2][1] * es[2];
+        Bm[edge_group_tri(m, 3 * s + 2)] = Gs[2][2] * es[2];
+      }
+    }
+  sync();
+  for (int i = ty; i < m; i += ns)
+    for (int j = tx; j <= i; j += ns) Bm[edge_group_tri(i, j)] = (i == j ? 1.0 : 0.0) - sw[i / 3] * A[edge_group_tri(i, j)] * sw[j / 3];
+  sync();
+  // the pivots of I - T Nt T: a right-looking Cholesky whose column kk stays unscaled (every worker takes 1 / sqrt(a_kk) itself);
+  // element (i, j) is its own worker's, updated in ascending kk
+  double piv = 1.0;
+  for (int kk = 0; kk < m; ++kk) {
+    const double akk = Bm[edge_group_tri(kk, kk)];
+    if (!(akk >= piv)) piv = akk;
+    if (!(akk > 0.0)) break;   // (every worker reads the same a_kk: they leave together)
+    const double r = 1.0 / sqrt(akk);
+    const int i0 = kk + 1 + ((ty - (kk + 1)) & (ns - 1)), j0 = kk + 1 + ((tx - (kk + 1)) & (ns - 1));
+    for (int i = i0; i < m; i += ns) {
+      const double li = Bm[edge_group_tri(i, kk)] * r;
+      for (int j = j0; j <= i; j += ns) Bm[edge_group_tri(i, j)] -= li * (Bm[edge_group_tri(j, kk)] * r);
+    }
+    sync();
+  }
+  sync();
+  if (!(piv > 0.0)) {
+    if (lin == 0) {
+      *d2 = sqrt(-1.0);
+      *pivot = piv;
+    }
+    return;
+  }
+  // K; the product Nt D (I - D) Nt is skipped where every w (1 - w) is zero (it would add zeros)
+  bool frac = false;
+  for (int t = 0; t < k; ++t) frac = frac || wv[t] * (1.0 - wv[t]) != 0.0;
+  for (int i = ty; i < m; i += ns)
+    for (int j = tx; j <= i; j += ns) {
+      double sum = 0.0;
+      if (frac)
+        for (int l = 0; l < m; ++l) {
+          const double ail = l <= i ? A[edge_group_tri(i, l)] : A[edge_group_tri(l, i)];
+          const double alj = j <= l ? A[edge_group_tri(l, j)] : A[edge_group_tri(j, l)];
+          sum += ail * (wv[l / 3] * (1.0 - wv[l / 3])) * alj;
+        }
+      Bm[edge_group_tri(i, j)] = ((i == j ? 1.0 : 0.0) + A[edge_group_tri(i, j)] * ((1.0 - wv[i / 3]) - wv[j / 3])) - sum;
+    }
+  sync();
+  // K = L L^T with c carried along as row m: after step kk row m holds c - L[:, :kk] z[:kk]
+  for (int kk = 0; kk < m; ++kk) {
+    const double akk = Bm[edge_group_tri(kk, kk)];
+    const double r = akk > 0.0 ? 1.0 / sqrt(akk) : sqrt(-1.0);
+    const int i0 = kk + 1 + ((ty - (kk + 1)) & (ns - 1)), j0 = kk + 1 + ((tx - (kk + 1)) & (ns - 1));
+    for (int i = i0; i <= m; i += ns) {
+      const double li = Bm[edge_group_tri(i, kk)] * r;
+      for (int j = j0; j <= i && j < m; j += ns) Bm[edge_group_tri(i, j)] -= li * (Bm[edge_group_tri(j, kk)] * r);
+    }
+    sync();
+  }
+  for (int t = lin; t < m; t += nt) {
+    const double akk = Bm[edge_group_tri(t, t)];
+    const double z = Bm[edge_group_tri(m, t)] * (akk > 0.0 ? 1.0 / sqrt(akk) : sqrt(-1.0));
+    zz[t] = z * z;
+  }
+  sync();
+  if (lin == 0) {
+    double sum = 0.0;
+    for (int t = 0; t < m; ++t) sum += zz[t];
+    *d2 = sum;
+    *pivot = piv;
+  }
+}
+
 // The 3 x 3 pieces of sgo_joint_greedy's block-pivoted Cholesky.  A candidate c keeps C_c = S_cc - W_c^T W_c
 // as its lower triangle C6 = [c00 c10 c11 c20 c21 c22] and q_c = e_c - W_c^T z.  `double`, comparisons and sqrt only: the host
 // (sgo_joint_greedy_rule) and k_joint_grow compile this text.

@@ -104,6 +104,7 @@ void free_graph(sgo_ctx* c) {
   c->selinv.tried = false;
   c->selinv.why.clear();
   c->joint.n = -1;
+  c->ejoint.n = -1;
   c->amg_pending = false;
   c->order_xy.clear();
   c->rows_pending = false;
