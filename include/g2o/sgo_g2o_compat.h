@@ -930,6 +930,7 @@ class SparseOptimizer : public OptimizableGraph {
     bool anyFree = false;
     for (auto* v : _activeVertices) anyFree = anyFree || !v->fixed();
     if (_activeVertices.empty() || !anyFree) return -1;
+    if (levenbergOnDevice()) return deviceLevenberg(iterations);
     if (!gpuEligible()) return hostOptimize(iterations, online);
     if (!uploadGraph()) return 0;
     sgo_stats* st = new sgo_stats();
@@ -1595,7 +1596,7 @@ class SparseOptimizer : public OptimizableGraph {
     // Gauss-Newton) is refused instead of being solved in O(n^3) on the host.
     if (n > kHostSolverMaxUnknowns) {
       std::cerr << "SparseOptimizer::optimize: " << n << " unknowns in a graph the device path does not cover "
-                << "(only VertexSE2 / EdgeSE2 with no kernel or a kernel of robust_kernel_impl.h under Gauss-Newton is); refusing"
+                << "(only VertexSE2 / EdgeSE2 with no kernel or a kernel of robust_kernel_impl.h is); refusing"
                 << std::endl;
       return 0;
     }
@@ -1680,8 +1681,52 @@ class SparseOptimizer : public OptimizableGraph {
   std::vector<LmIteration> _lmTrace;
   static constexpr int kHostSolverMaxUnknowns = 3000;
 
-  bool gpuEligible() const {
-    if (_algorithm->kind() != OptimizationAlgorithm::GaussNewton) return false;
+  // Levenberg-Marquardt on a pose graph the dense host solver refuses for its size (more than kHostSolverMaxUnknowns unknowns): the
+  // library's sgo_optimize_lm -- g2o's schedule on the multifrontal factor -- with the marshalling of the Gauss-Newton route.
+  // Everything the host solver solves stays there.
+  bool levenbergOnDevice() const {
+    if (_algorithm->kind() != OptimizationAlgorithm::Levenberg || !deviceTypes()) return false;
+    int n = 0;
+    for (auto* v : _activeVertices) n += v->fixed() ? 0 : v->dimension();
+    return n > kHostSolverMaxUnknowns;
+  }
+  // Returns the iterations counted, as the host solver does; _lmTrace is the call's trace (lambda and robust chi2 after every
+  // iteration, its trials).  0 with one line on std::cerr when a terminate action is registered (the decisions are taken on the
+  // device, which knows g2o's own termination only) and when the multifrontal analysis refuses the graph.
+  int deviceLevenberg(int iterations) {
+    _lmTrace.clear();
+    if (_terminateAction) {
+      std::cerr << "SparseOptimizer::optimize: a graph of this size under Levenberg-Marquardt takes sgo_optimize_lm, which applies no "
+                << "SparseOptimizerTerminateAction (remove the action, or use Gauss-Newton, whose device path applies it); refusing" << std::endl;
+      return 0;
+    }
+    if (!uploadGraph()) return 0;
+    // sgo_optimize_lm refuses a graph that carries an incremental overlay (a PCG context whose graph grew under Gauss-Newton, now
+    // or in an earlier call): this route gives such a graph the full set-up
+    if (std::strstr(sgo_solver_description(_ctx), "incremental overlay")) {
+      _graphOnDevice = false;
+      if (!uploadGraph()) return 0;
+    }
+    _lastStats.reset();   // (lastStats() is the last Gauss-Newton call's: none now)
+    std::unique_ptr<sgo_lm_stats> st(new sgo_lm_stats());
+    const int done = sgo_optimize_lm(_ctx, iterations, 0.0, st.get());
+    if (done < 0) {
+      std::cerr << "SparseOptimizer::optimize: " << sgo_last_error(_ctx) << (done == SGO_ENOTHING ? "; refusing" : "") << std::endl;
+      return 0;
+    }
+    for (int k = 0; k < st->iters_done; ++k) _lmTrace.push_back({st->lambda[k], st->robust_chi2[k + 1], st->trials[k]});
+    if (st->iters_done > 0) _lmLambda = st->lambda[st->iters_done - 1];
+    if (_verbose)
+      for (int k = 0; k < st->iters_done; ++k)
+        std::cerr << "iteration= " << k << "\t chi2= " << st->chi2[k + 1] << "\t lambda= " << st->lambda[k] << "\t trials= " << st->trials[k]
+                  << std::endl;
+    downloadEstimates();
+    return done;
+  }
+
+  bool gpuEligible() const { return _algorithm->kind() == OptimizationAlgorithm::GaussNewton && deviceTypes(); }
+  // every active vertex a VertexSE2 and every active edge an EdgeSE2 whose kernel, if any, the device evaluates
+  bool deviceTypes() const {
     for (auto* v : _activeVertices)
       if (typeid(*v) != typeid(VertexSE2)) return false;
     for (auto* e : _activeEdges) {

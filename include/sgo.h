@@ -239,6 +239,49 @@ int sgo_gain_stop(double last_robust_chi2, double robust_chi2, double gain_tol);
 #define SGO_STOP_FAILED 2
 int sgo_optimize_gn_until(sgo_ctx* ctx, int32_t max_iters, double gain_tol, sgo_stats* out, int32_t* stop_reason);
 
+/* (later additions, version 107) Levenberg-Marquardt on the multifrontal factor.
+ * Replaces: SparseOptimizer::optimize(iters) with OptimizationAlgorithmLevenberg on a pose-only SE(2) graph, with g2o 2020.5.29's
+ * schedule.  lambda_0 = lambda_init, or 1e-5 * max |diag(H)| at the starting poses when lambda_init <= 0, is set at iteration 0 of
+ * every call, and nu = 2.  One trial solves (H + lambda I) x = b -- H and b the robustified system of every kernel kind at the
+ * accepted poses -- and scores the poses (+) x by
+ *     scale = x . (lambda x + b) + 1e-3,   rho = (robust chi2 at the accepted poses - robust chi2 at the trial poses) / scale.
+ * It is accepted iff rho > 0, the trial chi2 is finite and the solve succeeded: lambda *= max(1/3, min(2/3, 1 - (2 rho - 1)^3)),
+ * nu = 2, the trial poses become the accepted ones.  Otherwise lambda *= nu, nu *= 2; a pivot that is not positive definite or a
+ * non-finite solution is such a rejection, not a failed call.  An iteration repeats trials while rho < 0 and fewer than ten have
+ * run; the call terminates after ten trials of one iteration, at rho == 0 exactly, or when lambda is no longer finite (that last
+ * trial is counted).
+ *
+ * sgo_lm_trial_rule is that rule for one trial as the library and its kernel compile it (no context, no GPU): `scale` includes the
+ * 1e-3; *lambda and *nu are updated in place.  Returns 1: accepted; 0: rejected with rho < 0 (the iteration tries again); 2:
+ * rejected with rho == 0; 3: rejected otherwise (rho is NaN, or positive with a non-finite trial chi2) -- the iteration ends.
+ *
+ * The solves go through the multifrontal factor: the resident plan on a multifrontal_cholesky context, otherwise a plan analysed once
+ * per set-up (as sgo_marginals_selected does), whatever path sgo_optimize_gn takes.  The trials and their decisions run on the
+ * device; the host reads the state once per round of queued trials (out->sync_rounds: 1 for a call without a rejection, at most
+ * 1 + the rejected trials).  Two calls from the same state return the same bits.
+ * Returns the iterations counted (out->iters_done; `out` may be NULL).  robust_chi2[k + 1], chi2[k + 1] and lambda[k] are the values
+ * at the accepted poses after iteration k, trials[k] its trials; robust_chi2[] never increases, and the entries [iters_done] are
+ * what sgo_chi2 returns after the call, bit for bit.  Afterwards the context is as after sgo_set_poses(the final poses):
+ * sgo_optimize_gn keeps its path and its bits, and the joint tables stay the snapshots they are.
+ * SGO_EINVAL, with nothing changed: max_iters outside [0, SGO_MAX_ITERS], a lambda_init that is not finite, an active incremental
+ * overlay, a multi-GPU context (sgo_debug_set_shard's emulation included).  SGO_ENOTHING when there is no free active vertex, and,
+ * with the analysis' reason in sgo_last_error, when the multifrontal analysis refuses the graph: use sgo_optimize_gn then. */
+#define SGO_LM_STOP_MAX_ITERS 0   /* max_iters iterations counted */
+#define SGO_LM_STOP_TRIALS    1   /* ten trials of one iteration rejected (g2o: Terminate) */
+#define SGO_LM_STOP_ZERO_GAIN 2   /* rho == 0 exactly */
+#define SGO_LM_STOP_LAMBDA    3   /* lambda no longer finite */
+typedef struct sgo_lm_stats {
+  int32_t iters_requested, iters_done, trials_total, stop_reason, sync_rounds;
+  double  lambda0;
+  double  lambda[SGO_MAX_ITERS];          /* after iteration k */
+  double  robust_chi2[SGO_MAX_ITERS + 1]; /* [0] at the start, [k+1] at the accepted poses after iteration k */
+  double  chi2[SGO_MAX_ITERS + 1];        /* plain chi2, same indexing */
+  int32_t trials[SGO_MAX_ITERS];
+  double  seconds_total;
+} sgo_lm_stats;
+int sgo_optimize_lm(sgo_ctx* ctx, int32_t max_iters, double lambda_init /* <= 0: 1e-5 * max diag(H) */, sgo_lm_stats* out);
+int sgo_lm_trial_rule(double cur, double trial, double scale, int solve_ok, double* lambda, double* nu); /* pure, no GPU */
+
 /* (later additions, version 107) Many closure hypotheses of the resident graph in one call: "is this set of
  * closures consistent", leave-one-out over a round's closures, cluster tests -- the same graph optimised once per hypothesis.
  *

@@ -40,6 +40,7 @@ SYMBOLS = [
     "sgo_joint_greedy", "sgo_joint_extend", "sgo_joint_greedy_rule",
     "sgo_edge_joint", "sgo_edge_groups", "sgo_edge_group_rule",
     "sgo_set_hypotheses_workspace", "sgo_hypotheses_bytes", "sgo_hypotheses_chunk", "sgo_hypotheses_workspace_bytes",
+    "sgo_optimize_lm", "sgo_lm_trial_rule",
 ]
 
 # SGO_JOINT_MAX_*: the limits of sgo_candidate_joint's table and of a subset of it
@@ -47,6 +48,11 @@ JOINT_MAX_CANDIDATES, JOINT_MAX_SUBSET = 256, 40
 
 # SGO_STOP_*: why sgo_optimize_gn_until ended
 STOP_MAX_ITERS, STOP_GAIN, STOP_FAILED = 0, 1, 2
+
+# SGO_LM_STOP_*: why sgo_optimize_lm ended
+LM_STOP_MAX_ITERS, LM_STOP_TRIALS, LM_STOP_ZERO_GAIN, LM_STOP_LAMBDA = 0, 1, 2, 3
+# what sgo_lm_trial_rule returns
+LM_RETRY, LM_ACCEPT, LM_ZERO_GAIN, LM_END = 0, 1, 2, 3
 
 # SGO_HYP_*: the route sgo_optimize_gn_hypotheses took
 HYP_BATCHED, HYP_SEQUENTIAL = 1, 2
@@ -63,6 +69,14 @@ class SgoError(RuntimeError):
 def gain_stop(last_robust_chi2: float, robust_chi2: float, gain_tol: float) -> bool:
     """sgo_gain_stop: the rule sgo_optimize_gn_until stops by, as the library computes it (no context, no GPU)."""
     return bool(lib().sgo_gain_stop(last_robust_chi2, robust_chi2, gain_tol))
+
+
+def lm_trial_rule(cur: float, trial: float, scale: float, solve_ok: bool, lam: float, nu: float):
+    """sgo_lm_trial_rule: one trial of sgo_optimize_lm as the library (and its kernel) computes it, no context and no GPU: the robust
+    chi2 at the accepted and at the trial poses, scale = x . (lambda x + b) + 1e-3 -> (one of LM_*, lambda, nu after the trial)."""
+    a, b = C.c_double(lam), C.c_double(nu)
+    code = lib().sgo_lm_trial_rule(cur, trial, scale, int(bool(solve_ok)), C.byref(a), C.byref(b))
+    return code, a.value, b.value
 
 
 def edge_loo_rule(info6, P, e, w: float):
@@ -158,6 +172,17 @@ class Stats(C.Structure):
                 ("seconds_total", C.c_double), ("seconds_setup", C.c_double)]
 
 
+class LmStats(C.Structure):
+    """sgo_lm_stats (include/sgo.h)."""
+    _fields_ = [("iters_requested", C.c_int32), ("iters_done", C.c_int32), ("trials_total", C.c_int32), ("stop_reason", C.c_int32),
+                ("sync_rounds", C.c_int32), ("lambda0", C.c_double),
+                ("lam", C.c_double * SGO_MAX_ITERS),
+                ("robust_chi2", C.c_double * (SGO_MAX_ITERS + 1)),
+                ("chi2", C.c_double * (SGO_MAX_ITERS + 1)),
+                ("trials", C.c_int32 * SGO_MAX_ITERS),
+                ("seconds_total", C.c_double)]
+
+
 class HypothesisResult(C.Structure):
     """sgo_hypothesis_result (include/sgo.h)."""
     _fields_ = [("iters_done", C.c_int32), ("stop_reason", C.c_int32), ("chi2", C.c_double), ("robust_chi2", C.c_double)]
@@ -241,6 +266,8 @@ def lib():
     L.sgo_optimize_gn.argtypes = [vp, C.c_int32, C.POINTER(Stats)]
     L.sgo_optimize_gn_until.argtypes = [vp, C.c_int32, C.c_double, C.POINTER(Stats), i32]
     L.sgo_gain_stop.argtypes = [C.c_double, C.c_double, C.c_double]
+    L.sgo_optimize_lm.argtypes = [vp, C.c_int32, C.c_double, C.POINTER(LmStats)]
+    L.sgo_lm_trial_rule.argtypes = [C.c_double, C.c_double, C.c_double, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.sgo_optimize_gn_hypotheses.argtypes = [vp, C.c_int32, C.c_int32, C.c_double, u8, d, C.POINTER(HypothesisResult), d, d, d]
     L.sgo_hypothesis_isolated_vertex.restype = C.c_int32
     L.sgo_set_hypotheses_workspace.argtypes = [vp, C.c_int64]
@@ -635,6 +662,17 @@ class Optimizer:
         why = C.c_int32(-1)
         rc = self._check(lib().sgo_optimize_gn_until(self._h, max_iters, gain_tol, C.byref(st), C.byref(why)), "sgo_optimize_gn_until")
         return rc, self._stats_dict(rc, st, max_iters), why.value
+
+    def optimize_lm(self, max_iters: int = 20, lambda_init: float = 0.0):
+        """sgo_optimize_lm: Levenberg-Marquardt with g2o's schedule on the multifrontal factor -> (iterations counted, or -1 when the
+        analysis refuses the graph (last_error() has the reason); stats dict: lambda0, lambda / trials per iteration, robust_chi2 /
+        chi2 at the start and after every iteration, trials_total, stop_reason (one of LM_STOP_*), sync_rounds)."""
+        st = LmStats()
+        rc = self._check(lib().sgo_optimize_lm(self._h, max_iters, lambda_init, C.byref(st)), "sgo_optimize_lm")
+        d = max(st.iters_done, 0)
+        return rc, dict(rc=rc, iters_done=st.iters_done, trials_total=st.trials_total, stop_reason=st.stop_reason,
+                        sync_rounds=st.sync_rounds, lambda0=st.lambda0, lam=list(st.lam[:d]), trials=list(st.trials[:d]),
+                        robust_chi2=list(st.robust_chi2[: d + 1]), chi2=list(st.chi2[: d + 1]), seconds_total=st.seconds_total)
 
     def set_hypotheses_workspace(self, max_bytes: int) -> None:
         """sgo_set_hypotheses_workspace: the device memory optimize_hypotheses may take for per-hypothesis copies on a

@@ -385,6 +385,9 @@ void sgo_destroy(sgo_ctx* c) {
   if (c->selinv.d_cidx) hipFree(c->selinv.d_cidx);
   if (c->selinv.d_loo) hipFree(c->selinv.d_loo);
   if (c->selinv.d_loo_ids) hipFree(c->selinv.d_loo_ids);
+  if (c->lm.d_trial) hipFree(c->lm.d_trial);
+  if (c->lm.d_scratch) hipFree(c->lm.d_scratch);
+  if (c->lm.d_state) hipFree(c->lm.d_state);
   for (void* p : {(void*)c->joint.d_tab[0], (void*)c->joint.d_tab[1], (void*)c->joint.d_raw, (void*)c->joint.d_d2, (void*)c->joint.d_mask,
                   (void*)c->joint.d_grow, (void*)c->joint.d_gout, (void*)c->joint.d_gint, (void*)c->ejoint.d_tab[0], (void*)c->ejoint.d_tab[1],
                   (void*)c->ejoint.d_out, (void*)c->ejoint.d_mask})

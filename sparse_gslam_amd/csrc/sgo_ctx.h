@@ -295,6 +295,15 @@ struct sgo_ctx {
     size_t loo_cap = 0, loo_ids_cap = 0;
   } selinv;
 
+  // sgo_optimize_lm (sgo_lm.cpp): the trial poses [V][3], the call's scratch (sgo_lm.h: kLmScratchDoubles) and the device state;
+  // grown on demand, kept across graphs
+  struct Lm {
+    double* d_trial = nullptr;
+    double* d_scratch = nullptr;
+    sgo::LmState* d_state = nullptr;
+    size_t trial_cap = 0, scratch_cap = 0, state_cap = 0;
+  } lm;
+
   // sgo_candidate_joint's table (sgo_fsolve.cpp): S [3 n][3 n], e [n][3] and the failure flag in tab[cur]; a call builds in the
   // other buffer and switches when it has succeeded, so a refusal or a failure keeps the resident table.  n < 0: no table.
   struct Joint {

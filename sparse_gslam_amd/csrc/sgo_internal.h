@@ -389,6 +389,7 @@ enum KernelId : int {
   K_JOINT_GROW,         // sgo_joint_greedy / sgo_joint_extend: one launch per slice of seeds (sgo_jsearch.hip)
   K_EDGE_TABLE,         // sgo_edge_joint / sgo_edge_groups: the resident-edge table's own kernels (sgo_egroup.hip)
   K_EDGE_GROUPS,
+  K_LM,                 // sgo_optimize_lm: all launches of one call (sgo_lm.h)
   K_COUNT
 };
 extern const char* const kKernelNames[K_COUNT];

@@ -144,6 +144,12 @@ hipError_t mfront_optimize_batch(Mfront* m, hipStream_t s, const EdgeListDev& el
 // The factor phase of one iteration alone, at the current poses: edges (elements, chi2 partials), then merge and panels per level --
 // mfront_optimize's own launches up to and excluding the substitution and the update.  Clears the failure flags first; x is untouched.
 hipError_t mfront_factorize(Mfront* m, hipStream_t s, const EdgeListDev& el, const double* d_poses, double* d_hist, DirectResult* d_res);
+// sgo_optimize_lm's two shares of one attempt (sgo_lm.h): k_mf_edges at the accepted poses (elements; d_hist / d_res: scratch), and
+// merge, panels and substitution per level for (H + lambda I) x = b with lambda read from *st on the device.  Both obey the flags
+// word and neither clears it.
+struct LmState;
+void mfront_lm_edges(Mfront* m, hipStream_t s, const EdgeListDev& el, const double* d_poses, double* d_hist, DirectResult* d_res);
+void mfront_lm_solve(Mfront* m, hipStream_t s, const LmState* st, double* d_hist, DirectResult* d_res);
 // Test hook (sgo_debug_mfront_array): one resident array as stored after the last mfront_optimize or selected inversion;
 // SGO_ENOTHING before the first (SGO_MF_SEL: 0 bytes before the first selected inversion; SGO_MF_FS_Y / _X: before the first
 // multi-right-hand-side substitution).

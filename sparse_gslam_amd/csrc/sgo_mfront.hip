@@ -26,6 +26,7 @@
 
 #include "sgo_device.h"
 #include "sgo_internal.h"
+#include "sgo_lm.h"
 #include "sgo_mfront.h"
 #include "sgo_mfront_dev.h"
 #include "sgo_rules.h"
@@ -235,9 +236,16 @@ __global__ __launch_bounds__(kBlock) void k_mf_merge(MfDev M, int t0, int t1, st
 //   D2  the 16 x 16 Cholesky on wave 0 and the inverse of its factor on wave 1, one pivot behind (rows on the lanes, columns in
 //       registers, broadcasts by v_readlane; wave 0 hands every finished column and pivot to wave 1 through LDS);
 //   D3  L21 = P21 L11^-T on the matrix cores, refined once against L11, straight to the front's matrix.
-template <bool BATCH>
+// LM (sgo_optimize_lm, unbatched; sgo_lm.h): lambda of the device state is added once to the diagonal entries of the front's own
+// poses, after the edges' contributions -- the factor is that of H + lambda I.  The instantiations without it have no such code.
+struct MfLm {
+  const LmState* st;
+};
+template <bool BATCH, bool LM = false>
 __global__ __launch_bounds__(kMfThreads) void k_mf_panels(MfDev M, int lvl0, int it, int stamp_slot, int nparts, double* __restrict__ hist,
-                                                         DirectResult* __restrict__ res, std::conditional_t<BATCH, MfBatch, MfSingle> bt) {
+                                                         DirectResult* __restrict__ res,
+                                                         std::conditional_t<LM, MfLm, std::conditional_t<BATCH, MfBatch, MfSingle>> bt) {
+  static_assert(!(BATCH && LM), "sgo_optimize_lm is not batched");
   if constexpr (BATCH) mf_slice<double*>(bt, M, nullptr, nullptr, &hist, &res);
   extern __shared__ double Pn[];               // panel: column c at Pn + c * ldp, rows relative to k0 
   __shared__ double Yt[kMfPanel * kMfPanel];   // Yt[t * 16 + c] = (L11^-1)[c][t]
@@ -328,6 +336,11 @@ __global__ __launch_bounds__(kMfThreads) void k_mf_panels(MfDev M, int lvl0, int
     }
   }
   __syncthreads();
+  if constexpr (LM) {
+    const double lam = bt.st->lambda;
+    for (int p = tid; p < s3; p += kMfThreads) A[(size_t)p * ld + p] += lam;
+    __syncthreads();
+  }
   lapse(1);
   // D2: the 16 x 16 diagonal block of the panel at Pd (columns k0 .. k0 + wp): Cholesky on wave 0, the inverse of the factor on
   // wave 1, one pivot behind; L11 goes to the front's matrix, the inverse to Yt, the pivots' reciprocals to M.invd
@@ -697,6 +710,7 @@ __global__ __launch_bounds__(64) void k_mf_finish(MfDev M, int iters, int nparts
 // The value flags[0] takes when the gain rule ends the call: every later launch returns on it as on a failure's 1 or 2, and
 // k_mf_finish_until puts 0 back, so that FLAGS reads as after the plain call of as many iterations.
 constexpr int kMfStopped = 3;
+static_assert(kLmStopWord == kMfStopped, "sgo_optimize_lm's launches return on the same stop word");
 
 // One wave, between k_mf_edges and the first level's k_mf_panels of iteration `it` (2 <= it < iters): chi2 of this iteration from
 // the partial sums in mf_chi2_sum's order -- the bits the panel kernel would write --, then rules::gain_stop against the iteration
@@ -925,6 +939,7 @@ Mfront* mfront_create(hipStream_t s, DevArena* arena, int V, int n, const int* f
   if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_mf_panels<false>), hipFuncAttributeMaxDynamicSharedMemorySize, kPanelLds) != hipSuccess ||
       hipFuncSetAttribute(reinterpret_cast<const void*>(&k_mf_solve<false>), hipFuncAttributeMaxDynamicSharedMemorySize, kSolveLds) != hipSuccess ||
       hipFuncSetAttribute(reinterpret_cast<const void*>(&k_mf_panels<true>), hipFuncAttributeMaxDynamicSharedMemorySize, kPanelLds) != hipSuccess ||
+      hipFuncSetAttribute(reinterpret_cast<const void*>(&k_mf_panels<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, kPanelLds) != hipSuccess ||
       hipFuncSetAttribute(reinterpret_cast<const void*>(&k_mf_solve<true>), hipFuncAttributeMaxDynamicSharedMemorySize, kSolveLds) != hipSuccess) {
     (void)hipGetLastError();
     if (why) *why = "the device does not grant the kernels' dynamic LDS";
@@ -1117,6 +1132,36 @@ hipError_t mfront_factorize(Mfront* m, hipStream_t s, const EdgeListDev& el, con
                        h == 0 ? egrid : 0, d_hist, d_res, MfSingle{});
   }
   return hipGetLastError();
+}
+
+// sgo_optimize_lm's share of one attempt (sgo_lm.h): the elements at the accepted poses -- mfront_factorize's k_mf_edges launch; its
+// partial sums are not used --, and the factorisation of H + lambda I with the substitution: mfront_optimize's launches per level
+// with k_mf_panels' LM instantiation, which sums no chi2 (nparts = 0).  Neither clears the flags: the caller's launches own them.
+void mfront_lm_edges(Mfront* m, hipStream_t s, const EdgeListDev& el, const double* d_poses, double* d_hist, DirectResult* d_res) {
+  const MfDev& D = m->dev;
+  const int egrid = std::max(1, std::min((D.E + kBlock - 1) / kBlock, kMaxPartials));
+  if (el.kinds) hipLaunchKernelGGL((k_mf_edges<true, false>), dim3(egrid), dim3(kBlock), 0, s, D, el, d_poses, 0, 0, d_hist, d_res, MfSingle{});
+  else hipLaunchKernelGGL((k_mf_edges<false, false>), dim3(egrid), dim3(kBlock), 0, s, D, el, d_poses, 0, 0, d_hist, d_res, MfSingle{});
+}
+
+void mfront_lm_solve(Mfront* m, hipStream_t s, const LmState* st, double* d_hist, DirectResult* d_res) {
+  const MfPlan& P = m->plan;
+  const MfDev& D = m->dev;
+  for (int h = 0; h <= P.height; ++h) {
+    const int cnt = P.level_ptr[h + 1] - P.level_ptr[h];
+    if (h > 0) {
+      const int nt = m->mtile_ptr[h + 1] - m->mtile_ptr[h];
+      const int grid = std::max(1, std::min((nt + kWavesPerBlock - 1) / kWavesPerBlock, 8192));
+      hipLaunchKernelGGL(k_mf_merge<false>, dim3(grid), dim3(kBlock), 0, s, D, m->mtile_ptr[h], m->mtile_ptr[h + 1], MfSingle{});
+    }
+    hipLaunchKernelGGL((k_mf_panels<false, true>), dim3(cnt), dim3(kMfThreads), (size_t)m->level_lds[h], s, D, P.level_ptr[h], 0, -1, 0, d_hist, d_res,
+                       MfLm{st});
+  }
+  for (int h = P.height; h >= 0; --h) {
+    const int cnt = P.level_ptr[h + 1] - P.level_ptr[h];
+    hipLaunchKernelGGL(k_mf_solve<false>, dim3(cnt), dim3(kMfThreads), (size_t)m->level_solve_lds[h], s, D, P.level_ptr[h], MfSingle{});
+  }
+  m->ran = true;
 }
 
 // The plan's arrays by their SGO_MF_* numbers, from the host's copy

@@ -142,6 +142,14 @@ __device__ __forceinline__ void fs_candidate_q(const double* rec, const int* row
   }
 }
 
+// sgo_optimize_lm's share (sgo_lm.hip, sgo_lm.cpp): the free poses' diagonal targets, made by the first call on the plan out of the
+// same per-graph arena -- elimination position p's targets tgt[ptr[p] .. ptr[p + 1]), ascending: the fronts in post-order, which is
+// k_mf_panels' contribution order.
+struct LmDiagDev {
+  const int* ptr = nullptr;   // [n + 1]
+  const int* tgt = nullptr;
+};
+
 // The joint table of sgo_candidate_joint (sgo_fsolve.hip): S [3 n][3 n] row-major, then e [n][3], then one double: the
 // factorisation's failure flag
 constexpr int kJointThreads = 256;   // k_joint_subsets' workgroup: 16 x 16 over a trailing block; one thread per candidate of a mask
@@ -171,6 +179,8 @@ struct Mfront {
   bool fs_ready = false;             // fs's arrays and sel.cmap / sel.cmap_off exist
   const double *fs_Y = nullptr, *fs_X = nullptr;   // the last call's last chunk after the forward / backward pass (the context's scratch)
   int fs_cols = 0;                   // its columns (0: no call yet)
+  // Levenberg-Marquardt
+  LmDiagDev lm_diag;                 // (ptr == nullptr: not made yet)
 };
 
 // ---- kernels of the selected inversion (sgo_selinv.hip), one launch each; the host driver is sgo_selinv.cpp ----

@@ -35,6 +35,34 @@ SGO_RULE_HD inline bool gain_stop(double last, double cur, double gain_tol) {
 // ... and the iterations before which it is asked: at least two updates always run, and the closing pass decides nothing.
 SGO_RULE_HD inline bool gain_stop_applies(int it, int max_iters) { return it >= 2 && it < max_iters; }
 
+// One trial of sgo_optimize_lm (g2o 2020.5.29's OptimizationAlgorithmLevenberg::solve).  cur: the robust chi2
+// at the accepted poses; trial: at the trial poses; scale = x . (lambda x + b) + 1e-3; solve_ok == 0: the factorisation or the
+// substitution failed, which g2o scores as trial = DBL_MAX over scale = 1e-3.  With rho = (cur - trial) / scale the trial is accepted
+// iff rho > 0, the trial chi2 is finite and the solve succeeded: lambda *= max(1/3, min(2/3, 1 - (2 rho - 1)^3)), nu = 2.  Otherwise
+// lambda *= nu, nu *= 2.  Returns kLmAccept, or what the rejection means for the iteration: kLmRetry (rho < 0: another trial while
+// fewer than kLmMaxTrials have run), kLmZeroGain (rho == 0: the iteration ends and the call terminates) or kLmEnd (rho is NaN, or
+// positive with a non-finite trial: the iteration ends).  `double` and comparisons only: the host and k_lm_decide compile this text.
+constexpr int kLmMaxTrials = 10;
+constexpr int kLmRetry = 0, kLmAccept = 1, kLmZeroGain = 2, kLmEnd = 3;
+SGO_RULE_HD inline int lm_trial(double cur, double trial, double scale, int solve_ok, double* lambda, double* nu) {
+  if (!solve_ok) {
+    trial = 1.7976931348623157e308;
+    scale = 1e-3;
+  }
+  const double rho = (cur - trial) / scale;
+  if (rho > 0.0 && trial - trial == 0.0 && solve_ok) {   // (x - x == 0: x is finite)
+    const double t = 2.0 * rho - 1.0;
+    double alpha = 1.0 - t * t * t;
+    if (!(alpha < 2.0 / 3.0)) alpha = 2.0 / 3.0;
+    *lambda *= alpha > 1.0 / 3.0 ? alpha : 1.0 / 3.0;
+    *nu = 2.0;
+    return kLmAccept;
+  }
+  *lambda *= *nu;
+  *nu *= 2.0;
+  return rho < 0.0 ? kLmRetry : (rho == 0.0 ? kLmZeroGain : kLmEnd);
+}
+
 // The leave-one-out rule of sgo_edge_leave_one_out: what sgo_candidate_gate would say about a resident edge
 // had it never been inserted, from the edge's own quantities alone.  info: Omega's upper triangle by rows; P = J Sigma J^T at the
 // current poses WITH the edge in H (row-major, symmetric); e its error; w its kernel weight.  With Omega = G G^T (lower Cholesky),
