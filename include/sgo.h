@@ -426,7 +426,8 @@ int sgo_gate_edges(sgo_ctx* ctx, int32_t n, const int32_t* edge_ids, double chi2
  * kind where it evaluates phi; a graph that holds only NONE and DCS edges runs the kernels, and gives the bits, of one that never
  * made this call.  Keeps every resident structure: no set-up, sgo_stats.seconds_setup does not change, an earlier sgo_linearize
  * is void, and the first solve of the next sgo_optimize_gn / sgo_solve refreshes the hierarchy's coarse operators.  An edge whose
- * information is zero has e = 0, where every kind gives rho0 = 0 and weight 1: deactivating and gating compose with any kind
+ * information is zero has e = 0, where every kind gives rho0 = 0 and weight 1 (DCS with delta = 0 excepted: 2 d / (d + e) is
+ * 0 / 0 there, as in g2o): deactivating and gating compose with any kind
  * (sgo_gate_edges with NULL ids gates the edges with any kernel, all but NONE).
  * SGO_EINVAL, with nothing on the device changed: a multi-GPU context (sgo_debug_set_shard's emulation included), an id outside
  * [0, E), an unknown kind, a non-finite delta, delta < 0 for DCS, delta <= 0 for any other kind but NONE.  Of an id listed twice

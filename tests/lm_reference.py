@@ -10,22 +10,49 @@ import math
 import numpy as np
 import scipy.sparse as sp
 
+import robust_reference as rr
 from oracle import np_oracle
 
 STOP_MAX_ITERS, STOP_TRIALS, STOP_ZERO_GAIN, STOP_LAMBDA = 0, 1, 2, 3
 MAX_TRIALS = 10
 
 
-def levenberg(poses, fixed, ei, ej, meas, info, phi, iters, lambda_init=0.0, *, upper=2.0 / 3.0, eps=1e-3, reset_nu=True):
+def _system(kind, delta):
+    """-> (chi2(poses, ...) -> plain, robust;  linearize(poses, ...) -> H, b) of the graph: np_oracle's own with phi, or -- with
+    kinds (sgo_set_robust_kernels) -- through robust_reference's identity: chi2 = sum rho0, and the system is the unrobustified one
+    with information w Omega.  The schedule does not know the difference."""
+    if kind is None:
+        return (lambda P, fixed, ei, ej, meas, info, phi: np_oracle.chi2(P, ei, ej, meas, info, phi)[:2],
+                lambda P, fixed, ei, ej, meas, info, phi: np_oracle.linearize(P, fixed, ei, ej, meas, info, phi)[:2])
+    kind = np.asarray(kind)
+
+    def pairs(P, ei, ej, meas, info):
+        plain, _, e2 = np_oracle.chi2(P, ei, ej, meas, info, np.full(len(ei), -1.0))
+        r0, w = rr.rho_mixed(kind, e2, delta)
+        return plain, float(r0.sum()), w
+
+    def chi2(P, fixed, ei, ej, meas, info, phi):
+        return pairs(P, ei, ej, meas, info)[:2]
+
+    def linearize(P, fixed, ei, ej, meas, info, phi):
+        w = pairs(P, ei, ej, meas, info)[2]
+        return np_oracle.linearize(P, fixed, ei, ej, meas, np.asarray(info) * w[:, None], np.full(len(ei), -1.0))[:2]
+    return chi2, linearize
+
+
+def levenberg(poses, fixed, ei, ej, meas, info, phi, iters, lambda_init=0.0, *, kind=None, delta=None, upper=2.0 / 3.0, eps=1e-3,
+              reset_nu=True):
+    """kind, delta: per-edge kinds and parameters as sgo_set_robust_kernels takes them (phi is then not read)."""
     poses = np.array(poses, dtype=np.float64, copy=True)
     out = dict(lam=[], trials=[], records=[], stop_reason=STOP_MAX_ITERS, lambda0=None)
-    plain0, cur, _ = np_oracle.chi2(poses, ei, ej, meas, info, phi)
+    chi2_of, linearize_of = _system(kind, delta)
+    plain0, cur = chi2_of(poses, fixed, ei, ej, meas, info, phi)
     out["chi2"], out["robust_chi2"] = [plain0], [cur]
     lam, nu, ok, done = 0.0, 2.0, True, 0
     for it in range(iters):
         if not ok:
             break
-        H, b, _, _ = np_oracle.linearize(poses, fixed, ei, ej, meas, info, phi)
+        H, b = linearize_of(poses, fixed, ei, ej, meas, info, phi)
         if it == 0:
             lam = lambda_init if lambda_init > 0 else 1e-5 * float(np.max(np.abs(H.diagonal())))
             nu = 2.0
@@ -38,7 +65,7 @@ def levenberg(poses, fixed, ei, ej, meas, info, phi, iters, lambda_init=0.0, *, 
             tmp, tmp_plain, scale, trial = float("inf"), float("inf"), eps, poses
             if ok2:
                 trial = np_oracle.oplus(poses, fixed, x)
-                tmp_plain, tmp, _ = np_oracle.chi2(trial, ei, ej, meas, info, phi)
+                tmp_plain, tmp = chi2_of(trial, fixed, ei, ej, meas, info, phi)
                 scale += float(x @ (lam * x + b))
             rho = (cur - tmp) / scale
             accepted = rho > 0 and math.isfinite(tmp) and ok2

@@ -465,3 +465,48 @@ def test_the_calls_through_the_compat_headers(replay, tmp_path):
     assert all(tail[k] == -1 for k in ("not_active", "stale", "levenberg", "refused", "bad_row")), tail
     said = [ln for ln in res.stderr.split("\n") if "sgoEdgeJoint" in ln or "sgoEdgeGroups" in ln]
     assert len(said) == 7, res.stderr                                        # (stale and levenberg: both calls refuse)
+
+
+def test_mixed_kernel_kinds():
+    """test_gpu_robust_kernels._mixed's kinds (all nine on the closures, delta = 1.5) set before sgo_edge_joint / sgo_edge_groups: the
+    table's weights are sgo_edge_robust's and the reference's (tests/robust_reference.py), N and the groups' d2 and pivot meet the bars
+    of test_cases_against_the_reference with the reference fed information w Omega.  Groups of 1, 2, 5, 6 and 11 closures (no set of
+    closures disconnects the graph; how far a group is from that is the reference pivot's to say)."""
+    import robust_reference as rr
+    from test_gpu_robust_kernels import _mixed
+    g = graph(MFRONT)
+    kind, delta = _mixed(g)
+    cl = np.flatnonzero(g.phi >= 0)
+    edges = cl[::4][:200].astype(np.int32)
+    assert set(kind[edges]) == set(range(1, 10))
+    rng = np.random.default_rng(SEED)
+    groups = [np.sort(rng.choice(edges, size=k, replace=False)) for k in (1, 2, 5, 6, 11) for _ in range(8)]
+    M = _masks(groups, edges)
+    with capi.Optimizer(0) as o:
+        o.set_graph(*g.arrays())
+        o.set_robust_kernels(np.arange(g.E), kind, delta)
+        assert o.solver_description().startswith("multifrontal_cholesky"), o.solver_description()
+        assert o.optimize(20)[0] == 20
+        S0 = lr.Edges(o.get_poses(), g.fixed, g.ei, g.ej, g.meas, g.info, np.full(g.E, -1.0))
+        w = rr.rho_mixed(kind, S0.e2, delta)[1]
+        S = lr.Edges(o.get_poses(), g.fixed, g.ei, g.ej, g.meas, g.info, w=w)
+        T, ref = _reference(S, edges, groups)
+        N, e, wt = o.edge_joint(edges)
+        chi = np.array([(1.5 if b % 2 == 0 else 0.5) * (r["d2"] if np.isfinite(r["d2"]) else 1.0) for b, r in enumerate(ref)])
+        nfail, d2, dof, piv, fail = o.edge_groups(M, chi)
+        _, wd = o.edge_robust()
+    assert np.array_equal(bits(wt), bits(wd[edges])) and np.abs(wt - T["w"]).max() <= 1e-9
+    assert (T["w"] < 0.999).sum() >= 20 and np.array_equal(bits(N), bits(N.T.copy()))
+    rn = np.abs(N - T["N"]).max() / np.abs(T["N"]).max()
+    use = np.array([r["pivot"] >= 10 * eg.MIN_PIVOT for r in ref])
+    d2r, pr = np.array([r["d2"] for r in ref]), np.array([r["pivot"] for r in ref])
+    rd = float((np.abs(d2[use] - d2r[use]) / d2r[use]).max())
+    rp = float(np.abs(piv[use] - pr[use]).max())
+    print(f"mixed kinds: {edges.size} closures, {int(use.sum())} of {len(groups)} groups compared, {int((T['w'] < 0.999).sum())} weights below 0.999; "
+          f"N {rn:.2e} of max |N_ref|, d2 {rd:.2e} relative, pivot {rp:.2e} absolute")
+    assert use.sum() >= 8 and rn <= BAR and rd <= BAR and rp <= BAR
+    assert np.array_equal(dof, [r["dof"] for r in ref]) and nfail == int(fail.sum())
+    decided = piv >= eg.MIN_PIVOT
+    assert np.isnan(d2[~decided]).all() and np.isfinite(d2[decided]).all() and np.array_equal(fail, decided & (d2 > chi))
+    clear = use & (np.abs(d2r - chi) > 1e-3 * d2r)
+    assert np.array_equal(fail[clear], (d2r > chi)[clear])

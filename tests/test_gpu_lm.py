@@ -165,17 +165,34 @@ def test_dcs_graph_over_the_prefix_that_meets_the_condition():
 
 
 def test_mixed_kernels_hold_the_properties():
+    """... and follow the reference's trace (lm_reference.levenberg with kinds: information w Omega, chi2 = sum rho0) over the prefix
+    of its trials that meets the input condition: the reference stalls in its seventh iteration, whose last rejected trials have
+    |rho| down to 4e-5, as the DCS graph's do.  d is measured as in every case here, with the kinds set and
+    robust_reference.gauss_newton (the CPU oracle under the same identity) as the reference."""
+    import robust_reference as rr
+    from oracle import c_oracle
     from test_gpu_robust_kernels import _mixed
     g = _graph(600, 630, 5, phi=10.0)
     kind, delta = _mixed(g)
     start = lr.perturbed(g, 0.5)
+    ref = lr.levenberg(start, *g.arrays()[1:], 8, kind=kind, delta=delta)
+    _, gn = rr.gauss_newton(c_oracle, start, g, kind, delta, 8)
     for opts in ({}, dict(direct_rows=1)):
         with capi.Optimizer(0, **opts) as opt:
             opt.set_graph(*g.arrays())
             opt.set_robust_kernels(np.arange(g.E), kind, delta)
+            opt.set_poses(start)
+            _, st_gn = opt.optimize(8)
+            d = max([1e-12] + [abs(a - b) / b for k in ("chi2", "robust_chi2") for a, b in zip(st_gn[k], gn[k])
+                               if np.isfinite(a) and np.isfinite(b) and b > 0])
             rc, st, P, chi2_after = _lm_twice(opt, start, 8)
         _properties(rc, st, chi2_after)
         assert st["robust_chi2"][rc] < st["robust_chi2"][0] and np.isfinite(P).all()
+        whole = all(abs(r["rho"]) >= 1000.0 * d * (r["cur"] + r["tmp"]) / r["scale"] for r in ref["records"])
+        compared = _compare(st, ref, d, whole=whole)
+        accepted = sum(1 for i in range(compared) if st["robust_chi2"][i + 1] < st["robust_chi2"][i])
+        print("mixed kinds", opts, "compared", compared, "of", ref["iters_done"], "iterations, accepted inside", accepted, "whole", whole)
+        assert accepted >= 2, (compared, accepted)
 
 
 @pytest.mark.parametrize("name", mc.NAMES)

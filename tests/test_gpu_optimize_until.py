@@ -292,3 +292,38 @@ def test_terminate_action_through_the_shim_on_the_device(tmp_path):
     P = np.loadtxt(lines[2:2 + g.V])
     oP, _ = oracle_k(shape, 8)
     assert np.abs(P - oP).max() <= 1e-6, np.abs(P - oP).max()
+
+
+def test_mixed_kernel_kinds_on_the_multifrontal_path():
+    """test_gpu_robust_kernels._mixed's kinds (all nine on the closures, delta = 1.5): k_mf_gain_stop reads the robust chi2 the edge
+    kernel's KINDS instantiation summed.  The call is a prefix of the plain call bit for bit, stops where the rule says on the plain
+    call's history and on the reference's (robust_reference.gauss_newton; gains 1.5e-3 before the stop and 3e-5 at it, tolerance
+    5e-4), and leaves the poses and sgo_chi2 of the plain call cut at that count."""
+    import robust_reference as rr
+    from oracle import c_oracle
+    from test_gpu_robust_kernels import _mixed
+    shape, tol = (2500, 3400, 31), 5e-4
+    g = graph(shape)
+    kind, delta = _mixed(g)
+
+    def ctx():
+        opt = capi.Optimizer(0)
+        opt.set_graph(*g.arrays())
+        opt.set_robust_kernels(np.arange(g.E), kind, delta)
+        assert opt.solver_description().startswith("multifrontal_cholesky"), opt.solver_description()
+        return opt
+
+    with ctx() as opt:
+        dA, stA = opt.optimize(20)
+    assert dA == 20
+    k = rule_stop(stA["robust_chi2"], tol, 20)
+    _, ref = rr.gauss_newton(c_oracle, g.poses, g, kind, delta, 20)
+    assert 2 <= k < 20 and k == rule_stop(ref["robust_chi2"], tol, 20), (k, stA["robust_chi2"], ref["robust_chi2"])
+    with ctx() as opt:
+        B = dict(res=[opt.optimize_until(20, tol)], poses=opt.get_poses(), chi2=opt.chi2())
+    check_prefix(stA, B, k)
+    with ctx() as opt:
+        dC, stC = opt.optimize(k)
+        assert dC == k and same_bits(opt.get_poses(), B["poses"]) and opt.chi2() == B["chi2"]
+    assert same_bits(stC["robust_chi2"], B["res"][0][1]["robust_chi2"]) and same_bits(stC["chi2"], B["res"][0][1]["chi2"])
+    assert same_bits(list(B["chi2"]), [stC["chi2"][k], stC["robust_chi2"][k]])

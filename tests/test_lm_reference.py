@@ -63,3 +63,42 @@ def test_reference_reproduces_the_landmark_oracle(case):
 @pytest.mark.parametrize("constants", [dict(upper=0.5), dict(eps=0.0), dict(reset_nu=False)], ids=["two_thirds_to_half", "no_1e-3", "nu_not_reset"])
 def test_a_mutated_constant_is_noticed(case, constants):
     assert not agrees(run(case, **constants), case[2])
+
+
+def test_kinds_go_through_the_same_schedule(case):
+    """levenberg(kind=, delta=): information w Omega and chi2 = sum rho0 through robust_reference.  No kernel by kinds is the run
+    without one; DCS by kinds is DCS by phi; Huber, Cauchy and Tukey on the three closures change the trace, every recorded
+    robust chi2 is the sum of rho0 at that iterate, and the first trial's system is np_oracle's with information w Omega."""
+    import robust_reference as rr
+    g, start, _ = case
+    args = (g.fixed, g.ei, g.ej, g.meas, g.info)
+    cl = np.flatnonzero(np.abs(g.ei.astype(np.int64) - g.ej) != 1)
+    assert cl.size == 3
+    plain = run(case)
+    by_kind = lr.levenberg(start, *args, g.phi, ITERS, kind=np.zeros(g.E, dtype=np.int32), delta=np.ones(g.E))
+    assert by_kind["trials"] == plain["trials"] and np.allclose(by_kind["lam"], plain["lam"], rtol=1e-12, atol=0.0)
+    assert np.allclose(by_kind["robust_chi2"], plain["robust_chi2"], rtol=1e-12, atol=0.0)
+    e2 = np_oracle.chi2(start, g.ei, g.ej, g.meas, g.info, g.phi)[2]
+    d = float(np.sqrt(np.median(e2[cl])))                       # a width that bites at the start
+    phi = g.phi.copy()
+    phi[cl] = d
+    kind = np.zeros(g.E, dtype=np.int32)
+    kind[cl] = rr.DCS
+    a = lr.levenberg(start, *args, phi, ITERS)
+    b = lr.levenberg(start, *args, g.phi, ITERS, kind=kind, delta=np.where(kind > 0, d, 1.0))
+    assert a["trials"] == b["trials"] and a["stop_reason"] == b["stop_reason"]
+    assert np.allclose(a["lam"], b["lam"], rtol=1e-9, atol=0.0) and np.allclose(a["robust_chi2"], b["robust_chi2"], rtol=1e-9, atol=0.0)
+    assert a["robust_chi2"][0] < a["chi2"][0]
+    kind[cl] = [rr.HUBER, rr.CAUCHY, rr.TUKEY]
+    delta = np.where(kind > 0, d, 1.0)
+    m = lr.levenberg(start, *args, g.phi, ITERS, kind=kind, delta=delta)
+    assert m["robust_chi2"] != a["robust_chi2"] and m["robust_chi2"] != plain["robust_chi2"]
+    assert all(x >= y for x, y in zip(m["robust_chi2"], m["robust_chi2"][1:])) and m["robust_chi2"][0] < m["chi2"][0]
+    e2 = np_oracle.chi2(m["poses"], g.ei, g.ej, g.meas, g.info, g.phi)[2]
+    assert abs(m["robust_chi2"][-1] - rr.rho_mixed(kind, e2, delta)[0].sum()) <= 1e-12 * m["robust_chi2"][-1]
+    assert abs(m["chi2"][-1] - e2.sum()) <= 1e-12 * e2.sum()
+    # lambda_0 is 1e-5 of the largest diagonal entry of the system with information w Omega
+    e2 = np_oracle.chi2(start, g.ei, g.ej, g.meas, g.info, g.phi)[2]
+    w = rr.rho_mixed(kind, e2, delta)[1]
+    H = np_oracle.linearize(start, g.fixed, g.ei, g.ej, g.meas, g.info * w[:, None], g.phi)[0]
+    assert m["lambda0"] == 1e-5 * float(np.max(np.abs(H.diagonal()))) and (w[cl] < 1.0).any()
