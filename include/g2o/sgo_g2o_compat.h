@@ -1682,7 +1682,8 @@ class SparseOptimizer : public OptimizableGraph {
   static constexpr int kHostSolverMaxUnknowns = 3000;
 
   // Levenberg-Marquardt on a pose graph the dense host solver refuses for its size (more than kHostSolverMaxUnknowns unknowns): the
-  // library's sgo_optimize_lm -- g2o's schedule on the multifrontal factor -- with the marshalling of the Gauss-Newton route.
+  // library's sgo_optimize_lm -- g2o's schedule on the multifrontal factor --, or, for a graph whose size or density the multifrontal
+  // analysis refuses, sgo_optimize_lm_pcg -- the same schedule on the PCG --, with the marshalling of the Gauss-Newton route.
   // Everything the host solver solves stays there.
   bool levenbergOnDevice() const {
     if (_algorithm->kind() != OptimizationAlgorithm::Levenberg || !deviceTypes()) return false;
@@ -1692,7 +1693,7 @@ class SparseOptimizer : public OptimizableGraph {
   }
   // Returns the iterations counted, as the host solver does; _lmTrace is the call's trace (lambda and robust chi2 after every
   // iteration, its trials).  0 with one line on std::cerr when a terminate action is registered (the decisions are taken on the
-  // device, which knows g2o's own termination only) and when the multifrontal analysis refuses the graph.
+  // device, which knows g2o's own termination only).
   int deviceLevenberg(int iterations) {
     _lmTrace.clear();
     if (_terminateAction) {
@@ -1709,7 +1710,10 @@ class SparseOptimizer : public OptimizableGraph {
     }
     _lastStats.reset();   // (lastStats() is the last Gauss-Newton call's: none now)
     std::unique_ptr<sgo_lm_stats> st(new sgo_lm_stats());
-    const int done = sgo_optimize_lm(_ctx, iterations, 0.0, st.get());
+    int done = sgo_optimize_lm(_ctx, iterations, 0.0, st.get());
+    // (a graph the multifrontal analysis refuses for its size or density -- SGO_ENOTHING although there is a free active vertex --:
+    // the same schedule with the trials solved by the context's PCG)
+    if (done == SGO_ENOTHING && sgo_num_free(_ctx) > 0) done = sgo_optimize_lm_pcg(_ctx, iterations, 0.0, st.get());
     if (done < 0) {
       std::cerr << "SparseOptimizer::optimize: " << sgo_last_error(_ctx) << (done == SGO_ENOTHING ? "; refusing" : "") << std::endl;
       return 0;

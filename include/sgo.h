@@ -265,7 +265,8 @@ int sgo_optimize_gn_until(sgo_ctx* ctx, int32_t max_iters, double gain_tol, sgo_
  * sgo_optimize_gn keeps its path and its bits, and the joint tables stay the snapshots they are.
  * SGO_EINVAL, with nothing changed: max_iters outside [0, SGO_MAX_ITERS], a lambda_init that is not finite, an active incremental
  * overlay, a multi-GPU context (sgo_debug_set_shard's emulation included).  SGO_ENOTHING when there is no free active vertex, and,
- * with the analysis' reason in sgo_last_error, when the multifrontal analysis refuses the graph: use sgo_optimize_gn then. */
+ * with the analysis' reason in sgo_last_error, when the multifrontal analysis refuses the graph: use sgo_optimize_lm_pcg (below) or
+ * sgo_optimize_gn then. */
 #define SGO_LM_STOP_MAX_ITERS 0   /* max_iters iterations counted */
 #define SGO_LM_STOP_TRIALS    1   /* ten trials of one iteration rejected (g2o: Terminate) */
 #define SGO_LM_STOP_ZERO_GAIN 2   /* rho == 0 exactly */
@@ -281,6 +282,32 @@ typedef struct sgo_lm_stats {
 } sgo_lm_stats;
 int sgo_optimize_lm(sgo_ctx* ctx, int32_t max_iters, double lambda_init /* <= 0: 1e-5 * max diag(H) */, sgo_lm_stats* out);
 int sgo_lm_trial_rule(double cur, double trial, double scale, int solve_ok, double* lambda, double* nu); /* pure, no GPU */
+
+/* (later additions, version 107) Levenberg-Marquardt on the PCG: sgo_optimize_lm's schedule -- lambda_0, nu,
+ * the gain ratio over x . (lambda x + b) + 1e-3, ten trials, g2o's terminations, sgo_lm_stats filled the same way, the same return
+ * values and the same SGO_EINVAL refusals with nothing changed -- with every trial's (H + lambda I) x = b solved by the
+ * preconditioned conjugate gradients: cold from x = 0, at pcg_tol (times the chain-graph scale of sgo_optimize_gn) relative to the
+ * trial's own |b|, behind a hierarchy refreshed for H + lambda I before every trial.  It differs in three ways:
+ *   - It works on EVERY single-GPU context -- PCG with multigrid, PCG with block-Jacobi, single-launch direct, multifrontal; the last
+ *     two build the row plan and the hierarchy on first use, as sgo_marginals and sgo_linearize do -- and is never refused for the
+ *     graph's size or density.  SGO_ENOTHING only when there is no free active vertex.
+ *   - out->sync_rounds equals the trials run: the PCG reads its scalars on the host anyway, so the state is read once per trial.
+ *   - A trial whose solve breaks down (p . H p <= 0 or non-finite), or stops short of pcg_tol without standing at the
+ *     floating-point floor of its system, is a REJECTED trial, not a failed call: lambda grows and the next trial's system is
+ *     better conditioned.  sgo_optimize_gn's rebuild / re-aggregation recoveries are not used.
+ * The decision of a trial is taken on the device by the rule sgo_lm_trial_rule states; two calls from the same state return the same
+ * bits; robust_chi2[] never increases and its last entries are sgo_chi2's bits.  Afterwards the context is as after
+ * sgo_set_poses(the final poses): the next sgo_optimize_gn refreshes its hierarchy and starts cold, keeps its path and its bits; what
+ * the hierarchy has learned (its best count, the lag calibration) and the resident factor and joint tables are untouched.
+ *
+ * sgo_lm_pcg_trace: the trials of the context's last sgo_optimize_lm_pcg.  Returns their number and fills, for the first `cap` of
+ * them (either array may be NULL), the trial's PCG iteration count and how its solve ended: SGO_LM_SOLVE_CONVERGED (pcg_tol reached),
+ * SGO_LM_SOLVE_FLOOR (accepted at the floating-point floor), or, for a failed solve -- a rejected trial --, minus the PCG's stop
+ * code: -2 out of iterations or stagnated, -3 breakdown.  SGO_EINVAL for a NULL context or a negative cap. */
+#define SGO_LM_SOLVE_CONVERGED 1
+#define SGO_LM_SOLVE_FLOOR 2
+int sgo_optimize_lm_pcg(sgo_ctx* ctx, int32_t max_iters, double lambda_init /* <= 0: 1e-5 * max diag(H) */, sgo_lm_stats* out);
+int sgo_lm_pcg_trace(sgo_ctx* ctx, int32_t cap, int32_t* pcg_iters, int32_t* solve_stop);
 
 /* (later additions, version 107) Many closure hypotheses of the resident graph in one call: "is this set of
  * closures consistent", leave-one-out over a round's closures, cluster tests -- the same graph optimised once per hypothesis.

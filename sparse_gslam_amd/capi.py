@@ -40,7 +40,7 @@ SYMBOLS = [
     "sgo_joint_greedy", "sgo_joint_extend", "sgo_joint_greedy_rule",
     "sgo_edge_joint", "sgo_edge_groups", "sgo_edge_group_rule",
     "sgo_set_hypotheses_workspace", "sgo_hypotheses_bytes", "sgo_hypotheses_chunk", "sgo_hypotheses_workspace_bytes",
-    "sgo_optimize_lm", "sgo_lm_trial_rule",
+    "sgo_optimize_lm", "sgo_lm_trial_rule", "sgo_optimize_lm_pcg", "sgo_lm_pcg_trace",
 ]
 
 # SGO_JOINT_MAX_*: the limits of sgo_candidate_joint's table and of a subset of it
@@ -53,6 +53,8 @@ STOP_MAX_ITERS, STOP_GAIN, STOP_FAILED = 0, 1, 2
 LM_STOP_MAX_ITERS, LM_STOP_TRIALS, LM_STOP_ZERO_GAIN, LM_STOP_LAMBDA = 0, 1, 2, 3
 # what sgo_lm_trial_rule returns
 LM_RETRY, LM_ACCEPT, LM_ZERO_GAIN, LM_END = 0, 1, 2, 3
+# SGO_LM_SOLVE_*: how a trial's solve of sgo_optimize_lm_pcg ended (sgo_lm_pcg_trace; a failed solve: minus the PCG stop code)
+LM_SOLVE_CONVERGED, LM_SOLVE_FLOOR = 1, 2
 
 # SGO_HYP_*: the route sgo_optimize_gn_hypotheses took
 HYP_BATCHED, HYP_SEQUENTIAL = 1, 2
@@ -267,6 +269,8 @@ def lib():
     L.sgo_optimize_gn_until.argtypes = [vp, C.c_int32, C.c_double, C.POINTER(Stats), i32]
     L.sgo_gain_stop.argtypes = [C.c_double, C.c_double, C.c_double]
     L.sgo_optimize_lm.argtypes = [vp, C.c_int32, C.c_double, C.POINTER(LmStats)]
+    L.sgo_optimize_lm_pcg.argtypes = [vp, C.c_int32, C.c_double, C.POINTER(LmStats)]
+    L.sgo_lm_pcg_trace.argtypes = [vp, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     L.sgo_lm_trial_rule.argtypes = [C.c_double, C.c_double, C.c_double, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.sgo_optimize_gn_hypotheses.argtypes = [vp, C.c_int32, C.c_int32, C.c_double, u8, d, C.POINTER(HypothesisResult), d, d, d]
     L.sgo_hypothesis_isolated_vertex.restype = C.c_int32
@@ -669,10 +673,31 @@ class Optimizer:
         chi2 at the start and after every iteration, trials_total, stop_reason (one of LM_STOP_*), sync_rounds)."""
         st = LmStats()
         rc = self._check(lib().sgo_optimize_lm(self._h, max_iters, lambda_init, C.byref(st)), "sgo_optimize_lm")
+        return rc, self._lm_dict(rc, st)
+
+    @staticmethod
+    def _lm_dict(rc, st):
         d = max(st.iters_done, 0)
-        return rc, dict(rc=rc, iters_done=st.iters_done, trials_total=st.trials_total, stop_reason=st.stop_reason,
-                        sync_rounds=st.sync_rounds, lambda0=st.lambda0, lam=list(st.lam[:d]), trials=list(st.trials[:d]),
-                        robust_chi2=list(st.robust_chi2[: d + 1]), chi2=list(st.chi2[: d + 1]), seconds_total=st.seconds_total)
+        return dict(rc=rc, iters_done=st.iters_done, trials_total=st.trials_total, stop_reason=st.stop_reason,
+                    sync_rounds=st.sync_rounds, lambda0=st.lambda0, lam=list(st.lam[:d]), trials=list(st.trials[:d]),
+                    robust_chi2=list(st.robust_chi2[: d + 1]), chi2=list(st.chi2[: d + 1]), seconds_total=st.seconds_total)
+
+    def optimize_lm_pcg(self, max_iters: int = 20, lambda_init: float = 0.0):
+        """sgo_optimize_lm_pcg: optimize_lm's schedule with every trial solved by the context's PCG, on every single-GPU context and
+        never refused for the graph's size -> (iterations counted, optimize_lm's stats dict; sync_rounds = the trials run)."""
+        st = LmStats()
+        rc = self._check(lib().sgo_optimize_lm_pcg(self._h, max_iters, lambda_init, C.byref(st)), "sgo_optimize_lm_pcg")
+        return rc, self._lm_dict(rc, st)
+
+    def lm_pcg_trace(self):
+        """sgo_lm_pcg_trace: the trials of the last optimize_lm_pcg -> (pcg_iters, solve_stop), int32 arrays with one entry per trial;
+        solve_stop is LM_SOLVE_CONVERGED, LM_SOLVE_FLOOR, or minus the PCG stop code of a failed solve (a rejected trial)."""
+        n = self._check(lib().sgo_lm_pcg_trace(self._h, 0, None, None), "sgo_lm_pcg_trace")
+        its, how = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+        if n:
+            self._check(lib().sgo_lm_pcg_trace(self._h, n, its.ctypes.data_as(C.POINTER(C.c_int32)), how.ctypes.data_as(C.POINTER(C.c_int32))),
+                        "sgo_lm_pcg_trace")
+        return its, how
 
     def set_hypotheses_workspace(self, max_bytes: int) -> None:
         """sgo_set_hypotheses_workspace: the device memory optimize_hypotheses may take for per-hypothesis copies on a

@@ -295,13 +295,16 @@ struct sgo_ctx {
     size_t loo_cap = 0, loo_ids_cap = 0;
   } selinv;
 
-  // sgo_optimize_lm (sgo_lm.cpp): the trial poses [V][3], the call's scratch (sgo_lm.h: kLmScratchDoubles) and the device state;
+  // sgo_optimize_lm (sgo_lm.cpp) and sgo_optimize_lm_pcg: the trial poses [V][3], the call's scratch (sgo_lm.h: kLmScratchDoubles) and the device state;
   // grown on demand, kept across graphs
   struct Lm {
     double* d_trial = nullptr;
     double* d_scratch = nullptr;
     sgo::LmState* d_state = nullptr;
     size_t trial_cap = 0, scratch_cap = 0, state_cap = 0;
+    // the last sgo_optimize_lm_pcg (sgo_lm_pcg.cpp), per trial: its PCG iterations and how its solve ended (SGO_LM_SOLVE_*, or minus
+    // the PCG stop code of a failed one) -- what sgo_lm_pcg_trace hands out
+    std::vector<int32_t> pcg_iters, solve_stop;
   } lm;
 
   // sgo_candidate_joint's table (sgo_fsolve.cpp): S [3 n][3 n], e [n][3] and the failure flag in tab[cur]; a call builds in the

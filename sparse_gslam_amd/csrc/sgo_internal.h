@@ -593,7 +593,8 @@ void launch_linearize(hipStream_t s, const Sym0Dev& A, int g0, int g1, const Edg
 // (partials: [3][kMaxPartials], host-mapped -- the host adds the workgroups' sums itself, in order; returns the number of workgroups)
 int launch_diag_change(hipStream_t s, int row0, int row1, const double* dblk, double* dref, bool store_ref, double* partials);
 void launch_finalize(hipStream_t s, const Sym0Dev& A, int row0, int row1, const double* dgb, double* b, double* x, double* r, double* z,
-                     double* p, double* xs, double omega, double* partials, int* grid_out);
+                     double* p, double* xs, double omega, double* partials, int* grid_out,
+                     const double* lm_lambda = nullptr);   // lm_lambda: the instantiation that damps the diagonal (sgo_optimize_lm_pcg)
 void launch_init_scalars(hipStream_t s, PcgScalars* S, const double* rz_parts, int n_rz, const double* bb_parts,
                          int n_bb, double tol, int maxit, double bb_ref, double tol_cap);
 void launch_set_probe(hipStream_t s, PcgScalars* S, int probe_k, double probe_max);

@@ -264,15 +264,19 @@ __global__ __launch_bounds__(kBlock) void k_linearize(Sym0Dev A, int g0, int g1,
 // Per row: diagonal block (symmetric packing), block-diagonal inverse, and the PCG start state
 //   x = 0, r = b, z = Dinv b, p = z ; partials[0][blk] = r.z, partials[1][blk] = b.b
 // and, for the multigrid cycle's first smoothing sweep from zero, xs = omega Dinv b.
+// LM (sgo_optimize_lm_pcg): the damped system's -- *lm_lambda, the device state's damping, is added to the
+// three diagonal entries before the inverse, so dblk, dinv, z, p and xs are those of H + lambda I (dgb stays H's).
+template <bool LM>
 __global__ __launch_bounds__(kBlock) void k_finalize(Sym0Dev A, int row0, int row1, const double* __restrict__ dgb,
                                                      double* __restrict__ b, double* __restrict__ x,
                                                      double* __restrict__ r, double* __restrict__ z,
                                                      double* __restrict__ p, double* __restrict__ xs, double omega,
-                                                     double* __restrict__ partials) {
+                                                     double* __restrict__ partials, const double* __restrict__ lm_lambda) {
   double acc[2] = {0.0, 0.0};
+  const double shift = LM ? *lm_lambda : 0.0;
   for (int i = row0 + blockIdx.x * kBlock + threadIdx.x; i < row1; i += gridDim.x * kBlock) {   // (multi-GPU: this rank's rows)
     const double* d = dgb + 9 * (size_t)i;
-    const double dg[6] = {d[0], d[1], d[2], d[3], d[4], d[5]};
+    const double dg[6] = {LM ? d[0] + shift : d[0], d[1], d[2], LM ? d[3] + shift : d[3], d[4], LM ? d[5] + shift : d[5]};
     const double b0 = d[6], b1 = d[7], b2 = d[8];
     double di[6];
     dinv_from_block(dg, di);
@@ -1165,9 +1169,10 @@ void launch_linearize(hipStream_t s, const Sym0Dev& A, int g0, int g1, const Edg
   else SGO_LAUNCH(k_linearize<false>, dim3(grid), dim3(kBlock), 0, s, A, g0, g1, es, poses, dgb);
 }
 void launch_finalize(hipStream_t s, const Sym0Dev& A, int row0, int row1, const double* dgb, double* b, double* x, double* r, double* z,
-                     double* p, double* xs, double omega, double* partials, int* grid_out) {
+                     double* p, double* xs, double omega, double* partials, int* grid_out, const double* lm_lambda) {
   const int grid = grid_for(row1 - row0, kBlock);
-  SGO_LAUNCH(k_finalize, dim3(grid), dim3(kBlock), 0, s, A, row0, row1, dgb, b, x, r, z, p, xs, omega, partials);
+  if (lm_lambda) SGO_LAUNCH(k_finalize<true>, dim3(grid), dim3(kBlock), 0, s, A, row0, row1, dgb, b, x, r, z, p, xs, omega, partials, lm_lambda);
+  else SGO_LAUNCH(k_finalize<false>, dim3(grid), dim3(kBlock), 0, s, A, row0, row1, dgb, b, x, r, z, p, xs, omega, partials, lm_lambda);
   *grid_out = grid;
 }
 int launch_diag_change(hipStream_t s, int row0, int row1, const double* dblk, double* dref, bool store_ref, double* partials) {

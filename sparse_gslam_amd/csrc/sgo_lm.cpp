@@ -43,6 +43,10 @@ int lm_prepare(sgo_ctx* c, Mfront* m) {
   return SGO_OK;
 }
 
+}  // namespace
+
+namespace sgo {
+
 // (plain, robust) chi2 at `poses` into out2 by the very launches sgo_chi2 makes on this context, so that the call's history and
 // sgo_chi2 after it agree to the bit whatever path optimize() takes
 int lm_chi2(sgo_ctx* c, double* poses, double* out2) {
@@ -60,7 +64,28 @@ int lm_chi2(sgo_ctx* c, double* poses, double* out2) {
   return SGO_OK;
 }
 
-}  // namespace
+int lm_check_args(sgo_ctx* c, const char* name, int32_t max_iters, double lambda_init) {
+  const std::string who(name);
+  if (max_iters < 0 || max_iters > SGO_MAX_ITERS) {
+    c->err = who + ": max_iters must be in [0, SGO_MAX_ITERS]";
+    return SGO_EINVAL;
+  }
+  if (!std::isfinite(lambda_init)) {
+    c->err = who + ": lambda_init is not finite";
+    return SGO_EINVAL;
+  }
+  if (c->ov.active) {
+    c->err = who + ": the resident graph carries an incremental overlay (call sgo_set_graph_se2)";
+    return SGO_EINVAL;
+  }
+  if (multi_gpu_context(c)) {
+    c->err = who + ": not available in a multi-GPU context (call sgo_optimize_gn)";
+    return SGO_EINVAL;
+  }
+  return SGO_OK;
+}
+
+}  // namespace sgo
 
 extern "C" {
 
@@ -73,22 +98,7 @@ int sgo_optimize_lm(sgo_ctx* c, int32_t max_iters, double lambda_init, sgo_lm_st
   try {
     int rc = check_graph(c);
     if (rc) return rc;
-    if (max_iters < 0 || max_iters > SGO_MAX_ITERS) {
-      c->err = "sgo_optimize_lm: max_iters must be in [0, SGO_MAX_ITERS]";
-      return SGO_EINVAL;
-    }
-    if (!std::isfinite(lambda_init)) {
-      c->err = "sgo_optimize_lm: lambda_init is not finite";
-      return SGO_EINVAL;
-    }
-    if (c->ov.active) {
-      c->err = "sgo_optimize_lm: the resident graph carries an incremental overlay (call sgo_set_graph_se2)";
-      return SGO_EINVAL;
-    }
-    if (multi_gpu_context(c)) {
-      c->err = "sgo_optimize_lm: not available in a multi-GPU context (call sgo_optimize_gn)";
-      return SGO_EINVAL;
-    }
+    if ((rc = lm_check_args(c, "sgo_optimize_lm", max_iters, lambda_init))) return rc;
     if (out) {
       std::memset(out, 0, sizeof(*out));
       out->iters_requested = max_iters;
@@ -97,7 +107,7 @@ int sgo_optimize_lm(sgo_ctx* c, int32_t max_iters, double lambda_init, sgo_lm_st
     const double t0 = wall_s();
     HIP_TRY(c, hipSetDevice(c->device));
     Mfront* m = nullptr;
-    if ((rc = selinv_plan(c, &m, "sgo_optimize_lm", "sgo_optimize_gn")) || (rc = lm_prepare(c, m))) return rc;
+    if ((rc = selinv_plan(c, &m, "sgo_optimize_lm", "sgo_optimize_lm_pcg or sgo_optimize_gn")) || (rc = lm_prepare(c, m))) return rc;
     const MfDev& D = m->dev;
     sgo_ctx::Lm& Z = c->lm;
     const size_t V3 = 3 * (size_t)c->V;
@@ -119,12 +129,12 @@ int sgo_optimize_lm(sgo_ctx* c, int32_t max_iters, double lambda_init, sgo_lm_st
           mfront_lm_edges(m, c->stream, c->el, c->d_poses, c->d_hist, c->d_dres);
           if (attempt == 0) {
             launch_lm_lambda0(c->stream, D, m->lm_diag, partials);
-            launch_lm_begin(c->stream, D, partials, grid, chi0, lambda_init, max_iters, Z.d_state);
+            launch_lm_begin(c->stream, D.flags, partials, grid, chi0, lambda_init, max_iters, Z.d_state);
           }
           mfront_lm_solve(m, c->stream, Z.d_state, c->d_hist, c->d_dres);
           launch_lm_trial(c->stream, D, m->lm_diag, Z.d_state, c->d_poses, Z.d_trial, partials);
           if ((rc = lm_chi2(c, Z.d_trial, chi_trial))) return rc;
-          launch_lm_decide(c->stream, D, partials, grid, chi_trial, attempt, max_iters, Z.d_state);
+          launch_lm_decide(c->stream, D.flags, 1, partials, grid, chi_trial, attempt, max_iters, Z.d_state);
           launch_lm_commit(c->stream, Z.d_state, attempt, (int)V3, Z.d_trial, c->d_poses);
         }
         HIP_TRY(c, hipGetLastError());

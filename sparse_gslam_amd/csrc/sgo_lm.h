@@ -40,14 +40,39 @@ struct LmState {
 constexpr size_t kLmScratchDoubles = 4 + (size_t)kMaxPartials;
 
 void launch_lm_lambda0(hipStream_t s, const MfDev& M, const LmDiagDev& G, double* partials);
-void launch_lm_begin(hipStream_t s, const MfDev& M, const double* partials, int nparts, const double* chi2, double lambda_init, int max_iters,
+// flags: the multifrontal path's flag words (the stop word goes into flags[0]; flags[0] and flags[2] are the trial's solve failures),
+// or nullptr on the PCG route, whose host reads the state after every trial and hands the solve's outcome in as solve_ok
+void launch_lm_begin(hipStream_t s, int* flags, const double* partials, int nparts, const double* chi2, double lambda_init, int max_iters,
                      LmState* st);
 void launch_lm_trial(hipStream_t s, const MfDev& M, const LmDiagDev& G, const LmState* st, const double* poses, double* trial_poses,
                      double* partials);
-void launch_lm_decide(hipStream_t s, const MfDev& M, const double* partials, int nparts, const double* chi2_trial, int attempt, int max_iters,
-                      LmState* st);
+void launch_lm_decide(hipStream_t s, int* flags, int solve_ok, const double* partials, int nparts, const double* chi2_trial, int attempt,
+                      int max_iters, LmState* st);
 void launch_lm_commit(hipStream_t s, const LmState* st, int attempt, int V3, const double* trial_poses, double* poses);
 void launch_lm_finish(hipStream_t s, const MfDev& M);
 int lm_grid(int n);   // the grid of k_lm_lambda0 / k_lm_trial = their partials
 
+// ---- the PCG route (sgo_optimize_lm_pcg, sgo_lm_pcg.cpp): one attempt is
+//   k_linearize         H and b at the accepted poses into dgb (sgo_kernels.hip's own kernel)
+//   k_lm_lambda0_rows,  first attempt of a call: max |diag(H)| over the rows of dgb, then k_lm_begin as above
+//   k_finalize<LM>      the level-0 diagonal blocks, their inverses and the PCG start state of H + lambda I, lambda read from the state
+//   start_pcg, run_pcg  the hierarchy refreshed for H + lambda I, the cold solve at pcg_tol relative to its own |b| (sgo_solve.cpp)
+//   k_lm_trial_pcg      trial poses = poses (+) x, partial sums of x . (lambda x + b) from d_x and d_b
+//   chi2 at the trial poses, k_lm_decide (solve_ok from the host's reading of the solve), k_lm_commit
+// and one read of the state: the PCG reads its scalars on the host anyway.
+// dgb: [n][9] the rows' diagonal blocks (upper triangle) and right-hand sides; -> the workgroups' maxima of |d[0]|, |d[3]|, |d[5]|
+void launch_lm_lambda0_rows(hipStream_t s, int n, const double* dgb, double* partials);
+// free_id: row -> vertex (k_pose_update's map); x, b: the solve's solution and right-hand side in row order
+void launch_lm_trial_pcg(hipStream_t s, int n, const int* free_id, const LmState* st, int solve_ok, const double* poses, const double* x,
+                         const double* b, double* trial_poses, double* partials);
+
+}  // namespace sgo
+
+// the host side both routes share (sgo_lm.cpp)
+struct sgo_ctx;
+namespace sgo {
+// the argument checks of sgo_optimize_lm and sgo_optimize_lm_pcg (`name` in the error text): SGO_EINVAL with nothing changed
+int lm_check_args(sgo_ctx* c, const char* name, int32_t max_iters, double lambda_init);
+// (plain, robust) chi2 at `poses` into out2 by the very launches sgo_chi2 makes on this context
+int lm_chi2(sgo_ctx* c, double* poses, double* out2);
 }  // namespace sgo

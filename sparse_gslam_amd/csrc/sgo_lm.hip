@@ -10,6 +10,8 @@
 //                  factorisation (flags[0] == 1) or substitution (flags[2]) is solve_ok = 0, and both words are cleared
 //   k_lm_commit    trial poses -> poses, for the attempt k_lm_decide accepted
 //   k_lm_finish    one wave: clears the stop word
+//   k_lm_lambda0_rows, k_lm_trial_pcg   the PCG route's (sgo_optimize_lm_pcg; sgo_lm.h has that chain):
+//                  max |diag(H)| over the rows of the linearisation; trial poses and x . (lambda x + b) from the solve's x and b
 // Streaming kernels at the launch floor for the graphs the multifrontal analysis admits (3 n doubles read and written per attempt,
 // against a factorisation of the whole arena); no atomics, vector stores only, every sum in a fixed order.
 #include <algorithm>
@@ -55,8 +57,9 @@ __global__ __launch_bounds__(kBlock) void k_lm_lambda0(MfDev M, LmDiagDev G, dou
   }
 }
 
-__global__ __launch_bounds__(64) void k_lm_begin(MfDev M, const double* __restrict__ partials, int nparts, const double* __restrict__ chi2,
-                                                 double lambda_init, int max_iters, LmState* __restrict__ st) {
+__global__ __launch_bounds__(64) void k_lm_begin(int* __restrict__ flags, const double* __restrict__ partials, int nparts,
+                                                 const double* __restrict__ chi2, double lambda_init, int max_iters,
+                                                 LmState* __restrict__ st) {
   double mx = 0.0;
   for (int q = threadIdx.x; q < nparts; q += 64) mx = fmax(mx, partials[q]);
 #pragma unroll
@@ -71,7 +74,7 @@ __global__ __launch_bounds__(64) void k_lm_begin(MfDev M, const double* __restri
   st->commit_at = -1;
   st->stop = max_iters == 0 ? 1 : 0;
   st->stop_reason = SGO_LM_STOP_MAX_ITERS;
-  if (max_iters == 0) M.flags[0] = kLmStopWord;
+  if (max_iters == 0 && flags) flags[0] = kLmStopWord;
 }
 
 __global__ __launch_bounds__(kBlock) void k_lm_trial(MfDev M, LmDiagDev G, const LmState* __restrict__ st, const double* __restrict__ poses,
@@ -96,16 +99,21 @@ __global__ __launch_bounds__(kBlock) void k_lm_trial(MfDev M, LmDiagDev G, const
   block_sum_store<1>(acc, partials, kMaxPartials);
 }
 
-__global__ __launch_bounds__(64) void k_lm_decide(MfDev M, const double* __restrict__ partials, int nparts, const double* __restrict__ chi2_trial,
-                                                  int attempt, int max_iters, LmState* __restrict__ st) {
-  const int f0 = M.flags[0];
+// flags: the multifrontal path's words, nullptr on the PCG route (sgo_lm.h); solve_ok: what the host says of the trial's solve (the
+// factor route hands in 1: its failures are the flag words')
+__global__ __launch_bounds__(64) void k_lm_decide(int* __restrict__ flags, int solve_ok, const double* __restrict__ partials, int nparts,
+                                                  const double* __restrict__ chi2_trial, int attempt, int max_iters,
+                                                  LmState* __restrict__ st) {
+  const int f0 = flags ? flags[0] : 0;
   if (f0 == kLmStopWord) return;
   double s = 0.0;
   for (int q = threadIdx.x; q < nparts; q += 64) s += partials[q];
   s = wave_sum(s);
   if (threadIdx.x != 0) return;
-  const int solve_ok = f0 == 0 && M.flags[2] == 0;
-  M.flags[0] = M.flags[1] = M.flags[2] = 0;
+  if (flags) {
+    solve_ok = solve_ok && f0 == 0 && flags[2] == 0;
+    flags[0] = flags[1] = flags[2] = 0;
+  }
   double lambda = st->lambda, nu = st->nu;
   const int code = rules::lm_trial(st->cur, chi2_trial[1], s + 1e-3, solve_ok, &lambda, &nu);
   st->lambda = lambda;
@@ -133,8 +141,48 @@ __global__ __launch_bounds__(64) void k_lm_decide(MfDev M, const double* __restr
   if (reason >= 0) {
     st->stop = 1;
     st->stop_reason = reason;
-    M.flags[0] = kLmStopWord;
+    if (flags) flags[0] = kLmStopWord;
   }
+}
+
+// ---- the PCG route (sgo_lm.h)
+__global__ __launch_bounds__(kBlock) void k_lm_lambda0_rows(int n, const double* __restrict__ dgb, double* __restrict__ partials) {
+  __shared__ double sm[kWavesPerBlock];
+  double mx = 0.0;
+  for (int i = blockIdx.x * kBlock + threadIdx.x; i < n; i += gridDim.x * kBlock) {
+    const double* d = dgb + 9 * (size_t)i;
+    mx = fmax(mx, fmax(fabs(d[0]), fmax(fabs(d[3]), fabs(d[5]))));   // D's upper triangle by rows: the diagonal is 0, 3, 5
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) mx = fmax(mx, __shfl_xor(mx, o, 64));
+  if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = mx;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int k = 1; k < kWavesPerBlock; ++k) mx = fmax(mx, sm[k]);
+    partials[blockIdx.x] = mx;
+  }
+}
+
+// One lane per free row: the trial pose of its vertex (k_pose_update's map and arithmetic, into the second pose buffer) when the
+// solve succeeded, and the row's share of x . (lambda x + b), summed per workgroup in block_sum_store's order.
+__global__ __launch_bounds__(kBlock) void k_lm_trial_pcg(int n, const int* __restrict__ free_id, const LmState* __restrict__ st, int solve_ok,
+                                                         const double* __restrict__ poses, const double* __restrict__ x,
+                                                         const double* __restrict__ b, double* __restrict__ trial_poses,
+                                                         double* __restrict__ partials) {
+  const double lambda = st->lambda;
+  double acc[1] = {0.0};
+  for (int i = blockIdx.x * kBlock + threadIdx.x; i < n; i += gridDim.x * kBlock) {
+    const size_t v = 3 * (size_t)free_id[i], o = 3 * (size_t)i;
+    const double x0 = x[o], x1 = x[o + 1], x2 = x[o + 2];
+    acc[0] += x0 * (lambda * x0 + b[o]) + x1 * (lambda * x1 + b[o + 1]) + x2 * (lambda * x2 + b[o + 2]);
+    if (solve_ok) {
+      trial_poses[v] = poses[v] + x0;
+      trial_poses[v + 1] = poses[v + 1] + x1;
+      trial_poses[v + 2] = norm_theta(poses[v + 2] + x2);
+    }
+  }
+  block_sum_store<1>(acc, partials, kMaxPartials);
 }
 
 __global__ __launch_bounds__(kBlock) void k_lm_commit(const LmState* __restrict__ st, int attempt, int V3, const double* __restrict__ trial_poses,
@@ -154,22 +202,29 @@ int lm_grid(int n) { return std::max(1, std::min((n + kBlock - 1) / kBlock, kMax
 void launch_lm_lambda0(hipStream_t s, const MfDev& M, const LmDiagDev& G, double* partials) {
   hipLaunchKernelGGL(k_lm_lambda0, dim3(lm_grid(M.n)), dim3(kBlock), 0, s, M, G, partials);
 }
-void launch_lm_begin(hipStream_t s, const MfDev& M, const double* partials, int nparts, const double* chi2, double lambda_init, int max_iters,
+void launch_lm_begin(hipStream_t s, int* flags, const double* partials, int nparts, const double* chi2, double lambda_init, int max_iters,
                      LmState* st) {
-  hipLaunchKernelGGL(k_lm_begin, dim3(1), dim3(64), 0, s, M, partials, nparts, chi2, lambda_init, max_iters, st);
+  hipLaunchKernelGGL(k_lm_begin, dim3(1), dim3(64), 0, s, flags, partials, nparts, chi2, lambda_init, max_iters, st);
 }
 void launch_lm_trial(hipStream_t s, const MfDev& M, const LmDiagDev& G, const LmState* st, const double* poses, double* trial_poses,
                      double* partials) {
   hipLaunchKernelGGL(k_lm_trial, dim3(lm_grid(M.n)), dim3(kBlock), 0, s, M, G, st, poses, trial_poses, partials);
 }
-void launch_lm_decide(hipStream_t s, const MfDev& M, const double* partials, int nparts, const double* chi2_trial, int attempt, int max_iters,
-                      LmState* st) {
-  hipLaunchKernelGGL(k_lm_decide, dim3(1), dim3(64), 0, s, M, partials, nparts, chi2_trial, attempt, max_iters, st);
+void launch_lm_decide(hipStream_t s, int* flags, int solve_ok, const double* partials, int nparts, const double* chi2_trial, int attempt,
+                      int max_iters, LmState* st) {
+  hipLaunchKernelGGL(k_lm_decide, dim3(1), dim3(64), 0, s, flags, solve_ok, partials, nparts, chi2_trial, attempt, max_iters, st);
 }
 void launch_lm_commit(hipStream_t s, const LmState* st, int attempt, int V3, const double* trial_poses, double* poses) {
   hipLaunchKernelGGL(k_lm_commit, dim3(std::max(1, std::min((V3 + kBlock - 1) / kBlock, kMaxGrid))), dim3(kBlock), 0, s, st, attempt, V3,
                      trial_poses, poses);
 }
 void launch_lm_finish(hipStream_t s, const MfDev& M) { hipLaunchKernelGGL(k_lm_finish, dim3(1), dim3(64), 0, s, M); }
+void launch_lm_lambda0_rows(hipStream_t s, int n, const double* dgb, double* partials) {
+  hipLaunchKernelGGL(k_lm_lambda0_rows, dim3(lm_grid(n)), dim3(kBlock), 0, s, n, dgb, partials);
+}
+void launch_lm_trial_pcg(hipStream_t s, int n, const int* free_id, const LmState* st, int solve_ok, const double* poses, const double* x,
+                         const double* b, double* trial_poses, double* partials) {
+  hipLaunchKernelGGL(k_lm_trial_pcg, dim3(lm_grid(n)), dim3(kBlock), 0, s, n, free_id, st, solve_ok, poses, x, b, trial_poses, partials);
+}
 
 }  // namespace sgo
