@@ -652,7 +652,7 @@ class BlockSolver : public Solver {
 };
 class OptimizationAlgorithm {
  public:
-  enum Kind { GaussNewton, Levenberg };
+  enum Kind { GaussNewton, Levenberg, Dogleg };
   explicit OptimizationAlgorithm(Kind k, std::unique_ptr<Solver> s) : _kind(k), _solver(std::move(s)) {}
   virtual ~OptimizationAlgorithm() {}
   Kind kind() const { return _kind; }
@@ -668,6 +668,11 @@ class OptimizationAlgorithmGaussNewton : public OptimizationAlgorithm {
 class OptimizationAlgorithmLevenberg : public OptimizationAlgorithm {
  public:
   explicit OptimizationAlgorithmLevenberg(std::unique_ptr<Solver> s) : OptimizationAlgorithm(Levenberg, std::move(s)) {}
+};
+// Powell's dogleg: pose-only SE(2) graphs on the device (sgo_optimize_dogleg / sgo_optimize_dogleg_pcg); there is no host solver for it
+class OptimizationAlgorithmDogleg : public OptimizationAlgorithm {
+ public:
+  explicit OptimizationAlgorithmDogleg(std::unique_ptr<Solver> s) : OptimizationAlgorithm(Dogleg, std::move(s)) {}
 };
 
 // g2o/core/sparse_block_matrix.h, as far as SparseOptimizer::computeMarginals' result needs it: the blocks asked for, by hessian
@@ -930,6 +935,7 @@ class SparseOptimizer : public OptimizableGraph {
     bool anyFree = false;
     for (auto* v : _activeVertices) anyFree = anyFree || !v->fixed();
     if (_activeVertices.empty() || !anyFree) return -1;
+    if (_algorithm->kind() == OptimizationAlgorithm::Dogleg) return deviceDogleg(iterations);
     if (levenbergOnDevice()) return deviceLevenberg(iterations);
     if (!gpuEligible()) return hostOptimize(iterations, online);
     if (!uploadGraph()) return 0;
@@ -1503,6 +1509,13 @@ class SparseOptimizer : public OptimizableGraph {
     int trials;
   };
   const std::vector<LmIteration>& lmTrace() const { return _lmTrace; }
+  // ... and of the last optimize() under OptimizationAlgorithmDogleg (g2o: lastStep(), trustRegion() and the verbose output):
+  // the trust region after the iteration, robust chi2 after it, its trials, the accepted step's kind (SGO_DL_STEP_*, -1: none)
+  struct DoglegIteration {
+    double delta, chi2;
+    int trials, step;
+  };
+  const std::vector<DoglegIteration>& doglegTrace() const { return _dlTrace; }
 
   void computeActiveErrors() {
     for (auto* e : _activeEdges) e->computeError();
@@ -1725,6 +1738,45 @@ class SparseOptimizer : public OptimizableGraph {
         std::cerr << "iteration= " << k << "\t chi2= " << st->chi2[k + 1] << "\t lambda= " << st->lambda[k] << "\t trials= " << st->trials[k]
                   << std::endl;
     downloadEstimates();
+    return done;
+  }
+
+  // Powell's dogleg, beside Levenberg's dispatch: sgo_optimize_dogleg -- g2o's schedule, one factorisation per iteration on the
+  // multifrontal factor --, or, for a graph the multifrontal analysis refuses, sgo_optimize_dogleg_pcg.  The library has no host
+  // solver for this algorithm: a graph the device path does not cover, or a registered terminate action, is refused with one line.
+  std::vector<DoglegIteration> _dlTrace;
+  int deviceDogleg(int iterations) {
+    _dlTrace.clear();
+    if (!deviceTypes()) {
+      std::cerr << "SparseOptimizer::optimize: OptimizationAlgorithmDogleg covers VertexSE2 / EdgeSE2 graphs with no kernel or a kernel of "
+                << "robust_kernel_impl.h only; refusing" << std::endl;
+      return 0;
+    }
+    if (_terminateAction) {
+      std::cerr << "SparseOptimizer::optimize: OptimizationAlgorithmDogleg takes sgo_optimize_dogleg, which applies no "
+                << "SparseOptimizerTerminateAction (remove the action, or use Gauss-Newton, whose device path applies it); refusing" << std::endl;
+      return 0;
+    }
+    if (!uploadGraph()) return 0;
+    if (std::strstr(sgo_solver_description(_ctx), "incremental overlay")) {   // (refused by the call: the full set-up, as deviceLevenberg)
+      _graphOnDevice = false;
+      if (!uploadGraph()) return 0;
+    }
+    _lastStats.reset();   // (lastStats() is the last Gauss-Newton call's: none now)
+    std::unique_ptr<sgo_dogleg_stats> st(new sgo_dogleg_stats());
+    int done = sgo_optimize_dogleg(_ctx, iterations, 0.0, st.get());
+    if (done == SGO_ENOTHING && sgo_num_free(_ctx) > 0) done = sgo_optimize_dogleg_pcg(_ctx, iterations, 0.0, st.get());
+    if (done < 0) {
+      std::cerr << "SparseOptimizer::optimize: " << sgo_last_error(_ctx) << (done == SGO_ENOTHING ? "; refusing" : "") << std::endl;
+      return 0;
+    }
+    for (int k = 0; k < st->iters_done; ++k) _dlTrace.push_back({st->delta[k], st->robust_chi2[k + 1], st->trials[k], st->step_kind[k]});
+    if (_verbose)
+      for (int k = 0; k < st->iters_done; ++k)
+        std::cerr << "iteration= " << k << "\t chi2= " << st->chi2[k + 1] << "\t delta= " << st->delta[k] << "\t trials= " << st->trials[k]
+                  << std::endl;
+    downloadEstimates();
+    if (st->stop_reason == SGO_DL_STOP_DAMPING) return 0;   // (g2o: Fail)
     return done;
   }
 

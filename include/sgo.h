@@ -309,6 +309,61 @@ int sgo_lm_trial_rule(double cur, double trial, double scale, int solve_ok, doub
 int sgo_optimize_lm_pcg(sgo_ctx* ctx, int32_t max_iters, double lambda_init /* <= 0: 1e-5 * max diag(H) */, sgo_lm_stats* out);
 int sgo_lm_pcg_trace(sgo_ctx* ctx, int32_t cap, int32_t* pcg_iters, int32_t* solve_stop);
 
+/* (later additions, version 107) Powell's dogleg.
+ * Replaces: SparseOptimizer::optimize(iters) with OptimizationAlgorithmDogleg on a pose-only SE(2) graph, with g2o 2020.5.29's
+ * schedule.  At iteration 0 of every call delta = delta_init (<= 0: 1e4), the damping lambda = 1e-7 and "H was positive definite in
+ * every iteration" holds.  An iteration solves the UNDAMPED system H g = b once -- H and b the robustified system of every kernel
+ * kind at the accepted poses -- and forms the Cauchy step alpha b, alpha = b.b / b.Hb.  Every trial of the iteration is a blend of
+ * those two fixed vectors, chosen by delta:
+ *     |g| < delta: h = g (GN);   else |alpha b| > delta: h = (delta / |alpha b|) alpha b (SD);   else the point of the segment
+ *     from alpha b to g at distance delta (DL).
+ * With the linear gain L = -h.Hh + 2 b.h (|L| < 1e-12: 1e-12) and rho = (robust chi2 at the accepted poses - at poses (+) h) / L the
+ * trial is accepted iff rho > 0 and the trial chi2 is finite; rho > 0.75: delta = max(delta, 3 |h|); rho < 0.25: delta *= 0.5.  One
+ * deviation from g2o: a trial chi2 or rho that is not finite counts as rho = -inf (rejected, delta halved).  An iteration repeats
+ * trials until one is accepted or 100 have run; the latter ends the call (SGO_DL_STOP_TRIALS; that iteration is counted).
+ * Damping applies only after a failed solve (a pivot that is not positive definite, a non-finite solution, on the PCG a solve that
+ * neither converged nor stands at its floating-point floor): lambda *= 10, beyond 1e3 the call ends (SGO_DL_STOP_DAMPING, poses at
+ * the accepted ones), otherwise the solve is repeated on H + lambda I, as is every later solve of the call, each success followed
+ * by lambda = max(1e-12, lambda / 5).  While no solve has failed nothing is added and the GN step is sgo_optimize_gn's to the bit
+ * on a multifrontal_cholesky context.
+ *
+ * sgo_dogleg_step_rule / sgo_dogleg_trial_rule are the two rules as the library and its kernels compile them (no context, no GPU).
+ * forms = {b.b, b.g, g.g, b.Hb, b.Hg, g.Hg}; the step is h = a b + c g; returns its kind (SGO_DL_STEP_*), or SGO_EINVAL for a NULL
+ * pointer.  The trial rule updates *delta in place and returns 1: accepted, 0: rejected.
+ *
+ * sgo_optimize_dogleg solves through the multifrontal factor (the route of sgo_optimize_lm: refusals, plan and what the call leaves
+ * are that call's; a graph the analysis refuses: SGO_ENOTHING, use sgo_optimize_dogleg_pcg or sgo_optimize_gn); the host queues one
+ * iteration per remaining iteration and reads the state once per round: sync_rounds is 1 for a call without a rejection and at
+ * most 1 + the rejected trials while H stays positive definite.  A rejected trial costs one chi2 pass and three small launches: no
+ * edge pass, no factorisation.  sgo_optimize_dogleg_pcg solves with the context's preconditioned conjugate gradients (the route
+ * of sgo_optimize_lm_pcg: every single-GPU context, a refreshed hierarchy and a cold solve per ITERATION; the state is read once per
+ * solve and once per group of re-trials).  `solves` counts factorisations or PCG solves: iters_done while H stayed positive
+ * definite, whatever trials_total is.
+ * Returns the iterations counted (`out` may be NULL).  robust_chi2[k + 1], chi2[k + 1], delta[k] are the values after iteration k,
+ * trials[k] its trials, step_kind[k] the accepted trial's kind (-1: none); robust_chi2[] never increases and the entries
+ * [iters_done] are what sgo_chi2 returns after the call, bit for bit.  Two calls from the same state return the same bits. */
+#define SGO_DL_STOP_MAX_ITERS 0   /* max_iters iterations counted */
+#define SGO_DL_STOP_TRIALS    1   /* 100 trials of one iteration rejected (g2o: Terminate) */
+#define SGO_DL_STOP_DAMPING   2   /* the damping passed 1e3 without a successful solve (g2o: Fail) */
+#define SGO_DL_STEP_GN 0
+#define SGO_DL_STEP_SD 1
+#define SGO_DL_STEP_DL 2
+typedef struct sgo_dogleg_stats {
+  int32_t iters_requested, iters_done, trials_total, solves, stop_reason, sync_rounds;
+  double  delta0;
+  double  delta[SGO_MAX_ITERS];           /* after iteration k */
+  double  robust_chi2[SGO_MAX_ITERS + 1]; /* [0] at the start, [k+1] at the accepted poses after iteration k */
+  double  chi2[SGO_MAX_ITERS + 1];        /* plain chi2, same indexing */
+  int32_t trials[SGO_MAX_ITERS];
+  int32_t step_kind[SGO_MAX_ITERS];       /* SGO_DL_STEP_* of the accepted trial; -1: none */
+  double  lambda;                         /* the last damping a solve used; 0 while H was always positive definite */
+  double  seconds_total;
+} sgo_dogleg_stats;
+int sgo_optimize_dogleg(sgo_ctx* ctx, int32_t max_iters, double delta_init /* <= 0: 1e4 */, sgo_dogleg_stats* out);
+int sgo_optimize_dogleg_pcg(sgo_ctx* ctx, int32_t max_iters, double delta_init /* <= 0: 1e4 */, sgo_dogleg_stats* out);
+int sgo_dogleg_step_rule(double delta, const double forms[6], double* a, double* c, double* step_norm, double* linear_gain); /* pure, no GPU */
+int sgo_dogleg_trial_rule(double cur, double trial, double linear_gain, double step_norm, double* delta);                    /* pure, no GPU */
+
 /* (later additions, version 107) Many closure hypotheses of the resident graph in one call: "is this set of
  * closures consistent", leave-one-out over a round's closures, cluster tests -- the same graph optimised once per hypothesis.
  *

@@ -41,6 +41,7 @@ SYMBOLS = [
     "sgo_edge_joint", "sgo_edge_groups", "sgo_edge_group_rule",
     "sgo_set_hypotheses_workspace", "sgo_hypotheses_bytes", "sgo_hypotheses_chunk", "sgo_hypotheses_workspace_bytes",
     "sgo_optimize_lm", "sgo_lm_trial_rule", "sgo_optimize_lm_pcg", "sgo_lm_pcg_trace",
+    "sgo_optimize_dogleg", "sgo_optimize_dogleg_pcg", "sgo_dogleg_step_rule", "sgo_dogleg_trial_rule",
 ]
 
 # SGO_JOINT_MAX_*: the limits of sgo_candidate_joint's table and of a subset of it
@@ -55,6 +56,10 @@ LM_STOP_MAX_ITERS, LM_STOP_TRIALS, LM_STOP_ZERO_GAIN, LM_STOP_LAMBDA = 0, 1, 2, 
 LM_RETRY, LM_ACCEPT, LM_ZERO_GAIN, LM_END = 0, 1, 2, 3
 # SGO_LM_SOLVE_*: how a trial's solve of sgo_optimize_lm_pcg ended (sgo_lm_pcg_trace; a failed solve: minus the PCG stop code)
 LM_SOLVE_CONVERGED, LM_SOLVE_FLOOR = 1, 2
+
+# SGO_DL_STOP_*: why sgo_optimize_dogleg ended; SGO_DL_STEP_*: the kind of a trial's step
+DL_STOP_MAX_ITERS, DL_STOP_TRIALS, DL_STOP_DAMPING = 0, 1, 2
+DL_STEP_GN, DL_STEP_SD, DL_STEP_DL = 0, 1, 2
 
 # SGO_HYP_*: the route sgo_optimize_gn_hypotheses took
 HYP_BATCHED, HYP_SEQUENTIAL = 1, 2
@@ -79,6 +84,24 @@ def lm_trial_rule(cur: float, trial: float, scale: float, solve_ok: bool, lam: f
     a, b = C.c_double(lam), C.c_double(nu)
     code = lib().sgo_lm_trial_rule(cur, trial, scale, int(bool(solve_ok)), C.byref(a), C.byref(b))
     return code, a.value, b.value
+
+
+def dogleg_step_rule(delta: float, forms):
+    """sgo_dogleg_step_rule: the step of one dogleg trial as the library (and its kernel) computes it, no context and no GPU:
+    forms = (b.b, b.g, g.g, b.Hb, b.Hg, g.Hg) of the right-hand side b and the Gauss-Newton step g -> (kind: one of DL_STEP_*,
+    a, c of the step a b + c g, its norm, the linear gain)."""
+    f = (C.c_double * 6)(*[float(x) for x in forms])
+    a, c, n, g = C.c_double(), C.c_double(), C.c_double(), C.c_double()
+    kind = lib().sgo_dogleg_step_rule(delta, f, C.byref(a), C.byref(c), C.byref(n), C.byref(g))
+    return kind, a.value, c.value, n.value, g.value
+
+
+def dogleg_trial_rule(cur: float, trial: float, linear_gain: float, step_norm: float, delta: float):
+    """sgo_dogleg_trial_rule: the decision of one dogleg trial as the library (and its kernel) computes it -> (accepted, delta
+    after the trial)."""
+    d = C.c_double(delta)
+    acc = lib().sgo_dogleg_trial_rule(cur, trial, linear_gain, step_norm, C.byref(d))
+    return bool(acc), d.value
 
 
 def edge_loo_rule(info6, P, e, w: float):
@@ -185,6 +208,19 @@ class LmStats(C.Structure):
                 ("seconds_total", C.c_double)]
 
 
+class DoglegStats(C.Structure):
+    """sgo_dogleg_stats (include/sgo.h)."""
+    _fields_ = [("iters_requested", C.c_int32), ("iters_done", C.c_int32), ("trials_total", C.c_int32), ("solves", C.c_int32),
+                ("stop_reason", C.c_int32), ("sync_rounds", C.c_int32), ("delta0", C.c_double),
+                ("delta", C.c_double * SGO_MAX_ITERS),
+                ("robust_chi2", C.c_double * (SGO_MAX_ITERS + 1)),
+                ("chi2", C.c_double * (SGO_MAX_ITERS + 1)),
+                ("trials", C.c_int32 * SGO_MAX_ITERS),
+                ("step_kind", C.c_int32 * SGO_MAX_ITERS),
+                ("lam", C.c_double),
+                ("seconds_total", C.c_double)]
+
+
 class HypothesisResult(C.Structure):
     """sgo_hypothesis_result (include/sgo.h)."""
     _fields_ = [("iters_done", C.c_int32), ("stop_reason", C.c_int32), ("chi2", C.c_double), ("robust_chi2", C.c_double)]
@@ -271,6 +307,10 @@ def lib():
     L.sgo_optimize_lm.argtypes = [vp, C.c_int32, C.c_double, C.POINTER(LmStats)]
     L.sgo_optimize_lm_pcg.argtypes = [vp, C.c_int32, C.c_double, C.POINTER(LmStats)]
     L.sgo_lm_pcg_trace.argtypes = [vp, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    L.sgo_optimize_dogleg.argtypes = [vp, C.c_int32, C.c_double, C.POINTER(DoglegStats)]
+    L.sgo_optimize_dogleg_pcg.argtypes = [vp, C.c_int32, C.c_double, C.POINTER(DoglegStats)]
+    L.sgo_dogleg_step_rule.argtypes = [C.c_double, C.POINTER(C.c_double), d, d, d, d]
+    L.sgo_dogleg_trial_rule.argtypes = [C.c_double, C.c_double, C.c_double, C.c_double, d]
     L.sgo_lm_trial_rule.argtypes = [C.c_double, C.c_double, C.c_double, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.sgo_optimize_gn_hypotheses.argtypes = [vp, C.c_int32, C.c_int32, C.c_double, u8, d, C.POINTER(HypothesisResult), d, d, d]
     L.sgo_hypothesis_isolated_vertex.restype = C.c_int32
@@ -698,6 +738,30 @@ class Optimizer:
             self._check(lib().sgo_lm_pcg_trace(self._h, n, its.ctypes.data_as(C.POINTER(C.c_int32)), how.ctypes.data_as(C.POINTER(C.c_int32))),
                         "sgo_lm_pcg_trace")
         return its, how
+
+    def optimize_dogleg(self, max_iters: int = 20, delta_init: float = 0.0):
+        """sgo_optimize_dogleg: Powell's dogleg with g2o's schedule, one factorisation per iteration on the multifrontal factor ->
+        (iterations counted, or -1 when the analysis refuses the graph (last_error() has the reason); stats dict: delta0, delta /
+        trials / step_kind per iteration, robust_chi2 / chi2 at the start and after every iteration, trials_total, solves,
+        stop_reason (one of DL_STOP_*), sync_rounds, lam: the last damping used)."""
+        st = DoglegStats()
+        rc = self._check(lib().sgo_optimize_dogleg(self._h, max_iters, delta_init, C.byref(st)), "sgo_optimize_dogleg")
+        return rc, self._dogleg_dict(rc, st)
+
+    def optimize_dogleg_pcg(self, max_iters: int = 20, delta_init: float = 0.0):
+        """sgo_optimize_dogleg_pcg: optimize_dogleg's schedule with the iteration's one solve done by the context's PCG, on every
+        single-GPU context and never refused for the graph's size -> (iterations counted, optimize_dogleg's stats dict)."""
+        st = DoglegStats()
+        rc = self._check(lib().sgo_optimize_dogleg_pcg(self._h, max_iters, delta_init, C.byref(st)), "sgo_optimize_dogleg_pcg")
+        return rc, self._dogleg_dict(rc, st)
+
+    @staticmethod
+    def _dogleg_dict(rc, st):
+        d = max(st.iters_done, 0)
+        return dict(rc=rc, iters_done=st.iters_done, trials_total=st.trials_total, solves=st.solves, stop_reason=st.stop_reason,
+                    sync_rounds=st.sync_rounds, delta0=st.delta0, delta=list(st.delta[:d]), trials=list(st.trials[:d]),
+                    step_kind=list(st.step_kind[:d]), robust_chi2=list(st.robust_chi2[: d + 1]), chi2=list(st.chi2[: d + 1]),
+                    lam=st.lam, seconds_total=st.seconds_total)
 
     def set_hypotheses_workspace(self, max_bytes: int) -> None:
         """sgo_set_hypotheses_workspace: the device memory optimize_hypotheses may take for per-hypothesis copies on a

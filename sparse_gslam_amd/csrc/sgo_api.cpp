@@ -388,6 +388,9 @@ void sgo_destroy(sgo_ctx* c) {
   if (c->lm.d_trial) hipFree(c->lm.d_trial);
   if (c->lm.d_scratch) hipFree(c->lm.d_scratch);
   if (c->lm.d_state) hipFree(c->lm.d_state);
+  if (c->dl.d_vec) hipFree(c->dl.d_vec);
+  if (c->dl.d_scratch) hipFree(c->dl.d_scratch);
+  if (c->dl.d_state) hipFree(c->dl.d_state);
   for (void* p : {(void*)c->joint.d_tab[0], (void*)c->joint.d_tab[1], (void*)c->joint.d_raw, (void*)c->joint.d_d2, (void*)c->joint.d_mask,
                   (void*)c->joint.d_grow, (void*)c->joint.d_gout, (void*)c->joint.d_gint, (void*)c->ejoint.d_tab[0], (void*)c->ejoint.d_tab[1],
                   (void*)c->ejoint.d_out, (void*)c->ejoint.d_mask})

@@ -307,6 +307,15 @@ struct sgo_ctx {
     std::vector<int32_t> pcg_iters, solve_stop;
   } lm;
 
+  // sgo_optimize_dogleg (sgo_dogleg.cpp) and sgo_optimize_dogleg_pcg: b and g by vertex [2][V][3], the call's scratch (sgo_dogleg.h:
+  // kDlScratchDoubles) and the device state; the trial poses are lm.d_trial.  Grown on demand, kept across graphs.
+  struct Dl {
+    double* d_vec = nullptr;
+    double* d_scratch = nullptr;
+    sgo::DlState* d_state = nullptr;
+    size_t vec_cap = 0, scratch_cap = 0, state_cap = 0;
+  } dl;
+
   // sgo_candidate_joint's table (sgo_fsolve.cpp): S [3 n][3 n], e [n][3] and the failure flag in tab[cur]; a call builds in the
   // other buffer and switches when it has succeeded, so a refusal or a failure keeps the resident table.  n < 0: no table.
   struct Joint {

@@ -47,6 +47,8 @@ int lm_prepare(sgo_ctx* c, Mfront* m) {
 
 namespace sgo {
 
+int lm_diag_prepare(sgo_ctx* c, Mfront* m) { return lm_prepare(c, m); }
+
 // (plain, robust) chi2 at `poses` into out2 by the very launches sgo_chi2 makes on this context, so that the call's history and
 // sgo_chi2 after it agree to the bit whatever path optimize() takes
 int lm_chi2(sgo_ctx* c, double* poses, double* out2) {
@@ -64,14 +66,14 @@ int lm_chi2(sgo_ctx* c, double* poses, double* out2) {
   return SGO_OK;
 }
 
-int lm_check_args(sgo_ctx* c, const char* name, int32_t max_iters, double lambda_init) {
+int lm_check_args(sgo_ctx* c, const char* name, int32_t max_iters, double lambda_init, const char* what) {
   const std::string who(name);
   if (max_iters < 0 || max_iters > SGO_MAX_ITERS) {
     c->err = who + ": max_iters must be in [0, SGO_MAX_ITERS]";
     return SGO_EINVAL;
   }
   if (!std::isfinite(lambda_init)) {
-    c->err = who + ": lambda_init is not finite";
+    c->err = who + ": " + what + " is not finite";
     return SGO_EINVAL;
   }
   if (c->ov.active) {

@@ -71,8 +71,11 @@ void launch_lm_trial_pcg(hipStream_t s, int n, const int* free_id, const LmState
 // the host side both routes share (sgo_lm.cpp)
 struct sgo_ctx;
 namespace sgo {
-// the argument checks of sgo_optimize_lm and sgo_optimize_lm_pcg (`name` in the error text): SGO_EINVAL with nothing changed
-int lm_check_args(sgo_ctx* c, const char* name, int32_t max_iters, double lambda_init);
+// the argument checks of sgo_optimize_lm, sgo_optimize_lm_pcg and the dogleg calls (`name` and the third argument's name `what` in the
+// error text): SGO_EINVAL with nothing changed
+int lm_check_args(sgo_ctx* c, const char* name, int32_t max_iters, double lambda_init, const char* what = "lambda_init");
 // (plain, robust) chi2 at `poses` into out2 by the very launches sgo_chi2 makes on this context
 int lm_chi2(sgo_ctx* c, double* poses, double* out2);
+// the free poses' diagonal targets (LmDiagDev) of the plan on the device, once per plan (sgo_optimize_dogleg shares them)
+int lm_diag_prepare(sgo_ctx* c, Mfront* m);
 }  // namespace sgo

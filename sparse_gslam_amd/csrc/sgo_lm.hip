@@ -24,20 +24,6 @@
 namespace sgo {
 namespace {
 
-// this pose's diagonal terms of the elements: the six entries of D and the three of b of every contribution to target t, added to acc
-__device__ __forceinline__ void lm_target_terms(const MfDev& M, int t, double (&acc)[9]) {
-  const MfTarget T = M.targets[t];
-  for (int c = T.c0; c < T.c1; ++c) {
-    const int w = M.contrib[c];
-    const double* el = M.elem + (size_t)kElemStride * (w >> 2);
-    const int side = w & 1;
-#pragma unroll
-    for (int q = 0; q < 6; ++q) acc[q] += el[6 * side + q];
-#pragma unroll
-    for (int q = 0; q < 3; ++q) acc[6 + q] += el[21 + 3 * side + q];
-  }
-}
-
 __global__ __launch_bounds__(kBlock) void k_lm_lambda0(MfDev M, LmDiagDev G, double* __restrict__ partials) {
   __shared__ double sm[kWavesPerBlock];
   double mx = 0.0;

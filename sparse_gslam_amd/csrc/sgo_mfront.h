@@ -148,6 +148,7 @@ hipError_t mfront_factorize(Mfront* m, hipStream_t s, const EdgeListDev& el, con
 // merge, panels and substitution per level for (H + lambda I) x = b with lambda read from *st on the device.  Both obey the flags
 // word and neither clears it.
 struct LmState;
+struct DlState;   // (sgo_dogleg.h: the state of sgo_optimize_dogleg, which solves through the same two shares)
 void mfront_lm_edges(Mfront* m, hipStream_t s, const EdgeListDev& el, const double* d_poses, double* d_hist, DirectResult* d_res);
 void mfront_lm_solve(Mfront* m, hipStream_t s, const LmState* st, double* d_hist, DirectResult* d_res);
 // Test hook (sgo_debug_mfront_array): one resident array as stored after the last mfront_optimize or selected inversion;

@@ -149,6 +149,20 @@ struct LmDiagDev {
   const int* ptr = nullptr;   // [n + 1]
   const int* tgt = nullptr;
 };
+// a pose's diagonal terms of the elements: the six entries of D and the three of b of every contribution to target t, added to acc
+// (k_lm_lambda0, k_lm_trial; k_dl_vectors of sgo_dogleg.hip)
+__device__ __forceinline__ void lm_target_terms(const MfDev& M, int t, double (&acc)[9]) {
+  const MfTarget T = M.targets[t];
+  for (int c = T.c0; c < T.c1; ++c) {
+    const int w = M.contrib[c];
+    const double* el = M.elem + (size_t)kElemStride * (w >> 2);
+    const int side = w & 1;
+#pragma unroll
+    for (int q = 0; q < 6; ++q) acc[q] += el[6 * side + q];
+#pragma unroll
+    for (int q = 0; q < 3; ++q) acc[6 + q] += el[21 + 3 * side + q];
+  }
+}
 
 // The joint table of sgo_candidate_joint (sgo_fsolve.hip): S [3 n][3 n] row-major, then e [n][3], then one double: the
 // factorisation's failure flag

@@ -63,6 +63,71 @@ SGO_RULE_HD inline int lm_trial(double cur, double trial, double scale, int solv
   return rho < 0.0 ? kLmRetry : (rho == 0.0 ? kLmZeroGain : kLmEnd);
 }
 
+// The step of one trial of sgo_optimize_dogleg (g2o 2020.5.29's OptimizationAlgorithmDogleg::solve).  With b
+// the right-hand side and g the Gauss-Newton step of H g = b, forms = {b.b, b.g, g.g, b.Hb, b.Hg, g.Hg}; the Cauchy step is
+// alpha b with alpha = b.b / b.Hb.  Every step is h = a b + c g:
+//   kDlGn  |g| < delta:            h = g                                  (a = 0, c = 1: the caller copies g)
+//   kDlSd  else |alpha b| > delta: h = (delta / |alpha b|) alpha b
+//   kDlDl  else:                   h = alpha b + beta (g - alpha b), with d = g - alpha b, k = alpha b . d, s2 = |alpha b|^2,
+//                                  D = sqrt(k^2 + |d|^2 (delta^2 - s2)), beta = (-k + D) / |d|^2 if k <= 0, else (delta^2 - s2) / (k + D)
+// step_norm = |h| and the linear gain L = -h.Hh + 2 b.h follow from the six forms; |L| < 1e-12 gives L = 1e-12.  `double`,
+// comparisons and sqrt only: the host (sgo_dogleg_step_rule) and k_dl_trial compile this text.
+constexpr int kDlMaxTrials = 100;
+constexpr int kDlGn = 0, kDlSd = 1, kDlDl = 2;
+constexpr double kDlDeltaInit = 1e4, kDlLambdaInit = 1e-7, kDlLambdaFactor = 10.0, kDlLambdaMin = 1e-12, kDlLambdaMax = 1e3;
+SGO_RULE_HD inline int dogleg_step(double delta, const double* forms, double* a, double* c, double* step_norm, double* linear_gain) {
+  const double bb = forms[0], bg = forms[1], gg = forms[2], bHb = forms[3], bHg = forms[4], gHg = forms[5];
+  const double alpha = bb / bHb;
+  const double gn_norm = std::sqrt(gg), s2 = alpha * alpha * bb, sd_norm = std::sqrt(s2);
+  int kind;
+  double ca, cc;
+  if (gn_norm < delta) {
+    kind = kDlGn;
+    ca = 0.0;
+    cc = 1.0;
+  } else if (sd_norm > delta) {
+    kind = kDlSd;
+    ca = (delta / sd_norm) * alpha;
+    cc = 0.0;
+  } else {
+    kind = kDlDl;
+    const double k = alpha * bg - s2;                         // alpha b . (g - alpha b)
+    const double d2 = (gg - 2.0 * alpha * bg) + s2;           // |g - alpha b|^2
+    const double gap = delta * delta - s2;
+    const double D = std::sqrt(k * k + d2 * gap);
+    const double beta = k <= 0.0 ? (-k + D) / d2 : gap / (k + D);
+    ca = alpha * (1.0 - beta);
+    cc = beta;
+  }
+  *a = ca;
+  *c = cc;
+  *step_norm = std::sqrt((ca * ca * bb + 2.0 * ca * cc * bg) + cc * cc * gg);
+  double L = -((ca * ca * bHb + 2.0 * ca * cc * bHg) + cc * cc * gHg) + 2.0 * (ca * bb + cc * bg);
+  if (L < 1e-12 && L > -1e-12) L = 1e-12;
+  *linear_gain = L;
+  return kind;
+}
+
+// ... and its decision.  cur: the robust chi2 at the accepted poses; trial: at the trial poses.  rho = (cur - trial) / L; the trial
+// is accepted iff rho > 0 and the trial chi2 is finite; rho > 0.75: delta = max(delta, 3 |h|); rho < 0.25: delta *= 0.5.  A trial
+// chi2 or a rho that is not finite counts as rho = -inf -- rejected, delta halved -- where g2o would repeat the identical trial.
+// Returns 1: accepted, 0: rejected.  The host (sgo_dogleg_trial_rule) and k_dl_decide compile this text.
+SGO_RULE_HD inline int dogleg_trial(double cur, double trial, double linear_gain, double step_norm, double* delta) {
+  if (linear_gain < 1e-12 && linear_gain > -1e-12) linear_gain = 1e-12;
+  const double rho = (cur - trial) / linear_gain;
+  if (!(trial - trial == 0.0) || !(rho - rho == 0.0)) {   // (x - x == 0: x is finite)
+    *delta *= 0.5;
+    return 0;
+  }
+  if (rho > 0.75) {
+    const double wide = 3.0 * step_norm;
+    if (wide > *delta) *delta = wide;
+  } else if (rho < 0.25) {
+    *delta *= 0.5;
+  }
+  return rho > 0.0 ? 1 : 0;
+}
+
 // The leave-one-out rule of sgo_edge_leave_one_out: what sgo_candidate_gate would say about a resident edge
 // had it never been inserted, from the edge's own quantities alone.  info: Omega's upper triangle by rows; P = J Sigma J^T at the
 // current poses WITH the edge in H (row-major, symmetric); e its error; w its kernel weight.  With Omega = G G^T (lower Cholesky),
