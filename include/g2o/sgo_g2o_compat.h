@@ -1133,6 +1133,72 @@ class SparseOptimizer : public OptimizableGraph {
     return rc;
   }
 
+  // ---- the covariance-aware closure search (extension; sgo_closure_search of include/sgo.h): every listed vertex j against every
+  // query vertex c at the current estimates, from one selected inversion and one panel solve.  With nq queries and n listed
+  // vertices, pair (q, t) at q n + t: (*m2) is the squared Mahalanobis distance (1 degree of freedom) from c's position in j's frame
+  // to the half-plane that contains the disc of `radius`, (*rel)[3 ..] the pose of c in j's frame, (*sigma)[2 ..] the 1-sigma linear
+  // and angular half-widths of a matcher's window in j's frame, (*near) = m2 <= chi2Max && j != c && |j - c| >= minSep, counted in
+  // the order of the active vertices (their ids where those are 0 .. V-1).  It replaces a Euclidean distance threshold on the
+  // estimates and a fixed search window.  Returns the number of near pairs.  Returns -1 with one line on std::cerr, the outputs
+  // untouched, where sgoEdgeLeaveOneOut does, for a vertex that is not an active vertex of the graph, and when the call itself
+  // refuses (sgo_last_error's text).
+  int sgoClosureSearch(const std::vector<int>& queryIds, const std::vector<int>& ids, double radius, double chi2Max, int minSep,
+                       std::vector<double>* m2, std::vector<double>* rel, std::vector<double>* sigma, std::vector<bool>* near) {
+    if (!_algorithm || !gpuEligible()) {
+      std::cerr << "SparseOptimizer::sgoClosureSearch: only the device path (VertexSE2 / EdgeSE2 under Gauss-Newton) has this search" << std::endl;
+      return -1;
+    }
+    if (_activeRevision != _revision || _activeVertices.empty()) {
+      std::cerr << "SparseOptimizer::sgoClosureSearch: the graph changed since the last initializeOptimization" << std::endl;
+      return -1;
+    }
+    const size_t nq = queryIds.size(), n = ids.size();
+    std::vector<int32_t> qc(nq + 1), jc(n + 1);   // (never a null list, whatever the counts)
+    for (size_t k = 0; k < nq + n; ++k) {
+      const int id = k < nq ? queryIds[k] : ids[k - nq];
+      // (the compact number uploadGraph gives: the vertex's place among the active vertices, which are sorted by id)
+      auto it = std::lower_bound(_activeVertices.begin(), _activeVertices.end(), id,
+                                 [](const OptimizableGraph::Vertex* a, int i) { return a->id() < i; });
+      if (it == _activeVertices.end() || (*it)->id() != id) {
+        std::cerr << "SparseOptimizer::sgoClosureSearch: vertex " << id << " is not an active vertex of the graph" << std::endl;
+        return -1;
+      }
+      (k < nq ? qc[k] : jc[k - nq]) = (int32_t)(it - _activeVertices.begin());
+    }
+    if (!uploadGraph()) return -1;
+    std::vector<double> mm(nq * n + 1), rr(3 * nq * n + 1), ss(2 * nq * n + 1);
+    std::vector<uint8_t> nn(nq * n + 1);
+    const int rc = sgo_closure_search(_ctx, (int32_t)nq, qc.data(), (int32_t)n, jc.data(), radius, chi2Max, (int32_t)minSep, mm.data(), rr.data(), nullptr,
+                                      ss.data(), nn.data());
+    if (rc < 0) {
+      std::cerr << "SparseOptimizer::sgoClosureSearch: " << sgo_last_error(_ctx) << std::endl;
+      return -1;
+    }
+    if (m2) m2->assign(mm.begin(), mm.begin() + nq * n);
+    if (rel) rel->assign(rr.begin(), rr.begin() + 3 * nq * n);
+    if (sigma) sigma->assign(ss.begin(), ss.begin() + 2 * nq * n);
+    if (near) {
+      near->resize(nq * n);
+      for (size_t t = 0; t < nq * n; ++t) (*near)[t] = nn[t] != 0;
+    }
+    return rc;
+  }
+  // ... with the vertices themselves
+  int sgoClosureSearch(const std::vector<const OptimizableGraph::Vertex*>& queries, const std::vector<const OptimizableGraph::Vertex*>& vertices,
+                       double radius, double chi2Max, int minSep, std::vector<double>* m2, std::vector<double>* rel, std::vector<double>* sigma,
+                       std::vector<bool>* near) {
+    std::vector<int> q, j;
+    for (size_t k = 0; k < queries.size() + vertices.size(); ++k) {
+      const OptimizableGraph::Vertex* v = k < queries.size() ? queries[k] : vertices[k - queries.size()];
+      if (!v) {
+        std::cerr << "SparseOptimizer::sgoClosureSearch: a null vertex in the lists" << std::endl;
+        return -1;
+      }
+      (k < queries.size() ? q : j).push_back(v->id());
+    }
+    return sgoClosureSearch(q, j, radius, chi2Max, minSep, m2, rel, sigma, near);
+  }
+
   // ---- the leave-GROUP-out test of clusters of edges that are in the graph (extension; sgo_edge_joint / sgo_edge_groups of
   // include/sgo.h).  sgoEdgeJoint builds the table of the listed edges (at most SGO_JOINT_MAX_CANDIDATES, none twice) at the current
   // estimates and keeps it in the backend; returns their number.  sgoEdgeGroups: groups[b] lists the members of group b (indices

@@ -786,6 +786,53 @@ int sgo_edge_groups(sgo_ctx* ctx, int32_t n, int32_t B, const uint8_t* member /*
 int sgo_edge_group_rule(int32_t k, const double* info6 /*[k][6]*/, const double* N /*[3k][3k]*/, const double* e /*[3k]*/,
                         const double* w /*[k]*/, double* d2, double* pivot, int32_t* dof);
 
+/* (later additions, version 107) Covariance-aware closure search: all listed poses against each query pose, from one selected
+ * inversion and one panel solve per 85 queries.  The step BEFORE a match exists: which poses are worth
+ * matching against the query pose at all, and with what search window.  A fixed Euclidean threshold on the current estimates
+ * misses true revisits after a long loop (drift) and a fixed matcher window is far wider than needed right after a closure.
+ * Per query vertex c and listed vertex j at the CURRENT poses, with H and Sigma = H^-1 exactly sgo_marginals_selected's (the call
+ * assembles, factorises and selectively inverts itself):
+ *   rel      = (t, phi), t = R(theta_j)^T (p_c - p_j), phi = normalize(theta_c - theta_j): the pose of c in j's frame, EdgeSE2's
+ *              prediction for an edge j -> c (the matcher searches in the submap's frame)
+ *   A, B     = d rel / d x_j, d rel / d x_c: the Jacobians of an EdgeSE2 j -> c at the measurement whose rotation is the identity, so
+ *              that P is the covariance of rel itself in j's frame (the edge whose measurement is rel has R(-phi) P R(-phi)^T:
+ *              the same m2 and sigma)
+ *   cov_rel  = P = 1/2 (Q + Q^T), Q = A Sigma_jj A^T + A Sigma_jc B^T + B Sigma_cj A^T + B Sigma_cc B^T   (row-major, exactly
+ *              symmetric; a fixed endpoint drops out; both fixed: P = 0)
+ *   m2       = max(0, |t| - radius)^2 / (u^T P_tt u), u = t / |t|: the squared Mahalanobis distance from the relative translation
+ *              to the half-plane {y : u^T y <= radius}.  The half-plane contains the disc |y| <= radius (u^T y <= |y|), so m2 is a
+ *              lower bound of the distance to the disc: a pose the exact disc test would keep is never dropped.  1 degree of
+ *              freedom.  A zero excess gives m2 = 0 whatever the denominator, a positive excess over a zero denominator +inf.
+ *   sigma    = (sqrt(lambda_max(P_tt)), sqrt(P_phiphi)): the 1-sigma linear and angular half-widths of the matcher's window in j's
+ *              frame; the caller scales them
+ *   near     = m2 <= chi2_max && j != c && |j - c| >= min_sep
+ * j == c gives rel = 0, P = 0, m2 = 0, sigma = 0, near = 0.  ids == NULL: vertices 0 .. n-1, of which one without an edge gives NaN
+ * everywhere and near = 0.  Returns the number of near pairs, or a negative code.  nq == 0 or n == 0 returns 0.
+ * An answer does not depend on nq, n, the pair's place in either list or on which queries share a panel; an id or a query listed
+ * twice is answered twice; two calls at the same poses give the same bits.  Nothing of Sigma crosses to the host: Sigma_jj and
+ * Sigma_cc are read in place in the selected inverse, Sigma_jc for all j is the three columns H^-1 E_c of sgo_factor_solve's
+ * substitution through the same factorisation.  A fixed query costs no solve.  The plan is sgo_marginals_selected's (a graph on the
+ * direct path or the PCG gets one of its own); like that call this one writes only what every Gauss-Newton iteration recomputes,
+ * and scratch: a later sgo_optimize_gn has the bits of a context that never called.
+ * SGO_ENOTHING with the analysis' reason when the multifrontal analysis refuses the graph (there is no cheap Sigma_jj of every pose
+ * without a factor): gate a Euclidean shortlist with sgo_candidate_gate then.
+ * SGO_EINVAL, with nothing on the device changed and no output written: negative counts, a null query, a null m2 with nq n > 0,
+ * n > V without ids, an id or a query outside [0, V), a listed id or a query without an edge, radius negative or not finite,
+ * chi2_max not finite, min_sep < 0, an active overlay, a multi-GPU context (sgo_debug_set_shard's emulation included).
+ * SGO_EINVAL with the outputs untouched when the factorisation is not positive definite; the next sgo_optimize_gn is unaffected.
+ *
+ * sgo_closure_search_rule: one pair's arithmetic alone, as the kernel compiles it (sgo_rules.h; no context, no GPU, like
+ * sgo_edge_loo_rule): the poses xj, xc and the blocks Sjj, Sjc (the rows of j), Scc of Sigma, row-major; a NULL Sjj or Scc stands
+ * for a FIXED pose, which drops out with the cross block (Sjc may be NULL then).  rel [3], cov_rel [9] and sigma [2] may be NULL.
+ * No special case for j == c.  Returns 0, SGO_EINVAL for a null xj, xc or m2 or a null Sjc between two free poses. */
+int sgo_closure_search(sgo_ctx* ctx, int32_t nq, const int32_t* query /*[nq] vertex ids*/,
+                       int32_t n, const int32_t* ids /*NULL: vertices 0..n-1*/,
+                       double radius, double chi2_max, int32_t min_sep,
+                       double* m2 /*[nq][n]*/, double* rel /*[nq][n][3] or NULL*/, double* cov_rel /*[nq][n][9] or NULL*/,
+                       double* sigma /*[nq][n][2] or NULL*/, uint8_t* near /*[nq][n] or NULL*/);
+int sgo_closure_search_rule(const double xj[3], const double xc[3], const double Sjj[9], const double Sjc[9], const double Scc[9],
+                            double radius, double* rel, double* cov_rel, double* m2, double* sigma);   /* pure, no GPU */
+
 /* (later additions, version 107) Greedy search for a large jointly compatible set on the resident table of sgo_candidate_joint
  * (DESIGN.md section 5l): "which of these candidates form the largest consistent set?" without a from-scratch factorisation per
  * extension.  Growing a subset by one candidate is one step of a block-pivoted Cholesky of S.  After the ordered pivots t_1 .. t_k

@@ -38,7 +38,7 @@ SYMBOLS = [
     "sgo_gain_stop", "sgo_optimize_gn_until", "sgo_optimize_gn_hypotheses", "sgo_hypothesis_isolated_vertex",
     "sgo_candidate_joint", "sgo_joint_subsets", "sgo_joint_pairs", "sgo_edge_leave_one_out", "sgo_edge_loo_rule",
     "sgo_joint_greedy", "sgo_joint_extend", "sgo_joint_greedy_rule",
-    "sgo_edge_joint", "sgo_edge_groups", "sgo_edge_group_rule",
+    "sgo_edge_joint", "sgo_edge_groups", "sgo_edge_group_rule", "sgo_closure_search", "sgo_closure_search_rule",
     "sgo_set_hypotheses_workspace", "sgo_hypotheses_bytes", "sgo_hypotheses_chunk", "sgo_hypotheses_workspace_bytes",
     "sgo_optimize_lm", "sgo_lm_trial_rule", "sgo_optimize_lm_pcg", "sgo_lm_pcg_trace",
     "sgo_optimize_dogleg", "sgo_optimize_dogleg_pcg", "sgo_dogleg_step_rule", "sgo_dogleg_trial_rule",
@@ -129,6 +129,22 @@ def edge_group_rule(info6, N, e, w):
     d2, piv, dof = C.c_double(), C.c_double(), C.c_int32(-1)
     rc = lib().sgo_edge_group_rule(k, _dp(o), _dp(Nm), _dp(ev), _dp(wv), C.byref(d2), C.byref(piv), C.byref(dof))
     return rc, d2.value, piv.value, dof.value
+
+
+def closure_search_rule(xj, xc, Sjj, Sjc, Scc, radius: float):
+    """sgo_closure_search_rule: one pair's arithmetic of sgo_closure_search as the library (and its kernel) computes it, no context
+    and no GPU: the poses xj, xc (3,) and the blocks Sjj, Sjc (the rows of j), Scc (3, 3) of Sigma -> (rel (3,), cov_rel (3, 3), m2,
+    sigma (2,)).  Sjj or Scc None: that pose is fixed and drops out with the cross block."""
+    def blk(S):
+        return None if S is None else np.ascontiguousarray(S, dtype=np.float64).reshape(9)
+    a, b = np.ascontiguousarray(xj, dtype=np.float64).reshape(3), np.ascontiguousarray(xc, dtype=np.float64).reshape(3)
+    jj, jc, cc = blk(Sjj), blk(Sjc), blk(Scc)
+    rel, P, m2, sg = np.empty(3), np.empty((3, 3)), C.c_double(), np.empty(2)
+    rc = lib().sgo_closure_search_rule(_dp(a), _dp(b), None if jj is None else _dp(jj), None if jc is None else _dp(jc),
+                                       None if cc is None else _dp(cc), float(radius), _dp(rel), _dp(P), C.byref(m2), _dp(sg))
+    if rc < 0:
+        raise SgoError(f"sgo_closure_search_rule: rc={rc}")
+    return rel, P, m2.value, sg
 
 
 # SGO_JSTOP_*: why a search of sgo_joint_greedy ended
@@ -349,6 +365,8 @@ def lib():
     L.sgo_edge_joint.argtypes = [vp, C.c_int32, i32, d, d, d]
     L.sgo_edge_groups.argtypes = [vp, C.c_int32, C.c_int32, u8, d, C.c_double, d, i32, d, u8]
     L.sgo_edge_group_rule.argtypes = [C.c_int32, d, d, d, d, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32)]
+    L.sgo_closure_search.argtypes = [vp, C.c_int32, i32, C.c_int32, i32, C.c_double, C.c_double, C.c_int32, d, d, d, d, u8]
+    L.sgo_closure_search_rule.argtypes = [d, d, d, d, d, C.c_double, d, d, C.POINTER(C.c_double), d]
     L.sgo_joint_greedy_rule.argtypes = [C.c_int32, d, d, i32, u8, d, C.c_int32, i32, i32, i32, d, d]
     L.sgo_kernel_profile.argtypes = [vp, C.POINTER(KernelStat), C.c_int]
     L.sgo_kernel_profile_samples.argtypes = [vp, C.c_int, C.POINTER(C.c_float), C.c_int]
@@ -996,6 +1014,24 @@ class Optimizer:
         if rc < 0:
             raise SgoError(f"sgo_edge_leave_one_out: rc={rc}: " + lib().sgo_last_error(self._h).decode())
         return rc, d2, red, cov, fl.astype(bool)
+
+    def closure_search(self, query, ids, radius: float, chi2_max: float, min_sep: int = 0):
+        """sgo_closure_search: every listed pose j (None: every vertex) against every query pose c from one selected inversion and
+        one panel solve -> (count, m2 (nq, n), rel (nq, n, 3), cov_rel (nq, n, 3, 3), sigma (nq, n, 2), near (nq, n) bool): rel is
+        c in j's frame, cov_rel its covariance, m2 the squared Mahalanobis distance (1 degree of freedom) from rel's translation
+        to the half-plane that contains the disc of `radius`, sigma the 1-sigma linear and angular half-widths of a matcher's
+        window, near = m2 <= chi2_max and j != c and |j - c| >= min_sep; count = near.sum().  SgoError with rc=-1 when the
+        multifrontal analysis refuses the graph (gate a Euclidean shortlist with candidate_gate then)."""
+        q = np.ascontiguousarray(query, dtype=np.int32).reshape(-1)
+        j = None if ids is None else np.ascontiguousarray(ids, dtype=np.int32).reshape(-1)
+        nq, n = q.size, (self.V if j is None else j.size)
+        m2, rel, P, sg = np.empty((nq, n)), np.empty((nq, n, 3)), np.empty((nq, n, 3, 3)), np.empty((nq, n, 2))
+        nr = np.zeros((nq, n), dtype=np.uint8)
+        rc = lib().sgo_closure_search(self._h, nq, _ip(q), n, None if j is None else _ip(j), float(radius), float(chi2_max), int(min_sep),
+                                      _dp(m2), _dp(rel), _dp(P), _dp(sg), nr.ctypes.data_as(C.POINTER(C.c_uint8)))
+        if rc < 0:
+            raise SgoError(f"sgo_closure_search: rc={rc}: " + lib().sgo_last_error(self._h).decode())
+        return rc, m2, rel, P, sg, nr.astype(bool)
 
     def edge_joint(self, edge_ids):
         """sgo_edge_joint: the table of the listed resident edges at the current poses -> (N (3 n, 3 n), e (n, 3), w (n,)):

@@ -385,6 +385,8 @@ void sgo_destroy(sgo_ctx* c) {
   if (c->selinv.d_cidx) hipFree(c->selinv.d_cidx);
   if (c->selinv.d_loo) hipFree(c->selinv.d_loo);
   if (c->selinv.d_loo_ids) hipFree(c->selinv.d_loo_ids);
+  if (c->selinv.d_search) hipFree(c->selinv.d_search);
+  if (c->selinv.d_search_idx) hipFree(c->selinv.d_search_idx);
   if (c->lm.d_trial) hipFree(c->lm.d_trial);
   if (c->lm.d_scratch) hipFree(c->lm.d_scratch);
   if (c->lm.d_state) hipFree(c->lm.d_state);
@@ -1232,6 +1234,12 @@ int sgo_gain_stop(double last_robust_chi2, double robust_chi2, double gain_tol) 
 
 int sgo_edge_loo_rule(const double* info6, const double* P9, const double* e3, double w, double* d2, double* redundancy, double* cov_loo) {
   return rules::edge_loo(info6, P9, e3, w, d2, redundancy, cov_loo);
+}
+
+int sgo_closure_search_rule(const double xj[3], const double xc[3], const double Sjj[9], const double Sjc[9], const double Scc[9], double radius,
+                            double* rel, double* cov_rel, double* m2, double* sigma) {
+  if (!xj || !xc || !m2 || (Sjj && Scc && !Sjc)) return SGO_EINVAL;
+  return rules::closure_search(xj, xc, Sjj != nullptr, Scc != nullptr, Sjj, Sjc, Scc, radius, rel, cov_rel, m2, sigma);
 }
 
 int sgo_optimize_gn_until(sgo_ctx* c, int32_t max_iters, double gain_tol, sgo_stats* out, int32_t* stop_reason) {

@@ -293,6 +293,11 @@ struct sgo_ctx {
     double* d_loo = nullptr;
     int* d_loo_ids = nullptr;
     size_t loo_cap = 0, loo_ids_cap = 0;
+    // sgo_closure_search (sgo_search.cpp): one chunk's results [kCsOut][queries][n], the failure flag, the count, then the
+    // per-workgroup counts [kMaxPartials]; every vertex's elimination position [V], the listed ids [n], the chunk's queries (int4 each)
+    double* d_search = nullptr;
+    int* d_search_idx = nullptr;
+    size_t search_cap = 0, search_idx_cap = 0;
   } selinv;
 
   // sgo_optimize_lm (sgo_lm.cpp) and sgo_optimize_lm_pcg: the trial poses [V][3], the call's scratch (sgo_lm.h: kLmScratchDoubles) and the device state;

@@ -38,9 +38,11 @@ int refuse_context(sgo_ctx* c, const char* who) {
   return SGO_OK;
 }
 
+}  // namespace
+
 // The substitution's own device arrays, once per plan: the extend-add maps, every front's place in a panel's update buffer and
-// the hessian index of every elimination position.
-int fs_prepare(sgo_ctx* c, Mfront* m, const char* who) {
+// the hessian index of every elimination position.  (These three are sgo_closure_search's too: sgo_search.cpp.)
+int sgo::fs_prepare(sgo_ctx* c, Mfront* m, const char* who) {
   if (m->fs_ready) return SGO_OK;
   if (!fs_prepare_device()) {
     c->err = std::string(who) + ": the device does not grant the kernels' dynamic LDS";
@@ -69,10 +71,7 @@ int fs_prepare(sgo_ctx* c, Mfront* m, const char* who) {
 
 // One chunk's scratch: the panel after the forward pass (it holds the right-hand sides before), after the backward pass, and the
 // fronts' update buffers, all for `panels` panels.
-struct FsScratch {
-  double *Y = nullptr, *X = nullptr, *U = nullptr;
-};
-int fs_scratch(sgo_ctx* c, int n3, int U3, int panels, FsScratch* S) {
+int sgo::fs_scratch(sgo_ctx* c, int n3, int U3, int panels, FsScratch* S) {
   const size_t vec = (size_t)panels * kMfPanel * (size_t)n3, upd = (size_t)panels * kMfPanel * (size_t)U3;
   sgo_ctx::SelInv& Z = c->selinv;
   int rc;
@@ -84,7 +83,7 @@ int fs_scratch(sgo_ctx* c, int n3, int U3, int panels, FsScratch* S) {
 }
 
 // Both passes over the factor for the `panels` panels whose right-hand sides sit in S.Y
-void fs_passes(sgo_ctx* c, Mfront* m, const FsScratch& S, int panels, int ncols) {
+void sgo::fs_passes(sgo_ctx* c, Mfront* m, const FsScratch& S, int panels, int ncols) {
   const MfPlan& P = m->plan;
   const int n3 = 3 * P.n;
   const double pass_bytes = 8.0 * (double)P.arena_doubles * panels + 16.0 * kMfPanel * (double)panels * ((double)n3 + m->fs.U3);
@@ -101,6 +100,8 @@ void fs_passes(sgo_ctx* c, Mfront* m, const FsScratch& S, int panels, int ncols)
   m->fs_X = S.X;
   m->fs_cols = ncols;
 }
+
+namespace {
 
 int factorize(sgo_ctx* c, Mfront* m) {
   Scope sc(c, K_MF_FACTOR, mfront_bytes(m, c->E, 1), true);

@@ -390,6 +390,7 @@ enum KernelId : int {
   K_EDGE_TABLE,         // sgo_edge_joint / sgo_edge_groups: the resident-edge table's own kernels (sgo_egroup.hip)
   K_EDGE_GROUPS,
   K_LM,                 // sgo_optimize_lm: all launches of one call (sgo_lm.h)
+  K_CLOSURE_SEARCH,     // sgo_closure_search: the pair kernel after the selected inversion and the queries' panel solve (sgo_search.hip)
   K_COUNT
 };
 extern const char* const kKernelNames[K_COUNT];

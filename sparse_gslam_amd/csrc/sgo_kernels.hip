@@ -42,7 +42,7 @@ const char* const kKernelNames[K_COUNT] = {
     "k_mf_edges + k_mf_merge + k_mf_panels (multifrontal factor phase)", "k_si_gather", "k_si_panels", "k_si_result",
     "k_fs_rhs", "k_fs_forward", "k_fs_backward", "k_fs_gate", "k_fs_gram", "k_fs_joint_table", "k_joint_subsets",
     "mfront_batch", "k_loo_edges", "k_joint_grow", "k_edge_cands + k_edge_table", "k_edge_groups",
-    "lm attempts (multifrontal factor + k_lm_*)"};
+    "lm attempts (multifrontal factor + k_lm_*)", "k_closure_search"};
 
 namespace {
 

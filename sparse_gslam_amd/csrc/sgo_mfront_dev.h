@@ -236,6 +236,33 @@ void launch_fs_forward(hipStream_t s, const MfDev& M, const MfSelDev& Z, const M
 void launch_fs_backward(hipStream_t s, const MfDev& M, int lvl0, int count, int panels, size_t lds, const double* Y, double* X, int n3);
 void launch_fs_gate(hipStream_t s, const FsCandDev& C, int t0, int t1, const double* W, int n3, double chi2_max, const int* flags, double* out);
 bool fs_prepare_device();   // the two substitution kernels' dynamic LDS
+// What the calls that substitute through the factor share (sgo_fsolve.cpp): fs_prepare makes the substitution's own device arrays
+// (once per plan); fs_scratch hands out one chunk's scratch for `panels` panels -- the panel after the forward pass (it holds the
+// right-hand sides before), after the backward pass, and the fronts' update buffers --; fs_passes queues both passes over the factor
+// for the panels whose right-hand sides sit in S.Y (ncols of their columns are in use), after which S.X holds H^-1 of them.
+struct FsScratch {
+  double *Y = nullptr, *X = nullptr, *U = nullptr;
+};
+int fs_prepare(sgo_ctx* c, Mfront* m, const char* who);
+int fs_scratch(sgo_ctx* c, int n3, int U3, int panels, FsScratch* S);
+void fs_passes(sgo_ctx* c, Mfront* m, const FsScratch& S, int panels, int ncols);
+
+// ---- the closure search's kernels (sgo_search.hip); the host driver is sgo_search.cpp ----
+constexpr int kCsOut = 13;   // per pair: m2, rel (3), cov_rel's upper triangle by rows (6), sigma (2), near
+constexpr int kCsChunkQueries = kFsChunkPanels * kMfPanel / 3;   // queries per pass over the factor: three columns each, packed
+// A chunk's queries on the device: (vertex id, elimination position or -1 for a fixed pose, the first of its three columns in
+// the chunk's panel or -1 for a fixed pose, unused)
+typedef int4 CsQueryDev;
+// panel (zeroed) <- the unit columns of the chunk's free queries at their elimination positions
+void launch_cs_unit(hipStream_t s, int cq, const CsQueryDev* queries, int n3, double* panel);
+// out: [kCsOut][cq][n] (field, query, listed vertex), then the factorisation's failure flag, then the count of near pairs;
+// partials: [kMaxPartials].  vpos[v]: vertex v's elimination position, -1 for a fixed active vertex, -2 for one without an edge.
+// ids == nullptr: vertices 0 .. n-1.  factor == false: a graph without a free pose (M, Z and X are not read).  X: the chunk's
+// columns H^-1 E after fs_passes (column k at X + k n3, rows by elimination position).
+void launch_closure_search(hipStream_t s, const MfDev& M, const MfSelDev& Z, bool factor, const int* vpos, const double* poses, int n, const int* ids,
+                           int cq, const CsQueryDev* queries, const double* X, int n3, double radius, double chi2_max, int min_sep, double* out,
+                           double* partials);
+
 // ---- the joint table of a candidate set and its subsets (sgo_candidate_joint / sgo_joint_subsets / sgo_joint_pairs) ----
 // G[3 s + a][3 t + b] = Q_st[a][b] for every candidate s of C and the candidates t of [t0, t1), whose columns are W
 void launch_fs_gram(hipStream_t s, const FsCandDev& C, int t0, int t1, const double* W, int n3, double* G);

@@ -235,6 +235,85 @@ SGO_RULE_HD inline int edge_loo(const double* info, const double* P, const doubl
   return 0;
 }
 
+// The pair rule of sgo_closure_search: how far, in the metric of the graph's own uncertainty, the query pose c
+// is from lying within `radius` of the listed pose j, and how wide a matcher's window must be.  xj, xc: the poses (x, y, theta); Sjj,
+// Sjc, Scc: the blocks of Sigma = H^-1 (row-major; Sjc has the rows of j); free_j / free_c == false: that pose is FIXED and drops
+// out with its cross block (its blocks are not read).
+//   rel     = (t, phi), t = R(theta_j)^T (p_c - p_j), phi = normalize(theta_c - theta_j): c in j's frame, EdgeSE2's prediction j -> c
+//   A, B    = d rel / d x_j, d rel / d x_c: the Jacobians of an EdgeSE2 j -> c as edge_jacobians (sgo_device.h) forms them with
+//             sz = 0, cz = 1 (P is the covariance of rel in j's frame; an edge whose measurement is rel has R(-phi) P R(-phi)^T, the
+//             same m2 and sigma).  The products with 1 and 0 are exact, so the entries are written out:
+//             A = [-R^T | (t_y, -t_x)^T; 0 0 -1], B = [R^T 0; 0 0 1]
+//   cov_rel = P = 1/2 (Q + Q^T), Q = A Sjj A^T + A Sjc B^T + B Sjc^T A^T + B Scc B^T   (one triangle computed and mirrored)
+//   m2      = max(0, |t| - radius)^2 / (u^T P_tt u), u = t / |t|: the squared Mahalanobis distance from t to the half-plane
+//             {y : u^T y <= radius}, which contains the disc |y| <= radius (u^T y <= |y|), so m2 never exceeds the distance to the
+//             disc; 1 degree of freedom.  A zero excess gives 0 whatever the denominator; a positive excess over a denominator that
+//             is not above zero gives +inf (a NaN denominator gives NaN)
+//   sigma   = (sqrt(lambda_max(P_tt)), sqrt(P_phiphi)): the 1-sigma half-widths of the matcher's window in j's frame
+// Returns 0.  `double`, comparisons, sqrt, floor, sin and cos only: the host (sgo_closure_search_rule) and k_closure_search compile this text.
+SGO_RULE_HD inline double closure_norm_theta(double t) {   // g2o::normalize_theta, as norm_theta of sgo_device.h
+  const double pi = 3.14159265358979323846;
+  if (t >= -pi && t < pi) return t;
+  const double m = floor(t / (2 * pi));
+  t = t - m * 2 * pi;
+  if (t >= pi) t -= 2 * pi;
+  if (t < -pi) t += 2 * pi;
+  return t;
+}
+// Q += X S Y^T for 3 x 3 matrices (S row-major)
+SGO_RULE_HD inline void closure_xsyt(const double (&X)[3][3], const double* S, const double (&Y)[3][3], double (&Q)[3][3]) {
+  double XS[3][3];
+  for (int a = 0; a < 3; ++a)
+    for (int b = 0; b < 3; ++b) XS[a][b] = X[a][0] * S[b] + X[a][1] * S[3 + b] + X[a][2] * S[6 + b];
+  for (int a = 0; a < 3; ++a)
+    for (int b = 0; b < 3; ++b) Q[a][b] += XS[a][0] * Y[b][0] + XS[a][1] * Y[b][1] + XS[a][2] * Y[b][2];
+}
+SGO_RULE_HD inline int closure_search(const double* xj, const double* xc, bool free_j, bool free_c, const double* Sjj, const double* Sjc,
+                                      const double* Scc, double radius, double* rel, double* cov_rel, double* m2, double* sigma) {
+  const double si = sin(xj[2]), ci = cos(xj[2]);
+  const double ddx = xc[0] - xj[0], ddy = xc[1] - xj[1];
+  const double tx = ci * ddx + si * ddy, ty = -si * ddx + ci * ddy;
+  if (rel) {
+    rel[0] = tx;
+    rel[1] = ty;
+    rel[2] = closure_norm_theta(xc[2] - xj[2]);
+  }
+  const double A[3][3] = {{-ci, -si, ty}, {si, -ci, -tx}, {0.0, 0.0, -1.0}};
+  const double B[3][3] = {{ci, si, 0.0}, {-si, ci, 0.0}, {0.0, 0.0, 1.0}};
+  double Q[3][3] = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}};
+  if (free_j) closure_xsyt(A, Sjj, A, Q);
+  if (free_j && free_c) {
+    double St[9];
+    for (int a = 0; a < 3; ++a)
+      for (int b = 0; b < 3; ++b) St[3 * a + b] = Sjc[3 * b + a];
+    closure_xsyt(A, Sjc, B, Q);
+    closure_xsyt(B, St, A, Q);
+  }
+  if (free_c) closure_xsyt(B, Scc, B, Q);
+  double P[3][3];
+  for (int a = 0; a < 3; ++a)
+    for (int b = a; b < 3; ++b) P[a][b] = P[b][a] = 0.5 * (Q[a][b] + Q[b][a]);
+  if (cov_rel)
+    for (int a = 0; a < 3; ++a)
+      for (int b = 0; b < 3; ++b) cov_rel[3 * a + b] = P[a][b];
+  const double d = sqrt(tx * tx + ty * ty);
+  const double excess = d - radius;
+  if (excess > 0.0) {
+    const double ux = tx / d, uy = ty / d;
+    const double den = ux * (P[0][0] * ux + P[0][1] * uy) + uy * (P[1][0] * ux + P[1][1] * uy);
+    *m2 = den > 0.0 ? excess * excess / den : (den <= 0.0 ? HUGE_VAL : den);
+  } else {
+    *m2 = excess <= 0.0 ? 0.0 : excess;   // (a NaN pose stays NaN)
+  }
+  if (sigma) {
+    const double h = 0.5 * (P[0][0] - P[1][1]);
+    const double lam = 0.5 * (P[0][0] + P[1][1]) + sqrt(h * h + P[0][1] * P[0][1]);
+    sigma[0] = sqrt(lam < 0.0 ? 0.0 : lam);
+    sigma[1] = sqrt(P[2][2] < 0.0 ? 0.0 : P[2][2]);
+  }
+  return 0;
+}
+
 // The leave-group-out rule of sgo_edge_groups: sgo_edge_leave_one_out's question about k resident edges
 // removed together, from the rows idx[0 .. k) of a resident-edge table: N (symmetric, leading dimension ld; block (s, t) at
 // N[(3 idx[s] + a) ld + 3 idx[t] + b]) = 1/2 (Q + Q^T) with Q = J H^-1 J^T, e (3 per row), w (the kernel weights) and info6 (Omega's
