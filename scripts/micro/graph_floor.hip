@@ -1,8 +1,12 @@
 // graph_floor.hip -- what a kernel node of a replayed hipGraph costs on this GPU: chains of K launches captured into a graph,
 // kernels with D dependent loads (pointer chase through a small buffer), grids of 8 / 256 / 2048 workgroups of 256 threads.
 // hipcc --offload-arch=gfx950 -O3 graph_floor.hip -o graph_floor && ./graph_floor
+// The kernel-argument section compares two builds (./graph_floor kernarg runs that section alone): the line above, and
+// hipcc --offload-arch=gfx950 -O3 -mllvm -amdgpu-kernarg-preload-count=8 -DKERNARG_PRELOAD=8 graph_floor.hip -o graph_floor_preload
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include <cstdio>
+#include <cstring>
 #include <vector>
 
 template <int D>
@@ -133,6 +137,42 @@ __global__ __launch_bounds__(256) void k_barriers(unsigned* __restrict__ counter
   if (v == -12345) fail[1] = v;
 }
 
+// the load of the kernel's own arguments, the round trip at the head of every chain.  Built with
+// -mllvm -amdgpu-kernarg-preload-count=8 the plain leading parameters of k_chase arrive in user SGPRs (the descriptor's
+// kernarg_preload_length is 4); a by-value aggregate in front stops the preload at its position, so k_chase_s, the same chain
+// behind a struct, still waits for its kernarg load in the same binary.  Built without the flag both wait for it.
+struct ChaseArgs {
+  const int* next;
+  int* out;
+  int n;
+};
+template <int D>
+__global__ __launch_bounds__(256) void k_chase_s(ChaseArgs a) {
+  int i = (blockIdx.x * 256 + threadIdx.x) % a.n;
+#pragma unroll
+  for (int d = 0; d < D; ++d) i = a.next[i];
+  if (D == 0 || i == -1) a.out[blockIdx.x * 256 + threadIdx.x] = i;
+  if (D > 0 && threadIdx.x == 0 && blockIdx.x == 0) a.out[0] = i;
+}
+// the solver's prologue: a stop flag behind one pointer, then a group bound behind a second one, then the operands
+struct FlagArgs {
+  const int* stop;
+  const int* grp;
+  const int* x;
+  int* out;
+};
+__global__ __launch_bounds__(256) void k_flag_p(const int* __restrict__ stop, const int* __restrict__ grp, const int* __restrict__ x,
+                                                int* __restrict__ out) {
+  const int g0 = grp[blockIdx.x];
+  if (*stop) return;
+  out[blockIdx.x * 256 + threadIdx.x] = x[(g0 + threadIdx.x) & 65535];
+}
+__global__ __launch_bounds__(256) void k_flag_s(FlagArgs a) {
+  const int g0 = a.grp[blockIdx.x];
+  if (*a.stop) return;
+  a.out[blockIdx.x * 256 + threadIdx.x] = a.x[(g0 + threadIdx.x) & 65535];
+}
+
 template <int D>
 double run(hipStream_t s, const int* next, int* out, int n, int grid, int K, int reps) {
   hipGraph_t g;
@@ -157,7 +197,50 @@ double run(hipStream_t s, const int* next, int* out, int n, int grid, int K, int
   return 1e3 * ms / (reps * K);
 }
 
-int main() {
+#ifndef KERNARG_PRELOAD
+#define KERNARG_PRELOAD 0   // what the build line passed as -amdgpu-kernarg-preload-count, for the label only
+#endif
+// median of 7 timings of a replayed chain of K nodes, alternating the two forms so that drift hits both alike
+template <class FA, class FB>
+void kernarg_pair(const char* what, hipStream_t s, int K, int reps, FA plain, FB behind_struct) {
+  double a[7], b[7];
+  for (int r = 0; r < 7; ++r) {
+    a[r] = run_any(s, K, reps, plain);
+    b[r] = run_any(s, K, reps, behind_struct);
+  }
+  std::sort(a, a + 7);
+  std::sort(b, b + 7);
+  std::printf("%-34s plain leading parameters %.3f us (min %.3f)   behind a struct %.3f us (min %.3f)   difference %+.3f us per node\n", what,
+              a[3], a[0], b[3], b[0], b[3] - a[3]);
+}
+void kernarg_section(hipStream_t s, const int* next, int* out, int n, const int* stop) {
+  std::printf("kernel arguments, built with -amdgpu-kernarg-preload-count=%d (%s):\n", KERNARG_PRELOAD,
+              KERNARG_PRELOAD ? "plain leading parameters preloaded into SGPRs, a struct in front is not" : "nothing preloaded, both forms load their arguments");
+  const int K = 64, reps = 50;
+  for (int grid : {8, 256}) {
+    char what[64];
+    ChaseArgs ca{next, out, n};
+    std::snprintf(what, sizeof what, "grid %3d, chain of 1 load:", grid);
+    kernarg_pair(what, s, K, reps, [&](int) { hipLaunchKernelGGL(k_chase<1>, dim3(grid), dim3(256), 0, s, next, out, n); },
+                 [&](int) { hipLaunchKernelGGL(k_chase_s<1>, dim3(grid), dim3(256), 0, s, ca); });
+    std::snprintf(what, sizeof what, "grid %3d, chain of 4 loads:", grid);
+    kernarg_pair(what, s, K, reps, [&](int) { hipLaunchKernelGGL(k_chase<4>, dim3(grid), dim3(256), 0, s, next, out, n); },
+                 [&](int) { hipLaunchKernelGGL(k_chase_s<4>, dim3(grid), dim3(256), 0, s, ca); });
+    // a kernel long enough (about 3 us) for the command processor to have read the next node's packet before it ends
+    std::snprintf(what, sizeof what, "grid %3d, chain of 12 loads:", grid);
+    kernarg_pair(what, s, K, reps, [&](int) { hipLaunchKernelGGL(k_chase<12>, dim3(grid), dim3(256), 0, s, next, out, n); },
+                 [&](int) { hipLaunchKernelGGL(k_chase_s<12>, dim3(grid), dim3(256), 0, s, ca); });
+    std::snprintf(what, sizeof what, "grid %3d, chain of 24 loads:", grid);
+    kernarg_pair(what, s, K, reps, [&](int) { hipLaunchKernelGGL(k_chase<24>, dim3(grid), dim3(256), 0, s, next, out, n); },
+                 [&](int) { hipLaunchKernelGGL(k_chase_s<24>, dim3(grid), dim3(256), 0, s, ca); });
+    FlagArgs fa{stop, next, next, out};
+    std::snprintf(what, sizeof what, "grid %3d, stop flag + group bound:", grid);
+    kernarg_pair(what, s, K, reps, [&](int) { hipLaunchKernelGGL(k_flag_p, dim3(grid), dim3(256), 0, s, stop, next, next, out); },
+                 [&](int) { hipLaunchKernelGGL(k_flag_s, dim3(grid), dim3(256), 0, s, fa); });
+  }
+}
+
+int main(int argc, char** argv) {
   const int n = 1 << 16;
   std::vector<int> h(n);
   for (int i = 0; i < n; ++i) h[i] = (int)(((long long)i * 40503 + 12345) % n);
@@ -168,6 +251,13 @@ int main() {
   hipStream_t s;
   hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
   const int K = 64, reps = 50;
+  {
+    int* stop;
+    hipMalloc(&stop, sizeof(int));
+    hipMemset(stop, 0, sizeof(int));
+    kernarg_section(s, next, out, n, stop);
+    if (argc > 1 && std::strcmp(argv[1], "kernarg") == 0) return 0;   // only this section
+  }
   for (int grid : {8, 256, 2048}) {
     std::printf("grid %4d: D=0 %.2f us  D=1 %.2f  D=2 %.2f  D=3 %.2f  D=4 %.2f  D=6 %.2f per node\n", grid, run<0>(s, next, out, n, grid, K, reps),
                 run<1>(s, next, out, n, grid, K, reps), run<2>(s, next, out, n, grid, K, reps), run<3>(s, next, out, n, grid, K, reps),

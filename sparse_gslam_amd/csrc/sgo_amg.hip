@@ -316,13 +316,14 @@ __global__ __launch_bounds__(kBlock) void k_filtered_diag(BsrDev F, const int* _
 // (filtered smoothing, P.dF != nullptr: the listed slots are the kept ones, D_F in place of D_i -- also for the diagonal slot's
 // own term)
 // (multi-GPU, row-owner mode: the entries of the rows [row0, row1) only; row1 == 0: all)
-__global__ __launch_bounds__(kBlock) void k_p_values(BsrDev F, PDev P, const int* __restrict__ agg,
+// (grp = P.val.grp, ngrp = P.val.ngrp: the first requests, leading parameters)
+__global__ __launch_bounds__(kBlock) void k_p_values(const int* __restrict__ grp, int ngrp, BsrDev F, PDev P, const int* __restrict__ agg,
                                                      const double* __restrict__ d, double omega_p, int row0, int row1) {
   const int lane = threadIdx.x & 63;
   int gi, gend, gstride;
-  group_walk(P.val.ngrp, &gi, &gend, &gstride);
+  group_walk(ngrp, &gi, &gend, &gstride);
   for (; gi < gend; gi += gstride) {
-    const int gb = P.val.grp[gi], ge = P.val.grp[gi + 1];
+    const int gb = grp[gi], ge = grp[gi + 1];
     double acc[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
     int key = -1 - lane;
     for (int t = gb + lane; t < ge; t += 64) {
@@ -399,23 +400,23 @@ __global__ __launch_bounds__(kBlock) void k_p_values(BsrDev F, PDev P, const int
 // that a record is five 16-byte-aligned loads instead of nine 8-byte ones -- A P 474 us, P^T A P 165 us: bytes, not load
 // instructions, are what the gathers pay for.)
 template <bool X_BSR, bool TRANSPOSE_X, bool OUT_BSR>
-__global__ __launch_bounds__(kBlock) void k_block_products(ProdMap mp, BsrDev XA, const double* __restrict__ X,
-                                                           const double* __restrict__ Y,
+__global__ __launch_bounds__(kBlock) void k_block_products(const int* __restrict__ grp, int ngrp, ProdMap mp, BsrDev XA,
+                                                           const double* __restrict__ X, const double* __restrict__ Y,
                                                            double* __restrict__ out, size_t nout, const int* __restrict__ mirror,
                                                            const int* __restrict__ rowof, int row0, int row1, int keep_key) {
   const int lane = threadIdx.x & 63;
   int gi, gend, gstride;
-  group_walk(mp.ngrp, &gi, &gend, &gstride);
+  group_walk(ngrp, &gi, &gend, &gstride);   // (grp = mp.grp, ngrp = mp.ngrp: leading parameters)
   int ngb = 0, nge = 0;   // the next group's bounds are requested while the current group is worked on
   if (gi < gend) {
-    ngb = mp.grp[gi];
-    nge = mp.grp[gi + 1];
+    ngb = grp[gi];
+    nge = grp[gi + 1];
   }
   for (; gi < gend; gi += gstride) {
     const int gb = ngb, ge = nge;
     if (gi + gstride < gend) {
-      ngb = mp.grp[gi + gstride];
-      nge = mp.grp[gi + gstride + 1];
+      ngb = grp[gi + gstride];
+      nge = grp[gi + gstride + 1];
     }
     double acc[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
     int key = -1 - lane;
@@ -474,8 +475,10 @@ __global__ __launch_bounds__(kBlock) void k_block_products(ProdMap mp, BsrDev XA
 // then the wave totals added in a fixed order): a single wave walking such a column stride by stride is a chain of ~70
 // dependent round trips (C5's last level: 4 350 entries per column, 109 us), a launch of its own costs 4 us per cycle.
 // (block: this workgroup's index within the restriction's part of the launch)
-__device__ __forceinline__ void restrict_groups(const PDev& P, const double* __restrict__ r, double* __restrict__ rc,
-                                                const PcgScalars* S, int row0, int row1, int nb_main, int block) {
+// (S, t_grp = P.t_grp, t_ngrp = P.t_ngrp, nb_main: what the first round of requests needs, from the kernel's leading parameters)
+__device__ __forceinline__ void restrict_groups(const PcgScalars* S, const int* __restrict__ t_grp, int t_ngrp, int nb_main,
+                                                const PDev& P, const double* __restrict__ r, double* __restrict__ rc,
+                                                int row0, int row1, int block) {
   const int lane = threadIdx.x & 63;
   const size_t np = (size_t)P.t_n;
   if (block >= nb_main) {   // a long column
@@ -505,11 +508,11 @@ __device__ __forceinline__ void restrict_groups(const PDev& P, const double* __r
     }
     return;
   }
-  GroupCursor gc = group_cursor(P.t_grp, P.t_ngrp, nb_main, block);
+  GroupCursor gc = group_cursor(t_grp, t_ngrp, nb_main, block);
   if (S && S->stop) return;
   for (bool first = true; gc.g < gc.gend; gc.g += gc.gstride, first = false) {
     int gb, ge;
-    group_bounds(gc, P.t_grp, first, gb, ge);
+    group_bounds(gc, t_grp, first, gb, ge);
     if (P.t_nlong > 0 && ge - gb > kLongColumn) continue;   // a long column: the workgroups at the end of the grid
     double acc[3] = {0.0, 0.0, 0.0};
     int key = -1 - lane;
@@ -530,30 +533,37 @@ __device__ __forceinline__ void restrict_groups(const PDev& P, const double* __r
     }
   }
 }
-__global__ __launch_bounds__(kBlock) void k_restrict_p(PDev P, const double* __restrict__ r, double* __restrict__ rc,
-                                                       const PcgScalars* S, int row0, int row1, int nb_main) {
-  restrict_groups(P, r, rc, S, row0, row1, nb_main, (int)blockIdx.x);
+__global__ __launch_bounds__(kBlock) void k_restrict_p(const PcgScalars* S, const int* __restrict__ t_grp, int t_ngrp, int nb_main,
+                                                       PDev P, const double* __restrict__ r, double* __restrict__ rc, int row0,
+                                                       int row1) {
+  restrict_groups(S, t_grp, t_ngrp, nb_main, P, r, rc, row0, row1, (int)blockIdx.x);
 }
 // The folded cycle's two level-0 launches that read the same right-hand side and do not depend on each other -- the
 // Jacobi pass of the wave-group kernel (M2 r, workgroups [0, nb_spmv)) and the restriction with P~^T (the workgroups
 // behind them) -- as ONE launch: on the graphs that fold level 0 a launch costs more than what it moves.
-__global__ __launch_bounds__(kBlock, 4) void k_jacobi0_restrict(Sym0Dev A, Spmv0Args a, int nb_spmv, PDev P, double* __restrict__ rc,
-                                                                 int nb_main) {
-  if ((int)blockIdx.x < nb_spmv) spmv0_groups<S0_JACOBI>(A, a, nb_spmv);
-  else restrict_groups(P, a.b, rc, a.S, 0, 0, nb_main, (int)blockIdx.x - nb_spmv);
+// (The leading parameters are the Jacobi pass's, the longer chain of the two: Spmv0Head, sgo_device.h.  The restriction finds
+// its group array in P: there is no room for it among the preloaded dwords.)
+__global__ __launch_bounds__(kBlock, 4) void k_jacobi0_restrict(const PcgScalars* __restrict__ S, const int* __restrict__ grp,
+                                                                 const int* __restrict__ grow, const int* __restrict__ gown,
+                                                                 const int* __restrict__ gtr, int ulo, int uhi, int nb_spmv, int nb_main,
+                                                                 Sym0Dev A, Spmv0Args a, PDev P, double* __restrict__ rc) {
+  if ((int)blockIdx.x < nb_spmv) spmv0_groups<S0_JACOBI>(Spmv0Head{S, grp, grow, gown, gtr, ulo, uhi}, A, a, nb_spmv);
+  else restrict_groups(S, P.t_grp, P.t_ngrp, nb_main, P, a.b, rc, 0, 0, (int)blockIdx.x - nb_spmv);
 }
 // r_c = P^T r on the stream
 void launch_restrict_p(hipStream_t s, const PDev& P, const double* r, double* rc, const PcgScalars* S, int row0, int row1) {
   const int nb = grid_for(P.t_ngrp, kWavesPerBlock);
-  SGO_LAUNCH(k_restrict_p, dim3(nb + P.t_nlong), dim3(kBlock), 0, s, P, r, rc, S, row0, row1, nb);
+  SGO_LAUNCH(k_restrict_p, dim3(nb + P.t_nlong), dim3(kBlock), 0, s, S, (const int*)P.t_grp, P.t_ngrp, nb, P, r, rc, row0, row1);
 }
 
 // x_i += sum over the entries e of row i of P_e (c1 u1 + c2 u2)[col(e)]  (+ xadd_i)
-__global__ __launch_bounds__(kBlock) void k_prolong_p(int n, PDev P, const double* __restrict__ u1, SpmvRatio r1,
+// (S, r_grp = P.r_grp, r_ngrp = P.r_ngrp: the first round of requests, leading parameters)
+__global__ __launch_bounds__(kBlock) void k_prolong_p(const PcgScalars* S, const int* __restrict__ r_grp, int r_ngrp, int n, PDev P,
+                                                      const double* __restrict__ u1, SpmvRatio r1,
                                                       const double* __restrict__ u2, SpmvRatio r2,
-                                                      double* __restrict__ x, const PcgScalars* S,
+                                                      double* __restrict__ x,
                                                       const double* __restrict__ xadd, int row0, int row1) {
-  GroupCursor gc = group_cursor(P.r_grp, P.r_ngrp, gridDim.x, blockIdx.x);
+  GroupCursor gc = group_cursor(r_grp, r_ngrp, gridDim.x, blockIdx.x);
   if (S && S->stop) return;
   double c1, c2;
   cycle_coefficients(r1, r2, u2 != nullptr, c1, c2);
@@ -562,7 +572,7 @@ __global__ __launch_bounds__(kBlock) void k_prolong_p(int n, PDev P, const doubl
   const size_t np = (size_t)P.r_n;
   for (bool first = true; gc.g < gc.gend; gc.g += gc.gstride, first = false) {
     int gb, ge;
-    group_bounds(gc, P.r_grp, first, gb, ge);
+    group_bounds(gc, r_grp, first, gb, ge);
     double acc[3] = {0.0, 0.0, 0.0};
     int key = -1 - lane;
     for (int e = gb + lane; e < ge; e += 64) {
@@ -728,14 +738,15 @@ __global__ __launch_bounds__(kBlock) void k_ptilde_values(FoldDev F, const doubl
 // Workgroups of 1024 threads: the consumer of the dot products re-reduces one partial sum per WORKGROUP in every one of its
 // own workgroups, so there should be a few hundred of them.
 constexpr int kFoldThreads = 1024;
-__global__ __launch_bounds__(kFoldThreads) void k_prolong_fold(PDev P, const double* __restrict__ u1, SpmvRatio r1,
+__global__ __launch_bounds__(kFoldThreads) void k_prolong_fold(const PcgScalars* S, const int* __restrict__ r_grp, int r_ngrp, PDev P,
+                                                               const double* __restrict__ u1, SpmvRatio r1,
                                                                const double* __restrict__ u2, SpmvRatio r2, const double* __restrict__ y,
-                                                               double* __restrict__ out, const PcgScalars* S, const double* __restrict__ dotA,
+                                                               double* __restrict__ out, const double* __restrict__ dotA,
                                                                const double* __restrict__ dotA2, double* __restrict__ partials) {
   constexpr int NW = kFoldThreads / 64;
   __shared__ double sm[4][NW];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  GroupCursor gc = group_cursor<NW>(P.r_grp, P.r_ngrp, gridDim.x, blockIdx.x);
+  GroupCursor gc = group_cursor<NW>(r_grp, r_ngrp, gridDim.x, blockIdx.x);   // (= P.r_grp, P.r_ngrp: leading parameters)
   if (S && S->stop) return;
   double c1 = 1.0, c2 = 0.0;
   // cycle_coefficients (sgo_device.h) with a reduction of its own: 1024 threads, and sm is shared with the dot products below
@@ -767,7 +778,7 @@ __global__ __launch_bounds__(kFoldThreads) void k_prolong_fold(PDev P, const dou
   double dotacc[2] = {0.0, 0.0};
   for (bool first = true; gc.g < gc.gend; gc.g += gc.gstride, first = false) {
     int gb, ge;
-    group_bounds(gc, P.r_grp, first, gb, ge);
+    group_bounds(gc, r_grp, first, gb, ge);
     double acc[3] = {0.0, 0.0, 0.0};
     int key = -1 - lane;
     for (int e = gb + lane; e < ge; e += 64) {
@@ -813,11 +824,11 @@ __global__ __launch_bounds__(kFoldThreads) void k_prolong_fold(PDev P, const dou
 
 // Levels >= 1: out_i = M2 b |_i + sum_f P~_f (c1 u1 + c2 u2)[col(f)],  M2 b = x1 + w D^-1 (b - A x1), x1 = w D^-1 b
 // (the operand of a slot (i, j) is made on the fly from b_j and D_j^-1: nothing but b and the coarse solution is read)
-__global__ __launch_bounds__(kBlock) void k_up_fold(BsrDev A, UpDev U, PDev PS, const double* __restrict__ b, double omega,
+__global__ __launch_bounds__(kBlock) void k_up_fold(const PcgScalars* S, const int* __restrict__ grp, int ngrp, BsrDev A, UpDev U,
+                                                    PDev PS, const double* __restrict__ b, double omega,
                                                     const double* __restrict__ u1, SpmvRatio r1, const double* __restrict__ u2,
-                                                    SpmvRatio r2, double* __restrict__ out, const PcgScalars* S,
-                                                    const double* __restrict__ xadd) {
-  GroupCursor gc = group_cursor(U.grp, U.ngrp, gridDim.x, blockIdx.x);
+                                                    SpmvRatio r2, double* __restrict__ out, const double* __restrict__ xadd) {
+  GroupCursor gc = group_cursor(grp, ngrp, gridDim.x, blockIdx.x);   // (= U.grp, U.ngrp: leading parameters)
   if (S && S->stop) return;
   double c1, c2;
   cycle_coefficients(r1, r2, u2 != nullptr, c1, c2);
@@ -825,7 +836,7 @@ __global__ __launch_bounds__(kBlock) void k_up_fold(BsrDev A, UpDev U, PDev PS, 
   const size_t ns = (size_t)A.nslot, np = (size_t)PS.r_n;
   for (bool first = true; gc.g < gc.gend; gc.g += gc.gstride, first = false) {
     int gb, ge;
-    group_bounds(gc, U.grp, first, gb, ge);
+    group_bounds(gc, grp, first, gb, ge);
     double acc[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};   // [0..2] A x1, [3..5] P~ e
     int key = -1 - lane;
     for (int t = gb + lane; t < ge; t += 64) {
@@ -877,10 +888,11 @@ __global__ __launch_bounds__(kBlock) void k_up_fold(BsrDev A, UpDev U, PDev PS, 
 }
 
 // dinv of a coarse level from its diagonal slots (first slot of each row)
-__global__ __launch_bounds__(kBlock) void k_level_dinv(BsrDev A) {
+// (n = A.n, rowptr = A.rowptr: the first request, leading parameters)
+__global__ __launch_bounds__(kBlock) void k_level_dinv(int n, const int* __restrict__ rowptr, BsrDev A) {
   const size_t ns = (size_t)A.nslot;
-  for (int i = blockIdx.x * kBlock + threadIdx.x; i < A.n; i += gridDim.x * kBlock) {
-    const int k0 = A.rowptr[i];
+  for (int i = blockIdx.x * kBlock + threadIdx.x; i < n; i += gridDim.x * kBlock) {
+    const int k0 = rowptr[i];
     // symmetrise (the Galerkin sum is symmetric up to rounding)
     const double d[6] = {A.blk[blk_at(0, k0, ns)], 0.5 * (A.blk[blk_at(1, k0, ns)] + A.blk[blk_at(3, k0, ns)]),
                          0.5 * (A.blk[blk_at(2, k0, ns)] + A.blk[blk_at(6, k0, ns)]), A.blk[blk_at(4, k0, ns)],
@@ -1630,14 +1642,14 @@ void launch_coarse_operator(Amg* m, hipStream_t s, AmgLevel& L, AmgLevel& C, boo
   }
   {
     Scope sc(m->prof, level0 ? K_SA_P0 : K_SA_P, (72.0 + 12.0 + 16.0) * P.val.n + 80.0 * P.r_n);
-    SGO_LAUNCH(k_p_values, dim3(grid_for(P.val.ngrp, kWavesPerBlock)), dim3(kBlock), 0, s, L.A, P, (const int*)L.agg,
-               (const double*)L.d, m->cfg.omega_p, row0, row1);
+    SGO_LAUNCH(k_p_values, dim3(grid_for(P.val.ngrp, kWavesPerBlock)), dim3(kBlock), 0, s, (const int*)P.val.grp, P.val.ngrp, L.A, P,
+               (const int*)L.agg, (const double*)L.d, m->cfg.omega_p, row0, row1);
   }
   if (own) sh.exchange(s, P.blk, 9, sh.part->pent, sh.part->pemax);
   {
     Scope sc(m->prof, level0 ? K_SA_AP0 : K_SA_AP, 156.0 * P.ap.n + 72.0 * P.nap);
     SGO_LAUNCH((k_block_products<true, false, false>), dim3(grid_for(P.ap.ngrp, kWavesPerBlock)), dim3(kBlock), 0, s,
-               P.ap, L.A, (const double*)nullptr, (const double*)P.blk, P.apblk, (size_t)P.nap, (const int*)nullptr,
+               (const int*)P.ap.grp, P.ap.ngrp, P.ap, L.A, (const double*)nullptr, (const double*)P.blk, P.apblk, (size_t)P.nap, (const int*)nullptr,
                (const int*)L.A.row, row0, P.local_lists ? 0 : row1, 0);   // (local lists hold this rank's products only: no filter)
   }
   if (L.fold) {
@@ -1649,7 +1661,7 @@ void launch_coarse_operator(Amg* m, hipStream_t s, AmgLevel& L, AmgLevel& C, boo
   {
     Scope sc(m->prof, level0 ? K_SA_RAP0 : K_SA_RAP, 156.0 * P.rap.n + 72.0 * C.A.nslot);
     SGO_LAUNCH((k_block_products<false, true, true>), dim3(grid_for(P.rap.ngrp, kWavesPerBlock)), dim3(kBlock), 0, s,
-               P.rap, BsrDev(), (const double*)P.blk, (const double*)P.apblk, C.A.blk, (size_t)C.A.nslot, (const int*)P.rap_mirror,
+               (const int*)P.rap.grp, P.rap.ngrp, P.rap, BsrDev(), (const double*)P.blk, (const double*)P.apblk, C.A.blk, (size_t)C.A.nslot, (const int*)P.rap_mirror,
                (const int*)P.row, row0, P.local_lists ? 0 : row1, 1);
   }
   if (own) sh.reduce(s, C.A.blk, 9 * (size_t)C.A.nslot);
@@ -1769,8 +1781,8 @@ void prolong0(Amg* m, hipStream_t s, const CoarseSol& cs, const PcgScalars* S) {
   const int row0 = own ? sh.row0 : 0, row1 = own ? sh.row1 : 0;
   if (L.smoothed) {
     Scope sc(m->prof, K_PROLONG_P0, 44.0 * L.P.r_n + 52.0 * L.A.n);
-    SGO_LAUNCH(k_prolong_p, dim3(grid_for(L.P.r_ngrp, kWavesPerBlock)), dim3(kBlock), 0, s, L.A.n, L.P, cs.u1, cs.c1, cs.u2, cs.c2,
-               L.xs, S, (const double*)nullptr, row0, row1);
+    SGO_LAUNCH(k_prolong_p, dim3(grid_for(L.P.r_ngrp, kWavesPerBlock)), dim3(kBlock), 0, s, S, (const int*)L.P.r_grp, L.P.r_ngrp, L.A.n, L.P,
+               cs.u1, cs.c1, cs.u2, cs.c2, L.xs, (const double*)nullptr, row0, row1);
   } else {
     Scope sc(m->prof, K_PROLONG0, 68.0 * L.A.n);
     SGO_LAUNCH(k_prolong_add, dim3(grid_for(own ? row1 - row0 : L.A.n, kBlock)), dim3(kBlock), 0, s, L.A.n, L.agg, L.d, cs.u1, cs.c1,
@@ -1819,7 +1831,9 @@ int cycle0_fold(Amg* m, hipStream_t s, const double* rhs, double* out, const Dot
   if (m->T0.ntile == 0) {   // wave-group kernel: the pass and the restriction in one launch
     const int nb_spmv = grid_for(m->S0.ngrp, kWavesPerBlock), nb_main = grid_for(L.PS.t_ngrp, kWavesPerBlock);
     Scope sc(m->prof, K_JACOBI0_RESTRICT, bytes_spmv0(m->S0, S0_JACOBI) + 44.0 * L.PS.t_n + 24.0 * L.A.n + 24.0 * L.nc);
-    SGO_LAUNCH(k_jacobi0_restrict, dim3(nb_spmv + nb_main + L.PS.t_nlong), dim3(kBlock), 0, s, m->S0, b, nb_spmv, L.PS, C.bk, nb_main);
+    SGO_LAUNCH(k_jacobi0_restrict, dim3(nb_spmv + nb_main + L.PS.t_nlong), dim3(kBlock), 0, s, b.S, (const int*)m->S0.grp, (const int*)m->S0.grow,
+               (const int*)m->S0.gown, (const int*)m->S0.gtr, b.u1 > 0 ? b.u0 : 0, b.u1 > 0 ? b.u1 : m->S0.ngrp, nb_spmv, nb_main, m->S0, b, L.PS,
+               C.bk);
   } else {
     pass0(m, s, S0_JACOBI, b);
     restrict_level(m, s, 0, rhs, S, true);
@@ -1828,8 +1842,8 @@ int cycle0_fold(Amg* m, hipStream_t s, const double* rhs, double* out, const Dot
   // (the dot products' partial sums are re-reduced by every workgroup of the consumer: a few hundred of them, not thousands)
   const int grid = std::min(grid_for(L.PS.r_ngrp, kFoldThreads / 64), 512);
   Scope sc(m->prof, K_PROLONG_FOLD0, 44.0 * L.PS.r_n + 72.0 * L.A.n);
-  SGO_LAUNCH(k_prolong_fold, dim3(grid), dim3(kFoldThreads), 0, s, L.PS, cs.u1, cs.c1, cs.u2, cs.c2, (const double*)L.rs, out, S, dots.vec,
-             dots.vec2, dots.vec ? dots.parts : nullptr);
+  SGO_LAUNCH(k_prolong_fold, dim3(grid), dim3(kFoldThreads), 0, s, S, (const int*)L.PS.r_grp, L.PS.r_ngrp, L.PS, cs.u1, cs.c1, cs.u2,
+             cs.c2, (const double*)L.rs, out, dots.vec, dots.vec2, dots.vec ? dots.parts : nullptr);
   return grid;
 }
 // out = cycle(0, rhs), the whole preconditioner: pre-smoothing from zero + residual, restriction, coarse solve (dense inverse, a
@@ -1896,8 +1910,8 @@ int prolong_postsmooth(Amg* m, hipStream_t s, AmgLevel& L, const double* rhs, do
   if (L.smoothed) {
     {
       Scope sc(m->prof, K_PROLONG_P, 80.0 * L.P.np + 52.0 * L.A.n);
-      SGO_LAUNCH(k_prolong_p, dim3(grid_for(L.P.r_ngrp, kWavesPerBlock)), dim3(kBlock), 0, s, L.A.n, L.P, cs.u1, cs.c1, cs.u2, cs.c2,
-                 L.xs, S, (const double*)nullptr, 0, 0);
+      SGO_LAUNCH(k_prolong_p, dim3(grid_for(L.P.r_ngrp, kWavesPerBlock)), dim3(kBlock), 0, s, S, (const int*)L.P.r_grp, L.P.r_ngrp, L.A.n, L.P,
+                 cs.u1, cs.c1, cs.u2, cs.c2, L.xs, (const double*)nullptr, 0, 0);
     }
     const double* x = L.xs;   // the first nu - 1 sweeps through the two residual buffers (free by now)
     for (int sw = 1; sw < nu; ++sw) {
@@ -1925,7 +1939,8 @@ int cycle_coarse_fold(Amg* m, hipStream_t s, int l, const double* rhs, double* o
   const CoarseSol cs = coarse_solve(m, s, l, S);
   Scope sc(m->prof, K_UP_FOLD, 80.0 * L.A.nslot + 44.0 * L.PS.r_n + 100.0 * L.A.n);
   const int grid = grid_for(L.U.ngrp, kWavesPerBlock);
-  SGO_LAUNCH(k_up_fold, dim3(grid), dim3(kBlock), 0, s, L.A, L.U, L.PS, rhs, m->cfg.omega, cs.u1, cs.c1, cs.u2, cs.c2, out, S, xadd);
+  SGO_LAUNCH(k_up_fold, dim3(grid), dim3(kBlock), 0, s, S, (const int*)L.U.grp, L.U.ngrp, L.A, L.U, L.PS, rhs, m->cfg.omega, cs.u1, cs.c1,
+             cs.u2, cs.c2, out, xadd);
   return grid;
 }
 // out = cycle(l, rhs'), l >= 1: rhs' = rhs - c sub with `sub` (the K-cycle's second step).  Pre-smoothing from zero + residual,
@@ -2047,7 +2062,7 @@ int amg_update(Amg* m, hipStream_t s, std::string* err) {
     launch_coarse_operator(m, s, L, C, l == 0);
     {
       Scope sc(m->prof, K_LEVEL_DINV, 120.0 * C.A.n);
-      SGO_LAUNCH(k_level_dinv, dim3(grid_for(C.A.n, kBlock)), dim3(kBlock), 0, s, C.A);
+      SGO_LAUNCH(k_level_dinv, dim3(grid_for(C.A.n, kBlock)), dim3(kBlock), 0, s, C.A.n, (const int*)C.A.rowptr, C.A);
     }
   }
   {
@@ -2864,7 +2879,7 @@ void level_values(Amg* m, hipStream_t s, int l) {
   if (l == 0) SGO_LAUNCH(k_positions0, dim3(grid_for(n, kBlock)), dim3(kBlock), 0, s, n, m->d_free_id, m->d_poses, L.pos);
   SGO_LAUNCH(k_centres, dim3(grid_for(nc, kWavesPerBlock)), dim3(kBlock), 0, s, nc, L.mem_ptr, L.mem, L.pos, C.pos, L.d);
   launch_coarse_operator(m, s, L, C, l == 0);
-  if (l + 1 < m->cfg.max_levels) SGO_LAUNCH(k_level_dinv, dim3(grid_for(C.A.n, kBlock)), dim3(kBlock), 0, s, C.A);
+  if (l + 1 < m->cfg.max_levels) SGO_LAUNCH(k_level_dinv, dim3(grid_for(C.A.n, kBlock)), dim3(kBlock), 0, s, C.A.n, (const int*)C.A.rowptr, C.A);
 }
 
 double ms_since(std::chrono::steady_clock::time_point t) {

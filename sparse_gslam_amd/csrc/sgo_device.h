@@ -458,6 +458,12 @@ __device__ __forceinline__ void group_walk(int ngrp, int* first, int* last, int*
 // sgo_kernels.hip spells the cursor out.  base: the walk covers the groups [base, base + ngrp).  The set-up and refresh
 // kernels -- k_linearize, k_galerkin, k_filtered_diag, k_p_values, k_block_products -- have no stop flag to overlap the
 // request with: they take group_walk and segment_end only.)
+// Kernel arguments: the command processor places the leading PLAIN parameters of a kernel (pointers and scalars, up to 14
+// dwords) in SGPRs before the first wave starts; whatever stands behind the first by-value struct is loaded from the
+// argument block, one more round trip at the head of the chain (NOTES.md section 49).  So a kernel of
+// the replayed iteration takes what its first round of requests needs -- the stop flag's address, the group array and its
+// extent -- as leading parameters and hands THOSE to group_cursor; the launch wrappers copy them out of the structs, which
+// stay complete.
 struct GroupCursor {
   int g, gend, gstride;   // this wave's group, the end of its XCD's band, the stride
   int gb0, ge0;           // the first group's bounds
@@ -583,11 +589,19 @@ __device__ __forceinline__ void dinv_from_block(const double (&d)[6], double* __
   di[0] = c00 * id; di[1] = c01 * id; di[2] = c02 * id; di[3] = c11 * id; di[4] = c12 * id; di[5] = c22 * id;
 }
 
+// The leading parameters of the kernels that run spmv0_groups: S = a.S; grp / grow / gown / gtr = A's; [ulo, uhi) the
+// wave groups to walk (a.u0, a.u1, or all of A.ngrp when a.u1 == 0), worked out by the launch wrapper.
+struct Spmv0Head {
+  const PcgScalars* S;
+  const int *grp, *grow, *gown, *gtr;
+  int ulo, uhi;
+};
 // Body of the wave-group level-0 product k_spmv0 (sgo_kernels.hip; modes and storage described there): the first
 // `nblocks` workgroups of a launch walk the groups -- the launch may carry workgroups with another job behind them
 // (sgo_amg.hip: the folded cycle's level-0 pass and its restriction in one launch).
+// h: what the first round of requests needs, as the kernel received it in its leading parameters (Spmv0Head above).
 template <int MODE>
-__device__ __forceinline__ void spmv0_groups(const Sym0Dev& A, const Spmv0Args& a, int nblocks) {
+__device__ __forceinline__ void spmv0_groups(const Spmv0Head& h, const Sym0Dev& A, const Spmv0Args& a, int nblocks) {
   // On the graphs that take this kernel a launch is a chain of dependent round trips (~0.3 us each on top of the 1.8-us
   // node of a replayed hipGraph: scripts/micro/graph_floor.hip), so the chain is kept short: the first group's descriptors
   // are requested before the stop flag is waited for, a slot's column with its meta byte, and the row's own data (diagonal
@@ -596,18 +610,17 @@ __device__ __forceinline__ void spmv0_groups(const Sym0Dev& A, const Spmv0Args& 
   const size_t nu = (size_t)A.nus;
   const double2* __restrict__ bp = reinterpret_cast<const double2*>(A.ublk);
   double dotacc[2] = {0.0, 0.0};
-  const int ulo = a.u1 > 0 ? a.u0 : 0, uhi = a.u1 > 0 ? a.u1 : A.ngrp;
-  GroupCursor gc = group_cursor(A.grp, uhi - ulo, nblocks, blockIdx.x, ulo);
+  GroupCursor gc = group_cursor(h.grp, h.uhi - h.ulo, nblocks, blockIdx.x, h.ulo);
   int f_r0 = 0, f_ob = 0, f_tb = 0;
   if (gc.g < gc.gend) {
-    f_r0 = A.grow[gc.g]; f_ob = A.gown[gc.g]; f_tb = A.gtr[gc.g];
+    f_r0 = h.grow[gc.g]; f_ob = h.gown[gc.g]; f_tb = h.gtr[gc.g];
   }
-  if (a.S && a.S->stop) return;
+  if (h.S && h.S->stop) return;
   for (bool first = true; gc.g < gc.gend; gc.g += gc.gstride, first = false) {
     int gb, ge;
-    group_bounds(gc, A.grp, first, gb, ge);
-    const int r0 = first ? f_r0 : A.grow[gc.g];
-    int ob = first ? f_ob : A.gown[gc.g], tb = first ? f_tb : A.gtr[gc.g];
+    group_bounds(gc, h.grp, first, gb, ge);
+    const int r0 = first ? f_r0 : h.grow[gc.g];
+    int ob = first ? f_ob : h.gown[gc.g], tb = first ? f_tb : h.gtr[gc.g];
     double acc[3] = {0.0, 0.0, 0.0};
     int row = -1 - lane;
     for (int kb = gb; kb < ge; kb += 64) {

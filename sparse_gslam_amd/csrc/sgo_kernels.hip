@@ -447,17 +447,18 @@ __device__ __forceinline__ void ratios2(const SpmvRatio& r1, const SpmvRatio& r2
 // (<= 64 VGPRs, no spills) keeps the whole grid resident: 37 -> 30 us per sweep on C4 (6.0 TB/s).
 template <int MODE>
 __global__ __launch_bounds__(kBlock, ((MODE == SPMV_JACOBI || MODE == SPMV_PRE_RESID) ? 8 : 1))
-void k_spmv(BsrDev A, SpmvArgs a) {
+void k_spmv(const PcgScalars* __restrict__ S, const int* __restrict__ grp, int ngrp, BsrDev A, SpmvArgs a) {
   // the first group's bounds are requested BEFORE the stop flag is waited for: on the coarse levels a launch is a
-  // chain of four or five dependent memory round trips, and this folds two of them into one
+  // chain of four or five dependent memory round trips, and this folds two of them into one.  S = a.S, grp = A.grp,
+  // ngrp = A.ngrp: what that first request needs, as leading parameters (preloaded, sgo_device.h)
   int g, gend, gstride;
-  group_walk(A.ngrp, &g, &gend, &gstride);
+  group_walk(ngrp, &g, &gend, &gstride);
   int gb0 = 0, ge0 = 0;
   if (g < gend) {
-    gb0 = A.grp[g];
-    ge0 = A.grp[g + 1];
+    gb0 = grp[g];
+    ge0 = grp[g + 1];
   }
-  if (a.S && a.S->stop) return;
+  if (S && S->stop) return;
   const int lane = threadIdx.x & 63;
   const size_t ns = (size_t)A.nslot;
   double c1 = 1.0, c2 = 0.0;
@@ -493,7 +494,7 @@ void k_spmv(BsrDev A, SpmvArgs a) {
   };
   double dotacc[2] = {0.0, 0.0};
   for (bool first = true; g < gend; g += gstride, first = false) {
-    const int gb = first ? gb0 : A.grp[g], ge = first ? ge0 : A.grp[g + 1];
+    const int gb = first ? gb0 : grp[g], ge = first ? ge0 : grp[g + 1];
     double acc[3] = {0.0, 0.0, 0.0};
     int row = -1 - lane;
     for (int k = gb + lane; k < ge; k += 64) {
@@ -572,8 +573,10 @@ void k_spmv(BsrDev A, SpmvArgs a) {
 // (Graphs below kSmallGraphPairs take it: a few hundred to a thousand workgroups; the row data held across the scan costs
 // registers, 4 workgroups per CU are plenty.)
 template <int MODE>
-__global__ __launch_bounds__(kBlock, 4) void k_spmv0(Sym0Dev A, Spmv0Args a) {
-  spmv0_groups<MODE>(A, a, (int)gridDim.x);
+__global__ __launch_bounds__(kBlock, 4) void k_spmv0(const PcgScalars* __restrict__ S, const int* __restrict__ grp,
+                                                     const int* __restrict__ grow, const int* __restrict__ gown,
+                                                     const int* __restrict__ gtr, int ulo, int uhi, Sym0Dev A, Spmv0Args a) {
+  spmv0_groups<MODE>(Spmv0Head{S, grp, grow, gown, gtr, ulo, uhi}, A, a, (int)gridDim.x);
 }
 
 // ---------------------------------------------------------------------------- k_spmv0t
@@ -648,10 +651,14 @@ __device__ __forceinline__ void tile_slot(const double* __restrict__ xs, double*
 }
 
 template <int MODE, int kTileThreads, bool F32 = false>
-__global__ __launch_bounds__(kTileThreads) void k_spmv0t(Sym0Dev A, Tile0Dev TL, Spmv0Args a) {
+__global__ __launch_bounds__(kTileThreads) void k_spmv0t(const PcgScalars* __restrict__ S, const TileDesc* __restrict__ tile,
+                                                         const int* __restrict__ hfirst, int hstride, int ulo, int uhi, Sym0Dev A,
+                                                         Tile0Dev TL, Spmv0Args a) {
   // the stop flag, the tile descriptor and the tile's first halo column numbers are requested together (none of their
-  // addresses depends on another's value): phase 0 is a chain of two memory round trips instead of four
-  const int stop_flag = a.S ? a.S->stop : 0;
+  // addresses depends on another's value): phase 0 is a chain of two memory round trips instead of four.  What these
+  // requests need are the leading parameters (preloaded, sgo_device.h): S = a.S, tile / hfirst / hstride = TL's, [ulo, uhi)
+  // the tiles to walk (a.u0, a.u1, or all of TL.ntile when a.u1 == 0)
+  const int stop_flag = S ? S->stop : 0;
   extern __shared__ double lds[];
   __shared__ int next_group_cell;
   int* next_group = &next_group_cell;
@@ -660,11 +667,11 @@ __global__ __launch_bounds__(kTileThreads) void k_spmv0t(Sym0Dev A, Tile0Dev TL,
   const size_t nu = (size_t)A.nus;
   double dotacc[2] = {0.0, 0.0};
   const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, per_xcd = gridDim.x >> 3;
-  const int ulo = a.u1 > 0 ? a.u0 : 0, nun = (a.u1 > 0 ? a.u1 : TL.ntile) - ulo;
+  const int nun = uhi - ulo;
   const int tlo = ulo + (int)(((long long)nun * xcd) >> 3), thi = ulo + (int)(((long long)nun * (xcd + 1)) >> 3);
   for (int t = tlo + slot; t < thi; t += per_xcd) {
-    const int hc_first = tid < TL.hstride ? TL.hfirst[(size_t)t * TL.hstride + tid] : -1;
-    const TileDesc T = TL.tile[t];
+    const int hc_first = tid < hstride ? hfirst[(size_t)t * hstride + tid] : -1;
+    const TileDesc T = tile[t];
     if (stop_flag) return;
     const int nr = T.row1 - T.row0, nh = T.h1 - T.h0;
     long long* stamp = a.dbg_stamps ? a.dbg_stamps + 8 * (size_t)t : nullptr;
@@ -681,7 +688,7 @@ __global__ __launch_bounds__(kTileThreads) void k_spmv0t(Sym0Dev A, Tile0Dev TL,
       const int i = tid + q * kTileThreads;
       if (i < 3 * nr) xsl[q] = a.x[3 * (size_t)T.row0 + i];
     }
-    const int hc0 = tid < TL.hstride ? hc_first : (tid < nh ? TL.hcol[T.h0 + tid] : -1);
+    const int hc0 = tid < hstride ? hc_first : (tid < nh ? TL.hcol[T.h0 + tid] : -1);
     if (tid == 0) *next_group = T.g0 + NW;   // groups are handed out through an LDS counter (the first NW statically)
     int g = T.g0 + wave;
     bool has = g < T.g1;
@@ -1209,27 +1216,28 @@ void launch_slot_expand(hipStream_t s, int k0, int k1, const int* eidx, const Ed
 int launch_spmv_ex(hipStream_t s, const BsrDev& A, int mode, const SpmvArgs& a) {
   const int grid = grid_for(A.ngrp, kWavesPerBlock);
   switch (mode) {
-    case SPMV_AX: SGO_LAUNCH((k_spmv<SPMV_AX>), dim3(grid), dim3(kBlock), 0, s, A, a); break;
-    case SPMV_RESID: SGO_LAUNCH((k_spmv<SPMV_RESID>), dim3(grid), dim3(kBlock), 0, s, A, a); break;
+    case SPMV_AX: SGO_LAUNCH((k_spmv<SPMV_AX>), dim3(grid), dim3(kBlock), 0, s, a.S, A.grp, A.ngrp, A, a); break;
+    case SPMV_RESID: SGO_LAUNCH((k_spmv<SPMV_RESID>), dim3(grid), dim3(kBlock), 0, s, a.S, A.grp, A.ngrp, A, a); break;
     case SPMV_JACOBI:
-      SGO_LAUNCH((k_spmv<SPMV_JACOBI>), dim3(grid), dim3(kBlock), 0, s, A, a);
+      SGO_LAUNCH((k_spmv<SPMV_JACOBI>), dim3(grid), dim3(kBlock), 0, s, a.S, A.grp, A.ngrp, A, a);
       break;
-    case SPMV_JACOBI_P: SGO_LAUNCH((k_spmv<SPMV_JACOBI_P>), dim3(grid), dim3(kBlock), 0, s, A, a); break;
-    case SPMV_PRE_RESID_S: SGO_LAUNCH((k_spmv<SPMV_PRE_RESID_S>), dim3(grid), dim3(kBlock), 0, s, A, a); break;
-    case SPMV_PRE_RESID_ACC: SGO_LAUNCH((k_spmv<SPMV_PRE_RESID_ACC>), dim3(grid), dim3(kBlock), 0, s, A, a); break;
-    case SPMV_AX_C: SGO_LAUNCH((k_spmv<SPMV_AX_C>), dim3(grid), dim3(kBlock), 0, s, A, a); break;
+    case SPMV_JACOBI_P: SGO_LAUNCH((k_spmv<SPMV_JACOBI_P>), dim3(grid), dim3(kBlock), 0, s, a.S, A.grp, A.ngrp, A, a); break;
+    case SPMV_PRE_RESID_S: SGO_LAUNCH((k_spmv<SPMV_PRE_RESID_S>), dim3(grid), dim3(kBlock), 0, s, a.S, A.grp, A.ngrp, A, a); break;
+    case SPMV_PRE_RESID_ACC: SGO_LAUNCH((k_spmv<SPMV_PRE_RESID_ACC>), dim3(grid), dim3(kBlock), 0, s, a.S, A.grp, A.ngrp, A, a); break;
+    case SPMV_AX_C: SGO_LAUNCH((k_spmv<SPMV_AX_C>), dim3(grid), dim3(kBlock), 0, s, a.S, A.grp, A.ngrp, A, a); break;
     default:
-      SGO_LAUNCH((k_spmv<SPMV_PRE_RESID>), dim3(grid), dim3(kBlock), 0, s, A, a);
+      SGO_LAUNCH((k_spmv<SPMV_PRE_RESID>), dim3(grid), dim3(kBlock), 0, s, a.S, A.grp, A.ngrp, A, a);
       break;
   }
   return grid;
 }
 int launch_spmv0(hipStream_t s, const Sym0Dev& A, int mode, const Spmv0Args& a) {
   const int grid = grid_for(A.ngrp, kWavesPerBlock);
+  const int ulo = a.u1 > 0 ? a.u0 : 0, uhi = a.u1 > 0 ? a.u1 : A.ngrp;
   switch (mode) {
-    case S0_AX: SGO_LAUNCH((k_spmv0<S0_AX>), dim3(grid), dim3(kBlock), 0, s, A, a); break;
-    case S0_RESID: SGO_LAUNCH((k_spmv0<S0_RESID>), dim3(grid), dim3(kBlock), 0, s, A, a); break;
-    default: SGO_LAUNCH((k_spmv0<S0_JACOBI>), dim3(grid), dim3(kBlock), 0, s, A, a); break;
+    case S0_AX: SGO_LAUNCH((k_spmv0<S0_AX>), dim3(grid), dim3(kBlock), 0, s, a.S, A.grp, A.grow, A.gown, A.gtr, ulo, uhi, A, a); break;
+    case S0_RESID: SGO_LAUNCH((k_spmv0<S0_RESID>), dim3(grid), dim3(kBlock), 0, s, a.S, A.grp, A.grow, A.gown, A.gtr, ulo, uhi, A, a); break;
+    default: SGO_LAUNCH((k_spmv0<S0_JACOBI>), dim3(grid), dim3(kBlock), 0, s, a.S, A.grp, A.grow, A.gown, A.gtr, ulo, uhi, A, a); break;
   }
   return grid;
 }
@@ -1242,7 +1250,8 @@ void launch_spmv0t_inst(hipStream_t s, const Sym0Dev& A, const Tile0Dev& T, cons
                             kDynMax) == hipSuccess)
       lds_allowed = kDynMax;
   }
-  SGO_LAUNCH((k_spmv0t<MODE, NT, F32>), dim3(grid), dim3(NT), (size_t)T.lds_bytes, s, A, T, a);
+  SGO_LAUNCH((k_spmv0t<MODE, NT, F32>), dim3(grid), dim3(NT), (size_t)T.lds_bytes, s, a.S, (const TileDesc*)T.tile, (const int*)T.hfirst,
+             T.hstride, a.u1 > 0 ? a.u0 : 0, a.u1 > 0 ? a.u1 : T.ntile, A, T, a);
 }
 int launch_spmv0t(hipStream_t s, const Sym0Dev& A, const Tile0Dev& T, int mode, const Spmv0Args& a) {
   // as many tile workgroups as fit the CUs' LDS are resident; more tiles are walked in a loop
