@@ -9,8 +9,12 @@ namespace {
 
 constexpr double kPi = 3.14159265358979323846;
 
-// g2o::normalize_theta, branch structure kept literal (result in [-pi, pi)).
+// g2o::normalize_theta, branch structure and roundings kept literal (result in [-pi, pi)).  The product m 2 pi and the
+// subtraction are two roundings, as in the host statements (oracle/, numpy, sgo_rules.h on an x86-64 baseline host): fused into
+// one FMA the result differs wherever m 2 pi is inexact (from |m| = 11 on; 3e-11 at t = 1e6), and near an odd multiple of pi it can land
+// on the other side of the branch (tests/wrap_cases.py has such points).  Contraction is switched off for this body alone.
 __device__ __forceinline__ double norm_theta(double t) {
+#pragma clang fp contract(off)
   if (t >= -kPi && t < kPi) return t;
   double m = floor(t / (2 * kPi));
   t = t - m * 2 * kPi;

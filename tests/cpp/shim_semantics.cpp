@@ -1,6 +1,7 @@
 // shim_semantics.cpp -- container / bookkeeping semantics of the g2o-compat SparseOptimizer that the
 // reference relies on (SURVEY.md section 8(b) "semantic notes"); host only, no GPU call is made.
 // Prints "ok" and returns 0 when every check holds.
+#include <cstdlib>
 #include <deque>
 #include <iostream>
 
@@ -98,6 +99,20 @@ int main() {
   k.robustify(0.5, rho);
   CHECK(rho[0] == 0.5 && rho[1] == 1.0);
   CHECK(normalize_theta(3 * const_pi()) == -const_pi());
+  {
+    // tests/wrap_cases.py's parting points: t - m 2pi as a product and a difference, two roundings.  Fused into one, the
+    // first two differ in value (1e6: by 3e-11), the next three land on the other side of the branch, the last three
+    // (35pi, its successor, -37pi - 2 ulp; m = 17 and -19) a few ulp off.
+    auto hx = [](const char* s) { return std::strtod(s, nullptr); };
+    CHECK(normalize_theta(1e6) == hx("-0x1.6e254d0e2d180p-2"));
+    CHECK(normalize_theta(-1e6) == hx("0x1.6e254d0e00000p-2"));
+    CHECK(normalize_theta(hx("0x1.2106ca4910069p+6")) == hx("-0x1.921fb54442d10p+1"));
+    CHECK(normalize_theta(hx("-0x1.3a28c59d5433bp+6")) == hx("-0x1.921fb54442d10p+1"));
+    CHECK(normalize_theta(hx("0x1.4d02421c87558p+7")) == hx("0x1.921fb54442d00p+1"));
+    CHECK(normalize_theta(hx("0x1.b7d2ae42a9152p+6")) == hx("0x1.921fb54442d00p+1"));
+    CHECK(normalize_theta(hx("0x1.b7d2ae42a9153p+6")) == hx("-0x1.921fb54442d10p+1"));
+    CHECK(normalize_theta(hx("-0x1.d0f4a996ed426p+6")) == hx("0x1.921fb54442cc0p+1"));
+  }
   {
     // A large pose graph in a configuration the device path does not cover (Levenberg-Marquardt)
     // is refused (optimize() == 0, estimates untouched): the dense host solver serves the

@@ -30,6 +30,10 @@ HAND = [
     ((0, 0, 0), (0, 0, 2 * PI + 0.5), (0, 0, 0), (0, 0, 0.5)),
     ((0, 0, 0), (0, 0, -7.0), (0, 0, 0), (0, 0, -7.0 + 2 * PI)),
     ((0, 0, PI - 1e-9), (0, 0, -PI + 1e-9), (0, 0, 0), (0, 0, 2e-9)),  # a hair across the wrap
+    # t - m 2pi as a product and a difference, two roundings (tests/wrap_cases.py): m = 159154, where one fused rounding gives
+    # -0.3575641670467533, 3e-11 away and outside this table's 1e-12; and m = 3, where the product is still exact
+    ((0, 0, 0), (0, 0, 1e6), (0, 0, 0), (0, 0, -0.35756416701340044)),
+    ((0, 0, 0), (0, 0, 7 * PI), (0, 0, 0), (0, 0, -PI)),
 ]
 OMEGA = np.array([[4.0, 0.5, 0.25], [0.5, 9.0, 0.75], [0.25, 0.75, 16.0]])
 UT6 = OMEGA[np.triu_indices(3)]
