@@ -87,6 +87,28 @@ int main(void) {
            poses5[13], poses5[14], sgo_solver_description(ctx));
     ok = ok && done2 == 10 && st->chi2[done2] < 1e-16 && poses5[12] * poses5[12] + poses5[13] * poses5[13] < 1e-12;
   }
+  /* several maps at once -- a second robot's square beside the first one's graph: one sgo_optimize_gn_many instead of a loop of
+   * sgo_optimize_gn_until over the contexts; graphs of this size share ONE launch, a workgroup each (in_launch = 1) */
+  {
+    sgo_ctx* other = sgo_create(-1, NULL);
+    double start[4 * 3] = {0, 0, 0, 0.95, -0.03, PI / 2 - 0.04, 1.02, 0.97, PI + 0.03, 0.05, 1.03, -PI / 2 - 0.02};
+    if (!other || sgo_set_graph_se2(other, 4, start, fixed, 4, ei, ej, meas, info, phi) != SGO_OK) {
+      fprintf(stderr, "second context: %s\n", sgo_last_error(other));
+      return 1;
+    }
+    sgo_ctx* both[2] = {ctx, other};
+    sgo_many_result mr[2];
+    int32_t launches = 0;
+    const int good = sgo_optimize_gn_many(both, 2, 10, 0.0, NULL, mr, &launches);
+    if (good < 0) {
+      fprintf(stderr, "sgo_optimize_gn_many: %s\n", sgo_last_error(ctx));
+      return 1;
+    }
+    printf("two graphs in one call: %d optimised, %d and %d iterations, %d shared launch(es), in the launch: %d %d\n", good, (int)mr[0].rc,
+           (int)mr[1].rc, (int)launches, (int)mr[0].in_launch, (int)mr[1].in_launch);
+    ok = ok && good == 2 && mr[0].rc == 10 && mr[1].rc == 10 && mr[1].stop_reason == SGO_STOP_MAX_ITERS;
+    sgo_destroy(other);
+  }
   free(st);
   sgo_destroy(ctx);
   return ok ? 0 : 2;

@@ -940,21 +940,48 @@ class SparseOptimizer : public OptimizableGraph {
     if (!gpuEligible()) return hostOptimize(iterations, online);
     if (!uploadGraph()) return 0;
     sgo_stats* st = new sgo_stats();
-    int done = _terminateAction ? sgo_optimize_gn_until(_ctx, _terminateAction->iterationCap(iterations), _terminateAction->gainThreshold(), st, nullptr)
-                                : sgo_optimize_gn(_ctx, iterations, st);
-    if (done < 0 && done != SGO_ENOTHING) {
-      std::cerr << "SparseOptimizer::optimize: " << sgo_last_error(_ctx) << std::endl;
-      done = 0;
-    } else if (done == 0 && iterations > 0) {   // OptimizationAlgorithm::Fail: optimize() returns 0 upstream too
-      std::cerr << "SparseOptimizer::optimize: linear solve failed after " << st->iters_done << " iterations: "
-                << sgo_last_error(_ctx) << std::endl;
+    const int done = _terminateAction ? sgo_optimize_gn_until(_ctx, _terminateAction->iterationCap(iterations), _terminateAction->gainThreshold(), st, nullptr)
+                                      : sgo_optimize_gn(_ctx, iterations, st);
+    return finishDeviceCall(done, iterations, st);
+  }
+  // ---- many optimisers in one call (extension; sgo_optimize_gn_many of include/sgo.h): what the loop
+  //     for (SparseOptimizer* o : optimisers) o->optimize(iters);
+  // leaves -- every estimate, every return value (returned in the list's order) -- with the graphs of the single-launch path
+  // sharing ONE kernel launch, a workgroup each, instead of taking a launch and a synchronisation each.  Each optimiser's pending
+  // upload (its initializeOptimization, changed estimates) is done first, the estimates are written back after the call.  An
+  // optimiser whose optimize() is not Gauss-Newton on the device (the landmark graph's host Levenberg, device Levenberg, dogleg),
+  // one with a registered terminate action (its threshold is its own), one without a free active vertex and the second entry of
+  // an optimiser listed twice run their own optimize(iters), in the list's order, after the shared call; a NULL entry gets -1.
+  static std::vector<int> sgoOptimizeMany(const std::vector<SparseOptimizer*>& optimisers, int iters) {
+    std::vector<int> done(optimisers.size(), -1);
+    std::vector<size_t> shared;
+    std::vector<sgo_ctx*> ctxs;
+    for (size_t i = 0; i < optimisers.size(); ++i) {
+      SparseOptimizer* o = optimisers[i];
+      if (!o) continue;
+      bool anyFree = false, twice = false;
+      for (auto* v : o->_activeVertices) anyFree = anyFree || !v->fixed();
+      for (size_t k : shared) twice = twice || optimisers[k] == o;
+      if (twice || !o->_algorithm || !o->gpuEligible() || o->_terminateAction || !anyFree) continue;
+      if (!o->uploadGraph()) {
+        done[i] = 0;
+        continue;
+      }
+      shared.push_back(i);
+      ctxs.push_back(o->_ctx);
     }
-    if (_verbose)
-      for (int k = 0; k < st->iters_done; ++k)
-        std::cerr << "iteration= " << k << "\t chi2= " << st->chi2[k + 1] << "\t time= " << st->seconds[k]
-                  << "\t pcg= " << st->pcg_iters[k] << std::endl;
-    _lastStats.reset(st);
-    downloadEstimates();
+    if (!shared.empty()) {
+      std::vector<std::unique_ptr<sgo_stats>> st(shared.size());
+      std::vector<sgo_stats*> stp(shared.size());
+      for (size_t k = 0; k < shared.size(); ++k) stp[k] = (st[k] = std::unique_ptr<sgo_stats>(new sgo_stats())).get();
+      std::vector<sgo_many_result> res(shared.size());
+      const int rc = sgo_optimize_gn_many(ctxs.data(), (int32_t)ctxs.size(), iters, 0.0, stp.data(), res.data(), nullptr);
+      if (rc < 0) std::cerr << "SparseOptimizer::sgoOptimizeMany: " << sgo_last_error(ctxs[0]) << std::endl;
+      for (size_t k = 0; k < shared.size(); ++k)
+        done[shared[k]] = rc < 0 ? 0 : optimisers[shared[k]]->finishDeviceCall(res[k].rc, iters, st[k].release());
+    }
+    for (size_t i = 0; i < optimisers.size(); ++i)
+      if (optimisers[i] && done[i] == -1 && std::find(shared.begin(), shared.end(), i) == shared.end()) done[i] = optimisers[i]->optimize(iters);
     return done;
   }
   // ---- marginal covariances (SparseOptimizer::computeMarginals): the blocks (r, c) of H^-1 by HESSIAN index, as upstream, through
@@ -1846,6 +1873,23 @@ class SparseOptimizer : public OptimizableGraph {
     return done;
   }
 
+  // what optimize() and sgoOptimizeMany do behind the device's Gauss-Newton call: the messages, the statistics, the estimates
+  int finishDeviceCall(int done, int iterations, sgo_stats* st) {
+    if (done < 0 && done != SGO_ENOTHING) {
+      std::cerr << "SparseOptimizer::optimize: " << sgo_last_error(_ctx) << std::endl;
+      done = 0;
+    } else if (done == 0 && iterations > 0) {   // OptimizationAlgorithm::Fail: optimize() returns 0 upstream too
+      std::cerr << "SparseOptimizer::optimize: linear solve failed after " << st->iters_done << " iterations: "
+                << sgo_last_error(_ctx) << std::endl;
+    }
+    if (_verbose)
+      for (int k = 0; k < st->iters_done; ++k)
+        std::cerr << "iteration= " << k << "\t chi2= " << st->chi2[k + 1] << "\t time= " << st->seconds[k]
+                  << "\t pcg= " << st->pcg_iters[k] << std::endl;
+    _lastStats.reset(st);
+    downloadEstimates();
+    return done;
+  }
   bool gpuEligible() const { return _algorithm->kind() == OptimizationAlgorithm::GaussNewton && deviceTypes(); }
   // every active vertex a VertexSE2 and every active edge an EdgeSE2 whose kernel, if any, the device evaluates
   bool deviceTypes() const {

@@ -443,6 +443,42 @@ int64_t sgo_hypotheses_bytes(sgo_ctx* ctx, int32_t max_iters, int32_t want_edge_
 int64_t sgo_hypotheses_workspace_bytes(sgo_ctx* ctx);
 int32_t sgo_hypotheses_chunk(int64_t per_hypothesis_bytes, int64_t budget_bytes, int32_t B);
 
+/* (later additions, version 107) Many INDEPENDENT pose graphs in one call: a back-end that serves the graphs
+ * of a swarm, several sessions or maps of one robot, or a sweep over many logs.
+ * Replaces: a loop of SparseOptimizer::optimize(max_iters) over several SparseOptimizers -- for (i) sgo_optimize_gn_until(ctxs[i],
+ * ...), one launch and one synchronisation per graph, each on one compute unit while the rest of the chip idles.
+ *
+ * Context i ends as after sgo_optimize_gn_until(ctxs[i], max_iters, gain_tol, out[i], &res[i].stop_reason) -- poses, chi2 history,
+ * sgo_stats, sgo_last_error, bit for bit -- and res[i].rc is what that call would have returned; gain_tol <= 0 never stops, which
+ * is sgo_optimize_gn(max_iters).  out, or any entry of it, may be NULL.  sgo_stats.seconds_total is the wall time of the whole call.
+ * Every direct_ldlt context joins ONE launch of the single-launch kernel with a workgroup per graph, each working from its own
+ * plan, edges and poses (res[i].in_launch = 1).  Graphs whose kernel differs at compile time -- edges with kernels other than DCS
+ * (sgo_set_robust_kernels), a right-hand side too long for the LDS -- take a launch per kind, at most four, back to back; *launches
+ * (may be NULL) is their number, 1 for the usual homogeneous call.  A context on another path -- multifrontal_cholesky, PCG, an
+ * active incremental overlay, no free pose, SGO_DIRECT_DEBUG at its set-up -- runs its own sgo_optimize_gn_until inside the call,
+ * after the shared launch has been queued (in_launch = 0).
+ * A linear solve that fails fails its graph alone: rc 0, SGO_STOP_FAILED, the step not applied, the reason in that context's
+ * sgo_last_error; an error of one context's own route is that context's rc.  No other context is touched by either.
+ * Returns the number of contexts whose call ended without an error and without a failed solve; 0 for n == 0.
+ * The first context owns the call's workspace (job table, histories, result records; device and pinned host memory, grown on
+ * demand, reused by later calls, freed by its sgo_destroy) and its stream carries the launch, which starts after every
+ * participant's pending work; the call returns after the launch has finished.  With sgo_opts.profile the first context's
+ * "direct" slot records each shared launch once, with the summed bytes.  sgo_many_workspace_bytes: the bytes that workspace holds
+ * now (device + pinned), 0 before the first call that needed it, < 0 for a NULL context.
+ * SGO_EINVAL, with nothing queued and no pose or output written: n < 0, max_iters outside [0, SGO_MAX_ITERS], a non-finite
+ * gain_tol, a NULL ctxs or res with n > 0, a NULL or duplicate context, contexts on different devices, a multi-GPU context
+ * (sgo_debug_set_shard's emulation included).  SGO_ENOGRAPH, likewise, if any context has no graph.  At most 65535 graphs share
+ * a launch; more take further launches.  The contexts must not be used from other threads during the call. */
+typedef struct sgo_many_result {
+  int32_t rc;           /* what sgo_optimize_gn_until would have returned */
+  int32_t stop_reason;  /* SGO_STOP_*; written when rc >= 0 */
+  int32_t in_launch;    /* 1: ran in the shared launch, 0: own route */
+} sgo_many_result;
+int sgo_optimize_gn_many(sgo_ctx* const* ctxs, int32_t n, int32_t max_iters, double gain_tol,
+                         sgo_stats* const* out /*[n], entries or the array may be NULL*/, sgo_many_result* res /*[n]*/,
+                         int32_t* launches /*may be NULL*/);
+int64_t sgo_many_workspace_bytes(sgo_ctx* ctx);
+
 /* Replaces: computeActiveErrors(); activeChi2(); activeRobustChi2() (slc.cpp:288, drone.cpp:162-165).
  * Called right after sgo_optimize_gn or sgo_optimize_gn_until it returns the final entries of that call's history bit for bit
  * (on a direct_ldlt context the sums come from the single-launch kernel's own closing pass). */

@@ -42,6 +42,7 @@ SYMBOLS = [
     "sgo_set_hypotheses_workspace", "sgo_hypotheses_bytes", "sgo_hypotheses_chunk", "sgo_hypotheses_workspace_bytes",
     "sgo_optimize_lm", "sgo_lm_trial_rule", "sgo_optimize_lm_pcg", "sgo_lm_pcg_trace",
     "sgo_optimize_dogleg", "sgo_optimize_dogleg_pcg", "sgo_dogleg_step_rule", "sgo_dogleg_trial_rule",
+    "sgo_optimize_gn_many", "sgo_many_workspace_bytes",
 ]
 
 # SGO_JOINT_MAX_*: the limits of sgo_candidate_joint's table and of a subset of it
@@ -242,6 +243,11 @@ class HypothesisResult(C.Structure):
     _fields_ = [("iters_done", C.c_int32), ("stop_reason", C.c_int32), ("chi2", C.c_double), ("robust_chi2", C.c_double)]
 
 
+class ManyResult(C.Structure):
+    """sgo_many_result: one context's part of sgo_optimize_gn_many."""
+    _fields_ = [("rc", C.c_int32), ("stop_reason", C.c_int32), ("in_launch", C.c_int32)]
+
+
 def hypothesis_isolated_vertex(fixed, ei, ej, info, off) -> int:
     """sgo_hypothesis_isolated_vertex: the lowest free vertex the mask `off` (E,) leaves without an incident edge of non-zero
     information, or -1 (no context, no GPU)."""
@@ -329,6 +335,9 @@ def lib():
     L.sgo_dogleg_trial_rule.argtypes = [C.c_double, C.c_double, C.c_double, C.c_double, d]
     L.sgo_lm_trial_rule.argtypes = [C.c_double, C.c_double, C.c_double, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.sgo_optimize_gn_hypotheses.argtypes = [vp, C.c_int32, C.c_int32, C.c_double, u8, d, C.POINTER(HypothesisResult), d, d, d]
+    L.sgo_optimize_gn_many.argtypes = [C.POINTER(vp), C.c_int32, C.c_int32, C.c_double, C.POINTER(C.POINTER(Stats)), C.POINTER(ManyResult), i32]
+    L.sgo_many_workspace_bytes.restype = C.c_int64
+    L.sgo_many_workspace_bytes.argtypes = [vp]
     L.sgo_hypothesis_isolated_vertex.restype = C.c_int32
     L.sgo_set_hypotheses_workspace.argtypes = [vp, C.c_int64]
     L.sgo_hypotheses_bytes.restype = C.c_int64
@@ -582,6 +591,29 @@ def comm_unique_id() -> bytes:
     return buf.raw
 
 
+def optimize_many(opts, max_iters: int = 20, gain_tol: float = 0.0):
+    """sgo_optimize_gn_many: every Optimizer of `opts` as its own optimize_until(max_iters, gain_tol), the direct_ldlt ones in one
+    shared launch with a workgroup per graph -> (list with, per context, the stats dict optimize_until returns plus stop_reason
+    and in_launch; launches: the shared launches the call made).  A context whose own call would have raised carries its error
+    code in rc; SgoError for a refusal of the whole call."""
+    opts = list(opts)
+    n = len(opts)
+    handles = (C.c_void_p * max(n, 1))(*[o._h for o in opts])
+    stats = [Stats() for _ in opts]
+    sp = (C.POINTER(Stats) * max(n, 1))(*[C.pointer(st) for st in stats])
+    res = (ManyResult * max(n, 1))()
+    launches = C.c_int32(-1)
+    rc = lib().sgo_optimize_gn_many(handles, n, max_iters, float(gain_tol), sp, res, C.byref(launches))
+    if rc < 0:
+        raise SgoError(f"sgo_optimize_gn_many: rc={rc}: " + lib().sgo_last_error(opts[0]._h if n else None).decode())
+    out = []
+    for o, st, r in zip(opts, stats, res):
+        d = o._stats_dict(r.rc, st, max_iters)
+        d.update(stop_reason=r.stop_reason, in_launch=r.in_launch)
+        out.append(d)
+    return out, launches.value
+
+
 class Optimizer:
     """One ``sgo_ctx``: the device-side stand-in for the reference's pose-graph
     ``g2o::SparseOptimizer`` (src/sparse_gslam/include/graphs.h:31-40)."""
@@ -793,6 +825,10 @@ class Optimizer:
     def hypotheses_workspace_bytes(self) -> int:
         """sgo_hypotheses_workspace_bytes: the device bytes the context's hypotheses workspace holds now."""
         return int(self._check(lib().sgo_hypotheses_workspace_bytes(self._h), "sgo_hypotheses_workspace_bytes"))
+
+    def many_workspace_bytes(self) -> int:
+        """sgo_many_workspace_bytes: the bytes (device + pinned host) of the optimize_many workspace this context holds now."""
+        return int(self._check(lib().sgo_many_workspace_bytes(self._h), "sgo_many_workspace_bytes"))
 
     def optimize_hypotheses(self, edge_off, max_iters: int = 20, gain_tol: float = 0.0, poses0=None,
                             want=("hist", "poses", "edge_chi2"), out=None):

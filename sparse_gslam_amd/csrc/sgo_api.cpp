@@ -398,6 +398,8 @@ void sgo_destroy(sgo_ctx* c) {
                   (void*)c->ejoint.d_out, (void*)c->ejoint.d_mask})
     if (p) hipFree(p);
   if (c->hyp.d_ws) hipFree(c->hyp.d_ws);
+  if (c->many.d_ws) hipFree(c->many.d_ws);
+  if (c->many.h_ws) hipHostFree(c->many.h_ws);
   if (c->stream) hipStreamDestroy(c->stream);
   delete c;
 }

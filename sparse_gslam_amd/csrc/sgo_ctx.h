@@ -265,6 +265,15 @@ struct sgo_ctx {
     int64_t mf_budget = 0;
   } hyp;
 
+  // sgo_optimize_gn_many (sgo_many.cpp), held by the FIRST context of a call: the job table, then every job's chi2 history and
+  // result record, each of the three contiguous -- on the device and, at the same offsets, in pinned host memory (one upload, two
+  // read-backs per call).  Grown on demand, kept across graphs and calls, freed by sgo_destroy.
+  struct Many {
+    char* d_ws = nullptr;
+    char* h_ws = nullptr;             // pinned
+    size_t d_cap = 0, h_cap = 0;
+  } many;
+
   // Device scratch of sgo_marginals (sgo_marginals.cpp): the result blocks [npairs][9], the pairs' internal rows and the pairs
   // ordered by column vertex; grown on demand, kept across graphs.
   struct Marginals {
@@ -588,6 +597,10 @@ struct UntilGain {
   int32_t stop_reason;
 };
 int optimize_gn(sgo_ctx* c, int32_t iters, sgo_stats* out, UntilGain* until = nullptr);   // sgo_optimize_gn behind its argument checks
+// The two ends of a call on a factorisation path that sgo_optimize_gn_many (sgo_many.cpp) shares with optimize_gn: sgo_stats before
+// the call, and everything the context and sgo_stats get from the finished call's history (c->h_hist) and result record (c->h_dres).
+void stats_begin(const sgo_ctx* c, int32_t iters, sgo_stats* out);
+int factored_epilogue(sgo_ctx* c, int32_t iters, sgo_stats* out, double t0, UntilGain* until);
 double debug_spmv0_us(sgo_ctx* c, int mode, int variant, int reps);
 
 }  // namespace sgo

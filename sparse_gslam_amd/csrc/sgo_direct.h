@@ -5,6 +5,7 @@
 // (a dense coarsest inverse, 8 launches per PCG iteration) dominate at this size.
 #pragma once
 #include <string>
+#include <vector>
 
 #include <hip/hip_runtime.h>
 
@@ -68,6 +69,35 @@ struct DirectBatchLayout {
 DirectBatchLayout direct_batch_layout(const Direct* d, int V, int B, int iters);
 hipError_t direct_optimize_batch(Direct* d, hipStream_t s, const EdgeListDev& el, const double* d_poses_res, bool own_poses,
                                  const DirectBatchLayout& L, char* ws, int iters, double gain_tol, bool want_edge_chi2);
+// sgo_optimize_gn_many on this path: n DIFFERENT graphs, one workgroup each, in one launch of the MANY instantiation of the same
+// kernel per group of graphs that share its compile-time flags (the vector in global memory or in LDS, kernel kinds or DCS alone:
+// at most four groups, one for the usual homogeneous call; a group of more than kDirectManyGrid graphs takes further launches).
+// Workgroup b reads everything -- plan, edge list, outputs, iters, gain_tol -- from record b of a job table in device memory.
+//   direct_many_table     fills the caller's host table [n][kDirectJobBytes] (pinned: the caller uploads it in ONE copy), the
+//                         records of a group next to each other, and lists the launches; item i writes to ITS d_hist
+//                         [2 (iters + 1)] and d_res whatever its place in the table.  Marks every item's Direct as run.
+//   direct_optimize_many  one of those launches, on the table's device copy (so that the caller can bracket each launch).
+// direct_joins_many: false for a Direct whose debug dump is on (SGO_DIRECT_DEBUG): it keeps its own launch.
+constexpr size_t kDirectJobBytes = 288;
+constexpr int kDirectManyGrid = 65535;
+struct DirectManyItem {
+  Direct* d;
+  const EdgeListDev* el;
+  double* d_poses;
+  double* d_hist;
+  DirectResult* d_res;
+};
+struct DirectManyTable {
+  struct Launch {
+    int group, first, count;   // xb_global | kinds << 1; records [first, first + count) of the table
+    size_t lds_bytes;          // the largest of its jobs
+    double bytes;              // algorithmic bytes, summed (profile table)
+  };
+  std::vector<Launch> launches;
+};
+bool direct_joins_many(const Direct* d);
+void direct_many_table(int n, const DirectManyItem* items, int iters, double gain_tol, char* h_jobs, DirectManyTable* T);
+hipError_t direct_optimize_many(hipStream_t s, const DirectManyTable::Launch& L, const char* d_jobs);
 // What a batched launch of either factorisation path (this one, sgo_mfront.h) needs before it starts, one launch of k_hyp_prepare:
 // hypothesis b's information rows at info_b + b info_stride ([6][E]: 0 where off[b][E] is set, info_res elsewhere) and, with
 // poses_res != nullptr (the caller gave no starting poses), its copy of the resident poses at poses_b + b poses_stride.

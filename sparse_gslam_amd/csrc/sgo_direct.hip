@@ -85,6 +85,21 @@ struct DirectBatch {
   int2* brief;              // [B] {updates applied, failure code}: what the host reads of a hypothesis' DirectResult
 };
 struct DirectSingle {};     // the dim3(1) instantiations take nothing
+// The MANY instantiations (sgo_optimize_gn_many): workgroup b optimises the graph of jobs[b] -- a plan, an edge list and outputs of
+// its own, everything the other instantiations take by value.  One record per workgroup in device memory; its address is uniform
+// over the workgroup, so the fields are scalar loads and live in SGPRs as the kernel arguments do.
+struct alignas(16) DirectJob {
+  DirectDev D;
+  EdgeListDev el;
+  double* poses;
+  double* hist;
+  DirectResult* res;
+  double gain_tol;
+  int iters;
+};
+struct DirectMany {
+  const DirectJob* jobs;    // [gridDim.x]
+};
 // The DUMP instantiations (a debug run, sgo_debug_direct_array): where the snapshots of an iteration's LDS-resident state go.
 struct DirectDump {
   double *a_wd, *a_wo, *a_sd, *a_xb;   // after the assembly barrier: Wd [nI][10], Wo [NB][10], the separator triangle [tri], xb [3 n]
@@ -328,12 +343,26 @@ constexpr int kPF = 1;   // forward tasks per thread whose records are fetched o
 // DUMP: a debug run (SGO_DIRECT_DEBUG at set-up; plain instantiations only): every iteration copies the state that otherwise lives
 // and dies in the LDS to DirectDump's arrays at four points, so that the last iteration that ran can be checked stage by stage
 // (tests/direct_reference.py).  Everything it adds is under `if constexpr (DUMP)`: the other instantiations compile as without it.
-template <bool XG, bool KINDS, bool UNTIL, bool BATCH = false, bool DUMP = false>
+// MANY: one workgroup per GRAPH (sgo_optimize_gn_many; always with UNTIL): workgroup b takes the plan, the edge list, the outputs,
+// iters and gain_tol from jobs[b] (DirectMany above) and ignores the seven by-value arguments.  The body is the single-graph one:
+// the LDS carve-up below comes from the plan's own sizes, so the launch carries the largest lds_bytes of its jobs.
+template <bool XG, bool KINDS, bool UNTIL, bool BATCH = false, bool DUMP = false, bool MANY = false>
 __global__ __launch_bounds__(kDT) void k_direct(DirectDev D, EdgeListDev el, double* __restrict__ poses, int iters,
                                                 double* __restrict__ hist, DirectResult* __restrict__ res, double gain_tol,
-                                                std::conditional_t<BATCH, DirectBatch, std::conditional_t<DUMP, DirectDump, DirectSingle>> bt) {
+                                                std::conditional_t<MANY, DirectMany, std::conditional_t<BATCH, DirectBatch, std::conditional_t<DUMP, DirectDump, DirectSingle>>> bt) {
   static_assert(!DUMP || (!UNTIL && !BATCH), "the snapshots exist for the plain instantiations only");
+  static_assert(!MANY || (UNTIL && !BATCH && !DUMP), "a job carries its own gain_tol, and neither hypothesis copies nor snapshots");
   extern __shared__ double lds[];
+  if constexpr (MANY) {
+    const DirectJob* __restrict__ J = bt.jobs + blockIdx.x;
+    D = J->D;
+    el = J->el;
+    poses = J->poses;
+    hist = J->hist;
+    res = J->res;
+    gain_tol = J->gain_tol;
+    iters = J->iters;
+  }
   if constexpr (BATCH) {
     const size_t b = blockIdx.x;
     D.Wd += b * bt.Wd;
@@ -1236,15 +1265,17 @@ Direct* direct_create(hipStream_t s, DevArena* arena, int V, int n, const int* f
   const bool attr_set_already = (attr_devices.load() & dev_bit) != 0;
   bool attr_set = attr_set_already;
   if (e == hipSuccess && !attr_set) {
-    const void* const variants[16] = {reinterpret_cast<const void*>(&k_direct<false, false, false>), reinterpret_cast<const void*>(&k_direct<true, false, false>),
+    const void* const variants[20] = {reinterpret_cast<const void*>(&k_direct<false, false, false>), reinterpret_cast<const void*>(&k_direct<true, false, false>),
                                      reinterpret_cast<const void*>(&k_direct<false, true, false>), reinterpret_cast<const void*>(&k_direct<true, true, false>),
                                      reinterpret_cast<const void*>(&k_direct<false, false, true>), reinterpret_cast<const void*>(&k_direct<true, false, true>),
                                      reinterpret_cast<const void*>(&k_direct<false, true, true>), reinterpret_cast<const void*>(&k_direct<true, true, true>),
                                      reinterpret_cast<const void*>(&k_direct<false, false, true, true>), reinterpret_cast<const void*>(&k_direct<true, false, true, true>),
                                      reinterpret_cast<const void*>(&k_direct<false, true, true, true>), reinterpret_cast<const void*>(&k_direct<true, true, true, true>),
                                      reinterpret_cast<const void*>(&k_direct<false, false, false, false, true>), reinterpret_cast<const void*>(&k_direct<true, false, false, false, true>),
-                                     reinterpret_cast<const void*>(&k_direct<false, true, false, false, true>), reinterpret_cast<const void*>(&k_direct<true, true, false, false, true>)};
-    for (int v = 0; v < 16 && e == hipSuccess; ++v)
+                                     reinterpret_cast<const void*>(&k_direct<false, true, false, false, true>), reinterpret_cast<const void*>(&k_direct<true, true, false, false, true>),
+                                     reinterpret_cast<const void*>(&k_direct<false, false, true, false, false, true>), reinterpret_cast<const void*>(&k_direct<true, false, true, false, false, true>),
+                                     reinterpret_cast<const void*>(&k_direct<false, true, true, false, false, true>), reinterpret_cast<const void*>(&k_direct<true, true, true, false, false, true>)};
+    for (int v = 0; v < 20 && e == hipSuccess; ++v)
       e = hipFuncSetAttribute(variants[v], hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBudget);
     attr_set = e == hipSuccess;
     if (attr_set) attr_devices.fetch_or(dev_bit);
@@ -1371,6 +1402,65 @@ hipError_t direct_optimize_batch(Direct* d, hipStream_t s, const EdgeListDev& el
   } else if (d->xb_global) SGO_DIRECT_BATCH(true, false);
   else SGO_DIRECT_BATCH(false, false);
 #undef SGO_DIRECT_BATCH
+  return hipGetLastError();
+}
+
+// ---- sgo_optimize_gn_many: many graphs, one workgroup each
+static_assert(sizeof(DirectJob) == kDirectJobBytes, "sgo_direct.h sizes the callers' job tables by this");
+
+bool direct_joins_many(const Direct* d) { return !d->debug; }
+
+void direct_many_table(int n, const DirectManyItem* items, int iters, double gain_tol, char* h_jobs, DirectManyTable* T) {
+  T->launches.clear();
+  DirectJob* jobs = reinterpret_cast<DirectJob*>(h_jobs);
+  int at = 0;
+  for (int g = 0; g < 4; ++g) {   // the group's number: xb_global | kinds << 1
+    int first = at;
+    size_t lds = 0;
+    double bytes = 0.0;
+    auto close = [&]() {
+      if (at > first) T->launches.push_back({g, first, at - first, lds, bytes});
+      first = at;
+      lds = 0;
+      bytes = 0.0;
+    };
+    for (int i = 0; i < n; ++i) {
+      const DirectManyItem& it = items[i];
+      if (((it.d->xb_global ? 1 : 0) | (it.el->kinds ? 2 : 0)) != g) continue;
+      DirectJob& J = jobs[at++];
+      J.D = it.d->dev;
+      J.el = *it.el;
+      J.poses = it.d_poses;
+      J.hist = it.d_hist;
+      J.res = it.d_res;
+      J.gain_tol = gain_tol;
+      J.iters = iters;
+      lds = std::max(lds, it.d->info.lds_bytes);
+      bytes += direct_bytes(it.d, it.el->E, iters);
+      if (iters > 0) {
+        it.d->ran = true;
+        it.d->dumped = false;
+      }
+      if (at - first == kDirectManyGrid) close();
+    }
+    close();
+  }
+}
+
+hipError_t direct_optimize_many(hipStream_t s, const DirectManyTable::Launch& L, const char* d_jobs) {
+  DirectMany bt;
+  bt.jobs = reinterpret_cast<const DirectJob*>(d_jobs) + L.first;
+  // (the by-value arguments: ignored by the MANY instantiations)
+#define SGO_DIRECT_MANY(XG, KINDS) \
+  SGO_LAUNCH((k_direct<XG, KINDS, true, false, false, true>), dim3((unsigned)L.count), dim3(kDT), L.lds_bytes, s, DirectDev{}, EdgeListDev{}, \
+             (double*)nullptr, 0, (double*)nullptr, (DirectResult*)nullptr, 0.0, bt)
+  switch (L.group) {
+    case 0: SGO_DIRECT_MANY(false, false); break;
+    case 1: SGO_DIRECT_MANY(true, false); break;
+    case 2: SGO_DIRECT_MANY(false, true); break;
+    default: SGO_DIRECT_MANY(true, true); break;
+  }
+#undef SGO_DIRECT_MANY
   return hipGetLastError();
 }
 

@@ -1013,6 +1013,14 @@ static void copy_history(const sgo_ctx* c, int done, sgo_stats* out) {
   }
 }
 
+// What every optimize call writes of sgo_stats before it starts.
+void stats_begin(const sgo_ctx* c, int32_t iters, sgo_stats* out) {
+  if (!out) return;
+  std::memset(out, 0, sizeof(*out));
+  out->iters_requested = iters;
+  out->seconds_setup = c->setup_seconds;
+}
+
 // Small-graph path: the whole call is one launch (sgo_direct.h); mid-size path: one launch per level of the elimination tree and
 // Gauss-Newton iteration, no host round trip inside the call (sgo_mfront.h).
 // until (sgo_optimize_gn_until): the gain rule is applied on the device, no host round trip inside the call either.
@@ -1034,6 +1042,13 @@ static int optimize_factored(sgo_ctx* c, int32_t iters, sgo_stats* out, double t
   HIP_TRY(c, hipMemcpyAsync(c->h_dres, c->d_dres, sizeof(DirectResult), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   prof_flush(c);
+  return factored_epilogue(c, iters, out, t0, until);
+}
+
+// What a finished call of a factorisation path leaves in its context, from the history in c->h_hist and the result record in
+// c->h_dres (optimize_factored above; sgo_optimize_gn_many's shared launch, which puts each graph's two there): the stop reason, the
+// error text of a failure, sgo_stats, the return value.
+int factored_epilogue(sgo_ctx* c, int32_t iters, sgo_stats* out, double t0, UntilGain* until) {
   c->linearized = false;
   const DirectResult& R = *c->h_dres;
   const int done = R.done;
@@ -1221,11 +1236,7 @@ int optimize_gn(sgo_ctx* c, int32_t iters, sgo_stats* out, UntilGain* until) {
     c->err = "sgo_optimize_gn: iters must be in [0, SGO_MAX_ITERS]";
     return SGO_EINVAL;
   }
-  if (out) {
-    std::memset(out, 0, sizeof(*out));
-    out->iters_requested = iters;
-    out->seconds_setup = c->setup_seconds;
-  }
+  stats_begin(c, iters, out);
   if (c->n == 0) return SGO_ENOTHING;
   const double t0 = wall_s();
   read_call_knobs(c);
